@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- traced rays/s for one MVSDF training step (forward + loss + backward + grad-norm/clip + Adam) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5share] [--dtype f32|f32x3|bf16|bf16w|bf16x2|bf16x3] [--width 256|512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5share] [--dtype f32|f32x3|bf16|bf16w|bf16x2|bf16x3] [--width 256|512] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process (which never touches the GPU) starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a child, relays
@@ -202,6 +202,45 @@ def cpu_baseline(V, rays_per_view=None, views=None):
             'reference': ref}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, lo, opt):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy -- the model's output dict (out_<key>), the loss dict (loss_<key>)
+    and what the optimiser step left behind: the flat parameters, both Adam moments and {||grad||, clip coefficient} (adam_*).  Floating tensors keep
+    float64 or become float32, masks and counts become float32 / float64.  Inputs, weights and draws are seeded, so two builds run with the same arguments
+    can be compared array by array.  Above DUMP_BYTES in all, the largest arrays are cut to a fixed seeded sample of their flat entries."""
+    arrs = {}
+    for k in sorted(out.keys()):
+        v = out[k]                                               # (a deferred step's output dict resolves its pending keys here)
+        if isinstance(v, torch.Tensor):
+            arrs['out_' + k] = v
+    for k in sorted(lo.keys()):
+        if isinstance(lo[k], torch.Tensor):
+            arrs['loss_' + k] = lo[k]
+    arrs.update(adam_params=opt.flat_p, adam_exp_avg=opt.flat_m, adam_exp_avg_sq=opt.flat_v, adam_grad_norm_and_clip_coef=opt.norm_and_coef)
+    host = {}
+    for k, v in arrs.items():
+        v = v.detach()
+        host[k] = v.to(torch.float64 if v.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for k in sorted(host, key=lambda k: -host[k].nbytes):
+        if total <= DUMP_BYTES:
+            break
+        a = host[k].reshape(-1)
+        keep = max(1, a.size + (DUMP_BYTES - total) // a.itemsize)
+        idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+        total -= a.nbytes - a[idx].nbytes
+        host[k] = a[idx]
+    if not os.path.isdir(path):                                  # a directory made here ignores itself: a dump inside the checkout leaves `git status` clean
+        os.makedirs(path)
+        with open(os.path.join(path, '.gitignore'), 'w') as f:
+            f.write('*\n')
+    for k, a in host.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return sorted(host)
+
+
 def self_launch(a):
     """--gpus N > 1 outside a launcher: start the N ranks as fresh child processes (this process has made no GPU call) and relay."""
     s = socket.socket()
@@ -278,7 +317,11 @@ def main():
                     '(zero_grad, forward, loss, backward, all-reduce, optimiser) -- a stand-in for a slow or contended host.  The deferred step absorbs it while the host stays faster than the GPU on '
                     'average; the classic step (MVSDF_DEFERRED_STEP=0) pays what lands behind its mid-step wait')
     ap.add_argument('--variants', action='store_true', help='also time the opt-in lazy_unused_outputs step (secondary number; off by default so that a profile of this command holds the headline step only)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps, write what the last of them computed (output dict, losses, parameters and '
+                    'Adam state after the update) as DIR/<name>.npy, float32 / float64, at most 64 MB; rank 0 writes its shard')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     global W
     W = a.width or WORKLOAD_WIDTH.get(a.workload, 256)
     a.width = W
@@ -419,6 +462,8 @@ def main():
                  'cpus_per_rank': cpus_pinned, 'wall_ms_per_step': [d_ / a.steps * 1e3 for d_ in dts],
                  'gpu_ms_per_step': [float(t_[2]) for t_ in allr], 'host_enqueue_ms_per_step': [float(t_[3]) for t_ in allr]}
         dt = max(dts)                                            # the MAX over the ranks is the job's time
+    if a.dump_outputs and rank == 0:                             # outside the timed region, before the extra steps below move the optimiser state
+        dump_outputs(a.dump_outputs, out, lo, opt)
 
     # (every rank runs these extra steps: step() holds the gradient collective)
     # per-kernel durations of the tracer: HIP events on the launch stream around k_sphere_trace, the sampler launches and the secant /

@@ -17,7 +17,8 @@ pytestmark = pytest.mark.gpu
 SEED, TP = 3, 0.3
 # (W, B, P, V): a small case, and the per-rank shape of BASELINE configs[3] (c4: 8x256 networks, ONE view of 2048 px per rank, 4 source
 # views, depth maps replicated) with the two ranks this box can hold instead of eight
-# 'c4x8' is BASELINE configs[3] itself: 8 views x 2048 px = 16384 rays, one view per rank, run as EIGHT ranks sharing the one GPU of the test box
+# 'c4x8' is BASELINE configs[3]'s batch itself: 8 views x 2048 px = 16384 rays, run as FOUR ranks (two views each) sharing the one GPU of the test box --
+# with the pytest process that is five processes holding the GPU; a shared GPU admits at most six at a time, eight ranks would make nine
 CFGS = {'small': (64, 2, 96, 2), 'c4': (256, 2, 2048, 4), 'c4x8': (256, 8, 2048, 4)}
 
 WORKER = r'''
@@ -67,9 +68,9 @@ def run_step(rank, world, cfg='small'):
     return opt.flat_g.detach().cpu().clone(), {k: float(v.detach()) for k, v in lo.items()}
 
 
-@pytest.mark.parametrize('cfg,world', [('small', 2), ('c4', 2), ('c4x8', 8)])
+@pytest.mark.parametrize('cfg,world', [('small', 2), ('c4', 2), ('c4x8', 4)])
 def test_ranks_reproduce_the_single_process_gradient(cfg, world):
-    """('c4x8', 8): the 8-rank run of BASELINE configs[3] -- every rank takes ONE 2048-px view of the 16384-ray batch, eight processes on the one
+    """('c4x8', 4): BASELINE configs[3]'s 16384-ray batch sharded over four ranks -- every rank takes two 2048-px views, four processes on the one
     GPU (gloo transport): the rank-averaged gradient equals the single-process gradient of the whole 16384-ray step."""
     ref, ref_losses = run_step(0, 1, cfg)                                            # whole batch, no process group
     with tempfile.TemporaryDirectory() as td:

@@ -189,7 +189,7 @@ def test_reference_fixtures_pass_with_the_fmaf_chain_tracer():
 
 def test_step_driver_lazy_outputs_options_and_data_parallel_suites_pass_with_the_fmaf_chain_tracer():
     """The suites that exercise the tracer through the rest of the product (native step driver vs the Python route, deferred outputs, constructor
-    options, eval rendering / mesh grid, 8 ranks on one GPU) once more with the fmaf-chain arithmetic 'f32' (the main suite runs them on 'f32x3')."""
+    options, eval rendering / mesh grid, four ranks on one GPU) once more with the fmaf-chain arithmetic 'f32' (the main suite runs them on 'f32x3')."""
     e = dict(os.environ, MVSDF_TEST_TRACE_DTYPE='f32')
     p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-m', 'gpu', '-p', 'no:cacheprovider', 'tests/test_gpu_shapes.py', 'tests/test_gpu_native_step.py',
                         'tests/test_gpu_lazy.py', 'tests/test_gpu_options.py', 'tests/test_gpu_dp.py'], cwd=ROOT, env=e,
