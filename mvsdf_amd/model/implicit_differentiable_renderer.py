@@ -382,6 +382,8 @@ class IDRNetwork(nn.Module):
         if prev is not None:
             prev._expire()
         self._lazy_prev = None
+        if self.training:
+            self._check_point_groups(train_progress)
         if self.training and self.native_step and not self.lazy_unused_outputs and self.ray_tracer.events is None and not ops._MINSDF_SIDE_STREAM:
             out = self._forward_native(input, train_progress, object_mask_true)
             if out is not None:
@@ -690,6 +692,16 @@ class IDRNetwork(nn.Module):
         res = (vs, gs, bs, params, [p for p in params if p is not None])
         self._param_cache = (lins, objs, res)
         return res
+
+    @staticmethod
+    def _check_point_groups(train_progress):
+        """The reference concatenates the selected point groups of each term with torch.cat and raises on an empty list (idr.py:258-286): so does
+        this, before anything is launched, instead of handing a zero-row term to the loss kernels."""
+        for term, flags in (('depth', ('d_use_rt_surf', 'd_use_eik', 'd_use_dsurf_on', 'd_use_dsurf_jitter')),
+                            ('eikonal', ('eik_use_rt_surf', 'eik_use_eik', 'eik_use_dsurf_on', 'eik_use_dsurf_jitter'))):
+            if not any(getattr(conf, f)(train_progress) for f in flags):
+                raise ValueError('IDRNetwork.forward: every point group of the %s term is switched off at train_progress %g (conf.%s): '
+                                 'the reference fails here (torch.cat of an empty list, idr.py:258-286)' % (term, train_progress, ' / '.join(flags)))
 
     def _group_masks(self, train_progress, n_eik, n_ds):
         """Point groups in the reference's row order [hit | eikonal | on-surface | jittered] (idr.py:253-257): bit g selects group g for the

@@ -159,7 +159,7 @@ class NativeStep:
         self.Nout = desc.N[desc.n_sdf - 1]
         self.nl = desc.n_sdf + desc.n_render
         self._bwd = None
-        self._prm_key, self._prm, self._prm_list = None, None, None
+        self._prm_key, self._prm, self._prm_list, self._prm_src = None, None, None, None
         self._grad_key, self._grad_arrays = None, None
         self._counts = (C.c_longlong * 4)()
         self._counts_peek = (C.c_longlong * 4)()
@@ -177,10 +177,18 @@ class NativeStep:
                 pass
 
     # ---- parameters
-    def params(self, vs, gs, bs):
-        """ctypes struct of the raw parameter pointers, rebuilt only when a storage moved."""
-        if self._prm_list is None or len(self._prm_list) != len(vs) + len(bs) + sum(1 for g in gs if g is not None):
+    def _track(self, vs, gs, bs):
+        """The parameter list the cached pointer structs describe, rebuilt (and both caches dropped) when the caller hands over other list objects:
+        IDRNetwork._step_params builds new lists whenever a Parameter object was re-assigned, and the storages of the old objects still exist."""
+        src = self._prm_src
+        if src is None or src[0] is not vs or src[1] is not gs or src[2] is not bs:
+            self._prm_src = (vs, gs, bs)
             self._prm_list = list(vs) + [g for g in gs if g is not None] + list(bs)
+            self._prm_key = self._grad_key = None
+
+    def params(self, vs, gs, bs):
+        """ctypes struct of the raw parameter pointers, rebuilt only when a storage moved or other Parameter objects are passed."""
+        self._track(vs, gs, bs)
         key = tuple(map(_DATA_PTR, self._prm_list))               # (a storage that moved -- .to(), FlatAdam taking the parameters over -- shows here)
         if key != self._prm_key:
             for p in list(vs) + [g for g in gs if g is not None] + list(bs):
@@ -193,7 +201,8 @@ class NativeStep:
 
     def grad_arrays(self, vs, gs, bs):
         """Pointer arrays of the parameters' .grad buffers (the gradient sink), or None when one is missing / not a plain fp32 buffer."""
-        ps = self._prm_list if self._prm_list is not None else list(vs) + [g for g in gs if g is not None] + list(bs)
+        self._track(vs, gs, bs)
+        ps = self._prm_list
         grads = [p.grad for p in ps]
         for g_ in grads:                                          # (not `None in grads`: `in` compares with ==, i.e. 42 tensor comparisons)
             if g_ is None:

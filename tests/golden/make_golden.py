@@ -303,10 +303,55 @@ def g_sample_network(seed):
 SCENE = dict(size=2.6, center=(0.1, -0.2, 0.3), feat_hw=(60, 80), focal_scale=1.4)
 
 
-def g_idr(W, B, P, V, seed, tp, name=None, skip_in=(4,), smooth=None, use_invalid=False, use_mask=False, enable_rgb=True):
+@contextlib.contextmanager
+def ref_conf(overrides):
+    """Set `overrides` {name: value} on the reference's conf module (model.conf, the module idr.py and loss.py share) and restore every one afterwards.
+    A schedule switch (a callable of train_progress, conf.py:5-33) becomes a constant lambda."""
+    import model.loss as ref_loss
+    c = ref_loss.conf
+    old = {k: getattr(c, k) for k in overrides}
+    for k, v in overrides.items():
+        setattr(c, k, (lambda tp_, v=v: v) if callable(old[k]) else v)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            setattr(c, k, v)
+
+
+def conf_keys(overrides):
+    """-> {'conf_<name>': value}: how a fixture records its conf overrides (tests/test_gpu_idr.py applies them from these keys)."""
+    return {'conf_' + k: np.asarray(v) for k, v in overrides.items()}
+
+
+class PointsAllRecorder:
+    """forward_pre_hook on the reference's implicit_network: keeps the input of its one call with 3 R / 2 rows, points_all[N:] of idr.py:253-256
+    ordered [eikonal | on-surface | jittered] -- the depth-surface samples the reference drew, also when some groups are left out of
+    eikonal_points_hom (tp >= 1/6 with a dsurf switch on)."""
+
+    def __init__(self, net, R):
+        self.rows, self.x = 3 * R // 2, []
+        self.h = net.register_forward_pre_hook(lambda mod, a: self.x.append(a[0].detach().clone()) if a[0].shape[0] == self.rows else None)
+
+    def samples(self):
+        self.h.remove()
+        assert len(self.x) == 1, len(self.x)
+        x, n = self.x[0].numpy(), self.rows // 3
+        return x[n:2 * n].copy(), x[2 * n:].copy()
+
+
+def g_idr(W, B, P, V, seed, tp, name=None, skip_in=(4,), smooth=None, use_invalid=False, use_mask=False, enable_rgb=True, conf=None, dsurf=False):
     """smooth: conf.smooth(tp) of the depth term (loss.py:57-58: SmoothL1 instead of L1; None in the shipped conf) -- set on the reference's conf module for this fixture.
     use_mask: conf.use_mask = True (idr.py:186: the tracer and the rgb term see input['object_mask']) with a random 70 % object mask (stored in the fixture).
-    enable_rgb=False: conf.enable_rgb off (loss.py:184-187: rgb_loss = zeros(1))."""
+    enable_rgb=False: conf.enable_rgb off (loss.py:184-187: rgb_loss = zeros(1)).
+    conf: {name: value} set on the reference's conf module for this fixture (ref_conf), recorded as conf_<name>.
+    dsurf: a depth-surface switch is on at this tp: depth maps with 5 % holes, np.random.seed(seed + 6) for np.random.choice (idr.py:244), the samples
+    the reference drew stored as dsurf_on / dsurf_jitter, the outputs stored as copies taken before the loss (which rescales eikonal_points_hom in place)."""
+    with ref_conf(conf or {}):
+        _g_idr(W, B, P, V, seed, tp, name, skip_in, smooth, use_invalid, use_mask, enable_rgb, conf or {}, dsurf)
+
+
+def _g_idr(W, B, P, V, seed, tp, name, skip_in, smooth, use_invalid, use_mask, enable_rgb, conf, dsurf):
     import model.loss as ref_loss
     old_smooth, old_ui = ref_loss.conf.smooth, ref_loss.conf.use_invalid
     old_um, old_er = ref_loss.conf.use_mask, ref_loss.conf.enable_rgb
@@ -320,8 +365,13 @@ def g_idr(W, B, P, V, seed, tp, name=None, skip_in=(4,), smooth=None, use_invali
         inp['depths'] = gt['depths'] = synth.make_depth_maps(inp['depth_cams'], SCENE['size'], SCENE['center'], seed=seed, hole_frac=0.3)
     if use_mask:
         inp['object_mask'] = np.random.RandomState(seed + 17).uniform(size=inp['object_mask'].shape) < 0.7
+    if dsurf:
+        inp['depths'] = gt['depths'] = synth.make_depth_maps(inp['depth_cams'], SCENE['size'], SCENE['center'], seed=seed, hole_frac=0.05)
     m.train()
     torch.manual_seed(seed + 5)
+    if dsurf:
+        np.random.seed(seed + 6)
+        pts_rec = PointsAllRecorder(m.implicit_network, B * P)
     mi = {k: T(v) for k, v in inp.items()}
     with torch.no_grad():
         dirs, cam_loc = rend_util.get_camera_params(mi['uv'], mi['pose'], mi['intrinsics'])
@@ -332,7 +382,9 @@ def g_idr(W, B, P, V, seed, tp, name=None, skip_in=(4,), smooth=None, use_invali
         out = m(mi, tp)
     res = dict(rec.arrays())
     for k, v in out.items():
-        res['out_' + k] = v.detach().numpy()
+        res['out_' + k] = v.detach().numpy().copy() if dsurf else v.detach().numpy()
+    if dsurf:
+        res['dsurf_on'], res['dsurf_jitter'] = pts_rec.samples()
     # loss + gradients
     loss_fn = IDRLoss()
     gtt = {k: T(v) for k, v in gt.items()}
@@ -365,6 +417,7 @@ def g_idr(W, B, P, V, seed, tp, name=None, skip_in=(4,), smooth=None, use_invali
         res['depth_hole_frac'] = np.float32(0.3)
     if smooth is not None:
         res['smooth'] = np.float32(smooth)
+    res.update(conf_keys(conf))
     # the eikonal points drawn inside forward (torch CPU generator), for implementations that take them as input
     save(name or 'idr_w%d_tp%s' % (W, str(tp).replace('.', '')), W=W, B=B, P=P, V=V, seed=seed, tp=tp,
          scene_size=SCENE['size'], scene_center=np.array(SCENE['center']), feat_hw=np.array(SCENE['feat_hw']),
@@ -378,6 +431,22 @@ IDR_FIXTURES = {   # name: (W, B, P, V, seed, tp, skip_in) of the g_idr fixtures
     'idr_w64_skip8': (64, 2, 256, 3, 0, 0.3, (8,)), 'idr_w64_smooth': (64, 2, 256, 3, 0, 0.3, (4,)), 'idr_w64_invalid': (64, 2, 256, 3, 0, 0.3, (4,)),
     'idr_w64_usemask': (64, 2, 256, 3, 0, 0.3, (4,)), 'idr_w64_norgb': (64, 2, 256, 3, 0, 0.3, (4,)),
 }
+
+# g_idr fixtures of conf switches that change the kernel route (model/conf.py:5-33): name -> (W, B, P, V, conf overrides, dsurf); seed 0, tp 0.3
+_DSURF = {'d_use_dsurf_on': True, 'eik_use_dsurf_jitter': True, 'd_use_eik': False}     # depth-surface groups at tp >= 1/6: masks 0b0101 / 0b1011
+IDR_CONF_FIXTURES = {
+    'idr_w64_norgbgrad': (64, 2, 256, 3, {'disable_rgb_grad': True}, False),            # use_geo = 0 with the feature loss on (idr.py:331-334)
+    'idr_w64_nofeat': (64, 2, 256, 3, {'enable_feat': False}, False),                    # the loss without the feature term
+    'idr_w64_groups_a': (64, 2, 256, 3, {'d_use_eik': False, 'eik_use_rt_surf': False}, False),      # d_mask 0b0001 (device-counted rows only), e_mask 0b0010
+    'idr_w64_groups_b': (64, 2, 256, 3, {'d_use_rt_surf': False, 'eik_use_eik': False}, False),      # d_mask 0b0010, e_mask 0b0001
+    'idr_w64_groups_dsurf': (64, 2, 256, 3, _DSURF, True),
+    'idr_w256_groups_dsurf': (256, 2, 128, 2, _DSURF, True),
+}
+
+
+def g_idr_conf(name):
+    W, B, P, V, overrides, dsurf = IDR_CONF_FIXTURES[name]
+    g_idr(W, B, P, V, 0, 0.3, name, conf=overrides, dsurf=dsurf)
 
 
 def g_idr_eval(W, B, P, seed, render=0, name=None):
@@ -396,6 +465,9 @@ def g_idr_eval(W, B, P, seed, render=0, name=None):
          checksum=synth.state_checksum(sd), out_keys=np.array(sorted(out.keys())), **res)
 
 
+_MARGINS_LATER = ('idr_w64_usemask', 'idr_w64_norgb')         # not in the recorded margins (usemask's hits depend on its object mask, which this loop does not apply)
+
+
 def g_idr_relu_margins():
     """Decision margins of the RENDERING network's ReLUs in the reference forward of every g_idr fixture: min |pre-activation| per hidden layer over the
     hit rows (idr.py:160-165).  A pre-activation within the forward noise of zero (1e-6 .. 1e-5: the features and normals it is computed from agree with the
@@ -403,18 +475,23 @@ def g_idr_relu_margins():
     flips, which moves the entries of the (small) rendering-network gradients of that layer and the layers below it by up to ~1e-2 of their scale -- a tie, like
     the tracer's recorded margins.  tests/test_gpu_idr.py widens the sampled-entry tolerance of exactly those layers when a margin is below 1e-5."""
     res = {}
-    for name, (W, B, P, V, seed, tp, skip_in) in IDR_FIXTURES.items():
+    fixtures = [(name, f, {}, False) for name, f in IDR_FIXTURES.items() if name not in _MARGINS_LATER]
+    fixtures += [(name, (W, B, P, V, 0, 0.3, (4,)), ov, ds) for name, (W, B, P, V, ov, ds) in IDR_CONF_FIXTURES.items()]
+    for name, (W, B, P, V, seed, tp, skip_in), ov, ds in fixtures:
         m, sd = build_model(W, seed, skip_in=skip_in)
         inp, gt = synth.make_batch(B, P, V, seed=seed, **SCENE)
+        if ds:
+            inp['depths'] = synth.make_depth_maps(inp['depth_cams'], SCENE['size'], SCENE['center'], seed=seed, hole_frac=0.05)
         m.train()
         torch.manual_seed(seed + 5)
+        np.random.seed(seed + 6)                                 # (np.random.choice of the depth-surface samples, idr.py:244; not what the margins read)
         rn = m.rendering_network
         mins = {}
         hooks = []
         for l in range(rn.num_layers - 2):                       # the Linears followed by a ReLU
             hooks.append(getattr(rn, 'lin%d' % l).register_forward_hook(
                 lambda mod, i, o, l=l: mins.__setitem__(l, min(mins.get(l, np.inf), float(o.detach().abs().min())))))
-        with quiet():
+        with quiet(), ref_conf(ov):
             m({k: T(v) for k, v in inp.items()}, tp)
         for h in hooks:
             h.remove()
@@ -617,15 +694,40 @@ def g_dsurf(seed):
          pts_norm=pts_all.numpy(), valid=valid.numpy(), inbound=inbound.numpy())
 
 
-# fixtures `--check NAME ...` can regenerate, and the call that writes each
+# every committed fixture and the call that writes it (`--check NAME ...` regenerates from here; tests/test_golden_registry.py: no fixture without an entry).
+# A call that writes several fixtures appears under each of their names.
 RECIPES = {
+    'dsurf_unproject': lambda: g_dsurf(0),
+    'train4_w64': lambda: g_train(64, 2, 256, 3, 0, 0.3, 4, 1e-3),
+    'sdf_w64': lambda: g_sdf(64, 1000, 0), 'sdf_w256': lambda: g_sdf(256, 256, 0), 'sdf_w512': lambda: g_sdf(512, 256, 0),
+    'render_w64': lambda: g_render(64, 300, 0), 'rays': lambda: g_rays(0), 'sample_network': lambda: g_sample_network(0),
+    'trace_analytic_eval_ones': lambda: g_trace_analytic(0), 'trace_analytic_eval_rand': lambda: g_trace_analytic(0),
+    'trace_analytic_train_ones': lambda: g_trace_analytic(0), 'trace_analytic_train_rand': lambda: g_trace_analytic(0),
+    'trace_mlp_w64_eval': lambda: g_trace_mlp(64, 4, 1024, 0), 'trace_mlp_w64_train': lambda: g_trace_mlp(64, 4, 1024, 0),
+    'trace_mlp_w256_eval': lambda: g_trace_mlp(256, 2, 512, 0), 'trace_mlp_w256_train': lambda: g_trace_mlp(256, 2, 512, 0),
+    'trace_mlp_w512_eval': lambda: g_trace_mlp(512, 2, 512, 0), 'trace_mlp_w512_train': lambda: g_trace_mlp(512, 2, 512, 0),
+    'trace_mlp_w64_eval_render': lambda: g_trace_mlp(64, 4, 1024, 0, 1), 'trace_mlp_w64_train_render': lambda: g_trace_mlp(64, 4, 1024, 0, 1),
+    'trace_mlp_w256_eval_render': lambda: g_trace_mlp(256, 2, 512, 0, 1), 'trace_mlp_w256_train_render': lambda: g_trace_mlp(256, 2, 512, 0, 1),
+    'feat_corr': lambda: g_feat(0), 'feat_corr_v4': lambda: g_feat(0, 8, 200, 4, 'feat_corr_v4'), 'feat_corr_v8': lambda: g_feat(0, 8, 160, 8, 'feat_corr_v8'),
+    'carve': lambda: g_carve(0), 'carve_invalid': lambda: g_carve(0, True, 'carve_invalid'),
+    'sdf_bwd_w64': lambda: g_sdf_bwd(64, 150, 0), 'sdf_bwd_w64_skips36': lambda: g_sdf_bwd(64, 150, 0, (3, 6), 'sdf_bwd_w64_skips36'),
+    'sdf_bwd_w64_skip8': lambda: g_sdf_bwd(64, 150, 0, (8,), 'sdf_bwd_w64_skip8'), 'sdf_bwd_w64_skips48': lambda: g_sdf_bwd(64, 150, 0, (4, 8), 'sdf_bwd_w64_skips48'),
+    'render_bwd_w64': lambda: g_render_bwd(64, 150, 0),
     'idr_w64_tp03': lambda: g_idr(64, 2, 256, 3, 0, 0.3), 'idr_w64_tp06': lambda: g_idr(64, 2, 256, 3, 0, 0.6), 'idr_w256_tp03': lambda: g_idr(256, 2, 128, 2, 0, 0.3),
-    'sdf_w64': lambda: g_sdf(64, 1000, 0), 'render_w64': lambda: g_render(64, 300, 0), 'rays': lambda: g_rays(0), 'sample_network': lambda: g_sample_network(0),
-    'feat_corr': lambda: g_feat(0), 'carve': lambda: g_carve(0), 'sdf_bwd_w64': lambda: g_sdf_bwd(64, 150, 0), 'render_bwd_w64': lambda: g_render_bwd(64, 150, 0),
+    'idr_w64_phase0': lambda: g_idr_phase0(64, 3, 128, 2, 0, 0.1),
+    'idr_c1': lambda: g_idr(256, 1, 512, 4, 0, 0.3, 'idr_c1'), 'idr_c2': lambda: g_idr(256, 8, 256, 4, 0, 0.3, 'idr_c2'),
+    'idr_c3': lambda: g_idr(256, 8, 1024, 8, 0, 0.3, 'idr_c3'), 'idr_c5share': lambda: g_idr(256, 8, 512, 8, 0, 0.3, 'idr_c5share'),
+    'idr_w512': lambda: g_idr(512, 8, 128, 2, 0, 0.3, 'idr_w512'),
+    'idr_w64_skips36': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_skips36', (3, 6)), 'idr_w64_skip8': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_skip8', (8,)),
+    'idr_w64_smooth': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_smooth', (4,), 0.05),
+    'idr_w64_invalid': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_invalid', (4,), None, True),
     'idr_w64_usemask': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_usemask', (4,), None, False, True),
     'idr_w64_norgb': lambda: g_idr(64, 2, 256, 3, 0, 0.3, 'idr_w64_norgb', (4,), None, False, False, False),
+    'idr_w64_norgbgrad': lambda: g_idr_conf('idr_w64_norgbgrad'), 'idr_w64_nofeat': lambda: g_idr_conf('idr_w64_nofeat'),
+    'idr_w64_groups_a': lambda: g_idr_conf('idr_w64_groups_a'), 'idr_w64_groups_b': lambda: g_idr_conf('idr_w64_groups_b'),
+    'idr_w64_groups_dsurf': lambda: g_idr_conf('idr_w64_groups_dsurf'), 'idr_w256_groups_dsurf': lambda: g_idr_conf('idr_w256_groups_dsurf'),
     'idr_eval_w64': lambda: g_idr_eval(64, 2, 300, 0), 'idr_eval_w64_render': lambda: g_idr_eval(64, 2, 300, 0, 1), 'idr_eval_w256': lambda: g_idr_eval(256, 2, 200, 0),
-    'dsurf_unproject': lambda: g_dsurf(0),
+    'idr_relu_margins': lambda: g_idr_relu_margins(),
 }
 
 
@@ -709,4 +811,6 @@ if __name__ == '__main__':
     g_idr_eval(64, 2, 300, 0)
     g_idr_eval(64, 2, 300, 0, 1)
     g_idr_eval(256, 2, 200, 0)
+    for name in IDR_CONF_FIXTURES:                                              # conf switches that change the kernel route (model/conf.py:5-33)
+        g_idr_conf(name)
     g_idr_relu_margins()

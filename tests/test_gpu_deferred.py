@@ -293,3 +293,49 @@ def test_forward_blocks_die_by_reference_count(route):
     block = m._last_step.layout.fwd_bytes
     # (the model keeps its last record and the loss its last workspace: the figure moves by less than a block between two steps, it must not grow by one per step)
     assert block > 4 << 20 and grown < block, '%d bytes more allocated after eight more steps with the collector off (a forward block: %d)' % (grown, block)
+
+
+@pytest.mark.parametrize('deferred', [True, False])
+def test_reassigned_parameter_objects_are_used(deferred):
+    """A Parameter OBJECT replaced between two steps (`lin0.weight_v = nn.Parameter(...)`): the next step runs on the new objects -- outputs, loss
+    terms and every .grad equal those of a model that holds the same values in its original objects, bit for bit -- and the replaced objects' .grad
+    stays as the first step left it (NativeStep.params / grad_arrays follow the objects, not only the storages of the ones they saw first)."""
+    B, P, V, tp = 2, 300, 2, 0.3
+    inp, gt = _batch(B, P, V)
+
+    def step(m, seed):
+        torch.manual_seed(seed)
+        out = m(inp, tp)
+        lo = IDRLoss()(out, dict(gt), tp, B)
+        m.zero_grad()
+        lo['loss'].backward()
+        torch.cuda.synchronize()
+        return ({k: v.detach().clone() for k, v in out.items() if torch.is_tensor(v)}, {k: v.detach().clone() for k, v in lo.items()},
+                {k: p.grad.detach().clone() for k, p in m.named_parameters()})
+
+    a, b = _model(64, deferred), _model(64, deferred)
+    step(a, 11)
+    step(b, 11)
+    gen = torch.Generator().manual_seed(5)
+    old_v, old_b = a.implicit_network.lin0.weight_v, a.rendering_network.lin1.bias
+    new_v = (old_v.detach().cpu() * (1 + 0.2 * torch.randn(old_v.shape, generator=gen))).cuda()
+    new_b = (old_b.detach().cpu() + 0.2 * torch.randn(old_b.shape, generator=gen)).cuda()
+    old_grads = [old_v.grad.clone(), old_b.grad.clone()]
+    a.implicit_network.lin0.weight_v = torch.nn.Parameter(new_v.clone())
+    a.rendering_network.lin1.bias = torch.nn.Parameter(new_b.clone())
+    with torch.no_grad():                                         # model B: the same values in its original Parameter objects
+        b.implicit_network.lin0.weight_v.copy_(new_v)
+        b.rendering_network.lin1.bias.copy_(new_b)
+    o_a, l_a, g_a = step(a, 12)
+    o_b, l_b, g_b = step(b, 12)
+    assert int(o_b['network_object_mask'].sum()) > 0
+    for k in l_b:
+        _same(l_a[k], l_b[k], k)
+    assert set(o_a) == set(o_b)
+    for k in o_b:
+        _same(o_a[k], o_b[k], k)
+    assert list(g_a) == list(g_b)
+    for k in g_b:
+        _same(g_a[k], g_b[k], 'grad of ' + k)
+    _same(old_v.grad, old_grads[0], 'grad of the replaced weight_v')
+    _same(old_b.grad, old_grads[1], 'grad of the replaced bias')

@@ -39,7 +39,8 @@ SKIPS = {'idr_w64_skips36': (3, 6), 'idr_w64_skip8': (8,)}                      
 
 @pytest.mark.parametrize('order', ['outputs_first', 'loss_first'])
 @pytest.mark.parametrize('name', ['idr_w64_tp03', 'idr_w64_tp06', 'idr_w256_tp03', 'idr_c1', 'idr_c2', 'idr_c3', 'idr_c5share', 'idr_w512', 'idr_w64_phase0', 'idr_w64_skips36', 'idr_w64_skip8', 'idr_w64_smooth', 'idr_w64_invalid',
-                                  'idr_w64_usemask', 'idr_w64_norgb'])
+                                  'idr_w64_usemask', 'idr_w64_norgb', 'idr_w64_norgbgrad', 'idr_w64_nofeat', 'idr_w64_groups_a', 'idr_w64_groups_b',
+                                  'idr_w64_groups_dsurf', 'idr_w256_groups_dsurf'])
 def test_forward_loss_backward_vs_reference(name, order, monkeypatch):
     """idr_c1 = BASELINE configs[0] at its own shape (B = 1 view x 512 rays, V = 4, 8x256 networks); idr_w512 = the reference's SHIPPED
     configuration (8x512 SDF net, 4x512 rendering net, confs/mvsdf_dtu.conf:24,35; num_src = 2, scene_dataset.py:104) on 8 views x 128 px;
@@ -48,6 +49,9 @@ def test_forward_loss_backward_vs_reference(name, order, monkeypatch):
     (the SmoothL1 depth term of loss.py:57-58, off in the shipped conf, reachable through IDR_CONF); idr_w64_invalid = conf.use_invalid (carving_t, loss.py:43-44) on
     depth maps with 30 % holes; idr_w64_skip8 = skip_in (8,): a skip connection into the LAST Linear (idr.py:46-49,86); idr_w64_usemask = conf.use_mask = True
     (idr.py:186: tracer, partition and rgb term see a random 70 % object mask); idr_w64_norgb = conf.enable_rgb = False (loss.py:184-187).
+    Fixtures with conf_<name> keys were recorded with that conf switch set on the reference (make_golden.py::IDR_CONF_FIXTURES, tp = 0.3): idr_w64_norgbgrad =
+    disable_rgb_grad (use_geo = 0 with the feature loss on), idr_w64_nofeat = enable_feat off, idr_w64_groups_a / _b = depth / eikonal point-group masks
+    0b0001 / 0b0010 and 0b0010 / 0b0001, idr_w64_groups_dsurf / idr_w256_groups_dsurf = depth-surface groups at tp >= 1/6 (masks 0b0101 / 0b1011, geometry attached).
     order: 'outputs_first' reads the output dict before IDRLoss (the step resolves: one wait for the hit counts, the classic loss node); 'loss_first' runs
     IDRLoss + backward on the PENDING dict first (the deferred step: counts on the device, no wait) and compares the outputs afterwards -- the same checks."""
     g = golden(name)
@@ -62,6 +66,10 @@ def test_forward_loss_backward_vs_reference(name, order, monkeypatch):
     if 'use_invalid' in g.files:                                                  # conf.use_invalid: carving_t, on depth maps with holes (where it differs from carving_t2)
         from mvsdf_amd.model import loss as loss_mod
         monkeypatch.setattr(loss_mod.conf, 'use_invalid', True)
+    for k in g.files:                                                             # conf_<name>: a switch of the reference's conf set for this fixture
+        if k.startswith('conf_'):
+            v = g[k].item()
+            monkeypatch.setattr(loss_mod.conf, k[5:], (lambda tp_, v=v: v) if callable(getattr(loss_mod.conf, k[5:])) else v)
     W, B, P, V, seed, tp = int(g['W']), int(g['B']), int(g['P']), int(g['V']), int(g['seed']), float(g['tp'])
     model, sd = build(W, seed, SKIPS.get(name, (4,)))
     np.testing.assert_allclose(synth.state_checksum(sd), g['checksum'], rtol=0, atol=0)
@@ -119,7 +127,9 @@ def test_forward_loss_backward_vs_reference(name, order, monkeypatch):
     N = int(hit.sum())
     gth, gth_g = out['grad_theta'].detach().cpu().numpy(), g['out_grad_theta']
     assert np.abs(gth - gth_g).max() < 2e-3 * max(1.0, np.abs(gth_g).max())      # surface rows move with the 1e-5 depth noise
-    assert np.abs(gth[N:] - gth_g[N:]).max() < 1e-4 * max(1.0, np.abs(gth_g).max())   # eikonal samples: identical points
+    n_s = N if loss_mod.conf.eik_use_rt_surf(tp) else 0                         # grad_theta rows: [hit rows if selected | sample groups] (idr.py:278-286)
+    if gth.shape[0] > n_s:
+        assert np.abs(gth[n_s:] - gth_g[n_s:]).max() < 1e-4 * max(1.0, np.abs(gth_g).max())   # eikonal samples: identical points
     # |d sdf| = |grad f| * |d depth| with |grad f| ~ 1: the depth tolerance (1e-4 rel of depths <= 3.5, measured <= 1e-4 abs) carries over
     assert np.abs(out['sdf_output'].detach().cpu().numpy()[hit] - g['out_sdf_output'][hit]).max() < 1e-4
     assert np.abs(out['eikonal_output'].detach().cpu().numpy() - g['out_eikonal_output']).max() < 5e-5
@@ -162,6 +172,29 @@ def test_forward_loss_backward_vs_reference(name, order, monkeypatch):
         worst = max(worst, float(np.abs(vals - expect).max() / scale))
     print('%s: worst sampled gradient entry deviation %.3g of the scale%s' % (name, worst, ' (after the exact correction for %d flipped ReLU unit(s))' % corr['_n_flips'] if corr else ''))
     assert worst < 1e-3, worst                                                    # measured: <= 1.2e-4 (idr_c3), <= 2.1e-5 on the other fixtures
+
+
+OFF = lambda tp_: False
+
+
+@pytest.mark.parametrize('route', ['deferred', 'classic', 'python'])
+@pytest.mark.parametrize('term,tp', [('depth', 0.3), ('eikonal', 0.3), ('depth', 0.1)])
+def test_term_without_point_group_raises(term, tp, route, monkeypatch):
+    """Every point group of the depth term (d_use_*) or of the eikonal term (eik_use_*) switched off: the reference fails on torch.cat of an empty list
+    (idr.py:258-286).  IDRNetwork.forward raises a ValueError naming the term before anything is launched -- no zero-row term reaches the loss kernels;
+    tp = 0.1 is phase 0, where the depth-surface groups exist."""
+    from mvsdf_amd.model import loss as loss_mod
+    prefix = 'd_use_' if term == 'depth' else 'eik_use_'
+    for grp in ('rt_surf', 'eik', 'dsurf_on', 'dsurf_jitter'):
+        monkeypatch.setattr(loss_mod.conf, prefix + grp, OFF)
+    model, _ = build(64, 0)
+    model.train()
+    model.deferred_step = route == 'deferred'
+    model.native_step = route != 'python'
+    inp, _ = synth.make_batch(2, 64, 2, seed=0, feat_hw=(60, 80), focal_scale=1.4)
+    with pytest.raises(ValueError, match='%s term' % term):
+        model({k: t(v) for k, v in inp.items()}, tp)
+    assert model._steps == {} and '_last_rec' not in model.__dict__                   # nothing was set up or enqueued
 
 
 def _relu_flip_correction(model, sd, out, gt, tp, B):
