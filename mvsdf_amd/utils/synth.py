@@ -231,3 +231,82 @@ def make_depth_maps(depth_cams, size, center, seed=0, radius=0.6, hole_frac=0.15
         tz[rs.uniform(size=tz.shape) < hole_frac] = 0.0                       # holes
         out[b, 0, 0] = np.where(hit, tz, 0.0)
     return out
+
+
+def _rotation(rs):
+    q, r = np.linalg.qr(rs.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))[None]
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def _small_rotation(ax, ay):
+    cx, sx, cy, sy = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay)
+    return np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+
+
+# source-view roles of make_feat_edges: view 0 sits FORWARD of the reference camera (magnifies, and points close to the reference camera are behind it) and
+# holds a zero patch; view 1 is anti-correlated; the others are noisy copies of the reference features
+_EDGE_NOISE = (0.3, 0.35, 0.15, 1.0, 0.5)
+_EDGE_FORWARD = 0.8
+
+
+def make_feat_edges(seed=0, B=3, P=160, V=5, C=17, H=37, W=53, size=2.5, center=(0.1, -0.2, 0.05)):
+    """Inputs of get_feat_loss_corr (model/loss.py:115-165) built to reach its edges.  The reference projection of every point is chosen
+    in one of five zones: inside the map, in the half-pixel border band (bilinear taps fall outside: zeros padding), out of range but not
+    clamped (1 < |g| < 1.1), clamped (|g| > 1.1) and in front of the reference camera but behind source camera 0.  Source cameras are
+    small rotations of the reference camera (view 0 also moved forward), so their projections fall in the same zones.  Features: a smooth
+    field shared by all maps plus per-view noise (corr_loss on both sides of 0.5); source view 1 is negated (corr < 0); source view 0 has
+    a zero patch (the 1e-9 norm clamp).  Reference view 1 has no hit.  -> dict of float32 / bool arrays: feat [B,C,H,W],
+    feat_src [B,V,C,H,W], cam [B,2,4,4], src_cams [B,V,2,4,4], size [1], center [1,3], hits [B*P], points [N,3] (normalised, view-major)."""
+    rs = np.random.RandomState(seed + 5000)
+    center = np.asarray(center, np.float64)
+    f = 2.0 * max(H, W)                                          # image pixels; a map pixel is two image pixels (loss.py:142, grid / 2)
+    K = np.eye(4)
+    K[0, 0] = K[1, 1] = f
+    K[0, 2], K[1, 2] = W, H
+    hits = rs.uniform(size=(B, P)) < 0.85
+    if B > 1:
+        hits[1] = False
+    cams, srcs, pts = [], [], []
+    for b in range(B):
+        Rw = _rotation(rs)                                       # world -> camera
+        cw = center - 3.0 * Rw[2]
+        E = np.eye(4)
+        E[:3, :3], E[:3, 3] = Rw, -Rw @ cw
+        cams.append(np.stack([E, K]))
+        sv = []
+        for v in range(V):
+            Rv = _small_rotation(*rs.uniform(-0.02, 0.02, size=2)) @ Rw
+            cv = cw + 0.03 * rs.normal(size=3) + (_EDGE_FORWARD * Rw[2] if v == 0 else 0.0)
+            Ev = np.eye(4)
+            Ev[:3, :3], Ev[:3, 3] = Rv, -Rv @ cv
+            sv.append(np.stack([Ev, K]))
+        srcs.append(np.stack(sv))
+        zone = rs.choice(5, size=P, p=[0.3, 0.25, 0.15, 0.15, 0.15])
+        g = rs.uniform(-0.9, 0.9, size=(P, 2))
+        ax = rs.randint(2, size=P)
+        sgn = np.where(rs.uniform(size=P) < 0.5, -1.0, 1.0)
+        npx = np.where(ax == 0, W, H).astype(np.float64)
+        edge = np.select([zone == 1, zone == 2, zone == 3],
+                         [1.0 - rs.uniform(size=P) / npx, 1.0 + rs.uniform(0.05, 0.95, size=P) * 0.1, rs.uniform(1.12, 1.5, size=P)], 0.0)
+        sel = (zone >= 1) & (zone <= 3)
+        g[sel, ax[sel]] = sgn[sel] * edge[sel]
+        z = np.where(zone == 4, rs.uniform(0.2, 0.7, size=P), rs.uniform(2.6, 3.4, size=P))
+        xc = np.stack([g[:, 0] * W / f * z, g[:, 1] * H / f * z, z], 1)           # g = u / W - 1 with u = f x / z + W
+        pw = xc @ Rw + cw                                                          # camera -> world
+        pts.append(((pw - center) / size * 2)[hits[b]])
+    # features: field(gx, gy) = base + three plane waves per channel, on every map's own normalised pixel grid
+    gx, gy = np.meshgrid((np.arange(W) + 0.5) / W * 2 - 1, (np.arange(H) + 0.5) / H * 2 - 1)
+    base = rs.normal(size=(C, 1, 1))
+    amp, wx, wy, ph = rs.normal(size=(4, 3, C, 1, 1))
+    field = base + 0.7 * sum(amp[k] * np.sin((1 + 2 * abs(wx[k])) * gx + (1 + 2 * abs(wy[k])) * gy + 3 * ph[k]) for k in range(3))
+    feat = np.stack([field + 0.1 * rs.normal(size=(C, H, W)) for _ in range(B)])
+    fsrc = np.stack([np.stack([(-1.0 if v == 1 else 1.0) * field + _EDGE_NOISE[v % 5] * rs.normal(size=(C, H, W)) for v in range(V)])
+                     for _ in range(B)])
+    y0, x0 = int(0.3 * H), int(0.3 * W)
+    fsrc[:, 0, :, y0:max(int(0.55 * H), y0 + 1), x0:max(int(0.55 * W), x0 + 1)] = 0.0
+    return dict(feat=feat.astype(np.float32), feat_src=fsrc.astype(np.float32), cam=np.stack(cams).astype(np.float32),
+                src_cams=np.stack(srcs).astype(np.float32), size=np.array([size], np.float32), center=center[None].astype(np.float32),
+                hits=hits.reshape(-1), points=np.concatenate(pts).astype(np.float32))

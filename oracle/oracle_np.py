@@ -278,16 +278,18 @@ def _project_jac(pts_world, cam):
     return uv, dK @ E[:3, :3]
 
 
-def feat_corr_loss(diff_surf_pts, hit_counts, feat, cam, feat_src, src_cams, size, center, with_grad=False, eps=1e-6):
+def feat_corr_loss(diff_surf_pts, hit_counts, feat, cam, feat_src, src_cams, size, center, with_grad=False, eps=1e-6, per_point=False):
     """IDRLoss.get_feat_loss_corr (model/loss.py:115-165).  diff_surf_pts [N,3] (hit points, view-major), hit_counts[B].
     with_grad=True: also the ANALYTIC gradient w.r.t. the points (projection jacobian x bilinear-tap derivatives x the derivative of the normalised
     correlation; what the reference's autograd and csrc/loss_kernels.hip::k_feat_corr compute); with_grad='fd': central differences of the (piecewise smooth)
-    loss instead -- O(N) evaluations, the cross-check of the analytic form on small inputs (tests/test_oracle_np_golden.py)."""
+    loss instead -- O(N) evaluations, the cross-check of the analytic form on small inputs (tests/test_oracle_np_golden.py).
+    per_point=True: one more result, the weighted term of every point [N] (its corr_loss summed over the source views, / (B * V * m_b)); their sum
+    is the loss, and they are what k_feat_corr writes to loss_pp."""
     pts = np.asarray(diff_surf_pts, np.float64)
     ctr = np.asarray(center, np.float64).reshape(1, 3)
     nb = len(hit_counts)
 
-    def total(p, grad=None):
+    def total(p, grad=None, pp=None):
         losses, start = [], 0
         for b, cnt in enumerate(hit_counts):
             cnt = int(cnt)
@@ -327,6 +329,8 @@ def feat_corr_loss(diff_surf_pts, hit_counts, feat, cam, feat_src, src_cams, siz
                 cl = np.abs(1 - corr)
                 m = (inr[0] & inr[v]) * (cl < 0.5)
                 acc += (cl * m).sum()
+                if pp is not None:
+                    pp[start:start + cnt] += cl * m / (V * cnt) / nb
                 if grad is not None:
                     # d corr = <da, b> / (n0 nv) - corr <a, da> / n0^2 (norm above its floor) + the same with a <-> b
                     a_, b_ = vals[0], vals[v]
@@ -347,11 +351,64 @@ def feat_corr_loss(diff_surf_pts, hit_counts, feat, cam, feat_src, src_cams, siz
                 p2[i, c] -= eps
                 g[i, c] = (total(p1) - total(p2)) / (2 * eps)
         return loss, g
+    pp = np.zeros(pts.shape[0]) if per_point else None
     if not with_grad:
-        return total(pts)
+        loss = total(pts, pp=pp)
+        return (loss, pp) if per_point else loss
     g = np.zeros_like(pts)
-    loss = total(pts, g)
-    return loss, g
+    loss = total(pts, g, pp)
+    return (loss, g, pp) if per_point else (loss, g)
+
+
+def feat_corr_decisions(diff_surf_pts, hit_counts, feat, cam, feat_src, src_cams, size, center):
+    """The per-point quantities get_feat_loss_corr decides on (loss.py:142-155), float64: g_raw [N, 1 + V, 2] (normalised grid coordinates before
+    the +-1.1 clamp; index 0 = the reference view), depth [N, 1 + V] (camera z before the projection's divisions), corr_loss [N, V]."""
+    pts = np.asarray(diff_surf_pts, np.float64)
+    ctr = np.asarray(center, np.float64).reshape(1, 3)
+    V = src_cams.shape[1]
+    g_raw, depth, cl = np.zeros((pts.shape[0], 1 + V, 2)), np.zeros((pts.shape[0], 1 + V)), np.zeros((pts.shape[0], V))
+    start = 0
+    for b, cnt in enumerate(hit_counts):
+        cnt = int(cnt)
+        sl = slice(start, start + cnt)
+        start += cnt
+        if cnt == 0:
+            continue
+        pw = pts[sl] / 2.0 * float(size) + ctr
+        vals = []
+        for v, (cm, fm) in enumerate(zip([cam[b]] + list(src_cams[b]), [feat[b]] + list(feat_src[b]))):
+            cm = np.asarray(cm, np.float64)
+            H, W = fm.shape[1:]
+            uv = _project(pw, cm) / 2.0
+            g_raw[sl, v] = np.stack([uv[:, 0] / W * 2 - 1, uv[:, 1] / H * 2 - 1], 1)
+            depth[sl, v] = pw @ cm[0, 2, :3] + cm[0, 2, 3]
+            vals.append(_bilinear(np.asarray(fm, np.float64), np.clip(g_raw[sl, v, 0], -1.1, 1.1), np.clip(g_raw[sl, v, 1], -1.1, 1.1))[0])
+        n0 = np.maximum(np.linalg.norm(vals[0], axis=0), 1e-9)
+        for v in range(V):
+            corr = (vals[0] * vals[1 + v]).sum(0) / n0 / np.maximum(np.linalg.norm(vals[1 + v], axis=0), 1e-9)
+            cl[sl, v] = np.abs(1 - corr)
+    return g_raw, depth, cl
+
+
+FEAT_ZONES = ('inside', 'band', 'out', 'clamped', 'behind')
+
+
+def feat_corr_zones(g_raw, depth, H, W):
+    """Zone of every projection of feat_corr_decisions -> {zone: bool [N, 1 + V]}: inside (all four bilinear taps in the map), band (in range, but a
+    tap falls outside: zeros padding), out (1 < |g| <= 1.1 on some axis: out of range, not clamped), clamped (|g| > 1.1: zero gradient), behind
+    (camera z < 0).  'behind' overlaps the others."""
+    a = np.abs(g_raw)
+    inr = (a <= 1).all(-1)
+    inside = (a[..., 0] <= 1 - 1.0 / W) & (a[..., 1] <= 1 - 1.0 / H)
+    clamped = (a > 1.1).any(-1)
+    return dict(inside=inside, band=inr & ~inside, out=~inr & ~clamped, clamped=clamped, behind=depth < 0)
+
+
+def feat_corr_ties(g_raw, cl, tol=1e-5):
+    """Points within `tol` of a decision of the loss (|g| = 1, |g| = 1.1, corr_loss = 0.5), where an fp32 evaluation may legitimately decide the other way."""
+    a = np.abs(g_raw)
+    near_g = ((np.abs(a - 1.0) < tol) | (np.abs(a - 1.1) < tol)).any(-1).any(-1)
+    return near_g | (np.abs(cl - 0.5) < tol).any(-1)
 
 
 # ------------------------------------------------------------------------------------------------ depth carving + loss terms

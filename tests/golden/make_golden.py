@@ -521,6 +521,29 @@ def g_feat(seed, B=2, P=300, V=3, name='feat_corr'):
          focal_scale=SCENE['focal_scale'])
 
 
+def g_feat_edges(seed, name='feat_corr_edges'):
+    """get_feat_loss_corr at its edges (synth.make_feat_edges): projections inside the map, in the half-pixel border band (zeros-padded taps), out of
+    range but unclamped, clamped and behind a source camera; a zero-feature patch (norm clamp), anti-correlated features, C = 17, V = 5, a 37 x 53 map and a
+    reference view without hits.  The maps are regenerated from the seed; the fixture holds the points, the reference's loss and d loss / d points."""
+    d = synth.make_feat_edges(seed)
+    B, C, H, W = d['feat'].shape
+    V = d['feat_src'].shape[1]
+    p = T(d['points']).requires_grad_(True)
+    with quiet():
+        loss = IDRLoss().get_feat_loss_corr(p, None, T(d['feat']), T(d['cam']), T(d['feat_src']), T(d['src_cams']), T(d['size']), T(d['center']),
+                                            T(d['hits']), T(np.ones_like(d['hits'])))
+    loss.backward()
+    # the same reference code in float64 on the same (float32) inputs: separates the reference's fp32 rounding from a difference in semantics
+    D = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    p64 = D(d['points']).requires_grad_(True)
+    with quiet():
+        loss64 = IDRLoss().get_feat_loss_corr(p64, None, D(d['feat']), D(d['cam']), D(d['feat_src']), D(d['src_cams']), D(d['size']), D(d['center']),
+                                              T(d['hits']), T(np.ones_like(d['hits'])))
+    loss64.backward()
+    save(name, seed=seed, B=B, V=V, C=C, H=H, W=W, hits=d['hits'], points=d['points'], loss=loss.item(), dpoints=p.grad.numpy(),
+         loss64=loss64.item(), dpoints64=p64.grad.numpy())
+
+
 def g_carve(seed, use_invalid=False, name='carve'):
     """carving_t2 (my_utils.py:269-331) + get_depth_loss (loss.py:37-63) on bumpy depth maps with holes, a depth step and per-view scale
     errors: points inside / outside the surface, near it (views disagree: out_thresh_perc voting) and outside every frustum."""
@@ -709,6 +732,7 @@ RECIPES = {
     'trace_mlp_w64_eval_render': lambda: g_trace_mlp(64, 4, 1024, 0, 1), 'trace_mlp_w64_train_render': lambda: g_trace_mlp(64, 4, 1024, 0, 1),
     'trace_mlp_w256_eval_render': lambda: g_trace_mlp(256, 2, 512, 0, 1), 'trace_mlp_w256_train_render': lambda: g_trace_mlp(256, 2, 512, 0, 1),
     'feat_corr': lambda: g_feat(0), 'feat_corr_v4': lambda: g_feat(0, 8, 200, 4, 'feat_corr_v4'), 'feat_corr_v8': lambda: g_feat(0, 8, 160, 8, 'feat_corr_v8'),
+    'feat_corr_edges': lambda: g_feat_edges(0),
     'carve': lambda: g_carve(0), 'carve_invalid': lambda: g_carve(0, True, 'carve_invalid'),
     'sdf_bwd_w64': lambda: g_sdf_bwd(64, 150, 0), 'sdf_bwd_w64_skips36': lambda: g_sdf_bwd(64, 150, 0, (3, 6), 'sdf_bwd_w64_skips36'),
     'sdf_bwd_w64_skip8': lambda: g_sdf_bwd(64, 150, 0, (8,), 'sdf_bwd_w64_skip8'), 'sdf_bwd_w64_skips48': lambda: g_sdf_bwd(64, 150, 0, (4, 8), 'sdf_bwd_w64_skips48'),
@@ -814,3 +838,4 @@ if __name__ == '__main__':
     for name in IDR_CONF_FIXTURES:                                              # conf switches that change the kernel route (model/conf.py:5-33)
         g_idr_conf(name)
     g_idr_relu_margins()
+    g_feat_edges(0)                                                             # get_feat_loss_corr at image borders, zero features, C = 17, V = 5, 37 x 53

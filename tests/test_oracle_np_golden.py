@@ -206,3 +206,67 @@ def test_feat_corr_analytic_gradient_vs_reference_autograd(name):
         _, ga = ON.feat_corr_loss(g['points'][:n], *a1, with_grad=True)
         _, gf = ON.feat_corr_loss(g['points'][:n], *a1, with_grad='fd')
         assert np.abs(ga - gf).max() < 1e-4 * max(np.abs(gf).max(), 1e-6)
+
+
+def _feat_edges():
+    g = golden('feat_corr_edges')
+    d = synth.make_feat_edges(int(g['seed']))
+    assert np.array_equal(d['points'], g['points']) and np.array_equal(d['hits'], g['hits'])
+    assert d['feat'].shape == (int(g['B']), int(g['C']), int(g['H']), int(g['W'])) and d['feat_src'].shape[1] == int(g['V'])
+    counts = g['hits'].reshape(int(g['B']), -1).sum(1)
+    return g, d, (counts, d['feat'], d['cam'], d['feat_src'], d['src_cams'], d['size'][0], d['center'][0])
+
+
+def test_feat_corr_edges_vs_reference():
+    """get_feat_loss_corr where its edge branches fire (fixture feat_corr_edges: border taps with zeros padding, out-of-range and clamped projections,
+    points behind a source camera, a zero-feature patch, anti-correlated features, C = 17, V = 5, 37 x 53, a view without hits): the oracle's loss, its
+    per-point terms and its analytic d loss / d points against the reference's.  The reference's fp32 autograd differs from the float64 oracle by up to
+    3.7e-5 of the largest entry here (points 0.2-0.7 in front of the reference camera); the same reference code run in float64 agrees to 3e-8, so the
+    difference is the reference's fp32 rounding: the fp32 bound is 5e-5 and the float64 one 1e-6."""
+    g, d, args = _feat_edges()
+    H, W = d['feat'].shape[2:]
+    gr, depth, cl = ON.feat_corr_decisions(g['points'], *args)
+    zones = ON.feat_corr_zones(gr, depth, H, W)
+    for z in ON.FEAT_ZONES:
+        assert zones[z][:, 1:].any() and (z == 'behind' or zones[z][:, 0].any()), z
+    inr = (np.abs(gr) <= 1).all(-1)
+    both = inr[:, :1] & inr[:, 1:]
+    assert (both & (cl < 0.5)).sum() > 50 and (both & (cl >= 0.5)).sum() > 50 and (cl > 1).any()     # both sides of the mask; corr < 0
+    assert (both & (cl < 0.5) & zones['band'][:, 1:]).any() and (both & zones['band'][:, :1] & (cl < 0.5)).any()
+    fsrc0 = d['feat_src'][:, 0]
+    assert (fsrc0 == 0).all(1).any() and not ON.feat_corr_ties(gr, cl).any()
+    loss, dp, pp = ON.feat_corr_loss(g['points'], *args, with_grad=True, per_point=True)
+    assert abs(loss - float(g['loss'])) < 2e-6 and abs(loss - float(g['loss64'])) < 1e-9
+    assert abs(pp.sum() - loss) < 1e-12 and (pp > 0).sum() > 50
+    mx = np.abs(g['dpoints64']).max()
+    assert np.abs(dp - g['dpoints']).max() < 5e-5 * mx, np.abs(dp - g['dpoints']).max() / mx
+    assert np.abs(dp - g['dpoints64']).max() < 1e-6 * mx, np.abs(dp - g['dpoints64']).max() / mx
+
+
+def test_feat_corr_edges_gradient_vs_central_differences():
+    """The analytic d loss / d points against central differences of the loss, on points of every zone whose projections all stay clear of the kinks
+    (tap switches, |g| = 1 and 1.1, corr_loss = 0.5, corr = 1) by more than a step moves them."""
+    g, d, args = _feat_edges()
+    H, W = d['feat'].shape[2:]
+    pts = g['points'].astype(np.float64)
+    gr, depth, cl = ON.feat_corr_decisions(pts, *args)
+    zones = ON.feat_corr_zones(gr, depth, H, W)
+    a = np.abs(gr)
+    px = np.stack([((gr[..., 0] + 1) * W - 1) / 2, ((gr[..., 1] + 1) * H - 1) / 2], -1)
+    clear = ((np.abs(px - np.round(px)) > 0.02) | (a > 1.1)).all(-1).all(-1)
+    clear &= ((np.abs(a - 1) > 2e-3) & (np.abs(a - 1.1) > 2e-3)).all(-1).all(-1) & (np.abs(cl - 0.5) > 2e-3).all(-1) & (cl > 2e-3).all(-1)
+    _, ga = ON.feat_corr_loss(pts, *args, with_grad=True)
+    scale = np.abs(ga).max()
+    checked = 0
+    for z in ON.FEAT_ZONES:
+        idx = np.flatnonzero(zones[z].any(-1) & clear & (np.abs(ga).max(1) > 1e-3 * scale))[:2]
+        assert len(idx) == 2, z
+        for i in idx:
+            for c in range(3):
+                p1, p2 = pts.copy(), pts.copy()
+                p1[i, c] += 1e-6
+                p2[i, c] -= 1e-6
+                fd = (ON.feat_corr_loss(p1, *args) - ON.feat_corr_loss(p2, *args)) / 2e-6
+                assert abs(fd - ga[i, c]) < 1e-4 * scale, (z, i, c, fd, ga[i, c])
+                checked += 1
+    assert checked == 3 * 2 * len(ON.FEAT_ZONES)
