@@ -517,6 +517,30 @@ int mvsdf_loss_forward(const MvsdfLossArgs* a, void* blk, void* stream);
 int mvsdf_loss_backward(const MvsdfLossArgs* a, const void* blk, const float* const* g, float* g_rgb, float* g_grad, float* g_eo, float* g_sf,
                         float* g_diff, void* stream);
 
+/* ---- mesh extraction (mesh_kernels.hip; Python: mvsdf_amd/mesh.py, which states the vertex / face conventions) ----
+ * Marching cubes of an fp32 volume vol[i][j][k] = vol[i * strides[0] + j * strides[1] + k * strides[2]] (element strides, host arrays shape[3] /
+ * strides[3]) at `level`; a corner is inside when its value is < level.  Two calls: mvsdf_mc_count classifies the grid and leaves int64
+ * {vertices, faces, non-finite value seen} at the start of the workspace; the caller reads them (the one host synchronisation), allocates and calls
+ * mvsdf_mc_emit with the same volume and workspace.  Every extent must be >= 2.
+ * workspace bytes: 4 per grid point + O(points / 1024); 0 = refused (an extent below 2 or a grid the kernels cannot index).
+ * nv_cap / nf_cap: the rows verts / normals and faces can hold (nothing is written beyond them).  Vertex ids are int32: a caller refuses a
+ * volume whose counts exceed INT32_MAX. */
+size_t mvsdf_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int mvsdf_mc_count(const float* vol, const int64_t* shape, const int64_t* strides, float level, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_mc_emit(const float* vol, const int64_t* shape, const int64_t* strides, float level, const float* spacing, const float* origin, void* ws,
+                  size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap, void* stream);
+/* Connected components of a mesh (vertex connectivity through faces, union-find) -> vert_label[nv], face_label[nf]: components numbered by their lowest
+ * vertex id; the workspace starts with int64 {components, label of the largest by area (ties: the lowest face index), its vertices, its faces,
+ * 1 if a union-find loop hit its bound}.  1 <= nv, nf <= INT32_MAX, else the workspace query gives 0. */
+size_t mvsdf_mesh_cc_workspace_bytes(int64_t nv, int64_t nf);
+int mvsdf_mesh_components(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes, int32_t* vert_label,
+                          int32_t* face_label, void* stream);
+/* The vertices and faces with the given label, in their original order, faces re-indexed (trimesh's submesh).  normals / colors ([nv][3] fp32) may be NULL.
+ * Same workspace size as mvsdf_mesh_components. */
+int mvsdf_mesh_select(const int32_t* vert_label, const int32_t* face_label, int64_t nv, int64_t nf, int32_t label, const float* verts, const float* normals,
+                      const float* colors, const int32_t* faces, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_colors,
+                      int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

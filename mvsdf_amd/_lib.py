@@ -52,6 +52,15 @@ def lib():
         L.mvsdf_adam_step_scaled.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mvsdf_adam_step_fused.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mvsdf_loss_scale.argtypes = [C.c_void_p] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p, C.c_int] * 4 + [C.c_void_p, C.c_void_p]   # g: host array of 6 pointers
+        i64, vp, f32 = C.c_int64, C.c_void_p, C.c_float
+        L.mvsdf_mc_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_mc_workspace_bytes.argtypes = [i64] * 3
+        L.mvsdf_mc_count.argtypes = [vp, vp, vp, f32, vp, C.c_size_t, vp]
+        L.mvsdf_mc_emit.argtypes = [vp, vp, vp, f32, vp, vp, vp, C.c_size_t, vp, vp, vp, i64, i64, vp]
+        L.mvsdf_mesh_cc_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_mesh_cc_workspace_bytes.argtypes = [i64, i64]
+        L.mvsdf_mesh_components.argtypes = [vp, vp, i64, i64, vp, C.c_size_t, vp, vp, vp]
+        L.mvsdf_mesh_select.argtypes = [vp, vp, i64, i64, C.c_int32] + [vp] * 5 + [C.c_size_t] + [vp] * 4 + [i64, i64, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -71,6 +80,7 @@ EXPORTS = [
     'mvsdf_step_create', 'mvsdf_step_destroy', 'mvsdf_step_forward', 'mvsdf_step_wait_counts', 'mvsdf_step_backward', 'mvsdf_step_set_timing', 'mvsdf_step_trace_times', 'mvsdf_step_times',
     'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets',
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
+    'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',
 ]
 
 

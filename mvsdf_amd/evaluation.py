@@ -3,6 +3,7 @@ code/training/idr_train.py:221-230): the image is split into pixel chunks (utils
 IDRNetwork.forward in eval mode (HIP tracer in its eval branch, analytic normals: no autograd graph, unlike the reference whose normals
 need autograd.grad and therefore run outside no_grad), the `rgb_values` are merged back."""
 import math
+import os
 
 import numpy as np
 import torch
@@ -50,3 +51,16 @@ def evaluate_rendering(model, batches, img_res, n_pixels=10000):
         psnrs.append(calculate_psnr(rgb_eval * mask, rgb_gt * mask, mask))
         images.append(rgb_eval)
     return psnrs, images
+
+
+def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None):
+    """eval.py:109-125 with eval_cameras off: the SDF mesh on the device (mesh.surface_mesh), moved to world coordinates by scale_mat, reduced to its
+    largest connected component; with `path`, written as <path>/surface_world_coordinates_<epoch>.obj.  -> the Mesh, or None if no surface."""
+    from .mesh import surface_mesh
+    mesh = surface_mesh(model, resolution)
+    if mesh is None:
+        return None
+    mesh = mesh.apply_transform(scale_mat).largest_component()
+    if path is not None:
+        mesh.export(os.path.join(path, 'surface_world_coordinates_{0}.obj'.format(epoch)))
+    return mesh

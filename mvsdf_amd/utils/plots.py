@@ -2,8 +2,9 @@
 
 The reference evaluates `sdf(points)` on a resolution^3 grid in 50 000-point chunks, each a PyTorch MLP forward with a device->host
 copy, then runs scikit-image's marching cubes.  Here the grid points are GENERATED in chunks on the device and pushed through the
-tracing-MLP kernel (`mvsdf_sdf_col0`, fp32 MFMA); only the fp32 volume comes back.  Marching cubes itself is scikit-image (a
-third-party dependency of the reference, absent from this image): `get_surface_trace` raises ImportError without it.
+tracing-MLP kernel (`mvsdf_sdf_col0`, fp32 MFMA); only the fp32 volume comes back.  The functions below that mirror the reference keep
+its scikit-image / trimesh marching cubes (third-party, absent from this image: they raise ImportError without them); the on-device
+marching cubes, components and export of this project are mvsdf_amd/mesh.py (mesh.surface_mesh, evaluation.extract_world_mesh).
 """
 import numpy as np
 import torch
@@ -25,6 +26,11 @@ def sdf_on_uniform_grid(sdf, resolution, chunk=1 << 22, device=None):
     """z[resolution^3] float32 numpy = sdf at get_grid_uniform(resolution)['grid_points'], without materialising the point list:
     chunks of grid points are built on the device from their flat index.  `sdf`: ImplicitNetwork.native_sdf() (packed weights ->
     the HIP tracing-MLP kernel) or any callable points[n,3] -> [n]."""
+    return sdf_on_uniform_grid_device(sdf, resolution, chunk, device).cpu().numpy()
+
+
+def sdf_on_uniform_grid_device(sdf, resolution, chunk=1 << 22, device=None):
+    """sdf_on_uniform_grid as a float32 device tensor [resolution^3] (no host copy)."""
     n = resolution
     device = device or torch.device('cuda', torch.cuda.current_device())
     ax = torch.from_numpy(np.linspace(-1.0, 1.0, n)).to(device)                  # float64 like the reference, cast per point below
@@ -38,7 +44,7 @@ def sdf_on_uniform_grid(sdf, resolution, chunk=1 << 22, device=None):
         iy = idx // (n * n)
         pts = torch.stack([ax[ix], ax[iy], ax[iz]], -1).to(torch.float32)
         out[s:s + pts.shape[0]] = ops.sdf_col0(net, pts) if net is not None else sdf(pts).reshape(-1)
-    return out.cpu().numpy()
+    return out
 
 
 def lin2img(tensor, img_res):
@@ -54,6 +60,12 @@ def surface_volume(model, resolution):
     and evaluated by the tracing-MLP kernel (k_sdf_col0)."""
     z = sdf_on_uniform_grid(model.implicit_network.native_sdf(), resolution)
     return z.astype(np.float32).reshape(resolution, resolution, resolution).transpose([1, 0, 2])
+
+
+def surface_volume_device(model, resolution):
+    """surface_volume as a device tensor: a (y, x, z)-transposed VIEW of the grid values, no copy (mvsdf_amd.mesh.marching_cubes takes any strides)."""
+    z = sdf_on_uniform_grid_device(model.implicit_network.native_sdf(), resolution)
+    return z.view(resolution, resolution, resolution).permute(1, 0, 2)
 
 
 def surface_vertex_colors(model, verts, chunk=1 << 20):
