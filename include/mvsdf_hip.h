@@ -541,6 +541,22 @@ int mvsdf_mesh_select(const int32_t* vert_label, const int32_t* face_label, int6
                       const float* colors, const int32_t* faces, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_colors,
                       int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 
+/* ---- mesh trimming (mesh_cut.hip; Python: Mesh.cut_mask / Mesh.trim in mvsdf_amd/mesh.py, which states the semantics) ----
+ * The minimum cut of reference code/mesh_cut/mesh_cut.py over the faces: S* = the faces reachable from the source in the residual graph of a maximum
+ * flow (bright faces, red > thresh / 255 on average, tie to the source; faces sharing an edge are joined by 2 * smooth).  1 <= nv <= INT32_MAX,
+ * 1 <= nf <= INT32_MAX / 8, else the workspace query gives 0.  colors: fp32 [nv][3] (only the red channel is read).
+ * mvsdf_mesh_cut waits for the stream (its round loop reads flags from the device) -> removed[nf] (1 = in S*) and int64 {flow value, removed faces,
+ * vertices the kept faces use, error bits (1 duplicate directed edge, 2 repeated vertex id in a face, 4 vertex id out of range, 8 table overflow,
+ * 16 round limit, 32 relabel limit), push rounds, relabel launches} at the start of the workspace.  With error bits set nothing else is valid.
+ * smooth in [0, INT32_MAX / 6]. */
+size_t mvsdf_mesh_cut_workspace_bytes(int64_t nv, int64_t nf);
+int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_t nf, int32_t thresh, int32_t smooth, void* ws, size_t ws_bytes,
+                   uint8_t* removed, void* stream);
+/* After a successful mvsdf_mesh_cut with the same workspace: the kept faces and the vertices they use, in their original order, faces re-indexed.
+ * normals / colors may be NULL; nv_cap / nf_cap bound what is written. */
+int mvsdf_mesh_trim(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes,
+                    float* out_verts, float* out_normals, float* out_colors, int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

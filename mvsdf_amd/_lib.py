@@ -61,6 +61,10 @@ def lib():
         L.mvsdf_mesh_cc_workspace_bytes.argtypes = [i64, i64]
         L.mvsdf_mesh_components.argtypes = [vp, vp, i64, i64, vp, C.c_size_t, vp, vp, vp]
         L.mvsdf_mesh_select.argtypes = [vp, vp, i64, i64, C.c_int32] + [vp] * 5 + [C.c_size_t] + [vp] * 4 + [i64, i64, vp]
+        L.mvsdf_mesh_cut_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_mesh_cut_workspace_bytes.argtypes = [i64, i64]
+        L.mvsdf_mesh_cut.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp]
+        L.mvsdf_mesh_trim.argtypes = [vp] * 4 + [i64, i64, vp, C.c_size_t] + [vp] * 4 + [i64, i64, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -81,6 +85,7 @@ EXPORTS = [
     'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets',
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
     'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',
+    'mvsdf_mesh_cut_workspace_bytes', 'mvsdf_mesh_cut', 'mvsdf_mesh_trim',
 ]
 
 
