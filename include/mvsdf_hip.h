@@ -557,6 +557,38 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
 int mvsdf_mesh_trim(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes,
                     float* out_verts, float* out_normals, float* out_colors, int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 
+/* ---- DTU Chamfer evaluation (chamfer.hip; Python: mvsdf_amd/chamfer.py, which states the metric) ----
+ * All four operations leave int64 results at the start of their workspace; fp64 throughout.  Error bits: 1 more points than max_points,
+ * 2 vertex id out of range, 4 non-finite coordinate, 8 coordinate too far from the origin for the downsampling grid, 16 cell-table overflow,
+ * 32 round limit reached, 64 tree-walk bound.  With error bits set nothing else is valid.
+ * mvsdf_chamfer_key: the visiting key splitmix64(seed ^ i) of point i.
+ * Sampling, two calls: mvsdf_chamfer_sample_count waits for the stream -> {points (nv + samples), samples, error bits}; the caller allocates
+ * out[points][3] and calls mvsdf_chamfer_sample_emit with the same workspace (out = the vertices, then the samples in face order; cap bounds the rows
+ * written).  1 <= nv, nf <= INT32_MAX, else the workspace query gives 0. */
+uint64_t mvsdf_chamfer_key(uint64_t seed, int64_t i);
+size_t mvsdf_chamfer_sample_workspace_bytes(int64_t nv, int64_t nf);
+int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, int64_t max_points, void* ws, size_t ws_bytes,
+                               void* stream);
+int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, void* ws, size_t ws_bytes, double* out,
+                              int64_t cap, void* stream);
+/* The greedy radius filter: kept[n] (1 = kept) is the lexicographically-first maximal set with no two points within density (d^2 <= density^2) under
+ * ascending keys.  Waits for the stream (its round loop reads counts) -> {kept, rounds, error bits}; stops with bit 32 after max_rounds rounds
+ * (n rounds always suffice).  1 <= n <= INT32_MAX / 4. */
+size_t mvsdf_chamfer_downsample_workspace_bytes(int64_t n);
+int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint64_t seed, int64_t max_rounds, void* ws, size_t ws_bytes, uint8_t* kept,
+                             void* stream);
+/* The masks, no host wait: d_in / d_obs (capacity n rows) = the kept points inside the box / also observed, s_above (capacity m rows) = the stl points
+ * above the plane, each in input order -> {rows of d_in, of d_obs, of s_above, error bits (4: a non-finite stl point)}.  box: HOST fp32 [9] = lo[3], hi[3], bb[0][3]; obs: uint8
+ * [X][Y][Z] on the device, obs_shape: HOST int64 [3]; plane: HOST fp64 [4]. */
+size_t mvsdf_chamfer_mask_workspace_bytes(int64_t n, int64_t m);
+int mvsdf_chamfer_mask(const double* pts, const uint8_t* kept, int64_t n, const double* stl, int64_t m, const float* box, double res, const uint8_t* obs,
+                       const int64_t* obs_shape, const double* plane, void* ws, size_t ws_bytes, double* d_in, double* d_obs, double* s_above, void* stream);
+/* dist[q] = min over refs of sqrt((dx dx + dy dy) + dz dz), exact, +inf where it is not < max_dist.  Waits for the stream -> {distances below the
+ * cut-off, their fp64 sum (bits, fixed order), error bits}.  0 <= nq, 1 <= nr <= INT32_MAX. */
+size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr);
+int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs, int64_t nr, double max_dist, void* ws, size_t ws_bytes, double* dist,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,19 @@ def lib():
         L.mvsdf_mesh_cut_workspace_bytes.argtypes = [i64, i64]
         L.mvsdf_mesh_cut.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp]
         L.mvsdf_mesh_trim.argtypes = [vp] * 4 + [i64, i64, vp, C.c_size_t] + [vp] * 4 + [i64, i64, vp]
+        f64, u64, sz = C.c_double, C.c_uint64, C.c_size_t
+        L.mvsdf_chamfer_key.restype = u64
+        L.mvsdf_chamfer_key.argtypes = [u64, i64]
+        for fn in ('mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_nearest_workspace_bytes'):
+            getattr(L, fn).restype = sz
+            getattr(L, fn).argtypes = [i64, i64]
+        L.mvsdf_chamfer_downsample_workspace_bytes.restype = sz
+        L.mvsdf_chamfer_downsample_workspace_bytes.argtypes = [i64]
+        L.mvsdf_chamfer_sample_count.argtypes = [vp, vp, i64, i64, f64, i64, vp, sz, vp]
+        L.mvsdf_chamfer_sample_emit.argtypes = [vp, vp, i64, i64, f64, vp, sz, vp, i64, vp]
+        L.mvsdf_chamfer_downsample.argtypes = [vp, i64, f64, u64, i64, vp, sz, vp, vp]
+        L.mvsdf_chamfer_mask.argtypes = [vp, vp, i64, vp, i64, vp, f64, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_chamfer_nearest.argtypes = [vp, i64, vp, i64, f64, vp, sz, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -86,6 +99,9 @@ EXPORTS = [
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
     'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',
     'mvsdf_mesh_cut_workspace_bytes', 'mvsdf_mesh_cut', 'mvsdf_mesh_trim',
+    'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
+    'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
+    'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
 ]
 
 

@@ -1,0 +1,1038 @@
+// chamfer.hip -- on-device DTU Chamfer evaluation (the DTUeval-python steps the reference's README points to): mesh sampling, the greedy radius
+// filter, the observation / ground-plane masks and exact nearest distances with a cut-off.  Python: mvsdf_amd/chamfer.py, which states the metric;
+// tests/chamfer_ref.py restates it in numpy.  All arithmetic is fp64 without contraction, in the order the metric writes it.
+//
+// * Sampling: per-face counts, an int64 exclusive scan, an emit pass; output = the vertices, then the samples in face order.
+// * Downsampling: points binned into cells of edge density * (1 + 1e-6) in an open-addressing table keyed by a hash of the int64 cell coordinates
+//   (a collision only merges two buckets, which adds candidates and never hides one).  The kept set is the lexicographically-first maximal
+//   independent set under the keys splitmix64(seed ^ i): synchronous rounds (states ping-pong) keep a point once every lower-key neighbour is
+//   removed and remove it once one is kept.  The lowest undecided key is decided in every round, so N rounds always suffice.
+// * Masks: flags, int64 scans and an order-preserving scatter.
+// * Nearest distance: the references are sorted by a 63-bit Morton code (stable LSD radix sort, 4 bits per pass), cut into leaves of CH_LEAF
+//   consecutive points, and an implicit 8-ary tree of fp64 boxes is built over the leaves.  A query descends greedily to one leaf for a first
+//   bound, then walks the tree without a stack, pruning a box only when its lower bound exceeds min(best, max_dist)^2 by a relative 4e-9.  The
+//   minimum squared distance is exact (every point not pruned is compared with the metric's formula) and sqrt is monotonic, so the result is
+//   sqrt(min d^2) bit for bit.  A query with nothing within max_dist only meets boxes farther than the cut-off, which stops it near the root.
+// * Sums: fixed-order block reductions in fp64, no float atomics.
+//
+// Every device loop is bounded; the downsampling round loop on the host stops at the caller's limit and reports it.
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include "capi_util.h"
+
+#define CH_THREADS 256
+#define CH_ITEMS 8                                    // consecutive items per lane in the scans and sums
+#define CH_CHUNK (CH_THREADS * CH_ITEMS)
+#define CH_TOP_THREADS 1024
+#define CH_HDR 256                                    // bytes at the start of every workspace: int64 results the host reads
+#define CH_EMPTY 0xffffffffffffffffull
+#define CH_LEAF 16                                    // reference points per leaf
+#define CH_ARITY 8
+#define CH_MAX_LEVELS 16
+#define CH_RS_BINS 16                                 // radix sort: 4 bits per pass
+#define CH_RS_ITEMS 16
+#define CH_RS_CHUNK (CH_THREADS * CH_RS_ITEMS)
+#define CH_MORTON_BITS 21
+#define CH_DS_BATCH 4                                 // downsampling rounds per host check
+#define CH_MARGIN2 (1.0 + 4e-9)                       // relative margin of a box prune on squared distances
+#define CH_CELL_LIMIT 2147483648.0                    // |coordinate / cell| bound that keeps the 27-cell search exact
+
+enum {
+    CH_ERR_POINTS = 1,      // sampling: more points than max_points
+    CH_ERR_RANGE = 2,       // sampling: a vertex id outside [0, nv)
+    CH_ERR_FINITE = 4,      // a non-finite coordinate
+    CH_ERR_COORD = 8,       // downsampling: a coordinate too far from the origin for the cell grid
+    CH_ERR_HASH = 16,       // the cell table's probe bound (cannot happen at load factor 1/2)
+    CH_ERR_ROUNDS = 32,     // downsampling: the round limit was reached
+    CH_ERR_WALK = 64,       // nearest: a tree walk hit its bound (cannot happen)
+};
+
+enum { DS_UNDECIDED = 0, DS_KEPT = 1, DS_REMOVED = 2 };
+
+static inline size_t ch_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline unsigned ch_grid(long long n, long long per) { return (unsigned)((n + per - 1) / per); }
+
+__host__ __device__ __forceinline__ uint64_t ch_splitmix64(uint64_t x) {
+    x += 0x9e3779b97f4a7c15ull;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ double ch_d2(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__device__ __forceinline__ bool ch_finite3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
+
+// ================================================================ int64 exclusive scan (three launches) ================================================================
+// per-workgroup totals of a[n]
+__global__ __launch_bounds__(CH_THREADS) void k_ch_block_sum(const long long* __restrict__ a, long long n, long long* __restrict__ bsum) {
+    __shared__ long long sh[CH_THREADS];
+    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)threadIdx.x * CH_ITEMS;
+    long long s = 0;
+    for (int q = 0; q < CH_ITEMS; ++q)
+        if (base + q < n) s += a[base + q];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = CH_THREADS / 2; d; d >>= 1) {
+        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
+}
+
+// in place: exclusive scan of bsum[nb]; *total = the sum (one workgroup, serial ranges per lane)
+__global__ __launch_bounds__(CH_TOP_THREADS) void k_ch_scan_top(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
+    __shared__ long long sh[CH_TOP_THREADS];
+    const int t = threadIdx.x;
+    const long long per = (nb + CH_TOP_THREADS - 1) / CH_TOP_THREADS;
+    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
+    long long s = 0;
+    for (long long q = lo; q < hi; ++q) s += bsum[q];
+    sh[t] = s;
+    __syncthreads();
+    for (int d = 1; d < CH_TOP_THREADS; d <<= 1) {                // inclusive Hillis-Steele scan
+        const long long x = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] += x;
+        __syncthreads();
+    }
+    long long r = sh[t] - s;
+    for (long long q = lo; q < hi; ++q) {
+        const long long v = bsum[q];
+        bsum[q] = r;
+        r += v;
+    }
+    if (t == CH_TOP_THREADS - 1) *total = sh[t];
+}
+
+// out[i] = boff[block] + the exclusive prefix of a inside the block (out may alias a)
+__global__ __launch_bounds__(CH_THREADS) void k_ch_scan_apply(const long long* a, long long n, const long long* __restrict__ boff, long long* out) {
+    __shared__ long long sh[CH_THREADS];
+    const int t = threadIdx.x;
+    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)t * CH_ITEMS;
+    long long v[CH_ITEMS], s = 0;
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; ++q) {
+        v[q] = base + q < n ? a[base + q] : 0;
+        s += v[q];
+    }
+    sh[t] = s;
+    __syncthreads();
+    for (int d = 1; d < CH_THREADS; d <<= 1) {
+        const long long x = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] += x;
+        __syncthreads();
+    }
+    long long r = boff[blockIdx.x] + sh[t] - s;
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; ++q) {
+        if (base + q < n) out[base + q] = r;
+        r += v[q];
+    }
+}
+
+static size_t ch_scan_tmp_bytes(long long n) { return ch_align((size_t)(ch_grid(n, CH_CHUNK) + 1) * 8); }
+
+// exclusive scan of a[n] (n >= 1) into out (may alias a); tmp: ch_scan_tmp_bytes(n); total: one int64 on the device
+static void ch_scan(const long long* a, long long n, long long* out, void* tmp, long long* total, hipStream_t s) {
+    const unsigned nb = ch_grid(n, CH_CHUNK);
+    long long* bsum = (long long*)tmp;
+    hipLaunchKernelGGL(k_ch_block_sum, dim3(nb), dim3(CH_THREADS), 0, s, a, n, bsum);
+    hipLaunchKernelGGL(k_ch_scan_top, dim3(1), dim3(CH_TOP_THREADS), 0, s, bsum, (long long)nb, total);
+    hipLaunchKernelGGL(k_ch_scan_apply, dim3(nb), dim3(CH_THREADS), 0, s, a, n, (const long long*)bsum, out);
+}
+
+static int ch_read(void* host, const void* dev, size_t n, hipStream_t s, const char* what) {
+    if (int rc = mv_check(hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s), what)) return rc;
+    return mv_check(hipStreamSynchronize(s), what);
+}
+
+static int ch_write_header(void* ws, const long long* hdr, int n, hipStream_t s, const char* what) {
+    if (int rc = mv_check(hipMemcpyAsync(ws, hdr, (size_t)n * 8, hipMemcpyHostToDevice, s), what)) return rc;
+    return mv_check(hipStreamSynchronize(s), what);
+}
+
+// ================================================================ sampling ================================================================
+struct ChFace {
+    double a[3], v1[3], v2[3], n1, n2;
+};
+
+// the face's geometry; 0 = it samples nothing (zero area), else 1.  bad |= CH_ERR_RANGE / CH_ERR_FINITE.
+__device__ __forceinline__ int ch_face(const float* __restrict__ V, const int* __restrict__ F, long long f, long long nv, double density, ChFace* g,
+                                       int* bad) {
+    double p[3][3];
+    for (int s = 0; s < 3; ++s) {
+        const int id = F[f * 3 + s];
+        if (id < 0 || id >= nv) {
+            *bad |= CH_ERR_RANGE;
+            return 0;
+        }
+        for (int c = 0; c < 3; ++c) p[s][c] = (double)V[(long long)id * 3 + c];
+        if (!ch_finite3(p[s])) {
+            *bad |= CH_ERR_FINITE;
+            return 0;
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        g->a[c] = p[0][c];
+        g->v1[c] = p[1][c] - p[0][c];
+        g->v2[c] = p[2][c] - p[0][c];
+    }
+    const double* v1 = g->v1;
+    const double* v2 = g->v2;
+    const double l1 = sqrt((v1[0] * v1[0] + v1[1] * v1[1]) + v1[2] * v1[2]);
+    const double l2 = sqrt((v2[0] * v2[0] + v2[1] * v2[1]) + v2[2] * v2[2]);
+    const double cx = v1[1] * v2[2] - v1[2] * v2[1], cy = v1[2] * v2[0] - v1[0] * v2[2], cz = v1[0] * v2[1] - v1[1] * v2[0];
+    const double area2 = sqrt((cx * cx + cy * cy) + cz * cz);
+    if (!(area2 > 0)) return 0;
+    const double thr = density * sqrt(l1 * l2 / area2);
+    g->n1 = floor(l1 / thr);
+    g->n2 = floor(l2 / thr);
+    return 1;
+}
+
+// samples (i, j), i = 0..n1, j = 0..n2 (np.mgrid[:n1 + 1, :n2 + 1]) with s + t < 1.  s and t grow with i and j and fp addition is monotonic, so a row
+// ends at its first miss and the rows end at the first row that keeps nothing: the loops take at most 2 k + 2 steps for k samples.  out == NULL:
+// count only, stopping once the count passes `limit`.
+__device__ __forceinline__ long long ch_face_samples(const ChFace& g, double* __restrict__ out, long long at, long long cap, long long limit) {
+    const double d1 = fmax(g.n1, 1e-7), d2 = fmax(g.n2, 1e-7);
+    long long k = 0;
+    for (long long i = 0; (double)i <= g.n1 && k <= limit; ++i) {
+        const double s = ((double)i + 0.5) / d1;
+        long long row = 0;
+        for (long long j = 0; (double)j <= g.n2 && k <= limit; ++j) {
+            const double t = ((double)j + 0.5) / d2;
+            if (!(s + t < 1.0)) break;
+            if (out && at + k < cap) {
+                double* o = out + (at + k) * 3;
+                for (int c = 0; c < 3; ++c) o[c] = (g.v1[c] * s + g.v2[c] * t) + g.a[c];
+            }
+            ++k;
+            ++row;
+        }
+        if (!row) break;
+    }
+    return k;
+}
+
+// per-face sample counts; a face with more than max_points samples stops counting there and raises CH_ERR_POINTS
+__global__ __launch_bounds__(CH_THREADS) void k_ch_sample_count(const float* __restrict__ V, const int* __restrict__ F, long long nv, long long nf,
+                                                                 double density, long long max_points, long long* __restrict__ cnt, int* err) {
+    const long long f = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (f >= nf) return;
+    int bad = 0;
+    ChFace g;
+    long long k = 0;
+    if (ch_face(V, F, f, nv, density, &g, &bad)) {
+        k = ch_face_samples(g, nullptr, 0, 0, max_points);
+        if (k > max_points) {
+            bad |= CH_ERR_POINTS;
+            k = 0;
+        }
+    }
+    cnt[f] = k;
+    if (bad) atomicOr(err, bad);
+}
+
+// the vertices as fp64 (out may be NULL: check only)
+__global__ __launch_bounds__(CH_THREADS) void k_ch_vert_copy(const float* __restrict__ V, long long nv, double* __restrict__ out, int* err) {
+    const long long v = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (v >= nv) return;
+    double p[3];
+    for (int c = 0; c < 3; ++c) p[c] = (double)V[v * 3 + c];
+    if (out)
+        for (int c = 0; c < 3; ++c) out[v * 3 + c] = p[c];
+    if (!ch_finite3(p)) atomicOr(err, CH_ERR_FINITE);
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_ch_sample_emit(const float* __restrict__ V, const int* __restrict__ F, long long nv, long long nf,
+                                                                double density, const long long* __restrict__ off, double* __restrict__ out, long long cap) {
+    const long long f = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (f >= nf) return;
+    int bad = 0;
+    ChFace g;
+    if (ch_face(V, F, f, nv, density, &g, &bad)) ch_face_samples(g, out, nv + off[f], cap, LLONG_MAX - 1);
+}
+
+struct ChSampleLayout {
+    size_t cnt, tmp, flags, total;
+};
+
+static bool ch_sample_layout(long long nv, long long nf, ChSampleLayout* L) {
+    if (nv < 1 || nf < 1 || nv > INT_MAX || nf > INT_MAX) return false;
+    size_t o = CH_HDR;
+    L->cnt = o;   o += ch_align((size_t)nf * 8);
+    L->tmp = o;   o += ch_scan_tmp_bytes(nf);
+    L->flags = o; o += ch_align(4 * 8);
+    L->total = o;
+    return true;
+}
+
+// ================================================================ downsampling ================================================================
+__device__ __forceinline__ unsigned long long ch_cell_key(long long x, long long y, long long z) {
+    unsigned long long k = (unsigned long long)x * 0x9e3779b97f4a7c15ull ^ (unsigned long long)y * 0xc2b2ae3d27d4eb4full ^ (unsigned long long)z * 0x165667b19e3779f9ull;
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k == CH_EMPTY ? 0 : k;
+}
+
+__device__ __forceinline__ bool ch_cell(const double* p, double h, long long* c) {
+    for (int a = 0; a < 3; ++a) {
+        const double q = floor(p[a] / h);
+        if (!(fabs(q) < CH_CELL_LIMIT)) return false;
+        c[a] = (long long)q;
+    }
+    return true;
+}
+
+// the table slot holding key, or -1
+__device__ __forceinline__ long long ch_find(const unsigned long long* __restrict__ keys, unsigned long long tmask, unsigned long long key) {
+    unsigned long long slot = key & tmask;
+    for (unsigned long long probe = 0; probe <= tmask; ++probe) {
+        const unsigned long long k = keys[slot];
+        if (k == key) return (long long)slot;
+        if (k == CH_EMPTY) return -1;
+        slot = (slot + 1) & tmask;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_ds_insert(const double* __restrict__ P, long long n, double h, unsigned long long* keys, unsigned long long tmask,
+                                                           int* __restrict__ pslot, unsigned long long* cnt, int* err) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    pslot[i] = -1;
+    const double* p = P + i * 3;
+    if (!ch_finite3(p)) {
+        atomicOr(err, CH_ERR_FINITE);
+        return;
+    }
+    long long c[3];
+    if (!ch_cell(p, h, c)) {
+        atomicOr(err, CH_ERR_COORD);
+        return;
+    }
+    const unsigned long long key = ch_cell_key(c[0], c[1], c[2]);
+    unsigned long long slot = key & tmask;
+    for (unsigned long long probe = 0; probe <= tmask; ++probe) {
+        const unsigned long long prev = atomicCAS(keys + slot, CH_EMPTY, key);
+        if (prev == CH_EMPTY || prev == key) {
+            pslot[i] = (int)slot;
+            atomicAdd(cnt + slot, 1ull);
+            return;
+        }
+        slot = (slot + 1) & tmask;
+    }
+    atomicOr(err, CH_ERR_HASH);
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_ds_fill(long long n, const int* __restrict__ pslot, const long long* __restrict__ start, unsigned long long* cur,
+                                                         int* __restrict__ order) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int s = pslot[i];
+    order[start[s] + (long long)atomicAdd(cur + s, 1ull)] = (int)i;
+}
+
+// One synchronous round: a decided point keeps its state; an undecided one is removed if a lower-key neighbour (d^2 <= density^2) is kept, kept if
+// every lower-key neighbour is removed, else it waits.  Reads only `old`, so the round is the same whatever the schedule.  left: undecided after it.
+__global__ __launch_bounds__(CH_THREADS) void k_ds_round(const double* __restrict__ P, long long n, double h, double r2, unsigned long long seed,
+                                                          const unsigned long long* __restrict__ keys, unsigned long long tmask, const unsigned long long* __restrict__ cnt,
+                                                          const long long* __restrict__ start, const int* __restrict__ order, const unsigned char* __restrict__ old,
+                                                          unsigned char* __restrict__ nxt, int* left) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const unsigned char st = old[i];
+    if (st != DS_UNDECIDED) {
+        nxt[i] = st;
+        return;
+    }
+    const double* p = P + i * 3;
+    long long c[3];
+    ch_cell(p, h, c);                                             // the insert pass refused every point where this fails
+    const unsigned long long ki = ch_splitmix64(seed ^ (unsigned long long)i);
+    bool removed = false, blocked = false;
+    for (int d = 0; d < 27 && !removed; ++d) {
+        const long long s = ch_find(keys, tmask, ch_cell_key(c[0] + d / 9 - 1, c[1] + (d / 3) % 3 - 1, c[2] + d % 3 - 1));
+        if (s < 0) continue;
+        const long long b = start[s], e = b + (long long)cnt[s];
+        for (long long q = b; q < e; ++q) {
+            const int j = order[q];
+            if (j == i) continue;
+            const unsigned char sj = old[j];
+            if (sj == DS_REMOVED) continue;
+            if (ch_splitmix64(seed ^ (unsigned long long)j) >= ki) continue;
+            const double* pj = P + (long long)j * 3;
+            if (ch_d2(p[0], p[1], p[2], pj[0], pj[1], pj[2]) <= r2) {
+                if (sj == DS_KEPT) {
+                    removed = true;
+                    break;
+                }
+                blocked = true;
+            }
+        }
+    }
+    nxt[i] = removed ? DS_REMOVED : (blocked ? DS_UNDECIDED : DS_KEPT);
+    if (!removed && blocked) atomicAdd(left, 1);
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_ds_out(long long n, const unsigned char* __restrict__ st, unsigned char* __restrict__ kept,
+                                                        unsigned long long* nkept) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    const bool k = i < n && st[i] == DS_KEPT;
+    if (i < n) kept[i] = k;
+    unsigned long long v = k;
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(nkept, v);
+}
+
+struct ChDsLayout {
+    unsigned long long tsize;
+    size_t keys, cnt, start, cur, pslot, order, st0, st1, tmp, flags, total;
+};
+
+static bool ch_ds_layout(long long n, ChDsLayout* L) {
+    if (n < 1 || n > INT_MAX / 4) return false;
+    L->tsize = 1;
+    while (L->tsize < (unsigned long long)(2 * n)) L->tsize <<= 1;
+    size_t o = CH_HDR;
+    L->keys = o;  o += ch_align(L->tsize * 8);
+    L->cnt = o;   o += ch_align(L->tsize * 8);
+    L->start = o; o += ch_align(L->tsize * 8);
+    L->cur = o;   o += ch_align(L->tsize * 8);
+    L->pslot = o; o += ch_align((size_t)n * 4);
+    L->order = o; o += ch_align((size_t)n * 4);
+    L->st0 = o;   o += ch_align((size_t)n);
+    L->st1 = o;   o += ch_align((size_t)n);
+    L->tmp = o;   o += ch_scan_tmp_bytes((long long)L->tsize);
+    L->flags = o; o += ch_align((CH_DS_BATCH + 2) * 8);
+    L->total = o;
+    return true;
+}
+
+// ================================================================ masks ================================================================
+struct ChMaskArgs {
+    double lo[3], hi[3], bb0[3], res, plane[4];
+    long long dim[3];
+};
+
+__global__ __launch_bounds__(CH_THREADS) void k_mask_flags(const double* __restrict__ P, const unsigned char* __restrict__ kept, long long n, ChMaskArgs m,
+                                                            const unsigned char* __restrict__ obs, long long* __restrict__ fin, long long* __restrict__ fobs) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const double* p = P + i * 3;
+    bool in = kept[i] != 0;
+    for (int a = 0; a < 3; ++a) in = in && p[a] >= m.lo[a] && p[a] < m.hi[a];
+    bool ob = in;
+    long long g[3];
+    for (int a = 0; a < 3 && ob; ++a) {
+        const double x = rint((p[a] - m.bb0[a]) / m.res);        // round half to even (np.around)
+        ob = x >= 0.0 && x < (double)m.dim[a];
+        g[a] = ob ? (long long)x : 0;
+    }
+    if (ob) ob = obs[(g[0] * m.dim[1] + g[1]) * m.dim[2] + g[2]] != 0;
+    fin[i] = in;
+    fobs[i] = ob;
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_mask_plane(const double* __restrict__ S, long long m, ChMaskArgs a, long long* __restrict__ fab,
+                                                            long long* err) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= m) return;
+    const double* p = S + i * 3;
+    if (!ch_finite3(p)) atomicOr((unsigned long long*)err, (unsigned long long)CH_ERR_FINITE);
+    fab[i] = ((a.plane[0] * p[0] + a.plane[1] * p[1]) + a.plane[2] * p[2]) + a.plane[3] > 0.0;
+}
+
+// out[off[i]] = P[i] where the flag is set (flags are re-derived from off: off[i + 1] - off[i], and the total for the last item)
+__global__ __launch_bounds__(CH_THREADS) void k_mask_scatter(const double* __restrict__ P, long long n, const long long* __restrict__ off,
+                                                              const long long* __restrict__ total, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const long long o = off[i], nx = i + 1 < n ? off[i + 1] : *total;
+    if (nx > o)
+        for (int c = 0; c < 3; ++c) out[o * 3 + c] = P[i * 3 + c];
+}
+
+struct ChMaskLayout {
+    size_t fin, fobs, fab, tmp1, tmp2, tmp3, tot, total;
+};
+
+static bool ch_mask_layout(long long n, long long m, ChMaskLayout* L) {
+    if (n < 1 || m < 1 || n > (1ll << 40) || m > (1ll << 40)) return false;
+    size_t o = CH_HDR;
+    L->fin = o;  o += ch_align((size_t)n * 8);
+    L->fobs = o; o += ch_align((size_t)n * 8);
+    L->fab = o;  o += ch_align((size_t)m * 8);
+    L->tmp1 = o; o += ch_scan_tmp_bytes(n);
+    L->tmp2 = o; o += ch_scan_tmp_bytes(n);
+    L->tmp3 = o; o += ch_scan_tmp_bytes(m);
+    L->tot = o;  o += ch_align(4 * 8);
+    L->total = o;
+    return true;
+}
+
+// ================================================================ nearest distance ================================================================
+// per-workgroup box of the references (k_nn_bbox_final combines them); a non-finite coordinate raises CH_ERR_FINITE
+__global__ __launch_bounds__(CH_THREADS) void k_nn_bbox_part(const double* __restrict__ R, long long n, double* __restrict__ part, int* err) {
+    __shared__ double sh[6][CH_THREADS];
+    const long long base = (long long)blockIdx.x * CH_CHUNK;
+    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int bad = 0;
+    for (int q = 0; q < CH_ITEMS; ++q) {
+        const long long i = base + (long long)q * CH_THREADS + threadIdx.x;
+        if (i >= n) break;
+        const double* p = R + i * 3;
+        if (!ch_finite3(p)) {
+            bad = 1;
+            continue;
+        }
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fmin(b[a], p[a]);
+            b[3 + a] = fmax(b[3 + a], p[a]);
+        }
+    }
+    if (bad) atomicOr(err, CH_ERR_FINITE);
+    for (int a = 0; a < 6; ++a) sh[a][threadIdx.x] = b[a];
+    __syncthreads();
+    for (int d = CH_THREADS / 2; d; d >>= 1) {
+        if ((int)threadIdx.x < d)
+            for (int a = 0; a < 6; ++a)
+                sh[a][threadIdx.x] = a < 3 ? fmin(sh[a][threadIdx.x], sh[a][threadIdx.x + d]) : fmax(sh[a][threadIdx.x], sh[a][threadIdx.x + d]);
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// frame[0..2] = the box's low corner, frame[3..5] = 2^21 / extent (1 for a flat axis)
+__global__ __launch_bounds__(64) void k_nn_bbox_final(const double* __restrict__ part, long long nb, double* __restrict__ frame) {
+    const int a = threadIdx.x;
+    if (a >= 3) return;
+    double lo = INFINITY, hi = -INFINITY;
+    for (long long b = 0; b < nb; ++b) {
+        lo = fmin(lo, part[b * 6 + a]);
+        hi = fmax(hi, part[b * 6 + 3 + a]);
+    }
+    frame[a] = lo;
+    frame[3 + a] = hi > lo ? (double)(1 << CH_MORTON_BITS) / (hi - lo) : 1.0;
+}
+
+__device__ __forceinline__ unsigned long long ch_spread3(unsigned long long x) {   // 21 bits -> every third bit of 63
+    x &= 0x1fffff;
+    x = (x | x << 32) & 0x1f00000000ffffull;
+    x = (x | x << 16) & 0x1f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_nn_morton(const double* __restrict__ R, long long n, const double* __restrict__ frame,
+                                                           unsigned long long* __restrict__ key, int* __restrict__ val) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    unsigned long long m = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double x = (R[i * 3 + a] - frame[a]) * frame[3 + a];
+        const double c = x >= 0.0 ? fmin(x, (double)((1 << CH_MORTON_BITS) - 1)) : 0.0;
+        m |= ch_spread3((unsigned long long)c) << a;
+    }
+    key[i] = m;
+    val[i] = (int)i;
+}
+
+// radix sort, pass `shift`: per-workgroup digit counts, digit-major: hist[d * nb + b]
+__global__ __launch_bounds__(CH_THREADS) void k_rs_hist(const unsigned long long* __restrict__ key, long long n, int shift, long long* __restrict__ hist, int nb) {
+    __shared__ int c[CH_RS_BINS];
+    if (threadIdx.x < CH_RS_BINS) c[threadIdx.x] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * CH_RS_CHUNK;
+    for (int q = 0; q < CH_RS_ITEMS; ++q) {
+        const long long i = base + (long long)q * CH_THREADS + threadIdx.x;
+        if (i < n) atomicAdd(&c[(key[i] >> shift) & (CH_RS_BINS - 1)], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < CH_RS_BINS) hist[(long long)threadIdx.x * nb + blockIdx.x] = c[threadIdx.x];
+}
+
+// stable scatter: lane t owns items [base + t * CH_RS_ITEMS, + CH_RS_ITEMS); its place among equal digits of the workgroup is the count of those
+// digits in lanes < t (an exclusive scan over the lanes in LDS) plus its own running count
+__global__ __launch_bounds__(CH_THREADS) void k_rs_scatter(const unsigned long long* __restrict__ kin, const int* __restrict__ vin, long long n, int shift,
+                                                            const long long* __restrict__ off, int nb, unsigned long long* __restrict__ kout, int* __restrict__ vout) {
+    __shared__ int c[CH_RS_BINS][CH_THREADS];
+    const int t = threadIdx.x;
+    const long long base = (long long)blockIdx.x * CH_RS_CHUNK + (long long)t * CH_RS_ITEMS;
+#pragma unroll
+    for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] = 0;
+    for (int q = 0; q < CH_RS_ITEMS; ++q)
+        if (base + q < n) ++c[(kin[base + q] >> shift) & (CH_RS_BINS - 1)][t];
+    __syncthreads();
+    int own[CH_RS_BINS];
+#pragma unroll
+    for (int d = 0; d < CH_RS_BINS; ++d) own[d] = c[d][t];
+    for (int s = 1; s < CH_THREADS; s <<= 1) {                   // inclusive Hillis-Steele scan over the lanes, every digit at once
+        int x[CH_RS_BINS];
+#pragma unroll
+        for (int d = 0; d < CH_RS_BINS; ++d) x[d] = t >= s ? c[d][t - s] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] += x[d];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] -= own[d];    // exclusive; from here lane t alone uses column t as its running position
+    for (int q = 0; q < CH_RS_ITEMS; ++q) {
+        const long long i = base + q;
+        if (i >= n) break;
+        const unsigned long long k = kin[i];
+        const int d = (k >> shift) & (CH_RS_BINS - 1);
+        const long long dst = off[(long long)d * nb + blockIdx.x] + c[d][t]++;
+        kout[dst] = k;
+        vout[dst] = vin[i];
+    }
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_nn_gather(const double* __restrict__ R, long long n, const int* __restrict__ val, double* __restrict__ sp) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const long long j = val[i];
+    for (int c = 0; c < 3; ++c) sp[i * 3 + c] = R[j * 3 + c];
+}
+
+__global__ __launch_bounds__(CH_THREADS) void k_nn_leaf_box(const double* __restrict__ sp, long long n, long long nleaf, double* __restrict__ box) {
+    const long long l = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (l >= nleaf) return;
+    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const long long e = min(n, (l + 1) * CH_LEAF);
+    for (long long i = l * CH_LEAF; i < e; ++i)
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fmin(b[a], sp[i * 3 + a]);
+            b[3 + a] = fmax(b[3 + a], sp[i * 3 + a]);
+        }
+    for (int a = 0; a < 6; ++a) box[l * 6 + a] = b[a];
+}
+
+// node i of a level = the union of children [8 i, min(8 i + 8, nchild)) of the level below
+__global__ __launch_bounds__(CH_THREADS) void k_nn_node_box(const double* __restrict__ child, long long nchild, long long nnode, double* __restrict__ box) {
+    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (i >= nnode) return;
+    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const long long e = min(nchild, (i + 1) * CH_ARITY);
+    for (long long k = i * CH_ARITY; k < e; ++k)
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fmin(b[a], child[k * 6 + a]);
+            b[3 + a] = fmax(b[3 + a], child[k * 6 + 3 + a]);
+        }
+    for (int a = 0; a < 6; ++a) box[i * 6 + a] = b[a];
+}
+
+struct ChTree {
+    int top;                                          // root level (level 0 = the leaves)
+    long long cnt[CH_MAX_LEVELS], off[CH_MAX_LEVELS]; // nodes per level, their first box
+    long long n, nodes;
+};
+
+__device__ __forceinline__ double ch_box_lb2(const double* __restrict__ b, double x, double y, double z) {
+    const double gx = x < b[0] ? b[0] - x : (x > b[3] ? x - b[3] : 0.0);
+    const double gy = y < b[1] ? b[1] - y : (y > b[4] ? y - b[4] : 0.0);
+    const double gz = z < b[2] ? b[2] - z : (z > b[5] ? z - b[5] : 0.0);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+__device__ __forceinline__ double ch_leaf_min(const double* __restrict__ sp, long long n, long long l, double x, double y, double z, double best) {
+    const long long e = min(n, (l + 1) * CH_LEAF);
+    for (long long i = l * CH_LEAF; i < e; ++i) best = fmin(best, ch_d2(x, y, z, sp[i * 3], sp[i * 3 + 1], sp[i * 3 + 2]));
+    return best;
+}
+
+// dist[i] = min over the references of sqrt((dx dx + dy dy) + dz dz), +inf where that is not < max_dist
+__global__ __launch_bounds__(CH_THREADS) void k_nn_query(const double* __restrict__ Q, long long nq, const double* __restrict__ sp, const double* __restrict__ box,
+                                                          ChTree T, double max_dist, double* __restrict__ dist, int* err) {
+    const long long qi = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
+    if (qi >= nq) return;
+    const double x = Q[qi * 3], y = Q[qi * 3 + 1], z = Q[qi * 3 + 2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
+        atomicOr(err, CH_ERR_FINITE);
+        dist[qi] = INFINITY;
+        return;
+    }
+    const double cut2 = max_dist * max_dist;
+    double best = INFINITY;
+    // a first bound: follow the nearest child from the root to one leaf
+    {
+        long long i = 0;
+        for (int k = T.top; k > 0; --k) {
+            const long long b = i * CH_ARITY, e = min(T.cnt[k - 1], b + CH_ARITY);
+            long long pick = b;
+            double lbest = INFINITY;
+            for (long long c = b; c < e; ++c) {
+                const double lb = ch_box_lb2(box + (T.off[k - 1] + c) * 6, x, y, z);
+                if (lb < lbest) {
+                    lbest = lb;
+                    pick = c;
+                }
+            }
+            i = pick;
+        }
+        if (ch_box_lb2(box + i * 6, x, y, z) <= cut2 * CH_MARGIN2) best = ch_leaf_min(sp, T.n, i, x, y, z, best);
+    }
+    // the full walk: depth first over the implicit tree, children in index order, no stack (parent = i / 8, next sibling = i + 1)
+    int k = T.top;
+    long long i = 0;
+    const long long max_steps = 2 * T.nodes + 4;
+    long long step = 0;
+    for (; step < max_steps; ++step) {
+        const double bound = fmin(best, cut2) * CH_MARGIN2;
+        if (ch_box_lb2(box + (T.off[k] + i) * 6, x, y, z) <= bound) {
+            if (k > 0) {
+                --k;
+                i *= CH_ARITY;
+                continue;
+            }
+            best = ch_leaf_min(sp, T.n, i, x, y, z, best);
+        }
+        while (k < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[k])) {
+            i /= CH_ARITY;
+            ++k;
+        }
+        if (k == T.top) break;
+        ++i;
+    }
+    if (step >= max_steps) atomicOr(err, CH_ERR_WALK);
+    const double d = sqrt(best);
+    dist[qi] = d < max_dist ? d : INFINITY;
+}
+
+// fixed-order sums of the finite distances: per-workgroup (sum, count), then one workgroup over those
+__global__ __launch_bounds__(CH_THREADS) void k_nn_sum_part(const double* __restrict__ d, long long n, double* __restrict__ psum, long long* __restrict__ pcnt) {
+    __shared__ double ss[CH_THREADS];
+    __shared__ long long sc[CH_THREADS];
+    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)threadIdx.x * CH_ITEMS;
+    double s = 0.0;
+    long long c = 0;
+    for (int q = 0; q < CH_ITEMS; ++q)
+        if (base + q < n && isfinite(d[base + q])) {
+            s += d[base + q];
+            ++c;
+        }
+    ss[threadIdx.x] = s;
+    sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int w = CH_THREADS / 2; w; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            ss[threadIdx.x] += ss[threadIdx.x + w];
+            sc[threadIdx.x] += sc[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        psum[blockIdx.x] = ss[0];
+        pcnt[blockIdx.x] = sc[0];
+    }
+}
+
+__global__ __launch_bounds__(CH_TOP_THREADS) void k_nn_sum_final(const double* __restrict__ psum, const long long* __restrict__ pcnt, long long nb,
+                                                                  long long* __restrict__ hdr) {
+    __shared__ double ss[CH_TOP_THREADS];
+    __shared__ long long sc[CH_TOP_THREADS];
+    const int t = threadIdx.x;
+    const long long per = (nb + CH_TOP_THREADS - 1) / CH_TOP_THREADS;
+    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
+    double s = 0.0;
+    long long c = 0;
+    for (long long q = lo; q < hi; ++q) {
+        s += psum[q];
+        c += pcnt[q];
+    }
+    ss[t] = s;
+    sc[t] = c;
+    __syncthreads();
+    for (int w = CH_TOP_THREADS / 2; w; w >>= 1) {
+        if (t < w) {
+            ss[t] += ss[t + w];
+            sc[t] += sc[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        hdr[0] = sc[0];
+        hdr[1] = __double_as_longlong(ss[0]);
+    }
+}
+
+struct ChNnLayout {
+    ChTree T;
+    long long nbr, nbq, rs_nb;
+    size_t part, frame, k0, k1, v0, v1, hist, tmp, sp, box, psum, pcnt, flags, total;
+};
+
+static bool ch_nn_layout(long long nq, long long nr, ChNnLayout* L) {
+    if (nq < 0 || nr < 1 || nq > (1ll << 40) || nr > INT_MAX) return false;
+    ChTree& T = L->T;
+    T.n = nr;
+    T.cnt[0] = (nr + CH_LEAF - 1) / CH_LEAF;
+    T.off[0] = 0;
+    T.top = 0;
+    while (T.cnt[T.top] > 1) {
+        if (T.top + 1 >= CH_MAX_LEVELS) return false;
+        T.cnt[T.top + 1] = (T.cnt[T.top] + CH_ARITY - 1) / CH_ARITY;
+        T.off[T.top + 1] = T.off[T.top] + T.cnt[T.top];
+        ++T.top;
+    }
+    T.nodes = T.off[T.top] + 1;
+    L->nbr = ch_grid(nr, CH_CHUNK);
+    L->nbq = ch_grid(nq > 0 ? nq : 1, CH_CHUNK);
+    L->rs_nb = ch_grid(nr, CH_RS_CHUNK);
+    size_t o = CH_HDR;
+    L->part = o;  o += ch_align((size_t)L->nbr * 48);
+    L->frame = o; o += ch_align(6 * 8);
+    L->k0 = o;    o += ch_align((size_t)nr * 8);
+    L->k1 = o;    o += ch_align((size_t)nr * 8);
+    L->v0 = o;    o += ch_align((size_t)nr * 4);
+    L->v1 = o;    o += ch_align((size_t)nr * 4);
+    L->hist = o;  o += ch_align((size_t)L->rs_nb * CH_RS_BINS * 8);
+    L->tmp = o;   o += ch_scan_tmp_bytes(L->rs_nb * CH_RS_BINS) + ch_align(8);
+    L->sp = o;    o += ch_align((size_t)nr * 24);
+    L->box = o;   o += ch_align((size_t)T.nodes * 48);
+    L->psum = o;  o += ch_align((size_t)L->nbq * 8);
+    L->pcnt = o;  o += ch_align((size_t)L->nbq * 8);
+    L->flags = o; o += ch_align(4 * 8);
+    L->total = o;
+    return true;
+}
+
+extern "C" {
+
+uint64_t mvsdf_chamfer_key(uint64_t seed, int64_t i) { return ch_splitmix64(seed ^ (uint64_t)i); }
+
+size_t mvsdf_chamfer_sample_workspace_bytes(int64_t nv, int64_t nf) {
+    ChSampleLayout L;
+    return ch_sample_layout(nv, nf, &L) ? L.total : 0;
+}
+
+int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, int64_t max_points, void* ws, size_t ws_bytes,
+                               void* stream) {
+    ChSampleLayout L;
+    if (!verts || !faces || !ws || !ch_sample_layout(nv, nf, &L) || !(density > 0) || !isfinite(density) || max_points < 1)
+        return mv_fail(-1, "mvsdf_chamfer_sample_count: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_sample_count: workspace too small (mvsdf_chamfer_sample_workspace_bytes)");
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    long long* cnt = (long long*)(w + L.cnt);
+    long long* fl = (long long*)(w + L.flags);                    // [0]: error bits (int), [1]: the scan's total
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_sample_count"))) return rc;
+    hipLaunchKernelGGL(k_ch_vert_copy, dim3(ch_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, (double*)nullptr, (int*)fl);
+    hipLaunchKernelGGL(k_ch_sample_count, dim3(ch_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
+                       (long long)max_points, cnt, (int*)fl);
+    ch_scan(cnt, nf, cnt, w + L.tmp, fl + 1, s);
+    if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_sample_count"))) return rc;
+    long long h[2];
+    if ((rc = ch_read(h, fl, sizeof(h), s, "mvsdf_chamfer_sample_count"))) return rc;
+    const long long err = (int)h[0], samples = h[1];
+    long long hdr[3] = {nv + samples, samples, err};
+    if (!err && nv + samples > max_points) hdr[2] |= CH_ERR_POINTS;
+    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_sample_count");
+}
+
+int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, void* ws, size_t ws_bytes, double* out,
+                              int64_t cap, void* stream) {
+    ChSampleLayout L;
+    if (!verts || !faces || !ws || !out || !ch_sample_layout(nv, nf, &L) || !(density > 0) || cap < nv)
+        return mv_fail(-1, "mvsdf_chamfer_sample_emit: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_sample_emit: workspace too small (mvsdf_chamfer_sample_workspace_bytes)");
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ch_vert_copy, dim3(ch_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, out, (int*)(w + L.flags));
+    hipLaunchKernelGGL(k_ch_sample_emit, dim3(ch_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
+                       (const long long*)(w + L.cnt), out, (long long)cap);
+    return mv_check(hipGetLastError(), "mvsdf_chamfer_sample_emit");
+}
+
+size_t mvsdf_chamfer_downsample_workspace_bytes(int64_t n) {
+    ChDsLayout L;
+    return ch_ds_layout(n, &L) ? L.total : 0;
+}
+
+int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint64_t seed, int64_t max_rounds, void* ws, size_t ws_bytes, uint8_t* kept,
+                             void* stream) {
+    ChDsLayout L;
+    if (!pts || !ws || !kept || !ch_ds_layout(n, &L) || !(density > 0) || !isfinite(density) || max_rounds < 1)
+        return mv_fail(-1, "mvsdf_chamfer_downsample: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_downsample: workspace too small (mvsdf_chamfer_downsample_workspace_bytes)");
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    const double h = density * (1.0 + 1e-6), r2 = density * density;
+    const unsigned long long tmask = L.tsize - 1;
+    const unsigned gn = ch_grid(n, CH_THREADS);
+    unsigned long long* keys = (unsigned long long*)(w + L.keys);
+    unsigned long long* cnt = (unsigned long long*)(w + L.cnt);
+    long long* start = (long long*)(w + L.start);
+    unsigned char* st[2] = {(unsigned char*)(w + L.st0), (unsigned char*)(w + L.st1)};
+    int* fl = (int*)(w + L.flags);                                // [0]: error bits, [1]: kept (int64 at +8), [4..]: undecided after each round of a batch
+    long long hdr[3] = {0, 0, 0};                                 // kept, rounds, error bits
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(keys, 0xff, L.tsize * 8, s), "mvsdf_chamfer_downsample"))) return rc;
+    if ((rc = mv_check(hipMemsetAsync(cnt, 0, L.tsize * 8, s), "mvsdf_chamfer_downsample"))) return rc;
+    if ((rc = mv_check(hipMemsetAsync(w + L.cur, 0, L.tsize * 8, s), "mvsdf_chamfer_downsample"))) return rc;
+    if ((rc = mv_check(hipMemsetAsync(st[0], DS_UNDECIDED, (size_t)n, s), "mvsdf_chamfer_downsample"))) return rc;
+    if ((rc = mv_check(hipMemsetAsync(fl, 0, (CH_DS_BATCH + 2) * 8, s), "mvsdf_chamfer_downsample"))) return rc;
+    hipLaunchKernelGGL(k_ds_insert, dim3(gn), dim3(CH_THREADS), 0, s, pts, (long long)n, h, keys, tmask, (int*)(w + L.pslot), cnt, fl);
+    if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
+    int e = 0;
+    if ((rc = ch_read(&e, fl, 4, s, "mvsdf_chamfer_downsample"))) return rc;
+    hdr[2] = e;
+    if (!e) {
+        ch_scan((const long long*)cnt, (long long)L.tsize, start, w + L.tmp, (long long*)(fl + 2), s);
+        hipLaunchKernelGGL(k_ds_fill, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const int*)(w + L.pslot), (const long long*)start,
+                           (unsigned long long*)(w + L.cur), (int*)(w + L.order));
+        int cur = 0;
+        bool done = false;
+        while (!done) {
+            if (hdr[1] >= max_rounds) {
+                hdr[2] |= CH_ERR_ROUNDS;
+                break;
+            }
+            const int batch = (int)(max_rounds - hdr[1] < CH_DS_BATCH ? max_rounds - hdr[1] : CH_DS_BATCH);
+            if ((rc = mv_check(hipMemsetAsync(fl + 4, 0, CH_DS_BATCH * 4, s), "mvsdf_chamfer_downsample"))) return rc;
+            for (int b = 0; b < batch; ++b) {
+                hipLaunchKernelGGL(k_ds_round, dim3(gn), dim3(CH_THREADS), 0, s, pts, (long long)n, h, r2, (unsigned long long)seed,
+                                   (const unsigned long long*)keys, tmask, (const unsigned long long*)cnt, (const long long*)start,
+                                   (const int*)(w + L.order), (const unsigned char*)st[cur], st[cur ^ 1], fl + 4 + b);
+                cur ^= 1;
+            }
+            if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
+            int left[CH_DS_BATCH];
+            if ((rc = ch_read(left, fl + 4, sizeof(left), s, "mvsdf_chamfer_downsample"))) return rc;
+            for (int b = 0; b < batch && !done; ++b) {
+                ++hdr[1];
+                done = left[b] == 0;
+            }
+        }
+        if (done) {
+            if ((rc = mv_check(hipMemsetAsync(fl + 2, 0, 8, s), "mvsdf_chamfer_downsample"))) return rc;   // (the table scan's total)
+            hipLaunchKernelGGL(k_ds_out, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const unsigned char*)st[cur], kept,
+                               (unsigned long long*)(fl + 2));
+            if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
+            if ((rc = ch_read(&hdr[0], fl + 2, 8, s, "mvsdf_chamfer_downsample"))) return rc;
+        }
+    }
+    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_downsample");
+}
+
+size_t mvsdf_chamfer_mask_workspace_bytes(int64_t n, int64_t m) {
+    ChMaskLayout L;
+    return ch_mask_layout(n, m, &L) ? L.total : 0;
+}
+
+int mvsdf_chamfer_mask(const double* pts, const uint8_t* kept, int64_t n, const double* stl, int64_t m, const float* box, double res, const uint8_t* obs,
+                       const int64_t* obs_shape, const double* plane, void* ws, size_t ws_bytes, double* d_in, double* d_obs, double* s_above, void* stream) {
+    ChMaskLayout L;
+    if (!pts || !kept || !stl || !box || !obs || !obs_shape || !plane || !ws || !d_in || !d_obs || !s_above || !ch_mask_layout(n, m, &L) || !(res > 0))
+        return mv_fail(-1, "mvsdf_chamfer_mask: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_mask: workspace too small (mvsdf_chamfer_mask_workspace_bytes)");
+    ChMaskArgs a;
+    for (int k = 0; k < 3; ++k) {
+        a.lo[k] = (double)box[k];
+        a.hi[k] = (double)box[3 + k];
+        a.bb0[k] = (double)box[6 + k];
+        a.dim[k] = obs_shape[k];
+        if (obs_shape[k] < 1) return mv_fail(-1, "mvsdf_chamfer_mask: empty observation mask");
+    }
+    for (int k = 0; k < 4; ++k) a.plane[k] = plane[k];
+    a.res = res;
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    long long* fin = (long long*)(w + L.fin);
+    long long* fobs = (long long*)(w + L.fobs);
+    long long* fab = (long long*)(w + L.fab);
+    long long* tot = (long long*)(w + L.tot);
+    hipLaunchKernelGGL(k_mask_flags, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, kept, (long long)n, a, obs, fin, fobs);
+    if (int rc = mv_check(hipMemsetAsync(tot, 0, 4 * 8, s), "mvsdf_chamfer_mask")) return rc;
+    hipLaunchKernelGGL(k_mask_plane, dim3(ch_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, a, fab, tot + 3);
+    ch_scan(fin, n, fin, w + L.tmp1, tot, s);
+    ch_scan(fobs, n, fobs, w + L.tmp2, tot + 1, s);
+    ch_scan(fab, m, fab, w + L.tmp3, tot + 2, s);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fin, (const long long*)tot, d_in);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fobs,
+                       (const long long*)(tot + 1), d_obs);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, (const long long*)fab,
+                       (const long long*)(tot + 2), s_above);
+    if (int rc = mv_check(hipGetLastError(), "mvsdf_chamfer_mask")) return rc;
+    return mv_check(hipMemcpyAsync(ws, tot, 4 * 8, hipMemcpyDeviceToDevice, s), "mvsdf_chamfer_mask");
+}
+
+size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr) {
+    ChNnLayout L;
+    return ch_nn_layout(nq, nr, &L) ? L.total : 0;
+}
+
+int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs, int64_t nr, double max_dist, void* ws, size_t ws_bytes, double* dist,
+                          void* stream) {
+    ChNnLayout L;
+    if (!refs || !ws || (nq > 0 && (!queries || !dist)) || !ch_nn_layout(nq, nr, &L) || !(max_dist > 0))
+        return mv_fail(-1, "mvsdf_chamfer_nearest: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_nearest: workspace too small (mvsdf_chamfer_nearest_workspace_bytes)");
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    int* fl = (int*)(w + L.flags);
+    long long hdr[3] = {0, 0, 0};                                 // distances below the cut-off, their fp64 sum (bits), error bits
+    const int nb = (int)L.rs_nb;
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_nearest"))) return rc;
+    hipLaunchKernelGGL(k_nn_bbox_part, dim3((unsigned)L.nbr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (double*)(w + L.part), fl);
+    hipLaunchKernelGGL(k_nn_bbox_final, dim3(1), dim3(64), 0, s, (const double*)(w + L.part), L.nbr, (double*)(w + L.frame));
+    if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
+    int e = 0;
+    if ((rc = ch_read(&e, fl, 4, s, "mvsdf_chamfer_nearest"))) return rc;
+    hdr[2] = e;
+    if (!e) {
+        unsigned long long* k[2] = {(unsigned long long*)(w + L.k0), (unsigned long long*)(w + L.k1)};
+        int* v[2] = {(int*)(w + L.v0), (int*)(w + L.v1)};
+        const unsigned gr = ch_grid(nr, CH_THREADS);
+        hipLaunchKernelGGL(k_nn_morton, dim3(gr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (const double*)(w + L.frame), k[0], v[0]);
+        long long* hist = (long long*)(w + L.hist);
+        long long* tot = (long long*)(w + L.tmp + ch_scan_tmp_bytes(L.rs_nb * CH_RS_BINS));
+        int cur = 0;
+        for (int shift = 0; shift < 3 * CH_MORTON_BITS; shift += 4) {
+            hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (long long)nr, shift, hist, nb);
+            ch_scan(hist, L.rs_nb * CH_RS_BINS, hist, w + L.tmp, tot, s);
+            hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (const int*)v[cur], (long long)nr, shift,
+                               (const long long*)hist, nb, k[cur ^ 1], v[cur ^ 1]);
+            cur ^= 1;
+        }
+        double* sp = (double*)(w + L.sp);
+        double* box = (double*)(w + L.box);
+        const ChTree& T = L.T;
+        hipLaunchKernelGGL(k_nn_gather, dim3(gr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (const int*)v[cur], sp);
+        hipLaunchKernelGGL(k_nn_leaf_box, dim3(ch_grid(T.cnt[0], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)sp, (long long)nr, T.cnt[0], box);
+        for (int lv = 1; lv <= T.top; ++lv)
+            hipLaunchKernelGGL(k_nn_node_box, dim3(ch_grid(T.cnt[lv], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)(box + T.off[lv - 1] * 6),
+                               T.cnt[lv - 1], T.cnt[lv], box + T.off[lv] * 6);
+        if (nq > 0) {
+            hipLaunchKernelGGL(k_nn_query, dim3(ch_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, (long long)nq, (const double*)sp,
+                               (const double*)box, T, max_dist, dist, fl);
+            hipLaunchKernelGGL(k_nn_sum_part, dim3((unsigned)L.nbq), dim3(CH_THREADS), 0, s, (const double*)dist, (long long)nq, (double*)(w + L.psum),
+                               (long long*)(w + L.pcnt));
+            hipLaunchKernelGGL(k_nn_sum_final, dim3(1), dim3(CH_TOP_THREADS), 0, s, (const double*)(w + L.psum), (const long long*)(w + L.pcnt), L.nbq,
+                               (long long*)(fl + 2));
+        }
+        if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
+        long long r[3];                                           // error bits (int) at byte 0, k_nn_sum_final's count and sum at bytes 8 and 16
+        if ((rc = ch_read(r, fl, sizeof(r), s, "mvsdf_chamfer_nearest"))) return rc;
+        hdr[0] = nq > 0 ? r[1] : 0;
+        hdr[1] = nq > 0 ? r[2] : 0;
+        hdr[2] = (int)r[0];
+    }
+    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_nearest");
+}
+
+}  // extern "C"
