@@ -589,6 +589,29 @@ size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr);
 int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs, int64_t nr, double max_dist, void* ws, size_t ws_bytes, double* dist,
                           void* stream);
 
+/* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
+ * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.
+ * raw: fp32 [mvsdf_featext_raw_floats()] on the device, the layers in the order of mvsdf_amd/features.py::LAYERS, each its weight in PyTorch layout
+ * (Conv2d [cout][cin][k][k], ConvTranspose2d [cin][cout][k][k]) followed, where the layer has one, by its BatchNorm's weight, bias, running_mean and
+ * running_var.  mvsdf_featext_pack writes the folded weights to packed (mvsdf_featext_pack_bytes(), 256-byte aligned), stream-ordered.
+ * mvsdf_featext_forward: x NHWC [n][h][w][3]; ceil(h / 2) and ceil(w / 2) must be multiples of 4, else the workspace query gives 0.  out1 / out2 /
+ * out3 (NHWC, 32 channels, at ceil(h / 2) / 4, / 2 and / 1; each may be NULL) = final_conv_1/2/3 of the network.  Runs the stages
+ * [first_stage, last_stage) of 0 init_conv, 1..3 the encoder stages, 4..5 the decoder stages, 6 the heads (0, 7 = all); the workspace carries the
+ * activations between calls.  No host wait.  Results do not depend on n or on the call (no atomics). */
+size_t mvsdf_featext_raw_floats(void);
+size_t mvsdf_featext_pack_bytes(void);
+int mvsdf_featext_pack(const float* raw, void* packed, size_t packed_bytes, void* stream);
+size_t mvsdf_featext_workspace_bytes(int64_t n, int64_t h, int64_t w);
+int mvsdf_featext_forward(const float* packed, const float* x, int64_t n, int64_t h, int64_t w, void* ws, size_t ws_bytes, float* out1, float* out2,
+                          float* out3, int first_stage, int last_stage, void* stream);
+/* One layer alone: kind 0 = Conv2d(k in {1, 3, 5}, stride in {1, 2}, padding k / 2), kind 1 = ConvTranspose2d(3, 2, 1, output_padding 1); no
+ * BatchNorm.  weight: PyTorch layout over c1 + c2 input channels; bias [cout] or NULL; x1 NHWC [n][h][w][c1], x2 NHWC [n][h][w][c2] (read as the
+ * channels after x1's; c2 = 0: none); res NHWC [n][ho][wo][cout] or NULL; out = relu?(conv + bias + res) NHWC.  cout in {16, 32, 64, 128}; c1 and c2
+ * multiples of 16, or c2 = 0, kind 0 and cout <= 32.  The workspace holds the packed weights (0 from the query: unsupported). */
+size_t mvsdf_featext_layer_workspace_bytes(int kind, int cin, int cout, int k, int stride);
+int mvsdf_featext_layer(int kind, const float* weight, const float* bias, int cout, int k, int stride, const float* x1, int c1, const float* x2, int c2,
+                        int64_t n, int64_t h, int64_t w, const float* res, int relu, void* ws, size_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,15 @@ def lib():
         L.mvsdf_chamfer_downsample.argtypes = [vp, i64, f64, u64, i64, vp, sz, vp, vp]
         L.mvsdf_chamfer_mask.argtypes = [vp, vp, i64, vp, i64, vp, f64, vp, vp, vp, vp, sz, vp, vp, vp, vp]
         L.mvsdf_chamfer_nearest.argtypes = [vp, i64, vp, i64, f64, vp, sz, vp, vp]
+        for fn in ('mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_layer_workspace_bytes'):
+            getattr(L, fn).restype = sz
+        L.mvsdf_featext_raw_floats.argtypes = []
+        L.mvsdf_featext_pack_bytes.argtypes = []
+        L.mvsdf_featext_pack.argtypes = [vp, vp, sz, vp]
+        L.mvsdf_featext_workspace_bytes.argtypes = [i64] * 3
+        L.mvsdf_featext_forward.argtypes = [vp, vp, i64, i64, i64, vp, sz, vp, vp, vp, C.c_int, C.c_int, vp]
+        L.mvsdf_featext_layer_workspace_bytes.argtypes = [C.c_int] * 5
+        L.mvsdf_featext_layer.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, i64, i64, i64, vp, C.c_int, vp, sz, vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -102,6 +111,8 @@ EXPORTS = [
     'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
+    'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
+    'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
 ]
 
 
