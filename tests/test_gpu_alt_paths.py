@@ -30,7 +30,13 @@ TARGETS = ['tests/test_gpu_diff.py', 'tests/test_gpu_idr.py::test_forward_loss_b
            'tests/test_gpu_idr.py::test_forward_loss_backward_vs_reference[idr_w256_tp03-loss_first]',
            # a skip connection into the LAST Linear (idr.py:46-49,86): the one layout the per-layer route treats apart (k_pe_adj_top, bcast_sqrt2)
            'tests/test_gpu_options.py::test_several_skip_connections[sdf_bwd_w64_skip8]',
-           'tests/test_gpu_idr.py::test_forward_loss_backward_vs_reference[idr_w64_skip8-outputs_first]']
+           'tests/test_gpu_idr.py::test_forward_loss_backward_vs_reference[idr_w64_skip8-outputs_first]'] + \
+    ['tests/test_gpu_diff_fp64.py::%s[%s]' % (t, a + p) for a in ('x3', 'f32') for t, p in (     # the float64 rule at partial tiles, row windows, chunk edges
+        ('test_sdf_forward', '-w300-M300-Mg17'), ('test_sdf_forward', '-w64-M4097-Mg4097'), ('test_sdf_backward', '-w100-M300-Mg300-r5-Mb17-dn'),
+        ('test_sdf_backward', '-w300-M300-Mg17-r5-Mb150-nodn'), ('test_sdf_backward', '-skip8-M300-Mg300-r100-Mb150-nodn'),
+        ('test_sdf_backward', '-w64-M300-Mg300-r0-Mb257-dn'), ('test_sdf_backward_pair_finish', '-w300-M300-X5+17-D17+200'),
+        ('test_render_forward_backward', '-w256-no_normal-f256-N17-ctx300'), ('test_render_forward_backward', '-w64-idr-f32-N257-ctx257'),
+        ('test_sdf_entry_points_ignore_unwritten_allocations', ''))]
 
 
 @pytest.mark.parametrize('env', [{'MVSDF_FUSE': '0'}, {'MVSDF_SPLIT_CHAINS': '1'}, {'MVSDF_CHAIN_W8': '1'}, {'MVSDF_CHAIN_MT': '2'}, {'MVSDF_DELTA_CHAIN': '1'},
