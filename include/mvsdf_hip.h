@@ -612,6 +612,42 @@ size_t mvsdf_featext_layer_workspace_bytes(int kind, int cin, int cout, int k, i
 int mvsdf_featext_layer(int kind, const float* weight, const float* bias, int cout, int k, int stride, const float* x1, int c1, const float* x2, int c2,
                         int64_t n, int64_t h, int64_t w, const float* res, int relu, void* ws, size_t ws_bytes, float* out, void* stream);
 
+
+/* ---- Training batches assembled on the device (batch_kernels.hip; Python: mvsdf_amd/datasets/device_batches.py) ----
+ * One launch builds the whole step batch of SceneDataset.__getitem__ + collate_fn (mvsdf_amd/datasets/scene_dataset.py) for B views from pools that
+ * stay on the device for the whole run: per view b (v = views[b]) and per sampled pixel p (id = pix[p], or p itself when pix is NULL: full images)
+ *   rgb[b][p][3] = rgb_pool[v][id][3]; uv[b][p] = (id mod img_w, id div img_w) as floats; object_mask[b][p] = omask_pool[v][id] (perfect_mask likewise,
+ *   skipped when either pointer is NULL); pose / intrinsics [b][4][4]; cam [b][2][4][4] = cams_hd[v]; src_cams [b][s] = cams_hd[src[v][s]];
+ *   depths [b][1][dh][dw] and depth_cams [b][2][4][4] of the view itself (sel_depth_num = 1); size [b] and center [b][3] = the scene's.
+ * The feature maps: feats is the [n][32][fh][fw] pool in channels-last storage ([n][fh][fw][32] in memory), feat [b] = feats[v] and
+ * feat_src [b][s] = feats[src[v][s]] in the same storage, i.e. one contiguous block of fmap_floats = 32 fh fw per map: copied with 16-byte loads and
+ * stores (every map pointer 16-byte aligned, fmap_floats a multiple of 4).  Masks are bytes (torch.bool); ids int64.  View and pixel ids outside
+ * the pools leave their outputs unwritten.  No host wait, no allocation. */
+typedef struct {
+    int B, n, num_src;
+    int64_t P, img_w, total_pixels, depth_floats, fmap_floats;
+    const int64_t* views;                /* [B] */
+    const int64_t* pix;                  /* [P], or NULL: P == total_pixels, the whole image */
+    const int64_t* src;                  /* [n][num_src] source views (pair.txt) */
+    const float* rgb;                    /* [n][total_pixels][3] */
+    const uint8_t* omask;                /* [n][total_pixels] */
+    const uint8_t* pmask;                /* [n][total_pixels] or NULL */
+    const float* pose;                   /* [n][4][4] */
+    const float* intrinsics;             /* [n][4][4] */
+    const float* cams_hd;                /* [n][2][4][4] */
+    const float* depth_cams;             /* [n][2][4][4] */
+    const float* depths;                 /* [n][depth_floats] */
+    const float* size;                   /* [1] */
+    const float* center;                 /* [3] */
+    const float* feats;                  /* [n][fmap_floats] */
+    float* o_rgb; float* o_uv; uint8_t* o_omask; uint8_t* o_pmask;
+    float* o_pose; float* o_intrinsics; float* o_cam; float* o_src_cams; float* o_depths; float* o_depth_cams; float* o_size; float* o_center;
+    float* o_feat;                       /* [B][fmap_floats] */
+    float* o_feat_src;                   /* [B][num_src][fmap_floats] */
+} MvsdfBatchArgs;
+size_t mvsdf_batch_args_bytes(void);     /* sizeof(MvsdfBatchArgs) as compiled: the binding checks its mirror against it */
+int mvsdf_batch_gather(const MvsdfBatchArgs* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

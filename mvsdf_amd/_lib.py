@@ -87,6 +87,9 @@ def lib():
         L.mvsdf_featext_forward.argtypes = [vp, vp, i64, i64, i64, vp, sz, vp, vp, vp, C.c_int, C.c_int, vp]
         L.mvsdf_featext_layer_workspace_bytes.argtypes = [C.c_int] * 5
         L.mvsdf_featext_layer.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, i64, i64, i64, vp, C.c_int, vp, sz, vp, vp]
+        L.mvsdf_batch_args_bytes.restype = sz
+        L.mvsdf_batch_args_bytes.argtypes = []
+        L.mvsdf_batch_gather.argtypes = [vp, vp]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -113,6 +116,7 @@ EXPORTS = [
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
+    'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',
 ]
 
 

@@ -64,3 +64,87 @@ def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None):
     if path is not None:
         mesh.export(os.path.join(path, 'surface_world_coordinates_{0}.obj'.format(epoch)))
     return mesh
+
+
+def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
+             eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print):
+    """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
+    -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
+    view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
+    -> {'epoch', 'evaldir', 'mesh', 'psnrs'}."""
+    from PIL import Image
+    from .checkpoint import MODEL_SUBDIR
+    from .datasets.device_batches import DeviceBatches
+    from .datasets.scene_dataset import SceneDataset
+    from .model.implicit_differentiable_renderer import IDRNetwork
+    from .utils.config import load_conf
+    torch.set_default_dtype(torch.float32)
+    conf = load_conf(conf)
+    expname = conf.get_string('train.expname') + '_' + expname
+    expdir = os.path.join(exps_root, exps_folder_name, expname)
+    if timestamp == 'latest':
+        timestamps = os.listdir(expdir) if os.path.exists(expdir) else []
+        if not timestamps:
+            raise FileNotFoundError('WRONG EXP FOLDER: no run under %s' % expdir)
+        timestamp = sorted(timestamps)[-1]
+    evaldir = os.path.join(exps_root, evals_folder_name, expname)
+    os.makedirs(evaldir, exist_ok=True)
+
+    model = IDRNetwork(conf=conf.get_config('model')).cuda()
+    dataset_conf = dict(conf.get_config('dataset')) if 'dataset' in conf else {}
+    if feat_ckpt is not None:
+        dataset_conf['feat_ckpt'] = feat_ckpt
+    dataset = SceneDataset(data_dir, False, **dataset_conf)
+    if eval_rendering and not hasattr(dataset, 'perfect_masks'):
+        raise ValueError('--eval_rendering needs the perfect masks of the scene (%s/pmask/): the PSNR is taken inside them (eval.py:137)' % data_dir)
+    scale_mat = dataset.get_scale_mat()
+    saved = torch.load(os.path.join(expdir, timestamp, 'checkpoints', MODEL_SUBDIR, str(checkpoint) + '.pth'), map_location='cuda')
+    model.load_state_dict(saved['model_state_dict'])
+    epoch = saved['epoch']
+    printer('evaluating...')
+    model.eval()
+    mesh = extract_world_mesh(model, scale_mat, resolution, path=evaldir, epoch=epoch)
+    psnrs = None
+    if eval_rendering:
+        images_dir = os.path.join(evaldir, 'rendering')
+        os.makedirs(images_dir, exist_ok=True)
+        batches = DeviceBatches(dataset, 1, -1)
+        psnrs = []
+        for i in range(len(dataset)):
+            _, model_input, ground_truth = batches.batch(torch.tensor([i]))
+            model_input['object_mask'] = model_input['perfect_mask']
+            p, images = evaluate_rendering(model, [(model_input, ground_truth)], dataset.img_res)
+            Image.fromarray((images[0] * 255).astype(np.uint8)).save(os.path.join(images_dir, 'eval_%03d.png' % i))
+            psnrs += p
+        arr = np.array(psnrs).astype(np.float64)
+        msg = 'RENDERING EVALUATION {2}: psnr mean = {0} ; psnr std = {1}'.format('%.2f' % arr.mean(), '%.2f' % arr.std(), expname)
+        printer(msg)
+        with open(os.path.join(evaldir, 'psnr.txt'), 'w') as f:
+            f.write(msg + '\n')
+    return {'epoch': epoch, 'evaldir': evaldir, 'mesh': mesh, 'psnrs': psnrs}
+
+
+def eval_parser():
+    import argparse
+    p = argparse.ArgumentParser(description='Evaluate a trained MVSDF run: world-coordinate mesh and, optionally, rendering PSNR (the reference\'s evaluation/eval.py).')
+    p.add_argument('--data_dir', type=str, default='fill_in_data_dir')
+    p.add_argument('--conf', type=str, default='./confs/mvsdf_dtu.conf')
+    p.add_argument('--expname', type=str, default='test', help='The experiment name to be evaluated.')
+    p.add_argument('--exps_folder', type=str, default='exps', help='The experiments folder name.')
+    p.add_argument('--gpu', type=str, default='auto', help='GPU to use: an index, or auto / ignore (the current device)')
+    p.add_argument('--timestamp', default='latest', type=str, help='The experiment timestamp to test.')
+    p.add_argument('--checkpoint', default='latest', type=str, help='The trained model checkpoint to test')
+    p.add_argument('--resolution', default=512, type=int, help='Grid resolution for marching cube')
+    p.add_argument('--eval_rendering', default=False, action='store_true', help='If set, evaluate rendering quality.')
+    p.add_argument('--exps_root', type=str, default='../', help='Directory that holds exps/ and evals/ (the reference uses ../).')
+    p.add_argument('--feat_ckpt', type=str, default=None, help='Vis-MVSNet checkpoint for the feature extractor (SceneDataset feat_ckpt).')
+    return p
+
+
+def main(argv=None, printer=print):
+    from .training import select_gpu
+    opt = eval_parser().parse_args(argv)
+    select_gpu(opt.gpu)
+    return evaluate(data_dir=opt.data_dir, conf=opt.conf, expname=opt.expname, exps_folder_name=opt.exps_folder, evals_folder_name='evals',
+                    timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
+                    exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer)
