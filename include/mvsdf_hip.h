@@ -541,6 +541,31 @@ int mvsdf_mesh_select(const int32_t* vert_label, const int32_t* face_label, int6
                       const float* colors, const int32_t* faces, void* ws, size_t ws_bytes, float* out_verts, float* out_normals, float* out_colors,
                       int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 
+/* ---- sparse mesh extraction (mesh_sparse.hip; Python: mesh.sparse_marching_cubes, whose doc states the contract) ----
+ * The marching-cubes mesh of the n^3 lattice (value at point (i, j, k) = sdf(axis[i], axis[j], axis[k]), axis: fp32 [n]) over the cells of the
+ * active blocks of B^3 cells only, in the dense path's vertex / face order.  The caller evaluates the SDF at the points these calls generate:
+ *   mvsdf_smc_coarse_points: points [start, start + count) of the (nb + 1)^3 block corners, nb = ceil((n - 1) / B), as fp32 [count][3];
+ *   mvsdf_smc_seed: the corner values -> seed blocks (corners on both sides of `level`, or one within `tol` of it), given slots 0 .. seeds - 1;
+ *   mvsdf_smc_brick_points: points [start, start + count) of the bricks, item slot * (B + 3)^3 + local (lattice indices b B - 1 + local, clamped);
+ *   mvsdf_smc_closure: values of the slots [slot0, slot0 + count) (values[slot * (B + 3)^3 + local]) -> inactive neighbours across a face with a
+ *     crossing grid edge get the next slots, from slot0 + count on;
+ *   mvsdf_smc_count / mvsdf_smc_emit: the values of all `nactive` slots -> the mesh (like mvsdf_mc_count / mvsdf_mc_emit).
+ * The workspace starts with int64 {last seed / closure count, 0, 0, non-finite value seen, closure flag stores, missing vertex owner (never expected),
+ * 0, 0, vertices, faces} (mvsdf_smc_count writes the last two): the caller reads the count after each seed / closure call and the totals after
+ * mvsdf_smc_count.  Workspace queries give 0 for n < 3, B < 2 (or > 1024) or sizes the kernels cannot index; the emit workspace holds (B + 1)^3
+ * int32 per active block. */
+size_t mvsdf_smc_workspace_bytes(int64_t n, int64_t block);
+size_t mvsdf_smc_emit_workspace_bytes(int64_t n, int64_t block, int64_t nactive);
+int mvsdf_smc_coarse_points(const float* axis, int64_t n, int64_t block, int64_t start, int64_t count, float* pts, void* stream);
+int mvsdf_smc_seed(const float* coarse, int64_t n, int64_t block, float level, float tol, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_smc_brick_points(const float* axis, int64_t n, int64_t block, const void* ws, size_t ws_bytes, int64_t start, int64_t count, float* pts,
+                           void* stream);
+int mvsdf_smc_closure(const float* values, int64_t n, int64_t block, float level, int64_t slot0, int64_t count, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_smc_count(const float* values, int64_t n, int64_t block, float level, int64_t nactive, void* ws, size_t ws_bytes, void* ews, size_t ews_bytes,
+                    void* stream);
+int mvsdf_smc_emit(const float* values, int64_t n, int64_t block, float level, const float* spacing, const float* origin, int64_t nactive, void* ws,
+                   size_t ws_bytes, void* ews, size_t ews_bytes, float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap, void* stream);
+
 /* ---- mesh trimming (mesh_cut.hip; Python: Mesh.cut_mask / Mesh.trim in mvsdf_amd/mesh.py, which states the semantics) ----
  * The minimum cut of reference code/mesh_cut/mesh_cut.py over the faces: S* = the faces reachable from the source in the residual graph of a maximum
  * flow (bright faces, red > thresh / 255 on average, tie to the source; faces sharing an edge are joined by 2 * smooth).  1 <= nv <= INT32_MAX,

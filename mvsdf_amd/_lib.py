@@ -61,6 +61,16 @@ def lib():
         L.mvsdf_mesh_cc_workspace_bytes.argtypes = [i64, i64]
         L.mvsdf_mesh_components.argtypes = [vp, vp, i64, i64, vp, C.c_size_t, vp, vp, vp]
         L.mvsdf_mesh_select.argtypes = [vp, vp, i64, i64, C.c_int32] + [vp] * 5 + [C.c_size_t] + [vp] * 4 + [i64, i64, vp]
+        L.mvsdf_smc_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_smc_workspace_bytes.argtypes = [i64, i64]
+        L.mvsdf_smc_emit_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_smc_emit_workspace_bytes.argtypes = [i64, i64, i64]
+        L.mvsdf_smc_coarse_points.argtypes = [vp, i64, i64, i64, i64, vp, vp]
+        L.mvsdf_smc_seed.argtypes = [vp, i64, i64, f32, f32, vp, C.c_size_t, vp]
+        L.mvsdf_smc_brick_points.argtypes = [vp, i64, i64, vp, C.c_size_t, i64, i64, vp, vp]
+        L.mvsdf_smc_closure.argtypes = [vp, i64, i64, f32, i64, i64, vp, C.c_size_t, vp]
+        L.mvsdf_smc_count.argtypes = [vp, i64, i64, f32, i64, vp, C.c_size_t, vp, C.c_size_t, vp]
+        L.mvsdf_smc_emit.argtypes = [vp, i64, i64, f32, vp, vp, i64, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, i64, i64, vp]
         L.mvsdf_mesh_cut_workspace_bytes.restype = C.c_size_t
         L.mvsdf_mesh_cut_workspace_bytes.argtypes = [i64, i64]
         L.mvsdf_mesh_cut.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp]
@@ -110,6 +120,8 @@ EXPORTS = [
     'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets',
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
     'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',
+    'mvsdf_smc_workspace_bytes', 'mvsdf_smc_emit_workspace_bytes', 'mvsdf_smc_coarse_points', 'mvsdf_smc_seed', 'mvsdf_smc_brick_points',
+    'mvsdf_smc_closure', 'mvsdf_smc_count', 'mvsdf_smc_emit',
     'mvsdf_mesh_cut_workspace_bytes', 'mvsdf_mesh_cut', 'mvsdf_mesh_trim',
     'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',

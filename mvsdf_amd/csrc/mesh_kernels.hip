@@ -11,16 +11,7 @@
 #include <string.h>
 #include "capi_util.h"
 
-#define MC_TABLE static __constant__ const
-#include "mc_tables.h"
-
-#define MESH_THREADS 256
-#define MESH_ROUNDS 4
-#define MESH_CHUNK (MESH_THREADS * MESH_ROUNDS)
-#define MESH_SCAN_THREADS 1024
-#define MESH_HDR 256                                  // bytes at the start of every workspace: int64 results the host reads
-
-static_assert(MC_MAX_TRIS < 8, "k_mc_* count triangles per cell with 3 ballots");
+#include "mesh_common.h"
 
 struct MeshVol {
     const float* p;
@@ -30,30 +21,11 @@ struct MeshVol {
 
 __device__ __forceinline__ float vat(const MeshVol& v, long long i, long long j, long long k) { return v.p[i * v.s[0] + j * v.s[1] + k * v.s[2]]; }
 
-// exclusive rank of x (0 <= x < 2^nbits) among the block's items so far, in item order; `running` (uniform) carries the block's total across rounds.
-// Every lane of the block calls it the same number of times.
-__device__ __forceinline__ long long block_excl(int x, int nbits, int* s_w, long long& running) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    int pre = 0, tot = 0;
-    for (int b = 0; b < nbits; ++b) {
-        const unsigned long long m = __ballot((x >> b) & 1);
-        pre += __popcll(m & lt) << b;
-        tot += __popcll(m) << b;
-    }
-    if (lane == 0) s_w[w] = tot;
-    __syncthreads();
-    long long base = running;
-    int all = 0;
-    for (int q = 0; q < MESH_THREADS / 64; ++q) {
-        const int t = s_w[q];
-        if (q < w) base += t;
-        all += t;
-    }
-    __syncthreads();
-    running += all;
-    return base + pre;
-}
+// the accessor of mesh_common.h's formulas
+struct VolVal {
+    const MeshVol& v;
+    __device__ __forceinline__ float operator()(long long i, long long j, long long k) const { return vat(v, i, j, k); }
+};
 
 __device__ __forceinline__ void point_ijk(const MeshVol& v, long long p, long long& i, long long& j, long long& k) {
     const long long nyz = v.n[1] * v.n[2];
@@ -65,20 +37,13 @@ __device__ __forceinline__ void point_ijk(const MeshVol& v, long long p, long lo
 
 // crossing edges owned by grid point (i, j, k): bit a = the edge to (i, j, k) + e_a crosses the level
 __device__ __forceinline__ int point_edges(const MeshVol& v, long long i, long long j, long long k, bool in0) {
-    int bits = 0;
-    if (i + 1 < v.n[0] && in0 != (vat(v, i + 1, j, k) < v.level)) bits |= 1;
-    if (j + 1 < v.n[1] && in0 != (vat(v, i, j + 1, k) < v.level)) bits |= 2;
-    if (k + 1 < v.n[2] && in0 != (vat(v, i, j, k + 1) < v.level)) bits |= 4;
-    return bits;
+    return mc_point_edges(VolVal{v}, v.n, i, j, k, in0, v.level);
 }
 
 // cube index of the cell with lower corner (i, j, k) (bit c: corner (c & 1, c >> 1 & 1, c >> 2 & 1) is inside); -1 if there is no such cell
 __device__ __forceinline__ int cell_index(const MeshVol& v, long long i, long long j, long long k) {
     if (i + 1 >= v.n[0] || j + 1 >= v.n[1] || k + 1 >= v.n[2]) return -1;
-    int ci = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) ci |= (vat(v, i + (c & 1), j + (c >> 1 & 1), k + (c >> 2 & 1)) < v.level) << c;
-    return ci;
+    return mc_cube_index(VolVal{v}, i, j, k, v.level);
 }
 
 // ---- marching cubes, pass 1: vertices and triangles per workgroup (bv / bf), or -1 in bf when the workgroup saw a non-finite value ----
@@ -96,7 +61,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_count(MeshVol v, long long 
             bad |= !isfinite(x);
             nv = __popc(point_edges(v, i, j, k, x < v.level));
             const int ci = cell_index(v, i, j, k);
-            if (ci >= 0) nt = mc_tri_offset[ci + 1] - mc_tri_offset[ci];
+            if (ci >= 0) nt = mc_ntri(ci);
         }
         block_excl(nv, 2, s_w, rv);
         block_excl(nt, 3, s_w, rf);
@@ -107,71 +72,6 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_count(MeshVol v, long long 
         bf[blockIdx.x] = bad ? -1 : (int)rf;
     }
 }
-
-// exclusive int64 offsets of one or two per-workgroup count arrays (b may be NULL) -> oa / ob; tot[0] / tot[1] = the sums, tot[2] = 1 if a count was negative
-__global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan(const int* __restrict__ a, const int* __restrict__ b, int nb, long long* __restrict__ oa,
-                                                                 long long* __restrict__ ob, long long* __restrict__ tot) {
-    __shared__ long long sa[MESH_SCAN_THREADS], sb[MESH_SCAN_THREADS];
-    __shared__ int s_bad;
-    const int t = threadIdx.x, per = (nb + MESH_SCAN_THREADS - 1) / MESH_SCAN_THREADS;
-    const int lo = min(nb, t * per), hi = min(nb, lo + per);
-    if (t == 0) s_bad = 0;
-    long long ta = 0, tb = 0;
-    int bad = 0;
-    for (int q = lo; q < hi; ++q) {
-        bad |= a[q] < 0 || (b && b[q] < 0);
-        ta += a[q];
-        if (b) tb += b[q];
-    }
-    sa[t] = ta;
-    sb[t] = tb;
-    __syncthreads();
-    if (bad) s_bad = 1;
-    for (int d = 1; d < MESH_SCAN_THREADS; d <<= 1) {         // inclusive Hillis-Steele scan
-        const long long xa = t >= d ? sa[t - d] : 0, xb = t >= d ? sb[t - d] : 0;
-        __syncthreads();
-        sa[t] += xa;
-        sb[t] += xb;
-        __syncthreads();
-    }
-    long long ra = sa[t] - ta, rb = sb[t] - tb;
-    for (int q = lo; q < hi; ++q) {
-        oa[q] = ra;
-        ra += a[q];
-        if (b) {
-            ob[q] = rb;
-            rb += b[q];
-        }
-    }
-    if (t == MESH_SCAN_THREADS - 1) {
-        tot[0] = sa[t];
-        tot[1] = sb[t];
-    }
-    __syncthreads();
-    if (t == 0) tot[2] = s_bad;
-}
-
-// gradient component c at grid point g: central difference inside, one-sided at the border, over the spacing
-__device__ __forceinline__ float grad_c(const MeshVol& v, const long long* g, int c, float h) {
-    const long long n = v.n[c], x = g[c];
-    if (n < 2) return 0.0f;
-    long long lo[3] = {g[0], g[1], g[2]}, hi[3] = {g[0], g[1], g[2]};
-    float den = h;
-    if (x == 0) {
-        hi[c] = 1;
-    } else if (x == n - 1) {
-        lo[c] = n - 2;
-    } else {
-        lo[c] = x - 1;
-        hi[c] = x + 1;
-        den = 2.0f * h;
-    }
-    return (vat(v, hi[0], hi[1], hi[2]) - vat(v, lo[0], lo[1], lo[2])) / den;
-}
-
-struct McGeom {
-    float sp[3], org[3];
-};
 
 // ---- pass 2: the vertex id map (id of each point's first vertex), vertices and normals ----
 __global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long long npts, McGeom gm, const long long* __restrict__ ov, int* __restrict__ idmap,
@@ -193,20 +93,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long lo
         idmap[p] = (int)id;
         for (int a = 0; a < 3; ++a) {
             if (!(bits >> a & 1)) continue;
-            if (id < nv_cap) {
-                long long g1[3] = {g[0], g[1], g[2]};
-                g1[a] += 1;
-                const float x1 = vat(v, g1[0], g1[1], g1[2]);
-                const float t = (v.level - x) / (x1 - x);
-                float n[3];
-                for (int c = 0; c < 3; ++c) {
-                    verts[id * 3 + c] = c == a ? gm.org[c] + ((float)g[c] + t) * gm.sp[c] : gm.org[c] + (float)g[c] * gm.sp[c];
-                    const float d0 = grad_c(v, g, c, gm.sp[c]), d1 = grad_c(v, g1, c, gm.sp[c]);
-                    n[c] = d0 + t * (d1 - d0);
-                }
-                const float nn = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-                for (int c = 0; c < 3; ++c) normals[id * 3 + c] = nn > 0.0f ? n[c] / nn : 0.0f;
-            }
+            if (id < nv_cap) mc_vertex(VolVal{v}, v.n, g, a, x, v.level, gm, verts + id * 3, normals + id * 3);
             ++id;
         }
     }
@@ -214,11 +101,8 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long lo
 
 // vertex id of cube edge e of the cell at (i, j, k): the owner's first id plus its crossing edges along lower axes
 __device__ __forceinline__ int edge_vertex(const MeshVol& v, const int* __restrict__ idmap, long long i, long long j, long long k, int e) {
-    const int a = e >> 2, m = e & 3;
-    const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;         // the two other axes, lower first
     long long q[3] = {i, j, k};
-    q[o0] += m & 1;
-    q[o1] += m >> 1 & 1;
+    const int a = mc_edge_owner(e, q);
     const bool in0 = vat(v, q[0], q[1], q[2]) < v.level;
     const int bits = point_edges(v, q[0], q[1], q[2], in0);
     return idmap[(q[0] * v.n[1] + q[1]) * v.n[2] + q[2]] + __popc(bits & ((1 << a) - 1));
@@ -236,7 +120,7 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_faces(MeshVol v, long long 
         if (p < npts) {
             point_ijk(v, p, i, j, k);
             ci = cell_index(v, i, j, k);
-            if (ci >= 0) nt = mc_tri_offset[ci + 1] - mc_tri_offset[ci];
+            if (ci >= 0) nt = mc_ntri(ci);
         }
         const long long fid = block_excl(nt, 3, s_w, run);
         for (int t = 0; t < nt; ++t) {

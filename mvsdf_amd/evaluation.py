@@ -53,11 +53,13 @@ def evaluate_rendering(model, batches, img_res, n_pixels=10000):
     return psnrs, images
 
 
-def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None):
+def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None, sparse=False, block=None, margin=None):
     """eval.py:109-125 with eval_cameras off: the SDF mesh on the device (mesh.surface_mesh), moved to world coordinates by scale_mat, reduced to its
-    largest connected component; with `path`, written as <path>/surface_world_coordinates_<epoch>.obj.  -> the Mesh, or None if no surface."""
-    from .mesh import surface_mesh
-    mesh = surface_mesh(model, resolution)
+    largest connected component; with `path`, written as <path>/surface_world_coordinates_<epoch>.obj.  -> the Mesh, or None if no surface.
+    sparse=True: the mesh from mesh.sparse_marching_cubes (blocks of `block`^3 cells, `margin`; None: mesh.SPARSE_BLOCK / SPARSE_MARGIN)."""
+    from . import mesh as M
+    mesh = M.surface_mesh(model, resolution, sparse=sparse, block=M.SPARSE_BLOCK if block is None else block,
+                          margin=M.SPARSE_MARGIN if margin is None else margin)
     if mesh is None:
         return None
     mesh = mesh.apply_transform(scale_mat).largest_component()
@@ -67,11 +69,11 @@ def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None):
 
 
 def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
-             eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print):
+             eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None):
     """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
     -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
     view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
-    -> {'epoch', 'evaldir', 'mesh', 'psnrs'}."""
+    sparse_mesh / mesh_block / mesh_margin: extract_world_mesh's sparse / block / margin.  -> {'epoch', 'evaldir', 'mesh', 'psnrs'}."""
     from PIL import Image
     from .checkpoint import MODEL_SUBDIR
     from .datasets.device_batches import DeviceBatches
@@ -103,7 +105,7 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     epoch = saved['epoch']
     printer('evaluating...')
     model.eval()
-    mesh = extract_world_mesh(model, scale_mat, resolution, path=evaldir, epoch=epoch)
+    mesh = extract_world_mesh(model, scale_mat, resolution, path=evaldir, epoch=epoch, sparse=sparse_mesh, block=mesh_block, margin=mesh_margin)
     psnrs = None
     if eval_rendering:
         images_dir = os.path.join(evaldir, 'rendering')
@@ -138,6 +140,11 @@ def eval_parser():
     p.add_argument('--eval_rendering', default=False, action='store_true', help='If set, evaluate rendering quality.')
     p.add_argument('--exps_root', type=str, default='../', help='Directory that holds exps/ and evals/ (the reference uses ../).')
     p.add_argument('--feat_ckpt', type=str, default=None, help='Vis-MVSNet checkpoint for the feature extractor (SceneDataset feat_ckpt).')
+    p.add_argument('--sparse_mesh', default=False, action='store_true',
+                   help='Extract the mesh from the SDF evaluated only in blocks near the surface (the same mesh as the dense grid when every surface '
+                        'component reaches a seed block; mesh.sparse_marching_cubes).')
+    p.add_argument('--mesh_block', default=8, type=int, help='With --sparse_mesh: the block edge in grid cells.')
+    p.add_argument('--mesh_margin', default=0.5, type=float, help='With --sparse_mesh: the Lipschitz bound assumed of the SDF when seeding blocks.')
     return p
 
 
@@ -147,4 +154,5 @@ def main(argv=None, printer=print):
     select_gpu(opt.gpu)
     return evaluate(data_dir=opt.data_dir, conf=opt.conf, expname=opt.expname, exps_folder_name=opt.exps_folder, evals_folder_name='evals',
                     timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
-                    exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer)
+                    exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer, sparse_mesh=opt.sparse_mesh, mesh_block=opt.mesh_block,
+                    mesh_margin=opt.mesh_margin)

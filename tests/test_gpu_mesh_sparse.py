@@ -1,0 +1,225 @@
+"""Sparse mesh extraction over surface bricks (mvsdf_amd/mesh.py sparse_marching_cubes, csrc/mesh_sparse.hip) against the dense path
+(marching_cubes of the full volume, surface_mesh) bit for bit, and against the numpy restatement tests/smc_ref.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import mc_ref
+import smc_ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+# ---- analytic SDFs as torch expressions (pointwise: a point's value does not depend on its batch) ----
+def sphere(c=(0.0, 0.0, 0.0), r=0.6):
+    def f(p):
+        return torch.sqrt((p[:, 0] - c[0]) ** 2 + (p[:, 1] - c[1]) ** 2 + (p[:, 2] - c[2]) ** 2) - r
+    return f
+
+
+def union(*fs):
+    def f(p):
+        out = fs[0](p)
+        for g in fs[1:]:
+            out = torch.minimum(out, g(p))
+        return out
+    return f
+
+
+def three_spheres():
+    return union(sphere((-0.55, 0.0, 0.0), 0.25), sphere((0.2, 0.3, 0.0), 0.35), sphere((0.35, -0.55, 0.3), 0.2))
+
+
+def torus(R=0.5, r=0.18):
+    def f(p):
+        q = torch.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2) - R
+        return torch.sqrt(q * q + p[:, 2] ** 2) - r
+    return f
+
+
+def grid_box(n):
+    """a box whose faces lie ON grid planes of the n-lattice: values exactly 0 there (Chebyshev distance, exact in fp32)"""
+    x, _ = smc_ref.lattice(n)
+    half = [abs(float(x[int(round(t * (n - 1)))])) for t in (0.25, 0.35, 0.15)]
+
+    def f(p):
+        return torch.maximum(torch.maximum(p[:, 0].abs() - half[0], p[:, 1].abs() - half[1]), p[:, 2].abs() - half[2])
+    return f
+
+
+def periodic(k=7.0):
+    """many blobs (Lipschitz <= sqrt(3)): seeded with margin 2"""
+    def f(p):
+        return (torch.cos(k * p[:, 0]) + torch.cos(k * p[:, 1]) + torch.cos(k * p[:, 2]) - 1.5) / k
+    return f
+
+
+FIELDS = {'sphere': (lambda n: sphere((0.013, -0.021, 0.017)), 1.0), 'three_spheres': (lambda n: three_spheres(), 1.0),
+          'torus': (lambda n: torus(), 1.0), 'box': (grid_box, 1.0), 'periodic': (lambda n: periodic(), 2.0)}
+
+
+def _dense(f, n, level=0.0):
+    """the dense path on the same lattice: plots.sdf_on_uniform_grid_device's volume (as surface_volume_device lays it out), marching_cubes"""
+    from mvsdf_amd import mesh as M
+    from mvsdf_amd.utils import plots
+    x = np.linspace(-1.0, 1.0, n)
+    vol = plots.sdf_on_uniform_grid_device(f, n).view(n, n, n).permute(1, 0, 2)
+    return M.marching_cubes(vol, level, (x[2] - x[1],) * 3, (x[0],) * 3), vol
+
+
+def _same(a, b):
+    assert a is not None and b is not None
+    for x, y, what in [(a.vertices, b.vertices, 'vertices'), (a.normals, b.normals, 'normals'), (a.faces, b.faces, 'faces')]:
+        assert x.shape == y.shape and torch.equal(x, y), what
+
+
+@pytest.mark.parametrize('name', sorted(FIELDS))
+@pytest.mark.parametrize('n', [3, 33, 64, 129, 257])
+def test_analytic_fields_equal_the_dense_mesh(name, n):
+    from mvsdf_amd import mesh as M
+    make, margin = FIELDS[name]
+    f = make(n)
+    dense, vol = _dense(f, n)
+    x, h = smc_ref.lattice(n)
+    for B in (2, 3, 8, 16):
+        st = {}
+        sp = M.sparse_marching_cubes(f, n, block=B, margin=margin, stats=st)
+        if dense is None:
+            assert sp is None
+            continue
+        _same(sp, dense)
+        nb = smc_ref.blocks(n, B)
+        assert st['points_evaluated'] == (nb + 1) ** 3 + st['active_blocks'] * (B + 3) ** 3
+        if n <= 129 and (n <= 64 or B == 8):
+            v, fc, nr, info = smc_ref.sparse_marching_cubes(_np(vol), B, 0.0, margin, h, (h,) * 3, (x[0],) * 3)
+            assert np.array_equal(_np(sp.vertices), v) and np.array_equal(_np(sp.faces), fc)
+            assert np.abs(_np(sp.normals) - nr).max() <= 1e-6
+            assert (st['seeds'], st['active_blocks'], st['closure_rounds']) == (info['seeds'], info['active_blocks'], info['rounds'])
+
+
+def _model(W, trace_dtype=None):
+    from mvsdf_amd.model.implicit_differentiable_renderer import IDRNetwork
+    from mvsdf_amd.utils import synth
+    from mvsdf_amd.utils.config import ConfigDict
+    m = IDRNetwork(ConfigDict(synth.model_conf(W)))
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(W, 0).items()})
+    m = m.cuda().eval()
+    if trace_dtype is not None:
+        m.implicit_network.trace_dtype = trace_dtype
+    return m
+
+
+@pytest.mark.parametrize('dtype', ['f32x3', 'f32'])
+@pytest.mark.parametrize('W', [64, 256])
+def test_synthetic_models_equal_the_dense_mesh(W, dtype):
+    from mvsdf_amd import mesh as M
+    m = _model(W, dtype)
+    for n in (100, 128, 257):
+        dense = M.surface_mesh(m, n)
+        sp = M.surface_mesh(m, n, sparse=True)
+        _same(sp, dense)
+        assert torch.equal(sp.vertex_colors, dense.vertex_colors)
+
+
+def test_closure_reaches_grazed_blocks():
+    from mvsdf_amd import mesh as M
+    n, B = 129, 16
+    f = sphere((0.0, 0.125, 0.125), 0.51)                               # smc_ref.grazing_sphere_volume as a torch expression
+    dense, vol = _dense(f, n)
+    _, h = smc_ref.lattice(n)
+    seeds = smc_ref.seed_blocks(_np(vol), B, 0.0, 0.0, h)
+    active, rounds = smc_ref.closure(seeds, _np(vol), B, 0.0)
+    assert active.sum() > seeds.sum()                                  # blocks with every corner outside that hold surface
+    st = {}
+    sp = M.sparse_marching_cubes(f, n, block=B, margin=0.0, stats=st)
+    assert st['active_blocks'] > st['seeds'] and st['closure_rounds'] == rounds >= 2 and st['closure_stores'] >= 1
+    assert (st['seeds'], st['active_blocks']) == (int(seeds.sum()), int(active.sum()))
+    _same(sp, dense)
+
+
+def test_missed_component_contract():
+    from mvsdf_amd import mesh as M
+    n, B = 129, 16
+    x, h = smc_ref.lattice(n)
+    c = float(x[5 * B + B // 2]) + 0.3 * h                              # inside block (5, 5, 5), away from its corners
+    f = union(sphere((-0.3, -0.2, 0.1), 0.45), sphere((c, c, c), 0.3 * B * h))
+    dense, vol = _dense(f, n)
+    v, fc = _np(dense.vertices), _np(dense.faces).astype(np.int64)
+    labels, count = mc_ref.components(fc, len(v))
+    assert count == 2
+    tiny = labels[np.argmax(np.linalg.norm(v[fc[:, 0]] - c, axis=1) < 0.5 * B * h)]
+    sp = M.sparse_marching_cubes(f, n, block=B, margin=0.0)
+    wv, wf, wn = smc_ref.select_faces(v, fc, _np(dense.normals), labels != tiny)
+    assert np.array_equal(_np(sp.vertices), wv) and np.array_equal(_np(sp.faces), wf) and np.array_equal(_np(sp.normals), wn)
+    _same(M.sparse_marching_cubes(f, n, block=B, margin=1.0), dense)
+
+
+def test_edge_cases():
+    from mvsdf_amd import mesh as M
+    assert M.sparse_marching_cubes(lambda p: torch.ones(p.shape[0], device=p.device), 40, block=8) is None
+    assert M.sparse_marching_cubes(lambda p: -torch.ones(p.shape[0], device=p.device), 40, block=8) is None
+    assert M.sparse_marching_cubes(sphere((0.0, 0.0, 0.0), 0.6), 64, level=-5.0) is None
+
+    def nan_near_surface(p):
+        d = sphere()(p)
+        return torch.where((p - torch.tensor([0.6, 0.0, 0.0], device=p.device)).norm(dim=1) < 0.05, torch.full_like(d, float('nan')), d)
+    with pytest.raises(ValueError, match='non-finite'):
+        M.sparse_marching_cubes(nan_near_surface, 64, block=8)
+    st = {}
+    sp = M.sparse_marching_cubes(sphere(), 257, margin=0.0, stats=st)                # the bricks the surface and the closure need
+    assert sp is not None and st['points_evaluated'] < 0.25 * 257 ** 3
+    assert set(st) >= {'seeds', 'active_blocks', 'closure_rounds', 'points_evaluated', 'workspace_bytes'}
+
+
+def test_sphere_1024_equals_the_dense_mesh():
+    from mvsdf_amd import mesh as M
+    f = sphere((0.013, -0.021, 0.017), 0.6)
+    dense, vol = _dense(f, 1024)
+    del vol
+    sp = M.sparse_marching_cubes(f, 1024)
+    _same(sp, dense)
+
+
+def test_sphere_2048_sparse_only():
+    from mvsdf_amd import mesh as M
+    n, r = 2048, 0.6
+    st = {}
+    sp = M.sparse_marching_cubes(sphere((0.0, 0.0, 0.0), r), n, stats=st)
+    _, h = smc_ref.lattice(n)
+    v, f = sp.vertices.double(), sp.faces.long()
+    assert abs(sp.area() / (4 * np.pi * r * r) - 1) < 5e-3
+    p = v[f]
+    vol = float(torch.einsum('ij,ij->i', p[:, 0], torch.linalg.cross(p[:, 1], p[:, 2])).sum()) / 6.0
+    assert abs(vol / (4 / 3 * np.pi * r ** 3) - 1) < 5e-3
+    assert float((v.norm(dim=1) - r).abs().max()) < 0.02 * h
+    assert st['points_evaluated'] < 0.05 * n ** 3, st
+
+
+def test_eval_command_sparse_obj_equals_dense(tmp_path):
+    import train_scene
+    from mvsdf_amd import evaluation
+    from mvsdf_amd.checkpoint import MODEL_SUBDIR
+    from mvsdf_amd.model.implicit_differentiable_renderer import IDRNetwork
+    from mvsdf_amd.utils import synth
+    from mvsdf_amd.utils.config import ConfigDict
+    scene = train_scene.write_scene(tmp_path / 'dtu', 3, pmask=False)
+    conf = train_scene.write_conf(tmp_path / 'test.conf')
+    m = IDRNetwork(ConfigDict(synth.model_conf(64)))
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(64, 0).items()})
+    ck = tmp_path / 'exps' / 'mvsdf_sp' / '2026_01_01_00_00_00' / 'checkpoints' / MODEL_SUBDIR
+    os.makedirs(ck)
+    torch.save({'epoch': 5, 'model_state_dict': m.state_dict()}, str(ck / 'latest.pth'))
+    args = ['--data_dir', scene[0], '--conf', conf, '--expname', 'sp', '--exps_root', str(tmp_path), '--feat_ckpt', scene[1], '--resolution', '64',
+            '--gpu', 'ignore']
+    obj = tmp_path / 'evals' / 'mvsdf_sp' / 'surface_world_coordinates_5.obj'
+    evaluation.main(args, printer=lambda *a: None)
+    dense = obj.read_bytes()
+    os.remove(str(obj))
+    evaluation.main(args + ['--sparse_mesh'], printer=lambda *a: None)
+    assert len(dense) > 1000 and obj.read_bytes() == dense
