@@ -614,6 +614,22 @@ size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr);
 int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs, int64_t nr, double max_dist, void* ws, size_t ws_bytes, double* dist,
                           void* stream);
 
+/* ---- Depth-map fusion (fusion.hip; Python: mvsdf_amd/fusion.py, which states the definition) ----
+ * Two calls.  mvsdf_fusion_fuse validates every argument on the host, then (no host wait) writes masked[V][H][W], fused[V][H][W], counts[V][H][W]
+ * and leaves int64 {points kept, error bits} at the start of the workspace.  Error bits: 1 a non-finite matrix or threshold, 2 a pair index outside
+ * [0, V), 4 view < 1, 8 shapes (V < 1, H or W < 2, V*H*W > 2^40, H*W > INT32_MAX, a pair list longer than view); with any set nothing is launched.
+ * depths fp32 [V][H][W] and probs fp32 [V][3][H][W] (or NULL) on the device; pthresh: HOST fp32 [3]; pair_off: HOST int32 [V + 1] (pair_off[0] = 0),
+ * pair_src: HOST int32 [pair_off[V]], the source views of every view already cut to its first `view` entries; mats: HOST fp64, per pair slot T_rs
+ * then T_sr (row-major 4x4 each), followed by Pinv of every view.  The host arrays must stay alive until the caller has read the header.
+ * mvsdf_fusion_emit (same workspace, same V, H, W, npairs = pair_off[V]) writes the kept pixels in (view, y, x) order: points fp64 [cap][3],
+ * colors uint8 [cap][3] from images uint8 [V][H][W][3] (both NULL: no colours), view / pixel int32 [cap]; rows at or beyond cap are not written. */
+size_t mvsdf_fusion_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t npairs);
+int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthresh, int64_t V, int64_t H, int64_t W, const int32_t* pair_off,
+                      const int32_t* pair_src, const double* mats, int32_t view, int32_t vthresh, double pix_thresh, double dep_thresh, void* ws,
+                      size_t ws_bytes, float* masked, float* fused, int32_t* counts, void* stream);
+int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, int64_t npairs, void* ws, size_t ws_bytes, double* points,
+                      uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
+
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.
  * raw: fp32 [mvsdf_featext_raw_floats()] on the device, the layers in the order of mvsdf_amd/features.py::LAYERS, each its weight in PyTorch layout

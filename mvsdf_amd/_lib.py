@@ -88,6 +88,11 @@ def lib():
         L.mvsdf_chamfer_downsample.argtypes = [vp, i64, f64, u64, i64, vp, sz, vp, vp]
         L.mvsdf_chamfer_mask.argtypes = [vp, vp, i64, vp, i64, vp, f64, vp, vp, vp, vp, sz, vp, vp, vp, vp]
         L.mvsdf_chamfer_nearest.argtypes = [vp, i64, vp, i64, f64, vp, sz, vp, vp]
+        i32 = C.c_int32
+        L.mvsdf_fusion_workspace_bytes.restype = sz
+        L.mvsdf_fusion_workspace_bytes.argtypes = [i64] * 4
+        L.mvsdf_fusion_fuse.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, f64, f64, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_fusion_emit.argtypes = [vp, i64, i64, i64, i64, vp, sz, vp, vp, vp, vp, i64, vp]
         for fn in ('mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_layer_workspace_bytes'):
             getattr(L, fn).restype = sz
         L.mvsdf_featext_raw_floats.argtypes = []
@@ -126,6 +131,7 @@ EXPORTS = [
     'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
+    'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',

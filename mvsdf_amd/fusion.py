@@ -1,0 +1,183 @@
+"""Depth-map fusion on the device: step 1 of the reference's BYOD.md (the author's separate pcd-fusion script: probability filter, geometric
+consistency between a view and its source views, averaged depth, back-projection to one coloured cloud all_torch.ply).  Kernels:
+csrc/fusion.hip (the design: DESIGN.md); tests/fusion_ref.py restates every step in numpy.
+
+Inputs: cams fp64 [V,2,4,4] as utils.io.load_cam returns them, depths fp32 [V,H,W], probs fp32 [V,3,H,W] or None, pairs a list of V lists of
+view indices (nearest first), images uint8 [V,H,W,3] at depth-map size or None.
+
+The definition (fp64 throughout, in the order written, no FMA contraction; fp32 inputs are promoted exactly):
+
+- Matrices (host, numpy fp64, passed to the kernels as data).  P_v = K4_v @ E_v with E_v = cams[v,0] and K4_v the 4x4 identity with
+  cams[v,1,:3,:3] in its corner; Pinv_v = np.linalg.inv(P_v); T_rs = P_s @ Pinv_r.  A matrix-vector product is, per row,
+  ((t0*q0 + t1*q1) + t2*q2) + t3*q3.
+- Pixel convention: the reference's (my_utils.get_pixel_grids, grid_sample(align_corners=False)): pixel (x, y) sits at image coordinate
+  (x + 0.5, y + 0.5).
+- Step 1, probability mask.  m = (prob1 > fp32(t1)) & (prob2 > fp32(t2)) & (prob3 > fp32(t3)) & isfinite(depth) & (depth > 0) (fp32 compares,
+  as vismvsnet2mvsdf.py:53); probs=None: only the depth conditions.  masked_depth = depth where m, else 0.  Everything below reads masked depths.
+- Step 2, per reference pixel with d = masked_depth > 0 and per source s among the first `view` entries of pairs[r], in that order:
+  X = x + 0.5, Y = y + 0.5; p = T_rs (X*d, Y*d, d, 1); reject unless p2 > 0; u = p0/p2 - 0.5, v = p1/p2 - 0.5; reject unless 0 <= u <= W-1 and
+  0 <= v <= H-1; x0 = min(floor(u), W-2), y0 likewise, fx = u - x0, fy = v - y0; the four texels d00 d01 / d10 d11 of the source's masked depth
+  at rows y0, y0+1 and columns x0, x0+1 must all be > 0, else reject (a hole never bleeds a zero into a depth);
+  ds = (d00*(1-fx) + d01*fx)*(1-fy) + (d10*(1-fx) + d11*fx)*fy; b = T_sr ((u+0.5)*ds, (v+0.5)*ds, ds, 1); reject unless b2 > 0;
+  ex = b0/b2 - X, ey = b1/b2 - Y, zr = b2.  The source is consistent iff ex*ex + ey*ey < pix_thresh*pix_thresh and |zr - d| < dep_thresh * d.
+  (H or W below 2: ValueError.)
+- Step 3.  n = number of consistent sources (counts); the pixel is kept iff n >= vthresh; df = (d + zr_1 + zr_2 + ...) / (n + 1), the consistent
+  sources' zr added in pair order; fused_depth = fp32(df) if kept else 0.
+- Step 4.  The point of a kept pixel is rows 0..2 of Pinv_r (X*df, Y*df, df, 1); its colour is images[r, y, x].  Points come out in
+  (view, y, x) order.  bbox() is the exact min / max per axis.
+
+Not built: normals (BYOD.md passes --no_normal), voxel down-sampling (--downsample -1), the script's median fusion, --show_result.  The script's
+text is not available to this project, so its agreement with this definition beyond BYOD.md's description is not claimed.
+"""
+import numpy as np
+import torch
+
+from ._lib import check, lib, MvsdfError
+from .mesh import _header, _stream, _vp
+
+
+class Fused:
+    """The result of fuse_depths: points fp64 [N,3] (world), colors uint8 [N,3] or None, view int32 [N], pixel int32 [N] (y*W + x),
+    masked_depths fp32 [V,H,W], fused_depths fp32 [V,H,W] (0 where rejected), counts int32 [V,H,W]; all on the device."""
+
+    def __init__(self, points, colors, view, pixel, masked_depths, fused_depths, counts):
+        self.points, self.colors, self.view, self.pixel = points, colors, view, pixel
+        self.masked_depths, self.fused_depths, self.counts = masked_depths, fused_depths, counts
+
+    def __len__(self):
+        return self.points.shape[0]
+
+    def bbox(self):
+        """(lo, hi): the exact minimum / maximum of the points per axis, fp64 [3] each on the device (NaN for an empty cloud)"""
+        if len(self) == 0:
+            nan = torch.full((3,), float('nan'), dtype=torch.float64, device=self.points.device)
+            return nan, nan.clone()
+        return self.points.amin(0), self.points.amax(0)
+
+
+def projection_matrices(cams):
+    """-> (P, Pinv) fp64 numpy [V,4,4] of the definition's matrices"""
+    cams = np.asarray(cams, dtype=np.float64)
+    P, Pinv = np.empty((len(cams), 4, 4)), np.empty((len(cams), 4, 4))
+    for v, cam in enumerate(cams):                                          # one 2-d product / inverse at a time, as the definition writes them
+        K4 = np.eye(4)
+        K4[:3, :3] = cam[1, :3, :3]
+        P[v] = K4 @ cam[0]
+        Pinv[v] = np.linalg.inv(P[v])
+    return P, Pinv
+
+
+def _errors(err, what):
+    if err & 1:
+        raise ValueError('%s: a camera entry or a threshold is NaN or infinite' % what)
+    if err & 2:
+        raise ValueError('%s: a pair index is outside [0, V)' % what)
+    if err & 4:
+        raise ValueError('%s: view must be >= 1' % what)
+    if err & 8:
+        raise ValueError('%s: shapes disagree or are out of range (V >= 1, H and W >= 2)' % what)
+    if err:
+        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+
+
+def fuse_depths(cams, depths, pairs, probs=None, images=None, pthresh=(0.8, 0.7, 0.8), view=10, vthresh=2, pix_thresh=1.0, dep_thresh=0.01):
+    """The module's definition -> Fused.  Device tensors are used where they are (the stream is theirs); numpy / CPU input is copied to the GPU."""
+    what = 'fuse_depths'
+    d = torch.as_tensor(depths)
+    if d.dim() != 3:
+        raise ValueError('%s: depths must be [V, H, W], got shape %s' % (what, tuple(d.shape)))
+    V, H, W = d.shape
+    dev = d.device if d.is_cuda else torch.device('cuda')
+    cams = np.asarray(cams.cpu() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
+    if cams.shape != (V, 2, 4, 4):
+        raise ValueError('%s: cams must be [V, 2, 4, 4] for V = %d depth maps, got shape %s' % (what, V, cams.shape))
+    if len(pairs) != V:
+        raise ValueError('%s: pairs must hold one list per view (%d), got %d' % (what, V, len(pairs)))
+    if H < 2 or W < 2 or V < 1:
+        raise ValueError('%s: depth maps must be at least 2 x 2 (and V >= 1), got %d views of %d x %d' % (what, V, H, W))
+    view, vthresh = int(view), int(vthresh)
+    if view < 1:
+        raise ValueError('%s: view must be >= 1' % what)
+    if not np.isfinite(cams).all():
+        raise ValueError('%s: a camera entry is NaN or infinite' % what)
+    th = np.asarray([float(pix_thresh), float(dep_thresh)])
+    if not np.isfinite(th).all():
+        raise ValueError('%s: pix_thresh and dep_thresh must be finite' % what)
+    pairs = [[int(s) for s in p][:view] for p in pairs]
+    if any(s < 0 or s >= V for p in pairs for s in p):
+        raise ValueError('%s: a pair index is outside [0, %d)' % (what, V))
+    p = None
+    if probs is not None:
+        p = torch.as_tensor(probs)
+        if tuple(p.shape) != (V, 3, H, W):
+            raise ValueError('%s: probs must be [V, 3, H, W] = %s, got shape %s' % (what, (V, 3, H, W), tuple(p.shape)))
+        p = p.to(dev, torch.float32).contiguous()
+    img = None
+    if images is not None:
+        img = torch.as_tensor(images)
+        if tuple(img.shape) != (V, H, W, 3) or img.dtype != torch.uint8:
+            raise ValueError('%s: images must be uint8 [V, H, W, 3] = %s, got %s %s' % (what, (V, H, W, 3), img.dtype, tuple(img.shape)))
+        img = img.to(dev).contiguous()
+    d = d.to(dev, torch.float32).contiguous()
+    try:
+        P, Pinv = projection_matrices(cams)
+    except np.linalg.LinAlgError as e:
+        raise ValueError('%s: a camera has a singular projection' % what) from e
+    off = np.zeros(V + 1, np.int32)
+    off[1:] = np.cumsum([len(q) for q in pairs])
+    src = np.asarray([s for q in pairs for s in q], np.int32)
+    npairs = len(src)
+    mats = np.empty(npairs * 32 + V * 16, np.float64)
+    k = 0
+    for r, q in enumerate(pairs):                                           # T_rs, T_sr per pair slot
+        for s in q:
+            mats[k * 32:k * 32 + 16] = (P[s] @ Pinv[r]).reshape(-1)
+            mats[k * 32 + 16:k * 32 + 32] = (P[r] @ Pinv[s]).reshape(-1)
+            k += 1
+    mats[npairs * 32:] = Pinv.reshape(-1)
+    pt = np.asarray(pthresh, np.float32).reshape(3)
+    size = lib().mvsdf_fusion_workspace_bytes(V, H, W, npairs)
+    if size == 0:
+        raise ValueError('%s: %d views of %d x %d are beyond the limits (V*H*W <= 2^40, H*W < 2^31)' % (what, V, H, W))
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    masked = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    fused = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    counts = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    st = _stream(d)
+    check(lib().mvsdf_fusion_fuse(_vp(d), _vp(p), pt.ctypes.data, V, H, W, off.ctypes.data, src.ctypes.data if npairs else None, mats.ctypes.data,
+                                  view, vthresh, float(pix_thresh), float(dep_thresh), _vp(ws), size, _vp(masked), _vp(fused), _vp(counts), st),
+          'mvsdf_fusion_fuse')
+    total, err = _header(ws, 2)                                             # the one wait of the call; off / src / mats / pt live until here
+    _errors(err, what)
+    points = torch.empty(total, 3, dtype=torch.float64, device=dev)
+    colors = torch.empty(total, 3, dtype=torch.uint8, device=dev) if img is not None else None
+    vw = torch.empty(total, dtype=torch.int32, device=dev)
+    px = torch.empty(total, dtype=torch.int32, device=dev)
+    if total:
+        check(lib().mvsdf_fusion_emit(_vp(img), V, H, W, npairs, _vp(ws), size, _vp(points), _vp(colors), _vp(vw), _vp(px), total, st),
+              'mvsdf_fusion_emit')
+    return Fused(points, colors, vw, px, masked, fused, counts)
+
+
+def save_points(path, points, colors=None):
+    """A binary little-endian PLY point cloud: float x y z (+ uchar red green blue); chamfer.load_points reads it back."""
+    pts = torch.as_tensor(points).detach().cpu().numpy() if isinstance(points, torch.Tensor) else np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError('save_points: points must be [N, 3], got shape %s' % (pts.shape,))
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    head = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % len(pts)] + ['property float %s' % k for k in 'xyz']
+    if colors is not None:
+        col = torch.as_tensor(colors).detach().cpu().numpy() if isinstance(colors, torch.Tensor) else np.asarray(colors)
+        if col.shape != pts.shape or col.dtype != np.uint8:
+            raise ValueError('save_points: colors must be uint8 [N, 3] for N points')
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        head += ['property uchar red', 'property uchar green', 'property uchar blue']
+    vert = np.empty(len(pts), dtype=fields)
+    for i, k in enumerate('xyz'):
+        vert[k] = pts[:, i]
+    if colors is not None:
+        for i, k in enumerate(('red', 'green', 'blue')):
+            vert[k] = col[:, i]
+    with open(path, 'wb') as fh:
+        fh.write('\n'.join(head + ['end_header', '']).encode('ascii'))
+        fh.write(vert.tobytes())
