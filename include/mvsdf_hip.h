@@ -332,17 +332,24 @@ int mvsdf_dsurf_points(const float* depths, const float* kinv, const float* einv
 /* ---- optimiser tail on flat buffers (idr_train.py:289-302: all_norm, clip_grad_norm_(grad_cap), Adam.step), two launches ----
  * p, g, m, v: flat fp32 buffers of n elements (parameters, gradients, exp_avg, exp_avg_sq).  step >= 1 is the Adam step count AFTER
  * this update.  max_norm <= 0 disables clipping; otherwise g is scaled in place by min(1, max_norm / (||g|| + 1e-6)).
- * norm_out (device, 2 floats, may be NULL) receives {||g||, clip coefficient}; ws: mvsdf_adam_ws_floats() floats. */
+ * beta1 / beta2 are DOUBLES: 1 - beta and the bias corrections 1 - beta1^step, sqrt(1 - beta2^step) are formed from them in double and rounded once
+ * (a float 0.999 would put 1.3e-5 of relative error on 1 - beta2).
+ * norm_out (device, 2 floats, may be NULL) receives {||g||, clip coefficient}; ws: mvsdf_adam_ws_floats() floats, written before they are read.
+ * Alignment: the four buffers need only 4-byte alignment and no padding; when all four are 16-byte aligned the update uses 16-byte accesses, with the
+ * same per-element arithmetic (identical bits either way).  Nothing outside [0, n) of a buffer is written; the sums have a fixed order (the same call on
+ * the same state gives the same bits).
+ * Non-finite gradients are plain data: the coefficient applies only when it is below 1 (torch 1.7.1's clip_grad_norm_, `if clip_coef < 1:`), so a NaN norm
+ * clips nothing and the NaN stays in its own elements; an infinite norm gives coefficient 0 (finite gradients vanish, infinite ones become NaN). */
 size_t mvsdf_adam_ws_floats(void);
-int mvsdf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step, float max_norm,
+int mvsdf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step, float max_norm,
                     float* norm_out, float* ws, void* stream);
 /* Same with every gradient multiplied by grad_scale first (norm and clip see the scaled gradient): grad_scale = 1 / world size turns the
  * SUM of a data-parallel all-reduce into the rank average inside the optimiser launch -- no separate division pass over the bucket. */
-int mvsdf_adam_step_scaled(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step,
+int mvsdf_adam_step_scaled(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step,
                            float max_norm, float grad_scale, float* norm_out, float* ws, void* stream);
 /* ... and, with zero_grad != 0, ZEROS left in g instead of the scaled / clipped gradient: the `optimizer.zero_grad()` that opens the next iteration
  * (idr_train.py:283) then needs no launch of its own (the update pass touches every gradient element anyway). */
-int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step,
+int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step,
                           float max_norm, float grad_scale, int zero_grad, float* norm_out, float* ws, void* stream);
 
 /* masks -> what IDRLoss.forward needs from them, one launch: hit[R] = network_object_mask & object_mask (loss.py:21,206), view_start[B+1]

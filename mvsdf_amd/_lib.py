@@ -48,9 +48,9 @@ def lib():
         L.mvsdf_packed_bf16_bytes.restype = C.c_size_t
         L.mvsdf_packed_bf16_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.mvsdf_tracegen_state_bytes.restype = C.c_size_t
-        L.mvsdf_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mvsdf_adam_step_scaled.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mvsdf_adam_step_fused.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mvsdf_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float, C.c_double, C.c_double, C.c_float] + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mvsdf_adam_step_scaled.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float, C.c_double, C.c_double, C.c_float] + [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mvsdf_adam_step_fused.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float, C.c_double, C.c_double, C.c_float] + [C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mvsdf_loss_scale.argtypes = [C.c_void_p] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p, C.c_int] * 4 + [C.c_void_p, C.c_void_p]   # g: host array of 6 pointers
         i64, vp, f32 = C.c_int64, C.c_void_p, C.c_float
         L.mvsdf_mc_workspace_bytes.restype = C.c_size_t

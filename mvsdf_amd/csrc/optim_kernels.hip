@@ -21,7 +21,9 @@ __global__ __launch_bounds__(256) void k_sqnorm_partials(const float* __restrict
 
 struct AdamArgs {
     float* p; float* g; float* m; float* v; size_t n;
-    float lr, beta1, beta2, eps, bc1, bc2_sqrt;      // bias corrections 1 - beta1^t, sqrt(1 - beta2^t) (host doubles, rounded once)
+    float lr, beta2, eps;
+    float one_m_beta1, one_m_beta2, bc1, bc2_sqrt;   // 1 - beta1, 1 - beta2 and the bias corrections 1 - beta1^t, sqrt(1 - beta2^t): formed on the host in double from
+                                                     // the double betas, rounded once (1 - (float)0.999 is 1.3e-5 off 0.001: that much of every first exp_avg_sq)
     float max_norm;                                  // <= 0: no clipping
     float grad_scale;                                // applied to every gradient first (1 / world size after a SUM all-reduce)
     const float* part; int nparts;
@@ -32,8 +34,8 @@ struct AdamArgs {
 __device__ __forceinline__ void mv_adam_one(const AdamArgs& a, float coef, float step_size, float gi, float mi, float vi, float pi, float& g, float& m,
                                             float& v, float& p) {
     g = gi * a.grad_scale * coef;
-    m = mi + (g - mi) * (1.0f - a.beta1);                                                  // exp_avg.lerp_(grad, 1 - beta1)
-    v = vi * a.beta2 + (1.0f - a.beta2) * g * g;                                           // mul_(beta2).addcmul_(g, g, 1 - beta2)
+    m = mi + (g - mi) * a.one_m_beta1;                                                     // exp_avg.lerp_(grad, 1 - beta1)
+    v = vi * a.beta2 + a.one_m_beta2 * g * g;                                              // mul_(beta2).addcmul_(g, g, 1 - beta2)
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
     p = pi - step_size * (m / denom);
 }
@@ -48,7 +50,10 @@ __global__ __launch_bounds__(256) void k_adam_flat(AdamArgs a) {
     float4 g4 = {0.f, 0.f, 0.f, 0.f}, m4 = g4, v4 = g4, p4 = g4;
     const bool have = vec && i4 < n4;
     {
-        const size_t j = have ? i4 : 0;                          // clamped: no branch around the loads
+        // clamped: no branch around the loads.  With n < 4 (n4 = 0) index 0 is still loaded, 16 bytes from buffers shorter than that: safe, because a
+        // 16-byte load at a 16-byte-aligned address that holds a valid byte stays inside that byte's allocation granule (device allocations are whole
+        // multiples of far more than 16 bytes), and unused: `have` is false, the vector loop below runs zero trips, nothing of it reaches an output
+        const size_t j = have ? i4 : 0;
         if (vec) { g4 = ((const float4*)a.g)[j]; m4 = ((const float4*)a.m)[j]; v4 = ((const float4*)a.v)[j]; p4 = ((const float4*)a.p)[j]; }
     }
     if (threadIdx.x < 64) {                          // every block re-derives the norm from the partials, same order everywhere
@@ -57,6 +62,8 @@ __global__ __launch_bounds__(256) void k_adam_flat(AdamArgs a) {
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
         if (threadIdx.x == 0) {
             const float total = sqrtf(s) * a.grad_scale;
+            // Non-finite gradients: a NaN norm gives fminf(NaN, 1) = 1 -- nothing is clipped and the NaN stays in its own elements, torch 1.7.1's
+            // `if clip_coef < 1:` (the reference's pinned version; torch >= 1.10 multiplies unconditionally and spreads the NaN); an infinite norm gives 0
             float coef = 1.0f;
             if (a.max_norm > 0.0f) coef = fminf(a.max_norm / (total + 1e-6f), 1.0f);      // torch.nn.utils.clip_grad_norm_
             coef_s = coef;
@@ -89,15 +96,15 @@ extern "C" {
 
 size_t mvsdf_adam_ws_floats(void) { return OPT_BLOCKS_MAX; }
 
-int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step, float max_norm,
+int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step, float max_norm,
                           float grad_scale, int zero_grad, float* norm_out, float* ws, void* stream);
 
-int mvsdf_adam_step_scaled(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step, float max_norm,
+int mvsdf_adam_step_scaled(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step, float max_norm,
                            float grad_scale, float* norm_out, float* ws, void* stream) {
     return mvsdf_adam_step_fused(p, g, m, v, n, lr, beta1, beta2, eps, step, max_norm, grad_scale, 0, norm_out, ws, stream);
 }
 
-int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step, float max_norm,
+int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step, float max_norm,
                           float grad_scale, int zero_grad, float* norm_out, float* ws, void* stream) {
     if (!p || !g || !m || !v || !ws || n == 0 || step < 1 || !(grad_scale > 0.0f)) return mv_fail(-1, "mvsdf_adam_step: bad arguments");
     hipStream_t s = (hipStream_t)stream;
@@ -107,15 +114,16 @@ int mvsdf_adam_step_fused(float* p, float* g, float* m, float* v, size_t n, floa
     hipLaunchKernelGGL(k_sqnorm_partials, dim3(blocks), dim3(256), 0, s, g, n, ws);
     AdamArgs a;
     a.p = p; a.g = g; a.m = m; a.v = v; a.n = n;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    a.lr = lr; a.beta2 = (float)beta2; a.eps = eps;
+    a.one_m_beta1 = (float)(1.0 - beta1); a.one_m_beta2 = (float)(1.0 - beta2);
+    a.bc1 = (float)(1.0 - pow(beta1, (double)step));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
     a.max_norm = max_norm; a.grad_scale = grad_scale; a.part = ws; a.nparts = blocks; a.norm_out = norm_out; a.zero_grad = zero_grad ? 1 : 0;
     hipLaunchKernelGGL(k_adam_flat, dim3(blocks), dim3(256), 0, s, a);
     return mv_check(hipGetLastError(), "mvsdf_adam_step");
 }
 
-int mvsdf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step, float max_norm,
+int mvsdf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2, float eps, int step, float max_norm,
                     float* norm_out, float* ws, void* stream) {
     return mvsdf_adam_step_scaled(p, g, m, v, n, lr, beta1, beta2, eps, step, max_norm, 1.0f, norm_out, ws, stream);
 }

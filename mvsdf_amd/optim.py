@@ -130,6 +130,9 @@ class FlatAdam(torch.optim.Optimizer):
         zero_grad=True: the update pass leaves ZEROS in the gradients instead of the scaled / clipped values (torch's Adam leaves them; the reference's loop
         zeroes them at the top of the next iteration, idr_train.py:283): that zero_grad() then costs no launch.  Do not use it when the gradients are read
         after step().
+        Non-finite gradients follow torch 1.7.1's clip_grad_norm_ (`if clip_coef < 1:`), the reference's pinned version: the coefficient applies only when
+        it is below 1, so a NaN norm clips nothing and the NaN stays in its own elements (and the moments / parameters they update); an infinite norm
+        gives a coefficient of 0.  torch >= 1.10 would spread a NaN norm over every gradient instead.
         torch.optim.Optimizer's step pre / post hooks run if any are registered (the profiler range torch wraps around step() is skipped:
         it costs more host time than the two launches)."""
         assert closure is None

@@ -98,3 +98,17 @@ def test_build_is_keyed_by_content(tmp_path, monkeypatch):
     B.build()
     B.build(tag='dev')
     assert calls() == 0
+
+
+def test_adam_entry_points_take_double_betas():
+    """1 - beta and the bias corrections are formed in double from the caller's betas (a float 0.999 puts 1.3e-5 on 1 - beta2): the header and the
+    ctypes prototypes agree on `float lr, double beta1, double beta2, float eps` for all three entry points."""
+    import ctypes
+    import re
+    from mvsdf_amd import _lib
+    hdr = open(os.path.join(ROOT, 'include', 'mvsdf_hip.h')).read()
+    for name in ('mvsdf_adam_step', 'mvsdf_adam_step_scaled', 'mvsdf_adam_step_fused'):
+        decl = re.search(r'int %s\(([^;]*)\);' % name, hdr).group(1)
+        assert 'float lr, double beta1, double beta2, float eps' in ' '.join(decl.split()), name
+        at = getattr(_lib.lib(), name).argtypes
+        assert list(at[5:9]) == [ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_float], name

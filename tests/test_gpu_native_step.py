@@ -230,3 +230,71 @@ def test_host_time_of_a_native_step():
         res[native] = (time.perf_counter() - t0) / 100 * 1e3
     print('wall ms per tiny step: native %.3f, python route %.3f' % (res[True], res[False]))
     assert res[True] < res[False]
+
+
+_GROUP_SWITCHES = ('d_use_rt_surf', 'd_use_eik', 'd_use_dsurf_on', 'd_use_dsurf_jitter',
+                   'eik_use_rt_surf', 'eik_use_eik', 'eik_use_dsurf_on', 'eik_use_dsurf_jitter')
+
+
+def _one_step(m, native, inp, gt, tp, B):
+    """one forward + loss + backward on a model that is kept across calls -> (outputs, losses, gradient, the CPU generator's next draw)"""
+    loss_fn = IDRLoss()
+    loss_fn.native = native
+    torch.manual_seed(11)
+    out = m(inp, tp)
+    lo = loss_fn(out, dict(gt), tp, B)
+    m.zero_grad()
+    lo['loss'].backward()
+    torch.cuda.synchronize()
+    g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).flatten() for p in m.parameters()]).clone()
+    outs = {k: v.detach().clone() for k, v in out.items() if torch.is_tensor(v)}
+    return outs, {k: v.detach().clone() for k, v in lo.items()}, g, torch.rand(3)
+
+
+@pytest.mark.parametrize('tp', [0.1, 0.3])
+def test_native_equals_python_route_for_every_point_group_mask(tp, monkeypatch):
+    """k_step_bwd_assemble's mv_group_index must invert mv_group_row for every (d_mask, e_mask): the native route against the Python route (staged
+    kernels), bit for bit in outputs, losses and gradients, for all 256 settings of the eight conf.d_use_* / conf.eik_use_* switches -- at tp = 0.1
+    (geometry detached in front of the rendering net) and at tp = 0.3 (attached).  The batch carries depth maps, so a depth-surface switch that is on
+    draws n_ds = R / 2 samples per set; with all four off n_ds = 0.  A term without any group raises ValueError before any launch on both routes
+    (IDRNetwork._check_point_groups): exactly the 31 pairs with d_mask = 0 or e_mask = 0; the other 225 are compared."""
+    from mvsdf_amd.model import conf
+    B, P = 1, 64
+    models = {True: _model(64, True), False: _model(64, False)}
+    inp, gt = _batch(B, P, 2, phase0=True)
+    refused, compared, with_ds, n_hits = [], 0, 0, set()
+    for d_mask in range(16):
+        for e_mask in range(16):
+            bits = [bool(d_mask >> g & 1) for g in range(4)] + [bool(e_mask >> g & 1) for g in range(4)]
+            with monkeypatch.context() as mp:
+                for name, on in zip(_GROUP_SWITCHES, bits):
+                    mp.setattr(conf, name, (lambda tp_, on=on: on))
+                if d_mask == 0 or e_mask == 0:
+                    for native in (True, False):
+                        with pytest.raises(ValueError, match='every point group'):
+                            models[native](inp, tp)
+                    refused.append((d_mask, e_mask))
+                    continue
+                o_n, l_n, g_n, r_n = _one_step(models[True], True, inp, gt, tp, B)
+                o_p, l_p, g_p, r_p = _one_step(models[False], False, inp, gt, tp, B)
+            what = 'd_mask %d e_mask %d: ' % (d_mask, e_mask)
+            assert getattr(models[True], '_last_step', None) is not None, 'the native driver did not run'
+            assert set(o_n) == set(o_p)
+            for k in o_p:
+                _same(o_n[k], o_p[k], what + k)
+            for k in l_p:
+                _same(l_n[k], l_p[k], what + k)
+            _same(g_n, g_p, what + 'gradient')
+            assert torch.equal(r_n, r_p)
+            assert float(g_p.abs().max()) > 0
+            R, N = B * P, int(o_p['network_object_mask'].sum())
+            n_ds = R // 2 if (d_mask | e_mask) & 12 else 0
+            sizes = (N, R // 2, n_ds, n_ds)
+            assert o_p['eikonal_output'].shape[1] == sum(c for g, c in enumerate(sizes) if d_mask >> g & 1), what
+            assert o_p['grad_theta'].shape[0] == sum(c for g, c in enumerate(sizes) if e_mask >> g & 1), what
+            with_ds += n_ds > 0
+            n_hits.add(N)
+            compared += 1
+    assert len(refused) == 31 and compared == 225
+    assert refused == [(d, e) for d in range(16) for e in range(16) if d == 0 or e == 0]
+    assert with_ds == 225 - 9 and max(n_hits) > 0                      # (3 x 3 pairs use no depth-surface group at all)
