@@ -637,6 +637,29 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
 int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, int64_t npairs, void* ws, size_t ws_bytes, double* points,
                       uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
 
+/* ---- Point-cloud cleaning (cloud.hip; Python: mvsdf_amd/cloud.py, which states the definition) ----
+ * pts fp64 [n][3] on the device, fp64 throughout.  mvsdf_cloud_knn, _components and _clean share one workspace (mvsdf_cloud_clean_workspace_bytes,
+ * 0 unless 2 <= n <= INT32_MAX) and leave int64 {n_passed, n_clusters, largest, n_kept, m (fp64 bits), threshold (bits), eps (bits), rounds,
+ * error bits} at its start; entries a call does not compute are 0.  Error bits as the Chamfer calls: 4 a non-finite coordinate, 32 the round
+ * limit of the components loop, 64 a tree-walk bound; with any set nothing else is valid.  Every argument is validated before the first launch;
+ * each call waits for the stream once for the coordinate check, _components and _clean once more per round of the components loop (normally one).
+ * mvsdf_cloud_knn: d[i] = the mean of sqrt over the k smallest (dx dx + dy dy) + dz dz from point i to every other point (by index), summed in
+ * ascending order.  1 <= k <= 32, n >= k + 1.
+ * mvsdf_cloud_components: labels[i] = the smallest index in i's connected component under d2 <= eps * eps (every point takes part).
+ * mvsdf_cloud_clean: d as above; m = the element of rank (n - 1) / 2 of d; a point passes iff d <= knn_ratio * m; eps = eps_ratio * m; labels over
+ * the passed points (-1 elsewhere); keep[i] = 1 iff i passed and its component holds >= cluster_frac * (the largest component's count) points.
+ * Ratios finite and > 0, cluster_frac <= 1.
+ * mvsdf_cloud_compact (no host wait): the rows with keep != 0 of pts, colors uint8 [n][3], a and b int32 [n] (each of the three may be NULL with
+ * its output) in input order; rows at or beyond cap are not written -> int64 {rows kept}. */
+size_t mvsdf_cloud_clean_workspace_bytes(int64_t n);
+size_t mvsdf_cloud_compact_workspace_bytes(int64_t n);
+int mvsdf_cloud_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t ws_bytes, double* d, void* stream);
+int mvsdf_cloud_components(const double* pts, int64_t n, double eps, void* ws, size_t ws_bytes, int32_t* labels, void* stream);
+int mvsdf_cloud_clean(const double* pts, int64_t n, int32_t k, double knn_ratio, double eps_ratio, double cluster_frac, void* ws, size_t ws_bytes,
+                      double* d, int32_t* labels, uint8_t* keep, void* stream);
+int mvsdf_cloud_compact(const double* pts, const uint8_t* colors, const int32_t* a, const int32_t* b, const uint8_t* keep, int64_t n, void* ws,
+                        size_t ws_bytes, double* out_pts, uint8_t* out_colors, int32_t* out_a, int32_t* out_b, int64_t cap, void* stream);
+
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.
  * raw: fp32 [mvsdf_featext_raw_floats()] on the device, the layers in the order of mvsdf_amd/features.py::LAYERS, each its weight in PyTorch layout

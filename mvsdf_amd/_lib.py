@@ -93,6 +93,13 @@ def lib():
         L.mvsdf_fusion_workspace_bytes.argtypes = [i64] * 4
         L.mvsdf_fusion_fuse.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, f64, f64, vp, sz, vp, vp, vp, vp]
         L.mvsdf_fusion_emit.argtypes = [vp, i64, i64, i64, i64, vp, sz, vp, vp, vp, vp, i64, vp]
+        for fn in ('mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes'):
+            getattr(L, fn).restype = sz
+            getattr(L, fn).argtypes = [i64]
+        L.mvsdf_cloud_knn.argtypes = [vp, i64, i32, vp, sz, vp, vp]
+        L.mvsdf_cloud_components.argtypes = [vp, i64, f64, vp, sz, vp, vp]
+        L.mvsdf_cloud_clean.argtypes = [vp, i64, i32, f64, f64, f64, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_cloud_compact.argtypes = [vp] * 5 + [i64, vp, sz] + [vp] * 4 + [i64, vp]
         for fn in ('mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_layer_workspace_bytes'):
             getattr(L, fn).restype = sz
         L.mvsdf_featext_raw_floats.argtypes = []
@@ -132,6 +139,8 @@ EXPORTS = [
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
     'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit',
+    'mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes', 'mvsdf_cloud_knn', 'mvsdf_cloud_components', 'mvsdf_cloud_clean',
+    'mvsdf_cloud_compact',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',

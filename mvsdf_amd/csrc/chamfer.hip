@@ -8,153 +8,24 @@
 //   independent set under the keys splitmix64(seed ^ i): synchronous rounds (states ping-pong) keep a point once every lower-key neighbour is
 //   removed and remove it once one is kept.  The lowest undecided key is decided in every round, so N rounds always suffice.
 // * Masks: flags, int64 scans and an order-preserving scatter.
-// * Nearest distance: the references are sorted by a 63-bit Morton code (stable LSD radix sort, 4 bits per pass), cut into leaves of CH_LEAF
-//   consecutive points, and an implicit 8-ary tree of fp64 boxes is built over the leaves.  A query descends greedily to one leaf for a first
-//   bound, then walks the tree without a stack, pruning a box only when its lower bound exceeds min(best, max_dist)^2 by a relative 4e-9.  The
-//   minimum squared distance is exact (every point not pruned is compared with the metric's formula) and sqrt is monotonic, so the result is
-//   sqrt(min d^2) bit for bit.  A query with nothing within max_dist only meets boxes farther than the cut-off, which stops it near the root.
+// * Nearest distance (the sort and the tree live in nn_tree.h, shared with cloud.hip): the references are sorted by a 63-bit Morton code
+//   (stable LSD radix sort, 4 bits per pass), cut into leaves of CH_LEAF consecutive points, and an implicit 8-ary tree of fp64 boxes is built
+//   over the leaves.  A query descends greedily to one leaf for a first bound, then walks the tree without a stack, pruning a box only when its
+//   lower bound exceeds min(best, max_dist)^2 by a relative 4e-9.  The minimum squared distance is exact (every point not pruned is compared
+//   with the metric's formula) and sqrt is monotonic, so the result is sqrt(min d^2) bit for bit.  A query with nothing within max_dist only
+//   meets boxes farther than the cut-off, which stops it near the root.
 // * Sums: fixed-order block reductions in fp64, no float atomics.
 //
 // Every device loop is bounded; the downsampling round loop on the host stops at the caller's limit and reports it.
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
-
-#define CH_THREADS 256
-#define CH_ITEMS 8                                    // consecutive items per lane in the scans and sums
-#define CH_CHUNK (CH_THREADS * CH_ITEMS)
-#define CH_TOP_THREADS 1024
-#define CH_HDR 256                                    // bytes at the start of every workspace: int64 results the host reads
-#define CH_EMPTY 0xffffffffffffffffull
-#define CH_LEAF 16                                    // reference points per leaf
-#define CH_ARITY 8
-#define CH_MAX_LEVELS 16
-#define CH_RS_BINS 16                                 // radix sort: 4 bits per pass
-#define CH_RS_ITEMS 16
-#define CH_RS_CHUNK (CH_THREADS * CH_RS_ITEMS)
-#define CH_MORTON_BITS 21
-#define CH_DS_BATCH 4                                 // downsampling rounds per host check
-#define CH_MARGIN2 (1.0 + 4e-9)                       // relative margin of a box prune on squared distances
-#define CH_CELL_LIMIT 2147483648.0                    // |coordinate / cell| bound that keeps the 27-cell search exact
-
-enum {
-    CH_ERR_POINTS = 1,      // sampling: more points than max_points
-    CH_ERR_RANGE = 2,       // sampling: a vertex id outside [0, nv)
-    CH_ERR_FINITE = 4,      // a non-finite coordinate
-    CH_ERR_COORD = 8,       // downsampling: a coordinate too far from the origin for the cell grid
-    CH_ERR_HASH = 16,       // the cell table's probe bound (cannot happen at load factor 1/2)
-    CH_ERR_ROUNDS = 32,     // downsampling: the round limit was reached
-    CH_ERR_WALK = 64,       // nearest: a tree walk hit its bound (cannot happen)
-};
+#include "nn_tree.h"
 
 enum { DS_UNDECIDED = 0, DS_KEPT = 1, DS_REMOVED = 2 };
-
-static inline size_t ch_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline unsigned ch_grid(long long n, long long per) { return (unsigned)((n + per - 1) / per); }
 
 __host__ __device__ __forceinline__ uint64_t ch_splitmix64(uint64_t x) {
     x += 0x9e3779b97f4a7c15ull;
     x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
     x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
     return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ double ch_d2(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-__device__ __forceinline__ bool ch_finite3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
-// ================================================================ int64 exclusive scan (three launches) ================================================================
-// per-workgroup totals of a[n]
-__global__ __launch_bounds__(CH_THREADS) void k_ch_block_sum(const long long* __restrict__ a, long long n, long long* __restrict__ bsum) {
-    __shared__ long long sh[CH_THREADS];
-    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)threadIdx.x * CH_ITEMS;
-    long long s = 0;
-    for (int q = 0; q < CH_ITEMS; ++q)
-        if (base + q < n) s += a[base + q];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = CH_THREADS / 2; d; d >>= 1) {
-        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
-}
-
-// in place: exclusive scan of bsum[nb]; *total = the sum (one workgroup, serial ranges per lane)
-__global__ __launch_bounds__(CH_TOP_THREADS) void k_ch_scan_top(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
-    __shared__ long long sh[CH_TOP_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nb + CH_TOP_THREADS - 1) / CH_TOP_THREADS;
-    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
-    long long s = 0;
-    for (long long q = lo; q < hi; ++q) s += bsum[q];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < CH_TOP_THREADS; d <<= 1) {                // inclusive Hillis-Steele scan
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = sh[t] - s;
-    for (long long q = lo; q < hi; ++q) {
-        const long long v = bsum[q];
-        bsum[q] = r;
-        r += v;
-    }
-    if (t == CH_TOP_THREADS - 1) *total = sh[t];
-}
-
-// out[i] = boff[block] + the exclusive prefix of a inside the block (out may alias a)
-__global__ __launch_bounds__(CH_THREADS) void k_ch_scan_apply(const long long* a, long long n, const long long* __restrict__ boff, long long* out) {
-    __shared__ long long sh[CH_THREADS];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)t * CH_ITEMS;
-    long long v[CH_ITEMS], s = 0;
-#pragma unroll
-    for (int q = 0; q < CH_ITEMS; ++q) {
-        v[q] = base + q < n ? a[base + q] : 0;
-        s += v[q];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < CH_THREADS; d <<= 1) {
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = boff[blockIdx.x] + sh[t] - s;
-#pragma unroll
-    for (int q = 0; q < CH_ITEMS; ++q) {
-        if (base + q < n) out[base + q] = r;
-        r += v[q];
-    }
-}
-
-static size_t ch_scan_tmp_bytes(long long n) { return ch_align((size_t)(ch_grid(n, CH_CHUNK) + 1) * 8); }
-
-// exclusive scan of a[n] (n >= 1) into out (may alias a); tmp: ch_scan_tmp_bytes(n); total: one int64 on the device
-static void ch_scan(const long long* a, long long n, long long* out, void* tmp, long long* total, hipStream_t s) {
-    const unsigned nb = ch_grid(n, CH_CHUNK);
-    long long* bsum = (long long*)tmp;
-    hipLaunchKernelGGL(k_ch_block_sum, dim3(nb), dim3(CH_THREADS), 0, s, a, n, bsum);
-    hipLaunchKernelGGL(k_ch_scan_top, dim3(1), dim3(CH_TOP_THREADS), 0, s, bsum, (long long)nb, total);
-    hipLaunchKernelGGL(k_ch_scan_apply, dim3(nb), dim3(CH_THREADS), 0, s, a, n, (const long long*)bsum, out);
-}
-
-static int ch_read(void* host, const void* dev, size_t n, hipStream_t s, const char* what) {
-    if (int rc = mv_check(hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);
-}
-
-static int ch_write_header(void* ws, const long long* hdr, int n, hipStream_t s, const char* what) {
-    if (int rc = mv_check(hipMemcpyAsync(ws, hdr, (size_t)n * 8, hipMemcpyHostToDevice, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);
 }
 
 // ================================================================ sampling ================================================================
@@ -481,172 +352,6 @@ static bool ch_mask_layout(long long n, long long m, ChMaskLayout* L) {
 }
 
 // ================================================================ nearest distance ================================================================
-// per-workgroup box of the references (k_nn_bbox_final combines them); a non-finite coordinate raises CH_ERR_FINITE
-__global__ __launch_bounds__(CH_THREADS) void k_nn_bbox_part(const double* __restrict__ R, long long n, double* __restrict__ part, int* err) {
-    __shared__ double sh[6][CH_THREADS];
-    const long long base = (long long)blockIdx.x * CH_CHUNK;
-    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int bad = 0;
-    for (int q = 0; q < CH_ITEMS; ++q) {
-        const long long i = base + (long long)q * CH_THREADS + threadIdx.x;
-        if (i >= n) break;
-        const double* p = R + i * 3;
-        if (!ch_finite3(p)) {
-            bad = 1;
-            continue;
-        }
-        for (int a = 0; a < 3; ++a) {
-            b[a] = fmin(b[a], p[a]);
-            b[3 + a] = fmax(b[3 + a], p[a]);
-        }
-    }
-    if (bad) atomicOr(err, CH_ERR_FINITE);
-    for (int a = 0; a < 6; ++a) sh[a][threadIdx.x] = b[a];
-    __syncthreads();
-    for (int d = CH_THREADS / 2; d; d >>= 1) {
-        if ((int)threadIdx.x < d)
-            for (int a = 0; a < 6; ++a)
-                sh[a][threadIdx.x] = a < 3 ? fmin(sh[a][threadIdx.x], sh[a][threadIdx.x + d]) : fmax(sh[a][threadIdx.x], sh[a][threadIdx.x + d]);
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-// frame[0..2] = the box's low corner, frame[3..5] = 2^21 / extent (1 for a flat axis)
-__global__ __launch_bounds__(64) void k_nn_bbox_final(const double* __restrict__ part, long long nb, double* __restrict__ frame) {
-    const int a = threadIdx.x;
-    if (a >= 3) return;
-    double lo = INFINITY, hi = -INFINITY;
-    for (long long b = 0; b < nb; ++b) {
-        lo = fmin(lo, part[b * 6 + a]);
-        hi = fmax(hi, part[b * 6 + 3 + a]);
-    }
-    frame[a] = lo;
-    frame[3 + a] = hi > lo ? (double)(1 << CH_MORTON_BITS) / (hi - lo) : 1.0;
-}
-
-__device__ __forceinline__ unsigned long long ch_spread3(unsigned long long x) {   // 21 bits -> every third bit of 63
-    x &= 0x1fffff;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-
-__global__ __launch_bounds__(CH_THREADS) void k_nn_morton(const double* __restrict__ R, long long n, const double* __restrict__ frame,
-                                                           unsigned long long* __restrict__ key, int* __restrict__ val) {
-    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
-    if (i >= n) return;
-    unsigned long long m = 0;
-    for (int a = 0; a < 3; ++a) {
-        const double x = (R[i * 3 + a] - frame[a]) * frame[3 + a];
-        const double c = x >= 0.0 ? fmin(x, (double)((1 << CH_MORTON_BITS) - 1)) : 0.0;
-        m |= ch_spread3((unsigned long long)c) << a;
-    }
-    key[i] = m;
-    val[i] = (int)i;
-}
-
-// radix sort, pass `shift`: per-workgroup digit counts, digit-major: hist[d * nb + b]
-__global__ __launch_bounds__(CH_THREADS) void k_rs_hist(const unsigned long long* __restrict__ key, long long n, int shift, long long* __restrict__ hist, int nb) {
-    __shared__ int c[CH_RS_BINS];
-    if (threadIdx.x < CH_RS_BINS) c[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * CH_RS_CHUNK;
-    for (int q = 0; q < CH_RS_ITEMS; ++q) {
-        const long long i = base + (long long)q * CH_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&c[(key[i] >> shift) & (CH_RS_BINS - 1)], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x < CH_RS_BINS) hist[(long long)threadIdx.x * nb + blockIdx.x] = c[threadIdx.x];
-}
-
-// stable scatter: lane t owns items [base + t * CH_RS_ITEMS, + CH_RS_ITEMS); its place among equal digits of the workgroup is the count of those
-// digits in lanes < t (an exclusive scan over the lanes in LDS) plus its own running count
-__global__ __launch_bounds__(CH_THREADS) void k_rs_scatter(const unsigned long long* __restrict__ kin, const int* __restrict__ vin, long long n, int shift,
-                                                            const long long* __restrict__ off, int nb, unsigned long long* __restrict__ kout, int* __restrict__ vout) {
-    __shared__ int c[CH_RS_BINS][CH_THREADS];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * CH_RS_CHUNK + (long long)t * CH_RS_ITEMS;
-#pragma unroll
-    for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] = 0;
-    for (int q = 0; q < CH_RS_ITEMS; ++q)
-        if (base + q < n) ++c[(kin[base + q] >> shift) & (CH_RS_BINS - 1)][t];
-    __syncthreads();
-    int own[CH_RS_BINS];
-#pragma unroll
-    for (int d = 0; d < CH_RS_BINS; ++d) own[d] = c[d][t];
-    for (int s = 1; s < CH_THREADS; s <<= 1) {                   // inclusive Hillis-Steele scan over the lanes, every digit at once
-        int x[CH_RS_BINS];
-#pragma unroll
-        for (int d = 0; d < CH_RS_BINS; ++d) x[d] = t >= s ? c[d][t - s] : 0;
-        __syncthreads();
-#pragma unroll
-        for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] += x[d];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int d = 0; d < CH_RS_BINS; ++d) c[d][t] -= own[d];    // exclusive; from here lane t alone uses column t as its running position
-    for (int q = 0; q < CH_RS_ITEMS; ++q) {
-        const long long i = base + q;
-        if (i >= n) break;
-        const unsigned long long k = kin[i];
-        const int d = (k >> shift) & (CH_RS_BINS - 1);
-        const long long dst = off[(long long)d * nb + blockIdx.x] + c[d][t]++;
-        kout[dst] = k;
-        vout[dst] = vin[i];
-    }
-}
-
-__global__ __launch_bounds__(CH_THREADS) void k_nn_gather(const double* __restrict__ R, long long n, const int* __restrict__ val, double* __restrict__ sp) {
-    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const long long j = val[i];
-    for (int c = 0; c < 3; ++c) sp[i * 3 + c] = R[j * 3 + c];
-}
-
-__global__ __launch_bounds__(CH_THREADS) void k_nn_leaf_box(const double* __restrict__ sp, long long n, long long nleaf, double* __restrict__ box) {
-    const long long l = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
-    if (l >= nleaf) return;
-    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    const long long e = min(n, (l + 1) * CH_LEAF);
-    for (long long i = l * CH_LEAF; i < e; ++i)
-        for (int a = 0; a < 3; ++a) {
-            b[a] = fmin(b[a], sp[i * 3 + a]);
-            b[3 + a] = fmax(b[3 + a], sp[i * 3 + a]);
-        }
-    for (int a = 0; a < 6; ++a) box[l * 6 + a] = b[a];
-}
-
-// node i of a level = the union of children [8 i, min(8 i + 8, nchild)) of the level below
-__global__ __launch_bounds__(CH_THREADS) void k_nn_node_box(const double* __restrict__ child, long long nchild, long long nnode, double* __restrict__ box) {
-    const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
-    if (i >= nnode) return;
-    double b[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    const long long e = min(nchild, (i + 1) * CH_ARITY);
-    for (long long k = i * CH_ARITY; k < e; ++k)
-        for (int a = 0; a < 3; ++a) {
-            b[a] = fmin(b[a], child[k * 6 + a]);
-            b[3 + a] = fmax(b[3 + a], child[k * 6 + 3 + a]);
-        }
-    for (int a = 0; a < 6; ++a) box[i * 6 + a] = b[a];
-}
-
-struct ChTree {
-    int top;                                          // root level (level 0 = the leaves)
-    long long cnt[CH_MAX_LEVELS], off[CH_MAX_LEVELS]; // nodes per level, their first box
-    long long n, nodes;
-};
-
-__device__ __forceinline__ double ch_box_lb2(const double* __restrict__ b, double x, double y, double z) {
-    const double gx = x < b[0] ? b[0] - x : (x > b[3] ? x - b[3] : 0.0);
-    const double gy = y < b[1] ? b[1] - y : (y > b[4] ? y - b[4] : 0.0);
-    const double gz = z < b[2] ? b[2] - z : (z > b[5] ? z - b[5] : 0.0);
-    return (gx * gx + gy * gy) + gz * gz;
-}
-
 __device__ __forceinline__ double ch_leaf_min(const double* __restrict__ sp, long long n, long long l, double x, double y, double z, double best) {
     const long long e = min(n, (l + 1) * CH_LEAF);
     for (long long i = l * CH_LEAF; i < e; ++i) best = fmin(best, ch_d2(x, y, z, sp[i * 3], sp[i * 3 + 1], sp[i * 3 + 2]));
@@ -769,39 +474,16 @@ __global__ __launch_bounds__(CH_TOP_THREADS) void k_nn_sum_final(const double* _
 }
 
 struct ChNnLayout {
-    ChTree T;
-    long long nbr, nbq, rs_nb;
-    size_t part, frame, k0, k1, v0, v1, hist, tmp, sp, box, psum, pcnt, flags, total;
+    ChTreeLayout t;
+    long long nbq;
+    size_t psum, pcnt, flags, total;
 };
 
 static bool ch_nn_layout(long long nq, long long nr, ChNnLayout* L) {
     if (nq < 0 || nr < 1 || nq > (1ll << 40) || nr > INT_MAX) return false;
-    ChTree& T = L->T;
-    T.n = nr;
-    T.cnt[0] = (nr + CH_LEAF - 1) / CH_LEAF;
-    T.off[0] = 0;
-    T.top = 0;
-    while (T.cnt[T.top] > 1) {
-        if (T.top + 1 >= CH_MAX_LEVELS) return false;
-        T.cnt[T.top + 1] = (T.cnt[T.top] + CH_ARITY - 1) / CH_ARITY;
-        T.off[T.top + 1] = T.off[T.top] + T.cnt[T.top];
-        ++T.top;
-    }
-    T.nodes = T.off[T.top] + 1;
-    L->nbr = ch_grid(nr, CH_CHUNK);
-    L->nbq = ch_grid(nq > 0 ? nq : 1, CH_CHUNK);
-    L->rs_nb = ch_grid(nr, CH_RS_CHUNK);
     size_t o = CH_HDR;
-    L->part = o;  o += ch_align((size_t)L->nbr * 48);
-    L->frame = o; o += ch_align(6 * 8);
-    L->k0 = o;    o += ch_align((size_t)nr * 8);
-    L->k1 = o;    o += ch_align((size_t)nr * 8);
-    L->v0 = o;    o += ch_align((size_t)nr * 4);
-    L->v1 = o;    o += ch_align((size_t)nr * 4);
-    L->hist = o;  o += ch_align((size_t)L->rs_nb * CH_RS_BINS * 8);
-    L->tmp = o;   o += ch_scan_tmp_bytes(L->rs_nb * CH_RS_BINS) + ch_align(8);
-    L->sp = o;    o += ch_align((size_t)nr * 24);
-    L->box = o;   o += ch_align((size_t)T.nodes * 48);
+    if (!ch_tree_layout(nr, &o, &L->t)) return false;
+    L->nbq = ch_grid(nq > 0 ? nq : 1, CH_CHUNK);
     L->psum = o;  o += ch_align((size_t)L->nbq * 8);
     L->pcnt = o;  o += ch_align((size_t)L->nbq * 8);
     L->flags = o; o += ch_align(4 * 8);
@@ -985,41 +667,20 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
     hipStream_t s = (hipStream_t)stream;
     int* fl = (int*)(w + L.flags);
     long long hdr[3] = {0, 0, 0};                                 // distances below the cut-off, their fp64 sum (bits), error bits
-    const int nb = (int)L.rs_nb;
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_nearest"))) return rc;
-    hipLaunchKernelGGL(k_nn_bbox_part, dim3((unsigned)L.nbr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (double*)(w + L.part), fl);
-    hipLaunchKernelGGL(k_nn_bbox_final, dim3(1), dim3(64), 0, s, (const double*)(w + L.part), L.nbr, (double*)(w + L.frame));
+    ch_tree_frame(refs, (long long)nr, w, L.t, fl, s);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
     int e = 0;
     if ((rc = ch_read(&e, fl, 4, s, "mvsdf_chamfer_nearest"))) return rc;
     hdr[2] = e;
     if (!e) {
-        unsigned long long* k[2] = {(unsigned long long*)(w + L.k0), (unsigned long long*)(w + L.k1)};
-        int* v[2] = {(int*)(w + L.v0), (int*)(w + L.v1)};
-        const unsigned gr = ch_grid(nr, CH_THREADS);
-        hipLaunchKernelGGL(k_nn_morton, dim3(gr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (const double*)(w + L.frame), k[0], v[0]);
-        long long* hist = (long long*)(w + L.hist);
-        long long* tot = (long long*)(w + L.tmp + ch_scan_tmp_bytes(L.rs_nb * CH_RS_BINS));
-        int cur = 0;
-        for (int shift = 0; shift < 3 * CH_MORTON_BITS; shift += 4) {
-            hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (long long)nr, shift, hist, nb);
-            ch_scan(hist, L.rs_nb * CH_RS_BINS, hist, w + L.tmp, tot, s);
-            hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (const int*)v[cur], (long long)nr, shift,
-                               (const long long*)hist, nb, k[cur ^ 1], v[cur ^ 1]);
-            cur ^= 1;
-        }
-        double* sp = (double*)(w + L.sp);
-        double* box = (double*)(w + L.box);
-        const ChTree& T = L.T;
-        hipLaunchKernelGGL(k_nn_gather, dim3(gr), dim3(CH_THREADS), 0, s, refs, (long long)nr, (const int*)v[cur], sp);
-        hipLaunchKernelGGL(k_nn_leaf_box, dim3(ch_grid(T.cnt[0], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)sp, (long long)nr, T.cnt[0], box);
-        for (int lv = 1; lv <= T.top; ++lv)
-            hipLaunchKernelGGL(k_nn_node_box, dim3(ch_grid(T.cnt[lv], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)(box + T.off[lv - 1] * 6),
-                               T.cnt[lv - 1], T.cnt[lv], box + T.off[lv] * 6);
+        ch_tree_build(refs, (long long)nr, w, L.t, s);
+        const double* sp = (const double*)(w + L.t.sp);
+        const double* box = (const double*)(w + L.t.box);
+        const ChTree& T = L.t.T;
         if (nq > 0) {
-            hipLaunchKernelGGL(k_nn_query, dim3(ch_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, (long long)nq, (const double*)sp,
-                               (const double*)box, T, max_dist, dist, fl);
+            hipLaunchKernelGGL(k_nn_query, dim3(ch_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, (long long)nq, sp, box, T, max_dist, dist, fl);
             hipLaunchKernelGGL(k_nn_sum_part, dim3((unsigned)L.nbq), dim3(CH_THREADS), 0, s, (const double*)dist, (long long)nq, (double*)(w + L.psum),
                                (long long*)(w + L.pcnt));
             hipLaunchKernelGGL(k_nn_sum_final, dim3(1), dim3(CH_TOP_THREADS), 0, s, (const double*)(w + L.psum), (const long long*)(w + L.pcnt), L.nbq,

@@ -11,7 +11,10 @@ are that file's) with numpy / PIL / torch in place of OpenCV and open3d:
 * --show_range needs a viewer and is not built.
 
 Beyond the reference: range_source='fused' runs fusion.fuse_depths, writes all_torch.ply and takes the box of the whole cloud (a scene that needs
-no manual cut); fused_depth=True writes Fused.fused_depths, which also drops what the source views contradict, instead of the masked depths.
+no manual cut); range_source='clean' fuses likewise, makes the cut with cloud.clean_fused, writes all_torch.ply (the whole cloud) and cut.ply (the
+cleaned cloud: a later range_source='pcd' run reproduces the box, and a person can still edit the file) and takes the box of the cleaned cloud;
+fused_depth=True writes Fused.fused_depths (the cleaned ones under 'clean'), which also drops what the source views contradict, instead of the
+masked depths.
 """
 import os
 
@@ -154,11 +157,14 @@ def _pair_of(v):
 
 
 def convert_scene(data_root, range_source='pcd', pthresh='.7,.7,0', prob_mask=False, resize='1920,1080', crop='1920,1072',
-                  ext_image_path='eg/path/to/image/{:08}.jpg', ext_image_from_one=False, fused_depth=False):
+                  ext_image_path='eg/path/to/image/{:08}.jpg', ext_image_from_one=False, fused_depth=False, clean=None):
     """Writes <data_root>/imfunc4/{image_hd/%06d.png, mask_hd/%03d.png, depth/%03d.pfm, cameras_hd.npz} -> the imfunc4 directory.  Where
-    range_source='fused' or fused_depth run fuse_depths, it reads the masked depths with its own defaults (view 10, vthresh 2)."""
-    if range_source not in ('range', 'pcd', 'fused'):
-        raise ValueError("convert_scene: range_source must be 'range', 'pcd' or 'fused', got %r" % (range_source,))
+    range_source='fused' / 'clean' or fused_depth run fuse_depths, it reads the masked depths with its own defaults (view 10, vthresh 2).
+    clean: a dict of cloud.clean_points keywords for range_source='clean'."""
+    if range_source not in ('range', 'pcd', 'fused', 'clean'):
+        raise ValueError("convert_scene: range_source must be 'range', 'pcd', 'fused' or 'clean', got %r" % (range_source,))
+    if clean is not None and range_source != 'clean':
+        raise ValueError("convert_scene: clean is for range_source='clean', got range_source=%r" % (range_source,))
     resize_w, resize_h = _pair_of(resize)
     crop_w, crop_h = _pair_of(crop)
     pair, cams64, depths_np, probs_np = load_mvs_output(data_root, probs=prob_mask)
@@ -180,10 +186,10 @@ def convert_scene(data_root, range_source='pcd', pthresh='.7,.7,0', prob_mask=Fa
         return ext_image_path.format(int(ids[i]) + 1 if ext_image_from_one else int(ids[i]))
 
     fused = None
-    if range_source == 'fused' or fused_depth:
+    if range_source in ('fused', 'clean') or fused_depth:
         from .. import fusion as fu
         small = None
-        if range_source == 'fused':
+        if range_source in ('fused', 'clean'):
             small = np.stack([resize_bilinear_u8(load_image_u8(image_path(i)), d_w, d_h) for i in range(total_views)])
         fused = fu.fuse_depths(cams64, depths[:, 0], pair_indices(pair), images=small)
     if range_source == 'range':
@@ -194,6 +200,10 @@ def convert_scene(data_root, range_source='pcd', pthresh='.7,.7,0', prob_mask=Fa
         if len(fused) == 0:
             raise ValueError('convert_scene: the fusion kept no point, so there is no box to take')
         fu.save_points(os.path.join(data_root, 'all_torch.ply'), fused.points, fused.colors)
+        if range_source == 'clean':
+            from ..cloud import clean_fused
+            fused = clean_fused(fused, **(clean or {}))
+            fu.save_points(os.path.join(data_root, 'cut.ply'), fused.points, fused.colors)
         lo, hi = fused.bbox()
         center, size = points_range(torch.stack([lo, hi]).float().cpu())                       # fp32, as the cloud is once it is a PLY file
 
