@@ -660,6 +660,35 @@ int mvsdf_cloud_clean(const double* pts, int64_t n, int32_t k, double knn_ratio,
 int mvsdf_cloud_compact(const double* pts, const uint8_t* colors, const int32_t* a, const int32_t* b, const uint8_t* keep, int64_t n, void* ws,
                         size_t ws_bytes, double* out_pts, uint8_t* out_colors, int32_t* out_a, int32_t* out_b, int64_t cap, void* stream);
 
+/* ---- Mesh rendering (raster.hip; Python: mvsdf_amd/raster.py, which states the definition) ----
+ * A triangle mesh (verts fp32 [nv][3], faces int32 [nf][3], on the device) drawn into `views` cameras of H x W pixels.  P: fp64 [views][4][4] on the
+ * DEVICE, world -> pixels, rows 0..2 used, row 2 the camera depth; pixel (x, y) has its centre at (x + pixel_center, y + pixel_center), pixel_center
+ * 0.5 or 0.0.  fp64 throughout, no clipping (a face with a vertex not in front of its camera is skipped), no back-face culling.
+ * mvsdf_raster_draw fills the workspace's key buffer (mvsdf_raster_workspace_bytes; 0 unless 0 <= nv, nf <= INT32_MAX, 1 <= views <= 65535, H and W
+ * >= 2, H * W and nf * views <= INT32_MAX, views * H * W <= 2^40): per pixel the minimum of (bits(fp32 depth) << 32) | face id over the faces that
+ * cover the pixel centre, so the result does not depend on the schedule.  Faces whose clamped pixel box holds more than large_face_pixels pixels
+ * are compacted to a list and drawn by one wave each; the others by one lane each.  flags: 1 = issue every atomic (no plain-load test before it),
+ * 2 = count the atomics issued and the covered pixels (measurement builds of the call; slower).  The workspace starts with int64 {error bits,
+ * listed (face, view) items, atomics issued, covered pixels}.  Error bits: 1 a camera entry is NaN or infinite, 2 a face refers to a vertex
+ * outside [0, nv) (such a face is not drawn); with any set nothing else is valid.  A chunk of the views is drawn by passing P + 16 * first.
+ * mvsdf_raster_resolve (same workspace, views, H, W) writes depth fp32 [views][H][W] (0 where nothing was drawn) and face int32 (-1).
+ * mvsdf_raster_visibility: vis uint8 [views][nv] = the vertex is in front, the pixel whose centre is nearest lies in the image, holds a depth
+ * D > 0 with z <= D * (1 + depth_tol), and (masks uint8 [views][H][W] or NULL) its mask is set.  The workspace is its 256-byte header (error bit 1).
+ * mvsdf_raster_colors: per vertex, over the views in order, where visible as above: weight (n . g) / |g| with g = centers[v] - X (fp64 [views][3] on
+ * the device) if above cos_min, a zero normal weighing 1 with ignore_normals and skipping the vertex without; images uint8 [views][H][W][3]
+ * sampled bilinearly at (sx - pixel_center, sy - pixel_center); colors fp32 [nv][3] = sum / weights / 255 or the fallback, n_views int32 [nv] the
+ * views that contributed.  No call waits for the host. */
+size_t mvsdf_raster_workspace_bytes(int64_t nv, int64_t nf, int64_t views, int64_t H, int64_t W);
+int mvsdf_raster_draw(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, const double* P, int64_t views, int64_t H, int64_t W,
+                      double pixel_center, int64_t large_face_pixels, int32_t flags, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_raster_resolve(int64_t views, int64_t H, int64_t W, void* ws, size_t ws_bytes, float* depth, int32_t* face, void* stream);
+int mvsdf_raster_visibility(const float* verts, int64_t nv, const double* P, int64_t views, int64_t H, int64_t W, double pixel_center,
+                            const float* depth, const uint8_t* masks, double depth_tol, void* ws, size_t ws_bytes, uint8_t* vis, void* stream);
+int mvsdf_raster_colors(const float* verts, const float* normals, int64_t nv, const double* P, const double* centers, int64_t views, int64_t H,
+                        int64_t W, double pixel_center, const float* depth, const uint8_t* masks, const uint8_t* images, double depth_tol,
+                        double cos_min, int32_t ignore_normals, float fallback_r, float fallback_g, float fallback_b, void* ws, size_t ws_bytes,
+                        float* colors, int32_t* n_views, void* stream);
+
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.
  * raw: fp32 [mvsdf_featext_raw_floats()] on the device, the layers in the order of mvsdf_amd/features.py::LAYERS, each its weight in PyTorch layout

@@ -100,6 +100,12 @@ def lib():
         L.mvsdf_cloud_components.argtypes = [vp, i64, f64, vp, sz, vp, vp]
         L.mvsdf_cloud_clean.argtypes = [vp, i64, i32, f64, f64, f64, vp, sz, vp, vp, vp, vp]
         L.mvsdf_cloud_compact.argtypes = [vp] * 5 + [i64, vp, sz] + [vp] * 4 + [i64, vp]
+        L.mvsdf_raster_workspace_bytes.restype = sz
+        L.mvsdf_raster_workspace_bytes.argtypes = [i64] * 5
+        L.mvsdf_raster_draw.argtypes = [vp, vp, i64, i64, vp, i64, i64, i64, f64, i64, i32, vp, sz, vp]
+        L.mvsdf_raster_resolve.argtypes = [i64, i64, i64, vp, sz, vp, vp, vp]
+        L.mvsdf_raster_visibility.argtypes = [vp, i64, vp, i64, i64, i64, f64, vp, vp, f64, vp, sz, vp, vp]
+        L.mvsdf_raster_colors.argtypes = [vp, vp, i64, vp, vp, i64, i64, i64, f64, vp, vp, vp, f64, f64, i32, f32, f32, f32, vp, sz, vp, vp, vp]
         for fn in ('mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_layer_workspace_bytes'):
             getattr(L, fn).restype = sz
         L.mvsdf_featext_raw_floats.argtypes = []
@@ -141,6 +147,7 @@ EXPORTS = [
     'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit',
     'mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes', 'mvsdf_cloud_knn', 'mvsdf_cloud_components', 'mvsdf_cloud_clean',
     'mvsdf_cloud_compact',
+    'mvsdf_raster_workspace_bytes', 'mvsdf_raster_draw', 'mvsdf_raster_resolve', 'mvsdf_raster_visibility', 'mvsdf_raster_colors',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',

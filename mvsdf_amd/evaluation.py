@@ -69,11 +69,15 @@ def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None, 
 
 
 def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
-             eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None):
+             eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None,
+             color_mesh=False):
     """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
     -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
     view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
-    sparse_mesh / mesh_block / mesh_margin: extract_world_mesh's sparse / block / margin.  -> {'epoch', 'evaldir', 'mesh', 'psnrs'}."""
+    sparse_mesh / mesh_block / mesh_margin: extract_world_mesh's sparse / block / margin.  color_mesh: besides the OBJ (written as without it), the same
+    mesh in the colours of the input photographs as surface_world_coordinates_<epoch>_color.ply (raster.color_mesh_from_scene: image_hd/, the
+    world_mat_i of cameras_hd.npz at pixel_center 0, visibility masked by mask_hd/).  -> {'epoch', 'evaldir', 'mesh', 'psnrs'} (+ 'color_mesh', the
+    coloured Mesh or None, with color_mesh)."""
     from PIL import Image
     from .checkpoint import MODEL_SUBDIR
     from .datasets.device_batches import DeviceBatches
@@ -106,6 +110,11 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     printer('evaluating...')
     model.eval()
     mesh = extract_world_mesh(model, scale_mat, resolution, path=evaldir, epoch=epoch, sparse=sparse_mesh, block=mesh_block, margin=mesh_margin)
+    colored = None
+    if color_mesh and mesh is not None:
+        from . import raster
+        colored = raster.color_mesh_from_scene(mesh, data_dir)
+        colored.export(os.path.join(evaldir, 'surface_world_coordinates_{0}_color.ply'.format(epoch)))
     psnrs = None
     if eval_rendering:
         images_dir = os.path.join(evaldir, 'rendering')
@@ -123,7 +132,10 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
         printer(msg)
         with open(os.path.join(evaldir, 'psnr.txt'), 'w') as f:
             f.write(msg + '\n')
-    return {'epoch': epoch, 'evaldir': evaldir, 'mesh': mesh, 'psnrs': psnrs}
+    res = {'epoch': epoch, 'evaldir': evaldir, 'mesh': mesh, 'psnrs': psnrs}
+    if color_mesh:
+        res['color_mesh'] = colored
+    return res
 
 
 def eval_parser():
@@ -145,6 +157,8 @@ def eval_parser():
                         'component reaches a seed block; mesh.sparse_marching_cubes).')
     p.add_argument('--mesh_block', default=8, type=int, help='With --sparse_mesh: the block edge in grid cells.')
     p.add_argument('--mesh_margin', default=0.5, type=float, help='With --sparse_mesh: the Lipschitz bound assumed of the SDF when seeding blocks.')
+    p.add_argument('--color_mesh', default=False, action='store_true',
+                   help='Also write surface_world_coordinates_<epoch>_color.ply: the mesh in the colours of image_hd/ (mvsdf_amd/raster.py).')
     return p
 
 
@@ -155,4 +169,4 @@ def main(argv=None, printer=print):
     return evaluate(data_dir=opt.data_dir, conf=opt.conf, expname=opt.expname, exps_folder_name=opt.exps_folder, evals_folder_name='evals',
                     timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
                     exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer, sparse_mesh=opt.sparse_mesh, mesh_block=opt.mesh_block,
-                    mesh_margin=opt.mesh_margin)
+                    mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh)
