@@ -637,6 +637,28 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
 int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, int64_t npairs, void* ws, size_t ws_bytes, double* points,
                       uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
 
+/* ---- Plane-sweep stereo (stereo.hip; Python: mvsdf_amd/stereo.py, which states the definition) ----
+ * mvsdf_stereo_normalize: feats fp32 [n][C] on the device -> out fp32 [n][C], every texel divided by its fp64 norm (0 where the norm is 0); hdr: 16
+ * device bytes that receive int64 {0, error bits} (bit 1: a non-finite feature).  mvsdf_stereo_patches: images uint8 [V][H][W][3] -> out fp32
+ * [V][H][W][(2 radius + 1)^2], the mean-free grey patch with a clamped border (0 <= radius <= 15).  Neither waits for the host.
+ * mvsdf_stereo_sweep validates every argument on the host, then (no host wait) sweeps the views views[0 .. nviews) in turn over desc fp32
+ * [V][R][S][C] (device) and writes, for each of them, depths[view][R][S], probs[view][3][R][S], best_k[view][R][S] (-1: no valid hypothesis) and
+ * counts[view][R][S]; other views' outputs are not touched.  It leaves int64 {0, error bits} at the start of the workspace.  Error bits: 1 a
+ * non-finite descriptor, matrix entry, depth_min or interval, 2 a view or pair index outside [0, V), 4 a hypothesis count outside [1, 65535], 8 shapes
+ * (V < 1, R or S < 2, C < 1, R*S > INT32_MAX, R*S*D or V*R*S*C > 2^40, more than 255 sources for a view); with any but a non-finite descriptor set
+ * nothing is launched.  HOST arrays, alive until the caller has read the header: views int32 [nviews]; pair_off int32 [nviews + 1] (pair_off[0] = 0)
+ * and pair_src int32 [pair_off[nviews]], the sources of views[i]; mats fp64 [pair_off[nviews]][16], T_rs per pair slot (row-major 4x4); ranges fp64
+ * [nviews][2] = {depth_min, interval}; nhyp int32 [nviews].  The workspace (mvsdf_stereo_workspace_bytes with D = the largest nhyp and npairs =
+ * pair_off[nviews]; 0 beyond the limits) afterwards holds the last view's score volume, fp64 [D][R][S] with a quiet NaN where a hypothesis is
+ * invalid, at byte offset mvsdf_stereo_volume_offset (same arguments). */
+size_t mvsdf_stereo_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs);
+size_t mvsdf_stereo_volume_offset(int64_t R, int64_t S, int64_t D, int64_t npairs);
+int mvsdf_stereo_normalize(const float* feats, int64_t n, int64_t C, float* out, void* hdr, void* stream);
+int mvsdf_stereo_patches(const uint8_t* images, int64_t V, int64_t H, int64_t W, int32_t radius, float* out, void* stream);
+int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
+                       const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, void* ws, size_t ws_bytes, float* depths,
+                       float* probs, int32_t* best_k, int32_t* counts, void* stream);
+
 /* ---- Point-cloud cleaning (cloud.hip; Python: mvsdf_amd/cloud.py, which states the definition) ----
  * pts fp64 [n][3] on the device, fp64 throughout.  mvsdf_cloud_knn, _components and _clean share one workspace (mvsdf_cloud_clean_workspace_bytes,
  * 0 unless 2 <= n <= INT32_MAX) and leave int64 {n_passed, n_clusters, largest, n_kept, m (fp64 bits), threshold (bits), eps (bits), rounds,

@@ -115,6 +115,12 @@ def lib():
         L.mvsdf_featext_forward.argtypes = [vp, vp, i64, i64, i64, vp, sz, vp, vp, vp, C.c_int, C.c_int, vp]
         L.mvsdf_featext_layer_workspace_bytes.argtypes = [C.c_int] * 5
         L.mvsdf_featext_layer.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, i64, i64, i64, vp, C.c_int, vp, sz, vp, vp]
+        for fn in ('mvsdf_stereo_workspace_bytes', 'mvsdf_stereo_volume_offset'):
+            getattr(L, fn).restype = sz
+            getattr(L, fn).argtypes = [i64] * 4
+        L.mvsdf_stereo_normalize.argtypes = [vp, i64, i64, vp, vp, vp]
+        L.mvsdf_stereo_patches.argtypes = [vp, i64, i64, i64, i32, vp, vp]
+        L.mvsdf_stereo_sweep.argtypes = [vp, i64, i64, i64, i64, i64] + [vp] * 7 + [sz] + [vp] * 5
         L.mvsdf_batch_args_bytes.restype = sz
         L.mvsdf_batch_args_bytes.argtypes = []
         L.mvsdf_batch_gather.argtypes = [vp, vp]
@@ -150,6 +156,7 @@ EXPORTS = [
     'mvsdf_raster_workspace_bytes', 'mvsdf_raster_draw', 'mvsdf_raster_resolve', 'mvsdf_raster_visibility', 'mvsdf_raster_colors',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
+    'mvsdf_stereo_workspace_bytes', 'mvsdf_stereo_volume_offset', 'mvsdf_stereo_normalize', 'mvsdf_stereo_patches', 'mvsdf_stereo_sweep',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',
 ]
 

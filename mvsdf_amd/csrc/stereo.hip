@@ -1,0 +1,346 @@
+// stereo.hip -- on-device plane-sweep stereo: per reference view a depth map and three confidence maps from descriptor maps, cameras and pair lists (the
+// step BYOD.md calls "Run VisMVSNet", as a classical sweep).  Python: mvsdf_amd/stereo.py, which states the definition; tests/stereo_ref.py restates it
+// in numpy.  All arithmetic is fp64 without contraction, in the order the definition writes it.
+//
+// * k_ps_normalize: one lane per texel, unit descriptors rounded to fp32 (a texel of 32 channels is one 128-byte line); sets the error bit on a non-finite
+//   feature.  k_ps_finite: the same check alone, on descriptors that come from the caller.  k_ps_patches: the mean-free grey patch descriptor.
+// * k_ps_score: a 256-lane workgroup owns a 16 x 16 tile of reference pixels (four waves of 8 x 8) and PS_KCHUNK consecutive hypotheses; a lane keeps its
+//   pixel's descriptor in registers as doubles and walks k.  The 8 x 8 pixels of a wave at one k read a patch of about 9 x 9 source texels, and the next k
+//   moves that patch along the epipolar lines by about a texel, so the four-tap gathers are served by the CU's L1 and the XCD's L2 after the first touch.
+//   The dot products use fma(): the product of two fp32 values is exact in fp64, so fma(a, b, t) is t + a*b rounded once, the definition's value bit for
+//   bit (signed zeros included); nothing else is contracted.  Writes score[k][y][x] (a quiet NaN where no source is valid) and the count n_k as a byte.
+// * k_ps_pick: one lane per pixel walks the volume (coalesced over the lanes): winner, refinement, b2, the three confidences.
+//
+// One call sweeps every requested view in turn on the caller's stream; the score volume in the workspace is reused from view to view and holds the last
+// view's scores afterwards.  Every argument is validated on the host before anything is launched; only the finiteness of the descriptors is checked on the
+// device.  No atomics on floating point (the only atomic is the OR of an error bit).
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include "capi_util.h"
+
+#define PS_THREADS 256
+#define PS_TILE 16
+#define PS_KCHUNK 32
+#define PS_HDR 256                                    // bytes at the start of the workspace: int64 {0, error bits}
+#define PS_MAX_D 65535
+#define PS_MAX_SRC 255                                // n_k travels as a byte
+#define PS_MAX_ELEMS (1ll << 40)
+
+enum {
+    PS_ERR_FINITE = 1,      // a non-finite feature, matrix entry, depth_min or interval
+    PS_ERR_PAIR = 2,        // a pair or view index outside [0, V)
+    PS_ERR_DEPTHS = 4,      // D < 1 (or beyond PS_MAX_D)
+    PS_ERR_SHAPE = 8,       // V < 1, R or S < 2, C < 1, a pair list longer than PS_MAX_SRC, sizes beyond the limits
+};
+
+static inline size_t ps_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline long long ps_blocks(long long n, long long per) { return (n + per - 1) / per; }
+
+struct PsLayout {
+    size_t mats, src, vol, cnt, total;
+};
+
+static bool ps_layout(long long R, long long S, long long D, long long npairs, PsLayout* L) {
+    if (R < 2 || S < 2 || D < 1 || D > PS_MAX_D || npairs < 0 || npairs > INT_MAX || R > INT_MAX || S > INT_MAX || R * S > INT_MAX) return false;
+    if (R * S * D > PS_MAX_ELEMS) return false;
+    size_t o = PS_HDR;
+    L->mats = o; o += ps_align((size_t)(npairs > 0 ? npairs : 1) * 16 * 8);
+    L->src = o;  o += ps_align((size_t)(npairs > 0 ? npairs : 1) * 4);
+    L->vol = o;  o += ps_align((size_t)(R * S * D) * 8);
+    L->cnt = o;  o += ps_align((size_t)(R * S * D));
+    L->total = o;
+    return true;
+}
+
+__device__ __forceinline__ double ps_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// one row of a 4x4 matrix times q, in the definition's order
+__device__ __forceinline__ double ps_row(const double* __restrict__ t, double q0, double q1, double q2, double q3) {
+    return ((t[0] * q0 + t[1] * q1) + t[2] * q2) + t[3] * q3;
+}
+
+__global__ __launch_bounds__(PS_THREADS) void k_ps_normalize(const float* __restrict__ f, long long n, int C, float* __restrict__ out, long long* __restrict__ hdr) {
+    const long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float* __restrict__ p = f + i * C;
+    float* __restrict__ o = out + i * C;
+    double s = 0.0;
+    bool bad = false;
+    for (int c = 0; c < C; ++c) {
+        const double v = (double)p[c];
+        bad = bad || !isfinite(v);
+        s = s + v * v;
+    }
+    const double nrm = sqrt(s);
+    for (int c = 0; c < C; ++c) o[c] = nrm > 0.0 ? (float)((double)p[c] / nrm) : 0.0f;
+    if (bad) atomicOr((unsigned long long*)(hdr + 1), (unsigned long long)PS_ERR_FINITE);
+}
+
+__global__ __launch_bounds__(PS_THREADS) void k_ps_finite(const float* __restrict__ f, long long n, long long* __restrict__ hdr) {
+    bool bad = false;
+    for (long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * PS_THREADS) bad = bad || !isfinite(f[i]);
+    if (bad) atomicOr((unsigned long long*)(hdr + 1), (unsigned long long)PS_ERR_FINITE);
+}
+
+// grey = (299 R + 587 G + 114 B) / 1000; the (2 rad + 1)^2 patch around the pixel, border clamped, rows then columns, minus its mean
+__global__ __launch_bounds__(PS_THREADS) void k_ps_patches(const unsigned char* __restrict__ img, long long V, int H, int W, int rad, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+    const long long hw = (long long)H * W;
+    if (i >= V * hw) return;
+    const long long v = i / hw;
+    const int p = (int)(i - v * hw), y = p / W, x = p - y * W;
+    const unsigned char* __restrict__ im = img + v * hw * 3;
+    const int side = 2 * rad + 1;
+    double s = 0.0;
+    for (int dy = -rad; dy <= rad; ++dy) {
+        const int yy = min(max(y + dy, 0), H - 1);
+        for (int dx = -rad; dx <= rad; ++dx) {
+            const int xx = min(max(x + dx, 0), W - 1);
+            const unsigned char* q = im + ((long long)yy * W + xx) * 3;
+            s = s + (double)(299 * (int)q[0] + 587 * (int)q[1] + 114 * (int)q[2]) / 1000.0;
+        }
+    }
+    const double mean = s / (double)(side * side);
+    float* __restrict__ o = out + i * side * side;
+    for (int dy = -rad; dy <= rad; ++dy) {
+        const int yy = min(max(y + dy, 0), H - 1);
+        for (int dx = -rad; dx <= rad; ++dx) {
+            const int xx = min(max(x + dx, 0), W - 1);
+            const unsigned char* q = im + ((long long)yy * W + xx) * 3;
+            *o++ = (float)((double)(299 * (int)q[0] + 587 * (int)q[1] + 114 * (int)q[2]) / 1000.0 - mean);
+        }
+    }
+}
+
+// the four dot products of the reference descriptor with the texels g, g + C (next column), g + row, g + row + C, in channel order
+template <int CFIX>
+__device__ __forceinline__ void ps_dots(const double* ref, const float* __restrict__ fr, const float* __restrict__ g, long long row, int C, double& t00,
+                                        double& t01, double& t10, double& t11) {
+    if (CFIX == 32) {
+        const float4* __restrict__ a = (const float4*)g;
+        const float4* __restrict__ b = (const float4*)(g + 32);
+        const float4* __restrict__ c = (const float4*)(g + row);
+        const float4* __restrict__ d = (const float4*)(g + row + 32);
+        float4 va = a[0], vb = b[0], vc = c[0], vd = d[0];
+        t00 = ref[0] * (double)va.x; t01 = ref[0] * (double)vb.x; t10 = ref[0] * (double)vc.x; t11 = ref[0] * (double)vd.x;
+#define PS_STEP(i, m) t00 = fma(ref[i], (double)va.m, t00); t01 = fma(ref[i], (double)vb.m, t01); t10 = fma(ref[i], (double)vc.m, t10); t11 = fma(ref[i], (double)vd.m, t11);
+        PS_STEP(1, y) PS_STEP(2, z) PS_STEP(3, w)
+#pragma unroll
+        for (int q = 1; q < 8; ++q) {
+            va = a[q]; vb = b[q]; vc = c[q]; vd = d[q];
+            PS_STEP(4 * q, x) PS_STEP(4 * q + 1, y) PS_STEP(4 * q + 2, z) PS_STEP(4 * q + 3, w)
+        }
+#undef PS_STEP
+    } else {
+        double r = (double)fr[0];
+        t00 = r * (double)g[0]; t01 = r * (double)g[C]; t10 = r * (double)g[row]; t11 = r * (double)g[row + C];
+        for (int q = 1; q < C; ++q) {
+            r = (double)fr[q];
+            t00 = fma(r, (double)g[q], t00);
+            t01 = fma(r, (double)g[C + q], t01);
+            t10 = fma(r, (double)g[row + q], t10);
+            t11 = fma(r, (double)g[row + C + q], t11);
+        }
+    }
+}
+
+// scores of view r.  Grid: (tiles in x, tiles in y, chunks of PS_KCHUNK hypotheses); src / mats: the nsrc pair slots of this view (T_rs, row-major 4x4)
+template <int CFIX>
+__global__ __launch_bounds__(PS_THREADS) void k_ps_score(const float* __restrict__ desc, int R, int S, int C, int r, int nsrc, const int* __restrict__ src,
+                                                          const double* __restrict__ mats, double dmin, double interval, int D, double* __restrict__ vol,
+                                                          unsigned char* __restrict__ cnt) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int x = blockIdx.x * PS_TILE + ((w & 1) << 3) + (l & 7), y = blockIdx.y * PS_TILE + ((w >> 1) << 3) + (l >> 3);
+    if (x >= S || y >= R) return;
+    const int k0 = blockIdx.z * PS_KCHUNK, k1 = min(D, k0 + PS_KCHUNK);
+    const long long hw = (long long)R * S, row = (long long)S * C;
+    const long long pix = (long long)y * S + x;
+    const float* __restrict__ fr = desc + ((long long)r * hw + pix) * C;
+    double ref[CFIX ? CFIX : 1];
+    if (CFIX) {
+#pragma unroll
+        for (int c = 0; c < CFIX; ++c) ref[c] = (double)fr[c];
+    }
+    const double X = (double)x + 0.5, Y = (double)y + 0.5;
+    const double smax = (double)(S - 1), rmax = (double)(R - 1);
+    for (int k = k0; k < k1; ++k) {
+        const double d = dmin + (double)k * interval;
+        const double q0 = X * d, q1 = Y * d;
+        int n = 0;
+        double acc = 0.0;
+        for (int j = 0; j < nsrc; ++j) {
+            const double* __restrict__ T = mats + (long long)j * 16;
+            const double p2 = ps_row(T + 8, q0, q1, d, 1.0);
+            if (!(p2 > 0.0)) continue;
+            const double u = ps_row(T, q0, q1, d, 1.0) / p2 - 0.5;
+            const double v = ps_row(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
+            if (!(u >= 0.0 && u <= smax && v >= 0.0 && v <= rmax)) continue;
+            const double x0 = fmin(floor(u), (double)(S - 2)), y0 = fmin(floor(v), (double)(R - 2));
+            const double fx = u - x0, fy = v - y0;
+            const float* __restrict__ g = desc + ((long long)src[j] * hw + (long long)(int)y0 * S + (int)x0) * C;
+            double t00, t01, t10, t11;
+            ps_dots<CFIX>(ref, fr, g, row, C, t00, t01, t10, t11);
+            const double cs = (t00 * (1.0 - fx) + t01 * fx) * (1.0 - fy) + (t10 * (1.0 - fx) + t11 * fx) * fy;
+            acc = acc + cs;
+            ++n;
+        }
+        const long long at = (long long)k * hw + pix;
+        vol[at] = n ? acc / (double)n : ps_nan();
+        cnt[at] = (unsigned char)n;
+    }
+}
+
+// winner, refinement and confidences of every pixel of one view; used = the number of sources the view sweeps
+__global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict__ vol, const unsigned char* __restrict__ cnt, int hw, int D, double dmin,
+                                                         double interval, int used, float* __restrict__ depth, float* __restrict__ prob,
+                                                         int* __restrict__ best_k, int* __restrict__ counts) {
+    const int p = blockIdx.x * PS_THREADS + threadIdx.x;
+    if (p >= hw) return;
+    int ks = -1;
+    double b = -INFINITY;
+    for (int k = 0; k < D; ++k) {
+        const double s = vol[(long long)k * hw + p];
+        if (s > b) { b = s; ks = k; }                                           // NaN (invalid) never compares greater
+    }
+    float dep = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
+    int nk = 0;
+    if (ks >= 0) {
+        bool any = false;
+        double b2 = -INFINITY;
+        for (int k = 0; k < D; ++k) {
+            if (k >= ks - 1 && k <= ks + 1) continue;
+            const double s = vol[(long long)k * hw + p];
+            if (s == s) {
+                any = true;
+                if (s > b2) b2 = s;
+            }
+        }
+        double off = 0.0;
+        if (ks > 0 && ks < D - 1) {
+            const double a = vol[(long long)(ks - 1) * hw + p], c = vol[(long long)(ks + 1) * hw + p];
+            if (a == a && c == c) {
+                const double den = (a - 2.0 * b) + c;
+                if (den < 0.0) off = 0.5 * (a - c) / den;
+            }
+        }
+        dep = (float)(dmin + ((double)ks + off) * interval);
+        p1 = (float)fmin(fmax(b, 0.0), 1.0);
+        if (b <= 0.0) p2 = 0.0f;
+        else if (!any) p2 = 1.0f;
+        else p2 = (float)fmin(fmax(1.0 - fmax(b2, 0.0) / b, 0.0), 1.0);
+        nk = cnt[(long long)ks * hw + p];
+        p3 = (float)((double)nk / (double)used);
+    }
+    depth[p] = dep;
+    prob[p] = p1;
+    prob[hw + p] = p2;
+    prob[2 * (long long)hw + p] = p3;
+    best_k[p] = ks;
+    counts[p] = nk;
+}
+
+static int ps_header(void* hdr, long long err, hipStream_t s, const char* what) {
+    const long long h[2] = {0, err};
+    if (int rc = mv_check(hipMemcpyAsync(hdr, h, sizeof(h), hipMemcpyHostToDevice, s), what)) return rc;
+    return mv_check(hipStreamSynchronize(s), what);             // h lives on this stack frame
+}
+
+extern "C" {
+
+size_t mvsdf_stereo_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs) {
+    PsLayout L;
+    return ps_layout(R, S, D, npairs, &L) ? L.total : 0;
+}
+
+size_t mvsdf_stereo_volume_offset(int64_t R, int64_t S, int64_t D, int64_t npairs) {
+    PsLayout L;
+    return ps_layout(R, S, D, npairs, &L) ? L.vol : 0;
+}
+
+int mvsdf_stereo_normalize(const float* feats, int64_t n, int64_t C, float* out, void* hdr, void* stream) {
+    const char* what = "mvsdf_stereo_normalize";
+    if (!feats || !out || !hdr || n < 1 || C < 1 || C > INT_MAX || n > PS_MAX_ELEMS / C || ps_blocks(n, PS_THREADS) > INT_MAX)
+        return mv_fail(-1, "mvsdf_stereo_normalize: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mv_check(hipMemsetAsync(hdr, 0, 16, s), what)) return rc;
+    hipLaunchKernelGGL(k_ps_normalize, dim3((unsigned)ps_blocks(n, PS_THREADS)), dim3(PS_THREADS), 0, s, feats, (long long)n, (int)C, out, (long long*)hdr);
+    return mv_check(hipGetLastError(), what);
+}
+
+int mvsdf_stereo_patches(const uint8_t* images, int64_t V, int64_t H, int64_t W, int32_t radius, float* out, void* stream) {
+    if (!images || !out || V < 1 || H < 1 || W < 1 || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || radius < 0 || radius > 15 ||
+        V > PS_MAX_ELEMS / (H * W) / ((2 * radius + 1) * (2 * radius + 1)) || ps_blocks(V * H * W, PS_THREADS) > INT_MAX)
+        return mv_fail(-1, "mvsdf_stereo_patches: bad arguments");
+    hipLaunchKernelGGL(k_ps_patches, dim3((unsigned)ps_blocks(V * H * W, PS_THREADS)), dim3(PS_THREADS), 0, (hipStream_t)stream, images, (long long)V, (int)H,
+                       (int)W, (int)radius, out);
+    return mv_check(hipGetLastError(), "mvsdf_stereo_patches");
+}
+
+int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
+                       const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, void* ws, size_t ws_bytes, float* depths,
+                       float* probs, int32_t* best_k, int32_t* counts, void* stream) {
+    const char* what = "mvsdf_stereo_sweep";
+    if (!desc || !views || !pair_off || !mats || !ranges || !nhyp || !ws || !depths || !probs || !best_k || !counts || nviews < 0 || ws_bytes < PS_HDR)
+        return mv_fail(-1, "mvsdf_stereo_sweep: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    // ---- validation, all of it before the first launch ----
+    long long err = 0, npairs = 0, dmax = 1;
+    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > INT_MAX || pair_off[0] != 0) err |= PS_ERR_SHAPE;
+    else {
+        for (long long i = 0; i < nviews; ++i) {
+            const long long len = (long long)pair_off[i + 1] - pair_off[i];
+            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
+            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
+            if (nhyp[i] < 1 || nhyp[i] > PS_MAX_D) err |= PS_ERR_DEPTHS;
+            else if (nhyp[i] > dmax) dmax = nhyp[i];
+            if (!isfinite(ranges[2 * i]) || !isfinite(ranges[2 * i + 1])) err |= PS_ERR_FINITE;
+        }
+        npairs = pair_off[nviews];
+    }
+    PsLayout L;
+    if (!(err & PS_ERR_SHAPE) && (!ps_layout(R, S, dmax, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
+        err |= PS_ERR_SHAPE;
+    if (!(err & PS_ERR_SHAPE)) {
+        for (long long k = 0; k < npairs; ++k)
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
+        for (long long k = 0; k < npairs * 16; ++k)
+            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
+    }
+    if (err) return ps_header(ws, err, s, what);
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_sweep: workspace too small (mvsdf_stereo_workspace_bytes)");
+    // ---- uploads and launches ----
+    char* w = (char*)ws;
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what))) return rc;
+    if (npairs > 0) {
+        if ((rc = mv_check(hipMemcpyAsync(w + L.mats, mats, (size_t)npairs * 16 * 8, hipMemcpyHostToDevice, s), what))) return rc;
+        if ((rc = mv_check(hipMemcpyAsync(w + L.src, pair_src, (size_t)npairs * 4, hipMemcpyHostToDevice, s), what))) return rc;
+    }
+    const long long hw = R * S, total = V * hw * C;
+    long long fb = ps_blocks(total, PS_THREADS);
+    if (fb > 2048) fb = 2048;
+    hipLaunchKernelGGL(k_ps_finite, dim3((unsigned)fb), dim3(PS_THREADS), 0, s, desc, total, (long long*)ws);
+    const bool fast = C == 32 && ((uintptr_t)desc & 15) == 0;                 // 128-byte texels read as float4
+    double* vol = (double*)(w + L.vol);
+    unsigned char* cnt = (unsigned char*)(w + L.cnt);
+    for (long long i = 0; i < nviews; ++i) {
+        const int r = views[i], D = nhyp[i], nsrc = pair_off[i + 1] - pair_off[i];
+        const int* src = (const int*)(w + L.src) + pair_off[i];
+        const double* T = (const double*)(w + L.mats) + (long long)pair_off[i] * 16;
+        const dim3 grid((unsigned)ps_blocks(S, PS_TILE), (unsigned)ps_blocks(R, PS_TILE), (unsigned)ps_blocks(D, PS_KCHUNK));
+        if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_sweep: R beyond the grid limit");
+        if (fast)
+            hipLaunchKernelGGL(k_ps_score<32>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
+                               vol, cnt);
+        else
+            hipLaunchKernelGGL(k_ps_score<0>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
+                               vol, cnt);
+        hipLaunchKernelGGL(k_ps_pick, dim3((unsigned)ps_blocks(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)vol, (const unsigned char*)cnt, (int)hw,
+                           D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw, probs + (long long)r * 3 * hw, best_k + (long long)r * hw,
+                           counts + (long long)r * hw);
+    }
+    return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
+}
+
+}  // extern "C"

@@ -1,0 +1,262 @@
+"""Plane-sweep stereo on the device: the step the reference's BYOD.md calls "Run VisMVSNet" (a depth map and three probability maps per view), as a
+classical sweep over descriptor maps.  Vis-MVSNet's cost-volume network and its weights are not part of the reference tree, so this is NOT
+Vis-MVSNet: the three maps written here are confidences of a plane sweep, not Vis-MVSNet's probabilities, and BYOD.md's thresholds .8,.7,.8 do not
+suit them (the thresholds that do, chosen on the test scene: PTHRESH below and DESIGN.md).  What they share is the file layout, so
+prepare.load_mvs_output, tools/fusion.py and tools/vismvsnet2mvsdf.py read the output as they are.  Kernels: csrc/stereo.hip (the design:
+DESIGN.md); tests/stereo_ref.py restates every step in numpy.
+
+Inputs: feats fp32 [V,R,S,C] channels-last (features.extract_features(...).permute(0, 2, 3, 1), or patch_descriptors), any C >= 1; cams fp64
+[V,2,4,4] at feature-map scale as utils.io.load_cam / scale_camera return them, row 3 of cams[v,1] = depth_min, interval, number of hypotheses D,
+depth_max; pairs a list of V lists of view indices (nearest first), of which the first num_src are used.
+
+The definition (fp64 throughout, in the order written, no FMA contraction; fp32 inputs are promoted exactly):
+
+- Descriptors (normalize_descriptors).  n = sqrt(f_0*f_0 + f_1*f_1 + ...) summed in channel order from 0; f^_c = fp32(f_c / n) where n > 0, else 0.
+  The descriptor is rounded to fp32 and stored, so a texel of 32 channels is one 128-byte line.  plane_sweep takes descriptors as they are given.
+- Hypotheses of reference view r: d_k = depth_min + k*interval, k = 0..D-1, from cams[r,1,3].
+- Matrices, pixel convention and the row product are fusion.py's: P_v = K4_v @ E_v, T_rs = P_s @ inv(P_r) (numpy fp64 on the host); pixel (x, y) sits
+  at X = x + 0.5, Y = y + 0.5; a matrix row times q is ((t0*q0 + t1*q1) + t2*q2) + t3*q3.
+- Score of source s at (x, y, k), d = d_k: p = T_rs (X*d, Y*d, d, 1); the source is valid iff p2 > 0 and, with u = p0/p2 - 0.5, v = p1/p2 - 0.5,
+  0 <= u <= S-1 and 0 <= v <= R-1.  x0 = min(floor(u), S-2), y0 = min(floor(v), R-2), fx = u - x0, fy = v - y0;
+  t_ij = f^_r[0]*f^_s[y0+i, x0+j][0] + f^_r[1]*f^_s[y0+i, x0+j][1] + ... (from the first product on, in channel order);
+  c_s = (t00*(1-fx) + t01*fx)*(1-fy) + (t10*(1-fx) + t11*fx)*fy.
+- Aggregate: n_k = the number of valid sources; score_k = (0 + c_s1 + c_s2 + ..., valid sources in pair order) / n_k where n_k >= 1; otherwise the
+  hypothesis is invalid (NaN in the score volume).
+- Winner: k* = the valid k of greatest score, compared with a strict > from minus infinity on, so the lowest k wins a tie.  No valid k: depth and
+  the three confidences are 0, best_k = -1, counts = 0.
+- Refinement, only where 0 < k* < D-1 and k*-1 and k*+1 are valid: a, b, c = score[k*-1], score[k*], score[k*+1], den = (a - 2*b) + c,
+  off = (0.5*(a - c))/den if den < 0, else 0 (also wherever there is no refinement).  depth = fp32(depth_min + (k* + off)*interval).
+- Confidences, fp32 in [0, 1]: prob1 = min(max(b, 0), 1).  prob2 = 0 if b <= 0, else min(max(1 - max(b2, 0)/b, 0), 1) with b2 the greatest score
+  over the valid k with |k - k*| >= 2, and 1 where there is no such k.  prob3 = n_k* / (the number of sources used for r = min(num_src,
+  len(pairs[r]))).  counts holds n_k*.
+- patch_descriptors: grey = (299 R + 587 G + 114 B)/1000; the (2 radius + 1)^2 grey values around the pixel, rows then columns, coordinates clamped
+  to the image; mean = (0 + g_0 + g_1 + ...)/(2 radius + 1)^2; channel i = fp32(g_i - mean).
+
+Non-finite features or cameras, R or S below 2, D < 1 and a pair index outside [0, V) raise ValueError.
+
+Not built: Vis-MVSNet's learned regularisation, cascaded (coarse-to-fine) sweeps, visibility-weighted aggregation.
+"""
+import os
+
+import numpy as np
+import torch
+
+from ._lib import check, lib, MvsdfError
+from .fusion import projection_matrices
+from .mesh import _header, _stream, _vp
+
+PTHRESH = (0.7, 0.02, 0.9)        # thresholds on prob1, prob2, prob3 that suit these confidences (chosen on tests/stereo_scene.py: DESIGN.md)
+MAX_SRC, MAX_D = 255, 65535
+
+
+class Sweep:
+    """The result of plane_sweep: depths fp32 [V,R,S], probs fp32 [V,3,R,S], best_k int32 [V,R,S] (-1: no valid hypothesis), counts int32 [V,R,S]
+    (n_k*), all on the device and zero (best_k -1) for views that were not swept; scores: fp64 [D,R,S] of the last view swept (NaN where a
+    hypothesis is invalid) or None."""
+
+    def __init__(self, depths, probs, best_k, counts, scores=None):
+        self.depths, self.probs, self.best_k, self.counts, self.scores = depths, probs, best_k, counts, scores
+
+
+def _errors(err, what):
+    if err & 1:
+        raise ValueError('%s: a feature or a camera entry is NaN or infinite' % what)
+    if err & 2:
+        raise ValueError('%s: a pair or view index is outside [0, V)' % what)
+    if err & 4:
+        raise ValueError('%s: the number of depth hypotheses must be in [1, %d]' % (what, MAX_D))
+    if err & 8:
+        raise ValueError('%s: shapes disagree or are out of range (V >= 1, R and S >= 2, C >= 1, at most %d sources)' % (what, MAX_SRC))
+    if err:
+        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+
+
+def _feature_tensor(feats, what):
+    """-> (fp32 contiguous device tensor [V,R,S,C], device); host input is checked for finiteness here, before the GPU is touched"""
+    f = torch.as_tensor(feats)
+    if f.dim() != 4:
+        raise ValueError('%s: features must be [V, R, S, C], got shape %s' % (what, tuple(f.shape)))
+    V, R, S, C = f.shape
+    if V < 1 or R < 2 or S < 2 or C < 1:
+        raise ValueError('%s: features must be at least 2 x 2 texels of one channel (and V >= 1), got shape %s' % (what, tuple(f.shape)))
+    if not f.is_cuda and not bool(torch.isfinite(f).all()):
+        raise ValueError('%s: a feature is NaN or infinite' % what)
+    dev = f.device if f.is_cuda else torch.device('cuda')
+    return f.to(dev, torch.float32).contiguous(), dev
+
+
+def normalize_descriptors(feats):
+    """feats [V,R,S,C] -> the definition's unit descriptors, fp32 [V,R,S,C] on the device"""
+    what = 'normalize_descriptors'
+    f, dev = _feature_tensor(feats, what)
+    out = torch.empty_like(f)
+    hdr = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib().mvsdf_stereo_normalize(_vp(f), f.numel() // f.shape[3], f.shape[3], _vp(out), _vp(hdr), _stream(f)), 'mvsdf_stereo_normalize')
+    _errors(int(hdr.cpu()[1]), what)
+    return out
+
+
+def patch_descriptors(images_u8, radius=2):
+    """images uint8 [V,H,W,3] -> the definition's mean-free grey patches, fp32 [V,H,W,(2 radius + 1)^2] on the device (not normalised)"""
+    what = 'patch_descriptors'
+    img = torch.as_tensor(images_u8)
+    if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8 or min(img.shape[:3]) < 1:
+        raise ValueError('%s: images must be uint8 [V, H, W, 3], got %s %s' % (what, img.dtype, tuple(img.shape)))
+    radius = int(radius)
+    if radius < 0 or radius > 15:
+        raise ValueError('%s: radius must be in [0, 15], got %d' % (what, radius))
+    img = img.to(img.device if img.is_cuda else torch.device('cuda')).contiguous()
+    V, H, W, _ = img.shape
+    out = torch.empty(V, H, W, (2 * radius + 1) ** 2, dtype=torch.float32, device=img.device)
+    check(lib().mvsdf_stereo_patches(_vp(img), V, H, W, radius, _vp(out), _stream(img)), 'mvsdf_stereo_patches')
+    return out
+
+
+def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False):
+    """The module's definition -> Sweep.  Device tensors are used where they are (the stream is theirs); numpy / CPU input is copied to the GPU.
+    views: the reference views to sweep, in this order (default: all); scores=True also returns the score volume of the last of them."""
+    what = 'plane_sweep'
+    cams = np.asarray(cams.cpu() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
+    f = torch.as_tensor(descriptors)
+    if f.dim() == 4 and cams.shape != (f.shape[0], 2, 4, 4):
+        raise ValueError('%s: cams must be [V, 2, 4, 4] for V = %d descriptor maps, got shape %s' % (what, f.shape[0], cams.shape))
+    if f.dim() == 4 and len(pairs) != f.shape[0]:
+        raise ValueError('%s: pairs must hold one list per view (%d), got %d' % (what, f.shape[0], len(pairs)))
+    if not np.isfinite(cams).all():
+        raise ValueError('%s: a camera entry is NaN or infinite' % what)
+    num_src = int(num_src)
+    if num_src < 0:
+        raise ValueError('%s: num_src must be >= 0' % what)
+    V = len(pairs)
+    views = list(range(V)) if views is None else [int(v) for v in views]
+    if any(v < 0 or v >= V for v in views):
+        raise ValueError('%s: a view index is outside [0, %d)' % (what, V))
+    used = [[int(s) for s in pairs[v]][:num_src] for v in views]
+    if any(s < 0 or s >= V for q in used for s in q):
+        raise ValueError('%s: a pair index is outside [0, %d)' % (what, V))
+    if any(len(q) > MAX_SRC for q in used):
+        raise ValueError('%s: at most %d sources per view' % (what, MAX_SRC))
+    nhyp = cams[views, 1, 3, 2] if views else np.zeros(0)
+    if (nhyp != np.floor(nhyp)).any() or (nhyp < 1).any() or (nhyp > MAX_D).any():
+        raise ValueError('%s: the number of depth hypotheses (cams[v, 1, 3, 2]) must be a whole number in [1, %d]' % (what, MAX_D))
+    f, dev = _feature_tensor(f, what)
+    V, R, S, C = f.shape
+    try:
+        P, Pinv = projection_matrices(cams)
+    except np.linalg.LinAlgError as e:
+        raise ValueError('%s: a camera has a singular projection' % what) from e
+    off = np.zeros(len(views) + 1, np.int32)
+    off[1:] = np.cumsum([len(q) for q in used])
+    src = np.asarray([s for q in used for s in q], np.int32)
+    npairs = len(src)
+    mats = np.empty(max(npairs, 1) * 16, np.float64)
+    k = 0
+    for r, q in zip(views, used):
+        for s in q:
+            mats[k * 16:k * 16 + 16] = (P[s] @ Pinv[r]).reshape(-1)
+            k += 1
+    if not np.isfinite(mats[:npairs * 16]).all():
+        raise ValueError('%s: a camera entry is NaN or infinite' % what)
+    vw = np.asarray(views, np.int32)
+    ranges = np.ascontiguousarray(cams[views, 1, 3, :2] if views else np.zeros((0, 2)), np.float64)
+    nh = np.asarray(nhyp, np.int32)
+    dmax = int(nh.max()) if len(nh) else 1
+    size = lib().mvsdf_stereo_workspace_bytes(R, S, dmax, npairs)
+    if size == 0:
+        raise ValueError('%s: %d x %d texels of %d hypotheses are beyond the limits (R*S < 2^31, R*S*D <= 2^40)' % (what, R, S, dmax))
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    depths = torch.zeros(V, R, S, dtype=torch.float32, device=dev)
+    probs = torch.zeros(V, 3, R, S, dtype=torch.float32, device=dev)
+    best_k = torch.full((V, R, S), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros(V, R, S, dtype=torch.int32, device=dev)
+    if not views:
+        return Sweep(depths, probs, best_k, counts, None)
+    check(lib().mvsdf_stereo_sweep(_vp(f), V, R, S, C, len(views), vw.ctypes.data, off.ctypes.data, src.ctypes.data if npairs else None,
+                                   mats.ctypes.data, ranges.ctypes.data, nh.ctypes.data, _vp(ws), size, _vp(depths), _vp(probs), _vp(best_k),
+                                   _vp(counts), _stream(f)), 'mvsdf_stereo_sweep')
+    _, err = _header(ws, 2)                                                 # the one wait of the call; the host arrays live until here
+    _errors(err, what)
+    vol = None
+    if scores:
+        at = lib().mvsdf_stereo_volume_offset(R, S, dmax, npairs)
+        D = int(nh[-1])
+        vol = ws[at:at + D * R * S * 8].view(torch.float64).view(D, R, S).clone()
+    return Sweep(depths, probs, best_k, counts, vol)
+
+
+def _write_cam(path, cam):
+    """MVSNet's camera text with the four depth words (depth_min, interval, D, depth_max), which load_cam reads back"""
+    txt = 'extrinsic\n' + '\n'.join(' '.join('%.17g' % v for v in r) for r in cam[0]) + '\n\nintrinsic\n'
+    txt += '\n'.join(' '.join('%.17g' % v for v in r) for r in cam[1][:3, :3])
+    txt += '\n\n%.17g %.17g %d %.17g\n' % (cam[1, 3, 0], cam[1, 3, 1], int(cam[1, 3, 2]), cam[1, 3, 3])
+    with open(path, 'w') as f:
+        f.write(txt)
+
+
+def _find(folder, stem, exts):
+    for e in exts:
+        p = os.path.join(folder, stem + e)
+        if os.path.exists(p):
+            return p
+    raise FileNotFoundError('estimate_scene: none of %s in %s' % (', '.join(stem + e for e in exts), folder))
+
+
+def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', num_src=2, max_d=256, interval_scale=1, resize=None, crop=None,
+                   radius=2):
+    """BYOD.md's "Run VisMVSNet" step by plane sweep.  Reads <data_root>/images/<id:08>.jpg|png, cams/<id:08>_cam.txt and pair.txt; resizes
+    (prepare.resize_bilinear_u8) and centre-crops the images (resize / crop: 'W,H' or (W, H), default: as they are) and moves the cameras along;
+    computes descriptors at half that size, as Vis-MVSNet's depth maps are: with feat_ckpt FeatExt.from_checkpoint + extract_features, else
+    (descriptor='patch') patch_descriptors(radius) of the image resized to half; sweeps every view and writes into result_dir <id:08>_flow3.pfm,
+    <id:08>_flow{1,2,3}_prob.pfm, cam_<id:08>_flow3.txt (at depth-map scale), <id:08>.jpg (the cropped image) and pair.txt -> the Sweep."""
+    from PIL import Image
+    from .datasets import prepare
+    from .utils import io as sio
+    what = 'estimate_scene'
+    if feat_ckpt is None and descriptor != 'patch':
+        raise ValueError("%s: descriptor must be 'patch' where no feat_ckpt is given, got %r" % (what, descriptor))
+    pair_path = os.path.join(data_root, 'pair.txt')
+    pair = sio.load_pair(pair_path)
+    ids = pair['id_list']
+    images, cams = [], []
+    for vid in ids:
+        z = vid.zfill(8)
+        img = prepare.load_image_u8(_find(os.path.join(data_root, 'images'), z, ('.jpg', '.png')))
+        cam = sio.load_cam(os.path.join(data_root, 'cams', '%s_cam.txt' % z), max_d, interval_scale)
+        h0, w0 = img.shape[:2]
+        rw, rh = prepare._pair_of(resize) if resize is not None else (w0, h0)
+        cw, ch = prepare._pair_of(crop) if crop is not None else (rw, rh)
+        if cw > rw or ch > rh:
+            raise ValueError('%s: crop %d,%d is larger than the resized image %d,%d' % (what, cw, ch, rw, rh))
+        img = prepare.center_crop(prepare.resize_bilinear_u8(img, rw, rh), cw, ch)
+        cam = sio.scale_camera(cam, (rw / w0, rh / h0))
+        cam[1, 0, 2] -= (rw - cw) // 2
+        cam[1, 1, 2] -= (rh - ch) // 2
+        images.append(np.ascontiguousarray(img))
+        cams.append(cam)
+    if len({im.shape for im in images}) != 1:
+        raise ValueError('%s: the images differ in size after resize / crop; give resize and crop' % what)
+    H, W = images[0].shape[:2]
+    if feat_ckpt is not None:
+        from .features import FeatExt, extract_features, output_hw
+        R, S = output_hw(H, W)
+        net = FeatExt.from_checkpoint(feat_ckpt).cuda()
+        rgb = torch.from_numpy(np.stack(images)).permute(0, 3, 1, 2).float() / 255                # ImageNet normalisation, as SceneDataset feeds FeatExt
+        rgb = (rgb - torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)) / torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
+        feats = extract_features(net, rgb).permute(0, 2, 3, 1).contiguous()
+    else:
+        R, S = (H + 1) // 2, (W + 1) // 2
+        feats = patch_descriptors(np.stack([prepare.resize_bilinear_u8(im, S, R) for im in images]), radius)
+    cams = np.stack([sio.scale_camera(c, (S / W, R / H)) for c in cams])
+    sweep = plane_sweep(normalize_descriptors(feats), cams, prepare.pair_indices(pair), num_src=num_src)
+    os.makedirs(result_dir, exist_ok=True)
+    depths, probs = sweep.depths.cpu().numpy(), sweep.probs.cpu().numpy()
+    for i, vid in enumerate(ids):
+        z = vid.zfill(8)
+        sio.write_pfm(os.path.join(result_dir, '%s_flow3.pfm' % z), np.ascontiguousarray(depths[i]))
+        for j in range(3):
+            sio.write_pfm(os.path.join(result_dir, '%s_flow%d_prob.pfm' % (z, j + 1)), np.ascontiguousarray(probs[i, j]))
+        _write_cam(os.path.join(result_dir, 'cam_%s_flow3.txt' % z), cams[i])
+        Image.fromarray(images[i]).save(os.path.join(result_dir, '%s.jpg' % z), quality=95)
+    with open(pair_path) as fi, open(os.path.join(result_dir, 'pair.txt'), 'w') as fo:
+        fo.write(fi.read())
+    return sweep

@@ -1,0 +1,57 @@
+"""Depth and confidence maps by plane sweep on the device (mvsdf_amd/stereo.py, which states the algorithm), in place of the "Run VisMVSNet" step of
+the reference's BYOD.md; the flags are those of its test.py call.
+
+    python tools/mvs_depth.py --data_root DATA/SCAN --dataset_name general --num_src 2 --max_d 256 --interval_scale 1 --resize 768,576
+                              --crop 768,576 --write_result --result_dir OUT [--load_path vismvsnet.ckpt] [--descriptor patch] [--radius 2]
+
+Reads DATA/SCAN/images/<id:08>.jpg|png, cams/<id:08>_cam.txt and pair.txt; writes OUT/<id:08>_flow3.pfm, <id:08>_flow{1,2,3}_prob.pfm,
+cam_<id:08>_flow3.txt, <id:08>.jpg and pair.txt, which tools/fusion.py and tools/vismvsnet2mvsdf.py read.  With --load_path the descriptors are
+FeatExt's feature maps from that Vis-MVSNet checkpoint, else mean-free grey patches.  The three maps are confidences of a plane sweep, not
+Vis-MVSNet's probabilities: pass --pthresh .7,.02,.9 to the two tools that follow, not BYOD.md's .8,.7,.8.  --model_name is accepted and ignored (there is
+one sweep); --dataset_name other than general and a run without --write_result are refused.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--data_root', type=str, required=True)
+    ap.add_argument('--result_dir', type=str, required=True)
+    ap.add_argument('--dataset_name', type=str, default='general')
+    ap.add_argument('--model_name', type=str, default=None)
+    ap.add_argument('--load_path', type=str, default=None, help="a Vis-MVSNet checkpoint: FeatExt's feature maps as descriptors")
+    ap.add_argument('--descriptor', type=str, default='patch', choices=['patch'])
+    ap.add_argument('--radius', type=int, default=2)
+    ap.add_argument('--num_src', type=int, default=2)
+    ap.add_argument('--max_d', type=int, default=256)
+    ap.add_argument('--interval_scale', type=float, default=1.0)
+    ap.add_argument('--resize', type=str, default=None)
+    ap.add_argument('--crop', type=str, default=None)
+    ap.add_argument('--write_result', action='store_true', default=False)
+    a = ap.parse_args(argv)
+    if a.dataset_name != 'general':
+        ap.error('--dataset_name %s: only general (images/, cams/, pair.txt) is built' % a.dataset_name)
+    if not a.write_result:
+        ap.error('nothing to do without --write_result, as BYOD.md passes it')
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from mvsdf_amd import stereo
+    sweep = stereo.estimate_scene(a.data_root, a.result_dir, feat_ckpt=a.load_path, descriptor=a.descriptor, num_src=a.num_src, max_d=a.max_d,
+                                  interval_scale=a.interval_scale, resize=a.resize, crop=a.crop, radius=a.radius)
+    t = stereo.PTHRESH
+    p = sweep.probs
+    kept = (p[:, 0] > t[0]) & (p[:, 1] > t[1]) & (p[:, 2] > t[2]) & (sweep.depths > 0)
+    print('%d views of %d x %d -> %s; %.1f %% of the pixels pass --pthresh %s' % (p.shape[0], p.shape[2], p.shape[3], a.result_dir,
+                                                                                 100.0 * float(kept.float().mean()), ','.join('%g' % v for v in t)))
+
+
+if __name__ == '__main__':
+    main()
