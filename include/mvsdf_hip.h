@@ -735,6 +735,31 @@ int mvsdf_featext_layer(int kind, const float* weight, const float* bias, int co
                         int64_t n, int64_t h, int64_t w, const float* res, int relu, void* ws, size_t ws_bytes, float* out, void* stream);
 
 
+/* ---- View selection (viewsel.hip; Python: mvsdf_amd/viewsel.py, which states the definition) ----
+ * The pairwise score behind pair.txt from points fp64 [P][3], camera centres fp64 [V][3] and visibility, all on the device; fp64 throughout with the
+ * written-out atan2 / exp of csrc/det_math64.h.  1 <= V <= 65535, 0 <= P <= INT32_MAX.  hdr: 256 device bytes, int64 {0, error bits}; the two pack
+ * calls reset it, the other calls OR into it, and the caller reads it once at the end.  Error bits: 1 a non-finite point, centre or extrinsic entry,
+ * 2 a track entry outside [0, V) (or track offsets that do not ascend within [0, nnz]), 4 V or P outside the limits above (nothing is launched).
+ * mvsdf_viewsel_pack_dense: vis uint8 [V][P] (non-zero = seen) -> bits uint64 [P][ceil(V / 64)] (mvsdf_viewsel_bits_bytes; 0 beyond the limits), bit
+ * v mod 64 of word v / 64 of row p.  mvsdf_viewsel_pack_tracks: the same from CSR tracks, track_off int64 [P + 1] and track_view int32 [nnz]; a
+ * duplicate entry counts once.
+ * mvsdf_viewsel_scores: scores fp64 [V][V] (symmetric, zero diagonal) and counts int64 [V][V] (common points; the diagonal: the points a view sees);
+ * the workspace (mvsdf_viewsel_workspace_bytes) holds the int64 sums of the quantised weights.  theta0 finite, sigma1 and sigma2 finite and > 0.
+ * mvsdf_viewsel_depths: z fp64 [nviews][P] for the views first .. first + nviews: ((e0*x + e1*y) + e2*z) + e3 with e = ext_row2[v] (fp64 [V][4] on the
+ * device, row 2 of the extrinsic) where view v sees the point, +inf elsewhere.  P >= 1.  No call waits for the host (but for error bit 4).
+ * mvsdf_viewsel_weights_host is a HOST function (no GPU needed): theta [n] in degrees and the quantised weight wq [n] of the definition for n pairs
+ * of vectors a = c_i - p, b = c_j - p (fp64 [n][3], host memory), evaluated by the functions the kernel runs. */
+size_t mvsdf_viewsel_bits_bytes(int64_t V, int64_t P);
+size_t mvsdf_viewsel_workspace_bytes(int64_t V);
+int mvsdf_viewsel_pack_dense(const uint8_t* vis, int64_t V, int64_t P, void* bits, void* hdr, void* stream);
+int mvsdf_viewsel_pack_tracks(const int64_t* track_off, const int32_t* track_view, int64_t nnz, int64_t V, int64_t P, void* bits, void* hdr,
+                              void* stream);
+int mvsdf_viewsel_scores(const double* points, const double* centers, const void* bits, int64_t V, int64_t P, double theta0, double sigma1,
+                         double sigma2, void* ws, size_t ws_bytes, double* scores, int64_t* counts, void* hdr, void* stream);
+int mvsdf_viewsel_depths(const double* points, const void* bits, const double* ext_row2, int64_t V, int64_t P, int64_t first, int64_t nviews,
+                         double* z, void* hdr, void* stream);
+int mvsdf_viewsel_weights_host(const double* a, const double* b, int64_t n, double theta0, double sigma1, double sigma2, double* theta, int64_t* wq);
+
 /* ---- Training batches assembled on the device (batch_kernels.hip; Python: mvsdf_amd/datasets/device_batches.py) ----
  * One launch builds the whole step batch of SceneDataset.__getitem__ + collate_fn (mvsdf_amd/datasets/scene_dataset.py) for B views from pools that
  * stay on the device for the whole run: per view b (v = views[b]) and per sampled pixel p (id = pix[p], or p itself when pix is NULL: full images)

@@ -121,6 +121,15 @@ def lib():
         L.mvsdf_stereo_normalize.argtypes = [vp, i64, i64, vp, vp, vp]
         L.mvsdf_stereo_patches.argtypes = [vp, i64, i64, i64, i32, vp, vp]
         L.mvsdf_stereo_sweep.argtypes = [vp, i64, i64, i64, i64, i64] + [vp] * 7 + [sz] + [vp] * 5
+        L.mvsdf_viewsel_bits_bytes.restype = sz
+        L.mvsdf_viewsel_bits_bytes.argtypes = [i64, i64]
+        L.mvsdf_viewsel_workspace_bytes.restype = sz
+        L.mvsdf_viewsel_workspace_bytes.argtypes = [i64]
+        L.mvsdf_viewsel_pack_dense.argtypes = [vp, i64, i64, vp, vp, vp]
+        L.mvsdf_viewsel_pack_tracks.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+        L.mvsdf_viewsel_scores.argtypes = [vp, vp, vp, i64, i64, f64, f64, f64, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_viewsel_depths.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp]
+        L.mvsdf_viewsel_weights_host.argtypes = [vp, vp, i64, f64, f64, f64, vp, vp]
         L.mvsdf_batch_args_bytes.restype = sz
         L.mvsdf_batch_args_bytes.argtypes = []
         L.mvsdf_batch_gather.argtypes = [vp, vp]
@@ -157,6 +166,8 @@ EXPORTS = [
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_stereo_workspace_bytes', 'mvsdf_stereo_volume_offset', 'mvsdf_stereo_normalize', 'mvsdf_stereo_patches', 'mvsdf_stereo_sweep',
+    'mvsdf_viewsel_bits_bytes', 'mvsdf_viewsel_workspace_bytes', 'mvsdf_viewsel_pack_dense', 'mvsdf_viewsel_pack_tracks', 'mvsdf_viewsel_scores',
+    'mvsdf_viewsel_depths', 'mvsdf_viewsel_weights_host',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',
 ]
 
