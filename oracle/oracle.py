@@ -137,6 +137,10 @@ def trace(net, cam_loc, dirs, object_mask, training, minsdf_steps=None, interval
     """RayTracing.forward (ray_tracing.py:27-98) -> points[R,3], mask[R] bool, dists[R], rows[4]
     (+ margins[R,2] with margins=True: per ray min |sdf| and min |sdf - threshold| over every evaluation the ray made -- how far its
     sign / convergence decisions were from flipping, the quantities make_golden.py::MarginRecorder takes from the reference)."""
+    if not 2 <= int(n_steps) <= 1024:                      # the ranges mvsdf_trace accepts (trace_ray's per-ray sample arrays hold 1024)
+        raise ValueError('oracle.trace: n_steps %r outside [2, 1024]' % (n_steps,))
+    if not 0 <= int(line_step_iters) <= 30:
+        raise ValueError('oracle.trace: line_step_iters %r outside [0, 30]' % (line_step_iters,))
     cam_loc, dirs = _f(cam_loc), _f(dirs)
     B, P = dirs.shape[:2]
     R = B * P

@@ -602,6 +602,7 @@ static void point_at(const float *c, const float *d, float t, float *p) {   /* c
 typedef struct {
     float r, thr, line_search_step; int line_step_iters, st_iters, n_steps, n_secant; float dist_clip;
 } trace_params;
+#define ORC_MAX_STEPS 1024            /* the kernels' range (mvsdf_trace): 2 <= n_steps <= 1024, 0 <= line_step_iters <= 30 (1 << k stays an int) */
 
 /* ---- RayTracing.forward for ONE ray (ray_tracing.py:27-98), every global loop condition restated as a per-ray
  * predicate (finished rays are no-ops in the reference's masked updates).
@@ -650,7 +651,7 @@ static void trace_ray(const sdf_ctx *sc, const trace_params *tp, const float *c,
     if (sampler) {                                        /* ray_sampler (ray_tracing.py:198-258) */
         int n = tp->n_steps;
         float smin = acc_s, smax = acc_e;
-        float zi[512] = {0}, sv[512] = {0};
+        float zi[ORC_MAX_STEPS] = {0}, sv[ORC_MAX_STEPS] = {0};   /* n <= ORC_MAX_STEPS: orc_trace_m refuses anything else */
         for (int i = 0; i < n; ++i) {
             zi[i] = smin + intervals[i] * (smax - smin);
             point_at(c, d, zi[i], p);
@@ -720,6 +721,10 @@ void orc_trace_m(int analytic, int n_layers, const int *in, const int *out, int 
                  float r, float thr, float line_search_step, int line_step_iters, int st_iters, int n_steps,
                  int n_secant, float dist_clip, int training, const float *intervals, const float *minsdf_steps,
                  float *points, uint8_t *mask, float *dists, long long *rows, float *margins /* [R][2] or NULL */) {
+    if (n_steps < 2 || n_steps > ORC_MAX_STEPS || line_step_iters < 0 || line_step_iters > 30) {   /* oracle.trace raises before it gets here */
+        rows[0] = rows[1] = rows[2] = rows[3] = -1;
+        return;
+    }
     orc_net net;
     memset(&net, 0, sizeof(net));
     if (!analytic) make_net(&net, n_layers, in, out, skip_mask, multires, Wcat, bcat);
