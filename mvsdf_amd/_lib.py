@@ -4,6 +4,7 @@ The product path has NO fallback: if the shared library is missing or a call fai
 """
 import ctypes as C
 import os
+import struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get('MVSDF_LIB') or os.path.join(_HERE, 'libmvsdf_hip.so')   # MVSDF_LIB: dev override (ablation builds)
@@ -190,3 +191,24 @@ def stream_of(t):
     if t.is_cuda:
         return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
     return C.c_void_p(0)
+
+
+# what the scene-side modules (mesh, chamfer, cloud, fusion, raster, stereo, viewsel) pass to their calls: raw addresses, no contiguity check
+def _vp(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream(t):
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _header(ws, n):
+    """the int64 results a call leaves at the start of its workspace (reading them waits for the stream)"""
+    import torch
+    return [int(x) for x in ws[:8 * n].view(torch.int64).cpu()]
+
+
+def f64_from_bits(bits):
+    """the fp64 value a header word holds as its int64 bit pattern"""
+    return struct.unpack('<d', struct.pack('<q', bits))[0]

@@ -23,8 +23,8 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
-from .mesh import Mesh, _header, _ply_elements, _stream, _vp
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from .mesh import Mesh, _ply_elements
 
 U64 = 2 ** 64
 
@@ -62,7 +62,7 @@ def _positive(name, x, what):
 def _header_f64(ws, n):
     """the int64 header, with entry 1 (an fp64 sum stored as its bits) decoded"""
     h = _header(ws, n)
-    return h, float(np.array([h[1]], np.int64).view(np.float64)[0])
+    return h, f64_from_bits(h[1])
 
 
 def sample_mesh(mesh, density=0.2, max_points=2 ** 31 - 1):

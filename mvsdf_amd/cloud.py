@@ -32,8 +32,7 @@ to be tolerated.  And self is excluded by index, not by distance.
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
-from .mesh import _header, _stream, _vp
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
 
 MAX_NEIGHBORS = 32
 INT32_MAX = 2 ** 31 - 1
@@ -86,10 +85,6 @@ def _workspace(p, what):
     if size == 0:
         raise ValueError('%s: %d points (2 .. 2^31 - 1)' % (what, p.shape[0]))
     return torch.empty(size, dtype=torch.uint8, device=p.device), size
-
-
-def _f64(bits):
-    return float(np.array([bits], np.int64).view(np.float64)[0])
 
 
 def _device(t):
@@ -192,7 +187,7 @@ def _clean(p, colors, a, b, nb_neighbors, knn_ratio, eps_ratio, cluster_frac, wh
     n_passed, n_clusters, largest, n_kept, m, thr, eps, rounds, err = _header(ws, 9)
     _errors(err, what)
     pts, col, a, b = compact(p, keep, col, a, b, n_kept)
-    return Cleaned(pts, col, keep, d, labels, _f64(m), _f64(thr), _f64(eps), n_passed, n_clusters, largest, rounds), a, b
+    return Cleaned(pts, col, keep, d, labels, f64_from_bits(m), f64_from_bits(thr), f64_from_bits(eps), n_passed, n_clusters, largest, rounds), a, b
 
 
 def clean_points(points, colors=None, nb_neighbors=20, knn_ratio=3.0, eps_ratio=3.0, cluster_frac=1.0):

@@ -2,7 +2,7 @@
 // filter, the observation / ground-plane masks and exact nearest distances with a cut-off.  Python: mvsdf_amd/chamfer.py, which states the metric;
 // tests/chamfer_ref.py restates it in numpy.  All arithmetic is fp64 without contraction, in the order the metric writes it.
 //
-// * Sampling: per-face counts, an int64 exclusive scan, an emit pass; output = the vertices, then the samples in face order.
+// * Sampling: per-face counts, an int64 exclusive scan (geom_prims.h: mv_scan), an emit pass; output = the vertices, then the samples in face order.
 // * Downsampling: points binned into cells of edge density * (1 + 1e-6) in an open-addressing table keyed by a hash of the int64 cell coordinates
 //   (a collision only merges two buckets, which adds candidates and never hides one).  The kept set is the lexicographically-first maximal
 //   independent set under the keys splitmix64(seed ^ i): synchronous rounds (states ping-pong) keep a point once every lower-key neighbour is
@@ -136,11 +136,11 @@ struct ChSampleLayout {
 
 static bool ch_sample_layout(long long nv, long long nf, ChSampleLayout* L) {
     if (nv < 1 || nf < 1 || nv > INT_MAX || nf > INT_MAX) return false;
-    size_t o = CH_HDR;
-    L->cnt = o;   o += ch_align((size_t)nf * 8);
-    L->tmp = o;   o += ch_scan_tmp_bytes(nf);
-    L->flags = o; o += ch_align(4 * 8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    L->cnt = c.take((size_t)nf * 8);
+    L->tmp = c.take(mv_scan_tmp_bytes(nf));
+    L->flags = c.take(4 * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -274,18 +274,18 @@ static bool ch_ds_layout(long long n, ChDsLayout* L) {
     if (n < 1 || n > INT_MAX / 4) return false;
     L->tsize = 1;
     while (L->tsize < (unsigned long long)(2 * n)) L->tsize <<= 1;
-    size_t o = CH_HDR;
-    L->keys = o;  o += ch_align(L->tsize * 8);
-    L->cnt = o;   o += ch_align(L->tsize * 8);
-    L->start = o; o += ch_align(L->tsize * 8);
-    L->cur = o;   o += ch_align(L->tsize * 8);
-    L->pslot = o; o += ch_align((size_t)n * 4);
-    L->order = o; o += ch_align((size_t)n * 4);
-    L->st0 = o;   o += ch_align((size_t)n);
-    L->st1 = o;   o += ch_align((size_t)n);
-    L->tmp = o;   o += ch_scan_tmp_bytes((long long)L->tsize);
-    L->flags = o; o += ch_align((CH_DS_BATCH + 2) * 8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    L->keys = c.take(L->tsize * 8);
+    L->cnt = c.take(L->tsize * 8);
+    L->start = c.take(L->tsize * 8);
+    L->cur = c.take(L->tsize * 8);
+    L->pslot = c.take((size_t)n * 4);
+    L->order = c.take((size_t)n * 4);
+    L->st0 = c.take((size_t)n);
+    L->st1 = c.take((size_t)n);
+    L->tmp = c.take(mv_scan_tmp_bytes((long long)L->tsize));
+    L->flags = c.take((CH_DS_BATCH + 2) * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -339,15 +339,15 @@ struct ChMaskLayout {
 
 static bool ch_mask_layout(long long n, long long m, ChMaskLayout* L) {
     if (n < 1 || m < 1 || n > (1ll << 40) || m > (1ll << 40)) return false;
-    size_t o = CH_HDR;
-    L->fin = o;  o += ch_align((size_t)n * 8);
-    L->fobs = o; o += ch_align((size_t)n * 8);
-    L->fab = o;  o += ch_align((size_t)m * 8);
-    L->tmp1 = o; o += ch_scan_tmp_bytes(n);
-    L->tmp2 = o; o += ch_scan_tmp_bytes(n);
-    L->tmp3 = o; o += ch_scan_tmp_bytes(m);
-    L->tot = o;  o += ch_align(4 * 8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    L->fin = c.take((size_t)n * 8);
+    L->fobs = c.take((size_t)n * 8);
+    L->fab = c.take((size_t)m * 8);
+    L->tmp1 = c.take(mv_scan_tmp_bytes(n));
+    L->tmp2 = c.take(mv_scan_tmp_bytes(n));
+    L->tmp3 = c.take(mv_scan_tmp_bytes(m));
+    L->tot = c.take(4 * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -481,13 +481,13 @@ struct ChNnLayout {
 
 static bool ch_nn_layout(long long nq, long long nr, ChNnLayout* L) {
     if (nq < 0 || nr < 1 || nq > (1ll << 40) || nr > INT_MAX) return false;
-    size_t o = CH_HDR;
-    if (!ch_tree_layout(nr, &o, &L->t)) return false;
-    L->nbq = ch_grid(nq > 0 ? nq : 1, CH_CHUNK);
-    L->psum = o;  o += ch_align((size_t)L->nbq * 8);
-    L->pcnt = o;  o += ch_align((size_t)L->nbq * 8);
-    L->flags = o; o += ch_align(4 * 8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    if (!ch_tree_layout(nr, c, &L->t)) return false;
+    L->nbq = mv_ceil_div(nq > 0 ? nq : 1, CH_CHUNK);
+    L->psum = c.take((size_t)L->nbq * 8);
+    L->pcnt = c.take((size_t)L->nbq * 8);
+    L->flags = c.take(4 * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -512,17 +512,17 @@ int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t
     long long* fl = (long long*)(w + L.flags);                    // [0]: error bits (int), [1]: the scan's total
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_sample_count"))) return rc;
-    hipLaunchKernelGGL(k_ch_vert_copy, dim3(ch_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, (double*)nullptr, (int*)fl);
-    hipLaunchKernelGGL(k_ch_sample_count, dim3(ch_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
+    hipLaunchKernelGGL(k_ch_vert_copy, dim3(mv_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, (double*)nullptr, (int*)fl);
+    hipLaunchKernelGGL(k_ch_sample_count, dim3(mv_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
                        (long long)max_points, cnt, (int*)fl);
-    ch_scan(cnt, nf, cnt, w + L.tmp, fl + 1, s);
+    mv_scan(cnt, nf, cnt, w + L.tmp, fl + 1, s);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_sample_count"))) return rc;
     long long h[2];
-    if ((rc = ch_read(h, fl, sizeof(h), s, "mvsdf_chamfer_sample_count"))) return rc;
+    if ((rc = mv_read(h, fl, sizeof(h), s, "mvsdf_chamfer_sample_count"))) return rc;
     const long long err = (int)h[0], samples = h[1];
     long long hdr[3] = {nv + samples, samples, err};
     if (!err && nv + samples > max_points) hdr[2] |= CH_ERR_POINTS;
-    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_sample_count");
+    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_sample_count");
 }
 
 int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, void* ws, size_t ws_bytes, double* out,
@@ -533,8 +533,8 @@ int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t 
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_chamfer_sample_emit: workspace too small (mvsdf_chamfer_sample_workspace_bytes)");
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ch_vert_copy, dim3(ch_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, out, (int*)(w + L.flags));
-    hipLaunchKernelGGL(k_ch_sample_emit, dim3(ch_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
+    hipLaunchKernelGGL(k_ch_vert_copy, dim3(mv_grid(nv, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, (long long)nv, out, (int*)(w + L.flags));
+    hipLaunchKernelGGL(k_ch_sample_emit, dim3(mv_grid(nf, CH_THREADS)), dim3(CH_THREADS), 0, s, verts, faces, (long long)nv, (long long)nf, density,
                        (const long long*)(w + L.cnt), out, (long long)cap);
     return mv_check(hipGetLastError(), "mvsdf_chamfer_sample_emit");
 }
@@ -554,7 +554,7 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
     hipStream_t s = (hipStream_t)stream;
     const double h = density * (1.0 + 1e-6), r2 = density * density;
     const unsigned long long tmask = L.tsize - 1;
-    const unsigned gn = ch_grid(n, CH_THREADS);
+    const unsigned gn = mv_grid(n, CH_THREADS);
     unsigned long long* keys = (unsigned long long*)(w + L.keys);
     unsigned long long* cnt = (unsigned long long*)(w + L.cnt);
     long long* start = (long long*)(w + L.start);
@@ -570,10 +570,10 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
     hipLaunchKernelGGL(k_ds_insert, dim3(gn), dim3(CH_THREADS), 0, s, pts, (long long)n, h, keys, tmask, (int*)(w + L.pslot), cnt, fl);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
     int e = 0;
-    if ((rc = ch_read(&e, fl, 4, s, "mvsdf_chamfer_downsample"))) return rc;
+    if ((rc = mv_read(&e, fl, 4, s, "mvsdf_chamfer_downsample"))) return rc;
     hdr[2] = e;
     if (!e) {
-        ch_scan((const long long*)cnt, (long long)L.tsize, start, w + L.tmp, (long long*)(fl + 2), s);
+        mv_scan((const long long*)cnt, (long long)L.tsize, start, w + L.tmp, (long long*)(fl + 2), s);
         hipLaunchKernelGGL(k_ds_fill, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const int*)(w + L.pslot), (const long long*)start,
                            (unsigned long long*)(w + L.cur), (int*)(w + L.order));
         int cur = 0;
@@ -593,7 +593,7 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
             }
             if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
             int left[CH_DS_BATCH];
-            if ((rc = ch_read(left, fl + 4, sizeof(left), s, "mvsdf_chamfer_downsample"))) return rc;
+            if ((rc = mv_read(left, fl + 4, sizeof(left), s, "mvsdf_chamfer_downsample"))) return rc;
             for (int b = 0; b < batch && !done; ++b) {
                 ++hdr[1];
                 done = left[b] == 0;
@@ -604,10 +604,10 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
             hipLaunchKernelGGL(k_ds_out, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const unsigned char*)st[cur], kept,
                                (unsigned long long*)(fl + 2));
             if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
-            if ((rc = ch_read(&hdr[0], fl + 2, 8, s, "mvsdf_chamfer_downsample"))) return rc;
+            if ((rc = mv_read(&hdr[0], fl + 2, 8, s, "mvsdf_chamfer_downsample"))) return rc;
         }
     }
-    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_downsample");
+    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_downsample");
 }
 
 size_t mvsdf_chamfer_mask_workspace_bytes(int64_t n, int64_t m) {
@@ -637,16 +637,16 @@ int mvsdf_chamfer_mask(const double* pts, const uint8_t* kept, int64_t n, const 
     long long* fobs = (long long*)(w + L.fobs);
     long long* fab = (long long*)(w + L.fab);
     long long* tot = (long long*)(w + L.tot);
-    hipLaunchKernelGGL(k_mask_flags, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, kept, (long long)n, a, obs, fin, fobs);
+    hipLaunchKernelGGL(k_mask_flags, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, kept, (long long)n, a, obs, fin, fobs);
     if (int rc = mv_check(hipMemsetAsync(tot, 0, 4 * 8, s), "mvsdf_chamfer_mask")) return rc;
-    hipLaunchKernelGGL(k_mask_plane, dim3(ch_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, a, fab, tot + 3);
-    ch_scan(fin, n, fin, w + L.tmp1, tot, s);
-    ch_scan(fobs, n, fobs, w + L.tmp2, tot + 1, s);
-    ch_scan(fab, m, fab, w + L.tmp3, tot + 2, s);
-    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fin, (const long long*)tot, d_in);
-    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fobs,
+    hipLaunchKernelGGL(k_mask_plane, dim3(mv_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, a, fab, tot + 3);
+    mv_scan(fin, n, fin, w + L.tmp1, tot, s);
+    mv_scan(fobs, n, fobs, w + L.tmp2, tot + 1, s);
+    mv_scan(fab, m, fab, w + L.tmp3, tot + 2, s);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fin, (const long long*)tot, d_in);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fobs,
                        (const long long*)(tot + 1), d_obs);
-    hipLaunchKernelGGL(k_mask_scatter, dim3(ch_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, (const long long*)fab,
+    hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, (const long long*)fab,
                        (const long long*)(tot + 2), s_above);
     if (int rc = mv_check(hipGetLastError(), "mvsdf_chamfer_mask")) return rc;
     return mv_check(hipMemcpyAsync(ws, tot, 4 * 8, hipMemcpyDeviceToDevice, s), "mvsdf_chamfer_mask");
@@ -672,7 +672,7 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
     ch_tree_frame(refs, (long long)nr, w, L.t, fl, s);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
     int e = 0;
-    if ((rc = ch_read(&e, fl, 4, s, "mvsdf_chamfer_nearest"))) return rc;
+    if ((rc = mv_read(&e, fl, 4, s, "mvsdf_chamfer_nearest"))) return rc;
     hdr[2] = e;
     if (!e) {
         ch_tree_build(refs, (long long)nr, w, L.t, s);
@@ -680,7 +680,7 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
         const double* box = (const double*)(w + L.t.box);
         const ChTree& T = L.t.T;
         if (nq > 0) {
-            hipLaunchKernelGGL(k_nn_query, dim3(ch_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, (long long)nq, sp, box, T, max_dist, dist, fl);
+            hipLaunchKernelGGL(k_nn_query, dim3(mv_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, (long long)nq, sp, box, T, max_dist, dist, fl);
             hipLaunchKernelGGL(k_nn_sum_part, dim3((unsigned)L.nbq), dim3(CH_THREADS), 0, s, (const double*)dist, (long long)nq, (double*)(w + L.psum),
                                (long long*)(w + L.pcnt));
             hipLaunchKernelGGL(k_nn_sum_final, dim3(1), dim3(CH_TOP_THREADS), 0, s, (const double*)(w + L.psum), (const long long*)(w + L.pcnt), L.nbq,
@@ -688,12 +688,12 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
         }
         if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
         long long r[3];                                           // error bits (int) at byte 0, k_nn_sum_final's count and sum at bytes 8 and 16
-        if ((rc = ch_read(r, fl, sizeof(r), s, "mvsdf_chamfer_nearest"))) return rc;
+        if ((rc = mv_read(r, fl, sizeof(r), s, "mvsdf_chamfer_nearest"))) return rc;
         hdr[0] = nq > 0 ? r[1] : 0;
         hdr[1] = nq > 0 ? r[2] : 0;
         hdr[2] = (int)r[0];
     }
-    return ch_write_header(ws, hdr, 3, s, "mvsdf_chamfer_nearest");
+    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_nearest");
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 //   pointed at its root, roots get the smallest input index (atomicMin) and the count (atomicAdd) of their component, the lanes of a wave that
 //   share a root combined first, and the largest count decides what is kept.  Integer atomics only: labels and counts are a property of the
 //   graph, not of the schedule.
-// * Compaction: int64 flags, the house scan, a scatter in input order.
+// * Compaction: int64 flags, the house scan (geom_prims.h: mv_scan), a scatter in input order.
 //
 // Every device loop is bounded; the round loop on the host stops at CL_MAX_ROUNDS with CH_ERR_ROUNDS.
 #include "nn_tree.h"
@@ -309,15 +309,15 @@ struct ClLayout {
 
 static bool cl_layout(long long n, ClLayout* L) {
     if (n < 2 || n > INT_MAX) return false;
-    size_t o = CH_HDR;
-    if (!ch_tree_layout(n, &o, &L->t)) return false;
-    L->v2 = o;     o += ch_align((size_t)n * 4);                  // the median sort carries values nobody reads: v1 and this
-    L->parent = o; o += ch_align((size_t)n * 4);
-    L->minidx = o; o += ch_align((size_t)n * 4);
-    L->count = o;  o += ch_align((size_t)n * 4);
-    L->flags = o;  o += ch_align(CL_F_WORDS * 4);
-    L->par = o;    o += ch_align(4 * 8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    if (!ch_tree_layout(n, c, &L->t)) return false;
+    L->v2 = c.take((size_t)n * 4);  // the median sort carries values nobody reads: v1 and this
+    L->parent = c.take((size_t)n * 4);
+    L->minidx = c.take((size_t)n * 4);
+    L->count = c.take((size_t)n * 4);
+    L->flags = c.take(CL_F_WORDS * 4);
+    L->par = c.take(4 * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -327,17 +327,17 @@ struct ClCompactLayout {
 
 static bool cl_compact_layout(long long n, ClCompactLayout* L) {
     if (n < 1 || n > INT_MAX) return false;
-    size_t o = CH_HDR;
-    L->f = o;   o += ch_align((size_t)n * 8);
-    L->tmp = o; o += ch_scan_tmp_bytes(n);
-    L->tot = o; o += ch_align(8);
-    L->total = o;
+    WsCursor c{CH_HDR};
+    L->f = c.take((size_t)n * 8);
+    L->tmp = c.take(mv_scan_tmp_bytes(n));
+    L->tot = c.take(8);
+    L->total = c.o;
     return true;
 }
 
 static int cl_fail_header(void* ws, long long err, hipStream_t s, const char* what) {
     long long hdr[CL_HDR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, err};
-    return ch_write_header(ws, hdr, CL_HDR_WORDS, s, what);
+    return mv_write_header(ws, hdr, CL_HDR_WORDS, s, what);
 }
 
 // flags zeroed, the frame, one header read for CH_ERR_FINITE, the tree -> 0 and *perm, or nonzero after the failure header / a HIP error (*done set)
@@ -349,7 +349,7 @@ static int cl_begin(const double* pts, long long n, char* w, const ClLayout& L, 
     ch_tree_frame(pts, n, w, L.t, fl + CL_F_ERR, s);
     if ((rc = mv_check(hipGetLastError(), what))) return rc;
     int e = 0;
-    if ((rc = ch_read(&e, fl, 4, s, what))) return rc;
+    if ((rc = mv_read(&e, fl, 4, s, what))) return rc;
     if (e) return cl_fail_header(w, e, s, what);
     *perm = ch_tree_build(pts, n, w, L.t, s);
     *done = false;
@@ -360,7 +360,7 @@ static void cl_knn(long long n, int k, char* w, const ClLayout& L, const int* pe
     const double* sp = (const double*)(w + L.t.sp);
     const double* box = (const double*)(w + L.t.box);
     int* err = (int*)(w + L.flags) + CL_F_ERR;
-    const dim3 g(ch_grid(n, CH_THREADS)), b(CH_THREADS);
+    const dim3 g(mv_grid(n, CH_THREADS)), b(CH_THREADS);
     if (k <= 8)
         hipLaunchKernelGGL(k_cl_knn<8>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err);
     else if (k <= 16)
@@ -381,7 +381,7 @@ static int cl_components(const double* d, long long n, double cluster_frac, char
     int* parent = (int*)(w + L.parent);
     int* minidx = (int*)(w + L.minidx);
     int* count = (int*)(w + L.count);
-    const dim3 g(ch_grid(n, CH_THREADS)), b(CH_THREADS);
+    const dim3 g(mv_grid(n, CH_THREADS)), b(CH_THREADS);
     int rc;
     hipLaunchKernelGGL(k_cl_flag, g, b, 0, s, d, perm, n, par, parent, minidx, count, fl);
     long long rounds = 0;
@@ -391,7 +391,7 @@ static int cl_components(const double* d, long long n, double cluster_frac, char
         hipLaunchKernelGGL(k_cl_hook, g, b, 0, s, sp, box, L.t.T, par, parent, fl);
         if ((rc = mv_check(hipGetLastError(), what))) return rc;
         int r[2];
-        if ((rc = ch_read(r, fl, sizeof(r), s, what))) return rc;
+        if ((rc = mv_read(r, fl, sizeof(r), s, what))) return rc;
         ++rounds;
         if (r[CL_F_ERR]) return cl_fail_header(w, r[CL_F_ERR], s, what);
         if (!r[CL_F_PENDING]) break;
@@ -468,7 +468,7 @@ int mvsdf_cloud_clean(const double* pts, int64_t n, int32_t k, double knn_ratio,
     unsigned long long* keys[2] = {(unsigned long long*)(w + L.t.k0), (unsigned long long*)(w + L.t.k1)};
     int* vals[2] = {(int*)(w + L.t.v1), (int*)(w + L.v2)};
     if (perm != (const int*)(w + L.t.v0)) return mv_fail(-1, "mvsdf_cloud_clean: the permutation is not where the layout expects it");
-    hipLaunchKernelGGL(k_cl_keys, dim3(ch_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)d, (long long)n, keys[0]);
+    hipLaunchKernelGGL(k_cl_keys, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)d, (long long)n, keys[0]);
     const int cur = ch_radix_sort(keys, vals, n, 64, w, L.t, s);
     hipLaunchKernelGGL(k_cl_median, dim3(1), dim3(64), 0, s, (const unsigned long long*)keys[cur], (long long)n, knn_ratio, eps_ratio, (double*)(w + L.par));
     return cl_components(d, n, cluster_frac, w, L, perm, labels, keep, s, what);
@@ -485,9 +485,9 @@ int mvsdf_cloud_compact(const double* pts, const uint8_t* colors, const int32_t*
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
     long long* f = (long long*)(w + L.f);
-    const dim3 g(ch_grid(n, CH_THREADS)), blk(CH_THREADS);
+    const dim3 g(mv_grid(n, CH_THREADS)), blk(CH_THREADS);
     hipLaunchKernelGGL(k_cl_keep_flags, g, blk, 0, s, keep, (long long)n, f);
-    ch_scan(f, n, f, w + L.tmp, (long long*)(w + L.tot), s);
+    mv_scan(f, n, f, w + L.tmp, (long long*)(w + L.tot), s);
     hipLaunchKernelGGL(k_cl_compact, g, blk, 0, s, pts, colors, a, b, keep, (long long)n, (const long long*)f, (long long)cap, out_pts, out_colors, out_a,
                        out_b);
     if (int rc = mv_check(hipGetLastError(), what)) return rc;

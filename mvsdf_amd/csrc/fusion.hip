@@ -6,19 +6,13 @@
 // * k_fu_fuse: one lane per reference pixel, the source loop inside.  The 4x4 transforms T_rs / T_sr are kernel data indexed by (view, source slot),
 //   the same for every lane of a workgroup, so they come through the scalar cache; the four source texels are plain gathers.  Writes counts, the
 //   fp32 fused depth, the fp64 fused depth (the emit pass back-projects at it) and a keep flag.
-// * an int64 exclusive scan of the keep flags over all views: per-workgroup totals, one workgroup over those; the emit pass redoes the scan inside
-//   its workgroup, so no per-pixel offset is stored.  Points come out in (view, y, x) order.  No float atomics anywhere.
+// * an int64 exclusive scan of the keep flags over all views (geom_prims.h: mv_scan_blocks, i.e. k_scan_block_sum and k_scan_top); the emit pass ranks
+//   its own chunk (mv_chunk_rank), so no per-pixel offset is stored.  Points come out in (view, y, x) order.  No float atomics anywhere.
 //
 // Every argument is validated on the host before anything is launched: an error leaves {0, error bits} in the header and the device untouched.
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 
 #define FU_THREADS 256
-#define FU_ITEMS 8                                    // consecutive pixels per lane in the scan and the emit pass
-#define FU_CHUNK (FU_THREADS * FU_ITEMS)
-#define FU_TOP_THREADS 1024
 #define FU_HDR 256                                    // bytes at the start of the workspace: int64 {points, error bits}
 #define FU_MAX_PIXELS (1ll << 40)
 
@@ -29,9 +23,6 @@ enum {
     FU_ERR_SHAPE = 8,       // V < 1, H or W < 2, a pair list that disagrees with V or is longer than view, sizes beyond the limits
 };
 
-static inline size_t fu_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline long long fu_blocks(long long n, long long per) { return (n + per - 1) / per; }
-
 struct FuLayout {
     size_t mats, pinv, src, off, df, keep, bsum, total;
     long long nb;
@@ -40,23 +31,18 @@ struct FuLayout {
 static bool fu_layout(long long V, long long H, long long W, long long npairs, FuLayout* L) {
     if (V < 1 || H < 2 || W < 2 || npairs < 0 || V > INT_MAX || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || npairs > INT_MAX) return false;
     const long long n = V * H * W;
-    if (n > FU_MAX_PIXELS || V * fu_blocks(H * W, FU_THREADS) > INT_MAX) return false;
-    L->nb = fu_blocks(n, FU_CHUNK);
-    size_t o = FU_HDR;
-    L->mats = o; o += fu_align((size_t)(npairs > 0 ? npairs : 1) * 32 * 8);
-    L->pinv = o; o += fu_align((size_t)V * 16 * 8);
-    L->src = o;  o += fu_align((size_t)(npairs > 0 ? npairs : 1) * 4);
-    L->off = o;  o += fu_align((size_t)(V + 1) * 4);
-    L->df = o;   o += fu_align((size_t)n * 8);
-    L->keep = o; o += fu_align((size_t)n);
-    L->bsum = o; o += fu_align((size_t)(L->nb + 1) * 8);
-    L->total = o;
+    if (n > FU_MAX_PIXELS || V * mv_ceil_div(H * W, FU_THREADS) > INT_MAX) return false;
+    L->nb = mv_ceil_div(n, MV_CHUNK);
+    WsCursor c{FU_HDR};
+    L->mats = c.take((size_t)(npairs > 0 ? npairs : 1) * 32 * 8);
+    L->pinv = c.take((size_t)V * 16 * 8);
+    L->src = c.take((size_t)(npairs > 0 ? npairs : 1) * 4);
+    L->off = c.take((size_t)(V + 1) * 4);
+    L->df = c.take((size_t)n * 8);
+    L->keep = c.take((size_t)n);
+    L->bsum = c.take(mv_scan_tmp_bytes(n));
+    L->total = c.o;
     return true;
-}
-
-// one row of a 4x4 matrix times q, in the definition's order
-__device__ __forceinline__ double fu_row(const double* __restrict__ t, double q0, double q1, double q2, double q3) {
-    return ((t[0] * q0 + t[1] * q1) + t[2] * q2) + t[3] * q3;
 }
 
 // step 1
@@ -96,10 +82,10 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_fuse(const float* __restrict_
         for (int k = s0; k < s1; ++k) {
             const int s = src[k];
             const double* __restrict__ T = mats + (long long)k * 32;          // T_rs, then T_sr
-            const double p2 = fu_row(T + 8, q0, q1, d, 1.0);
+            const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
             if (!(p2 > 0.0)) continue;
-            const double u = fu_row(T, q0, q1, d, 1.0) / p2 - 0.5;
-            const double v = fu_row(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
+            const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
+            const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
             if (!(u >= 0.0 && u <= wmax && v >= 0.0 && v <= hmax)) continue;
             const double x0 = fmin(floor(u), (double)(W - 2)), y0 = fmin(floor(v), (double)(H - 2));
             const double fx = u - x0, fy = v - y0;
@@ -109,10 +95,10 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_fuse(const float* __restrict_
             const double ds = (d00 * (1.0 - fx) + d01 * fx) * (1.0 - fy) + (d10 * (1.0 - fx) + d11 * fx) * fy;
             const double b0q = (u + 0.5) * ds, b1q = (v + 0.5) * ds;
             const double* __restrict__ B = T + 16;
-            const double b2 = fu_row(B + 8, b0q, b1q, ds, 1.0);
+            const double b2 = mv_row4(B + 8, b0q, b1q, ds, 1.0);
             if (!(b2 > 0.0)) continue;
-            const double ex = fu_row(B, b0q, b1q, ds, 1.0) / b2 - X;
-            const double ey = fu_row(B + 4, b0q, b1q, ds, 1.0) / b2 - Y;
+            const double ex = mv_row4(B, b0q, b1q, ds, 1.0) / b2 - X;
+            const double ey = mv_row4(B + 4, b0q, b1q, ds, 1.0) / b2 - Y;
             if (ex * ex + ey * ey < pix2 && fabs(b2 - d) < dep_thresh * d) {
                 ++n;
                 acc += b2;
@@ -127,73 +113,18 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_fuse(const float* __restrict_
     keep[at] = kept ? 1 : 0;
 }
 
-// per-workgroup totals of the keep flags
-__global__ __launch_bounds__(FU_THREADS) void k_fu_block_sum(const unsigned char* __restrict__ keep, long long n, long long* __restrict__ bsum) {
-    __shared__ int sh[FU_THREADS];
-    const long long base = (long long)blockIdx.x * FU_CHUNK + (long long)threadIdx.x * FU_ITEMS;
-    int s = 0;
-    for (int q = 0; q < FU_ITEMS; ++q)
-        if (base + q < n) s += keep[base + q];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = FU_THREADS / 2; d; d >>= 1) {
-        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
-}
-
-// in place: exclusive scan of bsum[nb]; *total = the sum (one workgroup, serial ranges per lane)
-__global__ __launch_bounds__(FU_TOP_THREADS) void k_fu_scan_top(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
-    __shared__ long long sh[FU_TOP_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nb + FU_TOP_THREADS - 1) / FU_TOP_THREADS;
-    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
-    long long s = 0;
-    for (long long q = lo; q < hi; ++q) s += bsum[q];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < FU_TOP_THREADS; d <<= 1) {                // inclusive Hillis-Steele scan
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = sh[t] - s;
-    for (long long q = lo; q < hi; ++q) {
-        const long long v = bsum[q];
-        bsum[q] = r;
-        r += v;
-    }
-    if (t == FU_TOP_THREADS - 1) *total = sh[t];
-}
-
 // step 4: the kept pixels of chunk blockIdx.x, in order, from row boff[blockIdx.x] on; nothing is written at or beyond row cap
-__global__ __launch_bounds__(FU_THREADS) void k_fu_emit(const unsigned char* __restrict__ keep, const double* __restrict__ dfi, long long n, int H, int W,
+__global__ __launch_bounds__(MV_THREADS) void k_fu_emit(const unsigned char* __restrict__ keep, const double* __restrict__ dfi, long long n, int H, int W,
                                                          const double* __restrict__ pinv, const long long* __restrict__ boff,
                                                          const unsigned char* __restrict__ images, double* __restrict__ points,
                                                          unsigned char* __restrict__ colors, int* __restrict__ view, int* __restrict__ pixel, long long cap) {
-    __shared__ int sh[FU_THREADS];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * FU_CHUNK + (long long)t * FU_ITEMS;
-    int k[FU_ITEMS], s = 0;
-#pragma unroll
-    for (int q = 0; q < FU_ITEMS; ++q) {
-        k[q] = base + q < n ? keep[base + q] : 0;
-        s += k[q];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < FU_THREADS; d <<= 1) {
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long row = boff[blockIdx.x] + (sh[t] - s);
+    __shared__ int sh[MV_THREADS];
+    const long long base = (long long)blockIdx.x * MV_CHUNK + (long long)threadIdx.x * MV_ITEMS;
+    int k[MV_ITEMS];
+    long long row = mv_chunk_rank<MV_THREADS, MV_ITEMS>(keep, n, boff, k, sh);
     const long long hw = (long long)H * W;
 #pragma unroll
-    for (int q = 0; q < FU_ITEMS; ++q) {
+    for (int q = 0; q < MV_ITEMS; ++q) {
         if (!k[q]) continue;
         if (row < cap) {
             const long long at = base + q;
@@ -202,7 +133,7 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_emit(const unsigned char* __r
             const double df = dfi[at];
             const double q0 = ((double)x + 0.5) * df, q1 = ((double)y + 0.5) * df;
             const double* __restrict__ T = pinv + (long long)r * 16;
-            for (int c = 0; c < 3; ++c) points[row * 3 + c] = fu_row(T + 4 * c, q0, q1, df, 1.0);
+            for (int c = 0; c < 3; ++c) points[row * 3 + c] = mv_row4(T + 4 * c, q0, q1, df, 1.0);
             if (images)
                 for (int c = 0; c < 3; ++c) colors[row * 3 + c] = images[at * 3 + c];
             view[row] = r;
@@ -210,12 +141,6 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_emit(const unsigned char* __r
         }
         ++row;
     }
-}
-
-static int fu_header(void* ws, long long points, long long err, hipStream_t s, const char* what) {
-    const long long hdr[2] = {points, err};
-    if (int rc = mv_check(hipMemcpyAsync(ws, hdr, sizeof(hdr), hipMemcpyHostToDevice, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);             // hdr lives on this stack frame
 }
 
 extern "C" {
@@ -255,7 +180,10 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
         if (!isfinite(pix_thresh) || !isfinite(dep_thresh)) err |= FU_ERR_FINITE;
         if (probs && !(isfinite(pthresh[0]) && isfinite(pthresh[1]) && isfinite(pthresh[2]))) err |= FU_ERR_FINITE;
     }
-    if (err) return fu_header(ws, 0, err, s, what);
+    if (err) {
+        const long long hdr[2] = {0, err};
+        return mv_write_header(ws, hdr, 2, s, what);
+    }
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_fusion_fuse: workspace too small (mvsdf_fusion_workspace_bytes)");
     // ---- uploads and launches ----
     char* w = (char*)ws;
@@ -269,14 +197,12 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
     if ((rc = mv_check(hipMemcpyAsync(w + L.pinv, mats + npairs * 32, (size_t)V * 16 * 8, hipMemcpyHostToDevice, s), what))) return rc;
     if ((rc = mv_check(hipMemcpyAsync(w + L.off, pair_off, (size_t)(V + 1) * 4, hipMemcpyHostToDevice, s), what))) return rc;
     const float t1 = probs ? pthresh[0] : 0.f, t2 = probs ? pthresh[1] : 0.f, t3 = probs ? pthresh[2] : 0.f;
-    hipLaunchKernelGGL(k_fu_mask, dim3((unsigned)fu_blocks(n, FU_THREADS)), dim3(FU_THREADS), 0, s, depths, probs, (long long)V, hw, t1, t2, t3, masked);
-    const int tiles = (int)fu_blocks(hw, FU_THREADS);
+    hipLaunchKernelGGL(k_fu_mask, dim3(mv_grid(n, FU_THREADS)), dim3(FU_THREADS), 0, s, depths, probs, (long long)V, hw, t1, t2, t3, masked);
+    const int tiles = (int)mv_ceil_div(hw, FU_THREADS);
     hipLaunchKernelGGL(k_fu_fuse, dim3((unsigned)(V * tiles)), dim3(FU_THREADS), 0, s, (const float*)masked, (int)V, (int)H, (int)W, tiles,
                        (const int*)(w + L.off), (const int*)(w + L.src), (const double*)(w + L.mats), (int)vthresh, pix_thresh * pix_thresh, dep_thresh,
                        counts, fused, (double*)(w + L.df), (unsigned char*)(w + L.keep));
-    long long* bsum = (long long*)(w + L.bsum);
-    hipLaunchKernelGGL(k_fu_block_sum, dim3((unsigned)L.nb), dim3(FU_THREADS), 0, s, (const unsigned char*)(w + L.keep), n, bsum);
-    hipLaunchKernelGGL(k_fu_scan_top, dim3(1), dim3(FU_TOP_THREADS), 0, s, bsum, L.nb, (long long*)ws);
+    mv_scan_blocks((const unsigned char*)(w + L.keep), n, (long long*)(w + L.bsum), L.nb, (long long*)ws, s);
     return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
 }
 
@@ -287,7 +213,7 @@ int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, in
         return mv_fail(-1, "mvsdf_fusion_emit: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_fusion_emit: workspace too small (mvsdf_fusion_workspace_bytes)");
     char* w = (char*)ws;
-    hipLaunchKernelGGL(k_fu_emit, dim3((unsigned)L.nb), dim3(FU_THREADS), 0, (hipStream_t)stream, (const unsigned char*)(w + L.keep),
+    hipLaunchKernelGGL(k_fu_emit, dim3((unsigned)L.nb), dim3(MV_THREADS), 0, (hipStream_t)stream, (const unsigned char*)(w + L.keep),
                        (const double*)(w + L.df), (long long)(V * H * W), (int)H, (int)W, (const double*)(w + L.pinv), (const long long*)(w + L.bsum),
                        images, points, colors, view, pixel, (long long)cap);
     return mv_check(hipGetLastError(), "mvsdf_fusion_emit");

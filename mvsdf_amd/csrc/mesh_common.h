@@ -3,13 +3,14 @@
 // so the two cannot drift apart: the sparse path's output is pinned bit for bit to the dense one (tests/test_gpu_mesh_sparse.py).
 // Conventions: mvsdf_amd/mesh.py; the table: tools/gen_mc_tables.py -> mc_tables.h.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "geom_prims.h"
 
 #define MC_TABLE static __constant__ const
 #include "mc_tables.h"
 
 // Every counting pass maps items to workgroups in linear order: workgroup b owns items [b * MESH_CHUNK, (b + 1) * MESH_CHUNK), its 256 lanes take
-// MESH_CHUNK / 256 consecutive rounds of 256 (block_excl ranks them), and k_mesh_scan turns the per-workgroup totals into int64 offsets.
+// MESH_CHUNK / 256 consecutive rounds of 256 (block_excl ranks them), and k_mesh_scan turns the per-workgroup totals into int64 offsets.  Workspace
+// regions are 256-byte aligned (WsCursor).
 #define MESH_THREADS 256
 #define MESH_ROUNDS 4
 #define MESH_CHUNK (MESH_THREADS * MESH_ROUNDS)
@@ -114,33 +115,34 @@ __device__ __forceinline__ long long block_excl(int x, int nbits, int* s_w, long
     return base + pre;
 }
 
+// the running sums of k_mesh_scan's two arrays, scanned together
+struct MeshSum2 {
+    long long a, b;
+    __device__ MeshSum2& operator+=(const MeshSum2& o) {
+        a += o.a;
+        b += o.b;
+        return *this;
+    }
+};
+
 // exclusive int64 offsets of one or two per-workgroup count arrays (b may be NULL) -> oa / ob; tot[0] / tot[1] = the sums, tot[2] = 1 if a count was negative
 static __global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan(const int* __restrict__ a, const int* __restrict__ b, int nb, long long* __restrict__ oa,
                                                                  long long* __restrict__ ob, long long* __restrict__ tot) {
-    __shared__ long long sa[MESH_SCAN_THREADS], sb[MESH_SCAN_THREADS];
+    __shared__ MeshSum2 sh[MESH_SCAN_THREADS];
     __shared__ int s_bad;
     const int t = threadIdx.x, per = (nb + MESH_SCAN_THREADS - 1) / MESH_SCAN_THREADS;
     const int lo = min(nb, t * per), hi = min(nb, lo + per);
     if (t == 0) s_bad = 0;
-    long long ta = 0, tb = 0;
+    MeshSum2 own = {0, 0};
     int bad = 0;
     for (int q = lo; q < hi; ++q) {
         bad |= a[q] < 0 || (b && b[q] < 0);
-        ta += a[q];
-        if (b) tb += b[q];
+        own.a += a[q];
+        if (b) own.b += b[q];
     }
-    sa[t] = ta;
-    sb[t] = tb;
-    __syncthreads();
+    const MeshSum2 incl = mv_block_scan_incl<MESH_SCAN_THREADS>(own, sh);   // (its barriers order s_bad = 0 before the line below)
     if (bad) s_bad = 1;
-    for (int d = 1; d < MESH_SCAN_THREADS; d <<= 1) {         // inclusive Hillis-Steele scan
-        const long long xa = t >= d ? sa[t - d] : 0, xb = t >= d ? sb[t - d] : 0;
-        __syncthreads();
-        sa[t] += xa;
-        sb[t] += xb;
-        __syncthreads();
-    }
-    long long ra = sa[t] - ta, rb = sb[t] - tb;
+    long long ra = incl.a - own.a, rb = incl.b - own.b;
     for (int q = lo; q < hi; ++q) {
         oa[q] = ra;
         ra += a[q];
@@ -150,8 +152,8 @@ static __global__ __launch_bounds__(MESH_SCAN_THREADS) void k_mesh_scan(const in
         }
     }
     if (t == MESH_SCAN_THREADS - 1) {
-        tot[0] = sa[t];
-        tot[1] = sb[t];
+        tot[0] = incl.a;
+        tot[1] = incl.b;
     }
     __syncthreads();
     if (t == 0) tot[2] = s_bad;

@@ -16,9 +16,7 @@
 // the result rests on the capacity / excess bookkeeping (atomics) and the exact final relabel.
 //
 // Every device loop is bounded; the host loop is bounded by a limit derived from F and reports running into it instead of spinning.
-#include <limits.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 
 #define CUT_THREADS 256
 #define CUT_GR_ITEMS 8                                // faces per lane in the relabel launch
@@ -296,8 +294,6 @@ __global__ __launch_bounds__(CUT_THREADS) void k_cut_zero(int n, int* __restrict
 }
 
 // ---- workspace layout (every region 256-byte aligned) ----
-static inline size_t cut_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct CutLayout {
     unsigned long long tsize;                                     // half-edge table slots (a power of two >= 6 F)
     size_t keys, vals, twin, cf, tcap, excess0, excess, h, flags, flab, vlab, sel, sel_bytes, total;
@@ -310,29 +306,21 @@ static bool cut_layout(long long nv, long long nf, CutLayout* L) {
     while (L->tsize < (unsigned long long)(6 * nf)) L->tsize <<= 1;
     L->sel_bytes = mvsdf_mesh_cc_workspace_bytes(nv, nf);
     if (!L->sel_bytes) return false;
-    size_t o = CUT_HDR;
-    L->keys = o;   o += cut_align(L->tsize * 8);
-    L->vals = o;   o += cut_align(L->tsize * 4);
-    L->twin = o;   o += cut_align((size_t)nf * 12);
-    L->cf = o;     o += cut_align((size_t)nf * 12);
-    L->tcap = o;   o += cut_align((size_t)nf * 4);
-    L->excess0 = o; o += cut_align((size_t)nf * 4);
-    L->excess = o; o += cut_align((size_t)nf * 4);
-    L->h = o;      o += cut_align((size_t)nf * 4);
-    L->flags = o;  o += cut_align(2 * CUT_GR_BATCH * 4 + 4 * 8);
-    L->flab = o;   o += cut_align((size_t)nf * 4);
-    L->vlab = o;   o += cut_align((size_t)nv * 4);
-    L->sel = o;    o += cut_align(L->sel_bytes);
-    L->total = o;
+    WsCursor c{CUT_HDR};
+    L->keys = c.take(L->tsize * 8);
+    L->vals = c.take(L->tsize * 4);
+    L->twin = c.take((size_t)nf * 12);
+    L->cf = c.take((size_t)nf * 12);
+    L->tcap = c.take((size_t)nf * 4);
+    L->excess0 = c.take((size_t)nf * 4);
+    L->excess = c.take((size_t)nf * 4);
+    L->h = c.take((size_t)nf * 4);
+    L->flags = c.take(2 * CUT_GR_BATCH * 4 + 4 * 8);
+    L->flab = c.take((size_t)nf * 4);
+    L->vlab = c.take((size_t)nv * 4);
+    L->sel = c.take(L->sel_bytes);
+    L->total = c.o;
     return true;
-}
-
-static inline unsigned cut_grid(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-
-// copy n bytes from the device and wait for the stream
-static int cut_read(void* host, const void* dev, size_t n, hipStream_t s) {
-    if (int rc = mv_check(hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s), "mvsdf_mesh_cut")) return rc;
-    return mv_check(hipStreamSynchronize(s), "mvsdf_mesh_cut");
 }
 
 extern "C" {
@@ -363,7 +351,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
     int* err = flags + 2 * CUT_GR_BATCH;
     unsigned long long* sums = (unsigned long long*)(w + L.flags + 2 * CUT_GR_BATCH * 4 + 8);
     long long hdr[6] = {0, 0, 0, 0, 0, 0};                        // flow, removed faces, kept vertices, error bits, rounds, relabel launches
-    const unsigned gf = cut_grid(F, CUT_THREADS), gr = cut_grid(F, CUT_GR_CHUNK);
+    const unsigned gf = mv_grid(F, CUT_THREADS), gr = mv_grid(F, CUT_GR_CHUNK);
     int rc;
     if ((rc = mv_check(hipMemsetAsync(keys, 0xff, L.tsize * 8, s), "mvsdf_mesh_cut"))) return rc;
     if ((rc = mv_check(hipMemsetAsync(w + L.flags, 0, 2 * CUT_GR_BATCH * 4 + 4 * 8, s), "mvsdf_mesh_cut"))) return rc;
@@ -372,7 +360,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
                        (const unsigned long long*)keys, (const int*)vals, (unsigned long long)(L.tsize - 1), twin, cf, tcap, excess);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_mesh_cut"))) return rc;
     int e = 0;
-    if ((rc = cut_read(&e, err, 4, s))) return rc;
+    if ((rc = mv_read(&e, err, 4, s, "mvsdf_mesh_cut"))) return rc;
     hdr[3] = e;
     if (!e) {
         if ((rc = mv_check(hipMemcpyAsync(excess0, excess, (size_t)F * 4, hipMemcpyDeviceToDevice, s), "mvsdf_mesh_cut"))) return rc;
@@ -395,7 +383,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
                                        flags + b, flags + CUT_GR_BATCH + b);
                 if ((rc = mv_check(hipGetLastError(), "mvsdf_mesh_cut"))) return rc;
                 int fl[2 * CUT_GR_BATCH];
-                if ((rc = cut_read(fl, flags, sizeof(fl), s))) return rc;
+                if ((rc = mv_read(fl, flags, sizeof(fl), s, "mvsdf_mesh_cut"))) return rc;
                 for (int b = 0; b < CUT_GR_BATCH && !settled; ++b) {
                     ++launches;
                     if (!fl[b]) {
@@ -418,21 +406,20 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
             ++hdr[4];
         }
         if (done) {
-            hipLaunchKernelGGL(k_cut_zero, dim3(cut_grid(V, CUT_THREADS)), dim3(CUT_THREADS), 0, s, V, (int*)(w + L.vlab));
+            hipLaunchKernelGGL(k_cut_zero, dim3(mv_grid(V, CUT_THREADS)), dim3(CUT_THREADS), 0, s, V, (int*)(w + L.vlab));
             hipLaunchKernelGGL(k_cut_mark, dim3(gf), dim3(CUT_THREADS), 0, s, F, faces, (const int*)h, inf, (unsigned char*)removed,
                                (int*)(w + L.flab), (int*)(w + L.vlab), sums);
-            hipLaunchKernelGGL(k_cut_sums, dim3(cut_grid(F > V ? F : V, CUT_THREADS)), dim3(CUT_THREADS), 0, s, F, V, (const int*)tcap, (const int*)excess0,
+            hipLaunchKernelGGL(k_cut_sums, dim3(mv_grid(F > V ? F : V, CUT_THREADS)), dim3(CUT_THREADS), 0, s, F, V, (const int*)tcap, (const int*)excess0,
                                (const int*)(w + L.vlab), sums);
             if ((rc = mv_check(hipGetLastError(), "mvsdf_mesh_cut"))) return rc;
             unsigned long long sm[3];
-            if ((rc = cut_read(sm, sums, sizeof(sm), s))) return rc;
+            if ((rc = mv_read(sm, sums, sizeof(sm), s, "mvsdf_mesh_cut"))) return rc;
             hdr[0] = (long long)sm[0];
             hdr[1] = (long long)sm[1];
             hdr[2] = (long long)sm[2];
         }
     }
-    if ((rc = mv_check(hipMemcpyAsync(w, hdr, sizeof(hdr), hipMemcpyHostToDevice, s), "mvsdf_mesh_cut"))) return rc;
-    return mv_check(hipStreamSynchronize(s), "mvsdf_mesh_cut");
+    return mv_write_header(w, hdr, 6, s, "mvsdf_mesh_cut");
 }
 
 int mvsdf_mesh_trim(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes,

@@ -6,11 +6,7 @@
 // its 256 lanes take MESH_CHUNK / 256 consecutive rounds of 256.  A count pass writes one small total per workgroup, k_mesh_scan turns them into
 // int64 workgroup offsets, and the emit pass recounts the same items (per wave with __ballot / __popcll) to place each one.  Outputs therefore come
 // in item order and do not depend on scheduling.
-#include <limits.h>
-#include <math.h>
 #include <string.h>
-#include "capi_util.h"
-
 #include "mesh_common.h"
 
 struct MeshVol {
@@ -366,8 +362,6 @@ __global__ __launch_bounds__(MESH_THREADS) void k_sel_faces(const int* __restric
 }
 
 // ---- workspace layouts (every region 256-byte aligned) ----
-static inline size_t mesh_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline long long mesh_blocks(long long n) { return (n + MESH_CHUNK - 1) / MESH_CHUNK; }
 
 struct McLayout {
     long long npts, nb;
@@ -380,15 +374,15 @@ static bool mc_layout(long long nx, long long ny, long long nz, McLayout* L) {
     const long long lim = 1ll << 60;
     if (nx > lim / ny || nx * ny > lim / nz) return false;
     L->npts = nx * ny * nz;
-    L->nb = mesh_blocks(L->npts);
+    L->nb = mv_ceil_div(L->npts, MESH_CHUNK);
     if (L->nb > INT_MAX) return false;
-    size_t o = MESH_HDR;
-    L->idmap = o;  o += mesh_align((size_t)L->npts * 4);
-    L->bv = o;     o += mesh_align((size_t)L->nb * 4);
-    L->bf = o;     o += mesh_align((size_t)L->nb * 4);
-    L->ov = o;     o += mesh_align((size_t)L->nb * 8);
-    L->of = o;     o += mesh_align((size_t)L->nb * 8);
-    L->total = o;
+    WsCursor c{MESH_HDR};
+    L->idmap = c.take((size_t)L->npts * 4);
+    L->bv = c.take((size_t)L->nb * 4);
+    L->bf = c.take((size_t)L->nb * 4);
+    L->ov = c.take((size_t)L->nb * 8);
+    L->of = c.take((size_t)L->nb * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -399,23 +393,23 @@ struct CcLayout {
 
 static bool cc_layout(long long nv, long long nf, CcLayout* L) {
     if (nv < 1 || nf < 1 || nv > INT_MAX || nf > INT_MAX) return false;
-    L->nbv = mesh_blocks(nv);
-    L->nbf = mesh_blocks(nf);
-    size_t o = MESH_HDR;
-    L->parent = o;  o += mesh_align((size_t)nv * 4);
-    L->dense = o;   o += mesh_align((size_t)nv * 4);
-    L->acc = o;     o += mesh_align((size_t)nv * 8);
-    L->minface = o; o += mesh_align((size_t)nv * 4);
-    L->cv = o;      o += mesh_align((size_t)nv * 4);
-    L->cf = o;      o += mesh_align((size_t)nv * 4);
-    L->bc = o;      o += mesh_align((size_t)L->nbv * 4);
-    L->bo = o;      o += mesh_align((size_t)L->nbv * 8);
-    L->bc2 = o;     o += mesh_align((size_t)L->nbf * 4);
-    L->bo2 = o;     o += mesh_align((size_t)L->nbf * 8);
-    L->scal = o;    o += mesh_align(4 * 8);
-    L->err = o;     o += mesh_align(4);
+    L->nbv = mv_ceil_div(nv, MESH_CHUNK);
+    L->nbf = mv_ceil_div(nf, MESH_CHUNK);
+    WsCursor c{MESH_HDR};
+    L->parent = c.take((size_t)nv * 4);
+    L->dense = c.take((size_t)nv * 4);
+    L->acc = c.take((size_t)nv * 8);
+    L->minface = c.take((size_t)nv * 4);
+    L->cv = c.take((size_t)nv * 4);
+    L->cf = c.take((size_t)nv * 4);
+    L->bc = c.take((size_t)L->nbv * 4);
+    L->bo = c.take((size_t)L->nbv * 8);
+    L->bc2 = c.take((size_t)L->nbf * 4);
+    L->bo2 = c.take((size_t)L->nbf * 8);
+    L->scal = c.take(4 * 8);
+    L->err = c.take(4);
     L->vmap = L->dense;                                          // mvsdf_mesh_select reuses the dense-id region
-    L->total = o;
+    L->total = c.o;
     return true;
 }
 
@@ -429,8 +423,6 @@ static bool mc_vol(const float* vol, const int64_t* shape, const int64_t* stride
     }
     return true;
 }
-
-static inline unsigned mesh_grid(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 extern "C" {
 
@@ -495,19 +487,19 @@ int mvsdf_mesh_components(const float* verts, const int32_t* faces, int64_t nv, 
     int* err = (int*)(w + L.err);
     long long* ncomp = (long long*)(w + L.bo2);                  // k_mesh_scan's totals (3 int64) land in the face-offset region, unused here
     const int V = (int)nv, F = (int)nf;
-    hipLaunchKernelGGL(k_cc_init, dim3(mesh_grid(V > 4 ? V : 4, MESH_THREADS)), dim3(MESH_THREADS), 0, s, V, parent, acc, minface, cv, cf, scal, err);
-    hipLaunchKernelGGL(k_cc_hook, dim3(mesh_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, faces, F, V, parent, err);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(mesh_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, V, parent, err);
+    hipLaunchKernelGGL(k_cc_init, dim3(mv_grid(V > 4 ? V : 4, MESH_THREADS)), dim3(MESH_THREADS), 0, s, V, parent, acc, minface, cv, cf, scal, err);
+    hipLaunchKernelGGL(k_cc_hook, dim3(mv_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, faces, F, V, parent, err);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(mv_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, V, parent, err);
     hipLaunchKernelGGL(k_flag_count, dim3((unsigned)L.nbv), dim3(MESH_THREADS), 0, s, (const int*)parent, (long long)V, 0, 1, (int*)(w + L.bc));
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(w + L.bc), (const int*)nullptr, (int)L.nbv,
                        (long long*)(w + L.bo), (long long*)nullptr, ncomp);
     hipLaunchKernelGGL(k_cc_dense, dim3((unsigned)L.nbv), dim3(MESH_THREADS), 0, s, (const int*)parent, V, (const long long*)(w + L.bo), dense);
-    hipLaunchKernelGGL(k_cc_label_vertices, dim3(mesh_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const int*)parent, (const int*)dense, V, vert_label, cv);
-    hipLaunchKernelGGL(k_cc_faces, dim3(mesh_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, verts, faces, F, (const int*)vert_label, face_label, cf, minface, scal);
-    hipLaunchKernelGGL(k_cc_area, dim3(mesh_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, verts, faces, F, (const int*)face_label, acc,
+    hipLaunchKernelGGL(k_cc_label_vertices, dim3(mv_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const int*)parent, (const int*)dense, V, vert_label, cv);
+    hipLaunchKernelGGL(k_cc_faces, dim3(mv_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, verts, faces, F, (const int*)vert_label, face_label, cf, minface, scal);
+    hipLaunchKernelGGL(k_cc_area, dim3(mv_grid(F, MESH_THREADS)), dim3(MESH_THREADS), 0, s, verts, faces, F, (const int*)face_label, acc,
                        (const unsigned long long*)scal);
-    hipLaunchKernelGGL(k_cc_best_area, dim3(mesh_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const unsigned long long*)acc, (const long long*)ncomp, scal);
-    hipLaunchKernelGGL(k_cc_best_face, dim3(mesh_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const unsigned long long*)acc, (const int*)minface,
+    hipLaunchKernelGGL(k_cc_best_area, dim3(mv_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const unsigned long long*)acc, (const long long*)ncomp, scal);
+    hipLaunchKernelGGL(k_cc_best_face, dim3(mv_grid(V, MESH_THREADS)), dim3(MESH_THREADS), 0, s, (const unsigned long long*)acc, (const int*)minface,
                        (const long long*)ncomp, scal);
     hipLaunchKernelGGL(k_cc_result, dim3(1), dim3(1), 0, s, (const long long*)ncomp, (const unsigned long long*)scal, (const int*)face_label, (const int*)cv,
                        (const int*)cf, (const int*)err, F, (long long*)w);

@@ -17,9 +17,6 @@
 // and emitting rows is the dense path's ballot / popcount structure (block_excl, k_mesh_scan) over these items.
 // Face vertex ids come from a brick-local id map (R^3 int32 per slot: each owned point's first vertex id).  The closure guarantees that every
 // edge a kept face uses is owned by an active block.
-#include <limits.h>
-#include <math.h>
-#include "capi_util.h"
 #include "mesh_common.h"
 
 #define SMC_THREADS 256
@@ -195,13 +192,6 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_closure(const float* __rest
     }
     const unsigned long long m = __ballot(hit);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(hdr + SMC_STORES, (unsigned long long)__popcll(m));
-}
-
-// ---- non-finite evaluated values: one flag for the whole pool ----
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_finite(const float* __restrict__ vals, long long n, unsigned long long* __restrict__ hdr) {
-    bool bad = false;
-    for (long long x = (long long)blockIdx.x * SMC_THREADS + threadIdx.x; x < n; x += (long long)gridDim.x * SMC_THREADS) bad |= !isfinite(vals[x]);
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(hdr + SMC_BAD, 1ull);
 }
 
 // ---- row metadata: per place r of sblk, the active blocks of its i-slab [x, y) and of its (i, j)-column [z, w) ----
@@ -397,8 +387,6 @@ __global__ __launch_bounds__(MESH_THREADS) void k_smc_faces(const float* __restr
 }
 
 // ---- workspace layouts (every region 256-byte aligned) ----
-static inline size_t smc_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline long long smc_wgs(long long n) { return (n + MESH_CHUNK - 1) / MESH_CHUNK; }
 static inline int smc_bits(long long x) {
     int b = 0;
     while ((1ll << b) <= x) ++b;
@@ -423,15 +411,15 @@ static bool smc_layout(int64_t n, int64_t block, SmcLayout* L) {
     L->g.R = (int)block + 1;
     L->g.level = 0.0f;
     L->nblk = nb * nb * nb;
-    L->nwg = smc_wgs(L->nblk);
-    size_t o = MESH_HDR;
-    L->map = o;   o += smc_align((size_t)L->nblk * 4);
-    L->list = o;  o += smc_align((size_t)L->nblk * 4);
-    L->sblk = o;  o += smc_align((size_t)L->nblk * 4);
-    L->meta = o;  o += smc_align((size_t)L->nblk * 16);
-    L->bc = o;    o += smc_align((size_t)L->nwg * 4);
-    L->bo = o;    o += smc_align((size_t)L->nwg * 8);
-    L->total = o;
+    L->nwg = mv_ceil_div(L->nblk, MESH_CHUNK);
+    WsCursor c{MESH_HDR};
+    L->map = c.take((size_t)L->nblk * 4);
+    L->list = c.take((size_t)L->nblk * 4);
+    L->sblk = c.take((size_t)L->nblk * 4);
+    L->meta = c.take((size_t)L->nblk * 16);
+    L->bc = c.take((size_t)L->nwg * 4);
+    L->bo = c.take((size_t)L->nwg * 8);
+    L->total = c.o;
     return true;
 }
 
@@ -444,19 +432,17 @@ static bool smc_emit_layout(const SmcLayout& L, int64_t nact, SmcEmitLayout* E) 
     if (nact < 1 || nact > L.nblk) return false;
     const long long R = L.g.R;
     E->nrows = nact * R * R;
-    E->nwg = smc_wgs(E->nrows);
+    E->nwg = mv_ceil_div(E->nrows, MESH_CHUNK);
     if (E->nwg > INT_MAX) return false;
-    size_t o = 0;
-    E->idmap = o; o += smc_align((size_t)nact * R * R * R * 4);
-    E->bv = o;    o += smc_align((size_t)E->nwg * 4);
-    E->bf = o;    o += smc_align((size_t)E->nwg * 4);
-    E->ov = o;    o += smc_align((size_t)E->nwg * 8);
-    E->of = o;    o += smc_align((size_t)E->nwg * 8);
-    E->total = o;
+    WsCursor c{0};
+    E->idmap = c.take((size_t)nact * R * R * R * 4);
+    E->bv = c.take((size_t)E->nwg * 4);
+    E->bf = c.take((size_t)E->nwg * 4);
+    E->ov = c.take((size_t)E->nwg * 8);
+    E->of = c.take((size_t)E->nwg * 8);
+    E->total = c.o;
     return true;
 }
-
-static inline unsigned smc_grid(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 // the flagged blocks (state 1) take the slots base, base + 1, ... in linear order; the count lands in the header
 static void smc_compact(const SmcLayout& L, char* w, int mode, long long base, hipStream_t s) {
@@ -486,7 +472,7 @@ int mvsdf_smc_coarse_points(const float* axis, int64_t n, int64_t block, int64_t
     if (!axis || !pts || !smc_layout(n, block, &L)) return mv_fail(-1, "mvsdf_smc_coarse_points: bad arguments");
     const long long m = L.g.nb + 1;
     if (start < 0 || count < 1 || start > m * m * m - count) return mv_fail(-1, "mvsdf_smc_coarse_points: the range leaves the coarse lattice");
-    hipLaunchKernelGGL(k_smc_coarse_points, dim3(smc_grid(count, SMC_THREADS)), dim3(SMC_THREADS), 0, (hipStream_t)stream, axis, L.g, (long long)start,
+    hipLaunchKernelGGL(k_smc_coarse_points, dim3(mv_grid(count, SMC_THREADS)), dim3(SMC_THREADS), 0, (hipStream_t)stream, axis, L.g, (long long)start,
                        (long long)count, pts);
     return mv_check(hipGetLastError(), "mvsdf_smc_coarse_points");
 }
@@ -500,7 +486,7 @@ int mvsdf_smc_seed(const float* coarse, int64_t n, int64_t block, float level, f
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(w, 0, MESH_HDR, s);
     if (e != hipSuccess) return mv_check(e, "mvsdf_smc_seed");
-    hipLaunchKernelGGL(k_smc_seed, dim3(smc_grid(L.nblk, SMC_THREADS)), dim3(SMC_THREADS), 0, s, coarse, L.g, tol, (int*)(w + L.map), L.nblk,
+    hipLaunchKernelGGL(k_smc_seed, dim3(mv_grid(L.nblk, SMC_THREADS)), dim3(SMC_THREADS), 0, s, coarse, L.g, tol, (int*)(w + L.map), L.nblk,
                        (unsigned long long*)w);
     smc_compact(L, w, 0, 0, s);
     return mv_check(hipGetLastError(), "mvsdf_smc_seed");
@@ -513,7 +499,7 @@ int mvsdf_smc_brick_points(const float* axis, int64_t n, int64_t block, const vo
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_smc_brick_points: workspace too small (mvsdf_smc_workspace_bytes)");
     const long long P3 = (long long)L.g.P * L.g.P * L.g.P;
     if (start < 0 || count < 1 || start > L.nblk * P3 - count) return mv_fail(-1, "mvsdf_smc_brick_points: the range leaves the slots");
-    hipLaunchKernelGGL(k_smc_brick_points, dim3(smc_grid(count, SMC_THREADS)), dim3(SMC_THREADS), 0, (hipStream_t)stream, axis, L.g,
+    hipLaunchKernelGGL(k_smc_brick_points, dim3(mv_grid(count, SMC_THREADS)), dim3(SMC_THREADS), 0, (hipStream_t)stream, axis, L.g,
                        (const int*)((const char*)ws + L.list), (long long)start, (long long)count, pts);
     return mv_check(hipGetLastError(), "mvsdf_smc_brick_points");
 }
@@ -526,7 +512,7 @@ int mvsdf_smc_closure(const float* values, int64_t n, int64_t block, float level
     L.g.level = level;
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_smc_closure, dim3(smc_grid(count * 6 * L.g.R, SMC_THREADS)), dim3(SMC_THREADS), 0, s, values, L.g, (const int*)(w + L.list),
+    hipLaunchKernelGGL(k_smc_closure, dim3(mv_grid(count * 6 * L.g.R, SMC_THREADS)), dim3(SMC_THREADS), 0, s, values, L.g, (const int*)(w + L.list),
                        (int*)(w + L.map), (long long)slot0, (long long)count, (unsigned long long*)w);
     smc_compact(L, w, 0, slot0 + count, s);
     return mv_check(hipGetLastError(), "mvsdf_smc_closure");
@@ -544,11 +530,10 @@ int mvsdf_smc_count(const float* values, int64_t n, int64_t block, float level, 
     hipStream_t s = (hipStream_t)stream;
     const long long P3 = (long long)L.g.P * L.g.P * L.g.P;
     smc_compact(L, w, 1, 0, s);
-    hipLaunchKernelGGL(k_smc_meta, dim3(smc_grid(nactive, SMC_THREADS)), dim3(SMC_THREADS), 0, s, (const int*)(w + L.sblk), (int)nactive, L.g.nb,
+    hipLaunchKernelGGL(k_smc_meta, dim3(mv_grid(nactive, SMC_THREADS)), dim3(SMC_THREADS), 0, s, (const int*)(w + L.sblk), (int)nactive, L.g.nb,
                        (int4*)(w + L.meta));
-    const unsigned fin_wgs = smc_grid(nactive * P3, SMC_THREADS) < 4096u ? smc_grid(nactive * P3, SMC_THREADS) : 4096u;
-    hipLaunchKernelGGL(k_smc_finite, dim3(fin_wgs), dim3(SMC_THREADS), 0, s, values, nactive * P3,
-                       (unsigned long long*)w);
+    const unsigned fin_wgs = mv_grid(nactive * P3, MV_THREADS) < 4096u ? mv_grid(nactive * P3, MV_THREADS) : 4096u;
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3(fin_wgs), dim3(MV_THREADS), 0, s, values, nactive * P3, (unsigned long long*)w + SMC_BAD, 1ull);   // one flag for the whole pool
     hipLaunchKernelGGL(k_smc_count, dim3((unsigned)E.nwg), dim3(MESH_THREADS), 0, s, values, L.g, (const int*)(w + L.map), (const int*)(w + L.sblk),
                        (const int4*)(w + L.meta), E.nrows, smc_bits(3ll * L.g.R), smc_bits((long long)MC_MAX_TRIS * L.g.B), (int*)(x + E.bv), (int*)(x + E.bf));
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(x + E.bv), (const int*)(x + E.bf), (int)E.nwg, (long long*)(x + E.ov),

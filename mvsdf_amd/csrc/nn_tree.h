@@ -1,11 +1,8 @@
-// nn_tree.h -- what chamfer.hip and cloud.hip share: the constants and error bits, the int64 exclusive scan, the 64-bit LSD radix sort passes and the
+// nn_tree.h -- what chamfer.hip and cloud.hip share: the constants and error bits, the 64-bit LSD radix sort passes (their int64 scan is geom_prims.h's mv_scan) and the
 // Morton-sorted points with their implicit 8-ary tree of fp64 boxes (built by ch_tree_frame + ch_tree_build, walked without a stack by the
 // query kernels of either file).  Kernels are static: each including file gets its own copies.
 #pragma once
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 
 #define CH_THREADS 256
 #define CH_ITEMS 8                                    // consecutive items per lane in the scans and sums
@@ -34,105 +31,12 @@ enum {
     CH_ERR_WALK = 64,       // nearest: a tree walk hit its bound (cannot happen)
 };
 
-static inline size_t ch_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline unsigned ch_grid(long long n, long long per) { return (unsigned)((n + per - 1) / per); }
-
 __device__ __forceinline__ double ch_d2(double ax, double ay, double az, double bx, double by, double bz) {
     const double dx = ax - bx, dy = ay - by, dz = az - bz;
     return (dx * dx + dy * dy) + dz * dz;
 }
 
 __device__ __forceinline__ bool ch_finite3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
-
-// ================================================================ int64 exclusive scan (three launches) ================================================================
-// per-workgroup totals of a[n]
-static __global__ __launch_bounds__(CH_THREADS) void k_ch_block_sum(const long long* __restrict__ a, long long n, long long* __restrict__ bsum) {
-    __shared__ long long sh[CH_THREADS];
-    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)threadIdx.x * CH_ITEMS;
-    long long s = 0;
-    for (int q = 0; q < CH_ITEMS; ++q)
-        if (base + q < n) s += a[base + q];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = CH_THREADS / 2; d; d >>= 1) {
-        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
-}
-
-// in place: exclusive scan of bsum[nb]; *total = the sum (one workgroup, serial ranges per lane)
-static __global__ __launch_bounds__(CH_TOP_THREADS) void k_ch_scan_top(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
-    __shared__ long long sh[CH_TOP_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nb + CH_TOP_THREADS - 1) / CH_TOP_THREADS;
-    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
-    long long s = 0;
-    for (long long q = lo; q < hi; ++q) s += bsum[q];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < CH_TOP_THREADS; d <<= 1) {                // inclusive Hillis-Steele scan
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = sh[t] - s;
-    for (long long q = lo; q < hi; ++q) {
-        const long long v = bsum[q];
-        bsum[q] = r;
-        r += v;
-    }
-    if (t == CH_TOP_THREADS - 1) *total = sh[t];
-}
-
-// out[i] = boff[block] + the exclusive prefix of a inside the block (out may alias a)
-static __global__ __launch_bounds__(CH_THREADS) void k_ch_scan_apply(const long long* a, long long n, const long long* __restrict__ boff, long long* out) {
-    __shared__ long long sh[CH_THREADS];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * CH_CHUNK + (long long)t * CH_ITEMS;
-    long long v[CH_ITEMS], s = 0;
-#pragma unroll
-    for (int q = 0; q < CH_ITEMS; ++q) {
-        v[q] = base + q < n ? a[base + q] : 0;
-        s += v[q];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < CH_THREADS; d <<= 1) {
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = boff[blockIdx.x] + sh[t] - s;
-#pragma unroll
-    for (int q = 0; q < CH_ITEMS; ++q) {
-        if (base + q < n) out[base + q] = r;
-        r += v[q];
-    }
-}
-
-static size_t ch_scan_tmp_bytes(long long n) { return ch_align((size_t)(ch_grid(n, CH_CHUNK) + 1) * 8); }
-
-// exclusive scan of a[n] (n >= 1) into out (may alias a); tmp: ch_scan_tmp_bytes(n); total: one int64 on the device
-static void ch_scan(const long long* a, long long n, long long* out, void* tmp, long long* total, hipStream_t s) {
-    const unsigned nb = ch_grid(n, CH_CHUNK);
-    long long* bsum = (long long*)tmp;
-    hipLaunchKernelGGL(k_ch_block_sum, dim3(nb), dim3(CH_THREADS), 0, s, a, n, bsum);
-    hipLaunchKernelGGL(k_ch_scan_top, dim3(1), dim3(CH_TOP_THREADS), 0, s, bsum, (long long)nb, total);
-    hipLaunchKernelGGL(k_ch_scan_apply, dim3(nb), dim3(CH_THREADS), 0, s, a, n, (const long long*)bsum, out);
-}
-
-static int ch_read(void* host, const void* dev, size_t n, hipStream_t s, const char* what) {
-    if (int rc = mv_check(hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);
-}
-
-static int ch_write_header(void* ws, const long long* hdr, int n, hipStream_t s, const char* what) {
-    if (int rc = mv_check(hipMemcpyAsync(ws, hdr, (size_t)n * 8, hipMemcpyHostToDevice, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);
-}
 
 // ================================================================ the tree ================================================================
 // per-workgroup box of the references (k_nn_bbox_final combines them); a non-finite coordinate raises CH_ERR_FINITE
@@ -304,11 +208,11 @@ __device__ __forceinline__ double ch_box_lb2(const double* __restrict__ b, doubl
 struct ChTreeLayout {
     ChTree T;
     long long nbr, rs_nb;
-    size_t part, frame, k0, k1, v0, v1, hist, tmp, sp, box;
+    size_t part, frame, k0, k1, v0, v1, hist, tmp, tot, sp, box;
 };
 
-// the tree's shape over nr points and its buffers from *o on (advanced past them)
-static bool ch_tree_layout(long long nr, size_t* o, ChTreeLayout* L) {
+// the tree's shape over nr points and its buffers from the cursor on
+static bool ch_tree_layout(long long nr, WsCursor& c, ChTreeLayout* L) {
     if (nr < 1 || nr > INT_MAX) return false;
     ChTree& T = L->T;
     T.n = nr;
@@ -322,18 +226,19 @@ static bool ch_tree_layout(long long nr, size_t* o, ChTreeLayout* L) {
         ++T.top;
     }
     T.nodes = T.off[T.top] + 1;
-    L->nbr = ch_grid(nr, CH_CHUNK);
-    L->rs_nb = ch_grid(nr, CH_RS_CHUNK);
-    L->part = *o;  *o += ch_align((size_t)L->nbr * 48);
-    L->frame = *o; *o += ch_align(6 * 8);
-    L->k0 = *o;    *o += ch_align((size_t)nr * 8);
-    L->k1 = *o;    *o += ch_align((size_t)nr * 8);
-    L->v0 = *o;    *o += ch_align((size_t)nr * 4);
-    L->v1 = *o;    *o += ch_align((size_t)nr * 4);
-    L->hist = *o;  *o += ch_align((size_t)L->rs_nb * CH_RS_BINS * 8);
-    L->tmp = *o;   *o += ch_scan_tmp_bytes(L->rs_nb * CH_RS_BINS) + ch_align(8);
-    L->sp = *o;    *o += ch_align((size_t)nr * 24);
-    L->box = *o;   *o += ch_align((size_t)T.nodes * 48);
+    L->nbr = mv_ceil_div(nr, CH_CHUNK);
+    L->rs_nb = mv_ceil_div(nr, CH_RS_CHUNK);
+    L->part = c.take((size_t)L->nbr * 48);
+    L->frame = c.take(6 * 8);
+    L->k0 = c.take((size_t)nr * 8);
+    L->k1 = c.take((size_t)nr * 8);
+    L->v0 = c.take((size_t)nr * 4);
+    L->v1 = c.take((size_t)nr * 4);
+    L->hist = c.take((size_t)L->rs_nb * CH_RS_BINS * 8);
+    L->tmp = c.take(mv_scan_tmp_bytes(L->rs_nb * CH_RS_BINS));
+    L->tot = c.take(8);                                           // the scan's total, which nobody reads
+    L->sp = c.take((size_t)nr * 24);
+    L->box = c.take((size_t)T.nodes * 48);
     return true;
 }
 
@@ -348,11 +253,11 @@ static void ch_tree_frame(const double* refs, long long nr, char* w, const ChTre
 static int ch_radix_sort(unsigned long long* const k[2], int* const v[2], long long n, int bits, char* w, const ChTreeLayout& L, hipStream_t s) {
     const int nb = (int)L.rs_nb;
     long long* hist = (long long*)(w + L.hist);
-    long long* tot = (long long*)(w + L.tmp + ch_scan_tmp_bytes(L.rs_nb * CH_RS_BINS));
+    long long* tot = (long long*)(w + L.tot);
     int cur = 0;
     for (int shift = 0; shift < bits; shift += 4) {
         hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], n, shift, hist, nb);
-        ch_scan(hist, L.rs_nb * CH_RS_BINS, hist, w + L.tmp, tot, s);
+        mv_scan(hist, L.rs_nb * CH_RS_BINS, hist, w + L.tmp, tot, s);
         hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (const int*)v[cur], n, shift,
                            (const long long*)hist, nb, k[cur ^ 1], v[cur ^ 1]);
         cur ^= 1;
@@ -365,16 +270,16 @@ static int ch_radix_sort(unsigned long long* const k[2], int* const v[2], long l
 static const int* ch_tree_build(const double* refs, long long nr, char* w, const ChTreeLayout& L, hipStream_t s) {
     unsigned long long* k[2] = {(unsigned long long*)(w + L.k0), (unsigned long long*)(w + L.k1)};
     int* v[2] = {(int*)(w + L.v0), (int*)(w + L.v1)};
-    const unsigned gr = ch_grid(nr, CH_THREADS);
+    const unsigned gr = mv_grid(nr, CH_THREADS);
     hipLaunchKernelGGL(k_nn_morton, dim3(gr), dim3(CH_THREADS), 0, s, refs, nr, (const double*)(w + L.frame), k[0], v[0]);
     const int cur = ch_radix_sort(k, v, nr, 3 * CH_MORTON_BITS, w, L, s);
     double* sp = (double*)(w + L.sp);
     double* box = (double*)(w + L.box);
     const ChTree& T = L.T;
     hipLaunchKernelGGL(k_nn_gather, dim3(gr), dim3(CH_THREADS), 0, s, refs, nr, (const int*)v[cur], sp);
-    hipLaunchKernelGGL(k_nn_leaf_box, dim3(ch_grid(T.cnt[0], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)sp, nr, T.cnt[0], box);
+    hipLaunchKernelGGL(k_nn_leaf_box, dim3(mv_grid(T.cnt[0], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)sp, nr, T.cnt[0], box);
     for (int lv = 1; lv <= T.top; ++lv)
-        hipLaunchKernelGGL(k_nn_node_box, dim3(ch_grid(T.cnt[lv], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)(box + T.off[lv - 1] * 6),
+        hipLaunchKernelGGL(k_nn_node_box, dim3(mv_grid(T.cnt[lv], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)(box + T.off[lv - 1] * 6),
                            T.cnt[lv - 1], T.cnt[lv], box + T.off[lv] * 6);
     return v[cur];
 }

@@ -8,23 +8,17 @@
 //   when the new key is not smaller: the buffer only decreases, so a stale (larger) value read there only costs an atomic, never a pixel.
 // * k_ra_draw_small: one lane per (face, view) (blockIdx.y = the view, so the camera comes through the scalar cache), projecting its three vertices and
 //   walking its clamped pixel box.  A face whose box holds more than large_face_pixels pixels is flagged instead of drawn.
-// * the flags go through a count / scan / emit compaction (uint8 flags, per-workgroup totals, one workgroup over those, the emit pass redoes the scan
-//   inside its workgroup) to a list of (face, view) items; k_ra_draw_large gives each item to one wave, whose lanes stride over the box.  The grid is
+// * the flags go through a count / scan / emit compaction (geom_prims.h: mv_scan_blocks over the uint8 flags, then k_ra_emit ranks its own chunk with
+//   mv_chunk_rank) to a list of (face, view) items; k_ra_draw_large gives each item to one wave, whose lanes stride over the box.  The grid is
 //   fixed and strides over the list, whose length it reads on the device: no host wait between the two paths.
 // * k_ra_resolve: keys -> depth fp32 (0 where nothing was drawn) and face int32 (-1).
 // * k_ra_visibility: one lane per (vertex, view); k_ra_colors: one lane per vertex, the views in order inside, so the weighted sum has one order.
 //
 // There is no clipping: a face with a vertex not in front of the camera is skipped.  Every device loop is bounded by the clamped pixel box or the
 // view count; every index read from the caller (face -> vertex) is range-checked before it is used.
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 
 #define RA_THREADS 256
-#define RA_ITEMS 8                                    // consecutive items per lane in the scan and the emit pass
-#define RA_CHUNK (RA_THREADS * RA_ITEMS)
-#define RA_TOP_THREADS 1024
 #define RA_HDR 256                                    // bytes at the start of the workspace: int64 {error bits, large items, atomics, covered}
 #define RA_WAVES (RA_THREADS / 64)
 #define RA_LARGE_BLOCKS 4096                          // workgroups of the large path (it strides over the list)
@@ -36,9 +30,6 @@ enum {
     RA_ERR_INDEX = 2,       // a face refers to a vertex outside [0, nv)
 };
 enum { RA_FLAG_NO_PRETEST = 1, RA_FLAG_STATS = 2 };
-
-static inline size_t ra_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline long long ra_blocks(long long n, long long per) { return (n + per - 1) / per; }
 
 struct RaLayout {
     size_t keys, flags, list, bsum, total;
@@ -52,19 +43,19 @@ static bool ra_shape(long long views, long long H, long long W) {
 static bool ra_layout(long long nv, long long nf, long long views, long long H, long long W, RaLayout* L) {
     if (nv < 0 || nf < 0 || nv > INT_MAX || nf > INT_MAX || !ra_shape(views, H, W) || nf * views > INT_MAX) return false;
     L->items = nf * views;
-    L->nb = ra_blocks(L->items, RA_CHUNK);
-    size_t o = RA_HDR;
-    L->keys = o;  o += ra_align((size_t)(views * H * W) * 8);
-    L->flags = o; o += ra_align((size_t)(L->items > 0 ? L->items : 1));
-    L->list = o;  o += ra_align((size_t)(L->items > 0 ? L->items : 1) * 4);
-    L->bsum = o;  o += ra_align((size_t)(L->nb + 1) * 8);
-    L->total = o;
+    L->nb = mv_ceil_div(L->items, MV_CHUNK);
+    WsCursor c{RA_HDR};
+    L->keys = c.take((size_t)(views * H * W) * 8);
+    L->flags = c.take((size_t)(L->items > 0 ? L->items : 1));
+    L->list = c.take((size_t)(L->items > 0 ? L->items : 1) * 4);
+    L->bsum = c.take(mv_scan_tmp_bytes(L->items));
+    L->total = c.o;
     return true;
 }
 
 // one row of a 4x4 matrix times (q0, q1, q2, 1), in the definition's order
 __device__ __forceinline__ double ra_row(const double* __restrict__ t, double q0, double q1, double q2) {
-    return ((t[0] * q0 + t[1] * q1) + t[2] * q2) + t[3] * 1.0;
+    return mv_row4(t, q0, q1, q2, 1.0);
 }
 
 __device__ __forceinline__ double ra_edge(double px, double py, double qx, double qy, double rx, double ry) {
@@ -202,70 +193,15 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_draw_large(const float* __res
     if (STATS) ra_stats(hdr, na, nc);
 }
 
-// per-workgroup totals of the flags
-__global__ __launch_bounds__(RA_THREADS) void k_ra_block_sum(const unsigned char* __restrict__ flags, long long n, long long* __restrict__ bsum) {
-    __shared__ int sh[RA_THREADS];
-    const long long base = (long long)blockIdx.x * RA_CHUNK + (long long)threadIdx.x * RA_ITEMS;
-    int s = 0;
-    for (int q = 0; q < RA_ITEMS; ++q)
-        if (base + q < n) s += flags[base + q];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = RA_THREADS / 2; d; d >>= 1) {
-        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = sh[0];
-}
-
-// in place: exclusive scan of bsum[nb]; *total = the sum (one workgroup, serial ranges per lane)
-__global__ __launch_bounds__(RA_TOP_THREADS) void k_ra_scan_top(long long* __restrict__ bsum, long long nb, long long* __restrict__ total) {
-    __shared__ long long sh[RA_TOP_THREADS];
-    const int t = threadIdx.x;
-    const long long per = (nb + RA_TOP_THREADS - 1) / RA_TOP_THREADS;
-    const long long lo = min(nb, t * per), hi = min(nb, lo + per);
-    long long s = 0;
-    for (long long q = lo; q < hi; ++q) s += bsum[q];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < RA_TOP_THREADS; d <<= 1) {                // inclusive Hillis-Steele scan
-        const long long x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long r = sh[t] - s;
-    for (long long q = lo; q < hi; ++q) {
-        const long long v = bsum[q];
-        bsum[q] = r;
-        r += v;
-    }
-    if (t == RA_TOP_THREADS - 1) *total = sh[t];
-}
-
 // the flagged items of chunk blockIdx.x, in order, from entry boff[blockIdx.x] on
-__global__ __launch_bounds__(RA_THREADS) void k_ra_emit(const unsigned char* __restrict__ flags, long long n, const long long* __restrict__ boff,
+__global__ __launch_bounds__(MV_THREADS) void k_ra_emit(const unsigned char* __restrict__ flags, long long n, const long long* __restrict__ boff,
                                                          int* __restrict__ list) {
-    __shared__ int sh[RA_THREADS];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * RA_CHUNK + (long long)t * RA_ITEMS;
-    int k[RA_ITEMS], s = 0;
+    __shared__ int sh[MV_THREADS];
+    const long long base = (long long)blockIdx.x * MV_CHUNK + (long long)threadIdx.x * MV_ITEMS;
+    int k[MV_ITEMS];
+    long long row = mv_chunk_rank<MV_THREADS, MV_ITEMS>(flags, n, boff, k, sh);
 #pragma unroll
-    for (int q = 0; q < RA_ITEMS; ++q) {
-        k[q] = base + q < n ? flags[base + q] : 0;
-        s += k[q];
-    }
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < RA_THREADS; d <<= 1) {
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    long long row = boff[blockIdx.x] + (sh[t] - s);
-#pragma unroll
-    for (int q = 0; q < RA_ITEMS; ++q)
+    for (int q = 0; q < MV_ITEMS; ++q)
         if (k[q]) list[row++] = (int)(base + q);                  // row < the flags' total <= n, the list's length
 }
 
@@ -367,12 +303,11 @@ static void ra_launch_draw(const float* verts, const int32_t* faces, long long n
     unsigned char* flags = (unsigned char*)(w + L.flags);
     int* list = (int*)(w + L.list);
     long long* bsum = (long long*)(w + L.bsum);
-    hipLaunchKernelGGL((k_ra_draw_small<PRE, STATS>), dim3((unsigned)ra_blocks(nf, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, faces, nv,
+    hipLaunchKernelGGL((k_ra_draw_small<PRE, STATS>), dim3(mv_grid(nf, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, faces, nv,
                        nf, P, o, H, W, large, keys, flags, hdr);
-    hipLaunchKernelGGL(k_ra_block_sum, dim3((unsigned)L.nb), dim3(RA_THREADS), 0, s, (const unsigned char*)flags, L.items, bsum);
-    hipLaunchKernelGGL(k_ra_scan_top, dim3(1), dim3(RA_TOP_THREADS), 0, s, bsum, L.nb, (long long*)(hdr + 1));
-    hipLaunchKernelGGL(k_ra_emit, dim3((unsigned)L.nb), dim3(RA_THREADS), 0, s, (const unsigned char*)flags, L.items, (const long long*)bsum, list);
-    const long long waves = ra_blocks(L.items, RA_WAVES);
+    mv_scan_blocks((const unsigned char*)flags, L.items, bsum, L.nb, (long long*)(hdr + 1), s);
+    hipLaunchKernelGGL(k_ra_emit, dim3((unsigned)L.nb), dim3(MV_THREADS), 0, s, (const unsigned char*)flags, L.items, (const long long*)bsum, list);
+    const long long waves = mv_ceil_div(L.items, RA_WAVES);
     hipLaunchKernelGGL((k_ra_draw_large<PRE, STATS>), dim3((unsigned)(waves < RA_LARGE_BLOCKS ? waves : RA_LARGE_BLOCKS)), dim3(RA_THREADS), 0, s, verts,
                        faces, nv, nf, P, o, H, W, keys, (const int*)list, hdr);
 }
@@ -411,7 +346,7 @@ int mvsdf_raster_resolve(int64_t views, int64_t H, int64_t W, void* ws, size_t w
     if (!ws || !depth || !face || !ra_shape(views, H, W)) return mv_fail(-1, "mvsdf_raster_resolve: bad arguments");
     const long long n = views * H * W;
     if (ws_bytes < RA_HDR + (size_t)n * 8) return mv_fail(-1, "mvsdf_raster_resolve: workspace too small (mvsdf_raster_workspace_bytes)");
-    hipLaunchKernelGGL(k_ra_resolve, dim3((unsigned)ra_blocks(n, RA_THREADS)), dim3(RA_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_ra_resolve, dim3(mv_grid(n, RA_THREADS)), dim3(RA_THREADS), 0, (hipStream_t)stream,
                        (const unsigned long long*)((char*)ws + RA_HDR), n, depth, face);
     return mv_check(hipGetLastError(), "mvsdf_raster_resolve");
 }
@@ -426,7 +361,7 @@ int mvsdf_raster_visibility(const float* verts, int64_t nv, const double* P, int
     if (int rc = mv_check(hipMemsetAsync(ws, 0, RA_HDR, s), what)) return rc;
     hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
     if (nv > 0)
-        hipLaunchKernelGGL(k_ra_visibility, dim3((unsigned)ra_blocks(nv, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, (long long)nv, P,
+        hipLaunchKernelGGL(k_ra_visibility, dim3(mv_grid(nv, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, (long long)nv, P,
                            pixel_center, (int)H, (int)W, depth, masks, depth_tol, vis);
     return mv_check(hipGetLastError(), what);
 }
@@ -444,7 +379,7 @@ int mvsdf_raster_colors(const float* verts, const float* normals, int64_t nv, co
     hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
     hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, centers, (long long)views * 3, (unsigned long long*)ws);
     if (nv > 0)
-        hipLaunchKernelGGL(k_ra_colors, dim3((unsigned)ra_blocks(nv, RA_THREADS)), dim3(RA_THREADS), 0, s, verts, normals, (long long)nv, P, centers,
+        hipLaunchKernelGGL(k_ra_colors, dim3(mv_grid(nv, RA_THREADS)), dim3(RA_THREADS), 0, s, verts, normals, (long long)nv, P, centers,
                            (int)views, pixel_center, (int)H, (int)W, depth, masks, images, depth_tol, cos_min, (int)ignore_normals, fallback_r, fallback_g,
                            fallback_b, colors, n_views);
     return mv_check(hipGetLastError(), what);

@@ -3,7 +3,7 @@
 // in numpy.  All arithmetic is fp64 without contraction, in the order the definition writes it.
 //
 // * k_ps_normalize: one lane per texel, unit descriptors rounded to fp32 (a texel of 32 channels is one 128-byte line); sets the error bit on a non-finite
-//   feature.  k_ps_finite: the same check alone, on descriptors that come from the caller.  k_ps_patches: the mean-free grey patch descriptor.
+//   feature.  k_any_nonfinite (geom_prims.h): the same check alone, on descriptors that come from the caller.  k_ps_patches: the mean-free grey patch descriptor.
 // * k_ps_score: a 256-lane workgroup owns a 16 x 16 tile of reference pixels (four waves of 8 x 8) and PS_KCHUNK consecutive hypotheses; a lane keeps its
 //   pixel's descriptor in registers as doubles and walks k.  The 8 x 8 pixels of a wave at one k read a patch of about 9 x 9 source texels, and the next k
 //   moves that patch along the epipolar lines by about a texel, so the four-tap gathers are served by the CU's L1 and the XCD's L2 after the first touch.
@@ -14,10 +14,7 @@
 // One call sweeps every requested view in turn on the caller's stream; the score volume in the workspace is reused from view to view and holds the last
 // view's scores afterwards.  Every argument is validated on the host before anything is launched; only the finiteness of the descriptors is checked on the
 // device.  No atomics on floating point (the only atomic is the OR of an error bit).
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 
 #define PS_THREADS 256
 #define PS_TILE 16
@@ -34,9 +31,6 @@ enum {
     PS_ERR_SHAPE = 8,       // V < 1, R or S < 2, C < 1, a pair list longer than PS_MAX_SRC, sizes beyond the limits
 };
 
-static inline size_t ps_align(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline long long ps_blocks(long long n, long long per) { return (n + per - 1) / per; }
-
 struct PsLayout {
     size_t mats, src, vol, cnt, total;
 };
@@ -44,21 +38,16 @@ struct PsLayout {
 static bool ps_layout(long long R, long long S, long long D, long long npairs, PsLayout* L) {
     if (R < 2 || S < 2 || D < 1 || D > PS_MAX_D || npairs < 0 || npairs > INT_MAX || R > INT_MAX || S > INT_MAX || R * S > INT_MAX) return false;
     if (R * S * D > PS_MAX_ELEMS) return false;
-    size_t o = PS_HDR;
-    L->mats = o; o += ps_align((size_t)(npairs > 0 ? npairs : 1) * 16 * 8);
-    L->src = o;  o += ps_align((size_t)(npairs > 0 ? npairs : 1) * 4);
-    L->vol = o;  o += ps_align((size_t)(R * S * D) * 8);
-    L->cnt = o;  o += ps_align((size_t)(R * S * D));
-    L->total = o;
+    WsCursor c{PS_HDR};
+    L->mats = c.take((size_t)(npairs > 0 ? npairs : 1) * 16 * 8);
+    L->src = c.take((size_t)(npairs > 0 ? npairs : 1) * 4);
+    L->vol = c.take((size_t)(R * S * D) * 8);
+    L->cnt = c.take((size_t)(R * S * D));
+    L->total = c.o;
     return true;
 }
 
 __device__ __forceinline__ double ps_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// one row of a 4x4 matrix times q, in the definition's order
-__device__ __forceinline__ double ps_row(const double* __restrict__ t, double q0, double q1, double q2, double q3) {
-    return ((t[0] * q0 + t[1] * q1) + t[2] * q2) + t[3] * q3;
-}
 
 __global__ __launch_bounds__(PS_THREADS) void k_ps_normalize(const float* __restrict__ f, long long n, int C, float* __restrict__ out, long long* __restrict__ hdr) {
     const long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
@@ -74,12 +63,6 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_normalize(const float* __rest
     }
     const double nrm = sqrt(s);
     for (int c = 0; c < C; ++c) o[c] = nrm > 0.0 ? (float)((double)p[c] / nrm) : 0.0f;
-    if (bad) atomicOr((unsigned long long*)(hdr + 1), (unsigned long long)PS_ERR_FINITE);
-}
-
-__global__ __launch_bounds__(PS_THREADS) void k_ps_finite(const float* __restrict__ f, long long n, long long* __restrict__ hdr) {
-    bool bad = false;
-    for (long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * PS_THREADS) bad = bad || !isfinite(f[i]);
     if (bad) atomicOr((unsigned long long*)(hdr + 1), (unsigned long long)PS_ERR_FINITE);
 }
 
@@ -171,10 +154,10 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_score(const float* __restrict
         double acc = 0.0;
         for (int j = 0; j < nsrc; ++j) {
             const double* __restrict__ T = mats + (long long)j * 16;
-            const double p2 = ps_row(T + 8, q0, q1, d, 1.0);
+            const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
             if (!(p2 > 0.0)) continue;
-            const double u = ps_row(T, q0, q1, d, 1.0) / p2 - 0.5;
-            const double v = ps_row(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
+            const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
+            const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
             if (!(u >= 0.0 && u <= smax && v >= 0.0 && v <= rmax)) continue;
             const double x0 = fmin(floor(u), (double)(S - 2)), y0 = fmin(floor(v), (double)(R - 2));
             const double fx = u - x0, fy = v - y0;
@@ -240,12 +223,6 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict
     counts[p] = nk;
 }
 
-static int ps_header(void* hdr, long long err, hipStream_t s, const char* what) {
-    const long long h[2] = {0, err};
-    if (int rc = mv_check(hipMemcpyAsync(hdr, h, sizeof(h), hipMemcpyHostToDevice, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);             // h lives on this stack frame
-}
-
 extern "C" {
 
 size_t mvsdf_stereo_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs) {
@@ -260,19 +237,19 @@ size_t mvsdf_stereo_volume_offset(int64_t R, int64_t S, int64_t D, int64_t npair
 
 int mvsdf_stereo_normalize(const float* feats, int64_t n, int64_t C, float* out, void* hdr, void* stream) {
     const char* what = "mvsdf_stereo_normalize";
-    if (!feats || !out || !hdr || n < 1 || C < 1 || C > INT_MAX || n > PS_MAX_ELEMS / C || ps_blocks(n, PS_THREADS) > INT_MAX)
+    if (!feats || !out || !hdr || n < 1 || C < 1 || C > INT_MAX || n > PS_MAX_ELEMS / C || mv_ceil_div(n, PS_THREADS) > INT_MAX)
         return mv_fail(-1, "mvsdf_stereo_normalize: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = mv_check(hipMemsetAsync(hdr, 0, 16, s), what)) return rc;
-    hipLaunchKernelGGL(k_ps_normalize, dim3((unsigned)ps_blocks(n, PS_THREADS)), dim3(PS_THREADS), 0, s, feats, (long long)n, (int)C, out, (long long*)hdr);
+    hipLaunchKernelGGL(k_ps_normalize, dim3(mv_grid(n, PS_THREADS)), dim3(PS_THREADS), 0, s, feats, (long long)n, (int)C, out, (long long*)hdr);
     return mv_check(hipGetLastError(), what);
 }
 
 int mvsdf_stereo_patches(const uint8_t* images, int64_t V, int64_t H, int64_t W, int32_t radius, float* out, void* stream) {
     if (!images || !out || V < 1 || H < 1 || W < 1 || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || radius < 0 || radius > 15 ||
-        V > PS_MAX_ELEMS / (H * W) / ((2 * radius + 1) * (2 * radius + 1)) || ps_blocks(V * H * W, PS_THREADS) > INT_MAX)
+        V > PS_MAX_ELEMS / (H * W) / ((2 * radius + 1) * (2 * radius + 1)) || mv_ceil_div(V * H * W, PS_THREADS) > INT_MAX)
         return mv_fail(-1, "mvsdf_stereo_patches: bad arguments");
-    hipLaunchKernelGGL(k_ps_patches, dim3((unsigned)ps_blocks(V * H * W, PS_THREADS)), dim3(PS_THREADS), 0, (hipStream_t)stream, images, (long long)V, (int)H,
+    hipLaunchKernelGGL(k_ps_patches, dim3(mv_grid(V * H * W, PS_THREADS)), dim3(PS_THREADS), 0, (hipStream_t)stream, images, (long long)V, (int)H,
                        (int)W, (int)radius, out);
     return mv_check(hipGetLastError(), "mvsdf_stereo_patches");
 }
@@ -307,7 +284,10 @@ int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64
         for (long long k = 0; k < npairs * 16; ++k)
             if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
     }
-    if (err) return ps_header(ws, err, s, what);
+    if (err) {
+        const long long hdr[2] = {0, err};
+        return mv_write_header(ws, hdr, 2, s, what);
+    }
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_sweep: workspace too small (mvsdf_stereo_workspace_bytes)");
     // ---- uploads and launches ----
     char* w = (char*)ws;
@@ -318,9 +298,9 @@ int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64
         if ((rc = mv_check(hipMemcpyAsync(w + L.src, pair_src, (size_t)npairs * 4, hipMemcpyHostToDevice, s), what))) return rc;
     }
     const long long hw = R * S, total = V * hw * C;
-    long long fb = ps_blocks(total, PS_THREADS);
+    long long fb = mv_ceil_div(total, MV_THREADS);
     if (fb > 2048) fb = 2048;
-    hipLaunchKernelGGL(k_ps_finite, dim3((unsigned)fb), dim3(PS_THREADS), 0, s, desc, total, (long long*)ws);
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
     const bool fast = C == 32 && ((uintptr_t)desc & 15) == 0;                 // 128-byte texels read as float4
     double* vol = (double*)(w + L.vol);
     unsigned char* cnt = (unsigned char*)(w + L.cnt);
@@ -328,7 +308,7 @@ int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64
         const int r = views[i], D = nhyp[i], nsrc = pair_off[i + 1] - pair_off[i];
         const int* src = (const int*)(w + L.src) + pair_off[i];
         const double* T = (const double*)(w + L.mats) + (long long)pair_off[i] * 16;
-        const dim3 grid((unsigned)ps_blocks(S, PS_TILE), (unsigned)ps_blocks(R, PS_TILE), (unsigned)ps_blocks(D, PS_KCHUNK));
+        const dim3 grid((unsigned)mv_ceil_div(S, PS_TILE), (unsigned)mv_ceil_div(R, PS_TILE), (unsigned)mv_ceil_div(D, PS_KCHUNK));
         if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_sweep: R beyond the grid limit");
         if (fast)
             hipLaunchKernelGGL(k_ps_score<32>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
@@ -336,7 +316,7 @@ int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64
         else
             hipLaunchKernelGGL(k_ps_score<0>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
                                vol, cnt);
-        hipLaunchKernelGGL(k_ps_pick, dim3((unsigned)ps_blocks(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)vol, (const unsigned char*)cnt, (int)hw,
+        hipLaunchKernelGGL(k_ps_pick, dim3(mv_grid(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)vol, (const unsigned char*)cnt, (int)hw,
                            D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw, probs + (long long)r * 3 * hw, best_k + (long long)r * hw,
                            counts + (long long)r * hw);
     }

@@ -15,10 +15,7 @@
 // Error bits (int64 {0, bits} in the 256-byte header; the pack calls reset it, the others OR into it): 1 a non-finite point, centre or extrinsic entry,
 // 2 a track entry outside [0, V) or track offsets that are not ascending within [0, nnz], 4 V < 1, V > 65535 or P >= 2^31 (nothing is launched).
 #include <float.h>
-#include <limits.h>
-#include <math.h>
-#include <stdint.h>
-#include "capi_util.h"
+#include "geom_prims.h"
 #include "det_math64.h"
 
 #define VS_THREADS 256
@@ -35,7 +32,6 @@ enum {
 
 typedef unsigned long long vs_u64;
 
-static inline long long vs_blocks(long long n, long long per) { return (n + per - 1) / per; }
 static inline long long vs_min(long long a, long long b) { return a < b ? a : b; }
 
 // ---- the definition's arithmetic, host and device (mvsdf_viewsel_weights_host runs the same functions on the CPU) ----
@@ -77,10 +73,10 @@ __host__ __device__ static inline long long vs_quantise(double w) { return (long
 
 // ---- kernels ----
 
-__global__ __launch_bounds__(VS_THREADS) void k_vs_finite(const double* __restrict__ f, long long n, long long* __restrict__ hdr) {
-    bool bad = false;
-    for (long long i = (long long)blockIdx.x * VS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * VS_THREADS) bad = bad || !isfinite(f[i]);
-    if (bad) atomicOr((vs_u64*)(hdr + 1), (vs_u64)VS_ERR_FINITE);
+// ORs VS_ERR_FINITE into the header when an entry of f[n] is not finite
+static void vs_finite(const double* f, long long n, void* hdr, hipStream_t s) {
+    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3((unsigned)vs_min(mv_ceil_div(n, MV_THREADS), 1024ll)), dim3(MV_THREADS), 0, s, f, n, (vs_u64*)hdr + 1,
+                       (vs_u64)VS_ERR_FINITE);
 }
 
 // vis uint8 [V][P] -> bits [P][nw]; consecutive lanes take consecutive points of one word, so the 64 byte reads of a lane are coalesced over the wave
@@ -187,16 +183,14 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_depths(const double* __restri
     const int v = v0 + k;
     double out = INFINITY;
     if ((bits[p * nw + (v >> 6)] >> (v & 63)) & 1) {
-        const double* __restrict__ e = E + 4 * v;
-        out = ((e[0] * pts[3 * p] + e[1] * pts[3 * p + 1]) + e[2] * pts[3 * p + 2]) + e[3];
+        out = mv_row4(E + 4 * v, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], 1.0);
     }
     z[idx] = out;
 }
 
-static int vs_header(void* hdr, long long err, hipStream_t s, const char* what) {
-    const long long h[2] = {0, err};
-    if (int rc = mv_check(hipMemcpyAsync(hdr, h, sizeof(h), hipMemcpyHostToDevice, s), what)) return rc;
-    return mv_check(hipStreamSynchronize(s), what);             // h lives on this stack frame
+static int vs_shape_header(void* hdr, hipStream_t s, const char* what) {
+    const long long h[2] = {0, VS_ERR_SHAPE};
+    return mv_write_header(hdr, h, 2, s, what);
 }
 
 static inline bool vs_shape_ok(int64_t V, int64_t P) { return V >= 1 && V <= VS_MAX_V && P >= 0 && P <= INT_MAX; }
@@ -219,11 +213,11 @@ int mvsdf_viewsel_pack_dense(const uint8_t* vis, int64_t V, int64_t P, void* bit
     const char* what = "mvsdf_viewsel_pack_dense";
     if (!hdr || (P > 0 && (!bits || !vis))) return mv_fail(-1, "mvsdf_viewsel_pack_dense: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (!vs_shape_ok(V, P)) return vs_header(hdr, VS_ERR_SHAPE, s, what);
+    if (!vs_shape_ok(V, P)) return vs_shape_header(hdr, s, what);
     if (int rc = mv_check(hipMemsetAsync(hdr, 0, VS_HDR, s), what)) return rc;
     if (P == 0) return 0;
     const int nw = vs_words(V);
-    const long long blocks = vs_blocks((long long)P * nw, VS_THREADS);
+    const long long blocks = mv_ceil_div((long long)P * nw, VS_THREADS);
     if (blocks > INT_MAX) return mv_fail(-1, "mvsdf_viewsel_pack_dense: P * ceil(V / 64) beyond the grid limit");
     hipLaunchKernelGGL(k_vs_pack_dense, dim3((unsigned)blocks), dim3(VS_THREADS), 0, s, vis, (int)V, (long long)P, nw, (vs_u64*)bits);
     return mv_check(hipGetLastError(), what);
@@ -233,10 +227,10 @@ int mvsdf_viewsel_pack_tracks(const int64_t* track_off, const int32_t* track_vie
     const char* what = "mvsdf_viewsel_pack_tracks";
     if (!hdr || !track_off || (P > 0 && !bits) || nnz < 0 || (nnz > 0 && !track_view)) return mv_fail(-1, "mvsdf_viewsel_pack_tracks: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (!vs_shape_ok(V, P)) return vs_header(hdr, VS_ERR_SHAPE, s, what);
+    if (!vs_shape_ok(V, P)) return vs_shape_header(hdr, s, what);
     if (int rc = mv_check(hipMemsetAsync(hdr, 0, VS_HDR, s), what)) return rc;
     if (P == 0) return 0;
-    hipLaunchKernelGGL(k_vs_pack_tracks, dim3((unsigned)vs_blocks(P, VS_THREADS)), dim3(VS_THREADS), 0, s, (const long long*)track_off, track_view,
+    hipLaunchKernelGGL(k_vs_pack_tracks, dim3(mv_grid(P, VS_THREADS)), dim3(VS_THREADS), 0, s, (const long long*)track_off, track_view,
                        (long long)nnz, (int)V, (long long)P, vs_words(V), (vs_u64*)bits, (long long*)hdr);
     return mv_check(hipGetLastError(), what);
 }
@@ -254,18 +248,18 @@ int mvsdf_viewsel_scores(const double* points, const double* centers, const void
     int rc;
     if ((rc = mv_check(hipMemsetAsync(S, 0, (size_t)vv * 8, s), what))) return rc;
     if ((rc = mv_check(hipMemsetAsync(counts, 0, (size_t)vv * 8, s), what))) return rc;
-    hipLaunchKernelGGL(k_vs_finite, dim3((unsigned)vs_min(vs_blocks(3 * V, VS_THREADS), 1024ll)), dim3(VS_THREADS), 0, s, centers, (long long)(3 * V), (long long*)hdr);
+    vs_finite(centers, 3 * V, hdr, s);
     if (P > 0) {
-        hipLaunchKernelGGL(k_vs_finite, dim3((unsigned)vs_min(vs_blocks(3 * P, VS_THREADS), 1024ll)), dim3(VS_THREADS), 0, s, points, (long long)(3 * P), (long long*)hdr);
+        vs_finite(points, 3 * P, hdr, s);
         const int nw = vs_words(V);
         const long long tiles = (long long)nw * (nw + 1) / 2;
-        long long slices = vs_min(vs_min(vs_blocks(VS_TARGET_WGS, tiles), vs_blocks(P, VS_THREADS)), 65535ll);       // >= 1: P > 0
-        const long long per = vs_blocks(P, slices);
-        slices = vs_blocks(P, per);
+        long long slices = vs_min(vs_min(mv_ceil_div(VS_TARGET_WGS, tiles), mv_ceil_div(P, VS_THREADS)), 65535ll);       // >= 1: P > 0
+        const long long per = mv_ceil_div(P, slices);
+        slices = mv_ceil_div(P, per);
         hipLaunchKernelGGL(k_vs_score, dim3((unsigned)tiles, (unsigned)slices), dim3(VS_THREADS), 0, s, points, centers, (const vs_u64*)bits, (int)V, (long long)P, nw,
                            per, theta0, sigma1, sigma2, S, (vs_u64*)counts);
     }
-    hipLaunchKernelGGL(k_vs_finish, dim3((unsigned)vs_blocks(vv, VS_THREADS)), dim3(VS_THREADS), 0, s, S, vv, scores);
+    hipLaunchKernelGGL(k_vs_finish, dim3(mv_grid(vv, VS_THREADS)), dim3(VS_THREADS), 0, s, S, vv, scores);
     return mv_check(hipGetLastError(), what);
 }
 
@@ -274,13 +268,11 @@ int mvsdf_viewsel_depths(const double* points, const void* bits, const double* e
     const char* what = "mvsdf_viewsel_depths";
     if (!vs_shape_ok(V, P) || P < 1 || !points || !bits || !ext_row2 || !z || !hdr || first < 0 || nviews < 1 || first + nviews > V)
         return mv_fail(-1, "mvsdf_viewsel_depths: bad arguments");
-    const long long blocks = vs_blocks((long long)nviews * P, VS_THREADS);
+    const long long blocks = mv_ceil_div((long long)nviews * P, VS_THREADS);
     if (blocks > INT_MAX) return mv_fail(-1, "mvsdf_viewsel_depths: nviews * P beyond the grid limit");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_vs_finite, dim3((unsigned)vs_min(vs_blocks(4 * nviews, VS_THREADS), 1024ll)), dim3(VS_THREADS), 0, s, ext_row2 + 4 * first,
-                       (long long)(4 * nviews), (long long*)hdr);
-    if (first == 0)
-        hipLaunchKernelGGL(k_vs_finite, dim3((unsigned)vs_min(vs_blocks(3 * P, VS_THREADS), 1024ll)), dim3(VS_THREADS), 0, s, points, (long long)(3 * P), (long long*)hdr);
+    vs_finite(ext_row2 + 4 * first, 4 * nviews, hdr, s);
+    if (first == 0) vs_finite(points, 3 * P, hdr, s);
     hipLaunchKernelGGL(k_vs_depths, dim3((unsigned)blocks), dim3(VS_THREADS), 0, s, points, (const vs_u64*)bits, ext_row2, (int)first, (int)nviews, (long long)P,
                        vs_words(V), z);
     return mv_check(hipGetLastError(), what);

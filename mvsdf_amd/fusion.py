@@ -32,8 +32,7 @@ text is not available to this project, so its agreement with this definition bey
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
-from .mesh import _header, _stream, _vp
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp
 
 
 class Fused:

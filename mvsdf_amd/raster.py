@@ -34,8 +34,8 @@ anything is launched; a mesh on the CPU raises MvsdfError.  An empty mesh gives 
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
-from .mesh import Mesh, _header, _stream, _vp
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from .mesh import Mesh
 
 LARGE_FACE_PIXELS = 16                               # faces whose clamped pixel box holds more go to the wave-per-face path
 KEY_BUDGET_PIXELS = 1 << 27                          # default view chunk: at most 1 GiB of keys ...

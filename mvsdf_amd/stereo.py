@@ -41,9 +41,8 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp
 from .fusion import projection_matrices
-from .mesh import _header, _stream, _vp
 
 PTHRESH = (0.7, 0.02, 0.9)        # thresholds on prob1, prob2, prob3 that suit these confidences (chosen on tests/stereo_scene.py: DESIGN.md)
 MAX_SRC, MAX_D = 255, 65535

@@ -46,8 +46,7 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError
-from .mesh import _header, _stream, _vp
+from ._lib import check, lib, MvsdfError, _header, _stream, _vp
 
 MAX_VIEWS = 65535
 INT32_MAX = 2 ** 31 - 1

@@ -354,3 +354,39 @@ def test_errors():
     assert lib().mvsdf_cloud_knn(p.data_ptr(), 8, 8, ws.data_ptr(), 1 << 20, d.data_ptr(), None) != 0
     assert lib().mvsdf_cloud_knn(p.data_ptr(), 500, 8, ws.data_ptr(), 1024, d.data_ptr(), None) != 0
     assert lib().mvsdf_cloud_clean_workspace_bytes(1) == 0 and lib().mvsdf_cloud_clean_workspace_bytes(2 ** 31) == 0
+
+
+# ---- the compaction's scan (csrc/geom_prims.h: mv_scan) at its chunk edges: 2048 items per workgroup, 1024 lanes in the top scan ----
+def _compact_case(n, keep):
+    """cloud.compact == torch boolean indexing in every carried array, and the header's n_kept == the number of set flags"""
+    g = torch.Generator().manual_seed(n)
+    pts = torch.rand(n, 3, dtype=torch.float64, generator=g).cuda()
+    col = torch.randint(0, 256, (n, 3), dtype=torch.uint8, generator=g).cuda()
+    a = torch.arange(n, dtype=torch.int32).cuda()
+    b = torch.randint(-2 ** 31, 2 ** 31 - 1, (n,), dtype=torch.int32, generator=g).cuda()
+    keep = keep.cuda()
+    sel = keep.bool()
+    want = int(sel.sum())
+    got = cloud.compact(pts, keep, colors=col, a=a, b=b)                      # n_kept read from the header
+    for t, src in zip(got, (pts, col, a, b)):
+        assert t.shape[0] == want and torch.equal(t, src[sel])
+    again = cloud.compact(pts, keep, colors=col, a=a, b=b, n_kept=want)       # the caller's capacity: nothing beyond it is written
+    for t, src in zip(again, (pts, col, a, b)):
+        assert torch.equal(t, src[sel])
+    only = cloud.compact(pts, keep)
+    assert only[1] is None and only[2] is None and only[3] is None and torch.equal(only[0], pts[sel])
+
+
+@pytest.mark.parametrize('n', [1, 255, 256, 257, 2047, 2048, 2049, 4097])
+def test_compact_at_the_scan_chunk_edges(n):
+    i = torch.arange(n)
+    for keep in (torch.ones(n), torch.zeros(n), i % 2, (i + 1) % 2, i == 0, i == n - 1):
+        _compact_case(n, keep.to(torch.uint8))
+
+
+def test_compact_with_more_chunks_than_top_scan_lanes():
+    """n = 2048 * 1024 + 2049 makes 1026 chunks: every lane of the one-workgroup top scan owns two chunk totals (per = 2) and the last lanes none"""
+    n = 2048 * 1024 + 2049
+    keep = (torch.rand(n, generator=torch.Generator().manual_seed(7)) < 0.37).to(torch.uint8)
+    _compact_case(n, keep)
+    _compact_case(n, (torch.arange(n) == n - 1).to(torch.uint8))

@@ -166,3 +166,25 @@ def test_the_library_refuses_what_the_binding_would_let_through():
     assert call([0, 2, 2], [1, 0], eye, 1) == [0, 8]                            # a pair list longer than view
     n, err = call([0, 1, 2], [1, 0], eye, 10)
     assert err == 0 and n == V * H * W                                          # identity transforms: every pixel sees itself
+
+
+@pytest.mark.parametrize('vhw', [(1, 2, 1024), (1, 3, 683), (2, 32, 33)])
+def test_emit_across_a_scan_chunk_edge(vhw):
+    """2048, 2049 and 2112 pixels: the kept pixels end at, one beyond, and well beyond the first 2048-pixel chunk of the keep-flag scan
+    (csrc/geom_prims.h: mv_scan_blocks, and mv_chunk_rank in k_fu_emit).  The two-view scene with every hole filled, so vthresh = 0 keeps every pixel"""
+    V, H, W = vhw
+    cams, depths, _ = S.make_views(2, (H, W), clean=True)
+    depths = np.where(depths > 0, depths, np.float32(2.5))[:V]
+    cams, pairs = cams[:V], [[1], [0]][:V] if V == 2 else [[]]
+    rs = np.random.RandomState(V * H * W)
+    images = rs.randint(0, 256, (V, H, W, 3)).astype(np.uint8)
+    _check(cams, depths, pairs, images=images, vthresh=0, want_points=lambda n: n == V * H * W)
+    holes = np.where(rs.uniform(size=depths.shape) < 0.4, np.float32(0), depths)
+    holes.reshape(-1)[[2047, -1]] = depths.reshape(-1)[[2047, -1]]              # both sides of the chunk edge are kept
+    _check(cams, holes, pairs, images=images, vthresh=0, want_points=lambda n: V * H * W // 2 < n < V * H * W)
+    if V == 2:
+        _check(cams, depths, pairs, vthresh=1, want_points=lambda n: 0 < n < V * H * W)
+    last = np.zeros_like(depths)
+    last[-1, -1, -1] = depths[-1, -1, -1]
+    f = _check(cams, last, pairs, images=images, vthresh=0, want_points=lambda n: n == 1)   # only the last pixel survives
+    assert int(f.view[0]) == V - 1 and int(f.pixel[0]) == H * W - 1

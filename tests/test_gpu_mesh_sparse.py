@@ -223,3 +223,37 @@ def test_eval_command_sparse_obj_equals_dense(tmp_path):
     os.remove(str(obj))
     evaluation.main(args + ['--sparse_mesh'], printer=lambda *a: None)
     assert len(dense) > 1000 and obj.read_bytes() == dense
+
+
+class _Counting:
+    """a pointwise SDF that counts the points it was given and returns NaN for the bad_at-th of them"""
+
+    def __init__(self, f, bad_at=None):
+        self.f, self.n, self.bad_at = f, 0, bad_at
+
+    def __call__(self, p):
+        d = self.f(p)
+        if self.bad_at is not None and self.n <= self.bad_at < self.n + p.shape[0]:
+            d = d.clone()
+            d[self.bad_at - self.n] = float('nan')
+        self.n += p.shape[0]
+        return d
+
+
+def test_a_nonfinite_value_at_the_end_of_the_pool_and_beyond_the_first_grid_stride():
+    """the finite check over the evaluated bricks (csrc/geom_prims.h: k_any_nonfinite) runs a capped grid of 4096 x 256 lanes that strides over the pool: a
+    NaN in the pool's last value, and one that only a lane's second round reaches, must both raise.  The values reach the pool in the order the SDF is asked
+    for them, after the (nb + 1)^3 block corners"""
+    from mvsdf_amd import mesh as M
+    n, B = 257, 8
+    dry = _Counting(sphere())
+    assert M.sparse_marching_cubes(dry, n, block=B, margin=0.0) is not None
+    ncoarse = (-(-(n - 1) // B) + 1) ** 3
+    pool = dry.n - ncoarse
+    assert pool % (B + 3) ** 3 == 0 and pool > 4096 * 256 + 4096
+    for at in (dry.n - 1, ncoarse + 4096 * 256 + 4095):
+        f = _Counting(sphere(), at)
+        with pytest.raises(ValueError, match='non-finite'):
+            M.sparse_marching_cubes(f, n, block=B, margin=0.0)
+        if at == dry.n - 1:
+            assert f.n == dry.n                                              # it was the last value of the pool

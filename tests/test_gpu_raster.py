@@ -308,3 +308,26 @@ def test_render_mesh_gives_a_scene_the_masks_eval_rendering_needs(trained, tmp_p
     assert len(res['psnrs']) == len(P) and os.path.exists(os.path.join(res['evaldir'], 'psnr.txt'))
     with pytest.raises(SystemExit):                                           # the masks are there now: not written over
         _tool('render_mesh').main([t['obj'], '--data_dir', t['scene'][0], '--out', out, '--mask_dir', pmask])
+
+
+@pytest.mark.parametrize('nf,nviews', [(512, 4), (683, 3)])
+def test_large_face_list_across_a_scan_chunk_edge(nf, nviews):
+    """faces x views = 2048 and 2049 items: the compaction of the flagged (face, view) items (csrc/geom_prims.h: mv_scan_blocks + mv_chunk_rank in k_ra_emit)
+    ends exactly at, and one item beyond, the first 2048-item chunk"""
+    verts, faces, P = S.soup()
+    faces = np.ascontiguousarray(np.concatenate([faces] * (nf // len(faces) + 1))[:nf])
+    faces[-1] = faces[0]                                                      # an ordinary triangle: the last item of the list is a drawn one
+    P = np.concatenate([P, np.stack([R.look_at((-2.0, 2.2, 0.6), (0.0, 0.0, 0.0), S.SOUP_HW, 1.2 * S.SOUP_HW[0]),
+                                     R.look_at((0.3, 0.4, 3.0), (0.0, 0.0, 0.0), S.SOUP_HW, 1.2 * S.SOUP_HW[0], up=(0.0, 1.0, 0.0))])])[:nviews]
+    assert faces.shape[0] * P.shape[0] == (2048 if nviews == 4 else 2049)
+    st = {}
+    depth, face = R.rasterize(verts, faces, P, S.SOUP_HW, 0.5, st)
+    boxes = st['boxes']
+    assert (boxes[:, -1] > 0).all() and (boxes == 0).any() and (boxes.reshape(-1)[:2048] > 0).sum() > 1024   # the inputs exercise the case
+    m = _gpu_mesh(verts, faces)
+    every = raster.rasterize(m, P=P, hw=S.SOUP_HW, large_face_pixels=0)        # every drawn item is flagged and listed
+    none = raster.rasterize(m, P=P, hw=S.SOUP_HW, large_face_pixels=2 ** 40)
+    _same_raster(every, depth, face, 'large_face_pixels=0')
+    _same_raster(none, depth, face, 'large_face_pixels=2**40')
+    assert torch.equal(every.depth, none.depth) and torch.equal(every.face, none.face)
+    assert every.stats['large_items'] == nf * nviews - int((boxes == 0).sum()) and none.stats['large_items'] == 0

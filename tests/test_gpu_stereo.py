@@ -202,3 +202,21 @@ def test_estimate_scene_feeds_the_fusion_and_the_converter(tmp_path):
     for name in ('cameras_hd.npz', 'image_hd/000004.png', 'mask_hd/004.png', 'depth/004.pfm'):
         assert os.path.exists(os.path.join(scene_dir, name)), name
     assert os.path.exists(os.path.join(out, 'cut.ply')) and os.path.exists(os.path.join(out, 'all_torch.ply'))
+
+
+def test_a_nonfinite_feature_is_found_at_the_end_and_beyond_the_first_grid_stride():
+    """the finite check (csrc/geom_prims.h: k_any_nonfinite) runs a capped grid of 2048 x 256 lanes that strides over the descriptors: a NaN in the last
+    element, and one that only a lane's second round reaches, must both raise"""
+    V, R, S, C = 2, 96, 96, 32
+    assert V * R * S * C > 2048 * 256 + 4096
+    cams, pairs = SC.make_cams(V, (R, S), focal=225.0, n_depths=2)
+    g = torch.Generator().manual_seed(5)
+    desc = torch.nn.functional.normalize(torch.randn(V, R, S, C, generator=g), dim=3).cuda()
+    good = stereo.plane_sweep(desc, cams, pairs)
+    for at in (desc.numel() - 1, 2048 * 256 + 4095):
+        bad = desc.clone()
+        bad.view(-1)[at] = float('nan')
+        with pytest.raises(ValueError, match='NaN or infinite'):
+            stereo.plane_sweep(bad, cams, pairs)
+    again = stereo.plane_sweep(desc, cams, pairs)
+    assert torch.equal(again.depths, good.depths) and torch.equal(again.probs, good.probs)

@@ -213,3 +213,31 @@ def test_select_views_tool_rewrites_pair_from_a_mesh(tmp_path):
     s_ref, c_ref = R.view_scores(verts.astype(np.float64), viewsel.centers_from_cams(res['cams']), vis)
     assert (pairs, pair_scores) == R.select_pairs(s_ref, c_ref, 2)
     assert [pair[str(i)]['score'] for i in range(6)] == pair_scores
+
+
+def test_nonfinite_entries_at_the_end_and_beyond_the_first_grid_stride():
+    """the finite check (csrc/geom_prims.h: k_any_nonfinite) runs a capped grid of 1024 x 256 lanes that strides over its array: a NaN in the last element
+    of the points, the centres and the extrinsics, and one in the points that only a lane's second round reaches, must all raise"""
+    V, P = 3, 90000
+    assert 3 * P > 1024 * 256 + 4096
+    points, centers = _scene(V, P, seed=9)
+    vis = np.ones((V, P), bool)
+    E = np.stack([np.eye(4)] * V)
+    E[:, 2, 3] = 6.0
+    for at in (3 * P - 1, 1024 * 256 + 4095):
+        bad = points.copy()
+        bad.reshape(-1)[at] = np.nan
+        with pytest.raises(ValueError, match='NaN or infinite'):
+            viewsel.view_scores(bad, centers, vis)
+        with pytest.raises(ValueError, match='NaN or infinite'):
+            viewsel.depth_ranges(bad, vis, E)
+    badc = centers.copy()
+    badc[V - 1, 2] = np.inf
+    with pytest.raises(ValueError, match='NaN or infinite'):
+        viewsel.view_scores(points, badc, vis)
+    badE = E.copy()
+    badE[V - 1, 2, 3] = np.nan
+    with pytest.raises(ValueError, match='NaN or infinite'):
+        viewsel.depth_ranges(points, vis, badE)
+    out = viewsel.depth_ranges(points, vis, E)                              # and the next call is clean again
+    assert np.array_equal(out.cpu().numpy().view(np.uint64), R.depth_ranges(points, vis, E).view(np.uint64))
