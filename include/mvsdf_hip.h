@@ -658,6 +658,23 @@ int mvsdf_stereo_patches(const uint8_t* images, int64_t V, int64_t H, int64_t W,
 int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
                        const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, void* ws, size_t ws_bytes, float* depths,
                        float* probs, int32_t* best_k, int32_t* counts, void* stream);
+/* Semi-global regularisation of a score volume (the definition: mvsdf_amd/stereo.py).  mvsdf_stereo_regularize: score fp64 [D][R][S] on the device
+ * (a NaN = an invalid hypothesis) -> out fp64 [D][R][S], the regularised scores A (NaN where the input is); out must not overlap score.  paths is 4 or
+ * 8, 0 <= p1 <= p2 finite, R and S >= 1, 1 <= D <= 4096 (MAX_D_SGM), R*S <= INT32_MAX, R*S*D <= 2^40.  ws: mvsdf_stereo_sgm_workspace_bytes (0
+ * beyond the limits) device bytes; they receive int64 {0, error bits}: 1 an infinite score (out is then not valid), 16 a refused argument (nothing is
+ * launched).  No host wait unless an argument is refused.
+ * mvsdf_stereo_sweep_sgm is mvsdf_stereo_sweep with the regularisation between the scores and the pick of every view: the winner, the refinement and
+ * prob2 come from A, prob1 is the raw score at the winner, prob3 and counts its n_k.  Error bit 16: p1, p2 or paths refused, or a hypothesis count
+ * above 4096.  Its workspace is mvsdf_stereo_sweep_sgm_workspace_bytes (same arguments as mvsdf_stereo_workspace_bytes); afterwards the last view's raw
+ * volume is at mvsdf_stereo_volume_offset and its regularised volume, fp64 [D][R][S], at byte offset mvsdf_stereo_workspace_bytes. */
+size_t mvsdf_stereo_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D);
+int mvsdf_stereo_regularize(const double* score, int64_t R, int64_t S, int64_t D, double p1, double p2, int32_t paths, void* ws, size_t ws_bytes,
+                            double* out, void* stream);
+size_t mvsdf_stereo_sweep_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs);
+int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views,
+                           const int32_t* pair_off, const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, double p1,
+                           double p2, int32_t paths, void* ws, size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts,
+                           void* stream);
 
 /* ---- Point-cloud cleaning (cloud.hip; Python: mvsdf_amd/cloud.py, which states the definition) ----
  * pts fp64 [n][3] on the device, fp64 throughout.  mvsdf_cloud_knn, _components and _clean share one workspace (mvsdf_cloud_clean_workspace_bytes,

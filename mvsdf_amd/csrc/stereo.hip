@@ -10,6 +10,15 @@
 //   The dot products use fma(): the product of two fp32 values is exact in fp64, so fma(a, b, t) is t + a*b rounded once, the definition's value bit for
 //   bit (signed zeros included); nothing else is contracted.  Writes score[k][y][x] (a quiet NaN where no source is valid) and the count n_k as a byte.
 // * k_ps_pick: one lane per pixel walks the volume (coalesced over the lanes): winner, refinement, b2, the three confidences.
+// * k_sg_path: one direction of the semi-global regularisation (stereo.py: "Regularisation").  A 256-lane workgroup owns a bundle of G adjacent paths and
+//   walks them step by step; lane t owns path t % G and the hypotheses t / G, t / G + 256 / G, ...  The previous step's path costs L live in LDS, k-major
+//   ([k + 1][path], rows 0 and D + 1 hold +inf, so k - 1 and k + 1 need no branch and consecutive lanes touch consecutive words), double-buffered: one
+//   barrier per step.  An invalid L is +inf there, so every minimum skips it by itself; a path's minimum m is reduced over the wave by shuffles and over
+//   the four waves through LDS, and m = +inf is the definition's restart (q outside the image or without a valid k).  The costs and the running sum T of
+//   the next step are loaded before the barrier of this one.  Launch r adds L_r into T in place (out), the last one turns T into A; stream order is the
+//   summation order, and every element is written by one lane per launch.  For the six directions with dy != 0 a step is an image row and the G paths of
+//   a bundle are G consecutive x (8 doubles = 64 bytes per k at D <= 256); the two horizontal directions step along x with bundles of adjacent rows, their
+//   reads are strided by S and served by L2 for the 16 steps a 128-byte line lasts, so they take the smallest G that fills the lanes (more workgroups).
 //
 // One call sweeps every requested view in turn on the caller's stream; the score volume in the workspace is reused from view to view and holds the last
 // view's scores afterwards.  Every argument is validated on the host before anything is launched; only the finiteness of the descriptors is checked on the
@@ -29,7 +38,12 @@ enum {
     PS_ERR_PAIR = 2,        // a pair or view index outside [0, V)
     PS_ERR_DEPTHS = 4,      // D < 1 (or beyond PS_MAX_D)
     PS_ERR_SHAPE = 8,       // V < 1, R or S < 2, C < 1, a pair list longer than PS_MAX_SRC, sizes beyond the limits
+    PS_ERR_SGM = 16,        // the regularisation's p1, p2, paths, or D > SG_MAX_D
 };
+
+#define SG_MAX_D 4096                                 // stereo.py: MAX_D_SGM
+#define SG_MAX_ITEMS 2048                             // G * D at most this where G > 1: the two LDS buffers then take 32 KB
+#define SG_MAX_G 8
 
 struct PsLayout {
     size_t mats, src, vol, cnt, total;
@@ -174,10 +188,12 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_score(const float* __restrict
     }
 }
 
-// winner, refinement and confidences of every pixel of one view; used = the number of sources the view sweeps
-__global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict__ vol, const unsigned char* __restrict__ cnt, int hw, int D, double dmin,
-                                                         double interval, int used, float* __restrict__ depth, float* __restrict__ prob,
-                                                         int* __restrict__ best_k, int* __restrict__ counts) {
+// winner, refinement and confidences of every pixel of one view; used = the number of sources the view sweeps.  REG: vol is the regularised volume
+// and prob1 the raw score (raw) at its winner
+template <bool REG>
+__global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict__ vol, const double* __restrict__ raw, const unsigned char* __restrict__ cnt,
+                                                         int hw, int D, double dmin, double interval, int used, float* __restrict__ depth,
+                                                         float* __restrict__ prob, int* __restrict__ best_k, int* __restrict__ counts) {
     const int p = blockIdx.x * PS_THREADS + threadIdx.x;
     if (p >= hw) return;
     int ks = -1;
@@ -208,7 +224,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict
             }
         }
         dep = (float)(dmin + ((double)ks + off) * interval);
-        p1 = (float)fmin(fmax(b, 0.0), 1.0);
+        p1 = (float)fmin(fmax(REG ? raw[(long long)ks * hw + p] : b, 0.0), 1.0);
         if (b <= 0.0) p2 = 0.0f;
         else if (!any) p2 = 1.0f;
         else p2 = (float)fmin(fmax(1.0 - fmax(b2, 0.0) / b, 0.0), 1.0);
@@ -222,6 +238,257 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict
     best_k[p] = ks;
     counts[p] = nk;
 }
+
+// ================================================================ semi-global regularisation ================================================================
+// one direction: step t of path c visits pixel (py0 + cy*c + ty*t, px0 + cx*c + tx*t); c = c0 + 0 .. npaths - 1
+struct SgDir {
+    int py0, cy, ty, px0, cx, tx, c0, npaths, nsteps;
+};
+enum { SG_FIRST = 0, SG_ADD = 1, SG_LAST = 2 };       // what a launch does with T: write L, add L, add L and turn the sum into A
+
+__device__ __forceinline__ double sg_min(double a, double b) { return b < a ? b : a; }          // no NaN reaches it
+
+// the steps at which p0 + cc*c + tt*t can be inside [0, n) for some c in [ca, cb]
+__device__ __forceinline__ void sg_clip(int p0, int cc, int tt, int ca, int cb, int n, int& lo, int& hi) {
+    const int a = p0 + cc * ca, b = p0 + cc * cb;
+    if (tt > 0) { lo = max(lo, -b); hi = min(hi, n - 1 - a); }
+    else if (tt < 0) { lo = max(lo, a - (n - 1)); hi = min(hi, b); }
+}
+
+template <int ITEMS>
+__global__ __launch_bounds__(PS_THREADS) void k_sg_path(const double* __restrict__ score, double* __restrict__ out, int R, int S, int D, SgDir dir, int lg,
+                                                         double p1, double p2, int mode, double inv_paths, unsigned long long* __restrict__ errword) {
+    extern __shared__ double sg_lds[];
+    const int G = 1 << lg, kstride = PS_THREADS >> lg;
+    const int t = threadIdx.x, g = t & (G - 1), kq = t >> lg, wave = t >> 6;
+    const int rows = (D + 2) * G;                                         // doubles per buffer
+    double* __restrict__ red = sg_lds + 2 * rows;                         // [2][4 waves][G]: the waves' minima of every path
+    const double inf = INFINITY;
+    for (int i = t; i < 2 * rows; i += PS_THREADS) sg_lds[i] = inf;
+    if (t < 2 * 4 * SG_MAX_G) red[t] = inf;
+    const int pi = blockIdx.x * G + g;
+    const bool active = pi < dir.npaths;
+    const int c = dir.c0 + pi;
+    int lo = 0, hi = dir.nsteps - 1;
+    {
+        const int ca = dir.c0 + blockIdx.x * G, cb = min(ca + G - 1, dir.c0 + dir.npaths - 1);
+        sg_clip(dir.py0, dir.cy, dir.ty, ca, cb, R, lo, hi);
+        sg_clip(dir.px0, dir.cx, dir.tx, ca, cb, S, lo, hi);
+    }
+    const long long hw = (long long)R * S;
+    const int py = dir.py0 + dir.cy * c, px = dir.px0 + dir.cx * c;
+    double cn[ITEMS], tn[ITEMS];                                          // the next step's scores and running sums
+    bool in_n = false;
+    long long pix_n = 0;
+#define SG_FETCH(step)                                                                                      \
+    {                                                                                                       \
+        const int y_ = py + dir.ty * (step), x_ = px + dir.tx * (step);                                     \
+        in_n = active && (step) <= hi && y_ >= 0 && y_ < R && x_ >= 0 && x_ < S;                            \
+        pix_n = (long long)y_ * S + x_;                                                                     \
+        _Pragma("unroll") for (int j = 0; j < ITEMS; ++j) {                                                 \
+            const int k_ = kq + j * kstride;                                                                \
+            const bool ok_ = in_n && k_ < D;                                                                \
+            cn[j] = ok_ ? score[(long long)k_ * hw + pix_n] : ps_nan();                                     \
+            tn[j] = ok_ && mode != SG_FIRST ? out[(long long)k_ * hw + pix_n] : 0.0;                        \
+        }                                                                                                   \
+    }
+    SG_FETCH(lo)
+    __syncthreads();
+    bool bad = false;
+    int cur = 0;
+    for (int step = lo; step <= hi; ++step) {
+        const double* __restrict__ prev = sg_lds + cur * rows;
+        double* __restrict__ next = sg_lds + (cur ^ 1) * rows;
+        const double* __restrict__ rp = red + cur * 4 * SG_MAX_G;
+        const double m = sg_min(sg_min(rp[g], rp[SG_MAX_G + g]), sg_min(rp[2 * SG_MAX_G + g], rp[3 * SG_MAX_G + g]));
+        const bool restart = !(m < inf);
+        const double jump = m + p2;
+        const bool in = in_n;
+        const long long pix = pix_n;
+        double cc[ITEMS], tt[ITEMS];
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) { cc[j] = cn[j]; tt[j] = tn[j]; }
+        if (step < hi) SG_FETCH(step + 1)
+        double mine = inf;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const int k = kq + j * kstride;
+            if (k < D) {
+                const double s = cc[j];
+                double L = inf;
+                if (s == s) {
+                    bad = bad || isinf(s);
+                    const double cost = 1.0 - s;
+                    if (restart) L = cost;
+                    else {
+                        const double best = sg_min(sg_min(prev[(k + 1) * G + g], prev[k * G + g] + p1), sg_min(prev[(k + 2) * G + g] + p1, jump));
+                        L = cost + (best - m);
+                    }
+                    const long long at = (long long)k * hw + pix;
+                    if (mode == SG_FIRST) out[at] = L;
+                    else if (mode == SG_ADD) out[at] = tt[j] + L;
+                    else out[at] = 1.0 - (tt[j] + L) * inv_paths;              // inv_paths is 1/4 or 1/8: the product is the exact quotient
+                    mine = sg_min(mine, L);
+                } else if (in && mode == SG_FIRST) out[(long long)k * hw + pix] = ps_nan();
+                next[(k + 1) * G + g] = L;
+            }
+        }
+        for (int d = G; d < 64; d <<= 1) mine = sg_min(mine, __shfl_xor(mine, d));
+        if ((t & 63) < G) red[(cur ^ 1) * 4 * SG_MAX_G + wave * SG_MAX_G + g] = mine;
+        __syncthreads();
+        cur ^= 1;
+    }
+#undef SG_FETCH
+    if (__ballot(bad) && (t & 63) == 0) atomicOr(errword, (unsigned long long)PS_ERR_FINITE);
+}
+
+// ---- host side of the regularisation ----
+static bool sg_limits(long long R, long long S, long long D) {
+    return R >= 1 && S >= 1 && D >= 1 && D <= SG_MAX_D && R <= INT_MAX && S <= INT_MAX && R * S <= INT_MAX && R * S * D <= PS_MAX_ELEMS;
+}
+
+static bool sg_args(double p1, double p2, int paths) { return isfinite(p1) && isfinite(p2) && p1 >= 0.0 && p1 <= p2 && (paths == 4 || paths == 8); }
+
+template <int ITEMS>
+static int sg_launch(unsigned grid, size_t lds, hipStream_t s, const double* score, double* out, int R, int S, int D, const SgDir& dir, int lg, double p1,
+                     double p2, int mode, double inv_paths, unsigned long long* errword) {
+    static size_t allowed = 48 * 1024;                                    // above it the kernel has to be told (once per size)
+    if (lds > allowed) {
+        if (int rc = mv_check(hipFuncSetAttribute((const void*)k_sg_path<ITEMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "mvsdf_stereo_regularize"))
+            return rc;
+        allowed = lds;
+    }
+    hipLaunchKernelGGL(k_sg_path<ITEMS>, dim3(grid), dim3(PS_THREADS), lds, s, score, out, R, S, D, dir, lg, p1, p2, mode, inv_paths, errword);
+    return 0;
+}
+
+// the launches of one volume: out = A(score).  The limits and the arguments have been checked.
+static int sg_run(const double* score, double* out, long long R, long long S, long long D, double p1, double p2, int paths, unsigned long long* errword,
+                  hipStream_t s) {
+    static const int DIRS[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};       // (dy, dx), the definition's order
+    int lgv = 0, lgh = 0;                                                 // log2 G of the directions with dy != 0 / of the horizontal ones
+    while ((2 << lgv) <= SG_MAX_G && (long long)(2 << lgv) * D <= SG_MAX_ITEMS) ++lgv;
+    while (lgh < lgv && (long long)(1 << lgh) * D < PS_THREADS) ++lgh;
+    for (int h = 0; h < 2; ++h)                                           // development library only: MVSDF_SGM_LGV / MVSDF_SGM_LGH = log2 G, for timing other bundles
+        if (const char* e = mv_dev_env(h ? "MVSDF_SGM_LGH" : "MVSDF_SGM_LGV")) {
+            const int v = atoi(e);
+            if (v >= 0 && (1 << v) <= SG_MAX_G && ((long long)D << v) <= 16 * PS_THREADS && (v == 0 || ((long long)D << v) <= SG_MAX_ITEMS)) (h ? lgh : lgv) = v;
+        }
+    for (int r = 0; r < paths; ++r) {
+        const int dy = DIRS[r][0], dx = DIRS[r][1];
+        SgDir d;
+        int lg;
+        if (dy != 0) {
+            d.py0 = dy > 0 ? 0 : (int)R - 1; d.cy = 0; d.ty = dy;
+            d.px0 = 0; d.cx = 1; d.tx = dx;
+            d.c0 = dx > 0 ? -((int)R - 1) : 0;
+            d.npaths = (int)S + (dx != 0 ? (int)R - 1 : 0);
+            d.nsteps = (int)R;
+            lg = lgv;
+        } else {
+            d.py0 = 0; d.cy = 1; d.ty = 0;
+            d.px0 = dx > 0 ? 0 : (int)S - 1; d.cx = 0; d.tx = dx;
+            d.c0 = 0;
+            d.npaths = (int)R;
+            d.nsteps = (int)S;
+            lg = lgh;
+        }
+        const unsigned grid = (unsigned)mv_ceil_div(d.npaths, 1 << lg);
+        const size_t lds = (size_t)(2 * (D + 2) * (1 << lg) + 2 * 4 * SG_MAX_G) * 8;
+        const long long need = mv_ceil_div(D << lg, PS_THREADS);          // hypotheses per lane
+        const int mode = r == 0 ? SG_FIRST : r == paths - 1 ? SG_LAST : SG_ADD;
+        const double inv = 1.0 / (double)paths;
+        int rc;
+#define SG_GO(N) sg_launch<N>(grid, lds, s, score, out, (int)R, (int)S, (int)D, d, lg, p1, p2, mode, inv, errword)
+        if (need <= 1) rc = SG_GO(1);
+        else if (need <= 2) rc = SG_GO(2);
+        else if (need <= 4) rc = SG_GO(4);
+        else if (need <= 8) rc = SG_GO(8);
+        else rc = SG_GO(16);
+#undef SG_GO
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// mvsdf_stereo_sweep (sgm false) and mvsdf_stereo_sweep_sgm: per view the scores, the regularisation where asked for, the pick
+static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths, const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews,
+                    const int32_t* views, const int32_t* pair_off, const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp,
+                    void* ws, size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts, void* stream) {
+    if (!desc || !views || !pair_off || !mats || !ranges || !nhyp || !ws || !depths || !probs || !best_k || !counts || nviews < 0 || ws_bytes < PS_HDR)
+        return mv_fail(-1, "mvsdf_stereo_sweep: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    // ---- validation, all of it before the first launch ----
+    long long err = 0, npairs = 0, dmax = 1;
+    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > INT_MAX || pair_off[0] != 0) err |= PS_ERR_SHAPE;
+    else {
+        for (long long i = 0; i < nviews; ++i) {
+            const long long len = (long long)pair_off[i + 1] - pair_off[i];
+            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
+            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
+            if (nhyp[i] < 1 || nhyp[i] > PS_MAX_D) err |= PS_ERR_DEPTHS;
+            else if (nhyp[i] > dmax) dmax = nhyp[i];
+            if (!isfinite(ranges[2 * i]) || !isfinite(ranges[2 * i + 1])) err |= PS_ERR_FINITE;
+        }
+        npairs = pair_off[nviews];
+    }
+    PsLayout L;
+    if (!(err & PS_ERR_SHAPE) && (!ps_layout(R, S, dmax, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
+        err |= PS_ERR_SHAPE;
+    if (sgm && (!sg_args(p1, p2, paths) || dmax > SG_MAX_D)) err |= PS_ERR_SGM;
+    if (!(err & PS_ERR_SHAPE)) {
+        for (long long k = 0; k < npairs; ++k)
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
+        for (long long k = 0; k < npairs * 16; ++k)
+            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
+    }
+    if (err) {
+        const long long hdr[2] = {0, err};
+        return mv_write_header(ws, hdr, 2, s, what);
+    }
+    if (ws_bytes < L.total + (sgm ? mv_align256((size_t)(R * S * dmax) * 8) : 0))
+        return mv_fail(-1, "mvsdf_stereo_sweep: workspace too small (mvsdf_stereo_workspace_bytes / mvsdf_stereo_sweep_sgm_workspace_bytes)");
+    // ---- uploads and launches ----
+    char* w = (char*)ws;
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what))) return rc;
+    if (npairs > 0) {
+        if ((rc = mv_check(hipMemcpyAsync(w + L.mats, mats, (size_t)npairs * 16 * 8, hipMemcpyHostToDevice, s), what))) return rc;
+        if ((rc = mv_check(hipMemcpyAsync(w + L.src, pair_src, (size_t)npairs * 4, hipMemcpyHostToDevice, s), what))) return rc;
+    }
+    const long long hw = R * S, total = V * hw * C;
+    long long fb = mv_ceil_div(total, MV_THREADS);
+    if (fb > 2048) fb = 2048;
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
+    const bool fast = C == 32 && ((uintptr_t)desc & 15) == 0;                 // 128-byte texels read as float4
+    double* vol = (double*)(w + L.vol);
+    unsigned char* cnt = (unsigned char*)(w + L.cnt);
+    double* reg = (double*)(w + L.total);                                    // the regularised volume (sgm)
+    for (long long i = 0; i < nviews; ++i) {
+        const int r = views[i], D = nhyp[i], nsrc = pair_off[i + 1] - pair_off[i];
+        const int* src = (const int*)(w + L.src) + pair_off[i];
+        const double* T = (const double*)(w + L.mats) + (long long)pair_off[i] * 16;
+        const dim3 grid((unsigned)mv_ceil_div(S, PS_TILE), (unsigned)mv_ceil_div(R, PS_TILE), (unsigned)mv_ceil_div(D, PS_KCHUNK));
+        if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_sweep: R beyond the grid limit");
+        if (fast)
+            hipLaunchKernelGGL(k_ps_score<32>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
+                               vol, cnt);
+        else
+            hipLaunchKernelGGL(k_ps_score<0>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
+                               vol, cnt);
+        if (sgm) {
+            if ((rc = sg_run(vol, reg, R, S, D, p1, p2, paths, (unsigned long long*)ws + 1, s))) return rc;
+            hipLaunchKernelGGL(k_ps_pick<true>, dim3(mv_grid(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)reg, (const double*)vol,
+                               (const unsigned char*)cnt, (int)hw, D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw,
+                               probs + (long long)r * 3 * hw, best_k + (long long)r * hw, counts + (long long)r * hw);
+        } else
+            hipLaunchKernelGGL(k_ps_pick<false>, dim3(mv_grid(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)vol, (const double*)vol,
+                               (const unsigned char*)cnt, (int)hw, D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw,
+                               probs + (long long)r * 3 * hw, best_k + (long long)r * hw, counts + (long long)r * hw);
+    }
+    return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
+}
+
 
 extern "C" {
 
@@ -257,70 +524,40 @@ int mvsdf_stereo_patches(const uint8_t* images, int64_t V, int64_t H, int64_t W,
 int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
                        const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, void* ws, size_t ws_bytes, float* depths,
                        float* probs, int32_t* best_k, int32_t* counts, void* stream) {
-    const char* what = "mvsdf_stereo_sweep";
-    if (!desc || !views || !pair_off || !mats || !ranges || !nhyp || !ws || !depths || !probs || !best_k || !counts || nviews < 0 || ws_bytes < PS_HDR)
-        return mv_fail(-1, "mvsdf_stereo_sweep: bad arguments");
+    return ps_sweep("mvsdf_stereo_sweep", false, 0.0, 0.0, 0, desc, V, R, S, C, nviews, views, pair_off, pair_src, mats, ranges, nhyp, ws, ws_bytes, depths,
+                    probs, best_k, counts, stream);
+}
+
+size_t mvsdf_stereo_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D) { return sg_limits(R, S, D) ? PS_HDR : 0; }
+
+int mvsdf_stereo_regularize(const double* score, int64_t R, int64_t S, int64_t D, double p1, double p2, int32_t paths, void* ws, size_t ws_bytes,
+                            double* out, void* stream) {
+    const char* what = "mvsdf_stereo_regularize";
+    if (!score || !out || !ws || ws_bytes < PS_HDR) return mv_fail(-1, "mvsdf_stereo_regularize: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    // ---- validation, all of it before the first launch ----
-    long long err = 0, npairs = 0, dmax = 1;
-    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > INT_MAX || pair_off[0] != 0) err |= PS_ERR_SHAPE;
-    else {
-        for (long long i = 0; i < nviews; ++i) {
-            const long long len = (long long)pair_off[i + 1] - pair_off[i];
-            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
-            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
-            if (nhyp[i] < 1 || nhyp[i] > PS_MAX_D) err |= PS_ERR_DEPTHS;
-            else if (nhyp[i] > dmax) dmax = nhyp[i];
-            if (!isfinite(ranges[2 * i]) || !isfinite(ranges[2 * i + 1])) err |= PS_ERR_FINITE;
-        }
-        npairs = pair_off[nviews];
-    }
-    PsLayout L;
-    if (!(err & PS_ERR_SHAPE) && (!ps_layout(R, S, dmax, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
-        err |= PS_ERR_SHAPE;
-    if (!(err & PS_ERR_SHAPE)) {
-        for (long long k = 0; k < npairs; ++k)
-            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
-        for (long long k = 0; k < npairs * 16; ++k)
-            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
-    }
-    if (err) {
-        const long long hdr[2] = {0, err};
+    if (!sg_limits(R, S, D) || !sg_args(p1, p2, paths)) {
+        const long long hdr[2] = {0, PS_ERR_SGM};
         return mv_write_header(ws, hdr, 2, s, what);
     }
-    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_sweep: workspace too small (mvsdf_stereo_workspace_bytes)");
-    // ---- uploads and launches ----
-    char* w = (char*)ws;
-    int rc;
-    if ((rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what))) return rc;
-    if (npairs > 0) {
-        if ((rc = mv_check(hipMemcpyAsync(w + L.mats, mats, (size_t)npairs * 16 * 8, hipMemcpyHostToDevice, s), what))) return rc;
-        if ((rc = mv_check(hipMemcpyAsync(w + L.src, pair_src, (size_t)npairs * 4, hipMemcpyHostToDevice, s), what))) return rc;
-    }
-    const long long hw = R * S, total = V * hw * C;
-    long long fb = mv_ceil_div(total, MV_THREADS);
-    if (fb > 2048) fb = 2048;
-    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
-    const bool fast = C == 32 && ((uintptr_t)desc & 15) == 0;                 // 128-byte texels read as float4
-    double* vol = (double*)(w + L.vol);
-    unsigned char* cnt = (unsigned char*)(w + L.cnt);
-    for (long long i = 0; i < nviews; ++i) {
-        const int r = views[i], D = nhyp[i], nsrc = pair_off[i + 1] - pair_off[i];
-        const int* src = (const int*)(w + L.src) + pair_off[i];
-        const double* T = (const double*)(w + L.mats) + (long long)pair_off[i] * 16;
-        const dim3 grid((unsigned)mv_ceil_div(S, PS_TILE), (unsigned)mv_ceil_div(R, PS_TILE), (unsigned)mv_ceil_div(D, PS_KCHUNK));
-        if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_sweep: R beyond the grid limit");
-        if (fast)
-            hipLaunchKernelGGL(k_ps_score<32>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
-                               vol, cnt);
-        else
-            hipLaunchKernelGGL(k_ps_score<0>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
-                               vol, cnt);
-        hipLaunchKernelGGL(k_ps_pick, dim3(mv_grid(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)vol, (const unsigned char*)cnt, (int)hw,
-                           D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw, probs + (long long)r * 3 * hw, best_k + (long long)r * hw,
-                           counts + (long long)r * hw);
-    }
-    return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
+    const size_t bytes = (size_t)(R * S * D) * 8;
+    if ((const char*)score < (const char*)out + bytes && (const char*)out < (const char*)score + bytes)
+        return mv_fail(-1, "mvsdf_stereo_regularize: out overlaps score");
+    if (int rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what)) return rc;
+    if (int rc = sg_run(score, out, R, S, D, p1, p2, paths, (unsigned long long*)ws + 1, s)) return rc;
+    return mv_check(hipGetLastError(), what);
+}
+
+size_t mvsdf_stereo_sweep_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs) {
+    PsLayout L;
+    return ps_layout(R, S, D, npairs, &L) && D <= SG_MAX_D ? L.total + mv_align256((size_t)(R * S * D) * 8) : 0;
+}
+
+int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views,
+                           const int32_t* pair_off, const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, double p1,
+                           double p2, int32_t paths, void* ws, size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts,
+                           void* stream) {
+    return ps_sweep("mvsdf_stereo_sweep_sgm", true, p1, p2, paths, desc, V, R, S, C, nviews, views, pair_off, pair_src, mats, ranges, nhyp, ws, ws_bytes,
+                    depths, probs, best_k, counts, stream);
 }
 
 }  // extern "C"

@@ -29,12 +29,29 @@ The definition (fp64 throughout, in the order written, no FMA contraction; fp32 
 - Confidences, fp32 in [0, 1]: prob1 = min(max(b, 0), 1).  prob2 = 0 if b <= 0, else min(max(1 - max(b2, 0)/b, 0), 1) with b2 the greatest score
   over the valid k with |k - k*| >= 2, and 1 where there is no such k.  prob3 = n_k* / (the number of sources used for r = min(num_src,
   len(pairs[r]))).  counts holds n_k*.
+- Regularisation (regularize_scores; plane_sweep(regularize=...), off by default): semi-global aggregation of the score volume (SGM,
+  Hirschmueller), between the aggregate and the winner.  Input: score[k][y][x], fp64 [D,R,S], NaN where the hypothesis is invalid, every other entry
+  finite; the penalties P1, P2 and the number of paths.
+  Cost: C(p,k) = 1 - score[k][p] where valid; an invalid entry takes no part in any minimum.
+  Directions (dy, dx), in this order: (0,1), (0,-1), (1,0), (-1,0), (1,1), (-1,-1), (1,-1), (-1,1); paths = 4 uses the first four, paths = 8 all.
+  Path cost along direction r, with q = p - r: L_r(p,k) is invalid where C(p,k) is.  Otherwise, if q is outside the image or no k is valid at q,
+  L_r(p,k) = C(p,k) (the path restarts there).  Otherwise m = the minimum of L_r(q,j) over the valid j,
+  best = min(L_r(q,k), L_r(q,k-1) + P1, L_r(q,k+1) + P1, m + P2) over those of the four terms that exist and are valid, and
+  L_r(p,k) = C(p,k) + (best - m).
+  Sum: T(p,k) = ((L_1 + L_2) + L_3) + ... in direction order, from the first term on.  Regularised score: A(p,k) = 1 - T(p,k)/paths (the division
+  by 4 or 8 is exact); A is NaN where C is invalid.
+  Winner, refinement and prob2 are the ones above applied to A unchanged (b, a, c and b2 are A's values).  prob1 stays the clamped RAW score at the
+  new k*, so a threshold on it keeps its meaning; prob3 and counts stay n_k*.
+  P1 and P2 are finite with 0 <= P1 <= P2, paths is 4 or 8 and D <= MAX_D_SGM = 4096 (one path's previous-step costs, held twice, are then 64 KB
+  of the CU's 160 KB of LDS); otherwise, and for an infinite score, ValueError.  Every minimum is exact and every sum is one lane's own in a fixed
+  order, so the result does not depend on the schedule.  tests/stereo_sgm_ref.py restates it in numpy.
 - patch_descriptors: grey = (299 R + 587 G + 114 B)/1000; the (2 radius + 1)^2 grey values around the pixel, rows then columns, coordinates clamped
   to the image; mean = (0 + g_0 + g_1 + ...)/(2 radius + 1)^2; channel i = fp32(g_i - mean).
 
 Non-finite features or cameras, R or S below 2, D < 1 and a pair index outside [0, V) raise ValueError.
 
-Not built: Vis-MVSNet's learned regularisation, cascaded (coarse-to-fine) sweeps, visibility-weighted aggregation.
+Not built: Vis-MVSNet's learned regularisation (the semi-global aggregation above stands in for it), cascaded (coarse-to-fine) sweeps,
+visibility-weighted aggregation.
 """
 import os
 
@@ -46,15 +63,17 @@ from .fusion import projection_matrices
 
 PTHRESH = (0.7, 0.02, 0.9)        # thresholds on prob1, prob2, prob3 that suit these confidences (chosen on tests/stereo_scene.py: DESIGN.md)
 MAX_SRC, MAX_D = 255, 65535
+MAX_D_SGM = 4096                  # the most hypotheses regularize_scores takes
+SGM_DEFAULTS = (0.1, 0.8, 8)      # P1, P2, paths (chosen on the noisy test scene: DESIGN.md)
 
 
 class Sweep:
     """The result of plane_sweep: depths fp32 [V,R,S], probs fp32 [V,3,R,S], best_k int32 [V,R,S] (-1: no valid hypothesis), counts int32 [V,R,S]
     (n_k*), all on the device and zero (best_k -1) for views that were not swept; scores: fp64 [D,R,S] of the last view swept (NaN where a
-    hypothesis is invalid) or None."""
+    hypothesis is invalid) or None; reg_scores: that view's regularised scores A where the sweep regularised and scores were asked for, else None."""
 
-    def __init__(self, depths, probs, best_k, counts, scores=None):
-        self.depths, self.probs, self.best_k, self.counts, self.scores = depths, probs, best_k, counts, scores
+    def __init__(self, depths, probs, best_k, counts, scores=None, reg_scores=None):
+        self.depths, self.probs, self.best_k, self.counts, self.scores, self.reg_scores = depths, probs, best_k, counts, scores, reg_scores
 
 
 def _errors(err, what):
@@ -66,6 +85,8 @@ def _errors(err, what):
         raise ValueError('%s: the number of depth hypotheses must be in [1, %d]' % (what, MAX_D))
     if err & 8:
         raise ValueError('%s: shapes disagree or are out of range (V >= 1, R and S >= 2, C >= 1, at most %d sources)' % (what, MAX_SRC))
+    if err & 16:
+        raise ValueError('%s: the regularisation needs finite 0 <= P1 <= P2, paths 4 or 8 and at most %d hypotheses' % (what, MAX_D_SGM))
     if err:
         raise MvsdfError('%s failed (error bits %d)' % (what, err))
 
@@ -111,10 +132,64 @@ def patch_descriptors(images_u8, radius=2):
     return out
 
 
-def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False):
+def _sgm_args(regularize, what):
+    """None -> None; True -> the defaults; (p1, p2) or (p1, p2, paths) -> (p1, p2, paths), checked"""
+    if regularize is None or regularize is False:
+        return None
+    if regularize is True:
+        return SGM_DEFAULTS
+    try:
+        r = tuple(regularize)
+    except TypeError:
+        r = ()
+    if len(r) not in (2, 3):
+        raise ValueError('%s: regularize must be None, True, (p1, p2) or (p1, p2, paths), got %r' % (what, regularize))
+    return _sgm_checked(r[0], r[1], r[2] if len(r) == 3 else SGM_DEFAULTS[2], what)
+
+
+def _sgm_checked(p1, p2, paths, what):
+    p1, p2 = float(p1), float(p2)
+    if not (np.isfinite(p1) and np.isfinite(p2) and 0.0 <= p1 <= p2):
+        raise ValueError('%s: the penalties must be finite with 0 <= p1 <= p2, got %r, %r' % (what, p1, p2))
+    if paths != 4 and paths != 8:
+        raise ValueError('%s: paths must be 4 or 8, got %r' % (what, paths))
+    return p1, p2, int(paths)
+
+
+def regularize_scores(volume, p1=SGM_DEFAULTS[0], p2=SGM_DEFAULTS[1], paths=SGM_DEFAULTS[2]):
+    """volume [D,R,S] (NaN = an invalid hypothesis) -> the definition's regularised scores A, fp64 [D,R,S] on the device"""
+    what = 'regularize_scores'
+    p1, p2, paths = _sgm_checked(p1, p2, paths, what)
+    v = torch.as_tensor(volume)
+    if v.dim() != 3:
+        raise ValueError('%s: the volume must be [D, R, S], got shape %s' % (what, tuple(v.shape)))
+    D, R, S = v.shape
+    if D < 1 or R < 1 or S < 1:
+        raise ValueError('%s: the volume must hold at least one hypothesis of one pixel, got shape %s' % (what, tuple(v.shape)))
+    if D > MAX_D_SGM:
+        raise ValueError('%s: at most %d hypotheses, got %d' % (what, MAX_D_SGM, D))
+    if R * S > 2 ** 31 - 1 or R * S * D > 2 ** 40:
+        raise ValueError('%s: %d x %d pixels of %d hypotheses are beyond the limits (R*S < 2^31, R*S*D <= 2^40)' % (what, R, S, D))
+    if not v.is_cuda and bool(torch.isinf(v).any()):
+        raise ValueError('%s: a score is infinite' % what)
+    v = v.to(v.device if v.is_cuda else torch.device('cuda'), torch.float64).contiguous()
+    out = torch.empty_like(v)
+    size = lib().mvsdf_stereo_sgm_workspace_bytes(R, S, D)
+    ws = torch.empty(size, dtype=torch.uint8, device=v.device)
+    check(lib().mvsdf_stereo_regularize(_vp(v), R, S, D, p1, p2, paths, _vp(ws), size, _vp(out), _stream(v)), 'mvsdf_stereo_regularize')
+    _, err = _header(ws, 2)
+    if err & 1:
+        raise ValueError('%s: a score is infinite' % what)
+    _errors(err, what)
+    return out
+
+
+def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, regularize=None):
     """The module's definition -> Sweep.  Device tensors are used where they are (the stream is theirs); numpy / CPU input is copied to the GPU.
-    views: the reference views to sweep, in this order (default: all); scores=True also returns the score volume of the last of them."""
+    views: the reference views to sweep, in this order (default: all); scores=True also returns the score volume of the last of them.
+    regularize: None (winner-take-all on the raw scores), True (the regularisation with SGM_DEFAULTS), (p1, p2) or (p1, p2, paths)."""
     what = 'plane_sweep'
+    sgm = _sgm_args(regularize, what)
     cams = np.asarray(cams.cpu() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
     f = torch.as_tensor(descriptors)
     if f.dim() == 4 and cams.shape != (f.shape[0], 2, 4, 4):
@@ -138,6 +213,8 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False):
     nhyp = cams[views, 1, 3, 2] if views else np.zeros(0)
     if (nhyp != np.floor(nhyp)).any() or (nhyp < 1).any() or (nhyp > MAX_D).any():
         raise ValueError('%s: the number of depth hypotheses (cams[v, 1, 3, 2]) must be a whole number in [1, %d]' % (what, MAX_D))
+    if sgm and (nhyp > MAX_D_SGM).any():
+        raise ValueError('%s: the regularisation takes at most %d depth hypotheses' % (what, MAX_D_SGM))
     f, dev = _feature_tensor(f, what)
     V, R, S, C = f.shape
     try:
@@ -160,7 +237,7 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False):
     ranges = np.ascontiguousarray(cams[views, 1, 3, :2] if views else np.zeros((0, 2)), np.float64)
     nh = np.asarray(nhyp, np.int32)
     dmax = int(nh.max()) if len(nh) else 1
-    size = lib().mvsdf_stereo_workspace_bytes(R, S, dmax, npairs)
+    size = (lib().mvsdf_stereo_sweep_sgm_workspace_bytes if sgm else lib().mvsdf_stereo_workspace_bytes)(R, S, dmax, npairs)
     if size == 0:
         raise ValueError('%s: %d x %d texels of %d hypotheses are beyond the limits (R*S < 2^31, R*S*D <= 2^40)' % (what, R, S, dmax))
     ws = torch.empty(size, dtype=torch.uint8, device=dev)
@@ -170,17 +247,24 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False):
     counts = torch.zeros(V, R, S, dtype=torch.int32, device=dev)
     if not views:
         return Sweep(depths, probs, best_k, counts, None)
-    check(lib().mvsdf_stereo_sweep(_vp(f), V, R, S, C, len(views), vw.ctypes.data, off.ctypes.data, src.ctypes.data if npairs else None,
-                                   mats.ctypes.data, ranges.ctypes.data, nh.ctypes.data, _vp(ws), size, _vp(depths), _vp(probs), _vp(best_k),
-                                   _vp(counts), _stream(f)), 'mvsdf_stereo_sweep')
+    head = (_vp(f), V, R, S, C, len(views), vw.ctypes.data, off.ctypes.data, src.ctypes.data if npairs else None, mats.ctypes.data, ranges.ctypes.data,
+            nh.ctypes.data)
+    tail = (_vp(ws), size, _vp(depths), _vp(probs), _vp(best_k), _vp(counts), _stream(f))
+    if sgm:
+        check(lib().mvsdf_stereo_sweep_sgm(*head, sgm[0], sgm[1], sgm[2], *tail), 'mvsdf_stereo_sweep_sgm')
+    else:
+        check(lib().mvsdf_stereo_sweep(*head, *tail), 'mvsdf_stereo_sweep')
     _, err = _header(ws, 2)                                                 # the one wait of the call; the host arrays live until here
     _errors(err, what)
-    vol = None
+    vol = reg = None
     if scores:
         at = lib().mvsdf_stereo_volume_offset(R, S, dmax, npairs)
         D = int(nh[-1])
         vol = ws[at:at + D * R * S * 8].view(torch.float64).view(D, R, S).clone()
-    return Sweep(depths, probs, best_k, counts, vol)
+        if sgm:
+            at = lib().mvsdf_stereo_workspace_bytes(R, S, dmax, npairs)
+            reg = ws[at:at + D * R * S * 8].view(torch.float64).view(D, R, S).clone()
+    return Sweep(depths, probs, best_k, counts, vol, reg)
 
 
 def _write_cam(path, cam):
@@ -201,18 +285,19 @@ def _find(folder, stem, exts):
 
 
 def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', num_src=2, max_d=256, interval_scale=1, resize=None, crop=None,
-                   radius=2):
+                   radius=2, regularize=None):
     """BYOD.md's "Run VisMVSNet" step by plane sweep.  Reads <data_root>/images/<id:08>.jpg|png, cams/<id:08>_cam.txt and pair.txt; resizes
     (prepare.resize_bilinear_u8) and centre-crops the images (resize / crop: 'W,H' or (W, H), default: as they are) and moves the cameras along;
     computes descriptors at half that size, as Vis-MVSNet's depth maps are: with feat_ckpt FeatExt.from_checkpoint + extract_features, else
     (descriptor='patch') patch_descriptors(radius) of the image resized to half; sweeps every view and writes into result_dir <id:08>_flow3.pfm,
-    <id:08>_flow{1,2,3}_prob.pfm, cam_<id:08>_flow3.txt (at depth-map scale), <id:08>.jpg (the cropped image) and pair.txt -> the Sweep."""
+    <id:08>_flow{1,2,3}_prob.pfm, cam_<id:08>_flow3.txt (at depth-map scale), <id:08>.jpg (the cropped image) and pair.txt -> the Sweep.  regularize: plane_sweep's."""
     from PIL import Image
     from .datasets import prepare
     from .utils import io as sio
     what = 'estimate_scene'
     if feat_ckpt is None and descriptor != 'patch':
         raise ValueError("%s: descriptor must be 'patch' where no feat_ckpt is given, got %r" % (what, descriptor))
+    _sgm_args(regularize, what)
     pair_path = os.path.join(data_root, 'pair.txt')
     pair = sio.load_pair(pair_path)
     ids = pair['id_list']
@@ -246,7 +331,7 @@ def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', nu
         R, S = (H + 1) // 2, (W + 1) // 2
         feats = patch_descriptors(np.stack([prepare.resize_bilinear_u8(im, S, R) for im in images]), radius)
     cams = np.stack([sio.scale_camera(c, (S / W, R / H)) for c in cams])
-    sweep = plane_sweep(normalize_descriptors(feats), cams, prepare.pair_indices(pair), num_src=num_src)
+    sweep = plane_sweep(normalize_descriptors(feats), cams, prepare.pair_indices(pair), num_src=num_src, regularize=regularize)
     os.makedirs(result_dir, exist_ok=True)
     depths, probs = sweep.depths.cpu().numpy(), sweep.probs.cpu().numpy()
     for i, vid in enumerate(ids):

@@ -3,12 +3,14 @@ the reference's BYOD.md; the flags are those of its test.py call.
 
     python tools/mvs_depth.py --data_root DATA/SCAN --dataset_name general --num_src 2 --max_d 256 --interval_scale 1 --resize 768,576
                               --crop 768,576 --write_result --result_dir OUT [--load_path vismvsnet.ckpt] [--descriptor patch] [--radius 2]
+                              [--sgm [P1,P2]] [--sgm_paths 8]
 
 Reads DATA/SCAN/images/<id:08>.jpg|png, cams/<id:08>_cam.txt and pair.txt; writes OUT/<id:08>_flow3.pfm, <id:08>_flow{1,2,3}_prob.pfm,
 cam_<id:08>_flow3.txt, <id:08>.jpg and pair.txt, which tools/fusion.py and tools/vismvsnet2mvsdf.py read.  With --load_path the descriptors are
 FeatExt's feature maps from that Vis-MVSNet checkpoint, else mean-free grey patches.  The three maps are confidences of a plane sweep, not
 Vis-MVSNet's probabilities: pass --pthresh .7,.02,.9 to the two tools that follow, not BYOD.md's .8,.7,.8.  --model_name is accepted and ignored (there is
-one sweep); --dataset_name other than general and a run without --write_result are refused.
+one sweep); --dataset_name other than general and a run without --write_result are refused.  --sgm regularises the score volume of every view by
+semi-global aggregation before the depth is picked (penalties P1,P2, default .1,.8; --sgm_paths 4 or 8 directions), which helps on noisy photographs.
 """
 import argparse
 import os
@@ -33,7 +35,19 @@ def parse_args(argv=None):
     ap.add_argument('--resize', type=str, default=None)
     ap.add_argument('--crop', type=str, default=None)
     ap.add_argument('--write_result', action='store_true', default=False)
+    ap.add_argument('--sgm', type=str, nargs='?', const='', default=None, metavar='P1,P2',
+                    help='semi-global regularisation of the score volume; penalties for a one-step change and a jump (default .1,.8)')
+    ap.add_argument('--sgm_paths', type=int, default=8, choices=[4, 8])
     a = ap.parse_args(argv)
+    a.regularize = None
+    if a.sgm is not None:
+        try:
+            pen = [float(v) for v in a.sgm.split(',')] if a.sgm else [0.1, 0.8]
+        except ValueError:
+            pen = []
+        if len(pen) != 2 or not 0 <= pen[0] <= pen[1] < float('inf'):
+            ap.error('--sgm %s: two penalties P1,P2 with 0 <= P1 <= P2' % a.sgm)
+        a.regularize = (pen[0], pen[1], a.sgm_paths)
     if a.dataset_name != 'general':
         ap.error('--dataset_name %s: only general (images/, cams/, pair.txt) is built' % a.dataset_name)
     if not a.write_result:
@@ -45,7 +59,7 @@ def main(argv=None):
     a = parse_args(argv)
     from mvsdf_amd import stereo
     sweep = stereo.estimate_scene(a.data_root, a.result_dir, feat_ckpt=a.load_path, descriptor=a.descriptor, num_src=a.num_src, max_d=a.max_d,
-                                  interval_scale=a.interval_scale, resize=a.resize, crop=a.crop, radius=a.radius)
+                                  interval_scale=a.interval_scale, resize=a.resize, crop=a.crop, radius=a.radius, regularize=a.regularize)
     t = stereo.PTHRESH
     p = sweep.probs
     kept = (p[:, 0] > t[0]) & (p[:, 1] > t[1]) & (p[:, 2] > t[2]) & (sweep.depths > 0)

@@ -8,7 +8,12 @@ same definition written as plain torch calls in fp64 on the same GPU, one view a
 line: both medians, the ratio, and the gather bandwidth the HIP path achieves = 4 taps x C x 4 bytes per valid (pixel, hypothesis, source) over its
 time (the bytes the lanes request; most are served by L1 / L2).
 
-    python tools/time_stereo.py [--views 10 --hw 288,384 --channels 32 --depths 256 --num_src 2 --repeats 3 --torch_repeats 1 --chunk 8]
+--sgm times the semi-global regularisation instead (same protocol, one JSON line): the sweep with regularize=True against the sweep without it, and
+regularize_scores on the last view's score volume against the same definition as plain fp64 torch calls (regularize_torch below: one image row or
+column per step, elementwise minima and sums in the definition's order, so it is compared bit for bit); the bytes the passes move = per direction
+the scores read, the running sum read (not by the first) and written.
+
+    python tools/time_stereo.py [--views 10 --hw 288,384 --channels 32 --depths 256 --num_src 2 --repeats 3 --torch_repeats 1 --chunk 8] [--sgm]
 """
 import argparse
 import json
@@ -91,6 +96,65 @@ def sweep_torch(desc, cams, pairs, num_src, chunk):
     return out, nvalid
 
 
+SGM_DIRECTIONS = [(0, 1), (0, -1), (1, 0), (-1, 0), (1, 1), (-1, -1), (1, -1), (-1, 1)]
+
+
+def regularize_torch(score, p1, p2, paths):
+    """the regularisation of mvsdf_amd/stereo.py in torch fp64; score [D,R,S] on the device (NaN = invalid) -> A"""
+    inf = float('inf')
+    cost_all = 1.0 - score
+    T = None
+    for dy, dx in SGM_DIRECTIONS[:paths]:
+        cost = cost_all if dy else cost_all.transpose(1, 2)                  # horizontal: the same walk over the columns
+        sy, sx = (dy, dx) if dy else (dx, 0)
+        D, R, S = cost.shape
+        L = torch.empty_like(cost)
+        edge = torch.full((D, 1), inf, dtype=cost.dtype, device=cost.device)
+        top = torch.full((1, S), inf, dtype=cost.dtype, device=cost.device)
+        prev = None
+        for y in (range(R) if sy > 0 else range(R - 1, -1, -1)):
+            c = cost[:, y]
+            if prev is None:
+                row = c
+            else:
+                own = torch.where(torch.isnan(prev), torch.full_like(prev, inf), prev)
+                if sx > 0:
+                    own = torch.cat([edge, own[:, :S - 1]], 1)
+                elif sx < 0:
+                    own = torch.cat([own[:, 1:], edge], 1)
+                m = own.min(0).values
+                below = torch.cat([top, own[:D - 1] + p1], 0)
+                above = torch.cat([own[1:] + p1, top], 0)
+                best = torch.minimum(torch.minimum(own, below), torch.minimum(above, (m + p2)[None]))
+                row = torch.where(torch.isfinite(m)[None], c + (best - m[None]), c)
+            L[:, y] = row
+            prev = row
+        L = L if dy else L.transpose(1, 2)
+        T = L if T is None else T + L
+    return torch.where(torch.isnan(score), score, 1.0 - T / float(paths))
+
+
+def time_sgm(a, stereo, desc, cams, pairs, hw):
+    p1, p2, paths = stereo.SGM_DEFAULTS
+    _, plain = _timed(lambda: stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src), a.repeats)
+    _, runs = _timed(lambda: stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src, regularize=True), a.repeats)
+    vol = stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src, views=[a.views - 1], scores=True).scores
+    out, vruns = _timed(lambda: stereo.regularize_scores(vol, p1, p2, paths), a.repeats)
+    ref, truns = _timed(lambda: regularize_torch(vol, p1, p2, paths), a.torch_repeats)
+    same = torch.isnan(out) == torch.isnan(ref)
+    differ = int((~same).sum()) + int((out[same & ~torch.isnan(ref)] != ref[same & ~torch.isnan(ref)]).sum())
+    hip, base, one, tor = (float(np.median(v)) for v in (runs, plain, vruns, truns))
+    moved = (3 * paths - 1) * vol.numel() * 8
+    print(json.dumps({'sgm': [p1, p2, paths], 'views': a.views, 'hw': list(hw), 'channels': a.channels, 'depths': a.depths, 'num_src': a.num_src,
+                      'sweep_sgm_median_ms': round(hip, 2), 'sweep_sgm_runs_ms': [round(v, 2) for v in runs], 'sweep_plain_median_ms': round(base, 2),
+                      'sweep_plain_runs_ms': [round(v, 2) for v in plain], 'sgm_over_plain': round(hip / base, 2),
+                      'regularize_hip_median_ms': round(one, 3), 'regularize_hip_runs_ms': [round(v, 3) for v in vruns],
+                      'regularize_torch_median_ms': round(tor, 1), 'regularize_torch_runs_ms': [round(v, 1) for v in truns],
+                      'torch_over_hip': round(tor / one, 1), 'elements_that_differ_from_torch': differ, 'elements': int(vol.numel()),
+                      'invalid_share': round(float(torch.isnan(vol).double().mean()), 4), 'bytes_moved_per_volume': moved,
+                      'GBps': round(moved / (one * 1e-3) / 1e9, 1)}))
+
+
 def _timed(fn, repeats):
     runs = []
     for rep in range(repeats + 1):                                # the first run warms up
@@ -113,12 +177,15 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--torch_repeats', type=int, default=1)
     ap.add_argument('--chunk', type=int, default=8)
+    ap.add_argument('--sgm', action='store_true', default=False, help='time the semi-global regularisation instead')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_stereo.py measures on the GPU'
     from mvsdf_amd import stereo
     hw = tuple(int(v) for v in a.hw.split(','))
     cams, pairs, feats = scene(a.views, hw, a.channels, a.depths)
     desc = stereo.normalize_descriptors(feats.cuda())
+    if a.sgm:
+        return time_sgm(a, stereo, desc, cams, pairs, hw)
     sw, runs = _timed(lambda: stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src), a.repeats)
     (ref, nvalid), truns = _timed(lambda: sweep_torch(desc, cams, pairs, a.num_src, a.chunk), a.torch_repeats)
     diff = (sw.depths - ref).abs()
