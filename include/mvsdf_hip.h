@@ -675,6 +675,19 @@ int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, i
                            const int32_t* pair_off, const int32_t* pair_src, const double* mats, const double* ranges, const int32_t* nhyp, double p1,
                            double p2, int32_t paths, void* ws, size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts,
                            void* stream);
+/* The cascade (mvsdf_amd/stereo.py, "Cascade").  mvsdf_stereo_upsample: depth fp32 [V][r][s] and best_k int32 [V][r][s] of a coarser sweep (device)
+ * -> out fp64 [V][R][S], the centres at the finer size (a quiet NaN where no parent of a pixel has a winner); r and s >= 2, R and S >= 1; no host wait.
+ * mvsdf_stereo_band is mvsdf_stereo_sweep over a band of depth_num hypotheses (1 .. 64, MAX_D_BAND) per pixel, centres[view][R][S] fp64 on the device
+ * (NaN: no centre) + (k - depth_num / 2) * steps[i]: all of views[0 .. nviews) in one launch (1 <= nviews <= 65535, no view twice), no score volume
+ * in global memory, best_k = the index within the band.  steps: HOST fp64 [nviews], finite and positive; the other host arrays as
+ * mvsdf_stereo_sweep's.  Further error bits: 32 depth_num, a step or a repeated view refused (nothing is launched), 64 an infinite centre (found on
+ * the device; the outputs are then not valid).  The workspace (mvsdf_stereo_band_workspace_bytes, 0 beyond the limits) holds the header, the per-view
+ * arrays, the matrices and the source indices: it depends on nviews and npairs = pair_off[nviews] only, not on depth_num, R or S. */
+int mvsdf_stereo_upsample(const float* depth, const int32_t* best_k, int64_t V, int64_t r, int64_t s, int64_t R, int64_t S, double* out, void* stream);
+size_t mvsdf_stereo_band_workspace_bytes(int64_t R, int64_t S, int64_t depth_num, int64_t nviews, int64_t npairs);
+int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
+                      const int32_t* pair_src, const double* mats, const double* steps, const double* centres, int32_t depth_num, void* ws,
+                      size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts, void* stream);
 
 /* ---- Point-cloud cleaning (cloud.hip; Python: mvsdf_amd/cloud.py, which states the definition) ----
  * pts fp64 [n][3] on the device, fp64 throughout.  mvsdf_cloud_knn, _components and _clean share one workspace (mvsdf_cloud_clean_workspace_bytes,

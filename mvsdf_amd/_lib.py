@@ -128,6 +128,10 @@ def lib():
         L.mvsdf_stereo_sweep_sgm_workspace_bytes.restype = sz
         L.mvsdf_stereo_sweep_sgm_workspace_bytes.argtypes = [i64] * 4
         L.mvsdf_stereo_sweep_sgm.argtypes = [vp, i64, i64, i64, i64, i64] + [vp] * 6 + [f64, f64, i32, vp, sz] + [vp] * 5
+        L.mvsdf_stereo_upsample.argtypes = [vp, vp] + [i64] * 5 + [vp, vp]
+        L.mvsdf_stereo_band_workspace_bytes.restype = sz
+        L.mvsdf_stereo_band_workspace_bytes.argtypes = [i64] * 5
+        L.mvsdf_stereo_band.argtypes = [vp, i64, i64, i64, i64, i64] + [vp] * 6 + [i32, vp, sz] + [vp] * 5
         L.mvsdf_viewsel_bits_bytes.restype = sz
         L.mvsdf_viewsel_bits_bytes.argtypes = [i64, i64]
         L.mvsdf_viewsel_workspace_bytes.restype = sz
@@ -174,6 +178,7 @@ EXPORTS = [
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_stereo_workspace_bytes', 'mvsdf_stereo_volume_offset', 'mvsdf_stereo_normalize', 'mvsdf_stereo_patches', 'mvsdf_stereo_sweep',
     'mvsdf_stereo_sgm_workspace_bytes', 'mvsdf_stereo_regularize', 'mvsdf_stereo_sweep_sgm_workspace_bytes', 'mvsdf_stereo_sweep_sgm',
+    'mvsdf_stereo_upsample', 'mvsdf_stereo_band_workspace_bytes', 'mvsdf_stereo_band',
     'mvsdf_viewsel_bits_bytes', 'mvsdf_viewsel_workspace_bytes', 'mvsdf_viewsel_pack_dense', 'mvsdf_viewsel_pack_tracks', 'mvsdf_viewsel_scores',
     'mvsdf_viewsel_depths', 'mvsdf_viewsel_weights_host',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',

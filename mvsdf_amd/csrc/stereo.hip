@@ -39,6 +39,8 @@ enum {
     PS_ERR_DEPTHS = 4,      // D < 1 (or beyond PS_MAX_D)
     PS_ERR_SHAPE = 8,       // V < 1, R or S < 2, C < 1, a pair list longer than PS_MAX_SRC, sizes beyond the limits
     PS_ERR_SGM = 16,        // the regularisation's p1, p2, paths, or D > SG_MAX_D
+    PS_ERR_BAND = 32,       // the band's number of hypotheses outside [1, PB_MAX_D], a step that is not finite and positive, a view listed twice
+    PS_ERR_CENTRE = 64,     // an infinite centre (found on the device)
 };
 
 #define SG_MAX_D 4096                                 // stereo.py: MAX_D_SGM
@@ -142,6 +144,34 @@ __device__ __forceinline__ void ps_dots(const double* ref, const float* __restri
     }
 }
 
+// one hypothesis of one reference pixel (X, Y = its centre, d = the depth, ref / fr = its descriptor): the sum of c_s over the valid sources in pair
+// order, n = their number.  k_ps_score and k_ps_band share it, so both give the same bits.
+template <int CFIX>
+__device__ __forceinline__ double ps_sample(const float* __restrict__ desc, long long hw, long long row, int R, int S, int C, const double* ref,
+                                            const float* __restrict__ fr, double X, double Y, double d, int nsrc, const int* __restrict__ src,
+                                            const double* __restrict__ mats, int& n) {
+    const double smax = (double)(S - 1), rmax = (double)(R - 1);
+    const double q0 = X * d, q1 = Y * d;
+    double acc = 0.0;
+    for (int j = 0; j < nsrc; ++j) {
+        const double* __restrict__ T = mats + (long long)j * 16;
+        const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
+        if (!(p2 > 0.0)) continue;
+        const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
+        const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
+        if (!(u >= 0.0 && u <= smax && v >= 0.0 && v <= rmax)) continue;
+        const double x0 = fmin(floor(u), (double)(S - 2)), y0 = fmin(floor(v), (double)(R - 2));
+        const double fx = u - x0, fy = v - y0;
+        const float* __restrict__ g = desc + ((long long)src[j] * hw + (long long)(int)y0 * S + (int)x0) * C;
+        double t00, t01, t10, t11;
+        ps_dots<CFIX>(ref, fr, g, row, C, t00, t01, t10, t11);
+        const double cs = (t00 * (1.0 - fx) + t01 * fx) * (1.0 - fy) + (t10 * (1.0 - fx) + t11 * fx) * fy;
+        acc = acc + cs;
+        ++n;
+    }
+    return acc;
+}
+
 // scores of view r.  Grid: (tiles in x, tiles in y, chunks of PS_KCHUNK hypotheses); src / mats: the nsrc pair slots of this view (T_rs, row-major 4x4)
 template <int CFIX>
 __global__ __launch_bounds__(PS_THREADS) void k_ps_score(const float* __restrict__ desc, int R, int S, int C, int r, int nsrc, const int* __restrict__ src,
@@ -160,83 +190,158 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_score(const float* __restrict
         for (int c = 0; c < CFIX; ++c) ref[c] = (double)fr[c];
     }
     const double X = (double)x + 0.5, Y = (double)y + 0.5;
-    const double smax = (double)(S - 1), rmax = (double)(R - 1);
     for (int k = k0; k < k1; ++k) {
-        const double d = dmin + (double)k * interval;
-        const double q0 = X * d, q1 = Y * d;
         int n = 0;
-        double acc = 0.0;
-        for (int j = 0; j < nsrc; ++j) {
-            const double* __restrict__ T = mats + (long long)j * 16;
-            const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
-            if (!(p2 > 0.0)) continue;
-            const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
-            const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
-            if (!(u >= 0.0 && u <= smax && v >= 0.0 && v <= rmax)) continue;
-            const double x0 = fmin(floor(u), (double)(S - 2)), y0 = fmin(floor(v), (double)(R - 2));
-            const double fx = u - x0, fy = v - y0;
-            const float* __restrict__ g = desc + ((long long)src[j] * hw + (long long)(int)y0 * S + (int)x0) * C;
-            double t00, t01, t10, t11;
-            ps_dots<CFIX>(ref, fr, g, row, C, t00, t01, t10, t11);
-            const double cs = (t00 * (1.0 - fx) + t01 * fx) * (1.0 - fy) + (t10 * (1.0 - fx) + t11 * fx) * fy;
-            acc = acc + cs;
-            ++n;
-        }
+        const double acc = ps_sample<CFIX>(desc, hw, row, R, S, C, ref, fr, X, Y, dmin + (double)k * interval, nsrc, src, mats, n);
         const long long at = (long long)k * hw + pix;
         vol[at] = n ? acc / (double)n : ps_nan();
         cnt[at] = (unsigned char)n;
     }
 }
 
-// winner, refinement and confidences of every pixel of one view; used = the number of sources the view sweeps.  REG: vol is the regularised volume
-// and prob1 the raw score (raw) at its winner
+// the definition's winner, refinement and confidences of one pixel from its scores vol[k * stride] (NaN = invalid), k < D; used = the number of sources
+// the view sweeps.  REG: vol holds regularised scores and prob1 is the raw score (raw) at their winner.  k_ps_pick walks the volume in global memory,
+// k_ps_band its tile's band in LDS.
+struct PsPick {
+    int ks, nk;             // k* (-1: no valid hypothesis) and n_k*
+    double off;             // the refinement
+    float p1, p2, p3;
+};
+
+template <bool REG>
+__device__ __forceinline__ PsPick ps_pick(const double* vol, const double* raw, const unsigned char* cnt, long long stride, int D, int used) {
+    PsPick o = {-1, 0, 0.0, 0.0f, 0.0f, 0.0f};
+    double b = -INFINITY;
+    for (int k = 0; k < D; ++k) {
+        const double s = vol[(long long)k * stride];
+        if (s > b) { b = s; o.ks = k; }                                         // NaN (invalid) never compares greater
+    }
+    const int ks = o.ks;
+    if (ks < 0) return o;
+    bool any = false;
+    double b2 = -INFINITY;
+    for (int k = 0; k < D; ++k) {
+        if (k >= ks - 1 && k <= ks + 1) continue;
+        const double s = vol[(long long)k * stride];
+        if (s == s) {
+            any = true;
+            if (s > b2) b2 = s;
+        }
+    }
+    if (ks > 0 && ks < D - 1) {
+        const double a = vol[(long long)(ks - 1) * stride], c = vol[(long long)(ks + 1) * stride];
+        if (a == a && c == c) {
+            const double den = (a - 2.0 * b) + c;
+            if (den < 0.0) o.off = 0.5 * (a - c) / den;
+        }
+    }
+    o.p1 = (float)fmin(fmax(REG ? raw[(long long)ks * stride] : b, 0.0), 1.0);
+    if (b <= 0.0) o.p2 = 0.0f;
+    else if (!any) o.p2 = 1.0f;
+    else o.p2 = (float)fmin(fmax(1.0 - fmax(b2, 0.0) / b, 0.0), 1.0);
+    o.nk = cnt[(long long)ks * stride];
+    o.p3 = (float)((double)o.nk / (double)used);
+    return o;
+}
+
+// winner, refinement and confidences of every pixel of one view, one lane per pixel (coalesced over the lanes)
 template <bool REG>
 __global__ __launch_bounds__(PS_THREADS) void k_ps_pick(const double* __restrict__ vol, const double* __restrict__ raw, const unsigned char* __restrict__ cnt,
                                                          int hw, int D, double dmin, double interval, int used, float* __restrict__ depth,
                                                          float* __restrict__ prob, int* __restrict__ best_k, int* __restrict__ counts) {
     const int p = blockIdx.x * PS_THREADS + threadIdx.x;
     if (p >= hw) return;
-    int ks = -1;
-    double b = -INFINITY;
-    for (int k = 0; k < D; ++k) {
-        const double s = vol[(long long)k * hw + p];
-        if (s > b) { b = s; ks = k; }                                           // NaN (invalid) never compares greater
-    }
-    float dep = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
-    int nk = 0;
-    if (ks >= 0) {
-        bool any = false;
-        double b2 = -INFINITY;
-        for (int k = 0; k < D; ++k) {
-            if (k >= ks - 1 && k <= ks + 1) continue;
-            const double s = vol[(long long)k * hw + p];
-            if (s == s) {
-                any = true;
-                if (s > b2) b2 = s;
-            }
+    const PsPick o = ps_pick<REG>(vol + p, raw + p, cnt + p, hw, D, used);
+    depth[p] = o.ks >= 0 ? (float)(dmin + ((double)o.ks + o.off) * interval) : 0.0f;
+    prob[p] = o.p1;
+    prob[hw + p] = o.p2;
+    prob[2 * (long long)hw + p] = o.p3;
+    best_k[p] = o.ks;
+    counts[p] = o.nk;
+}
+
+// ================================================================ the cascade: centres and the band sweep ================================================================
+// stereo.py: "Cascade".  k_ps_upsample: one lane per pixel of the finer size, the centre from the four parents that have a winner.
+__global__ __launch_bounds__(PS_THREADS) void k_ps_upsample(const float* __restrict__ depth, const int* __restrict__ best_k, long long V, int r, int s, int R,
+                                                             int S, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+    const long long HW = (long long)R * S;
+    if (i >= V * HW) return;
+    const long long v = i / HW;
+    const int p = (int)(i - v * HW), y = p / S, x = p - y * S;
+    const double u = fmin(fmax((((double)x + 0.5) * (double)s) / (double)S - 0.5, 0.0), (double)(s - 1));
+    const double w = fmin(fmax((((double)y + 0.5) * (double)r) / (double)R - 0.5, 0.0), (double)(r - 1));
+    const double x0 = fmin(floor(u), (double)(s - 2)), y0 = fmin(floor(w), (double)(r - 2));
+    const double fx = u - x0, fy = w - y0;
+    const long long at = v * ((long long)r * s) + (long long)(int)y0 * s + (int)x0;
+    const double wt[4] = {(1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy};
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const long long t = at + (q >> 1) * s + (q & 1);
+        if (best_k[t] >= 0) {
+            num = num + wt[q] * (double)depth[t];
+            den = den + wt[q];
         }
-        double off = 0.0;
-        if (ks > 0 && ks < D - 1) {
-            const double a = vol[(long long)(ks - 1) * hw + p], c = vol[(long long)(ks + 1) * hw + p];
-            if (a == a && c == c) {
-                const double den = (a - 2.0 * b) + c;
-                if (den < 0.0) off = 0.5 * (a - c) / den;
-            }
-        }
-        dep = (float)(dmin + ((double)ks + off) * interval);
-        p1 = (float)fmin(fmax(REG ? raw[(long long)ks * hw + p] : b, 0.0), 1.0);
-        if (b <= 0.0) p2 = 0.0f;
-        else if (!any) p2 = 1.0f;
-        else p2 = (float)fmin(fmax(1.0 - fmax(b2, 0.0) / b, 0.0), 1.0);
-        nk = cnt[(long long)ks * hw + p];
-        p3 = (float)((double)nk / (double)used);
     }
-    depth[p] = dep;
-    prob[p] = p1;
-    prob[hw + p] = p2;
-    prob[2 * (long long)hw + p] = p3;
-    best_k[p] = ks;
-    counts[p] = nk;
+    out[i] = den > 0.0 ? num / den : ps_nan();
+}
+
+// k_ps_band: a 256-lane workgroup owns an 8 x 8 tile of reference pixels of one view (blockIdx.z: the slot in the view list) and the whole band of Db
+// hypotheses around every pixel's centre.  Lane l of every wave owns pixel l of the tile; wave w scores the hypotheses w, w + 4, ... with ps_sample
+// (the four waves walk neighbouring depths at the same time, so their gathers meet in L1) into the tile's LDS image: score[k][pixel] fp64 and
+// n_k[k][pixel] as bytes, 9 * 64 * Db bytes, 36 KB at PB_MAX_D, conflict-free (consecutive lanes, consecutive words).  After the one barrier wave 0
+// picks from LDS (ps_pick) and writes the pixel's outputs: no score leaves the CU, every output element has one writer, no atomics but the error bit.
+#define PB_TILE 8
+#define PB_MAX_D 64                                   // stereo.py: MAX_D_BAND
+
+template <int CFIX>
+__global__ __launch_bounds__(PS_THREADS) void k_ps_band(const float* __restrict__ desc, int R, int S, int C, const int* __restrict__ views,
+                                                         const int* __restrict__ pair_off, const double* __restrict__ steps,
+                                                         const int* __restrict__ src, const double* __restrict__ mats, const double* __restrict__ centres,
+                                                         int Db, float* __restrict__ depths, float* __restrict__ probs, int* __restrict__ best_k,
+                                                         int* __restrict__ counts, unsigned long long* __restrict__ errword) {
+    extern __shared__ double pb_score[];                                  // [Db][64], then the counts [Db][64] as bytes
+    unsigned char* pb_cnt = (unsigned char*)(pb_score + Db * 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int r = views[blockIdx.z], off = pair_off[blockIdx.z], nsrc = pair_off[blockIdx.z + 1] - off;
+    const double step = steps[blockIdx.z];
+    const int x = blockIdx.x * PB_TILE + (l & 7), y = blockIdx.y * PB_TILE + (l >> 3);
+    const bool inside = x < S && y < R;
+    const long long hw = (long long)R * S, row = (long long)S * C;
+    const long long pix = inside ? (long long)y * S + x : 0;
+    const double c = centres[(long long)r * hw + pix];
+    const bool has = inside && isfinite(c);                               // NaN: no centre (an infinite one is refused below)
+    const int half = Db >> 1;
+    if (w < Db) {
+        const float* __restrict__ fr = desc + ((long long)r * hw + pix) * C;
+        double ref[CFIX ? CFIX : 1];
+        if (CFIX) {
+#pragma unroll
+            for (int q = 0; q < CFIX; ++q) ref[q] = (double)fr[q];
+        }
+        const double X = (double)x + 0.5, Y = (double)y + 0.5;
+        for (int k = w; k < Db; k += PS_THREADS / 64) {
+            const double d = c + (double)(k - half) * step;
+            int n = 0;
+            double acc = 0.0;
+            if (has && d > 0.0) acc = ps_sample<CFIX>(desc, hw, row, R, S, C, ref, fr, X, Y, d, nsrc, src + off, mats + (long long)off * 16, n);
+            pb_score[k * 64 + l] = n ? acc / (double)n : ps_nan();
+            pb_cnt[k * 64 + l] = (unsigned char)n;
+        }
+    }
+    __syncthreads();
+    if (w) return;
+    if (__ballot(inside && isinf(c)) && l == 0) atomicOr(errword, (unsigned long long)PS_ERR_CENTRE);
+    if (!inside) return;
+    const PsPick o = ps_pick<false>(pb_score + l, pb_score + l, pb_cnt + l, 64, Db, nsrc);
+    const long long at = (long long)r * hw + pix;
+    depths[at] = o.ks >= 0 ? (float)(c + ((double)(o.ks - half) + o.off) * step) : 0.0f;
+    probs[3 * at - 2 * pix] = o.p1;                                       // [r][0][pix]
+    probs[3 * at - 2 * pix + hw] = o.p2;
+    probs[3 * at - 2 * pix + 2 * hw] = o.p3;
+    best_k[at] = o.ks;
+    counts[at] = o.nk;
 }
 
 // ================================================================ semi-global regularisation ================================================================
@@ -490,6 +595,27 @@ static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths,
 }
 
 
+// ---- host side of the band sweep ----
+struct PbLayout {
+    size_t views, off, steps, mats, src, total;
+};
+
+// header, per view its index, first pair slot and step, matrices and source indices: nothing that grows with the band, R or S
+static bool pb_layout(long long R, long long S, long long Db, long long nviews, long long npairs, PbLayout* L) {
+    if (R < 2 || S < 2 || R > INT_MAX || S > INT_MAX || R * S > INT_MAX || Db < 1 || Db > PB_MAX_D || nviews < 0 || nviews > 65535 || npairs < 0 ||
+        npairs > INT_MAX)
+        return false;
+    WsCursor c{PS_HDR};
+    L->views = c.take((size_t)(nviews > 0 ? nviews : 1) * 4);
+    L->off = c.take((size_t)(nviews + 1) * 4);
+    L->steps = c.take((size_t)(nviews > 0 ? nviews : 1) * 8);
+    L->mats = c.take((size_t)(npairs > 0 ? npairs : 1) * 16 * 8);
+    L->src = c.take((size_t)(npairs > 0 ? npairs : 1) * 4);
+    L->total = c.o;
+    return true;
+}
+
+
 extern "C" {
 
 size_t mvsdf_stereo_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs) {
@@ -558,6 +684,86 @@ int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, i
                            void* stream) {
     return ps_sweep("mvsdf_stereo_sweep_sgm", true, p1, p2, paths, desc, V, R, S, C, nviews, views, pair_off, pair_src, mats, ranges, nhyp, ws, ws_bytes,
                     depths, probs, best_k, counts, stream);
+}
+
+int mvsdf_stereo_upsample(const float* depth, const int32_t* best_k, int64_t V, int64_t r, int64_t s, int64_t R, int64_t S, double* out, void* stream) {
+    if (!depth || !best_k || !out || V < 1 || r < 2 || s < 2 || R < 1 || S < 1 || r > INT_MAX || s > INT_MAX || r * s > INT_MAX || R > INT_MAX ||
+        S > INT_MAX || R * S > INT_MAX || V > PS_MAX_ELEMS / (R * S) || V > PS_MAX_ELEMS / (r * s) || mv_ceil_div(V * R * S, PS_THREADS) > INT_MAX)
+        return mv_fail(-1, "mvsdf_stereo_upsample: bad arguments");
+    hipLaunchKernelGGL(k_ps_upsample, dim3(mv_grid(V * R * S, PS_THREADS)), dim3(PS_THREADS), 0, (hipStream_t)stream, depth, best_k, (long long)V, (int)r,
+                       (int)s, (int)R, (int)S, out);
+    return mv_check(hipGetLastError(), "mvsdf_stereo_upsample");
+}
+
+size_t mvsdf_stereo_band_workspace_bytes(int64_t R, int64_t S, int64_t depth_num, int64_t nviews, int64_t npairs) {
+    PbLayout L;
+    return pb_layout(R, S, depth_num, nviews, npairs, &L) ? L.total : 0;
+}
+
+int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views, const int32_t* pair_off,
+                      const int32_t* pair_src, const double* mats, const double* steps, const double* centres, int32_t depth_num, void* ws,
+                      size_t ws_bytes, float* depths, float* probs, int32_t* best_k, int32_t* counts, void* stream) {
+    const char* what = "mvsdf_stereo_band";
+    if (!desc || !views || !pair_off || !mats || !steps || !centres || !ws || !depths || !probs || !best_k || !counts || nviews < 1 || ws_bytes < PS_HDR)
+        return mv_fail(-1, "mvsdf_stereo_band: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    // ---- validation, all of it before the first launch ----
+    long long err = 0, npairs = 0;
+    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > 65535 || pair_off[0] != 0) err |= PS_ERR_SHAPE;
+    else {
+        for (long long i = 0; i < nviews; ++i) {
+            const long long len = (long long)pair_off[i + 1] - pair_off[i];
+            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
+            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
+            for (long long j = 0; j < i; ++j)
+                if (views[j] == views[i]) err |= PS_ERR_BAND;                  // two workgroups would write the same maps
+            if (!(isfinite(steps[i]) && steps[i] > 0.0)) err |= PS_ERR_BAND;
+        }
+        npairs = pair_off[nviews];
+    }
+    if (depth_num < 1 || depth_num > PB_MAX_D) err |= PS_ERR_BAND;
+    PbLayout L;
+    if (!(err & (PS_ERR_SHAPE | PS_ERR_BAND)) &&
+        (!pb_layout(R, S, depth_num, nviews, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
+        err |= PS_ERR_SHAPE;
+    if (!(err & PS_ERR_SHAPE)) {
+        for (long long k = 0; k < npairs; ++k)
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
+        for (long long k = 0; k < npairs * 16; ++k)
+            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
+    }
+    if (err) {
+        const long long hdr[2] = {0, err};
+        return mv_write_header(ws, hdr, 2, s, what);
+    }
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_band: workspace too small (mvsdf_stereo_band_workspace_bytes)");
+    const dim3 grid((unsigned)mv_ceil_div(S, PB_TILE), (unsigned)mv_ceil_div(R, PB_TILE), (unsigned)nviews);
+    if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_band: R beyond the grid limit");
+    // ---- uploads and the one launch ----
+    char* w = (char*)ws;
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what))) return rc;
+    if ((rc = mv_check(hipMemcpyAsync(w + L.views, views, (size_t)nviews * 4, hipMemcpyHostToDevice, s), what))) return rc;
+    if ((rc = mv_check(hipMemcpyAsync(w + L.off, pair_off, (size_t)(nviews + 1) * 4, hipMemcpyHostToDevice, s), what))) return rc;
+    if ((rc = mv_check(hipMemcpyAsync(w + L.steps, steps, (size_t)nviews * 8, hipMemcpyHostToDevice, s), what))) return rc;
+    if (npairs > 0) {
+        if ((rc = mv_check(hipMemcpyAsync(w + L.mats, mats, (size_t)npairs * 16 * 8, hipMemcpyHostToDevice, s), what))) return rc;
+        if ((rc = mv_check(hipMemcpyAsync(w + L.src, pair_src, (size_t)npairs * 4, hipMemcpyHostToDevice, s), what))) return rc;
+    }
+    const long long total = V * R * S * C;
+    long long fb = mv_ceil_div(total, MV_THREADS);
+    if (fb > 2048) fb = 2048;
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
+    const size_t lds = (size_t)depth_num * 64 * 9;
+    if (C == 32 && ((uintptr_t)desc & 15) == 0)                               // 128-byte texels read as float4
+        hipLaunchKernelGGL(k_ps_band<32>, grid, dim3(PS_THREADS), lds, s, desc, (int)R, (int)S, (int)C, (const int*)(w + L.views), (const int*)(w + L.off),
+                           (const double*)(w + L.steps), (const int*)(w + L.src),
+                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + 1);
+    else
+        hipLaunchKernelGGL(k_ps_band<0>, grid, dim3(PS_THREADS), lds, s, desc, (int)R, (int)S, (int)C, (const int*)(w + L.views), (const int*)(w + L.off),
+                           (const double*)(w + L.steps), (const int*)(w + L.src),
+                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + 1);
+    return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
 }
 
 }  // extern "C"

@@ -208,6 +208,19 @@ def extract_features(feat_ext, rgb_2xd, batch=20):
     return out.permute(0, 3, 1, 2)
 
 
+def extract_pyramid(feat_ext, rgb_2xd, batch=20):
+    """All three of FeatExt's maps for every view of rgb_2xd [V,3,H,W], batch views per call -> ([V,R/4,S/4,32], [V,R/2,S/2,32], [V,R,S,32]) fp32,
+    channels-last in memory and in shape (what stereo.cascade_sweep takes, coarsest first), on the device.  The last is extract_features' output."""
+    dev = next(feat_ext.parameters()).device
+    V, _, h, w = rgb_2xd.shape
+    R, S = output_hw(h, w)
+    outs = [torch.empty((V, r, s, 32), dtype=torch.float32, device=dev) for r, s in ((R // 4, S // 4), (R // 2, S // 2), (R, S))]
+    for s in range(0, V, batch):
+        x = FeatExt._nhwc_input(rgb_2xd[s:s + batch].to(dev, torch.float32))
+        feat_ext.run(x, *(o[s:s + batch] for o in outs))
+    return tuple(outs)
+
+
 def conv_layer(x, weight, bias=None, stride=1, res=None, relu=False, x2=None, transposed=False):
     """One layer of the kernels alone (tests, timing): Conv2d(k, stride, padding k // 2) over NCHW x (channels-last or not), or with
     transposed=True ConvTranspose2d(3, 2, 1, output_padding 1); x2: more input channels read after x's (a concatenation that is never formed);

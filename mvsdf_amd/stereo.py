@@ -50,8 +50,38 @@ The definition (fp64 throughout, in the order written, no FMA contraction; fp32 
 
 Non-finite features or cameras, R or S below 2, D < 1 and a pair index outside [0, V) raise ValueError.
 
-Not built: Vis-MVSNet's learned regularisation (the semi-global aggregation above stands in for it), cascaded (coarse-to-fine) sweeps,
-visibility-weighted aggregation.
+Cascade (cascade_sweep, off by default; estimate_scene(cascade=...)): Vis-MVSNet's model_cas sweeps coarse to fine, 64 hypotheses over the whole
+range at 1/8 of the image size, then 32 and 16 around the upsampled previous depth at 1/4 and 1/2.  The same here, fp64 in the order written:
+
+- Stages: L of them, 1 <= L <= MAX_STAGES = 4.  Stage l has a descriptor map desc_l fp32 [V,R_l,S_l,C_l], R_l and S_l >= 2, any C_l >= 1, used as
+  given; the sizes of different stages need not be in integer ratio.
+- Cameras: cams fp64 [V,2,4,4] is at the size of the last stage; the camera of stage l is scale_camera(cams, (S_l/S_L, R_l/R_L)).  Matrices, pixel
+  convention and row product are the sweep's.
+- Hypotheses: interval and D come from cams[r,1,3].  interval_scales = (g_1..g_L), finite and positive, default (4, 2, 1) for L = 3;
+  depth_nums = (D_1..D_L), default (None, 32, 16); None is allowed for D_1 only and means ceil(D/g_1) (64 at max_d 256).  step_l = interval*g_l.
+- Stage 1 is the sweep above of desc_1 with the stage-1 cameras, depth_min, interval step_1 and D_1 hypotheses.  regularize= applies to this stage
+  only: it is the only one whose hypotheses are shared between pixels, which the path penalties presuppose.
+- Centres (upsample_depth), for stage l > 1, at pixel (x, y), from the previous stage's depth and best_k of size r x s:
+  u = ((x + 0.5)*s)/S_l - 0.5 clamped to [0, s-1], v likewise with r and R_l; x0 = min(floor(u), s-2), y0 = min(floor(v), r-2), fx = u - x0,
+  fy = v - y0.  The taps (dy, dx) = (0,0), (0,1), (1,0), (1,1), in this order, have the weights (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy; a tap is
+  valid iff its best_k >= 0.  num = ((0 + w*d) + ...) and den = ((0 + w) + ...) over the valid taps in that order, d the fp32 depth promoted.  The
+  centre is num/den where den > 0, otherwise NaN: no centre.
+- Band sweep (band_sweep): given centres fp64 [V,R,S] (NaN: none), D_b >= 1 and step > 0, the hypotheses of pixel p are
+  d_k = c_p + (k - floor(D_b/2))*step, k = 0..D_b-1.  A hypothesis is invalid for every source if its pixel has no centre or d_k <= 0.  Otherwise
+  score, validity, aggregate, winner, refinement, the three confidences and counts are the sweep's, word for word, over the D_b hypotheses of the
+  band; best_k is the index within the band and depth = fp32(c_p + ((k* - floor(D_b/2)) + off)*step).  No valid k: depth and the confidences are
+  0, best_k = -1, counts = 0.  D_b <= MAX_D_BAND = 64 (a tile's scores and counts stay in LDS; no score volume is written).
+- Result (cascade_sweep): stages[l] is a Sweep at stage l's size.  The final maps, at stage L's size: depths, best_k and counts are stage L's;
+  probs[0] and probs[2] are stage L's prob1 and prob3; probs[1] is stage 1's prob2 at the coarse pixel (((2y+1)*R_1)//(2*R_L),
+  ((2x+1)*S_1)//(2*S_L)) in integer arithmetic, and 0 where stage L has no winner: the full-range peak ratio is the distinctiveness PTHRESH's second
+  threshold was chosen for; inside a 16-step band it means little.  With L = 1 and g_1 = 1 the result is plane_sweep's, bit for bit.
+- ValueError, before the GPU is touched: L outside [1, 4]; tuples of the wrong length; a None elsewhere than in D_1; D_b outside [1, MAX_D_BAND]; a
+  non-finite or non-positive scale or step; V differing between stages; centres of the wrong shape; infinite centres (NaN is allowed; in a device
+  tensor they are found by the kernel); a view listed twice where a band is swept (every view of a band is swept by the one launch, and every
+  output has one writer); the sweep's conditions at every stage.  tests/stereo_cascade_ref.py restates all of it in numpy.
+
+Not built: Vis-MVSNet's learned regularisation (the semi-global aggregation above stands in for it), visibility-weighted aggregation,
+regularisation of the bands of stages 2 and up.
 """
 import os
 
@@ -64,6 +94,9 @@ from .fusion import projection_matrices
 PTHRESH = (0.7, 0.02, 0.9)        # thresholds on prob1, prob2, prob3 that suit these confidences (chosen on tests/stereo_scene.py: DESIGN.md)
 MAX_SRC, MAX_D = 255, 65535
 MAX_D_SGM = 4096                  # the most hypotheses regularize_scores takes
+MAX_D_BAND = 64                   # the most hypotheses of a band (band_sweep): the tile's scores and counts are then 36 KB of LDS
+MAX_STAGES = 4                    # of a cascade
+CASCADE_DEFAULTS = ((None, 32, 16), (4, 2, 1))      # depth_nums, interval_scales: Vis-MVSNet's 64 / 32 / 16 at max_d 256
 SGM_DEFAULTS = (0.1, 0.8, 8)      # P1, P2, paths (chosen on the noisy test scene: DESIGN.md)
 
 
@@ -87,12 +120,16 @@ def _errors(err, what):
         raise ValueError('%s: shapes disagree or are out of range (V >= 1, R and S >= 2, C >= 1, at most %d sources)' % (what, MAX_SRC))
     if err & 16:
         raise ValueError('%s: the regularisation needs finite 0 <= P1 <= P2, paths 4 or 8 and at most %d hypotheses' % (what, MAX_D_SGM))
+    if err & 32:
+        raise ValueError('%s: a band needs 1 to %d hypotheses, finite positive steps and every view at most once' % (what, MAX_D_BAND))
+    if err & 64:
+        raise ValueError('%s: a centre is infinite' % what)
     if err:
         raise MvsdfError('%s failed (error bits %d)' % (what, err))
 
 
-def _feature_tensor(feats, what):
-    """-> (fp32 contiguous device tensor [V,R,S,C], device); host input is checked for finiteness here, before the GPU is touched"""
+def _checked_features(feats, what):
+    """-> feats as a tensor [V,R,S,C] where it is; host input is checked for finiteness here.  Touches no GPU."""
     f = torch.as_tensor(feats)
     if f.dim() != 4:
         raise ValueError('%s: features must be [V, R, S, C], got shape %s' % (what, tuple(f.shape)))
@@ -101,6 +138,12 @@ def _feature_tensor(feats, what):
         raise ValueError('%s: features must be at least 2 x 2 texels of one channel (and V >= 1), got shape %s' % (what, tuple(f.shape)))
     if not f.is_cuda and not bool(torch.isfinite(f).all()):
         raise ValueError('%s: a feature is NaN or infinite' % what)
+    return f
+
+
+def _feature_tensor(feats, what):
+    """-> (fp32 contiguous device tensor [V,R,S,C], device); host input is checked for finiteness here, before the GPU is touched"""
+    f = _checked_features(feats, what)
     dev = f.device if f.is_cuda else torch.device('cuda')
     return f.to(dev, torch.float32).contiguous(), dev
 
@@ -184,12 +227,8 @@ def regularize_scores(volume, p1=SGM_DEFAULTS[0], p2=SGM_DEFAULTS[1], paths=SGM_
     return out
 
 
-def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, regularize=None):
-    """The module's definition -> Sweep.  Device tensors are used where they are (the stream is theirs); numpy / CPU input is copied to the GPU.
-    views: the reference views to sweep, in this order (default: all); scores=True also returns the score volume of the last of them.
-    regularize: None (winner-take-all on the raw scores), True (the regularisation with SGM_DEFAULTS), (p1, p2) or (p1, p2, paths)."""
-    what = 'plane_sweep'
-    sgm = _sgm_args(regularize, what)
+def _sweep_args(what, descriptors, cams, pairs, num_src, views):
+    """the checks plane_sweep and band_sweep share -> (descriptors as a tensor, cams fp64 numpy, the views to sweep, their sources)"""
     cams = np.asarray(cams.cpu() if isinstance(cams, torch.Tensor) else cams, dtype=np.float64)
     f = torch.as_tensor(descriptors)
     if f.dim() == 4 and cams.shape != (f.shape[0], 2, 4, 4):
@@ -210,13 +249,11 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, r
         raise ValueError('%s: a pair index is outside [0, %d)' % (what, V))
     if any(len(q) > MAX_SRC for q in used):
         raise ValueError('%s: at most %d sources per view' % (what, MAX_SRC))
-    nhyp = cams[views, 1, 3, 2] if views else np.zeros(0)
-    if (nhyp != np.floor(nhyp)).any() or (nhyp < 1).any() or (nhyp > MAX_D).any():
-        raise ValueError('%s: the number of depth hypotheses (cams[v, 1, 3, 2]) must be a whole number in [1, %d]' % (what, MAX_D))
-    if sgm and (nhyp > MAX_D_SGM).any():
-        raise ValueError('%s: the regularisation takes at most %d depth hypotheses' % (what, MAX_D_SGM))
-    f, dev = _feature_tensor(f, what)
-    V, R, S, C = f.shape
+    return f, cams, views, used
+
+
+def _pair_tables(what, cams, views, used):
+    """-> (pair_off int32 [len(views) + 1], pair_src int32, the number of pair slots, T_rs per slot as fp64 [slots * 16])"""
     try:
         P, Pinv = projection_matrices(cams)
     except np.linalg.LinAlgError as e:
@@ -233,6 +270,24 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, r
             k += 1
     if not np.isfinite(mats[:npairs * 16]).all():
         raise ValueError('%s: a camera entry is NaN or infinite' % what)
+    return off, src, npairs, mats
+
+
+def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, regularize=None):
+    """The module's definition -> Sweep.  Device tensors are used where they are (the stream is theirs); numpy / CPU input is copied to the GPU.
+    views: the reference views to sweep, in this order (default: all); scores=True also returns the score volume of the last of them.
+    regularize: None (winner-take-all on the raw scores), True (the regularisation with SGM_DEFAULTS), (p1, p2) or (p1, p2, paths)."""
+    what = 'plane_sweep'
+    sgm = _sgm_args(regularize, what)
+    f, cams, views, used = _sweep_args(what, descriptors, cams, pairs, num_src, views)
+    nhyp = cams[views, 1, 3, 2] if views else np.zeros(0)
+    if (nhyp != np.floor(nhyp)).any() or (nhyp < 1).any() or (nhyp > MAX_D).any():
+        raise ValueError('%s: the number of depth hypotheses (cams[v, 1, 3, 2]) must be a whole number in [1, %d]' % (what, MAX_D))
+    if sgm and (nhyp > MAX_D_SGM).any():
+        raise ValueError('%s: the regularisation takes at most %d depth hypotheses' % (what, MAX_D_SGM))
+    f, dev = _feature_tensor(f, what)
+    V, R, S, C = f.shape
+    off, src, npairs, mats = _pair_tables(what, cams, views, used)
     vw = np.asarray(views, np.int32)
     ranges = np.ascontiguousarray(cams[views, 1, 3, :2] if views else np.zeros((0, 2)), np.float64)
     nh = np.asarray(nhyp, np.int32)
@@ -267,6 +322,192 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, r
     return Sweep(depths, probs, best_k, counts, vol, reg)
 
 
+class Cascade:
+    """The result of cascade_sweep: depths fp32 [V,R,S], probs fp32 [V,3,R,S], best_k int32 [V,R,S] and counts int32 [V,R,S] at the last stage's
+    size (the module doc, "Cascade": probs[:,1] is stage 1's full-range peak ratio), and stages: the Sweep of every stage at its own size."""
+
+    def __init__(self, depths, probs, best_k, counts, stages):
+        self.depths, self.probs, self.best_k, self.counts, self.stages = depths, probs, best_k, counts, stages
+
+
+def _size_of(size, what):
+    try:
+        R, S = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('%s: size must be (R, S), got %r' % (what, size)) from None
+    if R < 1 or S < 1 or R * S > 2 ** 31 - 1:
+        raise ValueError('%s: size must be at least 1 x 1 (and R*S < 2^31), got %r' % (what, size))
+    return R, S
+
+
+def upsample_depth(depth, best_k, size):
+    """The module's centres: depth fp32 [V,r,s] and best_k int32 [V,r,s] of a sweep (-1: no winner), size = (R, S) -> fp64 [V,R,S] on the device,
+    NaN where none of a pixel's four parents has a winner."""
+    what = 'upsample_depth'
+    R, S = _size_of(size, what)
+    d, k = torch.as_tensor(depth), torch.as_tensor(best_k)
+    if d.dim() != 3 or tuple(k.shape) != tuple(d.shape) or d.shape[0] < 1 or d.shape[1] < 2 or d.shape[2] < 2:
+        raise ValueError('%s: depth and best_k must both be [V, r, s] with V >= 1 and r, s >= 2, got %s and %s' % (what, tuple(d.shape), tuple(k.shape)))
+    dev = d.device if d.is_cuda else (k.device if k.is_cuda else torch.device('cuda'))
+    d, k = d.to(dev, torch.float32).contiguous(), k.to(dev, torch.int32).contiguous()
+    V, r, s = d.shape
+    out = torch.empty(V, R, S, dtype=torch.float64, device=dev)
+    check(lib().mvsdf_stereo_upsample(_vp(d), _vp(k), V, r, s, R, S, _vp(out), _stream(d)), 'mvsdf_stereo_upsample')
+    return out
+
+
+def _band_args(what, depth_num, step, V):
+    """-> (D_b, steps fp64 [V]), checked"""
+    if isinstance(depth_num, bool) or depth_num != int(depth_num) or not 1 <= int(depth_num) <= MAX_D_BAND:
+        raise ValueError('%s: depth_num must be a whole number in [1, %d], got %r' % (what, MAX_D_BAND, depth_num))
+    steps = np.asarray(step, np.float64)
+    if steps.ndim == 0:
+        steps = np.full(V, float(steps))
+    if steps.shape != (V,):
+        raise ValueError('%s: step must be a number or one per view (%d), got shape %s' % (what, V, steps.shape))
+    if not (np.isfinite(steps) & (steps > 0)).all():
+        raise ValueError('%s: every step must be finite and positive' % what)
+    return int(depth_num), steps
+
+
+def _checked_centres(what, centres, shape):
+    c = torch.as_tensor(centres)
+    if tuple(c.shape) != tuple(shape):
+        raise ValueError('%s: centres must be [V, R, S] = %s, got shape %s' % (what, tuple(shape), tuple(c.shape)))
+    if not c.is_cuda and bool(torch.isinf(c).any()):
+        raise ValueError('%s: a centre is infinite' % what)
+    return c
+
+
+def band_sweep(descriptors, cams, pairs, centres, depth_num, step, num_src=2, views=None):
+    """The module's band sweep -> Sweep (scores None; best_k the index within the band).  centres fp64 [V,R,S] (NaN: none); depth_num = D_b; step: a
+    number or one per view (indexed by the view, as cams is).  Device tensors are used where they are.  views: the reference views to sweep (default:
+    all; none twice), all of them in one launch."""
+    what = 'band_sweep'
+    f, cams, views, used = _sweep_args(what, descriptors, cams, pairs, num_src, views)
+    if len(set(views)) != len(views):
+        raise ValueError('%s: a view is listed twice' % what)
+    if len(views) > 65535:
+        raise ValueError('%s: at most 65535 views per call' % what)
+    Db, steps = _band_args(what, depth_num, step, len(pairs))
+    f = _checked_features(f, what)
+    c = _checked_centres(what, centres, f.shape[:3])
+    return _band_run(what, f, cams, views, used, c, Db, steps)
+
+
+def _band_run(what, f, cams, views, used, c, Db, steps):
+    """band_sweep once every argument has been checked"""
+    f, dev = _feature_tensor(f, what)
+    V, R, S, C = f.shape
+    off, src, npairs, mats = _pair_tables(what, cams, views, used)
+    c = c.to(dev, torch.float64).contiguous()
+    depths = torch.zeros(V, R, S, dtype=torch.float32, device=dev)
+    probs = torch.zeros(V, 3, R, S, dtype=torch.float32, device=dev)
+    best_k = torch.full((V, R, S), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros(V, R, S, dtype=torch.int32, device=dev)
+    if not views:
+        return Sweep(depths, probs, best_k, counts, None)
+    size = lib().mvsdf_stereo_band_workspace_bytes(R, S, Db, len(views), npairs)
+    if size == 0:
+        raise ValueError('%s: %d x %d texels are beyond the limits (R*S < 2^31)' % (what, R, S))
+    ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    vw = np.asarray(views, np.int32)
+    st = np.ascontiguousarray(steps[views], np.float64)
+    check(lib().mvsdf_stereo_band(_vp(f), V, R, S, C, len(views), vw.ctypes.data, off.ctypes.data, src.ctypes.data if npairs else None, mats.ctypes.data,
+                                  st.ctypes.data, _vp(c), Db, _vp(ws), size, _vp(depths), _vp(probs), _vp(best_k), _vp(counts), _stream(f)),
+          'mvsdf_stereo_band')
+    _, err = _header(ws, 2)                                                 # the one wait of the call; the host arrays live until here
+    _errors(err, what)
+    return Sweep(depths, probs, best_k, counts, None)
+
+
+def _cascade_args(what, depth_nums, interval_scales, stages=None):
+    """-> (depth_nums, interval_scales) as tuples of one length L (= stages where given), checked; D_1 may be None"""
+    try:
+        dn, sc = tuple(depth_nums), tuple(interval_scales)
+    except TypeError:
+        raise ValueError('%s: depth_nums and interval_scales must be tuples, got %r and %r' % (what, depth_nums, interval_scales)) from None
+    L = len(dn) if stages is None else stages
+    if not 1 <= L <= MAX_STAGES:
+        raise ValueError('%s: a cascade has 1 to %d stages, got %d' % (what, MAX_STAGES, L))
+    if len(dn) != L or len(sc) != L:
+        raise ValueError('%s: depth_nums and interval_scales must hold one entry per stage (%d), got %d and %d' % (what, L, len(dn), len(sc)))
+    for l, d in enumerate(dn):
+        if d is None and l == 0:
+            continue
+        if d is None or isinstance(d, bool) or d != int(d) or not 1 <= int(d) <= (MAX_D if l == 0 else MAX_D_BAND):
+            raise ValueError('%s: depth_nums[%d] must be a whole number in [1, %d]%s, got %r' %
+                             (what, l, MAX_D if l == 0 else MAX_D_BAND, ' or None' if l == 0 else '', d))
+    try:
+        sc = tuple(float(g) for g in sc)
+    except (TypeError, ValueError):
+        raise ValueError('%s: interval_scales must be numbers, got %r' % (what, interval_scales)) from None
+    if not all(np.isfinite(g) and g > 0 for g in sc):
+        raise ValueError('%s: every interval scale must be finite and positive, got %r' % (what, sc))
+    return tuple(None if d is None else int(d) for d in dn), sc
+
+
+def cascade_sweep(descriptors_per_stage, cams, pairs, num_src=2, views=None, depth_nums=CASCADE_DEFAULTS[0], interval_scales=CASCADE_DEFAULTS[1],
+                  regularize=None):
+    """The module's cascade -> Cascade.  descriptors_per_stage: one map [V,R_l,S_l,C_l] per stage, coarsest first; cams [V,2,4,4] at the last
+    stage's size.  Stage 1 is plane_sweep (regularize applies to it alone), every later stage one upsample_depth and one band_sweep."""
+    from .utils.io import scale_camera
+    what = 'cascade_sweep'
+    try:
+        maps = list(descriptors_per_stage)
+    except TypeError:
+        raise ValueError('%s: descriptors_per_stage must be a list of descriptor maps' % what) from None
+    if not 1 <= len(maps) <= MAX_STAGES:
+        raise ValueError('%s: a cascade has 1 to %d stages, got %d' % (what, MAX_STAGES, len(maps)))
+    L = len(maps)
+    dn, sc = _cascade_args(what, depth_nums, interval_scales, L)
+    sgm = _sgm_args(regularize, what)
+    # ---- every stage's arguments, before the GPU is touched ----
+    args = [_sweep_args(what, m, cams, pairs, num_src, views) for m in maps]
+    maps = [_checked_features(a[0], what) for a in args]
+    if any(m.shape[0] != maps[0].shape[0] for m in maps):
+        raise ValueError('%s: the stages differ in their number of views: %s' % (what, [m.shape[0] for m in maps]))
+    _, cams, views, used = args[-1]
+    if L > 1 and len(set(views)) != len(views):
+        raise ValueError('%s: a view is listed twice' % what)
+    V = len(pairs)
+    nhyp = cams[:, 1, 3, 2]
+    if (nhyp[views] != np.floor(nhyp[views])).any() or (nhyp[views] < 1).any() or (nhyp[views] > MAX_D).any():
+        raise ValueError('%s: the number of depth hypotheses (cams[v, 1, 3, 2]) must be a whole number in [1, %d]' % (what, MAX_D))
+    d1 = np.ceil(nhyp / sc[0]) if dn[0] is None else np.full(V, float(dn[0]))
+    if (d1[views] < 1).any() or (d1[views] > MAX_D).any():
+        raise ValueError('%s: stage 1 would sweep a number of hypotheses outside [1, %d]' % (what, MAX_D))
+    if sgm and (d1[views] > MAX_D_SGM).any():
+        raise ValueError('%s: the regularisation takes at most %d depth hypotheses' % (what, MAX_D_SGM))
+    interval = cams[:, 1, 3, 1]
+    steps = [interval * g for g in sc]
+    for l in range(1, L):
+        if not (np.isfinite(steps[l][views]) & (steps[l][views] > 0)).all():
+            raise ValueError('%s: the step of stage %d (interval * %g) must be finite and positive for every view' % (what, l + 1, sc[l]))
+    RL, SL = maps[-1].shape[1:3]
+    stage_cams = []
+    for l, m in enumerate(maps):
+        c = scale_camera(cams, (m.shape[2] / SL, m.shape[1] / RL))
+        c[:, 1, 3, 1] = steps[l]
+        if l == 0:
+            c[:, 1, 3, 2] = np.where(np.isfinite(d1), d1, 0.0)
+        stage_cams.append(c)
+    # ---- the stages ----
+    stages = [plane_sweep(maps[0], stage_cams[0], pairs, num_src=num_src, views=views, regularize=regularize)]
+    for l in range(1, L):
+        prev = stages[-1]
+        centres = upsample_depth(prev.depths, prev.best_k, maps[l].shape[1:3])
+        stages.append(_band_run(what, maps[l], stage_cams[l], views, used, centres, dn[l], steps[l]))
+    last, first = stages[-1], stages[0]
+    R1, S1 = first.depths.shape[1:]
+    dev = last.depths.device
+    yy = ((2 * torch.arange(RL, device=dev) + 1) * R1) // (2 * RL)
+    xx = ((2 * torch.arange(SL, device=dev) + 1) * S1) // (2 * SL)
+    probs = last.probs.clone()
+    probs[:, 1] = torch.where(last.best_k >= 0, first.probs[:, 1][:, yy][:, :, xx], torch.zeros((), dtype=torch.float32, device=dev))
+    return Cascade(last.depths, probs, last.best_k, last.counts, stages)
+
+
 def _write_cam(path, cam):
     """MVSNet's camera text with the four depth words (depth_min, interval, D, depth_max), which load_cam reads back"""
     txt = 'extrinsic\n' + '\n'.join(' '.join('%.17g' % v for v in r) for r in cam[0]) + '\n\nintrinsic\n'
@@ -285,12 +526,15 @@ def _find(folder, stem, exts):
 
 
 def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', num_src=2, max_d=256, interval_scale=1, resize=None, crop=None,
-                   radius=2, regularize=None):
+                   radius=2, regularize=None, cascade=None):
     """BYOD.md's "Run VisMVSNet" step by plane sweep.  Reads <data_root>/images/<id:08>.jpg|png, cams/<id:08>_cam.txt and pair.txt; resizes
     (prepare.resize_bilinear_u8) and centre-crops the images (resize / crop: 'W,H' or (W, H), default: as they are) and moves the cameras along;
     computes descriptors at half that size, as Vis-MVSNet's depth maps are: with feat_ckpt FeatExt.from_checkpoint + extract_features, else
     (descriptor='patch') patch_descriptors(radius) of the image resized to half; sweeps every view and writes into result_dir <id:08>_flow3.pfm,
-    <id:08>_flow{1,2,3}_prob.pfm, cam_<id:08>_flow3.txt (at depth-map scale), <id:08>.jpg (the cropped image) and pair.txt -> the Sweep.  regularize: plane_sweep's."""
+    <id:08>_flow{1,2,3}_prob.pfm, cam_<id:08>_flow3.txt (at depth-map scale), <id:08>.jpg (the cropped image) and pair.txt -> the Sweep.  regularize: plane_sweep's.
+    cascade: None / False (the one full sweep), True (cascade_sweep with CASCADE_DEFAULTS) or (depth_nums, interval_scales): the same files from the
+    final maps of the cascade -> the Cascade.  Its finest stage has the size above and every coarser one ((R + 1)//2, (S + 1)//2) of the next; with
+    feat_ckpt the stages are FeatExt's maps (features.extract_pyramid, at most three), else patch_descriptors of the image resized to each size."""
     from PIL import Image
     from .datasets import prepare
     from .utils import io as sio
@@ -298,6 +542,15 @@ def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', nu
     if feat_ckpt is None and descriptor != 'patch':
         raise ValueError("%s: descriptor must be 'patch' where no feat_ckpt is given, got %r" % (what, descriptor))
     _sgm_args(regularize, what)
+    if cascade is None or cascade is False:
+        cascade = None
+    else:
+        try:
+            cascade = _cascade_args(what, *(CASCADE_DEFAULTS if cascade is True else tuple(cascade)))
+        except TypeError:
+            raise ValueError('%s: cascade must be None, True or (depth_nums, interval_scales), got %r' % (what, cascade)) from None
+        if feat_ckpt is not None and len(cascade[0]) > 3:
+            raise ValueError('%s: FeatExt has three maps; a cascade over them has at most three stages' % what)
     pair_path = os.path.join(data_root, 'pair.txt')
     pair = sio.load_pair(pair_path)
     ids = pair['id_list']
@@ -326,12 +579,25 @@ def estimate_scene(data_root, result_dir, feat_ckpt=None, descriptor='patch', nu
         net = FeatExt.from_checkpoint(feat_ckpt).cuda()
         rgb = torch.from_numpy(np.stack(images)).permute(0, 3, 1, 2).float() / 255                # ImageNet normalisation, as SceneDataset feeds FeatExt
         rgb = (rgb - torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)) / torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
-        feats = extract_features(net, rgb).permute(0, 2, 3, 1).contiguous()
+        if cascade:
+            from .features import extract_pyramid
+            feats = list(extract_pyramid(net, rgb))[3 - len(cascade[0]):]
+        else:
+            feats = extract_features(net, rgb).permute(0, 2, 3, 1).contiguous()
     else:
         R, S = (H + 1) // 2, (W + 1) // 2
-        feats = patch_descriptors(np.stack([prepare.resize_bilinear_u8(im, S, R) for im in images]), radius)
+        sizes = [(R, S)]
+        for _ in range(len(cascade[0]) - 1 if cascade else 0):
+            sizes.insert(0, ((sizes[0][0] + 1) // 2, (sizes[0][1] + 1) // 2))
+        feats = [patch_descriptors(np.stack([prepare.resize_bilinear_u8(im, s, r) for im in images]), radius) for r, s in sizes]
+        if not cascade:
+            feats = feats[0]
     cams = np.stack([sio.scale_camera(c, (S / W, R / H)) for c in cams])
-    sweep = plane_sweep(normalize_descriptors(feats), cams, prepare.pair_indices(pair), num_src=num_src, regularize=regularize)
+    if cascade:
+        sweep = cascade_sweep([normalize_descriptors(f) for f in feats], cams, prepare.pair_indices(pair), num_src=num_src, depth_nums=cascade[0],
+                              interval_scales=cascade[1], regularize=regularize)
+    else:
+        sweep = plane_sweep(normalize_descriptors(feats), cams, prepare.pair_indices(pair), num_src=num_src, regularize=regularize)
     os.makedirs(result_dir, exist_ok=True)
     depths, probs = sweep.depths.cpu().numpy(), sweep.probs.cpu().numpy()
     for i, vid in enumerate(ids):

@@ -13,7 +13,13 @@ regularize_scores on the last view's score volume against the same definition as
 column per step, elementwise minima and sums in the definition's order, so it is compared bit for bit); the bytes the passes move = per direction
 the scores read, the running sum read (not by the first) and written.
 
+--cascade times stereo.cascade_sweep with its defaults (stages of --hw / 4, --hw / 2 and --hw, seeded noise descriptors per stage, 64 / 32 / 16
+hypotheses at max_d 256; with --sgm its first stage is regularised) against the full sweep at --hw in the same run (same protocol, one JSON line),
+and splits it by stage with device events around the calls cascade_sweep makes (plane_sweep, then upsample_depth + band_sweep per stage), whose
+results are compared with cascade_sweep's bit for bit; samples = the (pixel, hypothesis) pairs each evaluates.
+
     python tools/time_stereo.py [--views 10 --hw 288,384 --channels 32 --depths 256 --num_src 2 --repeats 3 --torch_repeats 1 --chunk 8] [--sgm]
+                                [--cascade]
 """
 import argparse
 import json
@@ -155,6 +161,53 @@ def time_sgm(a, stereo, desc, cams, pairs, hw):
                       'GBps': round(moved / (one * 1e-3) / 1e9, 1)}))
 
 
+def time_cascade(a, stereo, desc, cams, pairs, hw):
+    from mvsdf_amd.utils.io import scale_camera
+    dn, sc = stereo.CASCADE_DEFAULTS
+    reg = True if a.sgm else None
+    sizes = [(hw[0] // 4, hw[1] // 4), (hw[0] // 2, hw[1] // 2), hw]
+    descs = [stereo.normalize_descriptors(torch.randn(a.views, r, s, a.channels, generator=torch.Generator().manual_seed(l + 1)).cuda())
+             for l, (r, s) in enumerate(sizes[:-1])] + [desc]
+    _, full = _timed(lambda: stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src, regularize=reg), a.repeats)
+    cas, runs = _timed(lambda: stereo.cascade_sweep(descs, cams, pairs, num_src=a.num_src, regularize=reg), a.repeats)
+    # the same calls one by one, between device events
+    stage_cams = []
+    for l, (r, s) in enumerate(sizes):
+        c = scale_camera(cams, (s / hw[1], r / hw[0]))
+        c[:, 1, 3, 1] = cams[:, 1, 3, 1] * sc[l]
+        if l == 0:
+            c[:, 1, 3, 2] = np.ceil(cams[:, 1, 3, 2] / sc[0])
+        stage_cams.append(c)
+
+    def staged():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in sizes + [0]]
+        ev[0].record()
+        out = [stereo.plane_sweep(descs[0], stage_cams[0], pairs, num_src=a.num_src, regularize=reg)]
+        ev[1].record()
+        for l in range(1, len(sizes)):
+            centres = stereo.upsample_depth(out[-1].depths, out[-1].best_k, sizes[l])
+            out.append(stereo.band_sweep(descs[l], stage_cams[l], pairs, centres, dn[l], stage_cams[l][:, 1, 3, 1], num_src=a.num_src))
+            ev[l + 1].record()
+        torch.cuda.synchronize()
+        return out, [ev[l].elapsed_time(ev[l + 1]) for l in range(len(sizes))]
+
+    split = []
+    for rep in range(a.repeats + 1):                              # the first run warms up
+        out, ms = staged()
+        if rep:
+            split.append(ms)
+    differ = sum(int((getattr(o, n) != getattr(st, n)).sum()) for o, st in zip(out, cas.stages) for n in ('depths', 'probs', 'best_k', 'counts'))
+    hip, base = float(np.median(runs)), float(np.median(full))
+    nums = [int(np.ceil(a.depths / sc[0])) if dn[0] is None else dn[0]] + list(dn[1:])
+    print(json.dumps({'cascade': [nums, list(sc)], 'sgm': bool(a.sgm), 'views': a.views, 'stage_hw': [list(v) for v in sizes], 'channels': a.channels,
+                      'depths': a.depths, 'num_src': a.num_src, 'cascade_median_ms': round(hip, 2), 'cascade_runs_ms': [round(v, 2) for v in runs],
+                      'full_sweep_median_ms': round(base, 2), 'full_sweep_runs_ms': [round(v, 2) for v in full], 'full_over_cascade': round(base / hip, 2),
+                      'stage_median_ms': [round(float(v), 3) for v in np.median(np.asarray(split), 0)],
+                      'stage_samples_per_view': [n * r * s for n, (r, s) in zip(nums, sizes)], 'full_samples_per_view': a.depths * hw[0] * hw[1],
+                      'stage_elements_that_differ_from_cascade_sweep': differ,
+                      'winner_share_last_stage': round(float((cas.best_k >= 0).double().mean()), 4)}))
+
+
 def _timed(fn, repeats):
     runs = []
     for rep in range(repeats + 1):                                # the first run warms up
@@ -178,12 +231,15 @@ def main():
     ap.add_argument('--torch_repeats', type=int, default=1)
     ap.add_argument('--chunk', type=int, default=8)
     ap.add_argument('--sgm', action='store_true', default=False, help='time the semi-global regularisation instead')
+    ap.add_argument('--cascade', action='store_true', default=False, help='time the coarse-to-fine cascade instead (with --sgm: its first stage regularised)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_stereo.py measures on the GPU'
     from mvsdf_amd import stereo
     hw = tuple(int(v) for v in a.hw.split(','))
     cams, pairs, feats = scene(a.views, hw, a.channels, a.depths)
     desc = stereo.normalize_descriptors(feats.cuda())
+    if a.cascade:
+        return time_cascade(a, stereo, desc, cams, pairs, hw)
     if a.sgm:
         return time_sgm(a, stereo, desc, cams, pairs, hw)
     sw, runs = _timed(lambda: stereo.plane_sweep(desc, cams, pairs, num_src=a.num_src), a.repeats)
