@@ -8,10 +8,10 @@
 
 #include <stdlib.h>
 int mv_fail(int code, const char* msg);          // records msg, returns code
-// Development / A-B switches (alternative launch paths that are independent implementations of the same passes: MVSDF_FUSE, MVSDF_SPLIT_CHAINS, MVSDF_CHAIN_W8,
-// MVSDF_CHAIN_MT, MVSDF_DELTA_CHAIN, MVSDF_LAYER_MT, MVSDF_WG_XCD, MVSDF_BF_CARRY, MVSDF_TAIL_STOP, MVSDF_NFIRST, MVSDF_MT_FIRST) exist only in a library built with
+// Development / A-B switches (alternative launch paths that are independent implementations of the same passes) exist only in a library built with
 // -DMVSDF_DEV_SWITCHES (mvsdf_amd/build.py: build(tag='dev'); tests/test_gpu_alt_paths.py and the sweep tools load it through MVSDF_LIB).  The product library never
-// reads them: its behaviour does not depend on stray environment variables.  (Product switches, read with getenv directly: MVSDF_TAIL, MVSDF_SPLIT_ROWS.)
+// reads them: its behaviour does not depend on stray environment variables.  The list: diff_route.h::MvDevSwitches for the differentiable passes; MVSDF_BF_CARRY,
+// MVSDF_TAIL_STOP, MVSDF_NFIRST, MVSDF_MT_FIRST, MVSDF_SGM_LGH / _LGV where they are read.  (Product switches, read with getenv directly: MVSDF_TAIL, MVSDF_SPLIT_ROWS.)
 static inline const char* mv_dev_env(const char* name) {
 #ifdef MVSDF_DEV_SWITCHES
     return getenv(name);

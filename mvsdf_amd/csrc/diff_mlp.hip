@@ -7,6 +7,7 @@
 #include "chain_x3.h"
 #include "capi_util.h"
 #include "step_internal.h"
+#include "diff_route.h"
 
 // ------------------------------------------------------------------------------------------------ small kernels
 // H0[row][0..d0) = PE(x[row]); H0[row][d0..ld) = 0       (embedder.py:10-36)
@@ -105,29 +106,81 @@ __global__ void k_add_inplace(float* __restrict__ dst, const float* __restrict__
     if (i < n) dst[i] += src[i];
 }
 
-// ------------------------------------------------------------------------------------------------ launch helpers
-template <int PRO, int EPI, int MT>
-static hipError_t launch_layer_mt(LayerArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)16 * MT * a.S * sizeof(float);
-    static size_t lds_set = 0;                                 // per instantiation: raise the dynamic-LDS cap once per size
-    if (lds > 48 * 1024 && lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_layer<PRO, EPI, MT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_set = lds;
-    }
-    hipLaunchKernelGGL((k_layer<PRO, EPI, MT, 4>), dim3((a.M + 16 * MT - 1) / (16 * MT)), dim3(MV_THREADS), lds, s, a);
+// ------------------------------------------------------------------------------------------------ switches, launch helpers
+// the development switches (diff_route.h), read once per process; the product library reads none (capi_util.h::mv_dev_env)
+const MvDevSwitches& mv_dev_switches() {
+    static const MvDevSwitches sw = mv_switches_from_env(mv_dev_env);
+    return sw;
+}
+
+#define MV_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return mv_check(e_, #expr); } while (0)
+// dynamic-LDS limit of the kernel instance K, raised only when a launch needs more than the default and more than any launch of K before it (one high-water
+// mark per instance; the runtime call costs a few microseconds of host time, a training step would make four of them)
+template <auto K>
+static hipError_t mv_lds_limit(size_t bytes) {
+    static size_t hw = 48 * 1024;
+    if (bytes <= hw) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) hw = bytes;
+    return e;
+}
+template <auto K, class... A>
+static hipError_t mv_launch(int blocks, int threads, size_t lds, hipStream_t s, const A&... a) {
+    const hipError_t e = mv_lds_limit<K>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), lds, s, a...);
     return hipGetLastError();
 }
+static int mv_blocks(int rows, int mt) { return (rows + 16 * mt - 1) / (16 * mt); }
 
 template <int PRO, int EPI>
 static hipError_t launch_layer(LayerArgs& a, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
-    // rows per workgroup: 16 while that still leaves the chip under-subscribed (one workgroup per CU), else 32 (weights
-    // reused by two row tiles).  MVSDF_LAYER_MT overrides (dev).
-    static int mt_env = -1;
-    if (mt_env < 0) { const char* e = mv_dev_env("MVSDF_LAYER_MT"); mt_env = e ? atoi(e) : 0; }
-    const bool small = mt_env ? (mt_env == 1) : (a.M <= 16 * 512);
-    return small ? launch_layer_mt<PRO, EPI, 1>(a, s) : launch_layer_mt<PRO, EPI, 2>(a, s);
+    const int mt = mv_layer_mt(a.M, mv_dev_switches());
+    const size_t lds = (size_t)16 * mt * a.S * sizeof(float);
+    return mt == 1 ? mv_launch<k_layer<PRO, EPI, 1, 4>>(mv_blocks(a.M, 1), MV_THREADS, lds, s, a)
+                   : mv_launch<k_layer<PRO, EPI, 2, 4>>(mv_blocks(a.M, 2), MV_THREADS, lds, s, a);
+}
+
+// ---- one launcher per chain-kernel family: the instance <MT, NTW, NW(, PD)> of a route (diff_route.h) -> the template instance.  Each family lists exactly
+// the instances it has -- the set of kernels in the library is what these lines name -- and refuses a route that names another one. ----
+#define MV_INST(K, ...) if (mv_route_is(r, __VA_ARGS__)) return mv_launch<K<__VA_ARGS__>>(blocks, 64 * r.nw, lds, s, a...)
+static bool mv_route_is(const MvRoute& r, int mt, int ntw, int nw, int pd = 0) { return r.mt == mt && r.ntw == ntw && r.nw == nw && r.pd == pd; }
+// the fp32 chains: four one-tile forms; k_chain_fwd / k_chain_bwd (the delta chain only) / k_chain_bwd2 have the two-tile form <2, 1, 16> too
+#define MV_F32_ONE_TILE(K) MV_INST(K, 1, 1, 16); MV_INST(K, 1, 2, 16); MV_INST(K, 1, 2, 8); MV_INST(K, 1, 4, 8)
+template <class... A> static hipError_t launch_chain_fwd(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_INST(k_chain_fwd, 2, 1, 16); MV_F32_ONE_TILE(k_chain_fwd); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_chain_bwd(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_INST(k_chain_bwd, 2, 1, 16); MV_F32_ONE_TILE(k_chain_bwd); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_chain_bwd2(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_INST(k_chain_bwd2, 2, 1, 16); MV_F32_ONE_TILE(k_chain_bwd2); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_render_chain_fwd(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_F32_ONE_TILE(k_render_chain_fwd); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_render_chain_bwd(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_F32_ONE_TILE(k_render_chain_bwd); return hipErrorInvalidValue;
+}
+// the split chains: the 8-wave forms only
+template <class... A> static hipError_t launch_chain_e1(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_INST(k_chain_e1, 1, 2, 8); MV_INST(k_chain_e1, 1, 4, 8); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_chain_e2(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_INST(k_chain_e2, 1, 2, 8); MV_INST(k_chain_e2, 1, 4, 8); return hipErrorInvalidValue;
+}
+// the x3 chains: two one-tile forms; k_chain_fwd_x3 / k_chain_bwd2_x3 have two two-tile forms too (the single-pass backward does not)
+#define MV_X3_ONE_TILE(K) MV_INST(K, 1, 1, 16, MV_X3_PD1); MV_INST(K, 1, 2, 16, 0)
+#define MV_X3_TWO_TILE(K) MV_INST(K, 2, 1, 16, MV_X3_PD2); MV_INST(K, 2, 4, 8, 0)
+template <class... A> static hipError_t launch_chain_fwd_x3(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_X3_TWO_TILE(k_chain_fwd_x3); MV_X3_ONE_TILE(k_chain_fwd_x3); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_chain_bwd_x3(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_X3_ONE_TILE(k_chain_bwd_x3); return hipErrorInvalidValue;
+}
+template <class... A> static hipError_t launch_chain_bwd2_x3(const MvRoute& r, int blocks, size_t lds, hipStream_t s, const A&... a) {
+    MV_X3_TWO_TILE(k_chain_bwd2_x3); MV_X3_ONE_TILE(k_chain_bwd2_x3); return hipErrorInvalidValue;
 }
 
 static LayerArgs base_args(const MvLayer& L, int S, int M) {
@@ -135,12 +188,6 @@ static LayerArgs base_args(const MvLayer& L, int S, int M) {
     memset(&a, 0, sizeof(a));
     a.L = L; a.S = S; a.M = M;
     return a;
-}
-
-static bool mv_chain_w8() {
-    static int v = -1;
-    if (v < 0) { const char* e = mv_dev_env("MVSDF_CHAIN_W8"); v = e ? atoi(e) : 0; }
-    return v != 0;
 }
 
 static int stride_for(const MvNet& a, const MvNet& b) { return a.S > b.S ? a.S : b.S; }
@@ -231,10 +278,8 @@ static hipError_t wgrad_launch(WgradNetArgs& a, hipStream_t s) {
     // XCD-aware block order (layer_kernels.h; same blocks, same arithmetic, another placement): on by default, MVSDF_WG_XCD=0 turns it off.  Round 4, rocprofv3:
     // 92.9 -> 85.0 us at c2, 154.6 -> 153.9 at the c5 share, 310.7 -> 304.0 at c3 (round 2's two orders -- a contiguous range per XCD, and this one at c2 on the
     // older kernel -- measured nothing)
-    static int xcd_env = -2;
-    if (xcd_env == -2) { const char* e = mv_dev_env("MVSDF_WG_XCD"); xcd_env = (e && *e) ? atoi(e) : -1; }
     a.nblocks = blk;
-    a.xcd_runs = xcd_env >= 0 ? (xcd_env != 0) : 1;
+    a.xcd_runs = mv_dev_switches().wg_xcd;
     const int grid = a.xcd_runs ? ((blk + 127) / 128) * 128 : blk;
     if (blk > 0) hipLaunchKernelGGL(k_wgrad_net, dim3(grid), dim3(MV_THREADS), 0, s, a);
     return hipGetLastError();
@@ -269,40 +314,18 @@ static int mv_single_skip(const MvNet& net) {
     return __builtin_ctz(m);
 }
 
-// Row tiles per workgroup of the fused chain kernels (the W <= 256, 16-wave instantiations).  A workgroup with two 16-row tiles takes
-// ~1.76x one tile (measured at c3: the phases are bound by the per-row loads / stores of the saved activations, not by the shared weight
-// fragments), so two tiles pay only when they save a round of the 256 CUs: 257..512 tiles (c5's per-GPU share: 248 -> 215 us), not
-// 513..768 (c3).  Four tiles never pay (3.8x).  MVSDF_CHAIN_MT=1|2 overrides (dev A/B).
-static int mv_chain_mt(int tiles16) {
-    static const int env = [] { const char* e = mv_dev_env("MVSDF_CHAIN_MT"); return e ? atoi(e) : 0; }();
-    if (env == 1 || env == 2) return env;
-    const int rounds1 = (tiles16 + 255) / 256, rounds2 = (tiles16 + 511) / 512;
-    return 1.76 * rounds2 < rounds1 ? 2 : 1;
-}
-/* Does the fused forward chain over the rows [E, M) alone need fewer / shorter rounds of workgroups than over [0, M)?  (the same model as
- * mv_chain_mt: a round of two-tile workgroups costs 1.76 rounds of one-tile workgroups)  The step asks before it moves the E sample rows beside the tracer. */
+/* Does the fused forward chain over the rows [E, M) alone need fewer / shorter rounds of workgroups than over [0, M)?  (the cost model that picks the row
+ * tiles per workgroup: diff_route.h)  The step asks before it moves the E sample rows beside the tracer. */
 int mv_chain_split_pays(const MvsdfNetDesc* d, int E, int M) {
     MvNet net;
-    if (E < 16 || E >= M || mv_make_net(d, &net) || mv_chain_ntw(net) != 2 || mv_chain_w8()) return 0;
-    auto cost = [](int tiles16) { const int r1 = (tiles16 + 255) / 256, r2 = (tiles16 + 511) / 512; return 1.76 * r2 < r1 ? 1.76 * r2 : 1.0 * r1; };
-    return cost((M - E + 15) / 16) < cost((M + 15) / 16) ? 1 : 0;
+    if (E < 16 || E >= M || mv_make_net(d, &net) || mv_chain_ntw(net) != 2 || mv_dev_switches().chain_w8) return 0;
+    return mv_chain_shorter((M - E + 15) / 16, (M + 15) / 16) ? 1 : 0;
 }
 
-// The fused chains in the three-term bf16 arithmetic (chain_x3.h) run when both descriptors carry the packs (MvsdfNetDesc.wx3); the dev library's
-// MVSDF_CHAIN_X3=0 keeps the fp32-input MFMA chains (A/B, tests/test_gpu_alt_paths.py).
-static bool mv_chain_x3_on() {
-    static const int env = [] {
-        const char* e = mv_dev_env("MVSDF_CHAIN_X3");
-        const char* f = mv_dev_env("MVSDF_FUSE");                 // (the dev switches that pick the per-layer / split fp32 launches mean the fp32 arithmetic everywhere)
-        if ((f && atoi(f) == 0) || mv_dev_env("MVSDF_SPLIT_CHAINS") || mv_dev_env("MVSDF_CHAIN_W8")) return 0;
-        return e ? atoi(e) : 1;
-    }();
-    return env != 0;
-}
-int mv_chain_x3_enabled() { return mv_chain_x3_on() ? 1 : 0; }
-// -> 0 and both nets when the x3 chains can run this network (needT: the transposed packs too)
+// The fused chains in the three-term bf16 arithmetic (chain_x3.h) run when both descriptors carry the packs (MvsdfNetDesc.wx3) -- a route asks for them only
+// where MvDevSwitches::chain_x3 lets it.  -> 0 and both nets when the x3 chains can run this network (needT: the transposed packs too)
 static int mv_x3_nets(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, bool needT, MvNetBf* xn, MvNetBf* xnT) {
-    if (!mv_chain_x3_on() || mv_make_net_x3(d, xn)) return 1;
+    if (mv_make_net_x3(d, xn)) return 1;
     if (needT) { if (!dT || mv_make_net_x3(dT, xnT)) return 1; }
     else *xnT = *xn;
     xnT->skip_mask = xn->skip_mask; xnT->multires = xn->multires;
@@ -310,35 +333,10 @@ static int mv_x3_nets(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, bool needT,
     xn->S = xnT->S = S16;
     return 0;
 }
-// row tiles per workgroup of the x3 chains: two tiles share the weight stream that bounds a phase (tile_engine_bf16s.h: 56 vs 41 us per evaluation), so
-// they pay as soon as they save a round of the 256 CUs
-static int mv_chain_mt_x3(int tiles16) {
-    static const int env = [] { const char* e = mv_dev_env("MVSDF_CHAIN_MT"); return e ? atoi(e) : 0; }();
-    if (env == 1 || env == 2) return env;
-    const int rounds1 = (tiles16 + 255) / 256, rounds2 = (tiles16 + 511) / 512;
-    return 1.45 * rounds2 < rounds1 ? 2 : 1;
-}
-
-// Carried-ring depth (k-blocks of the next phase's weights requested early, chain_x3.h) of the x3 chains.  One row tile per workgroup (<= 256 tiles: c2): 4 --
-// k_chain_fwd_x3 111 -> 97 us, the c2 step 1.503 -> 1.485 ms.  Two row tiles: 0 (the rolling fetch): with 2 the c5-share step went 1.51-1.55 -> 1.57-1.61 ms and c3
-// 4.04 -> 4.20 ms -- at those sizes the sample rows' chain runs BESIDE the tracer (mv_chain_split_pays), and a chain that keeps the L2 busy through its epilogues
-// takes that bandwidth from the tracer's own weight stream (k_ray_samples 0.446 -> 0.478 ms, k_sphere_trace 1.17 -> 1.27 ms at c3).
-#ifndef MV_X3_PD1
-#define MV_X3_PD1 4
-#endif
-#ifndef MV_X3_PD2
-#define MV_X3_PD2 0
-#endif
-
-#define MV_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return mv_check(e_, #expr); } while (0)
-// dynamic-LDS limit of one kernel instance, raised only when a launch needs more than any launch before it (`hw`: one static high-water mark per site;
-// the runtime call costs a few microseconds of host time, a training step would make four of them)
-template <class K>
-static hipError_t mv_lds_limit(K kern, size_t bytes, size_t& hw) {
-    if (bytes <= hw) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) hw = bytes;
-    return e;
+// the two nets of an entry point: the network itself (mode 0: SDF, 1: rendering) and its transposed packs
+static int mv_open_nets(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int mode, MvNet* net, MvNet* netT) {
+    const int rc = mv_make_net_mode(d, net, mode);
+    return rc ? rc : mv_make_net_mode(dT, netT, 2);
 }
 
 extern "C" {
@@ -360,6 +358,39 @@ int mvsdf_sdf_forward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float
 }
 
 }  // extern "C"
+
+// arguments of the fused forward chain over the rows [r_begin, r_end) (xnetT == NULL: no normals)
+template <class NET>
+static void fill_fwd_args(FwdArgsT<NET>& f, const NET& xnet, const NET* xnetT, int S, const MvNet& net, const SdfLayout& lo, const MvsdfNetDesc* d, const float* x,
+                          const FwdGather* g, int r_begin, int r_end, int Mg, float* y, float* nrm, float* ctx) {
+    memset(&f, 0, sizeof(f));
+    const int nl = lo.nl;
+    f.net = xnet; if (xnetT) f.netT = *xnetT;
+    f.S = S; f.M = r_end; f.Mg = Mg < r_end ? Mg : r_end; f.row_base = r_begin; f.ld0 = lo.ld0; f.x = x; f.H0 = ctx + lo.H0;
+    for (int l = 1; l < nl; ++l) f.A[l] = ctx + lo.A[l];
+    for (int l = 0; l < nl - 1; ++l) { f.Z[l] = ctx + lo.Z[l]; f.Sg[l] = ctx + lo.Sg[l]; }
+    for (int l = 1; l < nl - 1; ++l) f.U[l] = ctx + lo.U[l];
+    f.G0 = ctx + lo.G0; f.y = y; f.ldy = net.L[nl - 1].N; f.w_last_row0 = d->w[nl - 1]; f.nrm = nrm;
+    if (g) f.g = *g;
+}
+
+// fill the arguments of one fused chain pass over rows [row0, row0 + Mb) of a forward context
+template <class NETX>
+static void fill_chain_args(ChainArgsT<NETX>& c, const MvNet& net, const NETX& xnet, const NETX& xnetT, int S, const SdfLayout& lo, const SdfBwdLayout& bl, const float* ctx,
+                            int row0, int Mb, const float* dy, const float* dn, float* ws, float* dx, const float* w8) {
+    memset(&c, 0, sizeof(c));
+    const int nl = lo.nl;
+    const size_t r0 = (size_t)row0;
+    c.net = xnet; c.netT = xnetT; c.S = S; c.M = Mb; c.row_ld0 = lo.ld0;
+    c.dy = dy; c.ld_dy = net.L[nl - 1].N; c.w_last_row0 = w8;
+    for (int l = 0; l < nl - 1; ++l) {
+        c.Z[l] = ctx + lo.Z[l] + r0 * net.L[l].N; c.ZB[l] = ws + bl.ZB[l];
+        c.ZB2[l] = dn ? ws + bl.ZB2[l] : nullptr; c.ZB2o[l] = ws + bl.ZB2[l];
+        if (l + 1 < nl - 1) c.U[l + 1] = ctx + lo.U[l + 1] + r0 * net.L[l].N;
+        c.VB[l + 1] = ws + bl.VB[l + 1];
+    }
+    c.H0B = ws + bl.H0B; c.H0 = ctx + lo.H0 + r0 * lo.ld0; c.G0 = ctx + lo.G0 + r0 * lo.ld0; c.dn_in = dn; c.VB0w = ws + bl.VB[0]; c.dx = dx;
+}
 
 /* mvsdf_sdf_forward whose rows are gathered inside the fused chain kernel (g != NULL: the rows [eikonal | on-surface | jittered | pts[perm]], also
  * written to g->x_out) -- the training step's x_eval without a gather launch.  -> 1 when g was given but the per-layer route had to run: nothing was
@@ -385,72 +416,21 @@ int mv_sdf_forward_gather(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const f
     const SdfLayout lo = sdf_ctx_layout(net, M, Mg);
     const int nl = lo.nl, S = Mg > 0 ? stride_for(net, netT) : net.S;
     float* H0 = ctx + lo.H0;
-    static int fuse_fwd = -1;
-    if (fuse_fwd < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse_fwd = e ? atoi(e) : 1; }
-    const int ntw_f = mv_chain_ntw(net);
+    const int Mr = r_end - r_begin, tiles = (Mr + 15) / 16, ntw = mv_chain_ntw(net);
     MvNetBf xn, xnT;
-    if (fuse_fwd && ntw_f && nl >= 2 && net.L[nl - 1].NT <= 8 * ntw_f * 4 && !mv_x3_nets(d, dT, Mg > 0, &xn, &xnT)) {   // ... in the three-term bf16 arithmetic
+    MvRoute r = mv_route_sdf_forward(ntw, tiles, net.L[nl - 1].NT, true, g || sub, mv_dev_switches());
+    if (r.family == MV_FAM_X3 && mv_x3_nets(d, dT, Mg > 0, &xn, &xnT)) r = mv_route_sdf_forward(ntw, tiles, net.L[nl - 1].NT, false, g || sub, mv_dev_switches());
+    if (r.family == MV_FAM_X3) {                                 // value + normal of a row tile in one launch, in the three-term bf16 arithmetic
         FwdArgsX3 f;
-        memset(&f, 0, sizeof(f));
-        f.net = xn; f.netT = xnT;
-        const int Mr = r_end - r_begin;
-        f.S = xn.S; f.M = r_end; f.Mg = Mg < r_end ? Mg : r_end; f.row_base = r_begin; f.ld0 = lo.ld0; f.x = x; f.H0 = H0;
-        for (int l = 1; l < nl; ++l) f.A[l] = ctx + lo.A[l];
-        for (int l = 0; l < nl - 1; ++l) { f.Z[l] = ctx + lo.Z[l]; f.Sg[l] = ctx + lo.Sg[l]; }
-        for (int l = 1; l < nl - 1; ++l) f.U[l] = ctx + lo.U[l];
-        f.G0 = ctx + lo.G0; f.y = y; f.ldy = net.L[nl - 1].N; f.w_last_row0 = d->w[nl - 1]; f.nrm = nrm;
-        if (g) f.g = *g;
-        // (hidden width 257 .. 512, two row tiles: 8 waves x 4 column tiles -- a 16-row tile streams 1.57 MB of weight terms per phase, more than its matrix
-        // instructions take; at 37 000 rows of the 8x512 network 4208 (fp32 chain) / 3842 (one tile) / 2761 us (two tiles))
-        const int mt = mv_chain_mt_x3((Mr + 15) / 16);
-        const size_t lds = (size_t)3 * 16 * mt * xn.S * 2 + ((size_t)2 * ((16 * mt * lo.d0 + 3) & ~3) + 16 * mt * 4) * sizeof(float);
-        const dim3 grid((Mr + 16 * mt - 1) / (16 * mt));
-        if (ntw_f == 4 && mt == 2) {
-            { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_fwd_x3<2, 4, 8>, lds, hw)); }
-            hipLaunchKernelGGL((k_chain_fwd_x3<2, 4, 8>), grid, dim3(512), lds, s, f);
-            return mv_check(hipGetLastError(), "mvsdf_sdf_forward (x3 chain)");
-        }
-        // hidden width <= 256: 16 waves x 1 column tile; up to 512: 16 waves x 2 tiles
-        if (mt == 2) {
-            { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_fwd_x3<2, 1, 16, MV_X3_PD2>, lds, hw)); }
-            hipLaunchKernelGGL((k_chain_fwd_x3<2, 1, 16, MV_X3_PD2>), grid, dim3(1024), lds, s, f);
-        }
-        else if (ntw_f == 2) hipLaunchKernelGGL((k_chain_fwd_x3<1, 1, 16, MV_X3_PD1>), grid, dim3(1024), lds, s, f);
-        else hipLaunchKernelGGL((k_chain_fwd_x3<1, 2, 16>), grid, dim3(1024), lds, s, f);
-        return mv_check(hipGetLastError(), "mvsdf_sdf_forward (x3 chain)");
+        fill_fwd_args(f, xn, &xnT, xn.S, net, lo, d, x, g, r_begin, r_end, Mg, y, nrm, ctx);
+        return mv_check(launch_chain_fwd_x3(r, mv_blocks(Mr, r.mt), mv_lds_fwd_x3(r.mt, xn.S, lo.d0), s, f), "mvsdf_sdf_forward (x3 chain)");
     }
-    if (fuse_fwd && ntw_f && net.L[nl - 1].NT <= 8 * ntw_f * 4) {                  // value + normal of a row tile in one launch
+    if (r.family == MV_FAM_F32) {                                // ... on the fp32-input MFMA
         FwdArgs f;
-        memset(&f, 0, sizeof(f));
-        f.net = net; if (Mg > 0) f.netT = netT;
-        const int Mr = r_end - r_begin;
-        f.S = S; f.M = r_end; f.Mg = Mg < r_end ? Mg : r_end; f.row_base = r_begin; f.ld0 = lo.ld0; f.x = x; f.H0 = H0;
-        for (int l = 1; l < nl; ++l) f.A[l] = ctx + lo.A[l];
-        for (int l = 0; l < nl - 1; ++l) { f.Z[l] = ctx + lo.Z[l]; f.Sg[l] = ctx + lo.Sg[l]; }
-        for (int l = 1; l < nl - 1; ++l) f.U[l] = ctx + lo.U[l];
-        f.G0 = ctx + lo.G0; f.y = y; f.ldy = net.L[nl - 1].N; f.w_last_row0 = d->w[nl - 1]; f.nrm = nrm;
-        if (g) f.g = *g;
-        constexpr int MTC = 1, NWC = 8;
-        const size_t lds = ((size_t)16 * MTC * S + 2 * ((16 * MTC * lo.d0 + 3) & ~3) + 16 * MTC * 4) * sizeof(float);
-        // 16 waves per workgroup (one or two column tiles each): these launches are single waves of one-tile workgroups, i.e. chains of
-        // dependent layer phases; twice the waves halve every wave's share of the global loads / stores and of the epilogue between
-        // two GEMMs (measured 148 -> 127 us here, 173 -> 143 us for the backward pass).  MVSDF_CHAIN_W8=1: 8 waves (dev A/B).
-        const bool w8 = mv_chain_w8();
-        const dim3 grid((Mr + 16 * MTC - 1) / (16 * MTC));
-        const int mt = (ntw_f == 2 && !w8) ? mv_chain_mt((Mr + 15) / 16) : 1;
-        if (mt > 1) {
-            const size_t ldsm = ((size_t)16 * mt * S + 2 * ((16 * mt * lo.d0 + 3) & ~3) + 16 * mt * 4) * sizeof(float);
-            const dim3 gridm((Mr + 16 * mt - 1) / (16 * mt));
-            { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_fwd<2, 1, 16>, ldsm, hw)); }
-            hipLaunchKernelGGL((k_chain_fwd<2, 1, 16>), gridm, dim3(1024), ldsm, s, f);
-        }
-        else if (ntw_f == 2 && !w8) hipLaunchKernelGGL((k_chain_fwd<MTC, 1, 16>), grid, dim3(1024), lds, s, f);
-        else if (ntw_f == 2) hipLaunchKernelGGL((k_chain_fwd<MTC, 2, NWC>), grid, dim3(64 * NWC), lds, s, f);
-        else if (!w8) hipLaunchKernelGGL((k_chain_fwd<MTC, 2, 16>), grid, dim3(1024), lds, s, f);
-        else hipLaunchKernelGGL((k_chain_fwd<MTC, 4, NWC>), grid, dim3(64 * NWC), lds, s, f);
-        return mv_check(hipGetLastError(), "mvsdf_sdf_forward");
+        fill_fwd_args(f, net, Mg > 0 ? &netT : nullptr, S, net, lo, d, x, g, r_begin, r_end, Mg, y, nrm, ctx);
+        return mv_check(launch_chain_fwd(r, mv_blocks(Mr, r.mt), mv_lds_fwd_f32(r.mt, S, lo.d0), s, f), "mvsdf_sdf_forward");
     }
-    if (g || sub) return 1;                                      // per-layer route: rows must be materialised by the caller, all of them at once
+    if (r.family == MV_FAM_REFUSE) return r.rc;                  // per-layer route: rows must be materialised by the caller, all of them at once
     hipLaunchKernelGGL(k_pe_global, dim3((M * (3 * net.multires + 1) + 255) / 256), dim3(256), 0, s, x, M, net.multires, H0, lo.ld0);
     for (int l = 0; l < nl - 1; ++l) {                                            // hidden layers (idr.py:82-92)
         LayerArgs a = base_args(net.L[l], S, M);
@@ -505,9 +485,7 @@ extern "C" {
 int mvsdf_sdf_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float* x, int M, int Mg, int row0, int Mb, const float* dy,
                        const float* dn, const float* ctx, float* dW_cat, float* db_cat, float* dx, float* ws, void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net(d, &net);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 0, &net, &netT);
     if (rc) return rc;
     if (!x || !dy || !ctx || !ws || Mb <= 0 || row0 < 0 || row0 + Mb > M || (dn && row0 + Mb > Mg) || ((dW_cat == nullptr) != (db_cat == nullptr)))
         return mv_fail(-1, "mvsdf_sdf_backward: bad arguments");
@@ -525,144 +503,82 @@ int mvsdf_sdf_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const floa
     auto Uof = [&](int l) { return ctx + lo.U[l] + r0 * net.L[l - 1].N; };       // u_l has width out_{l-1}
     auto Sof = [&](int l) { return ctx + lo.Sg[l] + r0 * net.L[l].N; };
     const float* G0 = ctx + lo.G0 + r0 * lo.ld0;
-    // ---- the whole pass in one launch per row tile (gbar_0, E.1, E.2, input adjoint) when the chain kernels fit the network ----
-    static int fuse_all = -1;
-    if (fuse_all < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse_all = e ? atoi(e) : 1; if (mv_dev_env("MVSDF_SPLIT_CHAINS")) fuse_all = 0; }
-    const int ntw_b = mv_chain_ntw(net);
-    bool chains_done = false;
+    // ---- route (diff_route.h) ----
+    const int ntw = mv_chain_ntw(net), tiles = (Mb + 15) / 16;
     MvNetBf xn, xnT;
-    if (fuse_all >= 1 && ntw_b && nl >= 2 && !mv_x3_nets(d, dT, true, &xn, &xnT)) {     // the whole pass in the three-term bf16 arithmetic (chain_x3.h)
+    MvRoute r = mv_route_sdf_backward(ntw, tiles, true, sk == -2, mv_dev_switches());
+    if (r.family == MV_FAM_X3 && mv_x3_nets(d, dT, true, &xn, &xnT)) r = mv_route_sdf_backward(ntw, tiles, false, sk == -2, mv_dev_switches());
+    if (r.family == MV_FAM_REFUSE)
+        return mv_fail(r.rc, "mvsdf_sdf_backward: several skip connections need the fused chain kernels (MVSDF_FUSE / MVSDF_SPLIT_CHAINS unset)");
+    const bool whole = r.family == MV_FAM_X3 || r.family == MV_FAM_F32;   // the whole pass in one launch per row tile: gbar_0, E.1, E.2, input adjoint
+    // ---- chains: E.1, the adjoint of the normal chain (ascending), and E.2, the adjoint of the value chain (descending) ----
+    if (r.family == MV_FAM_X3) {                                 // ... in the three-term bf16 arithmetic (chain_x3.h)
         ChainArgsX3 c;
-        memset(&c, 0, sizeof(c));
-        c.net = xn; c.netT = xnT; c.S = xn.S; c.M = Mb; c.row_ld0 = lo.ld0;
-        c.dy = dy; c.ld_dy = net.L[nl - 1].N; c.w_last_row0 = w8;
-        for (int l = 0; l < nl - 1; ++l) {
-            c.Z[l] = Zof(l); c.ZB[l] = ws + bl.ZB[l];
-            c.ZB2[l] = dn ? ws + bl.ZB2[l] : nullptr; c.ZB2o[l] = ws + bl.ZB2[l];
-            if (l + 1 < nl - 1) c.U[l + 1] = Uof(l + 1);
-            c.VB[l + 1] = ws + bl.VB[l + 1];
-        }
-        c.H0B = ws + bl.H0B; c.H0 = H0; c.G0 = G0; c.dn_in = dn; c.VB0w = ws + bl.VB[0]; c.dx = dx;
-        const size_t lds = (size_t)3 * 16 * xn.S * 2 + (size_t)16 * lo.d0 * sizeof(float);
-        const dim3 grid((Mb + 15) / 16);
-        if (ntw_b == 2) hipLaunchKernelGGL((k_chain_bwd_x3<1, 1, 16, MV_X3_PD1>), grid, dim3(1024), lds, s, c);
-        else hipLaunchKernelGGL((k_chain_bwd_x3<1, 2, 16>), grid, dim3(1024), lds, s, c);
-        MV_TRY(hipGetLastError());
-        chains_done = true;
-    }
-    else if (fuse_all >= 1 && ntw_b) {                          // MVSDF_SPLIT_CHAINS=1: the separate E.1 / E.2 launches (dev A/B)
+        fill_chain_args(c, net, xn, xnT, xn.S, lo, bl, ctx, row0, Mb, dy, dn, ws, dx, w8);
+        MV_TRY(launch_chain_bwd_x3(r, mv_blocks(Mb, r.mt), mv_lds_bwd_x3(r.mt, xn.S, lo.d0), s, c));
+    } else if (r.family == MV_FAM_F32) {                         // ... on the fp32-input MFMA
         ChainArgs c;
-        memset(&c, 0, sizeof(c));
-        c.net = net; c.netT = netT; c.S = S; c.M = Mb; c.row_ld0 = lo.ld0;
-        c.dy = dy; c.ld_dy = net.L[nl - 1].N; c.w_last_row0 = w8;
-        for (int l = 0; l < nl - 1; ++l) {
-            c.Z[l] = Zof(l); c.ZB[l] = ws + bl.ZB[l];
-            c.ZB2[l] = dn ? ws + bl.ZB2[l] : nullptr; c.ZB2o[l] = ws + bl.ZB2[l];
-            if (l + 1 < nl - 1) c.U[l + 1] = Uof(l + 1);
-            c.VB[l + 1] = ws + bl.VB[l + 1];
-        }
-        c.H0B = ws + bl.H0B; c.H0 = H0; c.G0 = G0; c.dn_in = dn; c.VB0w = ws + bl.VB[0]; c.dx = dx;
-        constexpr int MTC = 1, NWC = 8;
-        const size_t lds = (size_t)16 * MTC * (S + lo.d0) * sizeof(float);
-        const bool w8 = mv_chain_w8();
-        const dim3 grid((Mb + 16 * MTC - 1) / (16 * MTC));
-        if (ntw_b == 2 && !w8) hipLaunchKernelGGL((k_chain_bwd<MTC, 1, 16>), grid, dim3(1024), lds, s, c);
-        else if (ntw_b == 2) hipLaunchKernelGGL((k_chain_bwd<MTC, 2, NWC>), grid, dim3(64 * NWC), lds, s, c);
-        else if (!w8) hipLaunchKernelGGL((k_chain_bwd<MTC, 2, 16>), grid, dim3(1024), lds, s, c);
-        else hipLaunchKernelGGL((k_chain_bwd<MTC, 4, NWC>), grid, dim3(64 * NWC), lds, s, c);
-        MV_TRY(hipGetLastError());
-        chains_done = true;
-    }
-    if (!chains_done && sk == -2) return mv_fail(-4, "mvsdf_sdf_backward: several skip connections need the fused chain kernels (MVSDF_FUSE / MVSDF_SPLIT_CHAINS unset)");
-    // ---- E.1: adjoint of the normal chain (ascending) ----
-    if (dn && !chains_done) {
-        hipLaunchKernelGGL(k_pe_normal_bwd, dim3((Mb * (3 * net.multires + 1) + 255) / 256), dim3(256), 0, s, H0, lo.ld0, dn, Mb,
-                           net.multires, ws + bl.VB[0], lo.ld0, sk > 0 ? ws + bl.VB[sk] : nullptr, sk > 0 ? net.L[sk].K : 0,
-                           sk > 0 ? net.L[sk].K - lo.d0 : 0);
-        static int fuse1_env = -1;
-        if (fuse1_env < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse1_env = e ? atoi(e) : 1; }
-        const int ntw_1 = mv_chain_ntw(net);
-        if (fuse1_env && ntw_1) {                                // the whole ascending chain in one launch
-            ChainArgs c;
-            memset(&c, 0, sizeof(c));
-            c.net = net; c.netT = netT; c.S = S; c.M = Mb; c.row_ld0 = lo.ld0;
-            c.VB0 = ws + bl.VB[0]; c.w_last_row0 = w8;
-            for (int l = 0; l < nl - 1; ++l) {
-                c.Z[l] = Zof(l);
-                if (l + 1 < nl - 1) c.U[l + 1] = Uof(l + 1);
-                c.VB[l + 1] = ws + bl.VB[l + 1];
-                c.ZB2o[l] = ws + bl.ZB2[l];
-            }
-            constexpr int MTC = 1, NWC = 8;
-            const size_t lds = (size_t)16 * MTC * (S + lo.d0) * sizeof(float);
-            if (ntw_1 == 2) hipLaunchKernelGGL((k_chain_e1<MTC, 2, NWC>), dim3((Mb + 16 * MTC - 1) / (16 * MTC)), dim3(64 * NWC), lds, s, c);
-            else hipLaunchKernelGGL((k_chain_e1<MTC, 4, NWC>), dim3((Mb + 16 * MTC - 1) / (16 * MTC)), dim3(64 * NWC), lds, s, c);
-            MV_TRY(hipGetLastError());
-        } else
-        for (int l = 0; l < nl - 1; ++l) {
-            LayerArgs a = base_args(net.L[l], S, Mb);
-            a.A = ws + bl.VB[l]; a.lda = ldA(l);
-            a.Z = Zof(l); a.ldz = net.L[l].N;
-            if (l == nl - 2) { a.bcast = w8; a.bcast_sqrt2 = (sk == nl - 1); } else { a.U = Uof(l + 1); a.ldu = net.L[l].N; }
-            a.out0 = ws + bl.VB[l + 1]; a.ld0 = net.L[l + 1].K;
-            a.out1 = ws + bl.ZB2[l]; a.ld1 = net.L[l].N;
-            a.skip_next = (l + 1 == sk);
-            MV_TRY((launch_layer<PRO_PLAIN, EPI_SBAR>(a, s)));
-        }
-    }
-    // ---- E.2: adjoint of the value chain (descending) ----
-    if (!chains_done) {
-    static int fuse_env = -1;
-    if (fuse_env < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse_env = e ? atoi(e) : 1; }
-    const int ntw_2 = mv_chain_ntw(net);
-    if (fuse_env && ntw_2) {                                    // all layers in one launch, the running adjoint stays in LDS
-        ChainArgs c;
-        memset(&c, 0, sizeof(c));
-        c.net = net; c.netT = netT; c.S = S; c.M = Mb; c.row_ld0 = lo.ld0;
-        c.dy = dy; c.ld_dy = net.L[nl - 1].N;
-        for (int l = 0; l < nl - 1; ++l) { c.Z[l] = Zof(l); c.ZB2[l] = dn ? ws + bl.ZB2[l] : nullptr; c.ZB[l] = ws + bl.ZB[l]; }
-        c.H0B = ws + bl.H0B;
-        constexpr int MTC = 1, NWC = 8;
-        const size_t lds = (size_t)16 * MTC * (S + lo.d0) * sizeof(float);
-        if (ntw_2 == 2) hipLaunchKernelGGL((k_chain_e2<MTC, 2, NWC>), dim3((Mb + 16 * MTC - 1) / (16 * MTC)), dim3(64 * NWC), lds, s, c);
-        else hipLaunchKernelGGL((k_chain_e2<MTC, 4, NWC>), dim3((Mb + 16 * MTC - 1) / (16 * MTC)), dim3(64 * NWC), lds, s, c);
-        MV_TRY(hipGetLastError());
+        fill_chain_args(c, net, net, netT, S, lo, bl, ctx, row0, Mb, dy, dn, ws, dx, w8);
+        MV_TRY(launch_chain_bwd(r, mv_blocks(Mb, r.mt), mv_lds_bwd_f32(r.mt, S, lo.d0), s, c));
     } else {
-    int cur = 0;
-    {
-        LayerArgs a = base_args(netT.L[nl - 1], S, Mb);
-        a.A = dy; a.lda = net.L[nl - 1].N;
-        a.csplit = net.L[nl - 1].K; a.out0 = ws + bl.HB[cur]; a.ld0 = net.L[nl - 1].K;
-        if (sk == nl - 1) {                                                        // skip into the last Linear: hidden part / PE part, both / sqrt(2)
-            a.csplit = net.L[nl - 1].K - lo.d0; a.scale_sqrt2 = 1; a.ld0 = net.L[nl - 2].N;
-            a.out1 = ws + bl.H0B; a.ld1 = lo.ld0;
+        if (dn)
+            hipLaunchKernelGGL(k_pe_normal_bwd, dim3((Mb * (3 * net.multires + 1) + 255) / 256), dim3(256), 0, s, H0, lo.ld0, dn, Mb,
+                               net.multires, ws + bl.VB[0], lo.ld0, sk > 0 ? ws + bl.VB[sk] : nullptr, sk > 0 ? net.L[sk].K : 0,
+                               sk > 0 ? net.L[sk].K - lo.d0 : 0);
+        if (r.family == MV_FAM_SPLIT) {                          // MVSDF_SPLIT_CHAINS=1: each chain in one launch, the running adjoint stays in LDS (dev A/B)
+            ChainArgs c;
+            fill_chain_args(c, net, net, netT, S, lo, bl, ctx, row0, Mb, dy, dn, ws, dx, w8);
+            c.VB0 = ws + bl.VB[0];
+            const size_t lds = mv_lds_bwd_f32(r.mt, S, lo.d0);
+            if (dn) MV_TRY(launch_chain_e1(r, mv_blocks(Mb, r.mt), lds, s, c));
+            MV_TRY(launch_chain_e2(r, mv_blocks(Mb, r.mt), lds, s, c));
+        } else {                                                 // one k_layer launch per layer
+            if (dn)
+                for (int l = 0; l < nl - 1; ++l) {
+                    LayerArgs a = base_args(net.L[l], S, Mb);
+                    a.A = ws + bl.VB[l]; a.lda = ldA(l);
+                    a.Z = Zof(l); a.ldz = net.L[l].N;
+                    if (l == nl - 2) { a.bcast = w8; a.bcast_sqrt2 = (sk == nl - 1); } else { a.U = Uof(l + 1); a.ldu = net.L[l].N; }
+                    a.out0 = ws + bl.VB[l + 1]; a.ld0 = net.L[l + 1].K;
+                    a.out1 = ws + bl.ZB2[l]; a.ld1 = net.L[l].N;
+                    a.skip_next = (l + 1 == sk);
+                    MV_TRY((launch_layer<PRO_PLAIN, EPI_SBAR>(a, s)));
+                }
+            int cur = 0;
+            {
+                LayerArgs a = base_args(netT.L[nl - 1], S, Mb);
+                a.A = dy; a.lda = net.L[nl - 1].N;
+                a.csplit = net.L[nl - 1].K; a.out0 = ws + bl.HB[cur]; a.ld0 = net.L[nl - 1].K;
+                if (sk == nl - 1) {                                                    // skip into the last Linear: hidden part / PE part, both / sqrt(2)
+                    a.csplit = net.L[nl - 1].K - lo.d0; a.scale_sqrt2 = 1; a.ld0 = net.L[nl - 2].N;
+                    a.out1 = ws + bl.H0B; a.ld1 = lo.ld0;
+                }
+                MV_TRY((launch_layer<PRO_PLAIN, EPI_SPLIT>(a, s)));
+            }
+            if (sk <= 0) MV_TRY(hipMemsetAsync(ws + bl.H0B, 0, (size_t)Mb * lo.ld0 * sizeof(float), s));
+            for (int l = nl - 2; l >= 0; --l) {
+                LayerArgs a = base_args(netT.L[l], S, Mb);
+                a.Z = Zof(l); a.ldz = net.L[l].N;
+                a.U = ws + bl.HB[cur]; a.ldu = net.L[l].N;
+                if (dn) { a.A = ws + bl.ZB2[l]; a.lda = net.L[l].N; a.Mg = Mb; }
+                a.out2 = ws + bl.ZB[l]; a.ld2 = net.L[l].N;
+                if (l == sk) {
+                    a.csplit = net.L[l].K - lo.d0; a.scale_sqrt2 = 1;
+                    a.out0 = ws + bl.HB[cur ^ 1]; a.ld0 = net.L[l - 1].N;
+                    a.out1 = ws + bl.H0B; a.ld1 = lo.ld0;
+                } else if (l == 0) {
+                    a.csplit = net.L[0].K;
+                    a.add = ws + bl.H0B; a.ldadd = lo.ld0;
+                    a.out0 = ws + bl.H0B; a.ld0 = lo.ld0;
+                } else {
+                    a.csplit = net.L[l].K;
+                    a.out0 = ws + bl.HB[cur ^ 1]; a.ld0 = net.L[l - 1].N;
+                }
+                MV_TRY((launch_layer<PRO_ZBAR, EPI_SPLIT>(a, s)));
+                cur ^= 1;
+            }
         }
-        MV_TRY((launch_layer<PRO_PLAIN, EPI_SPLIT>(a, s)));
     }
-    if (sk <= 0) MV_TRY(hipMemsetAsync(ws + bl.H0B, 0, (size_t)Mb * lo.ld0 * sizeof(float), s));
-    for (int l = nl - 2; l >= 0; --l) {
-        LayerArgs a = base_args(netT.L[l], S, Mb);
-        a.Z = Zof(l); a.ldz = net.L[l].N;
-        a.U = ws + bl.HB[cur]; a.ldu = net.L[l].N;
-        if (dn) { a.A = ws + bl.ZB2[l]; a.lda = net.L[l].N; a.Mg = Mb; }
-        a.out2 = ws + bl.ZB[l]; a.ld2 = net.L[l].N;
-        if (l == sk) {
-            a.csplit = net.L[l].K - lo.d0; a.scale_sqrt2 = 1;
-            a.out0 = ws + bl.HB[cur ^ 1]; a.ld0 = net.L[l - 1].N;
-            a.out1 = ws + bl.H0B; a.ld1 = lo.ld0;
-        } else if (l == 0) {
-            a.csplit = net.L[0].K;
-            a.add = ws + bl.H0B; a.ldadd = lo.ld0;
-            a.out0 = ws + bl.H0B; a.ld0 = lo.ld0;
-        } else {
-            a.csplit = net.L[l].K;
-            a.out0 = ws + bl.HB[cur ^ 1]; a.ld0 = net.L[l - 1].N;
-        }
-        MV_TRY((launch_layer<PRO_ZBAR, EPI_SPLIT>(a, s)));
-        cur ^= 1;
-    }
-    }
-    }   // !chains_done
     // ---- weight / bias gradients: W_l = zbar_l^T a_l (+ s_l^T vbar_l), every layer in one launch + one reduction ----
     if (dW_cat) {                                                                  // dW_cat == NULL: input adjoint only
         WgradNetArgs wa;
@@ -684,7 +600,7 @@ int mvsdf_sdf_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const floa
         MV_TRY(launch_wgrad_net(wa, s));
     }
     // ---- E.3: input adjoint ----
-    if (dx && !chains_done)
+    if (dx && !whole)
         hipLaunchKernelGGL(k_pe_input_bwd, dim3((Mb * 3 + 255) / 256), dim3(256), 0, s, H0, lo.ld0, ws + bl.H0B, lo.ld0, G0, lo.ld0,
                            dn, Mb, net.multires, dx);
     return mv_check(hipGetLastError(), "mvsdf_sdf_backward");
@@ -693,24 +609,6 @@ int mvsdf_sdf_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const floa
 }  // extern "C"
 
 // ---- the training step's SDF backward as two launches of chain passes instead of three sequential ones (functional._IdrStep.backward) ----
-// fill the arguments of one fused chain pass over rows [row0, row0 + Mb) of a forward context
-template <class NETX>
-static void fill_chain_args(ChainArgsT<NETX>& c, const MvNet& net, const NETX& xnet, const NETX& xnetT, int S, const SdfLayout& lo, const SdfBwdLayout& bl, const float* ctx,
-                            int row0, int Mb, const float* dy, const float* dn, float* ws, float* dx, const float* w8) {
-    memset(&c, 0, sizeof(c));
-    const int nl = lo.nl;
-    const size_t r0 = (size_t)row0;
-    c.net = xnet; c.netT = xnetT; c.S = S; c.M = Mb; c.row_ld0 = lo.ld0;
-    c.dy = dy; c.ld_dy = net.L[nl - 1].N; c.w_last_row0 = w8;
-    for (int l = 0; l < nl - 1; ++l) {
-        c.Z[l] = ctx + lo.Z[l] + r0 * net.L[l].N; c.ZB[l] = ws + bl.ZB[l];
-        c.ZB2[l] = dn ? ws + bl.ZB2[l] : nullptr; c.ZB2o[l] = ws + bl.ZB2[l];
-        if (l + 1 < nl - 1) c.U[l + 1] = ctx + lo.U[l + 1] + r0 * net.L[l].N;
-        c.VB[l + 1] = ws + bl.VB[l + 1];
-    }
-    c.H0B = ws + bl.H0B; c.H0 = ctx + lo.H0 + r0 * lo.ld0; c.G0 = ctx + lo.G0 + r0 * lo.ld0; c.dn_in = dn; c.VB0w = ws + bl.VB[0]; c.dx = dx;
-}
-
 extern "C" {
 
 /* Pass A: full first/second-order backward over rows [0, MbA) with upstream (dyA, dnA); keeps every per-layer adjoint in wsA
@@ -732,62 +630,36 @@ int mv_sdf_backward_pair_cnt(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int 
                              int row0X, int MbX, const float* dyX, const float* dnX, float* wsX, float* dx, const float* ctx, const long long* cnt, int n_hint,
                              void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net(d, &net);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 0, &net, &netT);
     if (rc) return rc;
     if (!dyA || !dnA || !wsA || !dyX || !wsX || !dx || !ctx || MbA <= 0 || MbX <= 0 || MbA > Mg || row0X < 0 || row0X + MbX > Mg || Mg > M)
         return mv_fail(-1, "mvsdf_sdf_backward_pair: bad arguments");
     if (cnt && row0X + MbX != MbA) return mv_fail(-1, "mv_sdf_backward_pair_cnt: the bounds of the two passes must end on the same row");
     if (n_hint < 0 || n_hint > MbX) n_hint = MbX;
     const int tiles_hint = cnt ? (row0X + n_hint + 15) / 16 + (n_hint + 15) / 16 : (MbA + 15) / 16 + (MbX + 15) / 16;
-    const int ntw_b = mv_chain_ntw(net);
-    if (!ntw_b) return mv_fail(-3, "mvsdf_sdf_backward_pair: network too wide for the fused chain kernels");
+    const int ntw = mv_chain_ntw(net);
+    MvNetBf xn, xnT;
+    MvRoute r = mv_route_sdf_backward_pair(ntw, tiles_hint, true, mv_dev_switches());
+    if (r.family == MV_FAM_REFUSE) return mv_fail(r.rc, "mvsdf_sdf_backward_pair: network too wide for the fused chain kernels");
     const float* w8 = d->w[net.n_layers - 1];
     if (!w8) return mv_fail(-1, "mvsdf_sdf_backward_pair: row-major last-layer weights missing");
+    if (r.family == MV_FAM_X3 && mv_x3_nets(d, dT, true, &xn, &xnT)) r = mv_route_sdf_backward_pair(ntw, tiles_hint, false, mv_dev_switches());
     hipStream_t s = (hipStream_t)stream;
     const SdfLayout lo = sdf_ctx_layout(net, M, Mg);
-    const int S = stride_for(net, netT);
-    MvNetBf xn, xnT;
-    if (net.n_layers >= 2 && !mv_x3_nets(d, dT, true, &xn, &xnT)) {                 // both passes in the three-term bf16 arithmetic (chain_x3.h)
+    const int na = mv_blocks(MbA, r.mt), nb = mv_blocks(MbX, r.mt);
+    if (r.family == MV_FAM_X3) {                                 // both passes in the three-term bf16 arithmetic (chain_x3.h)
         ChainArgsX3 a, b;
         fill_chain_args(a, net, xn, xnT, xn.S, lo, sdf_bwd_layout(net, MbA), ctx, 0, MbA, dyA, dnA, wsA, nullptr, w8);
         fill_chain_args(b, net, xn, xnT, xn.S, lo, sdf_bwd_layout(net, MbX), ctx, row0X, MbX, dyX, dnX, wsX, dx, w8);
         a.cnt = b.cnt = cnt; a.cnt_base = row0X; b.cnt_base = 0;
-        const int mt = mv_chain_mt_x3(tiles_hint);
-        const size_t lds = (size_t)3 * 16 * mt * xn.S * 2 + (size_t)16 * mt * lo.d0 * sizeof(float);
-        const int na = (MbA + 16 * mt - 1) / (16 * mt), nb = (MbX + 16 * mt - 1) / (16 * mt);
-        const dim3 grid(na + nb);
-        if (mt == 2 && ntw_b == 4) {
-            { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_bwd2_x3<2, 4, 8>, lds, hw)); }
-            hipLaunchKernelGGL((k_chain_bwd2_x3<2, 4, 8>), grid, dim3(512), lds, s, a, b, na);
-        }
-        else if (mt == 2) {
-            { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_bwd2_x3<2, 1, 16, MV_X3_PD2>, lds, hw)); }
-            hipLaunchKernelGGL((k_chain_bwd2_x3<2, 1, 16, MV_X3_PD2>), grid, dim3(1024), lds, s, a, b, na);
-        }
-        else if (ntw_b == 2) hipLaunchKernelGGL((k_chain_bwd2_x3<1, 1, 16, MV_X3_PD1>), grid, dim3(1024), lds, s, a, b, na);
-        else hipLaunchKernelGGL((k_chain_bwd2_x3<1, 2, 16>), grid, dim3(1024), lds, s, a, b, na);
-        return mv_check(hipGetLastError(), "mvsdf_sdf_backward_pair (x3 chains)");
+        return mv_check(launch_chain_bwd2_x3(r, na + nb, mv_lds_bwd_x3(r.mt, xn.S, lo.d0), s, a, b, na), "mvsdf_sdf_backward_pair (x3 chains)");
     }
+    const int S = stride_for(net, netT);
     ChainArgs a, b;
     fill_chain_args(a, net, net, netT, S, lo, sdf_bwd_layout(net, MbA), ctx, 0, MbA, dyA, dnA, wsA, nullptr, w8);
     fill_chain_args(b, net, net, netT, S, lo, sdf_bwd_layout(net, MbX), ctx, row0X, MbX, dyX, dnX, wsX, dx, w8);
     a.cnt = b.cnt = cnt; a.cnt_base = row0X; b.cnt_base = 0;
-    const bool w8w = mv_chain_w8();
-    const int mt = (ntw_b == 2 && !w8w) ? mv_chain_mt(tiles_hint) : 1;
-    const size_t lds = (size_t)16 * mt * (S + lo.d0) * sizeof(float);
-    const int na = (MbA + 16 * mt - 1) / (16 * mt), nb = (MbX + 16 * mt - 1) / (16 * mt);
-    const dim3 grid(na + nb);
-    if (mt == 2) {
-        { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_bwd2<2, 1, 16>, lds, hw)); }
-        hipLaunchKernelGGL((k_chain_bwd2<2, 1, 16>), grid, dim3(1024), lds, s, a, b, na);
-    }
-    else if (ntw_b == 2 && !w8w) hipLaunchKernelGGL((k_chain_bwd2<1, 1, 16>), grid, dim3(1024), lds, s, a, b, na);
-    else if (ntw_b == 2) hipLaunchKernelGGL((k_chain_bwd2<1, 2, 8>), grid, dim3(512), lds, s, a, b, na);
-    else if (!w8w) hipLaunchKernelGGL((k_chain_bwd2<1, 2, 16>), grid, dim3(1024), lds, s, a, b, na);
-    else hipLaunchKernelGGL((k_chain_bwd2<1, 4, 8>), grid, dim3(512), lds, s, a, b, na);
-    return mv_check(hipGetLastError(), "mvsdf_sdf_backward_pair");
+    return mv_check(launch_chain_bwd2(r, na + nb, mv_lds_bwd_f32(r.mt, S, lo.d0), s, a, b, na), "mvsdf_sdf_backward_pair");
 }
 
 // delta pass of the training step's SDF backward: extra upstream fbar[MbD] on output column 0 of rows [row0D, row0D + MbD); its first-order zbar_l
@@ -837,29 +709,30 @@ __global__ __launch_bounds__(256) void k_delta_apply(DeltaArgs a) {
     float* zb = a.ZB[l] + (size_t)row * N;
     for (int c = threadIdx.x; c < N; c += 256) zb[c] = zb[c] + f * sg[c];
 }
-static int mv_delta_chain() {
-    static int v = -1;
-    if (v < 0) { const char* e = mv_dev_env("MVSDF_DELTA_CHAIN"); v = e ? atoi(e) : 0; }
-    return v;
+// the layers' saved s_l and stored zbar_l of the hit rows [row0D, row0D + MbD)
+static void fill_delta_args(DeltaArgs& d, const MvNet& net, const SdfLayout& lo, const SdfBwdLayout& bl, const float* ctx, float* ws, int row0D, int MbD) {
+    memset(&d, 0, sizeof(d));
+    d.nl1 = lo.nl - 1; d.rows = MbD;
+    for (int l = 0; l < lo.nl - 1; ++l) {
+        d.N[l] = net.L[l].N;
+        d.Sg[l] = ctx + lo.Sg[l] + (size_t)row0D * net.L[l].N;
+        d.ZB[l] = ws + bl.ZB[l] + (size_t)row0D * net.L[l].N;
+    }
 }
-int mv_delta_is_chain() { return mv_delta_chain(); }
 
 static int sdf_delta_pass(const MvNet& net, const MvNet& netT, const SdfLayout& lo, const SdfBwdLayout& bl, const float* ctx, float* ws, int row0D,
                           int MbD, const float* fbar, hipStream_t s) {
-    if (!mv_delta_chain()) {
+    const MvRoute r = mv_route_delta(mv_chain_ntw(net), (MbD + 15) / 16, false, mv_dev_switches());
+    if (r.family == MV_FAM_REFUSE) return mv_fail(r.rc, "sdf_delta_pass: network too wide for the fused chain kernels");   // (both callers have said so already)
+    if (r.family == MV_FAM_SCALE) {
         DeltaArgs d;
-        memset(&d, 0, sizeof(d));
-        d.nl1 = lo.nl - 1; d.rows = MbD; d.fbar = fbar;
-        for (int l = 0; l < lo.nl - 1; ++l) {
-            d.N[l] = net.L[l].N;
-            d.Sg[l] = ctx + lo.Sg[l] + (size_t)row0D * net.L[l].N;
-            d.ZB[l] = ws + bl.ZB[l] + (size_t)row0D * net.L[l].N;
-        }
+        fill_delta_args(d, net, lo, bl, ctx, ws, row0D, MbD);
+        d.fbar = fbar;
         hipLaunchKernelGGL(k_delta_apply<false>, dim3(MbD, lo.nl - 1), dim3(256), 0, s, d);
         return mv_check(hipGetLastError(), "sdf_delta_pass");
     }
-    // MVSDF_DELTA_CHAIN=1: the first-order chain (the form this replaced; kept as the cross-check of tests/test_gpu_diff.py)
-    const int ntw_b = mv_chain_ntw(net);
+    // MVSDF_DELTA_CHAIN=1: the first-order chain (the form this replaced; kept as the cross-check of tests/test_gpu_diff.py).  Not a fill_chain_args site: E.2
+    // alone over the hit rows of a workspace laid out for all of them, accumulating
     const int nl = lo.nl, S = stride_for(net, netT);
     ChainArgs c;
     memset(&c, 0, sizeof(c));
@@ -867,19 +740,7 @@ static int sdf_delta_pass(const MvNet& net, const MvNet& netT, const SdfLayout& 
     c.net = net; c.netT = netT; c.S = S; c.M = MbD; c.row_ld0 = lo.ld0;
     c.ld_dy = net.L[nl - 1].N; c.dy_col0 = fbar; c.accum = 1;
     for (int l = 0; l < nl - 1; ++l) { c.Z[l] = ctx + lo.Z[l] + r0 * net.L[l].N; c.ZB[l] = ws + bl.ZB[l] + r0 * net.L[l].N; }
-    const bool w8w = mv_chain_w8();
-    const int mt = (ntw_b == 2 && !w8w) ? mv_chain_mt((MbD + 15) / 16) : 1;
-    const size_t lds = (size_t)16 * mt * (S + lo.d0) * sizeof(float);
-    const dim3 grid((MbD + 16 * mt - 1) / (16 * mt));
-    if (mt == 2) {
-        { static size_t hw = 0; MV_TRY(mv_lds_limit(k_chain_bwd<2, 1, 16>, lds, hw)); }
-        hipLaunchKernelGGL((k_chain_bwd<2, 1, 16>), grid, dim3(1024), lds, s, c);
-    }
-    else if (ntw_b == 2 && !w8w) hipLaunchKernelGGL((k_chain_bwd<1, 1, 16>), grid, dim3(1024), lds, s, c);
-    else if (ntw_b == 2) hipLaunchKernelGGL((k_chain_bwd<1, 2, 8>), grid, dim3(512), lds, s, c);
-    else if (!w8w) hipLaunchKernelGGL((k_chain_bwd<1, 2, 16>), grid, dim3(1024), lds, s, c);
-    else hipLaunchKernelGGL((k_chain_bwd<1, 4, 8>), grid, dim3(512), lds, s, c);
-    return mv_check(hipGetLastError(), "sdf_delta_pass");
+    return mv_check(launch_chain_bwd(r, mv_blocks(MbD, r.mt), mv_lds_bwd_f32(r.mt, S, lo.d0), s, c), "sdf_delta_pass");
 }
 
 // operands of the SDF net's weight gradients (layers a.L[l0 ...]) from the adjoints pass A (+ delta) left in `ws`
@@ -905,9 +766,7 @@ extern "C" {
 int mvsdf_sdf_backward_finish(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int M, int Mg, int Mb, const float* dy, const float* ctx, float* ws,
                               int row0D, int MbD, const float* fbar, float* dW_cat, float* db_cat, void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net(d, &net);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 0, &net, &netT);
     if (rc) return rc;
     if (!dy || !ctx || !ws || !dW_cat || !db_cat || Mb <= 0 || Mb > Mg || Mg > M || MbD < 0 || row0D < 0 || row0D + MbD > Mb || (MbD > 0 && !fbar))
         return mv_fail(-1, "mvsdf_sdf_backward_finish: bad arguments");
@@ -1000,25 +859,15 @@ int mvsdf_render_forward(const MvsdfNetDesc* d, const float* points, const float
         return mv_fail(-1, "mvsdf_render_forward: first layer too narrow for cat[points, PE(view), normals, feat]");
     hipStream_t s = (hipStream_t)stream;
     const RenderLayout lo = render_layout(net, N);
-    static int fuse_r = -1;
-    if (fuse_r < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse_r = e ? atoi(e) : 1; }
-    const int ntw_r = mv_chain_ntw(net);
-    if (fuse_r && ntw_r && net.L[nl - 1].NT <= 2) {                                // the whole network in one launch per row tile
+    const MvRoute r = mv_route_render_forward(mv_chain_ntw(net), net.L[nl - 1].NT, mv_dev_switches());
+    if (r.family == MV_FAM_F32) {                                                  // the whole network in one launch per row tile
         RenderChainArgs c;
         memset(&c, 0, sizeof(c));
         c.net = net; c.S = net.S; c.N = N; c.mv = multires_view; c.K0 = K0;
         c.points = points; c.view = view; c.normals = normals; c.feat = feat; c.ldfeat = ldfeat;
         for (int l = 0; l < nl; ++l) c.A[l] = ctx + lo.A[l];
         c.rgb_ctx = ctx + lo.rgb; c.rgb = rgb;
-        constexpr int MTC = 1, NWC = 8;
-        const bool w8 = mv_chain_w8();
-        const dim3 grid((N + 16 * MTC - 1) / (16 * MTC));
-        const size_t ldsr = (size_t)16 * MTC * net.S * sizeof(float);
-        if (ntw_r == 2 && !w8) hipLaunchKernelGGL((k_render_chain_fwd<MTC, 1, 16>), grid, dim3(1024), ldsr, s, c);
-        else if (ntw_r == 2) hipLaunchKernelGGL((k_render_chain_fwd<MTC, 2, NWC>), grid, dim3(64 * NWC), ldsr, s, c);
-        else if (!w8) hipLaunchKernelGGL((k_render_chain_fwd<MTC, 2, 16>), grid, dim3(1024), ldsr, s, c);
-        else hipLaunchKernelGGL((k_render_chain_fwd<MTC, 4, NWC>), grid, dim3(64 * NWC), ldsr, s, c);
-        return mv_check(hipGetLastError(), "mvsdf_render_forward");
+        return mv_check(launch_render_chain_fwd(r, mv_blocks(N, 1), mv_lds_render(net.S), s, c), "mvsdf_render_forward");
     }
     const size_t tot = (size_t)N * K0;
     hipLaunchKernelGGL(k_render_input, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, points, view, normals, feat, ldfeat, N,
@@ -1036,34 +885,29 @@ int mvsdf_render_forward(const MvsdfNetDesc* d, const float* points, const float
 
 }  // extern "C"
 
+// the most 16-column tiles of a transposed layer above the first: what a wave of the rendering net's fused backward must cover (diff_route.h)
+static int mv_render_upper_nt(const MvNet& netT) {
+    int nt = 0;
+    for (int l = 1; l < netT.n_layers; ++l) nt = netT.L[l].NT > nt ? netT.L[l].NT : nt;
+    return nt;
+}
 // the descending chain of the rendering net's backward: drgb[N][3] -> per-layer adjoints in `ws` + din[N][K0]
 static int render_backward_chain(const MvNet& net, const MvNet& netT, int N, int Nctx, const float* drgb, const float* ctx, float* din, float* ws,
                                  hipStream_t s, const long long* drgb_rows = nullptr, const long long* cnt = nullptr) {
     const int nl = net.n_layers, S = stride_for(net, netT);
     const RenderLayout lo = render_layout(net, Nctx);        // the forward context holds Nctx rows; the backward covers the first N
     const RenderBwdLayout bl = render_bwd_layout(net, N);
-    static int fuse_rb = -1;
-    if (fuse_rb < 0) { const char* e = mv_dev_env("MVSDF_FUSE"); fuse_rb = e ? atoi(e) : 1; }
-    const int ntw_rb = mv_chain_ntw(net);
-    bool fused_bwd = fuse_rb && ntw_rb;
-    for (int l = 1; l < nl; ++l) fused_bwd = fused_bwd && netT.L[l].NT <= 8 * ntw_rb;   // one column-tile group per wave above the first layer
-    if (fused_bwd) {
+    const MvRoute r = mv_route_render_backward(mv_chain_ntw(net), mv_render_upper_nt(netT), drgb_rows || cnt, mv_dev_switches());
+    if (r.family == MV_FAM_REFUSE) return mv_fail(r.rc, "render_backward_chain: row indirection / device-side counts need the fused chain kernel");
+    if (r.family == MV_FAM_F32) {
         RenderChainArgs c;
         memset(&c, 0, sizeof(c));
         c.net = net; c.netT = netT; c.S = S; c.N = N; c.K0 = net.L[0].K;
         c.drgb = drgb; c.rgbc = ctx + lo.rgb; c.din = din; c.drgb_rows = drgb_rows; c.cnt = cnt;
         for (int l = 0; l < nl; ++l) { c.Ac[l] = ctx + lo.A[l]; c.ZB[l] = ws + bl.ZB[l]; }
-        constexpr int MTC = 1, NWC = 8;
-        const bool w8 = mv_chain_w8();
-        const dim3 grid((N + 16 * MTC - 1) / (16 * MTC));
-        const size_t ldsr = (size_t)16 * MTC * S * sizeof(float);
-        if (ntw_rb == 2 && !w8) hipLaunchKernelGGL((k_render_chain_bwd<MTC, 1, 16>), grid, dim3(1024), ldsr, s, c);
-        else if (ntw_rb == 2) hipLaunchKernelGGL((k_render_chain_bwd<MTC, 2, NWC>), grid, dim3(64 * NWC), ldsr, s, c);
-        else if (!w8) hipLaunchKernelGGL((k_render_chain_bwd<MTC, 2, 16>), grid, dim3(1024), ldsr, s, c);
-        else hipLaunchKernelGGL((k_render_chain_bwd<MTC, 4, NWC>), grid, dim3(64 * NWC), ldsr, s, c);
-        MV_TRY(hipGetLastError());
-    } else {
-    if (drgb_rows || cnt) return mv_fail(-3, "render_backward_chain: row indirection / device-side counts need the fused chain kernel");
+        MV_TRY(launch_render_chain_bwd(r, mv_blocks(N, 1), mv_lds_render(S), s, c));
+        return 0;
+    }
     for (int l = nl - 1; l >= 0; --l) {                      // abar_l = zbar_l W_l ; zbar_{l-1} = abar_l . relu'(z_{l-1})
         LayerArgs a = base_args(netT.L[l], S, N);
         const bool last = (l == nl - 1);
@@ -1077,7 +921,6 @@ static int render_backward_chain(const MvNet& net, const MvNet& netT, int N, int
             a.csplit = net.L[0].K; a.out0 = din; a.ld0 = net.L[0].K;
             if (last) MV_TRY((launch_layer<PRO_TANH_BWD, EPI_SPLIT>(a, s))); else MV_TRY((launch_layer<PRO_PLAIN, EPI_SPLIT>(a, s)));
         }
-    }
     }
     return 0;
 }
@@ -1097,9 +940,7 @@ extern "C" {
 int mvsdf_render_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int N, int Nctx, const float* drgb, const float* ctx, float* dW_cat,
                           float* db_cat, float* din, float* ws, void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net_mode(d, &net, 1);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 1, &net, &netT);
     if (rc) return rc;
     if (!drgb || !ctx || !dW_cat || !db_cat || !din || !ws || N <= 0 || Nctx < N) return mv_fail(-1, "mvsdf_render_backward: bad arguments");
     hipStream_t s = (hipStream_t)stream;
@@ -1123,9 +964,7 @@ int mvsdf_render_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int N, 
 int mv_render_backward_chain(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int N, int Nctx, const float* drgb, const long long* drgb_rows, const float* ctx,
                              float* din, float* ws, const long long* cnt, void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net_mode(d, &net, 1);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 1, &net, &netT);
     if (rc) return rc;
     if (!drgb || !ctx || !din || !ws || N <= 0 || Nctx < N) return mv_fail(-1, "mv_render_backward_chain: bad arguments");
     rc = render_backward_chain(net, netT, N, Nctx, drgb, ctx, din, ws, (hipStream_t)stream, drgb_rows, cnt);
@@ -1135,9 +974,7 @@ int mv_render_backward_chain(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int 
 int mv_sdf_backward_delta(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int M, int Mg, int Mb, const float* ctx, float* ws, int row0D, int MbD,
                           const float* fbar, void* stream) {
     MvNet net, netT;
-    int rc = mv_make_net(d, &net);
-    if (rc) return rc;
-    rc = mv_make_net_mode(dT, &netT, 2);
+    int rc = mv_open_nets(d, dT, 0, &net, &netT);
     if (rc) return rc;
     if (!ctx || !ws || !fbar || Mb <= 0 || Mb > Mg || Mg > M || MbD <= 0 || row0D < 0 || row0D + MbD > Mb) return mv_fail(-1, "mv_sdf_backward_delta: bad arguments");
     if (!mv_chain_ntw(net)) return mv_fail(-3, "mv_sdf_backward_delta: network too wide for the fused chain kernels");
@@ -1157,13 +994,7 @@ int mv_sdf_backward_delta_fbar(const MvsdfNetDesc* d, int M, int Mg, int Mb, con
     const SdfLayout lo = sdf_ctx_layout(net, M, Mg);
     const SdfBwdLayout bl = sdf_bwd_layout(net, Mb);
     DeltaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nl1 = lo.nl - 1; a.rows = MbD;
-    for (int l = 0; l < lo.nl - 1; ++l) {
-        a.N[l] = net.L[l].N;
-        a.Sg[l] = ctx + lo.Sg[l] + (size_t)row0D * net.L[l].N;
-        a.ZB[l] = ws + bl.ZB[l] + (size_t)row0D * net.L[l].N;
-    }
+    fill_delta_args(a, net, lo, bl, ctx, ws, row0D, MbD);
     a.d_diff = d_diff; a.din = din; a.dx = dx; a.view_sorted = view_sorted; a.n_hit = n_eval + 3 * (size_t)row0D;
     a.din_ld = din_ld; a.use_geo = use_geo; a.Nout = Nout; a.dy_hit = dy + (size_t)row0D * Nout; a.fbar_out = fbar; a.cnt = cnt;
     hipLaunchKernelGGL(k_delta_apply<true>, dim3(MbD), dim3(256), 0, (hipStream_t)stream, a);
@@ -1214,13 +1045,8 @@ int mv_step_wgrad(const MvsdfNetDesc* sd, const MvsdfNetDesc* rd, int M, int Mg,
 // numbers: a step on such a network waits for the counts as before.)
 int mv_step_can_defer(const MvsdfNetDesc* sdf, const MvsdfNetDesc* sdfT, const MvsdfNetDesc* rnd, const MvsdfNetDesc* rndT) {
     MvNet net, netT, rnet, rnetT;
-    if (mv_make_net(sdf, &net) || mv_make_net_mode(sdfT, &netT, 2) || mv_make_net_mode(rnd, &rnet, 1) || mv_make_net_mode(rndT, &rnetT, 2)) return 0;
-    if (!mv_chain_ntw(net) || mv_delta_chain()) return 0;
-    const char* e = mv_dev_env("MVSDF_FUSE");
-    if (e && atoi(e) == 0) return 0;
-    const int ntw_rb = mv_chain_ntw(rnet);
-    if (!ntw_rb) return 0;
-    for (int l = 1; l < rnet.n_layers; ++l) if (rnetT.L[l].NT > 8 * ntw_rb) return 0;
+    if (mv_open_nets(sdf, sdfT, 0, &net, &netT) || mv_open_nets(rnd, rndT, 1, &rnet, &rnetT)) return 0;
+    if (!mv_route_can_defer(mv_chain_ntw(net), mv_chain_ntw(rnet), mv_render_upper_nt(rnetT), mv_dev_switches())) return 0;
     return net.n_layers + rnet.n_layers <= MV_WG_MAXL ? 1 : 0;
 }
 

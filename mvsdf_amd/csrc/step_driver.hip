@@ -150,7 +150,7 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     L.object_mask_out = take((size_t)R);
     fo.trace_ws_bytes = mvsdf_trace_workspace_bytes_n(R, d.tp.n_steps);
     fo.trace_ws = take(fo.trace_ws_bytes);
-    fo.chain_x3 = mv_chain_x3_enabled();
+    fo.chain_x3 = mv_dev_switches().chain_x3;
     for (int l = 0; l < nl; ++l) {
         fo.w[l] = take((size_t)d.N[l] * d.K[l] * 4);
         fo.wp[l] = take(mvsdf_packed_floats(d.N[l], d.K[l]) * 4);
@@ -568,7 +568,7 @@ static int step_backward_impl(void* step, const MvsdfStepParams* prm, int N, int
                 // weight gradients of BOTH networks in one k_wgrad_net / k_reduce_net pair.  (Round 3 ran the chunks that do not depend on fbar on a
                 // second stream beside a 9-phase delta chain; with the delta reduced to ~10 us the split measured no gain and is gone.)
                 float* fbar = (float*)(bwd + bo.fbar);
-                if (mv_delta_is_chain() && !cnt) {                                      // MVSDF_DELTA_CHAIN=1: the cross-check route
+                if (mv_dev_switches().delta_chain && !cnt) {                                      // MVSDF_DELTA_CHAIN=1: the cross-check route
                     ST_TRY(mvsdf_step_backward_fbar(d.n_eik, d.n_ds, N, Nout, din, st->K0r, use_geo, d_diff, dx, view_sorted, n_eval, dy, fbar, stream));
                     ST_TRY(mv_sdf_backward_delta(&sdf, &sdfT, M, M, Mb, ctx, wsA, E, N, fbar, stream));
                 } else {

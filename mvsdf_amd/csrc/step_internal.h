@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/mvsdf_hip.h"
+#include "diff_route.h"
 
 // optional row source of k_chain_fwd: the training step's evaluation rows [eikonal samples | on-surface samples | jittered samples | traced points of the
 // rays in sorted order] gathered on the fly (and written to x_out for the later consumers) instead of by a separate launch
@@ -44,7 +45,6 @@ int mv_chain_split_pays(const MvsdfNetDesc* d, int E, int M);
 // drgb_rows (may be NULL): sorted row r takes its upstream from drgb[drgb_rows[r]]; -3 when that needs the fused chain kernel and it does not apply
 int mv_render_backward_chain(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int N, int Nctx, const float* drgb, const long long* drgb_rows, const float* ctx,
                              float* din, float* ws, const long long* cnt, void* stream);
-int mv_delta_is_chain();                                       // MVSDF_DELTA_CHAIN=1
 int mv_sdf_backward_delta_fbar(const MvsdfNetDesc* d, int M, int Mg, int Mb, const float* ctx, float* ws, int row0D, int MbD, int Nout, const float* din,
                                int din_ld, int use_geo, const float* d_diff, const float* dx, const float* view_sorted, const float* n_eval, float* dy,
                                float* fbar, const long long* cnt, void* stream);
@@ -62,7 +62,7 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
                      float* stage_b, int stage_nb, void* stream);   // stage_src (optional): device-visible pinned host memory [na | nb] -> stage_a, stage_b
                                                                     // wx3 / wx3T (optional, per layer, entries may be null): the three-term bf16 packs of W_l / W_l^T
                                                                     // of the differentiable chains (chain_x3.h; layouts of mvsdf_pack_bf16x3_net / _bf16x3t_net)
-int mv_chain_x3_enabled();                                          // the fused SDF chains run in the three-term bf16 arithmetic when the packs exist (dev: MVSDF_CHAIN_X3=0)
+const MvDevSwitches& mv_dev_switches();                            // the development switches of diff_mlp.hip (diff_route.h), read once per process
 // stage 1 of mvsdf_trace_stage for a caller whose previous launch (mv_step_prologue) zeroed the counters
 extern "C" int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
