@@ -637,6 +637,28 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
 int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, int64_t npairs, void* ws, size_t ws_bytes, double* points,
                       uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
 
+/* ---- TSDF fusion (tsdf.hip; Python: mvsdf_amd/tsdf.py, which states the definition) ----
+ * mvsdf_tsdf_integrate validates every argument on the host, then (no host wait) writes tsdf fp32, weight int32 and valid uint8, each
+ * [dims[0]][dims[1]][dims[2]] on the device, and leaves int64 {0, error bits} at the start of the workspace.  Error bits: 1 a non-finite matrix,
+ * origin, voxel or trunc, or a NaN jump; 2 a view index outside [0, V); 4 voxel <= 0, trunc <= 0, jump < 0 or min_views < 1; 8 shapes (V < 1, H or
+ * W < 2, H*W > INT32_MAX, nviews < 1, a dim below 2 or above INT32_MAX, more than 2^40 lattice points); with any set nothing is launched.
+ * depths fp32 [V][H][W] on the device (a texel that is <= 0 or not finite is a hole); mats: HOST fp64 [nviews][16], P of the q-th visited view
+ * (row-major 4x4); views: HOST int32 [nviews], the depth map of the q-th visited view; origin: HOST fp64 [3]; dims: HOST int64 [3].  The host
+ * arrays must stay alive until the caller has read the header.
+ * Marching cubes under a validity mask (conventions: mvsdf_amd/mesh.py): like mvsdf_mc_count / mvsdf_mc_emit with valid uint8
+ * [shape[0]][shape[1]][shape[2]] (contiguous) beside the volume; the workspace starts with int64 {vertices, faces, non-finite VALID value seen}.
+ * workspace bytes: 6 per grid point + O(points / 1024); 0 = refused. */
+size_t mvsdf_tsdf_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t nviews);
+int mvsdf_tsdf_integrate(const float* depths, int64_t V, int64_t H, int64_t W, const double* mats, const int32_t* views, int64_t nviews,
+                         const double* origin, double voxel, const int64_t* dims, double trunc, double jump, int32_t min_views, void* ws,
+                         size_t ws_bytes, float* tsdf, int32_t* weight, uint8_t* valid, void* stream);
+size_t mvsdf_mcm_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int mvsdf_mcm_count(const float* vol, const uint8_t* valid, const int64_t* shape, const int64_t* strides, float level, void* ws, size_t ws_bytes,
+                    void* stream);
+int mvsdf_mcm_emit(const float* vol, const uint8_t* valid, const int64_t* shape, const int64_t* strides, float level, const float* spacing,
+                   const float* origin, void* ws, size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap,
+                   void* stream);
+
 /* ---- Plane-sweep stereo (stereo.hip; Python: mvsdf_amd/stereo.py, which states the definition) ----
  * mvsdf_stereo_normalize: feats fp32 [n][C] on the device -> out fp32 [n][C], every texel divided by its fp64 norm (0 where the norm is 0); hdr: 16
  * device bytes that receive int64 {0, error bits} (bit 1: a non-finite feature).  mvsdf_stereo_patches: images uint8 [V][H][W][3] -> out fp32

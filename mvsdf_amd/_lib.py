@@ -94,6 +94,13 @@ def lib():
         L.mvsdf_fusion_workspace_bytes.argtypes = [i64] * 4
         L.mvsdf_fusion_fuse.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, f64, f64, vp, sz, vp, vp, vp, vp]
         L.mvsdf_fusion_emit.argtypes = [vp, i64, i64, i64, i64, vp, sz, vp, vp, vp, vp, i64, vp]
+        L.mvsdf_tsdf_workspace_bytes.restype = sz
+        L.mvsdf_tsdf_workspace_bytes.argtypes = [i64] * 4
+        L.mvsdf_tsdf_integrate.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, f64, vp, f64, f64, i32, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_mcm_workspace_bytes.restype = sz
+        L.mvsdf_mcm_workspace_bytes.argtypes = [i64] * 3
+        L.mvsdf_mcm_count.argtypes = [vp, vp, vp, vp, f32, vp, sz, vp]
+        L.mvsdf_mcm_emit.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, sz, vp, vp, vp, i64, i64, vp]
         for fn in ('mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes'):
             getattr(L, fn).restype = sz
             getattr(L, fn).argtypes = [i64]
@@ -171,6 +178,7 @@ EXPORTS = [
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
     'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit',
+    'mvsdf_tsdf_workspace_bytes', 'mvsdf_tsdf_integrate', 'mvsdf_mcm_workspace_bytes', 'mvsdf_mcm_count', 'mvsdf_mcm_emit',
     'mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes', 'mvsdf_cloud_knn', 'mvsdf_cloud_components', 'mvsdf_cloud_clean',
     'mvsdf_cloud_compact',
     'mvsdf_raster_workspace_bytes', 'mvsdf_raster_draw', 'mvsdf_raster_resolve', 'mvsdf_raster_visibility', 'mvsdf_raster_colors',
