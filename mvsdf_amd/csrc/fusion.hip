@@ -4,7 +4,8 @@
 //
 // * k_fu_mask: masked depth of every pixel (fp32 compares against the probability thresholds).
 // * k_fu_fuse: one lane per reference pixel, the source loop inside.  The 4x4 transforms T_rs / T_sr are kernel data indexed by (view, source slot),
-//   the same for every lane of a workgroup, so they come through the scalar cache; the four source texels are plain gathers.  Writes counts, the
+//   the same for every lane of a workgroup, so they come through the scalar cache; the four source texels are plain gathers (the projection and the
+//   2x2 sample are geom_prims.h's mv_project_texel / mv_cell2, which tsdf.hip's integration uses too).  Writes counts, the
 //   fp32 fused depth, the fp64 fused depth (the emit pass back-projects at it) and a keep flag.
 // * an int64 exclusive scan of the keep flags over all views (geom_prims.h: mv_scan_blocks, i.e. k_scan_block_sum and k_scan_top); the emit pass ranks
 //   its own chunk (mv_chunk_rank), so no per-pixel offset is stored.  Points come out in (view, y, x) order.  No float atomics anywhere.
@@ -77,23 +78,16 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_fuse(const float* __restrict_
         const int y = p / W, x = p - y * W;
         const double X = (double)x + 0.5, Y = (double)y + 0.5;
         const double q0 = X * d, q1 = Y * d;
-        const double wmax = (double)(W - 1), hmax = (double)(H - 1);
         const int s0 = off[r], s1 = off[r + 1];
         for (int k = s0; k < s1; ++k) {
             const int s = src[k];
             const double* __restrict__ T = mats + (long long)k * 32;          // T_rs, then T_sr
-            const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
-            if (!(p2 > 0.0)) continue;
-            const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
-            const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
-            if (!(u >= 0.0 && u <= wmax && v >= 0.0 && v <= hmax)) continue;
-            const double x0 = fmin(floor(u), (double)(W - 2)), y0 = fmin(floor(v), (double)(H - 2));
-            const double fx = u - x0, fy = v - y0;
-            const float* __restrict__ g = masked + (long long)s * hw + (long long)(int)y0 * W + (int)x0;
-            const double d00 = (double)g[0], d01 = (double)g[1], d10 = (double)g[W], d11 = (double)g[W + 1];
-            if (!(d00 > 0.0 && d01 > 0.0 && d10 > 0.0 && d11 > 0.0)) continue;
-            const double ds = (d00 * (1.0 - fx) + d01 * fx) * (1.0 - fy) + (d10 * (1.0 - fx) + d11 * fx) * fy;
-            const double b0q = (u + 0.5) * ds, b1q = (v + 0.5) * ds;
+            MvProj pr;
+            if (!mv_project_texel(T, q0, q1, d, W, H, &pr)) continue;
+            const MvCell2 c = mv_cell2(masked + (long long)s * hw, W, H, pr.u, pr.v);
+            if (!(c.d00 > 0.0 && c.d01 > 0.0 && c.d10 > 0.0 && c.d11 > 0.0)) continue;
+            const double ds = c.bilinear();
+            const double b0q = (pr.u + 0.5) * ds, b1q = (pr.v + 0.5) * ds;
             const double* __restrict__ B = T + 16;
             const double b2 = mv_row4(B + 8, b0q, b1q, ds, 1.0);
             if (!(b2 > 0.0)) continue;

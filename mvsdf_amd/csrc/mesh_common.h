@@ -1,6 +1,7 @@
-// mesh_common.h -- the marching-cubes formulas the dense (mesh_kernels.hip) and the sparse (mesh_sparse.hip) extractors share: the table decode,
-// the crossing tests, the vertex position and the normal.  Both paths call these with an accessor val(i, j, k) -> the value at grid point (i, j, k),
-// so the two cannot drift apart: the sparse path's output is pinned bit for bit to the dense one (tests/test_gpu_mesh_sparse.py).
+// mesh_common.h -- the marching-cubes formulas the dense (mesh_kernels.hip: plain and masked) and the sparse (mesh_sparse.hip) extractors share: the
+// table decode, the crossing tests, the vertex position and the normal.  Both call these with an accessor val(i, j, k) -> the value at grid point
+// (i, j, k), so they cannot drift apart: the sparse path's output is pinned bit for bit to the dense one (tests/test_gpu_mesh_sparse.py).  mc_vertex
+// takes its gradient rule from the caller: McGrad (mc_grad_c, every point holds a value) unless a mask says otherwise (mesh_kernels.hip: McMaskGrad).
 // Conventions: mvsdf_amd/mesh.py; the table: tools/gen_mc_tables.py -> mc_tables.h.
 #pragma once
 #include "geom_prims.h"
@@ -72,10 +73,19 @@ __device__ __forceinline__ float mc_grad_c(const V& val, const long long* n, con
     return (val(hi[0], hi[1], hi[2]) - val(lo[0], lo[1], lo[2])) / den;
 }
 
-// the vertex on the crossing edge (g, g + e_a), x = the value at g: position and normal -> vert[3], normal[3]
-template <class V>
+// the gradient rule of a grid whose every point holds a value: mc_grad_c
+struct McGrad {
+    template <class V>
+    __device__ __forceinline__ float operator()(const V& val, const long long* n, const long long* g, int c, float h) const {
+        return mc_grad_c(val, n, g, c, h);
+    }
+};
+
+// the vertex on the crossing edge (g, g + e_a), x = the value at g: position and normal -> vert[3], normal[3].  grad(val, n, g, c, h) is the gradient
+// rule at the edge's two ends.
+template <class V, class G = McGrad>
 __device__ __forceinline__ void mc_vertex(const V& val, const long long* n, const long long* g, int a, float x, float level, const McGeom& gm,
-                                          float* vert, float* normal) {
+                                          float* vert, float* normal, const G& grad = G()) {
     long long g1[3] = {g[0], g[1], g[2]};
     g1[a] += 1;
     const float x1 = val(g1[0], g1[1], g1[2]);
@@ -83,7 +93,7 @@ __device__ __forceinline__ void mc_vertex(const V& val, const long long* n, cons
     float nr[3];
     for (int c = 0; c < 3; ++c) {
         vert[c] = c == a ? gm.org[c] + ((float)g[c] + t) * gm.sp[c] : gm.org[c] + (float)g[c] * gm.sp[c];
-        const float d0 = mc_grad_c(val, n, g, c, gm.sp[c]), d1 = mc_grad_c(val, n, g1, c, gm.sp[c]);
+        const float d0 = grad(val, n, g, c, gm.sp[c]), d1 = grad(val, n, g1, c, gm.sp[c]);
         nr[c] = d0 + t * (d1 - d0);
     }
     const float nn = sqrtf((nr[0] * nr[0] + nr[1] * nr[1]) + nr[2] * nr[2]);

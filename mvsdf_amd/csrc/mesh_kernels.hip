@@ -1,6 +1,8 @@
 // mesh_kernels.hip -- on-device mesh extraction (reference code/evaluation/eval.py:109-125, code/utils/plots.py:150-205):
-// marching cubes over an fp32 volume with arbitrary element strides, connected components of the mesh by union-find, and the compaction of one
-// component.  Conventions (vertex / face order, positions, normals): mvsdf_amd/mesh.py; the triangle table: tools/gen_mc_tables.py -> mc_tables.h.
+// marching cubes over an fp32 volume with arbitrary element strides, plain (mesh.marching_cubes) or under a per-point validity mask
+// (mesh.marching_cubes_masked, which meshes tsdf.hip's volumes): one set of passes, templates on a mask policy (McNoMask / McMask below); connected
+// components of the mesh by union-find, and the compaction of one component.  Conventions (vertex / face order, positions, normals, the mask's
+// additions): mvsdf_amd/mesh.py; tests/mc_ref.py and tests/tsdf_ref.py restate them in numpy; the triangle table: tools/gen_mc_tables.py -> mc_tables.h.
 //
 // Every pass maps items (grid points, vertices or faces) to workgroups in linear order: workgroup b owns items [b * MESH_CHUNK, (b + 1) * MESH_CHUNK),
 // its 256 lanes take MESH_CHUNK / 256 consecutive rounds of 256.  A count pass writes one small total per workgroup, k_mesh_scan turns them into
@@ -15,51 +17,144 @@ struct MeshVol {
     float level;
 };
 
-__device__ __forceinline__ float vat(const MeshVol& v, long long i, long long j, long long k) { return v.p[i * v.s[0] + j * v.s[1] + k * v.s[2]]; }
-
 // the accessor of mesh_common.h's formulas
 struct VolVal {
     const MeshVol& v;
-    __device__ __forceinline__ float operator()(long long i, long long j, long long k) const { return vat(v, i, j, k); }
+    __device__ __forceinline__ float operator()(long long i, long long j, long long k) const { return v.p[i * v.s[0] + j * v.s[1] + k * v.s[2]]; }
 };
 
-__device__ __forceinline__ void point_ijk(const MeshVol& v, long long p, long long& i, long long& j, long long& k) {
+// linear index (k fastest) of grid point (i, j, k), and back
+__device__ __forceinline__ long long point_at(const MeshVol& v, long long i, long long j, long long k) { return (i * v.n[1] + j) * v.n[2] + k; }
+
+__device__ __forceinline__ void point_ijk(const MeshVol& v, long long p, long long* g) {
     const long long nyz = v.n[1] * v.n[2];
-    i = p / nyz;
-    const long long r = p - i * nyz;
-    j = r / v.n[2];
-    k = r - j * v.n[2];
+    g[0] = p / nyz;
+    const long long r = p - g[0] * nyz;
+    g[1] = r / v.n[2];
+    g[2] = r - g[1] * v.n[2];
 }
 
-// crossing edges owned by grid point (i, j, k): bit a = the edge to (i, j, k) + e_a crosses the level
-__device__ __forceinline__ int point_edges(const MeshVol& v, long long i, long long j, long long k, bool in0) {
-    return mc_point_edges(VolVal{v}, v.n, i, j, k, in0, v.level);
+// crossing edges owned by grid point g: bit a = the edge to g + e_a crosses the level (in0: the value at g is inside)
+__device__ __forceinline__ int point_edges(const MeshVol& v, const long long* g, bool in0) {
+    return mc_point_edges(VolVal{v}, v.n, g[0], g[1], g[2], in0, v.level);
 }
 
-// cube index of the cell with lower corner (i, j, k) (bit c: corner (c & 1, c >> 1 & 1, c >> 2 & 1) is inside); -1 if there is no such cell
-__device__ __forceinline__ int cell_index(const MeshVol& v, long long i, long long j, long long k) {
-    if (i + 1 >= v.n[0] || j + 1 >= v.n[1] || k + 1 >= v.n[2]) return -1;
-    return mc_cube_index(VolVal{v}, i, j, k, v.level);
+// g = p's (i, j, k); true iff the cell with lower corner p lies in the grid
+__device__ __forceinline__ bool cell_ijk(const MeshVol& v, long long p, long long* g) {
+    point_ijk(v, p, g);
+    return g[0] + 1 < v.n[0] && g[1] + 1 < v.n[1] && g[2] + 1 < v.n[2];
 }
 
-// ---- marching cubes, pass 1: vertices and triangles per workgroup (bv / bf), or -1 in bf when the workgroup saw a non-finite value ----
-__global__ __launch_bounds__(MESH_THREADS) void k_mc_count(MeshVol v, long long npts, int* __restrict__ bv, int* __restrict__ bf) {
+// ================================================================ marching cubes: one set of passes, two mask policies ================================================================
+// The passes k_mc_count / k_mc_vertices / k_mc_faces are templates on a mask policy M, which says which points and cells take part:
+//   point(p)               grid point p holds a value
+//   cell_at(v, p, g)       the cell with lower corner p exists and its 8 corners hold values; g = p's (i, j, k) (the face pass splits p only then)
+//   around(v, g)           bit a: the grid edge (g, g + e_a) may carry a vertex
+//   keep(p, bits)          the count pass hands over point p's vertex-carrying edges
+//   bits(v, g, p), kStored the later passes ask for them: recomputed from the values, or (kStored) the byte keep stored -- then a value is read only
+//                          where a bit is set
+//   grad()                 mc_vertex's gradient rule
+// McNoMask (marching_cubes) is empty: a kernel instance carries no pointer and loads or stores nothing for it.  McMask (marching_cubes_masked) never
+// reads the value of an invalid point.
+
+struct McNoMask {
+    static constexpr bool kStored = false;
+    __device__ __forceinline__ bool point(long long) const { return true; }
+    __device__ __forceinline__ bool cell_at(const MeshVol& v, long long p, long long* g) const { return cell_ijk(v, p, g); }
+    __device__ __forceinline__ int around(const MeshVol&, const long long*) const { return 7; }
+    __device__ __forceinline__ void keep(long long, int) const {}
+    __device__ __forceinline__ int bits(const MeshVol& v, const long long* g, long long) const {
+        return point_edges(v, g, VolVal{v}(g[0], g[1], g[2]) < v.level);
+    }
+    __device__ __forceinline__ McGrad grad() const { return McGrad(); }
+};
+
+// gradient component c at the valid grid point g from its neighbours g -+ e_c that are in the grid and valid: both -> central difference over 2h, one ->
+// one-sided over h, none -> 0 (with every point valid: mc_grad_c)
+struct McMaskGrad {
+    const unsigned char* ok;
+    template <class V>
+    __device__ __forceinline__ float operator()(const V& val, const long long* n, const long long* g, int c, float h) const {
+        long long lo[3] = {g[0], g[1], g[2]}, hi[3] = {g[0], g[1], g[2]};
+        lo[c] -= 1;
+        hi[c] += 1;
+        const bool has_lo = lo[c] >= 0 && ok[(lo[0] * n[1] + lo[1]) * n[2] + lo[2]];
+        const bool has_hi = hi[c] < n[c] && ok[(hi[0] * n[1] + hi[1]) * n[2] + hi[2]];
+        if (!has_lo && !has_hi) return 0.0f;
+        if (!has_lo) lo[c] = g[c];
+        if (!has_hi) hi[c] = g[c];
+        const float den = has_lo && has_hi ? 2.0f * h : h;
+        return (val(hi[0], hi[1], hi[2]) - val(lo[0], lo[1], lo[2])) / den;
+    }
+};
+
+struct McMask {
+    const unsigned char* valid;                       // valid[i][j][k], contiguous
+    unsigned char* cell;                              // k_mcm_cells: the cell with this lower corner is valid
+    unsigned char* ebits;                             // k_mc_count: the point's crossing edges that touch a valid cell
+    static constexpr bool kStored = true;
+    __device__ __forceinline__ bool point(long long p) const { return valid[p]; }
+    __device__ __forceinline__ bool cell_at(const MeshVol& v, long long p, long long* g) const {
+        if (!cell[p]) return false;
+        point_ijk(v, p, g);
+        return true;
+    }
+    // bit a: one of the up to four cells around the grid edge (g, g + e_a) is valid (then both of its ends are)
+    __device__ __forceinline__ int around(const MeshVol& v, const long long* g) const {
+        int bits = 0;
+        for (int a = 0; a < 3; ++a) {
+            const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;
+            bool any = false;
+            for (int m = 0; m < 4; ++m) {
+                long long q[3] = {g[0], g[1], g[2]};
+                q[o0] -= m & 1;
+                q[o1] -= m >> 1;
+                if (q[o0] >= 0 && q[o1] >= 0) any = any || cell[point_at(v, q[0], q[1], q[2])];
+            }
+            if (any) bits |= 1 << a;
+        }
+        return bits;
+    }
+    __device__ __forceinline__ void keep(long long p, int bits) const { ebits[p] = (unsigned char)bits; }
+    __device__ __forceinline__ int bits(const MeshVol&, const long long*, long long p) const { return ebits[p]; }
+    __device__ __forceinline__ McMaskGrad grad() const { return McMaskGrad{valid}; }
+};
+
+// ---- pass 0, McMask only: cell[p] = the cell with lower corner p exists and its 8 corners are valid ----
+__global__ __launch_bounds__(MESH_THREADS) void k_mcm_cells(MeshVol v, long long npts, McMask m) {
+    const long long p = (long long)blockIdx.x * MESH_THREADS + threadIdx.x;
+    if (p >= npts) return;
+    long long g[3];
+    bool ok = cell_ijk(v, p, g);
+    if (ok) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ok = ok && m.valid[point_at(v, g[0] + (c & 1), g[1] + (c >> 1 & 1), g[2] + (c >> 2 & 1))];
+    }
+    m.cell[p] = ok ? 1 : 0;
+}
+
+// ---- pass 1: vertices and triangles per workgroup (bv / bf), or -1 in bf when the workgroup saw a non-finite value at a point that holds one ----
+template <class M>
+__global__ __launch_bounds__(MESH_THREADS) void k_mc_count(MeshVol v, long long npts, M m, int* __restrict__ bv, int* __restrict__ bf) {
     __shared__ int s_w[MESH_THREADS / 64];
     long long rv = 0, rf = 0;
     int bad = 0;
     for (int r = 0; r < MESH_ROUNDS; ++r) {
         const long long p = (long long)blockIdx.x * MESH_CHUNK + r * MESH_THREADS + threadIdx.x;
-        int nv = 0, nt = 0;
+        int bits = 0, nt = 0;
         if (p < npts) {
-            long long i, j, k;
-            point_ijk(v, p, i, j, k);
-            const float x = vat(v, i, j, k);
-            bad |= !isfinite(x);
-            nv = __popc(point_edges(v, i, j, k, x < v.level));
-            const int ci = cell_index(v, i, j, k);
-            if (ci >= 0) nt = mc_ntri(ci);
+            long long g[3];
+            point_ijk(v, p, g);
+            if (m.point(p)) {
+                const float x = VolVal{v}(g[0], g[1], g[2]);
+                bad |= !isfinite(x);
+                const int around = m.around(v, g);
+                if (around) bits = point_edges(v, g, x < v.level) & around;
+                if (m.cell_at(v, p, g)) nt = mc_ntri(mc_cube_index(VolVal{v}, g[0], g[1], g[2], v.level));
+            }
+            m.keep(p, bits);
         }
-        block_excl(nv, 2, s_w, rv);
+        block_excl(__popc(bits), 2, s_w, rv);
         block_excl(nt, 3, s_w, rf);
     }
     bad = __syncthreads_or(bad);
@@ -70,7 +165,8 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_count(MeshVol v, long long 
 }
 
 // ---- pass 2: the vertex id map (id of each point's first vertex), vertices and normals ----
-__global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long long npts, McGeom gm, const long long* __restrict__ ov, int* __restrict__ idmap,
+template <class M>
+__global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long long npts, M m, McGeom gm, const long long* __restrict__ ov, int* __restrict__ idmap,
                                                               float* __restrict__ verts, float* __restrict__ normals, long long nv_cap) {
     __shared__ int s_w[MESH_THREADS / 64];
     long long run = ov[blockIdx.x];
@@ -80,49 +176,53 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mc_vertices(MeshVol v, long lo
         long long g[3] = {0, 0, 0};
         float x = 0.0f;
         if (p < npts) {
-            point_ijk(v, p, g[0], g[1], g[2]);
-            x = vat(v, g[0], g[1], g[2]);
-            bits = point_edges(v, g[0], g[1], g[2], x < v.level);
+            if (!M::kStored) {                                       // recomputed bits need the point and its value
+                point_ijk(v, p, g);
+                x = VolVal{v}(g[0], g[1], g[2]);
+            }
+            bits = m.bits(v, g, p);
         }
         long long id = block_excl(__popc(bits), 2, s_w, run);
         if (p >= npts) continue;
         idmap[p] = (int)id;
+        if (M::kStored) {                                            // stored bits: the value is read only where an edge carries a vertex
+            if (!bits) continue;
+            point_ijk(v, p, g);
+            x = VolVal{v}(g[0], g[1], g[2]);
+        }
         for (int a = 0; a < 3; ++a) {
             if (!(bits >> a & 1)) continue;
-            if (id < nv_cap) mc_vertex(VolVal{v}, v.n, g, a, x, v.level, gm, verts + id * 3, normals + id * 3);
+            if (id < nv_cap) mc_vertex(VolVal{v}, v.n, g, a, x, v.level, gm, verts + id * 3, normals + id * 3, m.grad());
             ++id;
         }
     }
 }
 
-// vertex id of cube edge e of the cell at (i, j, k): the owner's first id plus its crossing edges along lower axes
-__device__ __forceinline__ int edge_vertex(const MeshVol& v, const int* __restrict__ idmap, long long i, long long j, long long k, int e) {
-    long long q[3] = {i, j, k};
-    const int a = mc_edge_owner(e, q);
-    const bool in0 = vat(v, q[0], q[1], q[2]) < v.level;
-    const int bits = point_edges(v, q[0], q[1], q[2], in0);
-    return idmap[(q[0] * v.n[1] + q[1]) * v.n[2] + q[2]] + __popc(bits & ((1 << a) - 1));
-}
-
-// ---- pass 3: faces (int32 vertex ids), cells in linear order, each cell's triangles in table order ----
-__global__ __launch_bounds__(MESH_THREADS) void k_mc_faces(MeshVol v, long long npts, const long long* __restrict__ of, const int* __restrict__ idmap,
+// ---- pass 3: faces (int32 vertex ids), cells in linear order, each cell's triangles in table order.  The vertex id of a cube edge: its owner's first
+// id plus the owner's vertex-carrying edges along lower axes ----
+template <class M>
+__global__ __launch_bounds__(MESH_THREADS) void k_mc_faces(MeshVol v, long long npts, M m, const long long* __restrict__ of, const int* __restrict__ idmap,
                                                            int* __restrict__ faces, long long nf_cap) {
     __shared__ int s_w[MESH_THREADS / 64];
     long long run = of[blockIdx.x];
     for (int r = 0; r < MESH_ROUNDS; ++r) {
         const long long p = (long long)blockIdx.x * MESH_CHUNK + r * MESH_THREADS + threadIdx.x;
-        long long i = 0, j = 0, k = 0;
-        int ci = -1, nt = 0;
-        if (p < npts) {
-            point_ijk(v, p, i, j, k);
-            ci = cell_index(v, i, j, k);
-            if (ci >= 0) nt = mc_ntri(ci);
+        long long g[3] = {0, 0, 0};
+        int ci = 0, nt = 0;
+        if (p < npts && m.cell_at(v, p, g)) {
+            ci = mc_cube_index(VolVal{v}, g[0], g[1], g[2], v.level);
+            nt = mc_ntri(ci);
         }
         const long long fid = block_excl(nt, 3, s_w, run);
         for (int t = 0; t < nt; ++t) {
             if (fid + t >= nf_cap) break;
             const int base = (mc_tri_offset[ci] + t) * 3;
-            for (int s = 0; s < 3; ++s) faces[(fid + t) * 3 + s] = edge_vertex(v, idmap, i, j, k, mc_tri_edges[base + s]);
+            for (int s = 0; s < 3; ++s) {
+                long long q[3] = {g[0], g[1], g[2]};
+                const int a = mc_edge_owner(mc_tri_edges[base + s], q);
+                const long long o = point_at(v, q[0], q[1], q[2]);
+                faces[(fid + t) * 3 + s] = idmap[o] + __popc(m.bits(v, q, o) & ((1 << a) - 1));
+            }
         }
     }
 }
@@ -365,19 +465,24 @@ __global__ __launch_bounds__(MESH_THREADS) void k_sel_faces(const int* __restric
 
 struct McLayout {
     long long npts, nb;
-    size_t idmap, bv, bf, ov, of, total;
+    size_t idmap, cell, ebits, bv, bf, ov, of, total;           // cell, ebits: McMask's two byte arrays (masked only)
 };
 
-// false: a dimension below 2, or a grid whose points or workgroups the kernels cannot index
-static bool mc_layout(long long nx, long long ny, long long nz, McLayout* L) {
+// false: a dimension below 2, or a grid whose points or workgroups the kernels cannot index (masked: k_mcm_cells takes one lane per point)
+static bool mc_layout(long long nx, long long ny, long long nz, bool masked, McLayout* L) {
     if (nx < 2 || ny < 2 || nz < 2) return false;
-    const long long lim = 1ll << 60;
+    const long long lim = 1ll << (masked ? 40 : 60);
     if (nx > lim / ny || nx * ny > lim / nz) return false;
     L->npts = nx * ny * nz;
     L->nb = mv_ceil_div(L->npts, MESH_CHUNK);
-    if (L->nb > INT_MAX) return false;
+    if (L->nb > INT_MAX || (masked && mv_ceil_div(L->npts, MESH_THREADS) > INT_MAX)) return false;
     WsCursor c{MESH_HDR};
     L->idmap = c.take((size_t)L->npts * 4);
+    L->cell = L->ebits = 0;
+    if (masked) {
+        L->cell = c.take((size_t)L->npts);
+        L->ebits = c.take((size_t)L->npts);
+    }
     L->bv = c.take((size_t)L->nb * 4);
     L->bf = c.take((size_t)L->nb * 4);
     L->ov = c.take((size_t)L->nb * 8);
@@ -413,8 +518,9 @@ static bool cc_layout(long long nv, long long nf, CcLayout* L) {
     return true;
 }
 
-static bool mc_vol(const float* vol, const int64_t* shape, const int64_t* strides, float level, McLayout* L, MeshVol* v) {
-    if (!vol || !shape || !strides || !mc_layout(shape[0], shape[1], shape[2], L)) return false;
+// the volume and its workspace layout from a call's arguments; false: a NULL pointer or a shape mc_layout refuses
+static bool mc_vol(const float* vol, const int64_t* shape, const int64_t* strides, float level, bool masked, McLayout* L, MeshVol* v) {
+    if (!vol || !shape || !strides || !mc_layout(shape[0], shape[1], shape[2], masked, L)) return false;
     v->p = vol;
     v->level = level;
     for (int a = 0; a < 3; ++a) {
@@ -424,45 +530,90 @@ static bool mc_vol(const float* vol, const int64_t* shape, const int64_t* stride
     return true;
 }
 
+static McMask mc_mask(const uint8_t* valid, const McLayout& L, void* ws) { return McMask{valid, (unsigned char*)ws + L.cell, (unsigned char*)ws + L.ebits}; }
+
+template <class M>
+static int mc_count(const MeshVol& v, const McLayout& L, M m, void* ws, void* stream, const char* what) {
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_mc_count<M>, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, m, (int*)(w + L.bv), (int*)(w + L.bf));
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(w + L.bv), (const int*)(w + L.bf), (int)L.nb,
+                       (long long*)(w + L.ov), (long long*)(w + L.of), (long long*)w);
+    return mv_check(hipGetLastError(), what);
+}
+
+static bool mc_emit_args(const float* spacing, const float* origin, const float* verts, const float* normals, const int32_t* faces, int64_t nv_cap,
+                         int64_t nf_cap, McGeom* gm) {
+    if (!spacing || !origin || nv_cap < 0 || nf_cap < 0 || (nv_cap && (!verts || !normals)) || (nf_cap && !faces)) return false;
+    for (int a = 0; a < 3; ++a) {
+        gm->sp[a] = spacing[a];
+        gm->org[a] = origin[a];
+    }
+    return true;
+}
+
+template <class M>
+static int mc_emit(const MeshVol& v, const McLayout& L, M m, const McGeom& gm, void* ws, float* verts, float* normals, int32_t* faces, int64_t nv_cap,
+                   int64_t nf_cap, void* stream, const char* what) {
+    char* w = (char*)ws;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_mc_vertices<M>, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, m, gm, (const long long*)(w + L.ov), (int*)(w + L.idmap),
+                       verts, normals, (long long)nv_cap);
+    hipLaunchKernelGGL(k_mc_faces<M>, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, m, (const long long*)(w + L.of), (const int*)(w + L.idmap),
+                       faces, (long long)nf_cap);
+    return mv_check(hipGetLastError(), what);
+}
+
 extern "C" {
 
 size_t mvsdf_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
     McLayout L;
-    return mc_layout(nx, ny, nz, &L) ? L.total : 0;
+    return mc_layout(nx, ny, nz, false, &L) ? L.total : 0;
 }
 
 int mvsdf_mc_count(const float* vol, const int64_t* shape, const int64_t* strides, float level, void* ws, size_t ws_bytes, void* stream) {
     McLayout L;
     MeshVol v;
-    if (!mc_vol(vol, shape, strides, level, &L, &v) || !ws) return mv_fail(-1, "mvsdf_mc_count: bad arguments (every extent must be >= 2)");
+    if (!mc_vol(vol, shape, strides, level, false, &L, &v) || !ws) return mv_fail(-1, "mvsdf_mc_count: bad arguments (every extent must be >= 2)");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_mc_count: workspace too small (mvsdf_mc_workspace_bytes)");
-    char* w = (char*)ws;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_count, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, (int*)(w + L.bv), (int*)(w + L.bf));
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(w + L.bv), (const int*)(w + L.bf), (int)L.nb,
-                       (long long*)(w + L.ov), (long long*)(w + L.of), (long long*)w);
-    return mv_check(hipGetLastError(), "mvsdf_mc_count");
+    return mc_count(v, L, McNoMask(), ws, stream, "mvsdf_mc_count");
 }
 
 int mvsdf_mc_emit(const float* vol, const int64_t* shape, const int64_t* strides, float level, const float* spacing, const float* origin, void* ws, size_t ws_bytes,
                   float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap, void* stream) {
     McLayout L;
     MeshVol v;
-    if (!mc_vol(vol, shape, strides, level, &L, &v) || !ws || !spacing || !origin || nv_cap < 0 || nf_cap < 0 || (nv_cap && (!verts || !normals)) || (nf_cap && !faces))
+    McGeom gm;
+    if (!mc_vol(vol, shape, strides, level, false, &L, &v) || !ws || !mc_emit_args(spacing, origin, verts, normals, faces, nv_cap, nf_cap, &gm))
         return mv_fail(-1, "mvsdf_mc_emit: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_mc_emit: workspace too small (mvsdf_mc_workspace_bytes)");
+    return mc_emit(v, L, McNoMask(), gm, ws, verts, normals, faces, nv_cap, nf_cap, stream, "mvsdf_mc_emit");
+}
+
+size_t mvsdf_mcm_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
+    McLayout L;
+    return mc_layout(nx, ny, nz, true, &L) ? L.total : 0;
+}
+
+int mvsdf_mcm_count(const float* vol, const uint8_t* valid, const int64_t* shape, const int64_t* strides, float level, void* ws, size_t ws_bytes, void* stream) {
+    McLayout L;
+    MeshVol v;
+    if (!mc_vol(vol, shape, strides, level, true, &L, &v) || !valid || !ws) return mv_fail(-1, "mvsdf_mcm_count: bad arguments (every extent must be >= 2)");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_mcm_count: workspace too small (mvsdf_mcm_workspace_bytes)");
+    const McMask m = mc_mask(valid, L, ws);
+    hipLaunchKernelGGL(k_mcm_cells, dim3(mv_grid(L.npts, MESH_THREADS)), dim3(MESH_THREADS), 0, (hipStream_t)stream, v, L.npts, m);
+    return mc_count(v, L, m, ws, stream, "mvsdf_mcm_count");
+}
+
+int mvsdf_mcm_emit(const float* vol, const uint8_t* valid, const int64_t* shape, const int64_t* strides, float level, const float* spacing, const float* origin,
+                   void* ws, size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap, void* stream) {
+    McLayout L;
+    MeshVol v;
     McGeom gm;
-    for (int a = 0; a < 3; ++a) {
-        gm.sp[a] = spacing[a];
-        gm.org[a] = origin[a];
-    }
-    char* w = (char*)ws;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_vertices, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, gm, (const long long*)(w + L.ov), (int*)(w + L.idmap),
-                       verts, normals, (long long)nv_cap);
-    hipLaunchKernelGGL(k_mc_faces, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, (const long long*)(w + L.of), (const int*)(w + L.idmap),
-                       faces, (long long)nf_cap);
-    return mv_check(hipGetLastError(), "mvsdf_mc_emit");
+    if (!mc_vol(vol, shape, strides, level, true, &L, &v) || !valid || !ws || !mc_emit_args(spacing, origin, verts, normals, faces, nv_cap, nf_cap, &gm))
+        return mv_fail(-1, "mvsdf_mcm_emit: bad arguments");
+    if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_mcm_emit: workspace too small (mvsdf_mcm_workspace_bytes)");
+    return mc_emit(v, L, mc_mask(valid, L, ws), gm, ws, verts, normals, faces, nv_cap, nf_cap, stream, "mvsdf_mcm_emit");
 }
 
 size_t mvsdf_mesh_cc_workspace_bytes(int64_t nv, int64_t nf) {

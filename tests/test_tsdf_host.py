@@ -159,10 +159,12 @@ def test_argument_errors_need_no_device():
 
 def test_plumbing():
     from mvsdf_amd import _lib, build
-    assert 'tsdf.hip' in build.SOURCES
+    assert 'tsdf.hip' in build.SOURCES and 'mesh_kernels.hip' in build.SOURCES
     hdr = open(os.path.join(ROOT, 'include', 'mvsdf_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    src = open(os.path.join(ROOT, 'mvsdf_amd', 'csrc', 'tsdf.hip')).read()
-    for name in ('mvsdf_tsdf_workspace_bytes', 'mvsdf_tsdf_integrate', 'mvsdf_mcm_workspace_bytes', 'mvsdf_mcm_count', 'mvsdf_mcm_emit'):
+    # the integration lives in tsdf.hip; the masked extractor's entry points sit beside marching_cubes' in mesh_kernels.hip, which shares mesh_common.h
+    for name, where in (('mvsdf_tsdf_workspace_bytes', 'tsdf.hip'), ('mvsdf_tsdf_integrate', 'tsdf.hip'), ('mvsdf_mcm_workspace_bytes', 'mesh_kernels.hip'),
+                        ('mvsdf_mcm_count', 'mesh_kernels.hip'), ('mvsdf_mcm_emit', 'mesh_kernels.hip')):
+        src = open(os.path.join(ROOT, 'mvsdf_amd', 'csrc', where)).read()
         assert name in _lib.EXPORTS and re.search(r'\b%s\s*\(' % name, hdr) and re.search(r'\b%s\s*\(' % name, src), name
-    assert '#include "mesh_common.h"' in src
+    assert '#include "mesh_common.h"' in open(os.path.join(ROOT, 'mvsdf_amd', 'csrc', 'mesh_kernels.hip')).read()
