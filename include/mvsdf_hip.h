@@ -589,6 +589,22 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
 int mvsdf_mesh_trim(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes,
                     float* out_verts, float* out_normals, float* out_colors, int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 
+/* ---- mesh simplification (mesh_simplify.hip; Python: Mesh.simplify in mvsdf_amd/mesh.py, which states the definition) ----
+ * Vertex clustering on the uniform grid of edge `cell` from `origin` (a HOST array of 3 doubles, or NULL = the low corner of the vertices' box) with
+ * quadric-error placement (quadric != 0) or the clusters' means (0).  1 <= nv <= INT32_MAX, 1 <= nf <= INT32_MAX / 3, else the workspace query gives 0.
+ * normals / colors ([nv][3] fp32) may be NULL.  mvsdf_mesh_simplify is the count pass: it waits for the stream (the host reads the box and the cluster
+ * count) and leaves int64 {clusters, output vertices, output faces, degenerate faces, duplicate faces, vertices placed by the quadric, error bits
+ * (1 non-finite vertex, 2 vertex id out of range, 4 cell index outside [0, 2^21))} at the start of the workspace.  With error bits set nothing else
+ * is valid.  counts_only != 0 skips the per-cluster sums and the placement: the counts are the same (quadric-placed stays 0), and no emit may follow.
+ * mvsdf_mesh_simplify_emit, after a successful full count with the same workspace: the used clusters ascending, and the kept faces in their original
+ * order and corner order, re-indexed.  out_normals / out_colors may be NULL (colours are 0 when the count pass got none); nv_cap / nf_cap bound
+ * what is written. */
+size_t mvsdf_mesh_simplify_workspace_bytes(int64_t nv, int64_t nf);
+int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, double cell,
+                        const double* origin, int32_t quadric, int32_t counts_only, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_mesh_simplify_emit(const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes, float* out_verts, float* out_normals,
+                             float* out_colors, int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
+
 /* ---- DTU Chamfer evaluation (chamfer.hip; Python: mvsdf_amd/chamfer.py, which states the metric) ----
  * All four operations leave int64 results at the start of their workspace; fp64 throughout.  Error bits: 1 more points than max_points,
  * 2 vertex id out of range, 4 non-finite coordinate, 8 coordinate too far from the origin for the downsampling grid, 16 cell-table overflow,

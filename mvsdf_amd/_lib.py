@@ -77,6 +77,10 @@ def lib():
         L.mvsdf_mesh_cut.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, vp, C.c_size_t, vp, vp]
         L.mvsdf_mesh_trim.argtypes = [vp] * 4 + [i64, i64, vp, C.c_size_t] + [vp] * 4 + [i64, i64, vp]
         f64, u64, sz = C.c_double, C.c_uint64, C.c_size_t
+        L.mvsdf_mesh_simplify_workspace_bytes.restype = sz
+        L.mvsdf_mesh_simplify_workspace_bytes.argtypes = [i64, i64]
+        L.mvsdf_mesh_simplify.argtypes = [vp] * 4 + [i64, i64, f64, vp, C.c_int32, C.c_int32, vp, sz, vp]
+        L.mvsdf_mesh_simplify_emit.argtypes = [vp, i64, i64, vp, sz] + [vp] * 4 + [i64, i64, vp]
         L.mvsdf_chamfer_key.restype = u64
         L.mvsdf_chamfer_key.argtypes = [u64, i64]
         for fn in ('mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_nearest_workspace_bytes'):
@@ -174,6 +178,7 @@ EXPORTS = [
     'mvsdf_smc_workspace_bytes', 'mvsdf_smc_emit_workspace_bytes', 'mvsdf_smc_coarse_points', 'mvsdf_smc_seed', 'mvsdf_smc_brick_points',
     'mvsdf_smc_closure', 'mvsdf_smc_count', 'mvsdf_smc_emit',
     'mvsdf_mesh_cut_workspace_bytes', 'mvsdf_mesh_cut', 'mvsdf_mesh_trim',
+    'mvsdf_mesh_simplify_workspace_bytes', 'mvsdf_mesh_simplify', 'mvsdf_mesh_simplify_emit',
     'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',

@@ -68,16 +68,26 @@ def extract_world_mesh(model, scale_mat, resolution=512, path=None, epoch=None, 
     return mesh
 
 
+def write_simplified_mesh(mesh, path, epoch, cell=None, target_faces=None):
+    """Mesh.simplify(cell=... | target_faces=...) of the world mesh, written as <path>/surface_world_coordinates_<epoch>_simplified.obj
+    -> the simplified Mesh, or None (and no file) when no face survives."""
+    out = mesh.simplify(cell=cell, target_faces=target_faces)
+    if out is not None:
+        out.export(os.path.join(path, 'surface_world_coordinates_{0}_simplified.obj'.format(epoch)))
+    return out
+
+
 def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
              eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None,
-             color_mesh=False):
+             color_mesh=False, simplify_cell=None, simplify_faces=None):
     """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
     -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
     view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
     sparse_mesh / mesh_block / mesh_margin: extract_world_mesh's sparse / block / margin.  color_mesh: besides the OBJ (written as without it), the same
     mesh in the colours of the input photographs as surface_world_coordinates_<epoch>_color.ply (raster.color_mesh_from_scene: image_hd/, the
     world_mat_i of cameras_hd.npz at pixel_center 0, visibility masked by mask_hd/).  -> {'epoch', 'evaldir', 'mesh', 'psnrs'} (+ 'color_mesh', the
-    coloured Mesh or None, with color_mesh)."""
+    coloured Mesh or None, with color_mesh).  simplify_cell / simplify_faces (one of them): besides the OBJ (written as
+    without them), write_simplified_mesh's surface_world_coordinates_<epoch>_simplified.obj; the result gets 'simplified_mesh'."""
     from PIL import Image
     from .checkpoint import MODEL_SUBDIR
     from .datasets.device_batches import DeviceBatches
@@ -115,6 +125,12 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
         from . import raster
         colored = raster.color_mesh_from_scene(mesh, data_dir)
         colored.export(os.path.join(evaldir, 'surface_world_coordinates_{0}_color.ply'.format(epoch)))
+    simplify = simplify_cell is not None or simplify_faces is not None
+    simplified = None
+    if simplify and mesh is not None:
+        simplified = write_simplified_mesh(mesh, evaldir, epoch, cell=simplify_cell, target_faces=simplify_faces)
+        if simplified is not None:
+            printer('simplified: %d -> %d faces (cell %.6g)' % (len(mesh), len(simplified), mesh.simplify_stats['cell'] or 0.0))
     psnrs = None
     if eval_rendering:
         images_dir = os.path.join(evaldir, 'rendering')
@@ -135,6 +151,8 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     res = {'epoch': epoch, 'evaldir': evaldir, 'mesh': mesh, 'psnrs': psnrs}
     if color_mesh:
         res['color_mesh'] = colored
+    if simplify:
+        res['simplified_mesh'] = simplified
     return res
 
 
@@ -159,6 +177,10 @@ def eval_parser():
     p.add_argument('--mesh_margin', default=0.5, type=float, help='With --sparse_mesh: the Lipschitz bound assumed of the SDF when seeding blocks.')
     p.add_argument('--color_mesh', default=False, action='store_true',
                    help='Also write surface_world_coordinates_<epoch>_color.ply: the mesh in the colours of image_hd/ (mvsdf_amd/raster.py).')
+    g = p.add_mutually_exclusive_group()
+    g.add_argument('--simplify_cell', default=None, type=float,
+                   help='Also write surface_world_coordinates_<epoch>_simplified.obj: Mesh.simplify on a grid of this edge (world units).')
+    g.add_argument('--simplify_faces', default=None, type=int, help='The same with Mesh.simplify(target_faces=N): at most N faces.')
     return p
 
 
@@ -169,4 +191,4 @@ def main(argv=None, printer=print):
     return evaluate(data_dir=opt.data_dir, conf=opt.conf, expname=opt.expname, exps_folder_name=opt.exps_folder, evals_folder_name='evals',
                     timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
                     exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer, sparse_mesh=opt.sparse_mesh, mesh_block=opt.mesh_block,
-                    mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh)
+                    mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh, simplify_cell=opt.simplify_cell, simplify_faces=opt.simplify_faces)

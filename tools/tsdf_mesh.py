@@ -3,12 +3,12 @@
 any training, and the paper's depth-map baseline.
 
     python tools/tsdf_mesh.py --data DIR [--pair DIR/pair.txt] [--resolution 256 | --voxel X] [--trunc_voxels 4] [--min_views 2]
-                              [--bbox cloud|PLY] [--no_fuse] [--largest] [--color] [--out DIR/tsdf_mesh.ply]
+                              [--bbox cloud|PLY] [--no_fuse] [--largest] [--simplify_faces N] [--color] [--out DIR/tsdf_mesh.ply]
 
 Reads cam_<id:08>_flow3.txt, <id:08>_flow3.pfm and <id:08>_flow{1,2,3}_prob.pfm from DIR (prepare.load_mvs_output).  By default the depth maps go
 through fuse_depths first (tools/fusion.py's options below) and its fused_depths are integrated; --no_fuse integrates the probability-masked raw
 maps.  The grid covers the box of the fused cloud (--bbox cloud) or of a given point-cloud PLY such as cut.ply, padded by the truncation band.
---color takes vertex colours from DIR's <id:08>.jpg|png resized to the depth-map size (raster.color_vertices).  Prints voxels, valid share,
+--simplify_faces N reduces the mesh to at most N faces (Mesh.simplify) before colouring and writing.  --color takes vertex colours from DIR's <id:08>.jpg|png resized to the depth-map size (raster.color_vertices).  Prints voxels, valid share,
 vertices and faces.
 """
 import argparse
@@ -30,6 +30,7 @@ def parse_args(argv=None):
     ap.add_argument('--bbox', type=str, default='cloud', help='"cloud": the fused cloud\'s box; or a point-cloud PLY such as cut.ply')
     ap.add_argument('--no_fuse', action='store_true', default=False, help='integrate the masked raw depth maps instead of fuse_depths\' fused ones')
     ap.add_argument('--largest', action='store_true', default=False, help='keep the largest connected component')
+    ap.add_argument('--simplify_faces', type=int, default=None, help='at most this many faces (Mesh.simplify(target_faces=N)), before --color')
     ap.add_argument('--color', action='store_true', default=False)
     ap.add_argument('--out', type=str, default=None, help='default: DATA/tsdf_mesh.ply (.ply or .obj)')
     ap.add_argument('--view', type=int, default=10, help='fuse_depths: sources per view')
@@ -42,6 +43,8 @@ def parse_args(argv=None):
         ap.error('give either --resolution or --voxel')
     if a.resolution is None and a.voxel is None:
         a.resolution = 256
+    if a.simplify_faces is not None and a.simplify_faces < 1:
+        ap.error('--simplify_faces must be >= 1')
     if not a.trunc_voxels > 0:
         ap.error('--trunc_voxels must be > 0')
     a.pthresh = [float(v) for v in a.pthresh.split(',')]
@@ -89,6 +92,12 @@ def main(argv=None):
         sys.exit('tsdf_mesh: no surface (no valid cell crosses zero)')
     if a.largest:
         mesh = mesh.largest_component()
+    if a.simplify_faces is not None:
+        before = len(mesh)
+        mesh = mesh.simplify(target_faces=a.simplify_faces)
+        if mesh is None:
+            sys.exit('tsdf_mesh: --simplify_faces %d left no face' % a.simplify_faces)
+        print('simplified: %d -> %d faces' % (before, len(mesh)))
     if a.color:
         paths = find_images(a.data, pair['id_list'])
         if paths is None:
