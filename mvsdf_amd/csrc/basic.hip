@@ -2,6 +2,7 @@
 // device self-test of det_math.  C ABI entry points for these live at the bottom (see include/mvsdf_hip.h).
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include "tile_engine.h"
 #include "trace_params.h"
 #include "capi_util.h"
@@ -307,34 +308,6 @@ __global__ __launch_bounds__(512) void k_sdf_col0_bf(NET net, const float* __res
     if (tid < ROWS && row0 + tid < n) y[row0 + tid] = out[tid];
 }
 
-// NET = MvNetBf (bf16 weights + activations) or MvNetBs<NS> (bf16 weights, activations as NS bf16 terms: tile_engine_bf16s.h)
-template <int MT, int NTW, class NET>
-static int launch_col0_bf(const NET& net, const float* x, int n, float* y, hipStream_t s) {
-    const int rows = 16 * MT, d0 = 3 + 6 * net.multires;
-    const size_t lds = ((size_t)rows * net.S + ((rows * d0 + 3) & ~3) + rows * 4 + rows) * 4;
-    // MVSDF_BF_CARRY=1 (dev / tests): the weight-fetch scheme of k_sphere_trace (tile_engine_bf16.h, CARRIED) instead of the row-sample kernels' (ROLLING);
-    // same arithmetic, bit-identical results (tests/test_gpu_bf16.py)
-    static int carry = -1;
-    if (carry < 0) { const char* ev = mv_dev_env("MVSDF_BF_CARRY"); carry = ev ? atoi(ev) : 0; }
-    hipError_t e = carry ? hipFuncSetAttribute((const void*)k_sdf_col0_bf<MT, NTW, true, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                         : hipFuncSetAttribute((const void*)k_sdf_col0_bf<MT, NTW, false, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return mv_check(e, "mvsdf_sdf_col0: LDS attribute");
-    if (carry) hipLaunchKernelGGL((k_sdf_col0_bf<MT, NTW, true, NET>), dim3((n + rows - 1) / rows), dim3(512), lds, s, net, x, n, y);
-    else hipLaunchKernelGGL((k_sdf_col0_bf<MT, NTW, false, NET>), dim3((n + rows - 1) / rows), dim3(512), lds, s, net, x, n, y);
-    return mv_check(hipGetLastError(), "mvsdf_sdf_col0 (bf16)");
-}
-
-template <class NET>
-static int dispatch_col0_bf(const NET& nb, const float* x, int n, float* y, int mt, hipStream_t s) {
-    int mx = 0;
-    for (int l = 0; l < nb.n_layers - 1; ++l) mx = nb.L[l].NT > mx ? nb.L[l].NT : mx;
-    if (mx > 32) return mv_fail(-1, "mvsdf_sdf_col0: network too wide");
-    if (mx > 16) return mt >= 2 ? launch_col0_bf<2, 4>(nb, x, n, y, s) : launch_col0_bf<1, 4>(nb, x, n, y, s);
-    if (mt >= 4) return launch_col0_bf<4, 2>(nb, x, n, y, s);
-    if (mt >= 2) return launch_col0_bf<2, 2>(nb, x, n, y, s);
-    return launch_col0_bf<1, 2>(nb, x, n, y, s);
-}
-
 __global__ void k_det_math(int op, const float* __restrict__ x, int n, float* __restrict__ y0, float* __restrict__ y1) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -355,14 +328,33 @@ __global__ void k_det_math(int op, const float* __restrict__ x, int n, float* __
     if (y1) y1[i] = b;
 }
 
-template <int MT, int NTW, int NW, bool XR = false>
-static int launch_col0(const MvNet& net, const float* x, int n, float* y, hipStream_t s) {
-    const int rows = 16 * MT, d0 = 3 + 6 * net.multires;
-    const size_t lds = ((size_t)rows * net.S + ((rows * d0 + 3) & ~3) + rows * 4 + rows) * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)k_sdf_col0<MT, NTW, NW, XR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// one launch of a k_sdf_col0 / k_sdf_col0_bf instance over mt row tiles (the dynamic-LDS cap is raised on every call)
+template <class K, class NET>
+static int launch_col0(K kernel, int mt, int nw, const NET& net, const float* x, int n, float* y, hipStream_t s, const char* where) {
+    const int rows = 16 * mt;
+    const size_t lds = mv_col0_lds_bytes(net.S, net.multires, mt);
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return mv_check(e, "mvsdf_sdf_col0: LDS attribute");
-    hipLaunchKernelGGL((k_sdf_col0<MT, NTW, NW, XR>), dim3((n + rows - 1) / rows), dim3(64 * NW), lds, s, net, x, n, y);
-    return mv_check(hipGetLastError(), "mvsdf_sdf_col0");
+    hipLaunchKernelGGL(kernel, dim3((n + rows - 1) / rows), dim3(64 * nw), lds, s, net, x, n, y);
+    return mv_check(hipGetLastError(), where);
+}
+// mvsdf_sdf_col0's route (trace_route.h::mv_route_col0) mapped to its template instance of k_sdf_col0 (MvNet) or k_sdf_col0_bf (MvNetBs<NS, WT>; xr: bf_carry)
+template <class NET>
+static int dispatch_col0(const NET& net, int engine, const float* x, int n, float* y, int mt, hipStream_t s) {
+    const MvInst r = mv_route_col0(engine, mv_hidden_nt(net), mt, mv_trace_switches());
+    if (r.rc) return mv_fail(r.rc, r.why);
+#define MV_COL0(MT_, NTW_, NW_, XR_) case mv_inst_key(MT_, NTW_, NW_) + XR_: return launch_col0(k_sdf_col0<MT_, NTW_, NW_, XR_>, MT_, NW_, net, x, n, y, s, "mvsdf_sdf_col0")
+#define MV_COL0_BF(MT_, NTW_) case mv_inst_key(MT_, NTW_, 8): return r.xr ? launch_col0(k_sdf_col0_bf<MT_, NTW_, true, NET>, MT_, 8, net, x, n, y, s, "mvsdf_sdf_col0 (bf16)") \
+                                                                       : launch_col0(k_sdf_col0_bf<MT_, NTW_, false, NET>, MT_, 8, net, x, n, y, s, "mvsdf_sdf_col0 (bf16)")
+    if constexpr (std::is_same<NET, MvNet>::value) {
+        switch (mv_inst_key(r.mt, r.ntw, r.nw) + r.xr) {
+            MV_COL0(1, 2, 8, true); MV_COL0(1, 2, 8, false); MV_COL0(2, 2, 8, false); MV_COL0(4, 2, 8, false); MV_COL0(1, 4, 8, false); MV_COL0(2, 4, 8, false);
+            MV_COL0(1, 4, 4, false); MV_COL0(2, 4, 4, false); MV_COL0(4, 4, 4, false);
+        }
+    } else {
+        switch (mv_inst_key(r.mt, r.ntw, r.nw)) { MV_COL0_BF(1, 2); MV_COL0_BF(2, 2); MV_COL0_BF(4, 2); MV_COL0_BF(1, 4); MV_COL0_BF(2, 4); }
+    }
+    return mv_fail(-1, "mvsdf_sdf_col0: no such kernel instance");
 }
 
 // =============================================================================================================
@@ -522,42 +514,9 @@ int mvsdf_pack_bf16w_net(int n_layers, const float* const* w, const int* N, cons
 
 int mvsdf_sdf_col0(const MvsdfNetDesc* desc, const float* x, int n, float* y, int mt, void* stream) {
     if (!x || !y || n <= 0) return mv_fail(-1, "mvsdf_sdf_col0: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    if (desc && desc->trace_dtype == 1) return mv_fail(-2, "mvsdf_sdf_col0: trace_dtype 1 (bf16 weights AND 8-bit activations) was removed in round 5: use 3 (bf16x2: same speed, parity-checked)");
-    if (desc && (desc->trace_dtype == 3 || desc->trace_dtype == 4)) {   // bf16 weights x activations carried as 2 / 3 bf16 terms
-        MvNetBs<2> n2;
-        MvNetBs<3> n3;
-        int rcb = desc->trace_dtype == 3 ? mv_make_net_bs(desc, &n2, 2) : mv_make_net_bs(desc, &n3, 3);
-        if (rcb) return rcb;
-        return desc->trace_dtype == 3 ? dispatch_col0_bf(n2, x, n, y, mt, s) : dispatch_col0_bf(n3, x, n, y, mt, s);
-    }
-    if (desc && desc->trace_dtype == 5) {                       // fp32 weights and activations as three bf16 terms each, six products
-        MvNetBs<3, 3> n33;
-        int rcb = mv_make_net_bs(desc, &n33, 3);
-        if (rcb) return rcb;
-        return dispatch_col0_bf(n33, x, n, y, mt, s);
-    }
-    MvNet net;
-    int rc = mv_make_net_trace(desc, &net);
-    if (rc) return rc;
-    if (mt != 1 && mt != 2 && mt != 4 && mt != 49) return mv_fail(-1, "mvsdf_sdf_col0: mt must be 1, 2, 4 (row tiles per workgroup) or 49 (the sphere tracer's carried-ring engine)");
-    if (mt == 49) {                                                        // the sphere tracer's engine: weight ring carried across layers (two column tiles per wave: width <= 256)
-        if (mv_wide(net)) return mv_fail(-1, "mvsdf_sdf_col0: mt = 49 needs a hidden width <= 256");
-        return launch_col0<1, 2, 8, true>(net, x, n, y, s);
-    }
-    int maxnt = 0;
-    for (int l = 0; l < net.n_layers - 1; ++l) maxnt = net.L[l].NT > maxnt ? net.L[l].NT : maxnt;
-    const bool eight = maxnt >= 16;                              // 8 waves x 2 column tiles from width 256 on; narrow nets: 4 waves x 4 tiles
-    if (eight) {
-        if (mv_wide(net)) return mt >= 2 ? launch_col0<2, 4, 8>(net, x, n, y, s) : launch_col0<1, 4, 8>(net, x, n, y, s);
-        if (mt >= 4) return launch_col0<4, 2, 8>(net, x, n, y, s);
-        if (mt >= 2) return launch_col0<2, 2, 8>(net, x, n, y, s);
-        return launch_col0<1, 2, 8>(net, x, n, y, s);
-    }
-    if (mv_wide(net)) return mt >= 2 ? launch_col0<2, 8, 4>(net, x, n, y, s) : launch_col0<1, 8, 4>(net, x, n, y, s);
-    if (mt >= 4) return launch_col0<4, 4, 4>(net, x, n, y, s);
-    if (mt >= 2) return launch_col0<2, 4, 4>(net, x, n, y, s);
-    return launch_col0<1, 4, 4>(net, x, n, y, s);
+    const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, true);
+    if (ec.rc) return mv_fail(ec.rc, ec.why);
+    return mv_with_trace_net(desc, ec.engine, [&](const auto& net) { return dispatch_col0(net, ec.engine, x, n, y, mt, (hipStream_t)stream); });
 }
 
 int mvsdf_det_math(int op, const float* x, int n, float* y0, float* y1, void* stream) {

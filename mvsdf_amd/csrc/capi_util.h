@@ -4,14 +4,16 @@
 #include "mlp_common.h"
 #include "tile_engine_bf16.h"
 #include "tile_engine_bf16s.h"
+#include "trace_route.h"
 #include "../../include/mvsdf_hip.h"
 
 #include <stdlib.h>
 int mv_fail(int code, const char* msg);          // records msg, returns code
 // Development / A-B switches (alternative launch paths that are independent implementations of the same passes) exist only in a library built with
 // -DMVSDF_DEV_SWITCHES (mvsdf_amd/build.py: build(tag='dev'); tests/test_gpu_alt_paths.py and the sweep tools load it through MVSDF_LIB).  The product library never
-// reads them: its behaviour does not depend on stray environment variables.  The list: diff_route.h::MvDevSwitches for the differentiable passes; MVSDF_BF_CARRY,
-// MVSDF_TAIL_STOP, MVSDF_NFIRST, MVSDF_MT_FIRST, MVSDF_SGM_LGH / _LGV where they are read.  (Product switches, read with getenv directly: MVSDF_TAIL, MVSDF_SPLIT_ROWS.)
+// reads them: its behaviour does not depend on stray environment variables.  The list: diff_route.h::MvDevSwitches for the differentiable passes,
+// trace_route.h::MvTraceSwitches for the tracer (with its product switch MVSDF_TAIL); MVSDF_SGM_LGH / _LGV where they are read.  (The other product switch, read
+// with getenv directly: MVSDF_SPLIT_ROWS.)
 static inline const char* mv_dev_env(const char* name) {
 #ifdef MVSDF_DEV_SWITCHES
     return getenv(name);
@@ -20,6 +22,7 @@ static inline const char* mv_dev_env(const char* name) {
     return nullptr;
 #endif
 }
+const MvTraceSwitches& mv_trace_switches();       // the tracer's switches (trace_route.h), read once per process (trace.hip)
 int mv_check(hipError_t e, const char* where);   // 0 on success
 // mode 0: SDF net (PE input + skip chaining checked); 1: plain chain; 2: transposed packs (no chaining check)
 int mv_make_net_mode(const MvsdfNetDesc* d, MvNet* net, int mode);
@@ -42,8 +45,19 @@ static inline int mv_chain_ntw(const MvNet& net) {
     return maxnt <= 16 ? 2 : (maxnt <= 32 ? 4 : 0);
 }
 
-static inline bool mv_wide(const MvNet& net) {
+// 16-column tiles of the widest hidden layer (the maxnt of trace_route.h)
+template <class NET> static inline int mv_hidden_nt(const NET& net) {
     int maxnt = 0;
     for (int l = 0; l < net.n_layers - 1; ++l) maxnt = net.L[l].NT > maxnt ? net.L[l].NT : maxnt;
-    return maxnt > 16;
+    return maxnt;
+}
+// f(the tracing net of a descriptor in its engine's type: trace_route.h::MvTraceEngine), or the code of the descriptor's refusal
+template <class F> static inline int mv_with_trace_net(const MvsdfNetDesc* d, int engine, F&& f) {
+    int rc;
+    switch (engine) {
+        case MV_ENG_BS2: { MvNetBs<2> n; return (rc = mv_make_net_bs(d, &n, 2)) ? rc : f(n); }
+        case MV_ENG_BS3: { MvNetBs<3> n; return (rc = mv_make_net_bs(d, &n, 3)) ? rc : f(n); }
+        case MV_ENG_X3: { MvNetBs<3, 3> n; return (rc = mv_make_net_bs(d, &n, 3)) ? rc : f(n); }
+        default: { MvNet n; return (rc = mv_make_net_trace(d, &n)) ? rc : f(n); }
+    }
 }

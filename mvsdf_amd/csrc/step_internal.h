@@ -66,4 +66,4 @@ const MvDevSwitches& mv_dev_switches();                            // the develo
 // stage 1 of mvsdf_trace_stage for a caller whose previous launch (mv_step_prologue) zeroed the counters
 extern "C" int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
-                              unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int rpw, void* stream);
+                              unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);

@@ -11,10 +11,11 @@
 //                    Also: sphere intersection (rend_util.py:141-162), left-out projection (ray_tracing.py:79-84),
 //                    and appending unfinished / non-hit rays to the sample work list.
 //   k_ray_samples  : ray_sampler + secant (ray_tracing.py:198-278) and minimal_sdf_points (280-308): each work item
-//                    is one ray x n_steps samples; rows of RPW rays are evaluated in full tiles, then one thread per
+//                    is one ray x n_steps samples; the rows are evaluated in full tiles, then one wave per
 //                    ray does the argmin / first-sign-change logic and the (dependent) secant rounds run compacted.
 //
-// No host synchronisation anywhere: list lengths stay on the device, grids are sized for the worst case.
+// No host synchronisation anywhere: list lengths stay on the device, grids are sized for the worst case.  The launch rules (instances, grids, tail filling) and
+// the workspace layout: trace_route.h.
 #include <stdlib.h>
 #include <type_traits>
 #include "tile_engine.h"
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
 
 // ---------------------------------------------------------------------------------------------------------------
 struct SampleCtx {
-    const float* cam_loc; const float* dirs; int R, P, training, RPW;
+    const float* cam_loc; const float* dirs; int R, P, training;
     const float* intervals; const float* steps;
     float* o_points; uint8_t* o_mask; float* o_dists;
     const float* w_zmin; const float* w_zmax;
@@ -699,27 +700,14 @@ __global__ __launch_bounds__(64 * NW, (mv_net_wt<NET>::v == 3 && NTW == 2 && MT 
     mv_eval_rows<MT, NTW, NW, NET>(net, tp, c, sg, q0, smem, n_list);
 }
 // ---------------------------------------------------------------------------------------------------------------
-// tail filling switches: MVSDF_TAIL=0 turns it off, MVSDF_TAIL=2 also enables it for the bf16 engine (measured slower there: DESIGN.md); MVSDF_TAIL_PROBE=1 makes mvsdf_trace_tail_probe() return per-workgroup records
-static int mv_tail_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MVSDF_TAIL"); v = e ? atoi(e) : 1; }
-    return v;
+// the tracer's switches (trace_route.h), read once per process; the development ones only by a library built with them (capi_util.h::mv_dev_env)
+const MvTraceSwitches& mv_trace_switches() {
+    static const MvTraceSwitches sw = mv_trace_switches_from_env([](const char* name) -> const char* { return getenv(name); }, mv_dev_env);
+    return sw;
 }
-static unsigned* g_tail_probe = nullptr;
-static unsigned* mv_tail_probe() { return g_tail_probe; }
 // dev hook (tools/tail_probe.py): device buffer [workgroups][4] that k_sphere_trace fills with {rounds, units helped, ticks tracing, ticks helping}
+static unsigned* g_tail_probe = nullptr;
 extern "C" void mv_trace_set_tail_probe(unsigned* buf) { g_tail_probe = buf; }
-// the min-sdf rows' own sample-value buffer: the second [R][n_steps] buffer of the workspace (behind the sampler's buffer and the rest lists)
-static float* mv_minsdf_sv(float* ws, int R, int n_steps) {
-    float* sec_state = ws + 2 * (size_t)R;
-    int* w_list = (int*)(sec_state + 4 * (size_t)R);
-    float* sv = (float*)(w_list + 3 * (size_t)R);
-    int* list_rest = (int*)(sv + (size_t)R * n_steps);
-    return (float*)(list_rest + 2 * (size_t)R);
-}
-
-// is the tail filling on for this call?  (mt1: row tiles per sphere-tracing workgroup.)  Only for grids of <= 256 workgroups (one per CU): with more,
-// a finished workgroup's slot is wanted by a tracing workgroup that has not started yet -- helping would delay it.
 static int mv_cu_count() {                                         // compute units of the current device (256 on an unpartitioned MI355X)
     static int n = 0;
     if (n == 0) {
@@ -729,190 +717,116 @@ static int mv_cu_count() {                                         // compute un
     }
     return n;
 }
-// The bound is also what makes the helpers' one wait safe (a helper that over-claimed a tile sleeps until the rows it owns are published, see the claim
-// loop in k_sphere_trace): with at most one workgroup per compute unit OF THIS DEVICE every workgroup of the grid can be resident at once, so the tracing
-// workgroups a waiting helper depends on never wait for its slot.  (A partitioned device reports fewer compute units and gets no tail filling at c2.)
-template <class NET>
-static bool mv_tail_on(int training, const float* steps, int R, int mt1) {
-    constexpr bool is_bf = !std::is_same<NET, MvNet>::value;
-    const int grid1 = (R + 8 * mt1 - 1) / (8 * mt1);
-    // on by default for the fmaf-chain engine and -- above 2048 rays -- for the three-weight-term engine 'f32x3' (round 6, three alternating runs each: c3 4.012 -> 3.961 ms,
-    // c5 share 2.270 -> 2.238; c2 1.470 vs 1.473: no difference, left off); the bf16-weight engines lose (c5 share bf16x2 1.506 -> 1.545): MVSDF_TAIL=2 only
-    const int need = !is_bf ? 1 : ((mv_net_wt<NET>::v == 3 && R > 2048) ? 1 : 2);
-    return training && steps && mv_tail_mode() >= need && grid1 <= mv_cu_count();
-}
 
-template <class NET>
-static size_t trace_lds_bytes(const NET& net, int MT, int sv_floats, int rpw, bool sphere = false) {
-    const int rows = 16 * MT, d0 = 3 + 6 * net.multires;
-    size_t f = (size_t)mv_act_rows<NET>(rows, sphere) * net.S + ((rows * d0 + 3) & ~3) + rows * 4 + rows + sv_floats;
-    return f * 4 + 16 + (size_t)rpw * (8 * 4 + 4) + 16;
-}
+// what every launch of one call shares (tail: trace_route.h::mv_tail_on, filled by mv_trace_launch)
+struct TraceCall {
+    int engine, R, P, training;
+    bool tail;
+    const MvTraceParams* tp;
+    const float *cam_loc, *dirs, *intervals, *steps;
+    const uint8_t* om;
+    float *points, *dists;
+    uint8_t* mask;
+    void* ws; unsigned long long* counters; hipStream_t stream;
+};
 
 template <int MT, int NTW, int NW, class NET>
-static hipError_t launch_stage1(const NET& net, const MvTraceParams& tp, const float* cam_loc, const float* dirs, const uint8_t* om, int B, int P,
-                                int training, const float* steps, int mt2, float* points, uint8_t* mask, float* dists, float* ws,
-                                unsigned long long* counters, hipStream_t stream) {
-    const int R = B * P, NR = 8 * MT;
-    float* w_zmin = ws;
-    float* w_zmax = w_zmin + R;
-    int* w_list = (int*)(w_zmax + 5 * (size_t)R);
-    int* w_list_min = w_list + R;
-    TailCtx tail;
-    memset(&tail, 0, sizeof(tail));
-    const int grid1 = (R + NR - 1) / NR;
-    // fp32 engine only: with the bf16 engine a tile takes half the time, the launch that follows is bound by its secant chains and the helpers
-    // cost the sphere kernel more than they save (measured: c2 +10 us, c5share +20 us per step)
-    if (mv_tail_on<NET>(training, steps, R, MT)) {
-        tail.enable = 1;
-        tail.steps = steps;
-        tail.sv = mv_minsdf_sv(ws, R, tp.n_steps);
-        tail.unit_rows = 16 * MT;
-        tail.spin = 1;
-        tail.probe = mv_tail_probe();
-        static int stop_env = -1;
-        if (stop_env < 0) { const char* e = mv_dev_env("MVSDF_TAIL_STOP"); stop_env = e ? atoi(e) : -1; }
-        tail.stop_left = stop_env >= 0 ? stop_env : grid1 / 4;      // (swept at c2: 0 / 16 / 32 / 48 / 64 of 256 -> tracer 1575 / 1527 / 1521 / 1507 / 1507 us, off: 1549)
-    }
-    const size_t lds1 = trace_lds_bytes(net, MT, 0, 0, NTW < 4);
+static hipError_t launch_stage1(const NET& net, const TraceCall& t) {
+    const MvTraceWs w = mv_trace_ws(t.R, t.tp->n_steps);
+    TailCtx tail = {};
+    if (t.tail) tail = {t.steps, mv_ws_at<float>(t.ws, w.sv_min), 16 * MT, 1, 1, mv_tail_stop_left(t.R, MT, mv_trace_switches()), g_tail_probe};
+    const size_t lds1 = mv_trace_lds_bytes(net.S, net.multires, MT, mv_act_rows<NET>(16 * MT, NTW < 4));
     static size_t set1 = 0;                                     // raise the dynamic-LDS cap once per size (per instantiation)
     if (lds1 > set1) {
         hipError_t e = hipFuncSetAttribute((const void*)k_sphere_trace<MT, NTW, NW, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
         if (e != hipSuccess) return e;
         set1 = lds1;
     }
-    hipLaunchKernelGGL((k_sphere_trace<MT, NTW, NW, NET>), dim3(grid1), dim3(64 * NW), lds1, stream, net, tp, cam_loc, dirs, om, R, P,
-                       training, points, mask, dists, w_zmin, w_zmax, w_list, w_list_min, counters, tail);
+    hipLaunchKernelGGL((k_sphere_trace<MT, NTW, NW, NET>), dim3(mv_sphere_grid(t.R, MT)), dim3(64 * NW), lds1, t.stream, net, *t.tp, t.cam_loc, t.dirs, t.om, t.R, t.P,
+                       t.training, t.points, t.mask, t.dists, mv_ws_at<float>(t.ws, w.w_zmin), mv_ws_at<float>(t.ws, w.w_zmax), mv_ws_at<int>(t.ws, w.w_list),
+                       mv_ws_at<int>(t.ws, w.w_list_min), t.counters, tail);
     return hipGetLastError();
 }
 
+// part 1: sampler rows + their reduction (the hit mask is FINAL after it); 2: secant + min-sdf rows in one launch; 4: min-sdf rows + their reduction alone (own
+// sample-value buffer: may run concurrently with part 1 on another stream); 8: secant alone
 template <int MT, int NTW, int NW, class NET>
-static hipError_t launch_stage2(const NET& net, const MvTraceParams& tp, const float* cam_loc, const float* dirs, int B, int P, int training,
-                                const float* intervals, const float* steps, float* points, uint8_t* mask, float* dists, float* ws,
-                                unsigned long long* counters, int parts, int mt1, hipStream_t stream) {
-    // parts bit 0: sampler rows + their reduction (the hit mask is FINAL after it); bit 1: secant + min-sdf rows in one launch;
-    // bit 2: min-sdf rows + their reduction alone (own sample-value buffer: may run concurrently with bit 0 on another stream); bit 3: secant alone
-    const int R = B * P, ROWS = 16 * MT;
-    float* w_zmin = ws;
-    float* w_zmax = w_zmin + R;
-    float* sec_state = w_zmax + R;                               // [4][R]
-    int* w_list = (int*)(sec_state + 4 * (size_t)R);
-    int* w_list_min = w_list + R;
-    int* sec_list = w_list_min + R;
-    float* sv = (float*)(sec_list + R);                          // [R * n_steps]
-    const size_t lds2 = trace_lds_bytes(net, MT, 0, 0);
+static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
+    const MvTraceParams& tp = *t.tp;
+    const MvTraceWs w = mv_trace_ws(t.R, tp.n_steps);
+    const size_t lds2 = mv_trace_lds_bytes(net.S, net.multires, MT, mv_act_rows<NET>(16 * MT));
     static size_t set2 = 0;
     if (lds2 > set2) {
         hipError_t e = hipFuncSetAttribute((const void*)k_ray_samples<MT, NTW, NW, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
         if (e != hipSuccess) return e;
         set2 = lds2;
     }
-    static int nf_env = -1;
-    if (nf_env < 0) { const char* e = mv_dev_env("MVSDF_NFIRST"); nf_env = e ? atoi(e) : 12; if (nf_env < 2) nf_env = 2; }
-    const int n = tp.n_steps, nf = nf_env < n ? nf_env : n;
+    const int n = tp.n_steps, nf = mv_first_window(n, mv_trace_switches());
+    const MvSampleGrids g = mv_sample_grids(t.R, n, nf, MT, t.training, t.tail, MV_RED_WAVES);
+    int *w_list = mv_ws_at<int>(t.ws, w.w_list), *w_list_min = mv_ws_at<int>(t.ws, w.w_list_min);
     SampleCtx c;
-    c.cam_loc = cam_loc; c.dirs = dirs; c.R = R; c.P = P; c.training = training; c.RPW = 0; c.intervals = intervals; c.steps = steps;
-    c.o_points = points; c.o_mask = mask; c.o_dists = dists; c.w_zmin = w_zmin; c.w_zmax = w_zmax; c.sec_state = sec_state;
-    c.sec_list = sec_list; c.sv = sv; c.counters = counters;
-    c.list_rest = (int*)(sv + (size_t)R * n); c.src_rest = c.list_rest + R; c.n_first = nf;
-    // worst-case grids (every ray listed); blocks beyond the device-side counts exit at once
-    auto blocks_for = [&](int per_item) { return (int)(((long long)R * per_item + ROWS - 1) / ROWS); };
-    const int sec_blocks = (R + 15) / 16, red_blocks = (R + MV_RED_WAVES - 1) / MV_RED_WAVES;   // one wave per listed ray, 16 per workgroup
+    c.cam_loc = t.cam_loc; c.dirs = t.dirs; c.R = t.R; c.P = t.P; c.training = t.training; c.intervals = t.intervals; c.steps = t.steps;
+    c.o_points = t.points; c.o_mask = t.mask; c.o_dists = t.dists; c.w_zmin = mv_ws_at<float>(t.ws, w.w_zmin); c.w_zmax = mv_ws_at<float>(t.ws, w.w_zmax);
+    c.sec_state = mv_ws_at<float>(t.ws, w.sec_state); c.sec_list = mv_ws_at<int>(t.ws, w.sec_list); c.sv = mv_ws_at<float>(t.ws, w.sv); c.counters = t.counters;
+    c.list_rest = mv_ws_at<int>(t.ws, w.list_rest); c.src_rest = mv_ws_at<int>(t.ws, w.src_rest); c.n_first = nf;
     const RowSeg none = {nullptr, nullptr, 0, 0, 1, 0, 0};
-    if (parts & 1) {
+    const dim3 wg(64 * NW), red_wg(64 * MV_RED_WAVES);
+    if (part == 1) {
         // sampler rays: first window of nf samples, then the other samples of the rays the window left open
-        const RowSeg first = {w_list, nullptr, (int)MV_CNT_N_SAMPLER, 0, nf, blocks_for(nf), 0};
-        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(first.blocks), dim3(64 * NW), lds2, stream, net, tp, c, first, none, 0);
-        hipLaunchKernelGGL(k_reduce_items, dim3(red_blocks), dim3(64 * MV_RED_WAVES), 0, stream, tp, c, w_list, (const int*)nullptr, (int)MV_CNT_N_SAMPLER, 0);
+        const RowSeg first = {w_list, nullptr, (int)MV_CNT_N_SAMPLER, 0, nf, g.first, 0};
+        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.first), wg, lds2, t.stream, net, tp, c, first, none, 0);
+        hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, w_list, (const int*)nullptr, (int)MV_CNT_N_SAMPLER, 0);
         if (nf < n) {
-            const RowSeg rest = {c.list_rest, c.src_rest, (int)MV_CNT_N_SAMPLER_REST, nf, n - nf, blocks_for(n - nf), 0};
-            hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(rest.blocks), dim3(64 * NW), lds2, stream, net, tp, c, rest, none, 0);
-            hipLaunchKernelGGL(k_reduce_items, dim3(red_blocks), dim3(64 * MV_RED_WAVES), 0, stream, tp, c, c.list_rest, c.src_rest, (int)MV_CNT_N_SAMPLER_REST, 1);
+            const RowSeg rest = {c.list_rest, c.src_rest, (int)MV_CNT_N_SAMPLER_REST, nf, n - nf, g.rest, 0};
+            hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.rest), wg, lds2, t.stream, net, tp, c, rest, none, 0);
+            hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, c.list_rest, c.src_rest, (int)MV_CNT_N_SAMPLER_REST, 1);
         }
+    } else if (part == 8) {
+        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.sec), wg, lds2, t.stream, net, tp, c, none, none, g.sec);
+    } else if (part == 2 || t.training) {
+        // min-sdf rows, behind the secant chains of the same launch (2) or alone (4).  With tail filling they are a queue that k_sphere_trace's finished workgroups
+        // have already served: units claimed dynamically (the grid stays worst-case: workgroups without a unit exit at once).  Their values go to the second
+        // sample-value buffer when they run alone or were started by the tail filling.
+        if (part == 4 || t.tail) c.sv = mv_ws_at<float>(t.ws, w.sv_min);
+        const int sec = part == 2 ? g.sec : 0;
+        const RowSeg minsdf = {w_list_min, nullptr, (int)MV_CNT_N_MINSDF, 0, n, g.minsdf, t.tail ? 1 : 0};
+        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(sec + g.minsdf), wg, lds2, t.stream, net, tp, c, minsdf, none, sec);
+        if (t.training) hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
     }
-    if (parts & 2) {
-        // with tail filling the min-sdf rows are a queue that k_sphere_trace's finished workgroups have already served: own value buffer,
-        // units claimed dynamically (the grid stays worst-case: workgroups without a unit exit at once)
-        const bool tail = mv_tail_on<NET>(training, steps, R, mt1);
-        SampleCtx cm = c;
-        if (tail) cm.sv = mv_minsdf_sv(ws, R, n);
-        const RowSeg minsdf = {w_list_min, nullptr, (int)MV_CNT_N_MINSDF, 0, n, training ? blocks_for(n) + (tail ? 1 : 0) : 0, tail ? 1 : 0};
-        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(sec_blocks + minsdf.blocks), dim3(64 * NW), lds2, stream, net, tp, cm, minsdf, none,
-                           sec_blocks);
-        if (training) hipLaunchKernelGGL(k_reduce_items, dim3(red_blocks), dim3(64 * MV_RED_WAVES), 0, stream, tp, cm, w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
-    }
-    if ((parts & 4) && training) {
-        SampleCtx c2 = c;
-        c2.sv = (float*)(c.src_rest + R);                        // second sample-value buffer [R * n_steps]
-        const bool tail = mv_tail_on<NET>(training, steps, R, mt1);
-        const RowSeg minsdf = {w_list_min, nullptr, (int)MV_CNT_N_MINSDF, 0, n, blocks_for(n) + (tail ? 1 : 0), tail ? 1 : 0};
-        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(minsdf.blocks), dim3(64 * NW), lds2, stream, net, tp, c2, minsdf, none, 0);
-        hipLaunchKernelGGL(k_reduce_items, dim3(red_blocks), dim3(64 * MV_RED_WAVES), 0, stream, tp, c2, w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
-    }
-    if (parts & 8)
-        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(sec_blocks), dim3(64 * NW), lds2, stream, net, tp, c, none, none, sec_blocks);
     return hipGetLastError();
 }
 
-// mt1: row tiles per workgroup of the sphere-tracing kernel (8*mt1 rays); mt2: row tiles per chunk of the sample-row kernels.
-#ifndef MV_SPHERE_NW16
-#define MV_SPHERE_NW16 1                                            // (-DMV_SPHERE_NW16=0: the 8-wave x 2-tile form, for A/B builds -- tools/pp_ab.sh)
-#endif
+// The route of a stage (trace_route.h) mapped to its template instance; part 0: the sphere kernel.  An instance the engine does not list is refused: the 4-wave
+// forms exist for the fp32 engine only, the sixteen-wave sphere form replaces <1, 2, 8> for the three-weight-term engine.
+#define MV_S1(ON_, MT_, NTW_, NW_) case mv_inst_key(MT_, NTW_, NW_): if constexpr (ON_) return launch_stage1<MT_, NTW_, NW_>(net, t); break
+#define MV_S2(ON_, MT_, NTW_, NW_) case mv_inst_key(MT_, NTW_, NW_): if constexpr (ON_) return launch_stage2<MT_, NTW_, NW_>(net, t, part); break
 template <class NET>
-hipError_t mv_trace_launch(int stages, const NET& net, const MvTraceParams& tp, int mt1, int mt2, const float* cam_loc, const float* dirs,
-                           const uint8_t* om, int B, int P, int training, const float* intervals, const float* steps, float* points,
-                           uint8_t* mask, float* dists, float* ws, unsigned long long* counters, hipStream_t stream) {
-    int maxnt = 0;
-    for (int l = 0; l < net.n_layers - 1; ++l) maxnt = net.L[l].NT > maxnt ? net.L[l].NT : maxnt;
-    if (maxnt > 32) return hipErrorInvalidValue;
-    // waves per workgroup: 8 (two per SIMD) once there are >= 2 column tiles per wave to share (width 256 up; forcing 4 there measured 0.78 -> 0.99 ms, round 3)
-    constexpr bool is_bf = !std::is_same<NET, MvNet>::value;                    // the bf16-MFMA engines are built for 8-wave workgroups only
-    const bool eight = is_bf || maxnt >= 16;
-    const bool wide = maxnt > 16;
-    hipError_t e = hipSuccess;
-    auto eff = [&](int mt) { return wide ? (mt >= 2 ? 2 : 1) : (mt >= 4 ? 4 : (mt >= 2 ? 2 : 1)); };   // the instantiation a requested tile count maps to
-    const int mt1_eff = eff(mt1), mt2_eff = eff(mt2);
-#define MV_S1(MT_, NTW_, NW_) e = launch_stage1<MT_, NTW_, NW_>(net, tp, cam_loc, dirs, om, B, P, training, steps, mt2_eff, points, mask, dists, ws, counters, stream)
-#define MV_S2(MT_, NTW_, NW_) e = launch_stage2<MT_, NTW_, NW_>(net, tp, cam_loc, dirs, B, P, training, intervals, steps, points, mask, dists, ws, counters, (stages >> 1) & 15, mt1_eff, stream)
-    if (stages & 1) {
-        if (eight) {
-            if (wide) { if (mt1 >= 2) MV_S1(2, 4, 8); else MV_S1(1, 4, 8); }
-            else if (mt1 >= 4) MV_S1(4, 2, 8); else if (mt1 >= 2) MV_S1(2, 2, 8);
-            else {
-                // one 16-row tile per workgroup, three weight terms: SIXTEEN waves x one column tile (late round 6).  The evaluations of this kernel wait for each
-                // other, a wave's share of a layer is a latency chain (k-blocks of 3 x 2 dependent instructions, then the softplus epilogue): half the chain per
-                // wave.  tools/micro/x3_engine_rounds.hip: 38.4 (8 waves x 2 tiles) -> 33.7 us per evaluation with the ping-pong tiles.  Same instruction sequence
-                // per output column: same bits.
-                if constexpr (MV_SPHERE_NW16 != 0 && mv_net_wt<NET>::v == 3) MV_S1(1, 1, 16); else MV_S1(1, 2, 8);
-            }
-        } else if constexpr (!is_bf) {
-            if (wide) { if (mt1 >= 2) MV_S1(2, 8, 4); else MV_S1(1, 8, 4); }
-            else if (mt1 >= 4) MV_S1(4, 4, 4); else if (mt1 >= 2) MV_S1(2, 4, 4); else MV_S1(1, 4, 4);
-        }
-        if (e != hipSuccess) return e;
+static hipError_t mv_launch_inst(const MvInst& r, const NET& net, const TraceCall& t, int part) {
+    constexpr bool f32 = std::is_same<NET, MvNet>::value, nw16 = MV_SPHERE_NW16 != 0 && mv_net_wt<NET>::v == 3;
+    if (r.rc) return hipErrorInvalidValue;
+    if (part == 0) switch (mv_inst_key(r.mt, r.ntw, r.nw)) {
+        MV_S1(nw16, 1, 1, 16); MV_S1(!nw16, 1, 2, 8); MV_S1(true, 2, 2, 8); MV_S1(true, 4, 2, 8); MV_S1(true, 1, 4, 8); MV_S1(true, 2, 4, 8);
+        MV_S1(f32, 1, 4, 4); MV_S1(f32, 2, 4, 4); MV_S1(f32, 4, 4, 4);
+    } else switch (mv_inst_key(r.mt, r.ntw, r.nw)) {
+        MV_S2(true, 1, 2, 8); MV_S2(true, 2, 2, 8); MV_S2(true, 4, 2, 8); MV_S2(true, 1, 4, 8); MV_S2(true, 2, 4, 8);
+        MV_S2(f32, 1, 4, 4); MV_S2(f32, 2, 4, 4); MV_S2(f32, 4, 4, 4);
     }
-    // the two sampler launches are small (about one wave of workgroups at a few thousand rays): 16-row chunks spread them over more
-    // CUs (measured 285 -> 241 us at 2048 rays).  MVSDF_MT_FIRST overrides (dev).
-    static int mtf_env = -1;
-    if (mtf_env < 0) { const char* e2 = mv_dev_env("MVSDF_MT_FIRST"); mtf_env = e2 ? atoi(e2) : 0; }
-    for (int part = 1; part <= 8; part <<= 1) {
-        if (!((stages >> 1) & part)) continue;
-        // (three weight terms: a 16-row evaluation is bound by its 3.1 MB weight stream, two tiles share it: c2 1.687 -> 1.664 ms, c5 share 2.539 -> 2.483)
-        const int mtp = part == 1 ? (mtf_env > 0 ? mtf_env : (mv_net_wt<NET>::v == 3 ? (mt2 > 2 ? 2 : mt2) : ((long long)B * P <= 4096 ? 1 : mt2))) : mt2;
-        const int st_ = stages;
-        stages = (stages & 1) | (part << 1);                    // MV_S2 reads `stages` for the parts to launch
-        if (eight) {
-            if (wide) { if (mtp >= 2) MV_S2(2, 4, 8); else MV_S2(1, 4, 8); }
-            else if (mtp >= 4) MV_S2(4, 2, 8); else if (mtp >= 2) MV_S2(2, 2, 8); else MV_S2(1, 2, 8);
-        } else if constexpr (!is_bf) {
-            if (wide) { if (mtp >= 2) MV_S2(2, 8, 4); else MV_S2(1, 8, 4); }
-            else if (mtp >= 4) MV_S2(4, 4, 4); else if (mtp >= 2) MV_S2(2, 4, 4); else MV_S2(1, 4, 4);
-        }
-        stages = st_;
-        if (e != hipSuccess) return e;
-    }
+    return hipErrorInvalidValue;
+}
 #undef MV_S1
 #undef MV_S2
+
+// stages bit 0: the sphere-tracing launch; bits 1..4: the parts 1, 2, 4, 8 of launch_stage2
+template <class NET>
+static hipError_t mv_trace_launch(int stages, const NET& net, TraceCall t, int mt, int mt_samples) {
+    const MvTraceSwitches& sw = mv_trace_switches();
+    const int maxnt = mv_hidden_nt(net);
+    const MvInst s1 = mv_route_sphere(t.engine, maxnt, mt);
+    if (s1.rc) return hipErrorInvalidValue;
+    t.tail = mv_tail_on(t.engine, t.training, t.steps != nullptr, t.R, s1.mt, mv_cu_count(), sw);
+    hipError_t e = (stages & 1) ? mv_launch_inst(s1, net, t, 0) : hipSuccess;
+    for (int part = 1; part <= 8 && e == hipSuccess; part <<= 1)
+        if ((stages >> 1) & part) e = mv_launch_inst(mv_route_samples(t.engine, maxnt, mt_samples, t.R, part, sw), net, t, part);
     return e;
 }
 
@@ -1146,68 +1060,43 @@ __global__ __launch_bounds__(1024) void k_gen_sort_list(int* __restrict__ list, 
     }
 }
 
-struct GenWs { float* w_zmin; float* w_zmax; float* sec_state; int* w_list; int* w_list_min; int* sec_list; float* sv; int* list_rest; int* src_rest; };
-static GenWs mv_gen_ws(void* ws, int R, int n) {
-    GenWs g;
-    g.w_zmin = (float*)ws; g.w_zmax = g.w_zmin + R; g.sec_state = g.w_zmax + R;
-    g.w_list = (int*)(g.sec_state + 4 * (size_t)R); g.w_list_min = g.w_list + R; g.sec_list = g.w_list_min + R;
-    g.sv = (float*)(g.sec_list + R); g.list_rest = (int*)(g.sv + (size_t)R * n); g.src_rest = g.list_rest + R;
-    return g;
-}
-
 // =============================================================================================================
 extern "C" {
 
-size_t mvsdf_trace_workspace_bytes_n(int R, int n_steps) { return (size_t)(R > 0 ? R : 0) * (44 + 8 * (size_t)(n_steps > 0 ? n_steps : 0)) + 256; }
+size_t mvsdf_trace_workspace_bytes_n(int R, int n_steps) { return mv_trace_ws(R, n_steps).total; }
 size_t mvsdf_trace_workspace_bytes(int R) { return mvsdf_trace_workspace_bytes_n(R, 128); }
 
 static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
-                      size_t workspace_bytes, int mt, int rpw, void* stream) {
-    MvNet net;
-    MvNetBs<2> net2;
-    MvNetBs<3> net3;
-    MvNetBs<3, 3> net33;
-    const int td = desc ? desc->trace_dtype : 0;
-    if (td == 1) return mv_fail(-2, "mvsdf_trace: trace_dtype 1 (bf16 weights AND 8-bit activations) was removed in round 5: use 3 (bf16x2: same speed, parity-checked)");
-    int rc = (td == 3 ? mv_make_net_bs(desc, &net2, 2) : (td == 4 ? mv_make_net_bs(desc, &net3, 3) :
-             (td == 5 ? mv_make_net_bs(desc, &net33, 3) : mv_make_net_trace(desc, &net))));
-    if (rc) return rc;
-    if (!tp || !cam_loc || !ray_dirs || !object_mask || !intervals || !points || !mask || !dists || !counters || !workspace)
-        return mv_fail(-1, "mvsdf_trace: null argument");
-    if (B <= 0 || P <= 0 || (long long)B * P >= (1 << 28)) return mv_fail(-1, "mvsdf_trace: B*P out of range");
-    if (training && !minsdf_steps) return mv_fail(-1, "mvsdf_trace: training needs minsdf_steps");
-    if (tp->n_steps < 2 || tp->n_steps > 1024 || tp->line_step_iters < 0 || tp->line_step_iters > 30)
-        return mv_fail(-1, "mvsdf_trace: tracer parameters out of range");
-    const int R = B * P;
-    if (workspace_bytes < mvsdf_trace_workspace_bytes_n(R, tp->n_steps)) return mv_fail(-1, "mvsdf_trace: workspace too small");
-    if (rpw < 1) rpw = 1;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    if ((stages & 1) && !(stages & 0x100)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them
-    if (e != hipSuccess) return mv_check(e, "mvsdf_trace: memset");
-    if (td == 3)
-        e = mv_trace_launch(stages, net2, *tp, mt, rpw, cam_loc, ray_dirs, object_mask, B, P, training, intervals,
-                            minsdf_steps ? minsdf_steps : intervals, points, mask, dists, (float*)workspace, counters, s);
-    else if (td == 4)
-        e = mv_trace_launch(stages, net3, *tp, mt, rpw, cam_loc, ray_dirs, object_mask, B, P, training, intervals,
-                            minsdf_steps ? minsdf_steps : intervals, points, mask, dists, (float*)workspace, counters, s);
-    else if (td == 5)
-        e = mv_trace_launch(stages, net33, *tp, mt, rpw, cam_loc, ray_dirs, object_mask, B, P, training, intervals,
-                            minsdf_steps ? minsdf_steps : intervals, points, mask, dists, (float*)workspace, counters, s);
-    else
-        e = mv_trace_launch(stages, net, *tp, mt, rpw, cam_loc, ray_dirs, object_mask, B, P, training, intervals,
-                            minsdf_steps ? minsdf_steps : intervals, points, mask, dists, (float*)workspace, counters, s);
-    return mv_check(e, "mvsdf_trace");
+                      size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+    const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, false);
+    if (ec.rc) return mv_fail(ec.rc, ec.why);
+    return mv_with_trace_net(desc, ec.engine, [&](const auto& net) {
+        if (!tp || !cam_loc || !ray_dirs || !object_mask || !intervals || !points || !mask || !dists || !counters || !workspace)
+            return mv_fail(-1, "mvsdf_trace: null argument");
+        if (B <= 0 || P <= 0 || (long long)B * P >= (1 << 28)) return mv_fail(-1, "mvsdf_trace: B*P out of range");
+        if (training && !minsdf_steps) return mv_fail(-1, "mvsdf_trace: training needs minsdf_steps");
+        if (tp->n_steps < 2 || tp->n_steps > 1024 || tp->line_step_iters < 0 || tp->line_step_iters > 30)
+            return mv_fail(-1, "mvsdf_trace: tracer parameters out of range");
+        const int R = B * P;
+        if (workspace_bytes < mvsdf_trace_workspace_bytes_n(R, tp->n_steps)) return mv_fail(-1, "mvsdf_trace: workspace too small");
+        hipStream_t s = (hipStream_t)stream;
+        hipError_t e = hipSuccess;
+        if ((stages & 1) && !(stages & 0x100)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them
+        if (e != hipSuccess) return mv_check(e, "mvsdf_trace: memset");
+        const TraceCall t = {ec.engine, R, P, training, false, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
+                             points, dists, mask, workspace, counters, s};
+        return mv_check(mv_trace_launch(stages, net, t, mt, mt_samples), "mvsdf_trace");
+    });
 }
 
 int mvsdf_trace(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                 const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                 float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
-                size_t workspace_bytes, int mt, int rpw, void* stream) {
+                size_t workspace_bytes, int mt, int mt_samples, void* stream) {
     return trace_impl(7, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
-                      workspace, workspace_bytes, mt, rpw, stream);
+                      workspace, workspace_bytes, mt, mt_samples, stream);
 }
 
 /* The launches of mvsdf_trace separately (same arguments, same workspace): stage 1 = sphere tracing (zeroes the counters),
@@ -1217,19 +1106,19 @@ int mvsdf_trace(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const floa
 int mvsdf_trace_stage(int stage, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
-                      size_t workspace_bytes, int mt, int rpw, void* stream) {
+                      size_t workspace_bytes, int mt, int mt_samples, void* stream) {
     if (stage < 1 || stage > 6) return mv_fail(-1, "mvsdf_trace_stage: stage must be 1..6");
     static const int bits[7] = {0, 1, 6, 2, 4, 8, 16};
     return trace_impl(bits[stage], desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
-                      workspace, workspace_bytes, mt, rpw, stream);
+                      workspace, workspace_bytes, mt, mt_samples, stream);
 }
 
 // the step driver's form of stage 1: the counters were zeroed by k_step_prologue (one fill node less per step)
 int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
-                              unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int rpw, void* stream) {
+                              unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
     return trace_impl(1 | 0x100, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
-                      workspace, workspace_bytes, mt, rpw, stream);
+                      workspace, workspace_bytes, mt, mt_samples, stream);
 }
 
 /* ---- generic tracer for an opaque SDF callable (see the kernel comments above) ---- */
@@ -1272,12 +1161,13 @@ int mvsdf_tracegen_finish(const MvsdfTraceParams* tp, const float* cam_loc, cons
     const int R = B * P;
     if (!cam_loc || !ray_dirs || !state || !points || !mask || !dists || !counters || !workspace) return mv_fail(-1, "mvsdf_tracegen_finish: null argument");
     if (workspace_bytes < mvsdf_trace_workspace_bytes_n(R, tp->n_steps)) return mv_fail(-1, "mvsdf_tracegen_finish: workspace too small");
-    GenWs w = mv_gen_ws(workspace, R, tp->n_steps);
+    const MvTraceWs w = mv_trace_ws(R, tp->n_steps);
     hipStream_t s = (hipStream_t)stream;
-    int* scratch = w.sec_list;                                  // per-ray entries before the stable compaction (sec_list is filled later)
+    int* scratch = mv_ws_at<int>(workspace, w.sec_list);        // per-ray entries before the stable compaction (sec_list is filled later)
+    int* w_list_min = mv_ws_at<int>(workspace, w.w_list_min);
     hipLaunchKernelGGL(k_gen_finish, dim3((R + 255) / 256), dim3(256), 0, s, *tp, cam_loc, ray_dirs, R, P, training, (const GenRay*)state, points, mask,
-                       dists, w.w_zmin, w.w_zmax, scratch, w.w_list_min, counters);
-    hipLaunchKernelGGL(k_gen_lists, dim3(1), dim3(1024), 0, s, R, w.w_list, w.w_list_min, scratch, counters);
+                       dists, mv_ws_at<float>(workspace, w.w_zmin), mv_ws_at<float>(workspace, w.w_zmax), scratch, w_list_min, counters);
+    hipLaunchKernelGGL(k_gen_lists, dim3(1), dim3(1024), 0, s, R, mv_ws_at<int>(workspace, w.w_list), w_list_min, scratch, counters);
     return mv_check(hipGetLastError(), "mvsdf_tracegen_finish");
 }
 
@@ -1288,10 +1178,11 @@ int mvsdf_tracegen_rows(const MvsdfTraceParams* tp, int kind, const float* cam_l
     if (rc) return rc;
     if (!cam_loc || !ray_dirs || !zs || !workspace || !out_pts || n_list <= 0 || n_list > B * P || kind < 0 || kind > 1)
         return mv_fail(-1, "mvsdf_tracegen_rows: bad arguments");
-    GenWs w = mv_gen_ws(workspace, B * P, tp->n_steps);
+    const MvTraceWs w = mv_trace_ws(B * P, tp->n_steps);
     const long long total = (long long)n_list * tp->n_steps;
     hipLaunchKernelGGL(k_gen_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_list, tp->n_steps,
-                       kind == 0 ? w.w_list : w.w_list_min, cam_loc, ray_dirs, P, zs, kind == 0 ? 1 : 0, w.w_zmin, w.w_zmax, out_pts);
+                       mv_ws_at<int>(workspace, kind == 0 ? w.w_list : w.w_list_min), cam_loc, ray_dirs, P, zs, kind == 0 ? 1 : 0,
+                       mv_ws_at<float>(workspace, w.w_zmin), mv_ws_at<float>(workspace, w.w_zmax), out_pts);
     return mv_check(hipGetLastError(), "mvsdf_tracegen_rows");
 }
 
@@ -1305,20 +1196,23 @@ int mvsdf_tracegen_reduce(const MvsdfTraceParams* tp, int kind, const float* cam
     const int R = B * P;
     if (!cam_loc || !ray_dirs || !intervals || !sv || !points || !mask || !dists || !counters || !workspace || kind < 0 || kind > 1 || (kind == 0 && !marks))
         return mv_fail(-1, "mvsdf_tracegen_reduce: bad arguments");
-    GenWs w = mv_gen_ws(workspace, R, tp->n_steps);
+    const MvTraceWs w = mv_trace_ws(R, tp->n_steps);
+    int* w_list = mv_ws_at<int>(workspace, w.w_list);
+    int* w_list_min = mv_ws_at<int>(workspace, w.w_list_min);
     SampleCtx c;
-    c.cam_loc = cam_loc; c.dirs = ray_dirs; c.R = R; c.P = P; c.training = training; c.RPW = 0; c.intervals = intervals;
+    c.cam_loc = cam_loc; c.dirs = ray_dirs; c.R = R; c.P = P; c.training = training; c.intervals = intervals;
     c.steps = minsdf_steps ? minsdf_steps : intervals;
-    c.o_points = points; c.o_mask = mask; c.o_dists = dists; c.w_zmin = w.w_zmin; c.w_zmax = w.w_zmax; c.sec_state = w.sec_state;
-    c.sec_list = w.sec_list; c.sv = (float*)sv; c.counters = counters; c.list_rest = w.list_rest; c.src_rest = w.src_rest; c.n_first = tp->n_steps;
+    c.o_points = points; c.o_mask = mask; c.o_dists = dists; c.w_zmin = mv_ws_at<float>(workspace, w.w_zmin); c.w_zmax = mv_ws_at<float>(workspace, w.w_zmax);
+    c.sec_state = mv_ws_at<float>(workspace, w.sec_state); c.sec_list = mv_ws_at<int>(workspace, w.sec_list); c.sv = (float*)sv; c.counters = counters;
+    c.list_rest = mv_ws_at<int>(workspace, w.list_rest); c.src_rest = mv_ws_at<int>(workspace, w.src_rest); c.n_first = tp->n_steps;
     hipStream_t s = (hipStream_t)stream;
     if (kind == 0) {
-        hipLaunchKernelGGL(k_reduce_items, dim3((R + MV_RED_WAVES - 1) / MV_RED_WAVES), dim3(64 * MV_RED_WAVES), 0, s, *tp, c, w.w_list, (const int*)nullptr, (int)MV_CNT_N_SAMPLER, 0);
+        hipLaunchKernelGGL(k_reduce_items, dim3((R + MV_RED_WAVES - 1) / MV_RED_WAVES), dim3(64 * MV_RED_WAVES), 0, s, *tp, c, w_list, (const int*)nullptr, (int)MV_CNT_N_SAMPLER, 0);
         hipError_t e = hipMemsetAsync(marks, 0, (size_t)R, s);
         if (e != hipSuccess) return mv_check(e, "mvsdf_tracegen_reduce: memset");
-        hipLaunchKernelGGL(k_gen_sort_list, dim3(1), dim3(1024), 0, s, w.sec_list, counters, (int)MV_CNT_N_SECANT, marks, R);
+        hipLaunchKernelGGL(k_gen_sort_list, dim3(1), dim3(1024), 0, s, c.sec_list, counters, (int)MV_CNT_N_SECANT, marks, R);
     } else {
-        hipLaunchKernelGGL(k_reduce_items, dim3((R + MV_RED_WAVES - 1) / MV_RED_WAVES), dim3(64 * MV_RED_WAVES), 0, s, *tp, c, w.w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
+        hipLaunchKernelGGL(k_reduce_items, dim3((R + MV_RED_WAVES - 1) / MV_RED_WAVES), dim3(64 * MV_RED_WAVES), 0, s, *tp, c, w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
     }
     return mv_check(hipGetLastError(), "mvsdf_tracegen_reduce");
 }
@@ -1332,9 +1226,9 @@ int mvsdf_tracegen_secant(const MvsdfTraceParams* tp, int op, const float* cam_l
     if (!cam_loc || !ray_dirs || !workspace || n_sec <= 0 || n_sec > R || op < 0 || op > 2 || (op == 0 && !pts_out) || (op == 1 && !vals) ||
         (op == 2 && (!points || !dists)))
         return mv_fail(-1, "mvsdf_tracegen_secant: bad arguments");
-    GenWs w = mv_gen_ws(workspace, R, tp->n_steps);
-    hipLaunchKernelGGL(k_gen_secant, dim3((n_sec + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, n_sec, R, P, w.sec_list, w.sec_state, cam_loc,
-                       ray_dirs, vals, pts_out, points, dists);
+    const MvTraceWs w = mv_trace_ws(R, tp->n_steps);
+    hipLaunchKernelGGL(k_gen_secant, dim3((n_sec + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, n_sec, R, P, mv_ws_at<int>(workspace, w.sec_list),
+                       mv_ws_at<float>(workspace, w.sec_state), cam_loc, ray_dirs, vals, pts_out, points, dists);
     (void)counters;
     return mv_check(hipGetLastError(), "mvsdf_tracegen_secant");
 }

@@ -7,7 +7,8 @@ functions onto csrc/geom_prims.h (WsCursor, mv_align256, mv_scan_tmp_bytes), by 
     MVSDF_LIB=<that library> python tests/test_workspace_layout_host.py
 
 which prints the dict below.  Shapes per function: the smallest accepted one, sizes just below, at and above a multiple of the 2048-item scan
-chunk (1024 for the marching-cubes passes), one large shape, and the refused shapes (0) the other host tests list."""
+chunk (1024 for the marching-cubes passes), one large shape, and the refused shapes (0) the other host tests list.  mvsdf_trace_workspace_bytes_n was added
+the same way from the parent of the commit that moved the tracer's layout into csrc/trace_route.h (MvTraceWs)."""
 import pytest
 
 I31 = 2 ** 31 - 1
@@ -42,6 +43,7 @@ SHAPES = {
                                      (1, 16, 4, 2), (16, 16, 0, 2), (16, 1, 4, 2), (16, 16, 65536, 2), (16, 16, 4, -1), (65536, 32768, 1, 0),
                                      (32768, 32768, 1025, 0)],
     'mvsdf_viewsel_workspace_bytes': [(1,), (2,), (64,), (65,), (65535,), (0,), (-1,), (65536,)],
+    'mvsdf_trace_workspace_bytes_n': [(1, 2), (17, 100), (2048, 128), (8193, 1024), (0, 100), (-5, 100), (17, 0)],
 }
 SHAPES['mvsdf_stereo_volume_offset'] = SHAPES['mvsdf_stereo_workspace_bytes']
 
@@ -62,7 +64,9 @@ EXPECTED = {
     'mvsdf_stereo_volume_offset': [768, 768, 1024, 1024, 1024, 1792, 0, 0, 0, 0, 0, 0, 0],
     'mvsdf_stereo_workspace_bytes': [1280, 9984, 19456, 19456, 19968, 3317761792, 0, 0, 0, 0, 0, 0, 0],
     'mvsdf_viewsel_workspace_bytes': [264, 288, 33024, 34056, 34358690056, 0, 0, 0],
+    'mvsdf_trace_workspace_bytes_n': [316, 14604, 2187520, 67477804, 256, 256, 1004],
 }
+EMPTY = {'mvsdf_trace_workspace_bytes_n': 256}       # this query refuses nothing: no rays = its 256 bytes of slack (every other one answers 0 to a refused shape)
 
 
 def _table():
@@ -76,7 +80,7 @@ def test_workspace_bytes_are_the_recorded_ones(fn):
     from mvsdf_amd import _lib
     f = getattr(_lib.lib(), fn)
     assert len(EXPECTED[fn]) == len(SHAPES[fn]) >= 6
-    assert any(x == 0 for x in EXPECTED[fn]) and sum(1 for x in EXPECTED[fn] if x) >= 5      # refusals and accepted shapes are both pinned
+    assert any(x == EMPTY.get(fn, 0) for x in EXPECTED[fn]) and sum(1 for x in EXPECTED[fn] if x != EMPTY.get(fn, 0)) >= 5      # refusals and accepted shapes are both pinned
     for shape, want in zip(SHAPES[fn], EXPECTED[fn]):
         assert int(f(*shape)) == want, (fn, shape)
 
