@@ -173,7 +173,9 @@ int mvsdf_trace(const MvsdfNetDesc* net, const MvsdfTraceParams* tp, const float
  * followed by stage 4: secant + min-sdf (only points / dists still change, ray_tracing.py:63-96); stage 4 may be split further into
  * stage 5: min-sdf rows + their reduction alone (independent of stage 3: they only need stage 1's work list, and use their own sample-value
  * buffer, so a caller may run them on another stream concurrently with stage 3) and stage 6: secant alone.  Lets a caller bracket each
- * kernel with events, and fetch the hit count to the host while stage 4 still runs. */
+ * kernel with events, and fetch the hit count to the host while stage 4 still runs.
+ * stage 7: secant alone like stage 6, in the sphere tracer's engine form where the engine has one for these latency chains (the three-weight-term engine up to
+ * hidden width 256: sixteen waves x one column tile, k_secant_chains); the stage-6 instance everywhere else.  Same results as stage 6, bit for bit. */
 int mvsdf_trace_stage(int stage, const MvsdfNetDesc* net, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
@@ -435,8 +437,26 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
 void mvsdf_step_destroy(void* step);
 /* IDRNetwork.forward, training mode: fold (+ bf16 packs) -> camera rays -> RayTracing.forward -> ray partition (hit counts start travelling
  * to the pinned buffer) -> ONE fused value + normal evaluation over [sample points | rays, hit first] -> rendering net -> output gather.
- * d_mask / e_mask: point groups of the depth / eikonal terms (see mvsdf_step_outputs). */
-int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepInputs* in, int d_mask, int e_mask, void* fwd, void* stream);
+ * d_mask / e_mask: point groups of the depth / eikonal terms (see mvsdf_step_outputs).
+ * mode: MVSDF_STEP_UNHIT_DEFER leaves out what only the rays WITHOUT a hit need and no training step reads -- minimal_sdf_points (ray_tracing.py:280-308: the
+ *   min-sdf rows, ~44 % of the tracer's rows at the bench shape), their evaluation rows [E + N, E + R) and their sdf_output: the last tracer launch runs the secant
+ *   chains only (stage 7 of mvsdf_trace_stage), the fused evaluation and the output gather bound the rays' rows by the device-side hit count.  Until
+ *   mvsdf_step_resolve_unhit has run on the block, `points` / `dists` / `sdf_output` of those rays and counters[MVSDF_CNT_ROWS_MINSDF] are not final.
+ *   MVSDF_STEP_UNHIT_EAGER: everything in the forward (the launch sequence up to round 6).  Same values either way. */
+#define MVSDF_STEP_UNHIT_DEFER 0
+#define MVSDF_STEP_UNHIT_EAGER 1
+int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepInputs* in, int d_mask, int e_mask, int mode, void* fwd, void* stream);
+/* What a MVSDF_STEP_UNHIT_DEFER forward left out, enqueued on `stream` from the forward block ALONE (folded weights and packs, the forward's own copy of the SDF
+ * biases and of the min-sdf steps, the tracer's workspace and counters, rays, perm and counts live there: no parameter, input or staging buffer is read), so it may
+ * run after any number of later forwards and optimiser steps and still evaluates at that forward's network: (1) the min-sdf rows alone + their reduction (stage 5),
+ * (2) the evaluation rows [E + N, E + R) through the eager step's chain kernel, (3) the scatter of their sdf_output.  Same kernels, rows independent of their
+ * chunk: the eager step's bits.  Nothing to do (every launch leaves at once) when no ray is without a hit.  Call it ONCE per block (a second call would count the
+ * min-sdf rows again); a MVSDF_STEP_UNHIT_EAGER block must not be passed.
+ * mvsdf_step_can_defer_unhit: 1 when this step's SDF network runs through the fused forward chain, which both calls need (else only MVSDF_STEP_UNHIT_EAGER).
+ * mvsdf_step_last_tracer_grid: out[2] = {secant workgroups, sample-row workgroups} of the last tracer launch of the last forward (0 row workgroups: deferred). */
+int mvsdf_step_resolve_unhit(void* step, void* fwd, void* stream);
+int mvsdf_step_can_defer_unhit(void* step);
+int mvsdf_step_last_tracer_grid(void* step, int out[2]);
 /* blocks until the counts of the last mvsdf_step_forward are on the host: {N hit, N hit & true mask, depth-surface samples found per set x 2}.
  * The one host wait of a CLASSIC training step (the fused evaluation enqueued behind the count record keeps the GPU busy meanwhile); a DEFERRED
  * step (below) never calls it. */

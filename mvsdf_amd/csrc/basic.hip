@@ -544,6 +544,7 @@ struct ProloArgs {
     uint8_t* ones;                       // optional [B * P]: filled with 1 (the all-ones object mask of the output dict, idr.py:187)
     unsigned long long* counters;        // optional [16]: zeroed (the tracer's device counters: saves its memset node)
     const float* stage_src; float* stage_a; float* stage_b; int stage_na, stage_nb;   // optional: pinned host memory [na | nb] -> two device buffers
+    float* stage_a2;                     // optional: a second copy of the first buffer (the forward block's own min-sdf steps)
     int ld;                              // LDS row stride (floats) >= max K
 };
 __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
@@ -557,7 +558,7 @@ __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
             const int nthr = ((int)gridDim.x - a.blk0[nl]) * 1024, ntot = a.stage_na + a.stage_nb;
             for (int i = idx; i < ntot; i += nthr) {
                 const float x = a.stage_src[i];
-                if (i < a.stage_na) a.stage_a[i] = x; else a.stage_b[i - a.stage_na] = x;
+                if (i < a.stage_na) { a.stage_a[i] = x; if (a.stage_a2) a.stage_a2[i] = x; } else a.stage_b[i - a.stage_na] = x;
             }
         }
         if (idx >= a.B * a.P) return;
@@ -595,6 +596,9 @@ __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
         float* tr = tile + jl * ld;
         if (j >= N) { for (int k = lane; k < K; k += 64) tr[k] = 0.0f; }
         else {
+            // this forward's own copy of the bias (optional: a.f.db -> a.f.dbias, the backward's fields): the parameters move on with the optimiser, an evaluation
+            // at THIS step's network that runs later (the step's deferred rows) reads the copy
+            if (lane == 0 && a.f.dbias[l]) a.f.dbias[l][j] = a.f.db[l][j];
             const float* vr = a.f.v[l] + (size_t)j * K;
             float* wr = a.f.w[l] + (size_t)j * K;
             if (!a.f.g[l]) {                                                   // weight_norm=False: w = v
@@ -745,7 +749,7 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
                      float* const* wpT, void* const* wp16, const int* nsplit, int wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
                      const float* intrinsics, int B, int P,
                      float* ray_dirs, float* cam_loc, uint8_t* ones, unsigned long long* counters, const float* stage_src, float* stage_a, int stage_na,
-                     float* stage_b, int stage_nb, void* stream) {
+                     float* stage_b, int stage_nb, float* stage_a2, const float* const* bias, float* const* bias_copy, void* stream) {
     ProloArgs a;
     int maxN; size_t maxTot;
     int rc = fill_fold_args(a.f, n_layers, N, K, &maxN, &maxTot);
@@ -757,6 +761,7 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
         a.f.v[l] = v[l]; a.f.g[l] = g[l]; a.f.w[l] = w[l]; a.f.wp[l] = wp[l]; a.f.wpT[l] = wpT[l];
         a.wp16[l] = wp16 ? (uint16_t*)wp16[l] : nullptr; a.nsplit[l] = nsplit ? nsplit[l] : 0;
         a.wx3[l] = wx3 ? (uint16_t*)wx3[l] : nullptr; a.wx3T[l] = wx3T ? (uint16_t*)wx3T[l] : nullptr;
+        if (bias && bias_copy && bias[l] && bias_copy[l]) { a.f.db[l] = bias[l]; a.f.dbias[l] = bias_copy[l]; }
         a.blk0[l] = blk; blk += mv_kpad(N[l]) / 16;                              // row groups incl. the W^T pack's zero padding (N padded to 32)
         if (K[l] > maxK) maxK = K[l];
     }
@@ -765,6 +770,7 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
     a.uv = uv; a.pose = pose; a.Kin = intrinsics; a.B = B; a.P = P; a.dirs = ray_dirs; a.cam_loc = cam_loc;
     a.wp16_mode = wp16_mode;
     a.ones = ones; a.counters = counters;
+    a.stage_a2 = stage_src ? stage_a2 : nullptr;
     a.stage_src = stage_src; a.stage_a = stage_a; a.stage_b = stage_b; a.stage_na = stage_src ? stage_na : 0; a.stage_nb = stage_src ? stage_nb : 0;
     if (stage_src && (!stage_a || !stage_b || stage_na < 0 || stage_nb < 0)) return mv_fail(-1, "mv_step_prologue: staged inputs without targets");
     a.ld = ((maxK + 3) & ~3) + 4;

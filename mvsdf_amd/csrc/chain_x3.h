@@ -152,7 +152,8 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int ROWS = 16 * MT, NTH = 64 * NW;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
-    const int row0 = a.row_base + blockIdx.x * ROWS, S16 = a.S, TS = ROWS * S16, nl = a.net.n_layers, d0 = 3 + 6 * a.net.multires;
+    MV_FWD_ROW_BOUNDS(a, ROWS)
+    const int S16 = a.S, TS = ROWS * S16, nl = a.net.n_layers, d0 = 3 + 6 * a.net.multires;
     const unsigned skm = a.net.skip_mask;
     uint16_t* act = (uint16_t*)smem;                                // three term tiles [ROWS][S16]
     float* pe = smem + (3 * TS) / 2;                                // [ROWS][d0] natural order (fp32)
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
     for (int i = tid; i < ROWS * 3; i += NTH) {
         const int row = row0 + i / 3, c = i - 3 * (i / 3);
         float v = 0.0f;
-        if (row < a.M) {
+        if (row < M_) {
             if (!a.g.pts) v = a.x[3 * (size_t)row0 + i];
             else {
                 const int E = a.g.n_eik + 2 * a.g.n_ds;
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
     __syncthreads();
     for (int idx = tid; idx < ROWS * a.ld0; idx += NTH) {
         const int rr = idx / a.ld0, k = idx - rr * a.ld0, row = row0 + rr;
-        if (row < a.M) a.H0[(size_t)row * a.ld0 + k] = k < d0 ? pe[rr * d0 + k] : 0.0f;
+        if (row < M_) a.H0[(size_t)row * a.ld0 + k] = k < d0 ? pe[rr * d0 + k] : 0.0f;
     }
     CH_PH(0)
     const bool top_skip = mv_skip_at(skm, nl - 1);
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
         {
             const bool inner = l + 1 < nl - 1;
             const MvLayerBf& Ln = inner ? a.net.L[l + 1] : a.netT.L[nl - 2];
-            ring.gemm(L, (inner || row0 < a.Mg) ? Ln.wp : nullptr, Ln.KB, Ln.NT, act, S16, TS, ct0, ntw, acc, w, lane);
+            ring.gemm(L, (inner || row0 < Mg_) ? Ln.wp : nullptr, Ln.KB, Ln.NT, act, S16, TS, ct0, ntw, acc, w, lane);
         }
         CH_PH(2)
         mv_barrier_lds();
@@ -236,16 +237,16 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
                         sg[i] = ss;
                     }
                     mv_x3_put4(act, S16, TS, rr, col0, h, nv);
-                    if (row < a.M) {
+                    if (row < M_) {
                         mv_st4(a.Z[l] + (size_t)row * N + col0, sg, vz && nv >= 4, nv);
                         mv_st4(a.A[l + 1] + (size_t)row * Kn + col0, h, va && nv >= 4, nv);
                     }
                     if (top) {
                         f32x4 s4;
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) s4[i] = (row < a.Mg && i < nv) ? sg[i] * wl[i] : 0.0f;
+                        for (int i = 0; i < 4; ++i) s4[i] = (row < Mg_ && i < nv) ? sg[i] * wl[i] : 0.0f;
                         stop[m][t] = s4;
-                        if (row < a.Mg) mv_st4(a.Sg[l] + (size_t)row * N + col0, s4, vz && nv >= 4, nv);
+                        if (row < Mg_) mv_st4(a.Sg[l] + (size_t)row * N + col0, s4, vz && nv >= 4, nv);
                     }
                 }
             }
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
                 const int rr = idx / d0, j = idx - rr * d0, row = row0 + rr;
                 const float v = dm_div_sqrt2(pe[rr * d0 + j]);
                 mv_x3_put1(act, S16, TS, rr, N + j, v);
-                if (row < a.M) a.A[l + 1][(size_t)row * Kn + N + j] = v;
+                if (row < M_) a.A[l + 1][(size_t)row * Kn + N + j] = v;
             }
         mv_x3_zero_cols<ROWS, NTH>(act, S16, TS, Kn, Kpn, tid);
         CH_PH(4)
@@ -287,14 +288,14 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         const int row = row0 + m * 16 + r;
-                        if (row < a.M) mv_st4(a.y + (size_t)row * a.ldy + col0, acc[m][t], false, nv);
+                        if (row < M_) mv_st4(a.y + (size_t)row * a.ldy + col0, acc[m][t], false, nv);
                     }
                 }
             }
         }
     }
     CH_PH(5)
-    if (row0 >= a.Mg) return;                                       // workgroup-uniform: no normals for these rows
+    if (row0 >= Mg_) return;                                       // workgroup-uniform: no normals for these rows
     // ---- normal chain (rows >= Mg inside the tile carry zeros).  u_L = W_L[0, :]; with a skip into the last Linear its PE part starts the PE adjoint.
     __syncthreads();                                                // every wave done reading the last layer's input -- and (vmcnt(0)) every sigma_l of this tile stored: the
                                                                     // normal chain reads them back (each lane its own elements, but nothing here should rest on that)
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int row = row0 + m * 16 + r;
-                const bool ok = l > 0 && t < ntw && row < a.Mg && nv > 0;
+                const bool ok = l > 0 && t < ntw && row < Mg_ && nv > 0;
                 zz[m][t] = mv_ld4(a.Z[l > 0 ? l - 1 : 0] + (ok ? (size_t)row * Nh + col0 : 0), ok && vh && nv >= 4, ok ? nv : 0);
             }
         }
@@ -359,7 +360,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
                             if (col < N) {
                                 const float g = padj[rr * d0 + col] + v[i];
                                 padj[rr * d0 + col] = g;
-                                if (row < a.Mg) a.G0[(size_t)row * a.ld0 + col] = g;
+                                if (row < Mg_) a.G0[(size_t)row * a.ld0 + col] = g;
                             }
                         }
                     } else {
@@ -367,9 +368,9 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
                         if (nv > 0) {
                             f32x4 s4;
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) s4[i] = (row < a.Mg && i < nv) ? zz[m][t][i] * v[i] : 0.0f;
+                            for (int i = 0; i < 4; ++i) s4[i] = (row < Mg_ && i < nv) ? zz[m][t][i] * v[i] : 0.0f;
                             mv_x3_put4(act, S16, TS, rr, col0, s4, nv);
-                            if (row < a.Mg) {
+                            if (row < Mg_) {
                                 mv_st4(a.U[l] + (size_t)row * Nh + col0, v, vh && nv >= 4, nv);
                                 mv_st4(a.Sg[l - 1] + (size_t)row * Nh + col0, s4, vh && nv >= 4, nv);
                             }
@@ -391,7 +392,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd_x3(FwdArgsX3 a) {
     __syncthreads();
     for (int idx = tid; idx < ROWS * 3; idx += NTH) {               // n = J_PE^T g_0
         const int rr = idx / 3, c = idx - 3 * rr, row = row0 + rr;
-        if (row >= a.Mg) continue;
+        if (row >= Mg_) continue;
         const float* h = pe + rr * d0;
         const float* g = padj + rr * d0;
         float v = g[c];

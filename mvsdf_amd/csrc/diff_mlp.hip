@@ -400,13 +400,20 @@ static void fill_chain_args(ChainArgsT<NETX>& c, const MvNet& net, const NETX& x
  * fused chain accepts a proper sub-range (-> 1 otherwise, nothing launched). */
 int mv_sdf_forward_gather(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float* x, const void* gather, int M, int Mg, int r_begin, int r_end,
                           float* y, float* nrm, float* ctx, void* stream) {
+    return mv_sdf_forward_gather_cnt(d, dT, x, gather, M, Mg, r_begin, r_end, nullptr, 0, 0, y, nrm, ctx, stream);
+}
+/* ... with device-side counts (step_internal.h): the grid covers [r_begin, r_end), the rows are bounded on the device by n = cnt_base + cnt[0] -- cnt_mode 1:
+ * they END at n; 2: they START at n (tiles aligned there).  Fused chains only (-> 1 otherwise, nothing launched). */
+int mv_sdf_forward_gather_cnt(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float* x, const void* gather, int M, int Mg, int r_begin, int r_end,
+                              const long long* cnt, int cnt_base, int cnt_mode, float* y, float* nrm, float* ctx, void* stream) {
     const FwdGather* g = (const FwdGather*)gather;
     MvNet net, netT;
     int rc = mv_make_net(d, &net);
     if (rc) return rc;
     if ((!x && !g) || !y || !ctx || M <= 0 || Mg < 0 || Mg > M || r_begin < 0 || r_end > M || r_begin >= r_end)
         return mv_fail(-1, "mvsdf_sdf_forward: bad arguments");
-    const bool sub = r_begin > 0 || r_end < M;
+    const bool sub = r_begin > 0 || r_end < M || cnt;
+    if (cnt && cnt_mode != 1 && cnt_mode != 2) return mv_fail(-1, "mvsdf_sdf_forward: cnt_mode must be 1 or 2");
     if (Mg > 0) {
         rc = mv_make_net_mode(dT, &netT, 2);
         if (rc) return rc;
@@ -423,11 +430,13 @@ int mv_sdf_forward_gather(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const f
     if (r.family == MV_FAM_X3) {                                 // value + normal of a row tile in one launch, in the three-term bf16 arithmetic
         FwdArgsX3 f;
         fill_fwd_args(f, xn, &xnT, xn.S, net, lo, d, x, g, r_begin, r_end, Mg, y, nrm, ctx);
+        f.cnt = cnt; f.cnt_base = cnt_base; f.cnt_mode = cnt_mode;
         return mv_check(launch_chain_fwd_x3(r, mv_blocks(Mr, r.mt), mv_lds_fwd_x3(r.mt, xn.S, lo.d0), s, f), "mvsdf_sdf_forward (x3 chain)");
     }
     if (r.family == MV_FAM_F32) {                                // ... on the fp32-input MFMA
         FwdArgs f;
         fill_fwd_args(f, net, Mg > 0 ? &netT : nullptr, S, net, lo, d, x, g, r_begin, r_end, Mg, y, nrm, ctx);
+        f.cnt = cnt; f.cnt_base = cnt_base; f.cnt_mode = cnt_mode;
         return mv_check(launch_chain_fwd(r, mv_blocks(Mr, r.mt), mv_lds_fwd_f32(r.mt, S, lo.d0), s, f), "mvsdf_sdf_forward");
     }
     if (r.family == MV_FAM_REFUSE) return r.rc;                  // per-layer route: rows must be materialised by the caller, all of them at once
@@ -1043,6 +1052,12 @@ int mv_step_wgrad(const MvsdfNetDesc* sd, const MvsdfNetDesc* rd, int M, int Mg,
 // Can mvsdf_step_backward run these networks with device-side counts?  Every launch of that route must be one of the fused forms that take them: the SDF
 // chains (any arithmetic), the elementwise delta, the rendering net's fused descending chain, k_wgrad_net.  (The per-layer fall-backs size their grids from host
 // numbers: a step on such a network waits for the counts as before.)
+// 1 when the fused forward chain covers this SDF network (mv_sdf_forward_gather_cnt launches instead of answering 1)
+int mv_chain_fwd_covers(const MvsdfNetDesc* d) {
+    MvNet net;
+    if (mv_make_net(d, &net)) return 0;
+    return mv_route_sdf_forward(mv_chain_ntw(net), 1, net.L[net.n_layers - 1].NT, false, true, mv_dev_switches()).family != MV_FAM_REFUSE ? 1 : 0;
+}
 int mv_step_can_defer(const MvsdfNetDesc* sdf, const MvsdfNetDesc* sdfT, const MvsdfNetDesc* rnd, const MvsdfNetDesc* rndT) {
     MvNet net, netT, rnet, rnetT;
     if (mv_open_nets(sdf, sdfT, 0, &net, &netT) || mv_open_nets(rnd, rndT, 1, &rnet, &rnetT)) return 0;

@@ -960,15 +960,28 @@ struct FwdArgsT {
     const float* w_last_row0;                  // W_L[0, :]
     float* nrm;                                // [Mg][3]
     FwdGather g;                               // g.pts != null: x is gathered (x is ignored)
+    // device-side counts (step_internal.h): cnt != null bounds the rows by n = cnt_base + cnt[0] on the device.  cnt_mode 1: the rows END at n (M / Mg are upper
+    // bounds); 2: the rows START at n (workgroup b owns the rows n + 16 MT b ..; row_base is ignored).  Workgroups wholly beyond the rows leave at once.
+    const long long* cnt; int cnt_base, cnt_mode;
 };
 typedef FwdArgsT<MvNet> FwdArgs;
+// row0 / M_ / Mg_ of a forward chain workgroup: its first row and the ends of the rows this launch evaluates / gives normals to
+#define MV_FWD_ROW_BOUNDS(a, ROWS) \
+    int row0 = (a).row_base + blockIdx.x * (ROWS), M_ = (a).M, Mg_ = (a).Mg; \
+    if ((a).cnt) { \
+        const int n_ = (a).cnt_base + (int)(a).cnt[0]; \
+        if ((a).cnt_mode == 2) row0 = n_ + blockIdx.x * (ROWS); \
+        else { M_ = M_ < n_ ? M_ : n_; Mg_ = Mg_ < n_ ? Mg_ : n_; } \
+        if (row0 >= M_) return; \
+    }
 
 template <int MT, int NTW, int NW>
 __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int ROWS = 16 * MT, NTH = 64 * NW;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
-    const int row0 = a.row_base + blockIdx.x * ROWS, S = a.S, nl = a.net.n_layers, d0 = 3 + 6 * a.net.multires;
+    MV_FWD_ROW_BOUNDS(a, ROWS)
+    const int S = a.S, nl = a.net.n_layers, d0 = 3 + 6 * a.net.multires;
     const unsigned skm = a.net.skip_mask;
     float* act = smem;
     float* pe = act + ROWS * S;                                  // [ROWS][d0] natural order
@@ -978,7 +991,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
     for (int i = tid; i < ROWS * 3; i += NTH) {
         const int row = row0 + i / 3, c = i - 3 * (i / 3);
         float v = 0.0f;
-        if (row < a.M) {
+        if (row < M_) {
             if (!a.g.pts) v = a.x[3 * (size_t)row0 + i];
             else {
                 const int E = a.g.n_eik + 2 * a.g.n_ds;
@@ -996,7 +1009,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
     __syncthreads();
     for (int idx = tid; idx < ROWS * a.ld0; idx += NTH) {
         const int rr = idx / a.ld0, k = idx - rr * a.ld0, row = row0 + rr;
-        if (row < a.M) a.H0[(size_t)row * a.ld0 + k] = k < d0 ? pe[rr * d0 + k] : 0.0f;
+        if (row < M_) a.H0[(size_t)row * a.ld0 + k] = k < d0 ? pe[rr * d0 + k] : 0.0f;
     }
     CH_PH(0)
     // ---- value chain
@@ -1033,7 +1046,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
                             dm_softplus_sigmoid100(z, &h, &sg);
                             if (to_skip) h = dm_div_sqrt2(h);
                             act[rr * S + mv_perm(col)] = h;
-                            if (row < a.M) {
+                            if (row < M_) {
                                 a.Z[l][(size_t)row * N + col] = sg;
                                 a.A[l + 1][(size_t)row * Kn + col] = h;
                             }
@@ -1046,7 +1059,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
                 const int rr = idx / d0, j = idx - rr * d0, row = row0 + rr;
                 const float v = dm_div_sqrt2(pe[rr * d0 + j]);
                 act[rr * S + mv_perm(N + j)] = v;
-                if (row < a.M) a.A[l + 1][(size_t)row * Kn + N + j] = v;
+                if (row < M_) a.A[l + 1][(size_t)row * Kn + N + j] = v;
             }
         if (Kpn > Kn) {
             const int pad = Kpn - Kn;
@@ -1082,7 +1095,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
                                 const int row = row0 + m * 16 + 4 * q + i;
-                                if (row < a.M) a.y[(size_t)row * a.ldy + col] = acc[m][t][i] + bv;
+                                if (row < M_) a.y[(size_t)row * a.ldy + col] = acc[m][t][i] + bv;
                             }
                     }
                 }
@@ -1090,7 +1103,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
         }
     }
     CH_PH(5)
-    if (row0 >= a.Mg) return;                                    // workgroup-uniform: no normals for these rows
+    if (row0 >= Mg_) return;                                    // workgroup-uniform: no normals for these rows
     // ---- normal chain (rows >= Mg inside the tile carry zeros)
     // (a skip connection into the LAST Linear, idr.py:46-49,86: u_L = W_L[0, :] splits like any skip layer's adjoint -- its PE part starts the PE adjoint)
     const bool top_skip = mv_skip_at(skm, nl - 1);
@@ -1109,7 +1122,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
             for (int u = 0; u < 4; ++u) {
                 const int idx = it * NTH * 4 + u * NTH + tid;
                 const int rr = idx / Kpq, k = idx - rr * Kpq, row = row0 + rr;
-                const bool ok = idx < ROWS * Kpq && row < a.Mg && k < Kq;
+                const bool ok = idx < ROWS * Kpq && row < Mg_ && k < Kq;
                 zpre[it][u] = a.Z[lq][ok ? (size_t)row * Kq + k : 0];
             }
     };
@@ -1127,7 +1140,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
                 const int idx = base + u * NTH + tid;
                 const int rr = idx / Kp, k = idx - rr * Kp, row = row0 + rr;
                 v[u] = 0.0f;
-                if (idx < ROWS * Kp && row < a.Mg && k < K) {
+                if (idx < ROWS * Kp && row < Mg_ && k < K) {
                     const float uu = top ? (top_skip ? dm_div_sqrt2(a.w_last_row0[k]) : a.w_last_row0[k]) : act[rr * S + mv_perm(k)];
                     v[u] = (zp ? zp[u] : a.Z[l][(size_t)row * K + k]) * uu;
                     a.Sg[l][(size_t)row * K + k] = v[u];
@@ -1171,15 +1184,15 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
                                 v = dm_div_sqrt2(v);
                                 if (col < N - d0) {
                                     act[rr * S + mv_perm(col)] = v;
-                                    if (row < a.Mg) a.U[l][(size_t)row * (N - d0) + col] = v;
+                                    if (row < Mg_) a.U[l][(size_t)row * (N - d0) + col] = v;
                                 } else padj[rr * d0 + (col - (N - d0))] += v;
                             } else if (l == 0) {
                                 const float g = padj[rr * d0 + col] + v;
                                 padj[rr * d0 + col] = g;
-                                if (row < a.Mg) a.G0[(size_t)row * a.ld0 + col] = g;
+                                if (row < Mg_) a.G0[(size_t)row * a.ld0 + col] = g;
                             } else {
                                 act[rr * S + mv_perm(col)] = v;
-                                if (row < a.Mg) a.U[l][(size_t)row * N + col] = v;
+                                if (row < Mg_) a.U[l][(size_t)row * N + col] = v;
                             }
                         }
                 }
@@ -1190,7 +1203,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(FwdArgs a) {
     __syncthreads();
     for (int idx = tid; idx < ROWS * 3; idx += NTH) {            // n = J_PE^T g_0
         const int rr = idx / 3, c = idx - 3 * rr, row = row0 + rr;
-        if (row >= a.Mg) continue;
+        if (row >= Mg_) continue;
         const float* h = pe + rr * d0;
         const float* g = padj + rr * d0;
         float v = g[c];

@@ -23,6 +23,7 @@ struct FwdOffsets {
     int chain_x3;
     size_t trace_ws, trace_ws_bytes;
     size_t inv, true_rows, true_rank, counts, view_sorted;
+    size_t bias[MVSDF_STEP_MAX_LAYERS], steps;                     // SDF layers: this forward's copy of the biases; its min-sdf steps (what mvsdf_step_resolve_unhit reads later)
     size_t x_eval, y_eval, n_eval, sdf_ctx, rgb_sorted, render_ctx;
 };
 struct BwdOffsets {
@@ -51,6 +52,8 @@ struct Step {
     hipStream_t side;                                // the sample rows of the fused evaluation run here, beside the tracer (created on first use)
     hipEvent_t ev_fork, ev_join;
     int split_rows;                                  // -1 undecided, 0 one launch over all rows, 1 samples beside the tracer + rays after it
+    int can_lazy;                                    // the rows of the rays without a hit can be left to mvsdf_step_resolve_unhit (the fused forward chain covers the SDF network)
+    int last_grid[2];                                // {secant workgroups, sample-row workgroups} of the last forward's last tracer launch
 };
 
 // descriptors of the two networks over the packs inside a forward block
@@ -169,6 +172,8 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     }
     L.perm = take((size_t)R * 8); fo.inv = take((size_t)R * 8); fo.true_rows = take((size_t)R * 8); fo.true_rank = take((size_t)R * 4); fo.counts = take(4 * 8 + 4 * 4);   // int64 counts[4], then float term_rows[3] (mvsdf_step_counts_offset + 32)
     fo.view_sorted = take((size_t)R * 12);
+    for (int l = 0; l < d.n_sdf; ++l) fo.bias[l] = take((size_t)d.N[l] * 4);
+    fo.steps = take((size_t)(d.tp.n_steps > 0 ? d.tp.n_steps : 0) * 4);
     fo.x_eval = take((size_t)M * 12); fo.y_eval = take((size_t)M * st->Nout * 4); fo.n_eval = take((size_t)M * 12);
     // the size functions need structurally valid descriptors: point every pack at the dummy
     make_descs(*st, &fake, (const char*)nullptr, &sdf, &sdfT, &rnd, &rndT);
@@ -176,6 +181,7 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     for (int i = 0; i < d.n_render; ++i) { rnd.wp[i] = rndT.wp[i] = &dummy; }
     const size_t ctx_f = mvsdf_sdf_ctx_floats(&sdf, M, M), rctx_f = mvsdf_render_ctx_floats(&rnd, R);
     if (!ctx_f || !rctx_f) { delete st; return mv_fail(-2, "mvsdf_step_create: network descriptor rejected (layer dims / skip mask)"); }
+    st->can_lazy = mv_chain_fwd_covers(&sdf);
     st->can_defer = (d.n_ds == 0 && mv_step_can_defer(&sdf, &sdfT, &rnd, &rndT)) ? 1 : 0;   // (phase 0 checks its depth-surface sample counts on the host: idr.py:244)
     fo.sdf_ctx = take(ctx_f * 4);
     fo.rgb_sorted = take((size_t)R * 12);
@@ -259,9 +265,14 @@ int mvsdf_step_times(void* step, float ms[6]) {
     return 0;
 }
 
-int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepInputs* in, int d_mask, int e_mask, void* fwd_, void* stream) {
+int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepInputs* in, int d_mask, int e_mask, int mode, void* fwd_, void* stream) {
     Step* st = (Step*)step;
     if (!st || !prm || !in || !fwd_) return mv_fail(-1, "mvsdf_step_forward: null argument");
+    if (mode != MVSDF_STEP_UNHIT_DEFER && mode != MVSDF_STEP_UNHIT_EAGER) return mv_fail(-1, "mvsdf_step_forward: mode must be MVSDF_STEP_UNHIT_DEFER or MVSDF_STEP_UNHIT_EAGER");
+    // lazy: minimal_sdf_points of the rays without a hit (ray_tracing.py:280-308), their evaluation rows [E + N, E + R) and their sdf_output are left to
+    // mvsdf_step_resolve_unhit: nothing in a training step reads them (loss.py:176-219 takes neither `points` nor `sdf_output`; the backward covers [0, E + N))
+    const bool lazy = mode == MVSDF_STEP_UNHIT_DEFER;
+    if (lazy && !st->can_lazy) return mv_fail(-3, "mvsdf_step_forward: MVSDF_STEP_UNHIT_DEFER is not available for this step (mvsdf_step_can_defer_unhit)");
     const MvsdfStepDesc& d = st->d;
     if (!in->uv || !in->pose || !in->intrinsics || !in->object_mask || !in->object_mask_true || !in->intervals || !in->minsdf_steps ||
         (d.n_eik > 0 && !in->eik_points) || (d.n_ds > 0 && (!in->ds_on || !in->ds_jit || !in->ds_counts)))
@@ -306,9 +317,14 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
                 return mv_fail(-1, "mvsdf_step_forward: host_stage is not device-visible pinned memory");
             }
         }
+        // what a later mvsdf_step_resolve_unhit reads and the caller does not keep: the SDF net's biases (the parameters move on with the optimiser) and the min-sdf steps
+        float* bias_copy[MVSDF_STEP_MAX_LAYERS];
+        for (int l = 0; l < nl; ++l) bias_copy[l] = (lazy && l < d.n_sdf) ? (float*)(fwd + fo.bias[l]) : nullptr;
+        float* steps_copy = lazy ? (float*)(fwd + fo.steps) : nullptr;
+        if (lazy && !stage_dev) ST_HIP(hipMemcpyAsync(steps_copy, in->minsdf_steps, (size_t)d.tp.n_steps * 4, hipMemcpyDeviceToDevice, s));
         ST_TRY(mv_step_prologue(nl, prm->v, prm->g, d.N, d.K, w, wp, wpT, wp16, nsplit, d.trace_dtype == 2 ? 1 : (d.trace_dtype == 5 ? 2 : 0), wx3, wx3T, in->uv, in->pose, in->intrinsics, d.B, d.P, ray_dirs, cam_loc,
                                 (uint8_t*)(fwd + L.object_mask_out), (unsigned long long*)(fwd + L.counters), stage_dev, (float*)in->minsdf_steps, d.tp.n_steps,
-                                (float*)in->eik_points, 3 * d.n_eik, stream));
+                                (float*)in->eik_points, 3 * d.n_eik, steps_copy, prm->b, bias_copy, stream));
     }
     MvsdfNetDesc sdf, sdfT, rnd, rndT;
     make_descs(*st, prm, fwd, &sdf, &sdfT, &rnd, &rndT);
@@ -350,11 +366,15 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     float* points = (float*)(fwd + L.points); uint8_t* mask = (uint8_t*)(fwd + L.mask); float* dists = (float*)(fwd + L.dists);
     unsigned long long* counters = (unsigned long long*)(fwd + L.counters);
     auto stage = [&](int which) {
+        if (lazy && which != 3)                                     // (no tail filling: the sphere kernel still writes the min-sdf work list and ranges)
+            return mv_trace_stage_notail(which, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
+                                         counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream);
         return mvsdf_trace_stage(which, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
                                  counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream);
     };
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[0], s));
-    ST_TRY(mv_trace_stage1_prezeroed(&sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
+    if (lazy) ST_TRY(stage(1));
+    else ST_TRY(mv_trace_stage1_prezeroed(&sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
                                      counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream));   // counters zeroed by the prologue
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[1], s));
     if (split) {                                                  // enqueued AFTER the sphere tracer: its workgroups take the CUs first
@@ -381,13 +401,16 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     }
     st->counts_pending = true; st->counts_stream = s;
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[3], s));
-    ST_TRY(stage(4));                                             // secant + min-sdf rows: only points / dists still move
+    ST_TRY(stage(lazy ? 7 : 4));                                  // secant (+ min-sdf rows unless they are left to mvsdf_step_resolve_unhit): only points / dists still move
+    mv_trace_last_grid(st->last_grid);
     if (st->timing) { ST_HIP(hipEventRecord(st->ev_t[4], s)); st->timed = true; }
     // 4. ONE fused value + normal evaluation over [samples | rays, hit first], rendering net on every sorted ray, output gather
     {
         // (the rows are gathered inside the chain kernel, which also leaves them in x_eval)
         if (split) { ST_HIP(hipStreamWaitEvent(s, st->ev_join, 0)); side_guard.armed = false; }   // the main stream is ordered behind the side work from here on
-        int rcf = mv_sdf_forward_gather(&sdf, &sdfT, nullptr, &g, M, M, split ? E : 0, M, y_eval, n_eval, (float*)(fwd + fo.sdf_ctx), stream);
+        // lazy: the rays' rows end at E + N on the device (cnt_mode 1); workgroups wholly beyond leave at once
+        int rcf = mv_sdf_forward_gather_cnt(&sdf, &sdfT, nullptr, &g, M, M, split ? E : 0, M, lazy ? counts : nullptr, E, 1, y_eval, n_eval, (float*)(fwd + fo.sdf_ctx), stream);
+        if (rcf == 1 && lazy) return mv_fail(-3, "mvsdf_step_forward: the fused forward chain refused a step it was said to cover");
         if (rcf == 1) {                                           // per-layer route: materialise the rows first
             const int total = M * 3;
             hipLaunchKernelGGL(k_step_gather_x, dim3((total + 255) / 256), dim3(256), 0, s, in->eik_points, d.n_eik, in->ds_on, in->ds_jit, d.n_ds, points, perm,
@@ -400,10 +423,52 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     float* rgb_sorted = (float*)(fwd + fo.rgb_sorted);
     ST_TRY(mvsdf_render_forward(&rnd, x_eval + 3 * (size_t)E, view_sorted, n_eval + 3 * (size_t)E, y_eval + (size_t)E * st->Nout + 2, st->Nout, R,
                                 d.view_spec, rgb_sorted, (float*)(fwd + fo.render_ctx), stream));
-    ST_TRY(mvsdf_step_outputs(R, d.n_eik, d.n_ds, st->Nout, counts, x_eval, y_eval, n_eval, inv, true_rows, rgb_sorted, d_mask, e_mask,
+    ST_TRY((lazy ? mv_step_outputs_hit : mvsdf_step_outputs)(R, d.n_eik, d.n_ds, st->Nout, counts, x_eval, y_eval, n_eval, inv, true_rows, rgb_sorted, d_mask, e_mask,
                               (float*)(fwd + L.rgb_values), (float*)(fwd + L.sdf_output), (float*)(fwd + L.diff_pts), (float*)(fwd + L.eik_out),
                               (float*)(fwd + L.points_hom), (float*)(fwd + L.grad_theta), (float*)(fwd + L.surf), stream));
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[5], s));
+    return 0;
+}
+
+// What a forward in MVSDF_STEP_UNHIT_DEFER mode left out, from its forward block alone: the folded weights and packs, this forward's copy of the biases and of the
+// min-sdf steps, the tracer's workspace (min-sdf work list, ranges) and counters, rays, perm and counts all live there.  Same kernels as the eager step, rows
+// independent of their chunk / tile: the same bits, at that step's network, however many optimiser steps later.
+int mvsdf_step_resolve_unhit(void* step, void* fwd_, void* stream) {
+    Step* st = (Step*)step;
+    if (!st || !fwd_) return mv_fail(-1, "mvsdf_step_resolve_unhit: null argument");
+    if (!st->can_lazy) return mv_fail(-3, "mvsdf_step_resolve_unhit: not available for this step (mvsdf_step_can_defer_unhit)");
+    const MvsdfStepDesc& d = st->d;
+    char* fwd = (char*)fwd_;
+    const MvsdfStepLayout& L = st->lay;
+    const FwdOffsets& fo = st->fo;
+    const int R = st->R, E = st->E, M = st->M;
+    MvsdfStepParams prm;
+    memset(&prm, 0, sizeof(prm));
+    for (int l = 0; l < d.n_sdf; ++l) prm.b[l] = (const float*)(fwd + fo.bias[l]);
+    MvsdfNetDesc sdf, sdfT, rnd, rndT;
+    make_descs(*st, &prm, fwd, &sdf, &sdfT, &rnd, &rndT);            // (the rendering net's descriptors are not used)
+    float* points = (float*)(fwd + L.points); uint8_t* mask = (uint8_t*)(fwd + L.mask); float* dists = (float*)(fwd + L.dists);
+    const float* steps = (const float*)(fwd + fo.steps);
+    // 1. minimal_sdf_points: the min-sdf rows alone + their reduction (points / dists of the listed rays); the all-ones mask of the block stands in for the object
+    //    mask, which these launches do not read (the list entries carry what the sphere kernel decided from it)
+    ST_TRY(mv_trace_stage_notail(5, &sdf, &d.tp, (const float*)(fwd + L.cam_loc), (const float*)(fwd + L.ray_dirs), (const uint8_t*)(fwd + L.object_mask_out), d.B, d.P, 1,
+                                 steps, steps, points, mask, dists, (unsigned long long*)(fwd + L.counters), fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream));
+    // 2. the evaluation rows of the rays without a hit: [E + N, E + R), N on the device (cnt_mode 2), through the chain kernel of the eager step
+    FwdGather g;
+    memset(&g, 0, sizeof(g));
+    g.pts = points; g.perm = (long long*)(fwd + L.perm); g.n_eik = d.n_eik; g.n_ds = d.n_ds; g.x_out = (float*)(fwd + fo.x_eval);
+    const long long* counts = (const long long*)(fwd + fo.counts);
+    float* y_eval = (float*)(fwd + fo.y_eval);
+    const int rcf = mv_sdf_forward_gather_cnt(&sdf, &sdfT, nullptr, &g, M, M, E, M, counts, E, 2, y_eval, (float*)(fwd + fo.n_eval), (float*)(fwd + fo.sdf_ctx), stream);
+    if (rcf) return rcf == 1 ? mv_fail(-3, "mvsdf_step_resolve_unhit: the fused forward chain refused a step it was said to cover") : rcf;
+    // 3. their sdf_output
+    return mv_step_unhit_scatter(R, E, st->Nout, counts, y_eval, g.perm, (float*)(fwd + L.sdf_output), stream);
+}
+int mvsdf_step_can_defer_unhit(void* step) { Step* st = (Step*)step; return (st && st->can_lazy) ? 1 : 0; }
+int mvsdf_step_last_tracer_grid(void* step, int out[2]) {
+    Step* st = (Step*)step;
+    if (!st || !out) return mv_fail(-1, "mvsdf_step_last_tracer_grid: null argument");
+    out[0] = st->last_grid[0]; out[1] = st->last_grid[1];
     return 0;
 }
 

@@ -37,6 +37,17 @@ int mv_step_can_defer(const MvsdfNetDesc* sdf, const MvsdfNetDesc* sdfT, const M
 // [r_begin, r_end): the rows this launch evaluates (a proper sub-range only through the fused chain; -> 1 otherwise)
 int mv_sdf_forward_gather(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float* x, const void* gather, int M, int Mg, int r_begin, int r_end,
                           float* y, float* nrm, float* ctx, void* stream);
+// ... with device-side counts: n = cnt_base + cnt[0]; cnt_mode 1: the rows of [r_begin, r_end) END at n; 2: they START at n (the grid still covers r_end - r_begin
+// rows: the worst case).  Fused chains only (-> 1 otherwise).  The training step evaluates the rows of its hit rays this way and those of the others when read.
+int mv_sdf_forward_gather_cnt(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const float* x, const void* gather, int M, int Mg, int r_begin, int r_end,
+                              const long long* cnt, int cnt_base, int cnt_mode, float* y, float* nrm, float* ctx, void* stream);
+// mvsdf_step_outputs for a step that defers the rays without a hit: their sdf_output is left to mv_step_unhit_scatter (sdf_output[perm[pos]] = y of row E + pos
+// for the sorted positions pos >= N, N = counts[0] on the device)
+int mv_step_outputs_hit(int R, int n_eik, int n_ds, int Nout, const long long* counts, const float* x_eval, const float* y_eval, const float* n_eval,
+                        const long long* inv, const long long* true_rows, const float* rgb_sorted, int d_mask, int e_mask, float* rgb_values, float* sdf_output,
+                        float* diff_pts, float* eik_out, float* points_hom, float* grad_theta, float* surf, void* stream);
+int mv_step_unhit_scatter(int R, int E, int Nout, const long long* counts, const float* y_eval, const long long* perm, float* sdf_output, void* stream);
+int mv_chain_fwd_covers(const MvsdfNetDesc* d);                  // 1 when the fused forward chain covers this SDF network
 // 1 when the fused chain over the rows [E, M) alone is a shorter launch than over [0, M) (diff_mlp.hip)
 int mv_chain_split_pays(const MvsdfNetDesc* d, int E, int M);
 
@@ -59,7 +70,10 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
                      float* const* wpT, void* const* wp16, const int* nsplit, int wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
                      const float* intrinsics, int B, int P,
                      float* ray_dirs, float* cam_loc, uint8_t* ones, unsigned long long* counters, const float* stage_src, float* stage_a, int stage_na,
-                     float* stage_b, int stage_nb, void* stream);   // stage_src (optional): device-visible pinned host memory [na | nb] -> stage_a, stage_b
+                     float* stage_b, int stage_nb, float* stage_a2, const float* const* bias, float* const* bias_copy,
+                     void* stream);                                 // stage_src (optional): device-visible pinned host memory [na | nb] -> stage_a, stage_b
+                                                                    // stage_a2 (optional): receives the first staged buffer as well
+                                                                    // bias / bias_copy (optional, per layer, entries may be null): bias_copy[l] receives bias[l]
                                                                     // wx3 / wx3T (optional, per layer, entries may be null): the three-term bf16 packs of W_l / W_l^T
                                                                     // of the differentiable chains (chain_x3.h; layouts of mvsdf_pack_bf16x3_net / _bf16x3t_net)
 const MvDevSwitches& mv_dev_switches();                            // the development switches of diff_mlp.hip (diff_route.h), read once per process
@@ -67,3 +81,9 @@ const MvDevSwitches& mv_dev_switches();                            // the develo
 extern "C" int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
                               unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
+// stage 1 (counters prezeroed) / 5 / 6 / 7 of mvsdf_trace_stage without tail filling: for a forward that keeps the min-sdf rows out (they run when read, stage 5)
+extern "C" int mv_trace_stage_notail(int stage, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
+                              int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
+                              unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
+// {secant workgroups, sample-row workgroups} of the last secant / min-sdf launch this thread enqueued (trace.hip)
+void mv_trace_last_grid(int out[2]);

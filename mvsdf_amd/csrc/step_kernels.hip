@@ -109,6 +109,7 @@ struct StepOutArgs {
     float* points_hom;      // [.][4]
     float* grad_theta;      // [.][3]
     float* surf;            // first n_true + n_eik valid
+    int hit_only;           // sdf_output of the hit rays only: the rows of the others are evaluated when read (mv_step_unhit_scatter)
 };
 __global__ void k_step_outputs(StepOutArgs a) {
     const int N = (int)a.counts[0], n_true = (int)a.counts[1];
@@ -120,7 +121,7 @@ __global__ void k_step_outputs(StepOutArgs a) {
             const int pos = (int)a.inv[i];
             const bool hit = pos < N;
             for (int c = 0; c < 3; ++c) a.rgb_values[3 * (size_t)i + c] = hit ? a.rgb_sorted[3 * (size_t)pos + c] : 1.0f;
-            a.sdf_output[i] = a.y_eval[(size_t)(a.E + pos) * a.Nout];
+            if (hit || !a.hit_only) a.sdf_output[i] = a.y_eval[(size_t)(a.E + pos) * a.Nout];
         } else if (i < seg1) {
             const int k = i - seg0;
             for (int c = 0; c < 3; ++c) a.diff_pts[3 * (size_t)k + c] = a.x_eval[3 * (size_t)(a.E + k) + c];
@@ -305,6 +306,42 @@ int mv_step_backward_assemble(int n_eik, int n_ds, int N, int Nout, int n_true, 
     return mv_check(hipGetLastError(), "mv_step_backward_assemble");
 }
 
+// sdf_output of the rays WITHOUT a hit from their evaluation rows (sorted positions [N, R), N on the device): the part of k_step_outputs a step with hit_only left out
+__global__ void k_step_unhit_scatter(int R, int E, int Nout, const long long* __restrict__ counts, const float* __restrict__ y_eval, const long long* __restrict__ perm,
+                                     float* __restrict__ sdf_output) {
+    const int pos = (int)counts[0] + blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos < R) sdf_output[perm[pos]] = y_eval[(size_t)(E + pos) * Nout];
+}
+int mv_step_unhit_scatter(int R, int E, int Nout, const long long* counts, const float* y_eval, const long long* perm, float* sdf_output, void* stream) {
+    if (R <= 0 || E < 0 || Nout <= 0 || !counts || !y_eval || !perm || !sdf_output) return mv_fail(-1, "mv_step_unhit_scatter: bad arguments");
+    hipLaunchKernelGGL(k_step_unhit_scatter, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, E, Nout, counts, y_eval, perm, sdf_output);
+    return mv_check(hipGetLastError(), "mv_step_unhit_scatter");
+}
+
+static int step_outputs_impl(int hit_only, int R, int n_eik, int n_ds, int Nout, const long long* counts, const float* x_eval, const float* y_eval,
+                             const float* n_eval, const long long* inv, const long long* true_rows, const float* rgb_sorted, int d_mask,
+                             int e_mask, float* rgb_values, float* sdf_output, float* diff_pts, float* eik_out, float* points_hom, float* grad_theta,
+                             float* surf, void* stream) {
+    if (R <= 0 || n_eik < 0 || n_ds < 0 || !counts || !x_eval || !y_eval || !n_eval || !inv || !true_rows || !rgb_sorted || !rgb_values ||
+        !sdf_output || !diff_pts || !eik_out || !points_hom || !grad_theta || !surf || (d_mask & ~15) || (e_mask & ~15))
+        return mv_fail(-1, "mvsdf_step_outputs: bad arguments");
+    StepOutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = R; a.E = n_eik + 2 * n_ds; a.n_eik = n_eik; a.n_ds = n_ds; a.Nout = Nout; a.d_mask = d_mask; a.e_mask = e_mask; a.counts = counts;
+    a.x_eval = x_eval; a.y_eval = y_eval; a.n_eval = n_eval; a.inv = inv; a.true_rows = true_rows; a.rgb_sorted = rgb_sorted;
+    a.rgb_values = rgb_values; a.sdf_output = sdf_output; a.diff_pts = diff_pts; a.eik_out = eik_out; a.points_hom = points_hom;
+    a.grad_theta = grad_theta; a.surf = surf; a.hit_only = hit_only;
+    const long long worst = 5ll * R + 3ll * a.E + n_eik;                  // rays + diff_pts + two group lists + surf at N = R
+    hipLaunchKernelGGL(k_step_outputs, dim3((unsigned)((worst + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return mv_check(hipGetLastError(), "mvsdf_step_outputs");
+}
+int mv_step_outputs_hit(int R, int n_eik, int n_ds, int Nout, const long long* counts, const float* x_eval, const float* y_eval, const float* n_eval,
+                        const long long* inv, const long long* true_rows, const float* rgb_sorted, int d_mask, int e_mask, float* rgb_values, float* sdf_output,
+                        float* diff_pts, float* eik_out, float* points_hom, float* grad_theta, float* surf, void* stream) {
+    return step_outputs_impl(1, R, n_eik, n_ds, Nout, counts, x_eval, y_eval, n_eval, inv, true_rows, rgb_sorted, d_mask, e_mask, rgb_values, sdf_output, diff_pts,
+                             eik_out, points_hom, grad_theta, surf, stream);
+}
+
 extern "C" {
 
 int mvsdf_partition_rays(const uint8_t* net_mask, const uint8_t* object_mask, const uint8_t* true_mask, const float* ray_dirs, int R,
@@ -320,18 +357,8 @@ int mvsdf_step_outputs(int R, int n_eik, int n_ds, int Nout, const long long* co
                        const float* n_eval, const long long* inv, const long long* true_rows, const float* rgb_sorted, int d_mask,
                        int e_mask, float* rgb_values, float* sdf_output, float* diff_pts, float* eik_out, float* points_hom, float* grad_theta,
                        float* surf, void* stream) {
-    if (R <= 0 || n_eik < 0 || n_ds < 0 || !counts || !x_eval || !y_eval || !n_eval || !inv || !true_rows || !rgb_sorted || !rgb_values ||
-        !sdf_output || !diff_pts || !eik_out || !points_hom || !grad_theta || !surf || (d_mask & ~15) || (e_mask & ~15))
-        return mv_fail(-1, "mvsdf_step_outputs: bad arguments");
-    StepOutArgs a;
-    memset(&a, 0, sizeof(a));
-    a.R = R; a.E = n_eik + 2 * n_ds; a.n_eik = n_eik; a.n_ds = n_ds; a.Nout = Nout; a.d_mask = d_mask; a.e_mask = e_mask; a.counts = counts;
-    a.x_eval = x_eval; a.y_eval = y_eval; a.n_eval = n_eval; a.inv = inv; a.true_rows = true_rows; a.rgb_sorted = rgb_sorted;
-    a.rgb_values = rgb_values; a.sdf_output = sdf_output; a.diff_pts = diff_pts; a.eik_out = eik_out; a.points_hom = points_hom;
-    a.grad_theta = grad_theta; a.surf = surf;
-    const long long worst = 5ll * R + 3ll * a.E + n_eik;                  // rays + diff_pts + two group lists + surf at N = R
-    hipLaunchKernelGGL(k_step_outputs, dim3((unsigned)((worst + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return mv_check(hipGetLastError(), "mvsdf_step_outputs");
+    return step_outputs_impl(0, R, n_eik, n_ds, Nout, counts, x_eval, y_eval, n_eval, inv, true_rows, rgb_sorted, d_mask, e_mask, rgb_values, sdf_output, diff_pts,
+                             eik_out, points_hom, grad_theta, surf, stream);
 }
 
 int mvsdf_step_backward_inputs(int stage, int n_eik, int n_ds, int N, int Nout, int n_true, const float* din, int din_ld, int din_feat0,

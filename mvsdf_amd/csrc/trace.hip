@@ -618,14 +618,15 @@ __global__ __launch_bounds__(64 * MV_RED_WAVES) void k_reduce_items(MvTraceParam
 
 // secant (ray_tracing.py:260-278) for 16*MT listed rays per workgroup: n_secant dependent rounds, every round one evaluation of
 // all the workgroup's rays (rows are full tiles instead of one or two rows per workgroup).
-template <int MT, int NTW, int NW, class NET>
+// SPHERE: k_sphere_trace's form of the evaluation (its LDS carve and its mv_eval_dispatch branch: the next layer's weight fetch carried under this layer's work)
+template <int MT, int NTW, int NW, class NET, bool SPHERE = false>
 __device__ void mv_secant_rays(const NET& net, const MvTraceParams& tp, const SampleCtx& c, int n_list, int block, float* smem) {
     constexpr int ROWS = 16 * MT;
     const int tid = threadIdx.x;
     const int r0 = block * ROWS;
     if (r0 >= n_list) return;
     const int n = min(ROWS, n_list - r0);
-    TraceLds lds = mv_carve<NET>(smem, ROWS, net.S, 3 + 6 * net.multires, 0);
+    TraceLds lds = mv_carve<NET, (SPHERE && NTW < 4)>(smem, ROWS, net.S, 3 + 6 * net.multires, 0);
     const bool mine = tid < n;
     int gid = 0;
     float cc[3] = {0, 0, 0}, d[3] = {0, 0, 0}, z_low = 0, z_high = 0, sdf_low = 0, sdf_high = 1, z_pred = 0;
@@ -640,7 +641,7 @@ __device__ void mv_secant_rays(const NET& net, const MvTraceParams& tp, const Sa
     for (int it = 0; it < tp.n_secant; ++it) {
         if (tid < ROWS) { float* p = lds.pts + tid * 3; p[0] = cc[0] + z_pred * d[0]; p[1] = cc[1] + z_pred * d[1]; p[2] = cc[2] + z_pred * d[2]; }
         __syncthreads();
-        mv_eval_dispatch<MT, NTW, NW>(net, (n + 15) >> 4, lds.act, lds.pe, lds.pts, lds.sdfv, tid);
+        mv_eval_dispatch<MT, NTW, NW, NET, SPHERE>(net, (n + 15) >> 4, lds.act, lds.pe, lds.pts, lds.sdfv, tid);
         if (mine) {
             const float sm = lds.sdfv[tid];
             if (sm > 0.f) { z_low = z_pred; sdf_low = sm; }
@@ -699,6 +700,15 @@ __global__ __launch_bounds__(64 * NW, (mv_net_wt<NET>::v == 3 && NTW == 2 && MT 
     }
     mv_eval_rows<MT, NTW, NW, NET>(net, tp, c, sg, q0, smem, n_list);
 }
+// The secant chains ALONE in k_sphere_trace's engine form (trace_route.h::mv_route_secant): 16 listed rays per workgroup, n_secant dependent evaluations each --
+// a latency chain like the sphere tracer's rounds, so it takes that kernel's shape: one row tile, the weight fetch carried across layers and, for the
+// three-weight-term engine, sixteen waves x one column tile with the ping-pong activation tiles.  Same instruction sequence per output column as the secant
+// workgroups of k_ray_samples: same bits.  For a caller that keeps the min-sdf rows out of the launch (the training step, which defers them until read).
+template <int MT, int NTW, int NW, class NET>
+__global__ __launch_bounds__(64 * NW) void k_secant_chains(NET net, MvTraceParams tp, SampleCtx c) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    mv_secant_rays<MT, NTW, NW, NET, true>(net, tp, c, (int)c.counters[MV_CNT_N_SECANT], blockIdx.x, smem);
+}
 // ---------------------------------------------------------------------------------------------------------------
 // the tracer's switches (trace_route.h), read once per process; the development ones only by a library built with them (capi_util.h::mv_dev_env)
 const MvTraceSwitches& mv_trace_switches() {
@@ -721,7 +731,7 @@ static int mv_cu_count() {                                         // compute un
 // what every launch of one call shares (tail: trace_route.h::mv_tail_on, filled by mv_trace_launch)
 struct TraceCall {
     int engine, R, P, training;
-    bool tail;
+    bool tail, no_tail;                                            // no_tail: the caller keeps the min-sdf rows out of this forward (stage flag 0x200)
     const MvTraceParams* tp;
     const float *cam_loc, *dirs, *intervals, *steps;
     const uint8_t* om;
@@ -729,6 +739,10 @@ struct TraceCall {
     uint8_t* mask;
     void* ws; unsigned long long* counters; hipStream_t stream;
 };
+
+// {secant workgroups, sample-row workgroups} of the last launch of parts 2 / 4 / 8 / 16 enqueued by this thread (the step driver reports it: mvsdf_step_last_tracer_grid)
+static thread_local int g_last_grid[2] = {0, 0};
+void mv_trace_last_grid(int out[2]) { out[0] = g_last_grid[0]; out[1] = g_last_grid[1]; }
 
 template <int MT, int NTW, int NW, class NET>
 static hipError_t launch_stage1(const NET& net, const TraceCall& t) {
@@ -783,6 +797,7 @@ static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
         }
     } else if (part == 8) {
         hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.sec), wg, lds2, t.stream, net, tp, c, none, none, g.sec);
+        g_last_grid[0] = g.sec; g_last_grid[1] = 0;
     } else if (part == 2 || t.training) {
         // min-sdf rows, behind the secant chains of the same launch (2) or alone (4).  With tail filling they are a queue that k_sphere_trace's finished workgroups
         // have already served: units claimed dynamically (the grid stays worst-case: workgroups without a unit exit at once).  Their values go to the second
@@ -791,8 +806,32 @@ static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
         const int sec = part == 2 ? g.sec : 0;
         const RowSeg minsdf = {w_list_min, nullptr, (int)MV_CNT_N_MINSDF, 0, n, g.minsdf, t.tail ? 1 : 0};
         hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(sec + g.minsdf), wg, lds2, t.stream, net, tp, c, minsdf, none, sec);
+        g_last_grid[0] = sec; g_last_grid[1] = g.minsdf;
         if (t.training) hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, w_list_min, (const int*)nullptr, (int)MV_CNT_N_MINSDF, 2);
     }
+    return hipGetLastError();
+}
+
+// part 16: the secant chains alone as k_secant_chains (LDS bytes: the sphere kernel's formula)
+template <int MT, int NTW, int NW, class NET>
+static hipError_t launch_secant(const NET& net, const TraceCall& t) {
+    const MvTraceParams& tp = *t.tp;
+    const MvTraceWs w = mv_trace_ws(t.R, tp.n_steps);
+    const size_t lds = mv_trace_lds_bytes(net.S, net.multires, MT, mv_act_rows<NET>(16 * MT, NTW < 4));
+    static size_t set = 0;
+    if (lds > set) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_secant_chains<MT, NTW, NW, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        set = lds;
+    }
+    SampleCtx c = {};
+    c.cam_loc = t.cam_loc; c.dirs = t.dirs; c.R = t.R; c.P = t.P; c.training = t.training; c.intervals = t.intervals; c.steps = t.steps;
+    c.o_points = t.points; c.o_mask = t.mask; c.o_dists = t.dists; c.w_zmin = mv_ws_at<float>(t.ws, w.w_zmin); c.w_zmax = mv_ws_at<float>(t.ws, w.w_zmax);
+    c.sec_state = mv_ws_at<float>(t.ws, w.sec_state); c.sec_list = mv_ws_at<int>(t.ws, w.sec_list); c.sv = mv_ws_at<float>(t.ws, w.sv); c.counters = t.counters;
+    c.list_rest = mv_ws_at<int>(t.ws, w.list_rest); c.src_rest = mv_ws_at<int>(t.ws, w.src_rest); c.n_first = tp.n_steps;
+    const int sec = (t.R + 16 * MT - 1) / (16 * MT);
+    hipLaunchKernelGGL((k_secant_chains<MT, NTW, NW, NET>), dim3(sec), dim3(64 * NW), lds, t.stream, net, tp, c);
+    g_last_grid[0] = sec; g_last_grid[1] = 0;
     return hipGetLastError();
 }
 
@@ -804,6 +843,10 @@ template <class NET>
 static hipError_t mv_launch_inst(const MvInst& r, const NET& net, const TraceCall& t, int part) {
     constexpr bool f32 = std::is_same<NET, MvNet>::value, nw16 = MV_SPHERE_NW16 != 0 && mv_net_wt<NET>::v == 3;
     if (r.rc) return hipErrorInvalidValue;
+    if (part == 16) {                                              // mv_route_secant: the sixteen-wave engine form, or the part-8 instance of k_ray_samples
+        if (r.nw == 16) { if constexpr (nw16) { if (r.mt == 1 && r.ntw == 1) return launch_secant<1, 1, 16>(net, t); } return hipErrorInvalidValue; }
+        part = 8;
+    }
     if (part == 0) switch (mv_inst_key(r.mt, r.ntw, r.nw)) {
         MV_S1(nw16, 1, 1, 16); MV_S1(!nw16, 1, 2, 8); MV_S1(true, 2, 2, 8); MV_S1(true, 4, 2, 8); MV_S1(true, 1, 4, 8); MV_S1(true, 2, 4, 8);
         MV_S1(f32, 1, 4, 4); MV_S1(f32, 2, 4, 4); MV_S1(f32, 4, 4, 4);
@@ -816,17 +859,18 @@ static hipError_t mv_launch_inst(const MvInst& r, const NET& net, const TraceCal
 #undef MV_S1
 #undef MV_S2
 
-// stages bit 0: the sphere-tracing launch; bits 1..4: the parts 1, 2, 4, 8 of launch_stage2
+// stages bit 0: the sphere-tracing launch; bits 1..4: the parts 1, 2, 4, 8 of launch_stage2; bit 5: part 16, the secant chains alone in the sphere tracer's engine form
 template <class NET>
 static hipError_t mv_trace_launch(int stages, const NET& net, TraceCall t, int mt, int mt_samples) {
     const MvTraceSwitches& sw = mv_trace_switches();
     const int maxnt = mv_hidden_nt(net);
     const MvInst s1 = mv_route_sphere(t.engine, maxnt, mt);
     if (s1.rc) return hipErrorInvalidValue;
-    t.tail = mv_tail_on(t.engine, t.training, t.steps != nullptr, t.R, s1.mt, mv_cu_count(), sw);
+    t.tail = !t.no_tail && mv_tail_on(t.engine, t.training, t.steps != nullptr, t.R, s1.mt, mv_cu_count(), sw);
     hipError_t e = (stages & 1) ? mv_launch_inst(s1, net, t, 0) : hipSuccess;
-    for (int part = 1; part <= 8 && e == hipSuccess; part <<= 1)
-        if ((stages >> 1) & part) e = mv_launch_inst(mv_route_samples(t.engine, maxnt, mt_samples, t.R, part, sw), net, t, part);
+    for (int part = 1; part <= 16 && e == hipSuccess; part <<= 1)
+        if ((stages >> 1) & part)
+            e = mv_launch_inst(part == 16 ? mv_route_secant(t.engine, maxnt, mt_samples, t.R, sw) : mv_route_samples(t.engine, maxnt, mt_samples, t.R, part, sw), net, t, part);
     return e;
 }
 
@@ -1085,7 +1129,8 @@ static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTracePara
         hipError_t e = hipSuccess;
         if ((stages & 1) && !(stages & 0x100)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them
         if (e != hipSuccess) return mv_check(e, "mvsdf_trace: memset");
-        const TraceCall t = {ec.engine, R, P, training, false, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
+        // 0x200: no tail filling in this call -- the caller keeps the min-sdf rows out of its forward (k_sphere_trace still writes their work list and ranges)
+        const TraceCall t = {ec.engine, R, P, training, false, (stages & 0x200) != 0, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
                              points, dists, mask, workspace, counters, s};
         return mv_check(mv_trace_launch(stages, net, t, mt, mt_samples), "mvsdf_trace");
     });
@@ -1102,13 +1147,14 @@ int mvsdf_trace(const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const floa
 /* The launches of mvsdf_trace separately (same arguments, same workspace): stage 1 = sphere tracing (zeroes the counters),
  * stage 2 = ray sampler + secant + min-sdf; or stage 3 = ray sampler rows only (`mask` is final after it) followed by
  * stage 4 = secant + min-sdf (only points / dists still change).  Lets a caller bracket each kernel with events and read the
- * hit count while the last stage still runs. */
+ * hit count while the last stage still runs.  Stage 5 = the min-sdf rows alone (own sample-value buffer), 6 = the secant chains alone as workgroups of
+ * k_ray_samples, 7 = the secant chains alone in the sphere tracer's engine form (k_secant_chains; same results as 6). */
 int mvsdf_trace_stage(int stage, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
                       size_t workspace_bytes, int mt, int mt_samples, void* stream) {
-    if (stage < 1 || stage > 6) return mv_fail(-1, "mvsdf_trace_stage: stage must be 1..6");
-    static const int bits[7] = {0, 1, 6, 2, 4, 8, 16};
+    if (stage < 1 || stage > 7) return mv_fail(-1, "mvsdf_trace_stage: stage must be 1..7");
+    static const int bits[8] = {0, 1, 6, 2, 4, 8, 16, 32};
     return trace_impl(bits[stage], desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
                       workspace, workspace_bytes, mt, mt_samples, stream);
 }
@@ -1118,6 +1164,15 @@ int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTraceParams* 
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
                               unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
     return trace_impl(1 | 0x100, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
+                      workspace, workspace_bytes, mt, mt_samples, stream);
+}
+// the step driver's stages with the min-sdf rows kept out of the forward: stage 1 (prezeroed) / 5 / 6 / 7 of mvsdf_trace_stage without tail filling
+int mv_trace_stage_notail(int stage, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
+                          int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
+                          unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+    static const int bits[8] = {0, 1 | 0x100, 0, 0, 0, 8, 16, 32};
+    if (stage < 1 || stage > 7 || !bits[stage]) return mv_fail(-1, "mv_trace_stage_notail: stage must be 1, 5, 6 or 7");
+    return trace_impl(bits[stage] | 0x200, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
                       workspace, workspace_bytes, mt, mt_samples, stream);
 }
 

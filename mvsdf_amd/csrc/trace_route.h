@@ -84,6 +84,17 @@ inline MvInst mv_route_samples(int engine, int maxnt, int mt_samples, int R, int
     if (part == 1) mt = sw.mt_first > 0 ? sw.mt_first : (engine == MV_ENG_X3 ? (mt_samples > 2 ? 2 : mt_samples) : (R <= 4096 ? 1 : mt_samples));
     return mv_inst_ladder(engine, maxnt, mt);
 }
+// The secant chains alone (stage 7 of mvsdf_trace_stage): n_secant dependent evaluations of 16 listed rays per workgroup -- the sphere tracer's shape of work, so
+// where mv_route_sphere has the sixteen-wave form for one row tile (three weight terms) the chains take it as k_secant_chains<1, 1, 16>; every other engine and
+// width keeps the part-8 instance of k_ray_samples.  (nw == 16 in the answer names the k_secant_chains instance; anything else is launch_stage2's part 8.)
+#ifndef MV_SECANT_NW16
+#define MV_SECANT_NW16 1                                            // (-DMV_SECANT_NW16=0: the part-8 instance everywhere, for A/B builds)
+#endif
+inline MvInst mv_route_secant(int engine, int maxnt, int mt_samples, int R, const MvTraceSwitches& sw) {
+    const MvInst s = mv_route_sphere(engine, maxnt, 1);
+    if (MV_SECANT_NW16 != 0 && s.rc == 0 && s.mt == 1 && s.ntw == 1 && s.nw == 16) return s;
+    return mv_route_samples(engine, maxnt, mt_samples, R, 8, sw);
+}
 // mvsdf_sdf_col0; mt = 49: the sphere tracer's engine, the weight ring carried across layers (two column tiles per wave: width <= 256).
 // Historical, kept: only the fp32 engine checks mt (the bf16-term engines take any mt down the ladder), only the bf16-term engines refuse maxnt > 32.
 inline MvInst mv_route_col0(int engine, int maxnt, int mt, const MvTraceSwitches& sw) {

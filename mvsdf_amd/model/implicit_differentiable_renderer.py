@@ -175,15 +175,27 @@ class LazyOutputs(dict):
     computed the first time one of the two keys is read, by the same kernels on the same inputs: every value a caller can observe equals the
     eager one.  Any access path (`[]`, get, items, values, iteration, dict(...), copy) goes through `_materialize` first when it may touch them."""
     _LAZY = ('points', 'sdf_output')
+    # A second group with its own resolver, for the native step (`late`: mvsdf_step_resolve_unhit through StepRecord.resolve_unhit -- the same deferral without the
+    # Python-orchestrated route and without an expiry: the forward block holds everything the late evaluation reads).  Every access path below serves both groups.
+    _LATE = ('points', 'sdf_output')
 
-    def __init__(self, data, materialize):
+    def __init__(self, data, materialize, late=None):
         super().__init__(data)
         self._pending = materialize
+        self._late = late
 
     def _materialize(self):
         if self._pending is not None:
             self._pending()                  # (an expired one raises and stays in place)
             self._pending = None
+
+    def _need(self, k=None):
+        """Before key k (None: any key) is observed or moved."""
+        if self._late is not None and (k is None or k in self._LATE):
+            late, self._late = self._late, None
+            late()
+        if k is None or k in self._LAZY:
+            self._materialize()
 
     def _expire(self):
         """The next forward re-folds the weights into the same packed buffers: the deferred rows can no longer be evaluated at this step's
@@ -195,51 +207,47 @@ class LazyOutputs(dict):
             self._pending = stale
 
     def __getitem__(self, k):
-        if k in self._LAZY:
-            self._materialize()
+        self._need(k)
         return super().__getitem__(k)
 
     def get(self, k, default=None):
-        if k in self._LAZY:
-            self._materialize()
+        self._need(k)
         return super().get(k, default)
 
     def __iter__(self):                      # also makes dict(self) / {**self} take the generic (keys + __getitem__) route
         return super().__iter__()
 
     def items(self):
-        self._materialize()
+        self._need()
         return super().items()
 
     def values(self):
-        self._materialize()
+        self._need()
         return super().values()
 
     def copy(self):
-        self._materialize()
+        self._need()
         return dict(super().items())
 
     def pop(self, k, *a):
-        if k in self._LAZY:
-            self._materialize()
+        self._need(k)
         return super().pop(k, *a)
 
     # every remaining way to observe or move the values goes through the eager ones
     def setdefault(self, k, default=None):
-        if k in self._LAZY:
-            self._materialize()
+        self._need(k)
         return super().setdefault(k, default)
 
     def popitem(self):
-        self._materialize()
+        self._need()
         return super().popitem()
 
     def update(self, *a, **k):
-        self._materialize()                  # an update may replace a lazy key: the pending evaluation must not overwrite it afterwards
+        self._need()                         # an update may replace a lazy key: the pending evaluation must not overwrite it afterwards
         return super().update(*a, **k)
 
     def __eq__(self, other):
-        self._materialize()
+        self._need()
         return super().__eq__(other)
 
     __hash__ = None
@@ -248,15 +256,15 @@ class LazyOutputs(dict):
         return not self.__eq__(other)
 
     def __or__(self, other):
-        self._materialize()
+        self._need()
         return dict(super().items()) | other
 
     def __ror__(self, other):
-        self._materialize()
+        self._need()
         return other | dict(super().items())
 
     def __ior__(self, other):
-        self._materialize()
+        self._need()
         return super().__ior__(other)
 
     def __copy__(self):
@@ -277,8 +285,8 @@ class PendingOutputs(LazyOutputs):
     and runs loss and backward with the counts taken on the device (native_step._DeferredStepLossFn).  Same values either way."""
     _LAZY = ('diff_surf_pts', 'rgb_values', 'grad_theta', 'eikonal_points_hom', 'eikonal_output', 'surf_indicator_output')
 
-    def __init__(self, data, fill, rec):
-        super().__init__(data, fill)                             # fill(target): NO reference back to this object inside it -- a closure over the dict it fills
+    def __init__(self, data, fill, rec, late=None):
+        super().__init__(data, fill, late)                       # fill(target): NO reference back to this object inside it -- a closure over the dict it fills
         self._mv_rec = rec                                       # would make dict, record and forward block (3.6 GB in the shipped workload) wait for the cyclic collector
 
     def _materialize(self):
@@ -291,7 +299,18 @@ class PendingOutputs(LazyOutputs):
         return self._mv_rec if self._pending is not None else None
 
     def raw(self, k):
+        """The entry as it stands, without resolving the N-shaped keys (`points` / `sdf_output` are still made final first)."""
+        if self._late is not None and k in self._LATE:
+            self._need(k)
         return dict.__getitem__(self, k)
+
+
+class StepOutputs(LazyOutputs):
+    """The output dict of a CLASSIC native training forward whose rays without a hit wait for their first reader (`late`); every other key is final."""
+    _LAZY = ()
+
+    def __init__(self, data, late):
+        super().__init__(data, None, late)
 
 
 class _StepStats(dict):
@@ -337,6 +356,10 @@ class IDRNetwork(nn.Module):
         # training forward without the host wait for the hit counts (PendingOutputs; IDRLoss + backward then read them on the device): the step's rate no longer
         # depends on host latency.  False: the classic step (one wait per forward).  Phase 0 (depth-surface samples, idr.py:226-247) always waits.
         self.deferred_step = type(self).DEFERRED_STEP
+        # The native step leaves minimal_sdf_points (~44 % of the tracer's rows at the bench shape), the evaluation rows and sdf_output of the rays WITHOUT a hit to the
+        # first reader of `points` / `sdf_output` (mvsdf_step_resolve_unhit: nothing in a training step reads them; no expiry, same values).  True, or MVSDF_EAGER_UNHIT=1:
+        # everything inside the forward, the launch sequence up to round 6.
+        self.eager_unhit_rows = os.environ.get('MVSDF_EAGER_UNHIT', '0') not in ('', '0')
         self._steps = {}                                         # NativeStep per batch shape / phase configuration
         self._ones = None                                        # all-ones object mask handed to the tracer when conf.use_mask is off
 
@@ -632,6 +655,7 @@ class IDRNetwork(nn.Module):
         rec.d_mask, rec.e_mask = self._group_masks(train_progress, n_eik, n_ds)
         rec.use_geo = not bool(train_progress < conf.phase[0] or conf.disable_rgb_grad)                       # idr.py:331-334
         rec.inputs_keep = keep                                   # the inputs stay alive as long as the step's record does
+        rec.eager_unhit = bool(self.eager_unhit_rows) or not st.can_defer_unhit
         NS.enqueue_forward(rec)                                  # everything of this forward is on the stream now; nothing waited for
         if stage_slot is not None:                               # the pinned draws may be rewritten once this forward's first kernel has read them
             stage_slot[2] = (st, rec.seq)
@@ -663,13 +687,14 @@ class IDRNetwork(nn.Module):
             dict.update(target, {'diff_surf_pts': diff_pts, 'rgb_values': rgb_values, 'grad_theta': grad_theta,
                                  'eikonal_points_hom': f.f(L.points_hom, (1, nd, 4, 1)), 'eikonal_output': eik_out, 'surf_indicator_output': surf})
 
+        late = rec.resolve_unhit if rec.unhit_pending else None   # (a bound method of the record: no reference back to the dict)
         if self.deferred_step and st.can_defer and dsurf is None and torch.is_grad_enabled():
-            out = PendingOutputs(eager, materialize, rec)
+            out = PendingOutputs(eager, materialize, rec, late)
             d_['last_stats'] = _StepStats(rec, R=R, E=st.E, counters=counters)
             return out
         materialize(eager)                                       # the classic step: its one host wait
         d_['last_stats'] = {'R': R, 'N': rec.N, 'E': st.E, 'counters': counters}
-        return eager
+        return StepOutputs(eager, late) if late is not None else eager
 
     def _step_params(self):
         """(weight_v list, weight_g list, bias list, all of them as one tuple) of both networks, SDF layers first.  The Parameter OBJECTS of a

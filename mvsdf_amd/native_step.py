@@ -71,7 +71,10 @@ def _bind():
         L.mvsdf_step_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.mvsdf_step_destroy.argtypes = [C.c_void_p]
         L.mvsdf_step_destroy.restype = None
-        L.mvsdf_step_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mvsdf_step_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.mvsdf_step_resolve_unhit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mvsdf_step_can_defer_unhit.argtypes = [C.c_void_p]
+        L.mvsdf_step_last_tracer_grid.argtypes = [C.c_void_p, C.c_void_p]
         L.mvsdf_step_wait_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.mvsdf_step_seq.argtypes = [C.c_void_p]
         L.mvsdf_step_seq.restype = C.c_longlong
@@ -167,6 +170,7 @@ class NativeStep:
         self.timing = False
         self.can_defer = bool(L.mvsdf_step_can_defer(h))          # every launch of the backward has a device-count form (the deferred step)
         self.counts_off = int(L.mvsdf_step_counts_offset(h))      # int64 counts[4] inside a forward block
+        self.can_defer_unhit = bool(L.mvsdf_step_can_defer_unhit(h))   # the rows of the rays without a hit can wait until `points` / `sdf_output` are read
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -219,12 +223,23 @@ class NativeStep:
         return self._grad_arrays
 
     # ---- calls
-    def forward(self, prm, d_mask, e_mask):
-        """-> the forward block (enqueued, nothing waited for); self.seq() names this forward."""
+    def forward(self, prm, d_mask, e_mask, eager_unhit=True):
+        """-> the forward block (enqueued, nothing waited for); self.seq() names this forward.  eager_unhit=False (MVSDF_STEP_UNHIT_DEFER): what only the
+        rays without a hit need is left to resolve_unhit(block)."""
         fwd = Block(self.layout.fwd_bytes, self.device)
-        check(lib().mvsdf_step_forward(self._h, C.byref(prm), C.byref(self.inputs), d_mask, e_mask, fwd.data_ptr(), _stream(self.device)),
-              'mvsdf_step_forward')
+        check(lib().mvsdf_step_forward(self._h, C.byref(prm), C.byref(self.inputs), d_mask, e_mask, 1 if eager_unhit else 0, fwd.data_ptr(),
+                                       _stream(self.device)), 'mvsdf_step_forward')
         return fwd
+
+    def resolve_unhit(self, fwd):
+        """mvsdf_step_resolve_unhit: min-sdf rows, evaluation rows and sdf_output of the rays without a hit, from the forward block alone (once per block)."""
+        check(lib().mvsdf_step_resolve_unhit(self._h, fwd.data_ptr(), _stream(self.device)), 'mvsdf_step_resolve_unhit')
+
+    def last_tracer_grid(self):
+        """(secant workgroups, sample-row workgroups) of the last tracer launch of the last forward; no row workgroups: the min-sdf rows were deferred."""
+        out = (C.c_int * 2)()
+        check(lib().mvsdf_step_last_tracer_grid(self._h, out), 'mvsdf_step_last_tracer_grid')
+        return int(out[0]), int(out[1])
 
     def wait_counts(self):
         check(lib().mvsdf_step_wait_counts(self._h, self._counts), 'mvsdf_step_wait_counts')
@@ -295,11 +310,20 @@ class NativeStep:
 class StepRecord:
     """What one forward leaves behind for its backward and for the output dict."""
     __slots__ = ('step', 'fwd', 'prm', 'params', 'N', 'n_true', 'counts', 'd_mask', 'e_mask', 'use_geo', 'n_layers', 'vs', 'gs', 'bs', 'keep', 'done', 'versions',
-                 'seq', 'inputs_keep', 'live', '__weakref__')
+                 'seq', 'inputs_keep', 'live', 'eager_unhit', 'unhit_pending', '__weakref__')
 
     def __init__(self):
         self.fwd = self.N = self.n_true = self.counts = self.seq = None
         self.done = False
+        self.eager_unhit = True                                   # False: the forward leaves the rays without a hit to resolve_unhit()
+        self.unhit_pending = False
+
+    def resolve_unhit(self):
+        """`points` / `sdf_output` of the rays without a hit, evaluated now from the forward block (mvsdf_step_resolve_unhit) if this forward left them out and
+        nobody asked before: at this step's weights, whatever happened to the parameters since.  No host wait."""
+        if self.unhit_pending:
+            self.unhit_pending = False
+            self.step.resolve_unhit(self.fwd)
 
     def resolve(self):
         """(N, n_true): host-side counts of this forward -- the classic step asks right after its forward, a deferred step only when somebody reads an
@@ -373,7 +397,8 @@ class _NativeStepFn(torch.autograd.Function):
 def enqueue_forward(rec):
     """mvsdf_step_forward for this record: everything of IDRNetwork.forward is on the stream when this returns; nothing is waited for."""
     st = rec.step
-    rec.fwd = st.forward(rec.prm, rec.d_mask, rec.e_mask)
+    rec.fwd = st.forward(rec.prm, rec.d_mask, rec.e_mask, rec.eager_unhit)
+    rec.unhit_pending = not rec.eager_unhit
     rec.seq = st.seq()
     # the backward reads the parameters again (weight-norm fold backward over prm->v / g): an in-place update between this forward and its backward
     # (forward A, forward B, backward B, opt.step(), backward A) must raise like autograd's saved-tensor check does, not mix old activations with new weights
