@@ -1,9 +1,11 @@
 """Stage 7 of mvsdf_trace_stage: the secant chains alone in the sphere tracer's engine form (k_secant_chains<1, 1, 16> for the three-weight-term engine up to
-hidden width 256, csrc/trace_route.h::mv_route_secant; the stage-6 instance for every other engine).
+hidden width 256, csrc/trace_route.h::mv_route_secant; the stage-6 instance for every other engine and, at width 512, for that engine too: the part-8 launch of
+k_ray_samples<., 4, 8>, one 16-ray workgroup per 16 rays of the batch, bounded by the device-side secant count).
 
 * 'f32x3': stages 1, 3, 7 against oracle.trace (the CPU model of that arithmetic) BIT FOR BIT on points / dists / mask of the secant rays and on the secant row
   counter -- the reference is the oracle, not another stage of the library under test.  Shapes: 4 secant rays (under one tile), 13, 17 (one ray into the second
-  workgroup), 60 (four workgroups, the last one partial) at width 64; 5 and 17 at width 256.  The counts are asserted from the device counters first: an input
+  workgroup), 60 (four workgroups, the last one partial) at width 64; 5 and 17 at width 256; 12 (under one 16-ray workgroup) and 21 (one workgroup and five
+  rays) at width 512.  The counts are asserted from the device counters first: an input
   that stopped exercising an edge fails instead of passing empty.
 * every other tracing arithmetic: stage 7 == stage 6 bit for bit (it runs the same instance)."""
 import ctypes as C
@@ -20,7 +22,8 @@ from mvsdf_amd.utils import synth
 pytestmark = pytest.mark.gpu
 N_STEPS = 100
 # (W, B, P, seed) -> (secant rays, rays on the min-sdf list), from the CPU oracle on the 'f32x3' arithmetic
-CASES = {(64, 1, 24, 1): (4, 0), (64, 2, 40, 5): (13, 6), (64, 1, 64, 3): (17, 11), (64, 1, 200, 3): (60, 27), (256, 1, 64, 3): (5, 42), (256, 2, 40, 5): (17, 44)}
+CASES = {(64, 1, 24, 1): (4, 0), (64, 2, 40, 5): (13, 6), (64, 1, 64, 3): (17, 11), (64, 1, 200, 3): (60, 27), (256, 1, 64, 3): (5, 42), (256, 2, 40, 5): (17, 44),
+         (512, 1, 24, 1): (12, 6), (512, 1, 64, 3): (21, 33)}
 
 
 def _rays(B, P, seed):
@@ -73,7 +76,7 @@ def test_stage7_secant_rays_equal_the_oracle(oracle, W, B, P, seed):
 @pytest.mark.parametrize('dtype', ['f32', 'bf16w', 'bf16x2', 'bf16x3'])
 def test_stage7_equals_stage6_on_the_other_engines(dtype):
     W, B, P, seed = 64, 1, 200, 3
-    for Wn in (W, 256):
+    for Wn in (W, 256, 512):
         net = ops.pack_trace_net(sdf_packed_net(synth.make_state_dict(Wn, 0)), dtype)
         dirs, cam = _rays(B, P, seed)
         steps = t(np.random.RandomState(0).uniform(size=N_STEPS).astype(np.float32))

@@ -2,15 +2,31 @@
 
   * the GENERIC route (ops.trace_generic: k_gen_init / k_gen_step / k_gen_finish / k_gen_lists / k_gen_rows / k_gen_secant / k_gen_sort_list around an opaque
     `sdf` callable) with the analytic SDF, every row of the table, training and eval;
-  * the FUSED route (ops.trace) with the W = 64 network on the fmaf-chain engine ('f32'), the three-term engine ('f32x3') and bf16-rounded weights ('bf16w'),
-    at (mt, mt_samples) in {(1, 1), (2, 3), (4, 4)};
+  * the FUSED route (ops.trace) with the W = 64, 256 and 512 networks on the fmaf-chain engine ('f32'), the three-term engine ('f32x3') and bf16-rounded
+    weights ('bf16w'), at (mt, mt_samples) in {(1, 1), (2, 3), (4, 4)} -- at W = 512 a request of 4 row tiles is clamped to 2 -- both as the one call and as its
+    launches one by one with the secant chains alone (mvsdf_trace_stage 1, 3, 7, 5: what the native step launches);
   * the two routes against each other with `sdf = ops.sdf_col0(net, .)`;
+  * the split engines ('bf16x2', 'bf16x3'), which have no bit-level CPU model (their softplus uses the hardware exp / log): the exact identities that remain --
+    every tiling and the staged form give the same bits, the generic route around ops.sdf_col0 equals the fused route -- with the lists the table declares
+    filled asserted non-empty from the device counters, so that no identity passes empty.  (Their arithmetic is held to the oracle by
+    tests/test_gpu_bf16s.py; its tracer comparison exempts every ray within 1e-6 of a decision, which is every secant ray: DESIGN.md.)
   * the host-side refusals of the C ABI.
+
+Where each instance csrc/trace_route.h can return runs (<row tiles, column tiles per wave, waves>; every id below covers r7 ... r33, n13, n129 and wrap):
+    k_sphere_trace (mv_route_sphere)          F32 W < 256   <1|2|4, 4, 4>   test_fused_route_bit_exact_vs_oracle[*-f32], [*-bf16w]
+                                              F32 W = 256   <1|2|4, 2, 8>   test_fused_route_wide_bit_exact_vs_oracle[*-f32-256], [*-bf16w-256]
+                                              X3  W <= 256  <1, 1, 16>, <2|4, 2, 8>   test_fused_route_bit_exact_vs_oracle[*-f32x3], ..._wide_...[*-f32x3-256]
+                                              BS2 / BS3 W <= 256   <1|2|4, 2, 8>   test_split_engines_tilings_give_the_same_bits[64-*-bf16x2], [256-*-bf16x3], ...
+                                              any W = 512   <1|2, 4, 8>   ..._wide_...[*-f32-512], [*-bf16w-512], [*-f32x3-512], test_split_engines_...[512-*-bf16x2], ...
+    k_ray_samples (mv_route_samples)          the same ladder over mt_samples = 1, 3 (-> 2), 4, in the same tests (part 1: one row tile up to 4096 rays, X3 at most two)
+    the secant chains alone (mv_route_secant) X3 W <= 256   k_secant_chains<1, 1, 16>; every other engine and width: the k_ray_samples instance of mt_samples --
+                                              the staged run (stage 7) of the same tests
 
 Every comparison is np.array_equal on points, mask, dists and the row counters over ALL rays (the oracle's sphere intersection is the kernel's): the project's
 rule for the bit-exact arithmetics, no tolerance.  tests/test_trace_cases_host.py holds the table to the branches these tests rely on."""
 import ctypes as C
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -23,7 +39,7 @@ from mvsdf_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
 
-CNT_N_SECANT, CNT_N_SAMPLER, CNT_N_MINSDF = 4, 5, 6               # include/mvsdf_hip.h MVSDF_CNT_*
+CNT_N_SECANT, CNT_N_SAMPLER, CNT_N_MINSDF, CNT_TAIL_WGS = 4, 5, 6, 11        # include/mvsdf_hip.h MVSDF_CNT_*
 TILINGS = ((1, 1), (2, 3), (4, 4))
 ENGINES = {'f32': False, 'f32x3': 'f32x3', 'bf16w': 'weights'}    # ops.TRACE_DTYPES name -> oracle.Net(bf16=...)
 
@@ -69,6 +85,16 @@ def assert_list_counters(cnt, counts, what):
     assert (int(cnt[CNT_N_SAMPLER]), int(cnt[CNT_N_SECANT]), int(cnt[CNT_N_MINSDF])) == tuple(counts), (what, cnt[:7].tolist(), counts)
 
 
+def assert_tail_counter(cnt, engine, W, R, mt, training, what):
+    """counters[MVSDF_CNT_TAIL_WGS]: under tail filling every sphere-tracing workgroup counts itself once when its rays are done, without it nobody does.  So the
+    counter is the sphere kernel's grid at the EFFECTIVE row tiles (W = 512: at most 2) where csrc/trace_route.h::mv_tail_on says on -- training, the fp32-MFMA
+    engines always, 'f32x3' above 2048 rays, the split engines only under MVSDF_TAIL=2, and at most one workgroup per compute unit -- and 0 elsewhere."""
+    grid = -(-R // (8 * (min(mt, 2) if W > 256 else mt)))
+    need = 1 if engine in ('f32', 'bf16w') or (engine == 'f32x3' and R > 2048) else 2
+    on = training and int(os.environ.get('MVSDF_TAIL', '1')) >= need and grid <= torch.cuda.get_device_properties(0).multi_processor_count
+    assert int(cnt[CNT_TAIL_WGS]) == (grid if on else 0), (what, 'tail filling', on, grid, int(cnt[CNT_TAIL_WGS]))
+
+
 class Counting:
     """An opaque `sdf` callable that records how many rows each call got"""
 
@@ -80,6 +106,33 @@ class Counting:
         self.calls.append(int(x.shape[0]))
         y = self.fn(x)
         return y.reshape(-1, 1) if self.column else y
+
+
+def trace_staged(net, d, c, training, mt, mts, stages=(1, 3, 7, 5)):
+    """The launches of ops.trace one by one through the C ABI: sphere tracing (1), the sampler rows (3), the secant chains ALONE in the form
+    csrc/trace_route.h::mv_route_secant picks (7), the min-sdf rows alone (5).  Same outputs, same counters as the one call."""
+    from mvsdf_amd._lib import TraceParams, check, lib, ptr, stream_of
+    B, P = c.ray_dirs.shape[:2]
+    R = B * P
+    tp = TraceParams(*TC.params_tuple(c.params))
+    desc = net.desc()
+    om = d['object_mask'].view(torch.uint8)
+    pts = torch.empty(R, 3, device='cuda'); mask = torch.empty(R, dtype=torch.uint8, device='cuda'); dists = torch.empty(R, device='cuda')
+    cnt = torch.empty(16, dtype=torch.int64, device='cuda')
+    wsb = lib().mvsdf_trace_workspace_bytes_n(R, tp.n_steps)
+    ws = torch.empty(wsb, dtype=torch.uint8, device='cuda')
+    for stage in stages:
+        check(lib().mvsdf_trace_stage(stage, C.byref(desc), C.byref(tp), ptr(d['cam_loc']), ptr(d['ray_dirs']), ptr(om), B, P, 1 if training else 0, ptr(d['intervals']),
+                                      ptr(d['minsdf_steps']), ptr(pts), ptr(mask), ptr(dists), ptr(cnt), ptr(ws), C.c_size_t(wsb), mt, mts, stream_of(d['ray_dirs'])),
+              'mvsdf_trace_stage(%d)' % stage)
+    return pts, mask.view(torch.bool), dists, cnt
+
+
+def assert_identical(got, ref, what):
+    """two runs of the library: points, mask, dists of all rays and counters[:7] (rows per stage, list lengths), bit for bit"""
+    for a, b, k in zip(got[:3], ref[:3], ('points', 'mask', 'dists')):
+        assert np.array_equal(a, b), (what, k, int((a != b).sum()))
+    assert np.array_equal(got[3][:7], ref[3][:7]), (what, got[3][:7].tolist(), ref[3][:7].tolist())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -155,12 +208,20 @@ def _fused_vs_oracle(oracle, name, W, engine, tilings):
     for training in (True, False):
         want = _oracle_net_run(name, W, engine, training)
         counts = list_counts(oracle, onet, c, training, want[3])
+        ref = None
         for mt, mts in tilings:
-            what = (name, engine, 'train' if training else 'eval', mt, mts)
+            what = (name, W, engine, 'train' if training else 'eval', mt, mts)
             got = to_np(ops.trace(net, d['cam_loc'], d['ray_dirs'], d['object_mask'], TC.params_tuple(c.params), training, d['intervals'], d['minsdf_steps'],
                                   mt=mt, mt_samples=mts))
             assert_same(got, want, what)
             assert_list_counters(got[3], counts, what)
+            assert_tail_counter(got[3], engine, W, c.object_mask.size, mt, training, what)
+            staged = to_np(trace_staged(net, d, c, training, mt, mts))
+            assert_tail_counter(staged[3], engine, W, c.object_mask.size, mt, training, what + ('staged',))
+            assert_same(staged, want, what + ('staged',))
+            assert_identical(staged, got, what + ('staged',))
+            ref = got if ref is None else ref
+            assert_identical(got, ref, what + tilings[0])        # (follows from the above; at W = 512 this is the clamped request (4, 4) against (2, 3))
 
 
 BIG = ('r2048', 'r2049', 'r4096', 'r4097', 'r8192', 'r8193')
@@ -182,6 +243,27 @@ def test_fused_route_bit_exact_vs_oracle(oracle, name, engine):
 @pytest.mark.parametrize('name,engine,tilings', BIG_RUNS, ids=['%s-%s' % r[:2] for r in BIG_RUNS])
 def test_fused_route_around_one_workgroup_per_compute_unit(oracle, name, engine, tilings):
     _fused_vs_oracle(oracle, name, 64, engine, tilings)
+
+
+# W = 256 and W = 512 (the reference's shipped width): the rows of trace_cases.WIDE.  The instruction model of 'f32x3' is slow at W = 512: a subset there, and no big row.
+WIDE = tuple(TC.WIDE)
+X3_512 = ('one', 'r7', 'r8', 'r9', 'r15', 'r16', 'r17', 'r31', 'r33', 'n2', 'n13', 'n129', 'wrap', 'miss7')
+WIDE_RUNS = [(n, e, W) for W in TC.WIDE_WIDTHS for e in ('f32', 'bf16w') for n in WIDE] + [(n, 'f32x3', 256) for n in WIDE] + [(n, 'f32x3', 512) for n in X3_512]
+# tail filling on / off one ray later (assert_tail_counter holds the pair to on / off on a device of 256 compute units): 'f32x3' (above 2048 rays only) at mt = 2, W = 256: a grid of 256 / 257; 'f32' at W = 512, where the EFFECTIVE mt of a request
+# of 4 is 2 -- the same on / off pair for (2, 3) and (4, 4); 'f32' at W = 256 and mt = 1
+WIDE_BIG_RUNS = [('r4096', 'f32x3', 256, ((2, 3),)), ('r4097', 'f32x3', 256, ((2, 3),)), ('r4096', 'f32', 512, ((2, 3), (4, 4))), ('r4097', 'f32', 512, ((2, 3), (4, 4))),
+                 ('r2048', 'f32', 256, ((1, 1),)), ('r2049', 'f32', 256, ((1, 1),))]
+
+
+@pytest.mark.parametrize('name,engine,W', WIDE_RUNS, ids=['%s-%s-%d' % r for r in WIDE_RUNS])
+def test_fused_route_wide_bit_exact_vs_oracle(oracle, name, engine, W):
+    assert TC.declared(name, W) is not None
+    _fused_vs_oracle(oracle, name, W, engine, TILINGS)
+
+
+@pytest.mark.parametrize('name,engine,W,tilings', WIDE_BIG_RUNS, ids=['%s-%s-%d' % r[:3] for r in WIDE_BIG_RUNS])
+def test_fused_route_wide_around_one_workgroup_per_compute_unit(oracle, name, engine, W, tilings):
+    _fused_vs_oracle(oracle, name, W, engine, tilings)
 
 
 def test_fused_route_width_256_three_term_engine(oracle):
@@ -212,6 +294,70 @@ def test_generic_route_equals_fused_route(oracle, name, engine):
         assert_list_counters(gen[3], counts, what + ('generic',))
         assert np.array_equal(gen[3][:7], fus[3][:7]), (what, gen[3][:7].tolist(), fus[3][:7].tolist())
         assert sum(sdf.calls) == int(want[3].sum())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# the split engines: exact identities on the edge rows
+SPLIT = ('bf16x2', 'bf16x3')
+SPLIT_WIDE = X3_512 + ('st0', 'b4', 'om_none')
+SPLIT_TILING_RUNS = [(64, n) for n in SMALL] + [(W, n) for W in TC.WIDE_WIDTHS for n in SPLIT_WIDE]
+SPLIT_ROUTE_RUNS = [(64, n) for n in ('default', 'r08', 'render', 'st0', 'wrap', 'n129', 'r17', 'b4')] + [(W, n) for W in TC.WIDE_WIDTHS for n in ('r17', 'n13', 'wrap')]
+
+
+@functools.lru_cache(maxsize=None)
+def _split_net(W, engine):
+    return ops.pack_trace_net(sdf_packed_net(synth.make_state_dict(W, 0)), engine)
+
+
+def assert_declared_lists_filled(cnt, name, W, training, what):
+    """The non-vacuity guard: the lists the table declares filled for the width-W network (on fp32 arithmetic, training) hold rays on this engine too.  The
+    rounded weights move a count by a ray or two, never to zero where the table says Y (Y: at least 3 rays at the wide networks) -- but for the single ray of the
+    rows in trace_cases.ROUNDED_EMPTY (tests/test_trace_cases_host.py holds both statements on the oracle of the rounded weights).  Eval has no min-sdf list."""
+    if (W, name) in TC.ROUNDED_EMPTY:
+        return
+    for k, want, in_eval in zip((CNT_N_SAMPLER, CNT_N_SECANT, CNT_N_MINSDF), TC.declared(name, W), (True, True, False)):
+        if want is True and (training or in_eval):
+            assert int(cnt[k]) > 0, (what, 'the list of counter %d is empty' % k, cnt[:7].tolist())
+
+
+@pytest.mark.parametrize('engine', SPLIT)
+@pytest.mark.parametrize('W,name', SPLIT_TILING_RUNS, ids=['%d-%s' % r for r in SPLIT_TILING_RUNS])
+def test_split_engines_tilings_give_the_same_bits(W, name, engine):
+    """(a) every (mt, mt_samples) of TILINGS, as one call and as the staged launches: the same points, mask, dists and counters[:7]"""
+    c = TC.case(name)
+    net = _split_net(W, engine)
+    assert net.trace_dtype == ops.TRACE_DTYPES[engine]
+    d = dev_case(c)
+    for training in (True, False):
+        ref = None
+        for mt, mts in TILINGS:
+            what = (name, W, engine, 'train' if training else 'eval', mt, mts)
+            got = to_np(ops.trace(net, d['cam_loc'], d['ray_dirs'], d['object_mask'], TC.params_tuple(c.params), training, d['intervals'], d['minsdf_steps'],
+                                  mt=mt, mt_samples=mts))
+            assert_declared_lists_filled(got[3], name, W, training, what)
+            assert_tail_counter(got[3], engine, W, c.object_mask.size, mt, training, what)
+            ref = got if ref is None else ref
+            assert_identical(got, ref, what + TILINGS[0])
+            assert_identical(to_np(trace_staged(net, d, c, training, mt, mts)), ref, what + ('staged',))
+
+
+@pytest.mark.parametrize('engine', SPLIT)
+@pytest.mark.parametrize('W,name', SPLIT_ROUTE_RUNS, ids=['%d-%s' % r for r in SPLIT_ROUTE_RUNS])
+def test_split_engines_generic_route_equals_fused_route(W, name, engine):
+    """(b) csrc/trace.hip's promise for ONE engine arithmetic, on the split engines: the generic route around ops.sdf_col0 (the row-sample kernels' weight fetch)
+    and the fused route (k_sphere_trace carries its weights across layers) agree on every output and on counters[:7]; the callable saw exactly the rows counted."""
+    c = TC.case(name)
+    net = _split_net(W, engine)
+    d = dev_case(c)
+    for training in (True, False):
+        sdf = Counting(lambda x: ops.sdf_col0(net, x))
+        args = (d['cam_loc'], d['ray_dirs'], d['object_mask'], TC.params_tuple(c.params), training, d['intervals'], d['minsdf_steps'])
+        gen = to_np(ops.trace_generic(sdf, *args))
+        fus = to_np(ops.trace(net, *args))
+        what = (name, W, engine, 'train' if training else 'eval')
+        assert_declared_lists_filled(fus[3], name, W, training, what)
+        assert_identical(gen, fus, what)
+        assert sum(sdf.calls) == int(gen[3][:4].sum()) == int(fus[3][:4].sum())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

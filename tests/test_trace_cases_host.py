@@ -58,6 +58,42 @@ def test_network_rows_do_what_they_declare(oracle, name):
             _check_declared(name, c.fused, TC.list_counts(out[3], c.params), out[3], c.params)
 
 
+@pytest.mark.parametrize('W', TC.WIDE_WIDTHS)
+@pytest.mark.parametrize('name', list(TC.WIDE))
+def test_wide_network_rows_do_what_they_declare(oracle, name, W):
+    """the per-width declarations (W = 256, W = 512): the same row fills other lists on another network"""
+    c = TC.case(name)
+    assert TC.declared(name, W) is not None and TC.declared(name, 64) is not None       # a row of the wide table is a row of the fused table
+    net = oracle.Net(synth.make_state_dict(W, 0))
+    for training in (True, False):
+        out = oracle.trace(net, c.cam_loc, c.ray_dirs, c.object_mask, training, c.minsdf_steps, c.intervals, **c.params)
+        _check_outputs(c, out)
+        if training:
+            _check_declared('%s at W = %d' % (name, W), TC.declared(name, W), TC.list_counts(out[3], c.params), out[3], c.params)
+
+
+@pytest.mark.parametrize('W', (64,) + TC.WIDE_WIDTHS)
+def test_rounded_weights_keep_the_declared_lists_filled(oracle, W):
+    """tests/test_gpu_trace_edges.py asserts on the split engines, which run on bf16-rounded weights and have no exact CPU model, that the lists a row declares
+    filled (for fp32 weights) hold rays.  On the oracle of the rounded weights that is so on every row but the ones of ROUNDED_EMPTY, which are empty there."""
+    net = oracle.Net(synth.make_state_dict(W, 0), bf16='weights')
+    for name in (TC.FUSED if W == 64 else TC.WIDE):
+        c = TC.case(name)
+        counts = TC.list_counts(oracle.trace(net, c.cam_loc, c.ray_dirs, c.object_mask, True, c.minsdf_steps, c.intervals, **c.params)[3], c.params)
+        filled = [got > 0 for want, got in zip(TC.declared(name, W), counts) if want is True]
+        assert not any(filled) if (W, name) in TC.ROUNDED_EMPTY else all(filled), (name, W, counts)
+    assert all(k[1] in TC.FUSED for k in TC.ROUNDED_EMPTY)
+
+
+def test_the_wide_table_fills_every_list_at_both_widths():
+    """each of the three lists is declared filled on several rows and empty on one, at W = 256 and at W = 512; 'inside' is declared per width"""
+    for k in range(len(TC.WIDE_WIDTHS)):
+        for lst in range(3):
+            assert sum(v[k][lst] is True for v in TC.WIDE.values()) >= 3 and any(v[k][lst] is False for v in TC.WIDE.values())
+    assert TC.WIDE['inside'][0] != TC.WIDE['inside'][1]
+    assert set(TC.WIDE) <= set(TC.FUSED)
+
+
 def test_the_table_reaches_every_branch(oracle):
     """Over the whole table (analytic SDF, training): each of the three lists is empty in one row and filled in another, both lists of the generic route's
     compaction kernel grow past a 1024-ray chunk, rays that miss the sphere take the -(d . c) projection, a camera sits inside the sphere, and the

@@ -8,7 +8,8 @@ camera_rays, np.random.RandomState(seed) for the object mask (uniform < p) and t
 
 `lists` declares, for TRAINING mode with the analytic SDF (helpers.analytic_sdf), which work lists the row is there to populate (True), to leave empty (False) or
 does not care about (None): (sampler, secant, min-sdf).  `fused` declares the same for the W = 64 network (synth.make_state_dict(64, 0), fp32 arithmetic) on the
-rows the fused-route tests use.  The comment behind each row records the oracle's counts when the row was written:
+rows the fused-route tests use; `WIDE` declares it for the W = 256 and the W = 512 network (synth.make_state_dict(W, 0), fp32 arithmetic) on the rows the
+fused-route tests run at those widths.  The comment behind each row records the oracle's counts when the row was written:
     isect / sampler / secant / min-sdf rays   (sampler = rows[1] / n_steps, secant = rows[2] / n_secant_steps, min-sdf = rows[3] / n_steps)
 -- a record for the reader; the tests assert the declarations, not these numbers."""
 import functools
@@ -35,6 +36,7 @@ ROWS = {
     'n2':           Row(1, 65, 6, 2.5, 0.8, 1.4, 1.0, 2, 10, 3, 8, 0.5, 0.7, (Y, N, Y), (Y, Y, Y)),                    # 64 / 11 / 0 / 43 | 64 / 22 / 7 / 20
     'n512':         Row(1, 63, 7, 2.5, 0.8, 1.4, 1.0, 512, 2, 5, 0, 0.5, 0.7, (Y, _, Y), None),                        # 62 / 42 / (0 steps) / 20 | -  (no secant steps)
     'one':          Row(1, 1, 8, 2.5, 0.8, 1.4, 1.0, 16, 10, 3, 8, 0.5, 1.1, (N, N, N), (Y, Y, N)),                    # 1 / 0 / 0 / 0 | 1 / 1 / 1 / 0
+    'one_s':        Row(1, 1, 100, 2.5, 0.8, 1.4, 1.0, 16, 10, 3, 8, 0.5, 1.1, None, (Y, Y, N)),                       # - | 1 / 1 / 1 / 0  ('one' with another seed: sampled on the bf16-rounded weights too, ROUNDED_EMPTY)
     'st0':          Row(1, 200, 9, 2.5, 0.8, 1.4, 1.0, 16, 0, 3, 8, 0.5, 0.7, (Y, Y, N), (Y, Y, N)),                   # 196 / 196 / 55 / 0 | 196 / 196 / 114 / 0  (no sphere tracing: every intersecting ray is sampled)
     # ---- the sampler's window (12 samples first, then the rest) and the 64-lane steps of the per-ray scans
     'n12':          Row(1, 301, 12, 2.5, 0.8, 1.4, 1.0, 12, 3, 1, 3, 0.5, 0.7, (Y, Y, Y), (Y, Y, Y)),                  # 298 / 102 / 55 / 149 | 298 / 275 / 181 / 18  (single pass)
@@ -69,6 +71,39 @@ ROWS = {
     # ---- four cameras, an odd number of rays each (gid / P picks the camera)
     'b4':           Row(4, 77, 61, 2.2, -0.3, 1.1, 1.0, 37, 3, 1, 3, 0.5, 0.6, (Y, Y, Y), (Y, Y, Y)),                  # 300 / 135 / 70 / 161 | 300 / 169 / 97 / 65
 }
+# ---- the wider networks: (sampler, secant, min-sdf) of synth.make_state_dict(W, 0) on fp32 arithmetic, training, per width -- the same row does different things at
+#      different widths ('inside': the W = 512 network is negative at the camera, the W = 256 one is not).  Y: at least 3 rays, N: none, _: one or two rays (the engines on
+#      bf16-rounded weights, whose lists tests/test_gpu_trace_edges.py holds to these declarations, move a count by a ray or two) and the rows that are there for their
+#      ray COUNT (r7 ... r33, as in `fused`).  Recorded counts: sampler / secant / min-sdf rays.
+#                   W = 256    W = 512
+WIDE = {
+    'one':      ((_, N, N), (_, _, N)),                             # 1 / 0 / 0 | 1 / 1 / 0
+    'r7':       ((_, _, _), (_, _, _)),                             # 1 / 0 / 5 | 3 / 1 / 4
+    'r8':       ((_, _, _), (_, _, _)),                             # 5 / 2 / 3 | 5 / 2 / 3
+    'r9':       ((_, _, _), (_, _, _)),                             # 7 / 4 / 2 | 8 / 5 / 1
+    'r15':      ((_, _, _), (_, _, _)),                             # 7 / 0 / 8 | 14 / 3 / 1
+    'r16':      ((_, _, _), (_, _, _)),                             # 9 / 3 / 6 | 11 / 6 / 4
+    'r17':      ((_, _, _), (_, _, _)),                             # 3 / 1 / 14 | 12 / 2 / 5
+    'r31':      ((_, _, _), (_, _, _)),                             # 12 / 5 / 19 | 17 / 10 / 14
+    'r33':      ((_, _, _), (_, _, _)),                             # 14 / 2 / 19 | 24 / 9 / 9
+    'n2':       ((Y, N, Y), (Y, N, Y)),                             # 9 / 0 / 46 | 22 / 0 / 37
+    'n12':      ((Y, Y, Y), (Y, Y, Y)),                             # 145 / 66 / 148 | 231 / 104 / 67
+    'n13':      ((Y, Y, Y), (Y, Y, Y)),                             # 140 / 67 / 154 | 226 / 94 / 70
+    'n64':      ((Y, Y, Y), (Y, Y, Y)),                             # 133 / 63 / 167 | 222 / 92 / 78
+    'n65':      ((Y, Y, Y), (Y, Y, Y)),                             # 143 / 74 / 149 | 228 / 110 / 69
+    'n129':     ((Y, Y, Y), (Y, Y, Y)),                             # 35 / 14 / 28 | 48 / 23 / 15
+    'st0':      ((Y, Y, N), (Y, Y, N)),                             # 196 / 36 / 0 | 196 / 54 / 0
+    'wrap':     ((Y, Y, N), (Y, Y, N)),                             # 196 / 37 / 0 | 196 / 55 / 0
+    'om_none':  ((Y, N, Y), (Y, N, Y)),                             # 41 / 0 / 257 | 115 / 0 / 183
+    'b4':       ((Y, Y, Y), (Y, Y, Y)),                             # 136 / 52 / 163 | 214 / 74 / 86
+    'inside':   ((Y, Y, Y), (N, N, Y)),                             # 227 / 164 / 104 | 0 / 0 / 167
+    'r08':      ((Y, Y, Y), (Y, Y, Y)),                             # 320 / 138 / 50 | 357 / 192 / 13
+    'miss7':    ((N, N, N), (N, N, N)),                             # 0 / 0 / 0 | 0 / 0 / 0
+}
+WIDE_WIDTHS = (256, 512)
+# (W, row): the lists the row declares filled are EMPTY on the bf16-rounded weights (oracle.Net(sd, bf16='weights'), the arithmetic the 'bf16x2' / 'bf16x3' engines
+# follow up to the order of their fp32 additions): the one ray of 'one' converges in sphere tracing there.  'one_s' is the row that keeps a single sampled ray.
+ROUNDED_EMPTY = {(64, 'one')}
 LONG_LISTS = {'st0_2049': 'sampler', 'om_none_2049': 'minsdf'}      # rows whose named list must hold more than 1024 rays (analytic SDF, training)
 WRAP = 'wrap'                                                        # intervals that start inside the object: the first sign change at sample 0
 ALL_MISS = 'miss7'                                                   # every ray misses the sphere: the -(d . c) projection in training, no evaluation at all
@@ -76,6 +111,13 @@ ALL_MISS = 'miss7'                                                   # every ray
 ANALYTIC = tuple(k for k, v in ROWS.items() if v.lists is not None) + (ALL_MISS, WRAP)
 FUSED = tuple(k for k, v in ROWS.items() if v.fused is not None) + (ALL_MISS, WRAP)
 NAMES = tuple(ROWS) + (ALL_MISS, WRAP)
+
+
+def declared(name, W):
+    """the (sampler, secant, min-sdf) declaration of a row for the width-W network on fp32 arithmetic, or None where the table declares nothing"""
+    if W == 64:
+        return case(name).fused
+    return WIDE[name][WIDE_WIDTHS.index(W)] if name in WIDE else None
 
 
 def _intervals(n):
