@@ -848,6 +848,26 @@ int mvsdf_viewsel_depths(const double* points, const void* bits, const double* e
                          double* z, void* hdr, void* stream);
 int mvsdf_viewsel_weights_host(const double* a, const double* b, int64_t n, double theta0, double sigma1, double sigma2, double* theta, int64_t* wq);
 
+/* ---- Image undistortion (undistort.hip; Python: mvsdf_amd/undistort.py, which states the definition) ----
+ * COLMAP's distorted camera models to pinhole views; fp64 throughout, the fisheye atan2 the written-out one of csrc/det_math64.h.  model: 0 no
+ * distortion, 1 radial (k1, k2), 2 OpenCV (k1, k2, p1, p2, k3, k4, k5, k6), 3 fisheye (k1 .. k4).  params: HOST fp64 [12] = fx, fy, cx, cy of the
+ * distorted camera and the model's coefficients, the unused ones 0.  pinhole / out_pinhole: HOST fp64 [4] = fx, fy, cx, cy of the undistorted view.
+ * Every value must be finite and the focal lengths > 0.
+ * mvsdf_undistort_points: points fp64 [n][2] on the device.  inverse != 0: source pixels -> pixels of the pinhole through the Newton iteration of the
+ * inverse map; inverse == 0: pixels of the pinhole -> source pixels through the forward map.  hdr: 256 device bytes, int64 {0, error bits}, reset by
+ * the call and read by the caller: 1 a non-finite value or a zero determinant, 2 an iteration that ended above 1e-10 px.
+ * mvsdf_undistort_images: src [views][H][W][C] -> dst [views][oH][oW][C] on the device, C in 1 .. 4, dtype 0 uint8 or 1 float32, bilinear; pixels that
+ * look outside the source are 0.  mask: uint8 [oH][oW] (1 = looks inside) or NULL.  Sides up to 2^24; all offsets are 64-bit.  No call waits.
+ * The _host functions run the same arithmetic on the CPU over host memory (no GPU needed); *err receives the error bits. */
+int mvsdf_undistort_points(const double* points, int64_t n, int model, const double* params, const double* pinhole, int inverse, double* out, void* hdr,
+                           void* stream);
+int mvsdf_undistort_images(const void* src, int64_t views, int64_t H, int64_t W, int64_t C, int dtype, int model, const double* params,
+                           const double* out_pinhole, int64_t oH, int64_t oW, void* dst, uint8_t* mask, void* stream);
+int mvsdf_undistort_points_host(const double* points, int64_t n, int model, const double* params, const double* pinhole, int inverse, double* out,
+                                int64_t* err);
+int mvsdf_undistort_images_host(const void* src, int64_t views, int64_t H, int64_t W, int64_t C, int dtype, int model, const double* params,
+                                const double* out_pinhole, int64_t oH, int64_t oW, void* dst, uint8_t* mask);
+
 /* ---- Training batches assembled on the device (batch_kernels.hip; Python: mvsdf_amd/datasets/device_batches.py) ----
  * One launch builds the whole step batch of SceneDataset.__getitem__ + collate_fn (mvsdf_amd/datasets/scene_dataset.py) for B views from pools that
  * stay on the device for the whole run: per view b (v = views[b]) and per sampled pixel p (id = pix[p], or p itself when pix is NULL: full images)

@@ -152,6 +152,10 @@ def lib():
         L.mvsdf_viewsel_scores.argtypes = [vp, vp, vp, i64, i64, f64, f64, f64, vp, sz, vp, vp, vp, vp]
         L.mvsdf_viewsel_depths.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp]
         L.mvsdf_viewsel_weights_host.argtypes = [vp, vp, i64, f64, f64, f64, vp, vp]
+        L.mvsdf_undistort_points.argtypes = [vp, i64, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+        L.mvsdf_undistort_images.argtypes = [vp, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, i64, vp, vp, vp]
+        L.mvsdf_undistort_points_host.argtypes = [vp, i64, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.mvsdf_undistort_images_host.argtypes = [vp, i64, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, i64, vp, vp]
         L.mvsdf_batch_args_bytes.restype = sz
         L.mvsdf_batch_args_bytes.argtypes = []
         L.mvsdf_batch_gather.argtypes = [vp, vp]
@@ -194,6 +198,7 @@ EXPORTS = [
     'mvsdf_stereo_upsample', 'mvsdf_stereo_band_workspace_bytes', 'mvsdf_stereo_band',
     'mvsdf_viewsel_bits_bytes', 'mvsdf_viewsel_workspace_bytes', 'mvsdf_viewsel_pack_dense', 'mvsdf_viewsel_pack_tracks', 'mvsdf_viewsel_scores',
     'mvsdf_viewsel_depths', 'mvsdf_viewsel_weights_host',
+    'mvsdf_undistort_points', 'mvsdf_undistort_images', 'mvsdf_undistort_points_host', 'mvsdf_undistort_images_host',
     'mvsdf_batch_args_bytes', 'mvsdf_batch_gather',
 ]
 

@@ -8,8 +8,11 @@ ERROR (IMAGE_ID POINT2D_IDX)...`.  Binary: little-endian, counts as uint64, the 
 name, image names end with a zero byte).  A pose maps world to camera: x_cam = R(qw, qx, qy, qz) x + t.
 
 Cameras: SIMPLE_PINHOLE and PINHOLE are taken as they are; SIMPLE_RADIAL, RADIAL and OPENCV only if every distortion parameter is 0; anything else
-raises ValueError (undistort the images first, e.g. with COLMAP's image_undistorter: undistortion is not built here).  COLMAP puts the centre of
-pixel (0, 0) at (0.5, 0.5), which is this project's X = x + 0.5 (fusion.py), so cx and cy are kept unchanged.
+raises ValueError (undistort the images first) unless undistortion is asked for: colmap_to_mvs(..., undistort=True), or tools/undistort.py
+beforehand, resamples the images on the device to pinhole views (mvsdf_amd/undistort.py states what is computed) for SIMPLE_RADIAL, RADIAL, OPENCV,
+FULL_OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE and RADIAL_FISHEYE cameras.  load_colmap_model(dir, allow_distortion=True) loads such a model;
+FOV, THIN_PRISM_FISHEYE and unknown models stay refused.  write_colmap_text writes a model back in the text format.  COLMAP puts the centre of pixel
+(0, 0) at (0.5, 0.5), which is this project's X = x + 0.5 (fusion.py), so cx and cy are kept unchanged.
 """
 import os
 import shutil
@@ -160,11 +163,12 @@ def _read_binary(d):
     return cameras, images, _points(ids, xyz, rgb, err, off, timg, tidx)
 
 
-def load_colmap_model(model_dir):
+def load_colmap_model(model_dir, allow_distortion=False):
     """-> {'cameras': {id: {'model', 'width', 'height', 'params' fp64}}, 'images': {id: {'q' (qw qx qy qz), 't', 'camera_id', 'name', 'xys' fp64 [n,2],
     'point3D_ids' int64 [n]}}, 'points': {'ids' int64 [N], 'xyz' fp64 [N,3], 'rgb' uint8 [N,3], 'error' fp64 [N], 'track_off' int64 [N+1],
     'track_image' int32, 'track_point2D' int32 (the tracks in CSR form, by COLMAP image id)}}.  Reads cameras.txt / images.txt / points3D.txt where
-    all three exist, else the .bin files.  Every camera must be one colmap_to_mvs can use (camera_intrinsics)."""
+    all three exist, else the .bin files.  Every camera must be one colmap_to_mvs can use (camera_intrinsics) or, with allow_distortion, one
+    mvsdf_amd/undistort.py can turn into such a camera (undistort.camera_block)."""
     names = ('cameras', 'images', 'points3D')
     if all(os.path.exists(os.path.join(model_dir, n + '.txt')) for n in names):
         cameras, images, points = _read_text(model_dir)
@@ -173,11 +177,42 @@ def load_colmap_model(model_dir):
     else:
         raise FileNotFoundError('colmap: %s holds neither cameras / images / points3D .txt nor .bin' % model_dir)
     for cam in cameras.values():
-        camera_intrinsics(cam)
+        if allow_distortion:
+            from ..undistort import camera_block
+            camera_block(cam)
+        else:
+            camera_intrinsics(cam)
     for iid, im in images.items():
         if im['camera_id'] not in cameras:
             raise ValueError('colmap: image %d refers to camera %d, which the model does not hold' % (iid, im['camera_id']))
     return {'cameras': cameras, 'images': images, 'points': points}
+
+
+def write_colmap_text(model, model_dir):
+    """A model (the dict load_colmap_model returns) -> model_dir/cameras.txt, images.txt and points3D.txt in COLMAP's text format; every float is
+    written with repr, so load_colmap_model reads back the same bits"""
+    os.makedirs(model_dir, exist_ok=True)
+
+    def floats(xs):
+        return ' '.join(repr(float(x)) for x in xs)
+    with open(os.path.join(model_dir, 'cameras.txt'), 'w') as f:
+        f.write('# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]\n# Number of cameras: %d\n' % len(model['cameras']))
+        for cid, c in model['cameras'].items():
+            f.write('%d %s %d %d %s\n' % (cid, c['model'], c['width'], c['height'], floats(c['params'])))
+    with open(os.path.join(model_dir, 'images.txt'), 'w') as f:
+        f.write('# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n#   POINTS2D[] as (X, Y, POINT3D_ID)\n'
+                '# Number of images: %d\n' % len(model['images']))
+        for iid, im in model['images'].items():
+            f.write('%d %s %d %s\n' % (iid, floats(list(im['q']) + list(im['t'])), im['camera_id'], im['name']))
+            f.write(' '.join('%r %r %d' % (float(x), float(y), p) for (x, y), p in zip(im['xys'], im['point3D_ids'])) + '\n')
+    pts = model['points']
+    with open(os.path.join(model_dir, 'points3D.txt'), 'w') as f:
+        f.write('# 3D point list with one line of data per point:\n#   POINT3D_ID, X, Y, Z, R, G, B, ERROR, TRACK[] as (IMAGE_ID, POINT2D_IDX)\n'
+                '# Number of points: %d\n' % len(pts['ids']))
+        for k, pid in enumerate(pts['ids']):
+            a, b = pts['track_off'][k], pts['track_off'][k + 1]
+            track = ' '.join('%d %d' % (i, j) for i, j in zip(pts['track_image'][a:b], pts['track_point2D'][a:b]))
+            f.write(('%d %s %d %d %d %r %s' % (pid, floats(pts['xyz'][k]), pts['rgb'][k][0], pts['rgb'][k][1], pts['rgb'][k][2], float(pts['error'][k]), track)).rstrip() + '\n')
 
 
 def model_views(model):
@@ -199,11 +234,15 @@ def model_views(model):
     return ids, [model['images'][i]['name'] for i in ids], cams, view
 
 
-def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, num_pairs=10, theta0=5, sigma1=1, sigma2=10):
+def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, num_pairs=10, theta0=5, sigma1=1, sigma2=10, undistort=False,
+                  blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
     """A COLMAP model and its (undistorted) images -> out_root/images/<i:08>.jpg|png (jpg and png copied as they are, other formats re-encoded as png),
     out_root/cams/<i:08>_cam.txt (extrinsic, intrinsic, `depth_min interval max_d depth_max` with interval = (depth_max - depth_min) / (max_d - 1) /
     interval_scale, from viewsel.depth_ranges) and out_root/pair.txt (viewsel.view_scores + select_pairs over the model's tracks).  max_d = 0, the
-    automatic hypothesis count of MVSNet's script, is not built.  -> {'ids', 'names', 'cams' [V,2,4,4], 'pairs', 'pair_scores', 'scores', 'counts'}."""
+    automatic hypothesis count of MVSNet's script, is not built.  undistort=True takes a model with distorted cameras (load_colmap_model's
+    allow_distortion): every image is resampled on the device to its camera's pinhole view (undistort.undistorted_camera with blank_pixels, min_scale,
+    max_scale) and written as png, and the camera files carry that view's intrinsics; pairs and depth ranges use points, centres and extrinsics only
+    and are what they are without it.  -> {'ids', 'names', 'cams' [V,2,4,4], 'pairs', 'pair_scores', 'scores', 'counts'}."""
     from .. import viewsel
     from ..stereo import _write_cam
     what = 'colmap_to_mvs'
@@ -212,7 +251,11 @@ def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, n
         raise ValueError('%s: max_d must be >= 2 (max_d = 0, the automatic hypothesis count, is not built), got %d' % (what, max_d))
     if not float(interval_scale) > 0:
         raise ValueError('%s: interval_scale must be > 0' % what)
-    model = load_colmap_model(model_dir)
+    model = load_colmap_model(model_dir, allow_distortion=bool(undistort))
+    if undistort:
+        from .. import undistort as und
+        source_cameras = model['cameras']
+        model = dict(model, cameras={cid: und.undistorted_camera(c, blank_pixels, min_scale, max_scale) for cid, c in source_cameras.items()})
     ids, names, cams, view = model_views(model)
     if not ids:
         raise ValueError('%s: the model holds no image' % what)
@@ -227,9 +270,16 @@ def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, n
     ranges = viewsel.depth_ranges(pts['xyz'], tracks, cams[:, 0]).cpu().numpy()
     os.makedirs(os.path.join(out_root, 'images'), exist_ok=True)
     os.makedirs(os.path.join(out_root, 'cams'), exist_ok=True)
+    if undistort:
+        for cid in sorted(source_cameras):                                  # one camera's images share one source map: they go through the kernel together
+            group = [i for i, iid in enumerate(ids) if model['images'][iid]['camera_id'] == cid]
+            und.undistort_files(source_cameras[cid], model['cameras'][cid], [paths[i] for i in group],
+                                [os.path.join(out_root, 'images', '%08d.png' % i) for i in group])
     for i, p in enumerate(paths):
         cams[i, 1, 3] = ranges[i, 0], (ranges[i, 1] - ranges[i, 0]) / (max_d - 1) / interval_scale, max_d, ranges[i, 1]
         _write_cam(os.path.join(out_root, 'cams', '%08d_cam.txt' % i), cams[i])
+        if undistort:
+            continue
         ext = os.path.splitext(p)[1].lower()
         if ext in ('.jpg', '.png'):
             shutil.copyfile(p, os.path.join(out_root, 'images', '%08d%s' % (i, ext)))
