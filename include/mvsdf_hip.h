@@ -98,7 +98,11 @@ enum {
     MVSDF_CNT_TAIL_NEXT = 9,    /* next unit of min-sdf rows to hand out */
     MVSDF_CNT_TAIL_READY = 10,  /* min-sdf list items completely written */
     MVSDF_CNT_TAIL_WGS = 11,    /* sphere-tracing workgroups whose rays are done */
-    MVSDF_CNT_TAIL_ROWS = 12    /* min-sdf rows evaluated inside the sphere-tracing kernel (a subset of counters[3]) */
+    MVSDF_CNT_TAIL_ROWS = 12,   /* min-sdf rows evaluated inside the sphere-tracing kernel (a subset of counters[3]) */
+    /* the sphere cut (mvsdf_trace_cut_stage): the sphere launch stops after a round limit, a resume launch finishes the rays that were not done */
+    MVSDF_CNT_N_SPILL = 13,         /* rays the limited launch handed to the resume launch */
+    MVSDF_CNT_N_SAMPLER_LATE = 14,  /* sampler rays the resume launch listed (their own list; counters[5] counts the first list only) */
+    MVSDF_CNT_LATE_ROUNDS = 15      /* evaluations the slowest workgroup of the resume launch still ran */
 };
 
 int mvsdf_version(void);
@@ -180,6 +184,20 @@ int mvsdf_trace_stage(int stage, const MvsdfNetDesc* net, const MvsdfTraceParams
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
                       size_t workspace_bytes, int mt, int mt_samples, void* stream);
+
+/* The sphere cut: stage 1 of mvsdf_trace_stage as two launches, for a caller with a second stream.  Most rays are final after st_iters + 1 dependent evaluations;
+ * stage 1 here stops every workgroup after max_rounds of them (<= 0: st_iters + 1), finalises its finished rays as usual and appends the complete state of the
+ * others to a spill list.  Stage 2 is the resume launch: the same kernel over the spilled rays, eight * mt per workgroup, to the end; its sampler rays go on a
+ * late list of their own.  Stage 3 evaluates the late list's sample rows (all n_steps in one pass) and reduces them.  Stages 2 and 3 touch nothing that
+ * mvsdf_trace_stage 3 (the sampler rows of the first list) reads or writes except atomic appends to the secant list, so the two may run concurrently; behind both,
+ * mvsdf_trace_stage 4 / 6 / 7 finds one secant list and mvsdf_trace_stage 4 / 5 one min-sdf list.  No launch uses tail filling.  Results are those of mvsdf_trace bit for
+ * bit; list orders and counters[8] (the late rays take one pass) may differ, counters[13..15] report the cut.  Same arguments as mvsdf_trace_stage; the workspace is
+ * mvsdf_trace_cut_workspace_bytes(B*P, n_steps) bytes for ALL launches of such a sequence: the regions of mvsdf_trace, then the spill list, the late list and its sample
+ * values (late list: int32[R] at byte offset al256(44 R + 8 R n_steps + 256) + 64 R). */
+size_t mvsdf_trace_cut_workspace_bytes(int R, int n_steps);
+int mvsdf_trace_cut_stage(int stage, int max_rounds, const MvsdfNetDesc* net, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                          const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
+                          float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
 
 /* ---- RayTracing.forward for an OPAQUE `sdf` callable (ray_tracing.py:27-32, called with a lambda at idr.py:194) ----
  * The per-ray state machine of mvsdf_trace split at its evaluation points, so that a host-side callable can be run between the launches:
@@ -456,6 +474,10 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
  * mvsdf_step_last_tracer_grid: out[2] = {secant workgroups, sample-row workgroups} of the last tracer launch of the last forward (0 row workgroups: deferred). */
 int mvsdf_step_resolve_unhit(void* step, void* fwd, void* stream);
 int mvsdf_step_can_defer_unhit(void* step);
+/* The sphere cut in MVSDF_STEP_UNHIT_DEFER forwards (mvsdf_trace_cut_stage: the late rays finish on a second stream beside the sampler windows, joined before the ray
+ * partition; no host wait).  enable < 0 (the default): where it pays (three-weight-term engine, one row tile per sphere workgroup, between half a workgroup and one per compute unit); 0: never -- the launch
+ * sequence without it; > 0: always.  max_rounds <= 0: st_iters + 1.  Same values with and without. */
+int mvsdf_step_set_sphere_cut(void* step, int enable, int max_rounds);
 int mvsdf_step_last_tracer_grid(void* step, int out[2]);
 /* blocks until the counts of the last mvsdf_step_forward are on the host: {N hit, N hit & true mask, depth-surface samples found per set x 2}.
  * The one host wait of a CLASSIC training step (the fused evaluation enqueued behind the count record keeps the GPU busy meanwhile); a DEFERRED

@@ -43,6 +43,8 @@ def lib():
         L.mvsdf_trace_workspace_bytes.argtypes = [C.c_int]
         L.mvsdf_trace_workspace_bytes_n.restype = C.c_size_t
         L.mvsdf_trace_workspace_bytes_n.argtypes = [C.c_int, C.c_int]
+        L.mvsdf_trace_cut_workspace_bytes.restype = C.c_size_t
+        L.mvsdf_trace_cut_workspace_bytes.argtypes = [C.c_int, C.c_int]
         for fn in ('mvsdf_sdf_ctx_floats', 'mvsdf_sdf_bwd_ws_floats', 'mvsdf_render_ctx_floats', 'mvsdf_render_bwd_ws_floats'):
             getattr(L, fn).restype = C.c_size_t
         L.mvsdf_adam_ws_floats.restype = C.c_size_t
@@ -168,14 +170,14 @@ def lib():
 # every symbol include/mvsdf_hip.h declares (tests/test_abi.py checks the header against this list and the .so)
 EXPORTS = [
     'mvsdf_version', 'mvsdf_abi_struct_sizes', 'mvsdf_last_error', 'mvsdf_packed_floats', 'mvsdf_fold_pack', 'mvsdf_fold_backward', 'mvsdf_fold_pack_net', 'mvsdf_fold_backward_net', 'mvsdf_packed_bf16_bytes', 'mvsdf_pack_bf16w_net', 'mvsdf_pack_bf16s_net', 'mvsdf_pack_bf16x3_net', 'mvsdf_pack_bf16x3t_net',
-    'mvsdf_sdf_col0', 'mvsdf_camera_rays', 'mvsdf_sphere_intersection', 'mvsdf_trace_workspace_bytes', 'mvsdf_trace_workspace_bytes_n', 'mvsdf_trace', 'mvsdf_trace_stage', 'mvsdf_det_math',
+    'mvsdf_sdf_col0', 'mvsdf_camera_rays', 'mvsdf_sphere_intersection', 'mvsdf_trace_workspace_bytes', 'mvsdf_trace_workspace_bytes_n', 'mvsdf_trace', 'mvsdf_trace_stage', 'mvsdf_trace_cut_workspace_bytes', 'mvsdf_trace_cut_stage', 'mvsdf_det_math',
     'mvsdf_tracegen_state_bytes', 'mvsdf_tracegen_init', 'mvsdf_tracegen_step', 'mvsdf_tracegen_finish', 'mvsdf_tracegen_rows', 'mvsdf_tracegen_reduce',
     'mvsdf_tracegen_secant',
     'mvsdf_sdf_ctx_floats', 'mvsdf_sdf_forward', 'mvsdf_sdf_bwd_ws_floats', 'mvsdf_sdf_backward', 'mvsdf_sdf_backward_pair', 'mvsdf_sdf_backward_finish',
     'mvsdf_feat_corr', 'mvsdf_depth_carve', 'mvsdf_loss_terms', 'mvsdf_loss_prep', 'mvsdf_loss_scale', 'mvsdf_adam_ws_floats', 'mvsdf_adam_step', 'mvsdf_adam_step_scaled', 'mvsdf_adam_step_fused',
     'mvsdf_partition_rays', 'mvsdf_step_outputs', 'mvsdf_step_backward_inputs', 'mvsdf_step_backward_fbar', 'mvsdf_dsurf_select', 'mvsdf_dsurf_points',
     'mvsdf_render_ctx_floats', 'mvsdf_render_bwd_ws_floats', 'mvsdf_render_forward', 'mvsdf_render_backward',
-    'mvsdf_step_create', 'mvsdf_step_destroy', 'mvsdf_step_forward', 'mvsdf_step_resolve_unhit', 'mvsdf_step_can_defer_unhit', 'mvsdf_step_last_tracer_grid', 'mvsdf_step_wait_counts', 'mvsdf_step_backward', 'mvsdf_step_set_timing', 'mvsdf_step_trace_times', 'mvsdf_step_times',
+    'mvsdf_step_create', 'mvsdf_step_destroy', 'mvsdf_step_forward', 'mvsdf_step_resolve_unhit', 'mvsdf_step_can_defer_unhit', 'mvsdf_step_set_sphere_cut', 'mvsdf_step_last_tracer_grid', 'mvsdf_step_wait_counts', 'mvsdf_step_backward', 'mvsdf_step_set_timing', 'mvsdf_step_trace_times', 'mvsdf_step_times',
     'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets',
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
     'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',

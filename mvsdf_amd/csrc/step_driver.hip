@@ -54,6 +54,10 @@ struct Step {
     int split_rows;                                  // -1 undecided, 0 one launch over all rows, 1 samples beside the tracer + rays after it
     int can_lazy;                                    // the rows of the rays without a hit can be left to mvsdf_step_resolve_unhit (the fused forward chain covers the SDF network)
     int last_grid[2];                                // {secant workgroups, sample-row workgroups} of the last forward's last tracer launch
+    // the sphere cut of the deferring forward (mvsdf_step_set_sphere_cut): the late rays finish on `late` beside the sampler windows
+    int cut_enable, cut_rounds, cut_on;              // cut_enable < 0: by the route's rule; cut_on: -1 undecided, 0 / 1 (streams and events exist)
+    hipStream_t late;                                // normal priority: its few workgroups are latency chains like the main stream's
+    hipEvent_t ev_cut, ev_late;
 };
 
 // descriptors of the two networks over the packs inside a forward block
@@ -137,6 +141,7 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     st->R = d.B * d.P; st->E = d.n_eik + 2 * d.n_ds; st->M = st->R + st->E; st->nl = nl;
     st->Nout = d.N[d.n_sdf - 1]; st->K0r = d.K[d.n_sdf];
     st->split_rows = -1;
+    st->cut_enable = -1; st->cut_on = -1;
     const int R = st->R, M = st->M;
     // probe descriptors (sizes only; the size functions do not dereference the pack pointers but the validity checks want non-null ones)
     MvsdfNetDesc sdf, sdfT, rnd, rndT;
@@ -151,7 +156,7 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     L.ray_dirs = take((size_t)R * 12); L.cam_loc = take((size_t)d.B * 12);
     L.points = take((size_t)R * 12); L.mask = take((size_t)R); L.dists = take((size_t)R * 4); L.counters = take(16 * 8);
     L.object_mask_out = take((size_t)R);
-    fo.trace_ws_bytes = mvsdf_trace_workspace_bytes_n(R, d.tp.n_steps);
+    fo.trace_ws_bytes = mvsdf_trace_cut_workspace_bytes(R, d.tp.n_steps);         // (the tracer's regions + the sphere cut's)
     fo.trace_ws = take(fo.trace_ws_bytes);
     fo.chain_x3 = mv_dev_switches().chain_x3;
     for (int l = 0; l < nl; ++l) {
@@ -226,6 +231,7 @@ void mvsdf_step_destroy(void* step) {
     if (st->timing) for (int i = 0; i < 9; ++i) hipEventDestroy(st->ev_t[i]);
     if (st->counts_host) { hipEventDestroy(st->ev_counts); hipHostFree(st->counts_host); }
     if (st->side) { hipStreamSynchronize(st->side); hipEventDestroy(st->ev_fork); hipEventDestroy(st->ev_join); hipStreamDestroy(st->side); }
+    if (st->late) { hipStreamSynchronize(st->late); hipEventDestroy(st->ev_cut); hipEventDestroy(st->ev_late); hipStreamDestroy(st->late); }
     delete st;
 }
 
@@ -240,6 +246,15 @@ int mvsdf_step_set_timing(void* step, int enable) {
         st->timing = 0;
     }
     st->timed = false; st->timed_bwd = false;
+    return 0;
+}
+
+int mvsdf_step_set_sphere_cut(void* step, int enable, int max_rounds) {
+    Step* st = (Step*)step;
+    if (!st) return mv_fail(-1, "mvsdf_step_set_sphere_cut: null step");
+    st->cut_enable = enable < 0 ? -1 : (enable ? 1 : 0);
+    st->cut_rounds = max_rounds > 0 ? max_rounds : 0;
+    st->cut_on = -1;                                              // decided again by the next forward (a stream that exists stays)
     return 0;
 }
 
@@ -362,6 +377,23 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
         ~SideGuard() { if (armed && side) (void)hipStreamSynchronize(side); }
     } side_guard{st->side, false};
     if (split) ST_HIP(hipEventRecord(st->ev_fork, s));             // (the folded weights are ready here)
+    // 1c. the sphere cut (deferring forward only: the eager sequence keeps its launches).  The sphere launch stops after st_iters + 1 evaluations; the rays that
+    // are not done finish on `late`, with their sampler rows, beside the sampler windows of the others; the streams join in front of the ray partition.
+    if (st->cut_on < 0) {
+        st->cut_on = st->cut_enable > 0 || (st->cut_enable < 0 && mv_trace_cut_pays(&sdf, R, d.mt));
+        if (st->cut_on && !st->late) {
+            if (hipStreamCreateWithFlags(&st->late, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); st->late = nullptr; st->cut_on = 0; }
+            else if (hipEventCreateWithFlags(&st->ev_cut, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st->ev_late, hipEventDisableTiming) != hipSuccess) {
+                (void)hipGetLastError();
+                if (st->ev_cut) { (void)hipEventDestroy(st->ev_cut); st->ev_cut = nullptr; }
+                if (st->ev_late) { (void)hipEventDestroy(st->ev_late); st->ev_late = nullptr; }
+                (void)hipStreamDestroy(st->late);
+                st->late = nullptr; st->cut_on = 0;
+            }
+        }
+    }
+    const bool cut = lazy && st->cut_on == 1;
+    SideGuard late_guard{st->late, false};
     // 2. rays + RayTracing.forward (idr.py:190-199)
     float* points = (float*)(fwd + L.points); uint8_t* mask = (uint8_t*)(fwd + L.mask); float* dists = (float*)(fwd + L.dists);
     unsigned long long* counters = (unsigned long long*)(fwd + L.counters);
@@ -373,7 +405,20 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
                                  counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream);
     };
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[0], s));
-    if (lazy) ST_TRY(stage(1));
+    auto cut_stage = [&](int which, void* strm) {
+        return mv_trace_cut_stage(which, st->cut_rounds, 1, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
+                                  counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, strm);
+    };
+    if (cut) {
+        // the resume launch goes on its stream BEFORE the first sampler window is enqueued: its few one-per-CU workgroups are placed first
+        ST_TRY(cut_stage(1, stream));
+        ST_HIP(hipEventRecord(st->ev_cut, s));
+        ST_HIP(hipStreamWaitEvent(st->late, st->ev_cut, 0));
+        late_guard.armed = true;
+        ST_TRY(cut_stage(2, (void*)st->late));
+        ST_TRY(cut_stage(3, (void*)st->late));
+        ST_HIP(hipEventRecord(st->ev_late, st->late));
+    } else if (lazy) ST_TRY(stage(1));
     else ST_TRY(mv_trace_stage1_prezeroed(&sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
                                      counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream));   // counters zeroed by the prologue
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[1], s));
@@ -386,6 +431,7 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
         else ST_HIP(hipEventRecord(st->ev_join, st->side));
     }
     ST_TRY(stage(3));                                             // the hit mask is final here (ray_tracing.py:61)
+    if (cut) { ST_HIP(hipStreamWaitEvent(s, st->ev_late, 0)); late_guard.armed = false; }   // ... with the late rays' share of it
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[2], s));
     // 3. stable partition (hit rays first) + both counts; they start travelling to the host while the rest of the forward runs
     long long* perm = (long long*)(fwd + L.perm); long long* inv = (long long*)(fwd + fo.inv); long long* true_rows = (long long*)(fwd + fo.true_rows);

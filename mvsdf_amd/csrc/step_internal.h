@@ -85,5 +85,10 @@ extern "C" int mv_trace_stage1_prezeroed(const MvsdfNetDesc* desc, const MvsdfTr
 extern "C" int mv_trace_stage_notail(int stage, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs, const uint8_t* object_mask,
                               int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
                               unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
+// the sphere cut (mvsdf_trace_cut_stage) for the step: prezeroed as in mv_trace_stage1_prezeroed; mv_trace_cut_pays: trace_route.h::mv_sphere_cut_on for this network
+extern "C" int mv_trace_cut_stage(int stage, int max_rounds, int prezeroed, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                              const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
+                              float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
+extern "C" int mv_trace_cut_pays(const MvsdfNetDesc* desc, int R, int mt);
 // {secant workgroups, sample-row workgroups} of the last secant / min-sdf launch this thread enqueued (trace.hip)
 void mv_trace_last_grid(int out[2]);

@@ -10,6 +10,13 @@
 //                    (ray_tracing.py:153,176) are per-ray no-ops for finished rays, so results are identical.
 //                    Also: sphere intersection (rend_util.py:141-162), left-out projection (ray_tracing.py:79-84),
 //                    and appending unfinished / non-hit rays to the sample work list.
+//                    The sphere cut (CutCtx; trace_route.h::mv_sphere_cut_on; mvsdf_trace_cut_stage): most workgroups are done after st_iters + 1 dependent
+//                    evaluations (no unspeculated back-off), a few need up to three more, and every launch behind this one waits for them.  With a round
+//                    limit a workgroup that still has live rays finalises the finished ones and appends the live ones' complete state to a spill list
+//                    (one atomic per workgroup, behind the loop); a RESUME launch of this same kernel -- an entry branch, the one evaluation call site --
+//                    loads eight * MT spilled rays per workgroup and runs the unchanged loop to the end, on a second stream beside the sampler windows
+//                    of the rays that were final.  A ray's state machine does not depend on its tile mates (they only decide which speculative rows
+//                    ride along, and those count only where the reference evaluates them): same results, same row counts.
 //   k_ray_samples  : ray_sampler + secant (ray_tracing.py:198-278) and minimal_sdf_points (280-308): each work item
 //                    is one ray x n_steps samples; the rows are evaluated in full tiles, then one wave per
 //                    ray does the argmin / first-sign-change logic and the (dependent) secant rounds run compacted.
@@ -105,10 +112,20 @@ struct TailCtx {
     int stop_left;                    // helpers take no new tile once at most this many workgroups still trace
     unsigned* probe;                  // optional [gridDim.x][4]: rounds, units helped, clock ticks tracing, clock ticks helping (dev)
 };
+// The cut ("the sphere cut" at k_sphere_trace): a launch with max_rounds > 0 stops after that many evaluations and appends the complete state of its rays that
+// still want one to `spill` (4 x float4 per ray, slots handed out from counters[MV_CNT_N_SPILL]); a launch with resume != 0 loads eight * MT of those states per
+// workgroup instead of starting rays, and lists its sampler rays on a list of its own (the kernel's w_list argument, counted in counters[MV_CNT_N_SAMPLER_LATE]).
+struct CutCtx {
+    float4* spill;
+    int max_rounds, resume;
+};
+// a spilled ray: {acc_s, acc_e, next_s, next_e} {curr_s, curr_e, t0, t1} {ts, te, gid, iters} {k | phase << 8 | flags << 16, -, -, -}
+#define MV_SPILL_F4 4
 // results of a workgroup's rays + work-list appends (ray_tracing.py:41-44, 73-94): the statement block k_sphere_trace runs once when its rays are done
+// (`spilled`: the ray is not done, the cut moved it to the resume launch)
 #define MV_SPHERE_FINALIZE \
     if (tid == 0 && nrows_total) atomicAdd(&counters[MV_CNT_ROWS_SPHERE], nrows_total); \
-    if (valid) { \
+    if (valid && !spilled) { \
         bool net_mask = acc_s < acc_e; \
         const bool sampler = unf_s; \
         float dist = acc_s; \
@@ -139,7 +156,7 @@ struct TailCtx {
             const bool smp = kind & MV_ITEM_SAMPLER; \
             w_zmin[gid] = zmin; \
             w_zmax[gid] = zmax; \
-            const unsigned long long idx = atomicAdd(&counters[smp ? MV_CNT_N_SAMPLER : MV_CNT_N_MINSDF], 1ull); \
+            const unsigned long long idx = atomicAdd(&counters[smp ? cnt_smp : MV_CNT_N_MINSDF], 1ull); \
             (smp ? w_list : w_list_min)[idx] = gid | (kind << 28); \
             if (!smp) n_pub = 1; \
         } \
@@ -151,7 +168,7 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
                                                             int R, int P, int training, float* __restrict__ o_points,
                                                             uint8_t* __restrict__ o_mask, float* __restrict__ o_dists,
                                                             float* __restrict__ w_zmin, float* __restrict__ w_zmax, int* __restrict__ w_list,
-                                                            int* __restrict__ w_list_min, unsigned long long* __restrict__ counters, TailCtx tail) {
+                                                            int* __restrict__ w_list_min, unsigned long long* __restrict__ counters, TailCtx tail, CutCtx cut) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int ROWS = 16 * MT, NR = 8 * MT;
     // (round 4, review item 8: the descriptor read at its uses through __builtin_amdgcn_kernarg_segment_ptr() instead of by value: SGPR spills 94 -> 88 in the
@@ -164,12 +181,22 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
     int* s_n = lds.misc;
 
     // ---- per-ray state (threads 0..NR-1 of wave 0) ----
-    const int gid = blockIdx.x * NR + tid;
-    const bool valid = (tid < NR) && (gid < R);
+    // (resume: workgroup b takes the spilled rays [NR * b, NR * b + NR) of the list a finished launch left; workgroups beyond its count leave at once)
+    const int n_spill = cut.resume ? (int)counters[MV_CNT_N_SPILL] : 0;
+    if (cut.resume && (int)blockIdx.x * NR >= n_spill) return;     // workgroup-uniform
+    const int cnt_smp = cut.resume ? (int)MV_CNT_N_SAMPLER_LATE : (int)MV_CNT_N_SAMPLER;
+    const int slot0 = blockIdx.x * NR + tid;
+    const bool valid = (tid < NR) && (slot0 < (cut.resume ? n_spill : R));
+    float4 sp2 = {0.f, 0.f, 0.f, 0.f};
+    if (cut.resume && valid) sp2 = cut.spill[MV_SPILL_F4 * (size_t)slot0 + 2];
+    const int gid = (cut.resume && valid) ? __float_as_int(sp2.z) : slot0;
     float c[3] = {0, 0, 0}, d[3] = {0, 0, 0};
     float t0 = 0.f, t1 = 0.f;
     bool isect = false, om = false;
-    if (valid) {
+    if (valid && cut.resume) {
+        const int b = gid / P;
+        for (int i = 0; i < 3; ++i) { c[i] = cam_loc[3 * b + i]; d[i] = dirs[3 * (size_t)gid + i]; }
+    } else if (valid) {
         const int b = gid / P;
         for (int i = 0; i < 3; ++i) { c[i] = cam_loc[3 * b + i]; d[i] = dirs[3 * (size_t)gid + i]; }
         isect = mv_sphere_isect(c, d, tp.r, t0, t1);
@@ -190,6 +217,15 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
     // levels before deep ones.  Results are identical; speculative rows count only if the reference would have evaluated them.
     bool hard_s = false, hard_e = false, bo_s = false, bo_e = false;
     const float lss1 = 1.0f - tp.line_search_step;
+    if (cut.resume && valid) {                                    // the state the cut launch wrote (below, behind the loop)
+        const float4 a = cut.spill[MV_SPILL_F4 * (size_t)slot0], b = cut.spill[MV_SPILL_F4 * (size_t)slot0 + 1];
+        const int f = __float_as_int(cut.spill[MV_SPILL_F4 * (size_t)slot0 + 3].x);
+        acc_s = a.x; acc_e = a.y; next_s = a.z; next_e = a.w; curr_s = b.x; curr_e = b.y; t0 = b.z; t1 = b.w; ts = sp2.x; te = sp2.y;
+        iters = __float_as_int(sp2.w); k = f & 0xff; phase = (f >> 8) & 3;
+        unf_s = (f >> 16) & 1; unf_e = (f >> 17) & 1; req_s = (f >> 18) & 1; req_e = (f >> 19) & 1; hard_s = (f >> 20) & 1; hard_e = (f >> 21) & 1;
+        bo_s = (f >> 22) & 1; bo_e = (f >> 23) & 1; isect = (f >> 24) & 1; om = (f >> 25) & 1;
+    }
+    bool spilled = false;                                         // the cut: this ray still wants an evaluation after max_rounds of them
     // helping mode (tail filling): once this workgroup's rays are done it evaluates min-sdf rows through the SAME evaluation call below (one
     // copy of the fused MLP in the kernel: a second call site costs 11 KB of code and the two copies evict each other from the instruction cache)
     bool helping = false;
@@ -244,7 +280,10 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
                     if (sr_e[dd] >= 0) { float* p = lds.pts + sr_e[dd] * 3; p[0] = c[0] + z * d[0]; p[1] = c[1] + z * d[1]; p[2] = c[2] + z * d[2]; }
                 }
             }
-            if (lane == 0) { s_n[0] = base; s_n[1] = n; }
+            // the cut: after max_rounds evaluations a workgroup with live rays ends like one without (n = 0 below: the finished rays are finalised), the live ones spill
+            const bool cut_now = cut.max_rounds > 0 && n_rounds >= (unsigned)cut.max_rounds && n > 0;
+            if (cut_now) spilled = req_s || req_e;
+            if (lane == 0) { s_n[0] = cut_now ? 0 : base; s_n[1] = n; }
         }
         int n = 0;
         if (!helping) {
@@ -421,6 +460,25 @@ __global__ __launch_bounds__(64 * NW) void k_sphere_trace(NET net, MvTraceParams
         // (mv_sdf_eval_col0 ended with a barrier; wave 0 rewrites pts/s_n only after its own reads above)
     }
 
+    // the spill, behind the loop: one atomic per workgroup, the rays take consecutive slots (the launcher keeps the cut away from tail filling: no helper gets here)
+    if (cut.resume && tid == 0) atomicMax(&counters[MV_CNT_LATE_ROUNDS], (unsigned long long)n_rounds);   // (what the late rays still needed: a figure for the records)
+    if (cut.max_rounds > 0 && w == 0) {
+        const unsigned long long ml = __ballot(spilled);
+        if (ml) {
+            int base = 0;
+            if (lane == 0) base = (int)atomicAdd(&counters[MV_CNT_N_SPILL], (unsigned long long)__popcll(ml));
+            base = __shfl(base, 0);
+            if (spilled) {
+                float4* o = cut.spill + MV_SPILL_F4 * (size_t)(base + __popcll(ml & ((1ull << lane) - 1ull)));
+                const int f = k | (phase << 8) | ((int)unf_s << 16) | ((int)unf_e << 17) | ((int)req_s << 18) | ((int)req_e << 19) | ((int)hard_s << 20) | ((int)hard_e << 21) |
+                              ((int)bo_s << 22) | ((int)bo_e << 23) | ((int)isect << 24) | ((int)om << 25);
+                o[0] = make_float4(acc_s, acc_e, next_s, next_e);
+                o[1] = make_float4(curr_s, curr_e, t0, t1);
+                o[2] = make_float4(ts, te, __int_as_float(gid), __int_as_float(iters));
+                o[3] = make_float4(__int_as_float(f), 0.f, 0.f, 0.f);
+            }
+        }
+    }
     if (tail.enable) {
         if (tid == 0 && h_units) atomicAdd(&counters[MV_CNT_TAIL_ROWS], (unsigned long long)h_units * (unsigned long long)ROWS);
         if (tail.probe && tid == 0) {
@@ -732,6 +790,7 @@ static int mv_cu_count() {                                         // compute un
 struct TraceCall {
     int engine, R, P, training;
     bool tail, no_tail;                                            // no_tail: the caller keeps the min-sdf rows out of this forward (stage flag 0x200)
+    int cut_rounds; bool resume;                                   // the sphere cut: round limit of the sphere launch (0: none); stage flag 0x400: the sphere launch resumes the spilled rays
     const MvTraceParams* tp;
     const float *cam_loc, *dirs, *intervals, *steps;
     const uint8_t* om;
@@ -756,9 +815,14 @@ static hipError_t launch_stage1(const NET& net, const TraceCall& t) {
         if (e != hipSuccess) return e;
         set1 = lds1;
     }
+    // the cut (mv_trace_cut_ws): a round limit with the spill list behind it, or the resume launch over that list (worst-case grid; its sampler rays on the late list)
+    const MvTraceCutWs cw = mv_trace_cut_ws(t.R, t.tp->n_steps);
+    if ((t.cut_rounds > 0 || t.resume) && t.tail) return hipErrorInvalidValue;      // (a helper of the tail filling is not a ray: nothing to spill)
+    const bool cutting = t.cut_rounds > 0 || t.resume;            // (only then does the workspace reach as far as the spill list: mvsdf_trace_cut_workspace_bytes)
+    const CutCtx cut = {cutting ? mv_ws_at<float4>(t.ws, cw.spill) : nullptr, t.resume ? 0 : t.cut_rounds, t.resume ? 1 : 0};
     hipLaunchKernelGGL((k_sphere_trace<MT, NTW, NW, NET>), dim3(mv_sphere_grid(t.R, MT)), dim3(64 * NW), lds1, t.stream, net, *t.tp, t.cam_loc, t.dirs, t.om, t.R, t.P,
-                       t.training, t.points, t.mask, t.dists, mv_ws_at<float>(t.ws, w.w_zmin), mv_ws_at<float>(t.ws, w.w_zmax), mv_ws_at<int>(t.ws, w.w_list),
-                       mv_ws_at<int>(t.ws, w.w_list_min), t.counters, tail);
+                       t.training, t.points, t.mask, t.dists, mv_ws_at<float>(t.ws, w.w_zmin), mv_ws_at<float>(t.ws, w.w_zmax),
+                       mv_ws_at<int>(t.ws, t.resume ? cw.list_late : w.w_list), mv_ws_at<int>(t.ws, w.w_list_min), t.counters, tail, cut);
     return hipGetLastError();
 }
 
@@ -795,6 +859,16 @@ static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
             hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.rest), wg, lds2, t.stream, net, tp, c, rest, none, 0);
             hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, c.list_rest, c.src_rest, (int)MV_CNT_N_SAMPLER_REST, 1);
         }
+    } else if (part == 32) {
+        // the late list of the sphere cut: all n samples in ONE pass (the n_first == n_steps path of the reduction), own sample values -- the two windows of part 1 may
+        // run beside this on another stream.  A few dozen rays: a second dependent window would cost more than the rows it saves.
+        const MvTraceCutWs cw = mv_trace_cut_ws(t.R, n);
+        int* list_late = mv_ws_at<int>(t.ws, cw.list_late);
+        c.sv = mv_ws_at<float>(t.ws, cw.sv_late); c.n_first = n;
+        const int blocks = mv_row_blocks(t.R, n, MT);
+        const RowSeg all = {list_late, nullptr, (int)MV_CNT_N_SAMPLER_LATE, 0, n, blocks, 0};
+        hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(blocks), wg, lds2, t.stream, net, tp, c, all, none, 0);
+        hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, list_late, (const int*)nullptr, (int)MV_CNT_N_SAMPLER_LATE, 0);
     } else if (part == 8) {
         hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.sec), wg, lds2, t.stream, net, tp, c, none, none, g.sec);
         g_last_grid[0] = g.sec; g_last_grid[1] = 0;
@@ -859,7 +933,8 @@ static hipError_t mv_launch_inst(const MvInst& r, const NET& net, const TraceCal
 #undef MV_S1
 #undef MV_S2
 
-// stages bit 0: the sphere-tracing launch; bits 1..4: the parts 1, 2, 4, 8 of launch_stage2; bit 5: part 16, the secant chains alone in the sphere tracer's engine form
+// stages bit 0: the sphere-tracing launch; bits 1..4: the parts 1, 2, 4, 8 of launch_stage2; bit 5: part 16, the secant chains alone in the sphere tracer's engine form;
+// bit 6: part 32, the late sampler list of the sphere cut (the instance of part 1)
 template <class NET>
 static hipError_t mv_trace_launch(int stages, const NET& net, TraceCall t, int mt, int mt_samples) {
     const MvTraceSwitches& sw = mv_trace_switches();
@@ -868,9 +943,10 @@ static hipError_t mv_trace_launch(int stages, const NET& net, TraceCall t, int m
     if (s1.rc) return hipErrorInvalidValue;
     t.tail = !t.no_tail && mv_tail_on(t.engine, t.training, t.steps != nullptr, t.R, s1.mt, mv_cu_count(), sw);
     hipError_t e = (stages & 1) ? mv_launch_inst(s1, net, t, 0) : hipSuccess;
-    for (int part = 1; part <= 16 && e == hipSuccess; part <<= 1)
+    for (int part = 1; part <= 32 && e == hipSuccess; part <<= 1)
         if ((stages >> 1) & part)
-            e = mv_launch_inst(part == 16 ? mv_route_secant(t.engine, maxnt, mt_samples, t.R, sw) : mv_route_samples(t.engine, maxnt, mt_samples, t.R, part, sw), net, t, part);
+            e = mv_launch_inst(part == 16 ? mv_route_secant(t.engine, maxnt, mt_samples, t.R, sw) : mv_route_samples(t.engine, maxnt, mt_samples, t.R, part == 32 ? 1 : part, sw),
+                               net, t, part);
     return e;
 }
 
@@ -1108,12 +1184,13 @@ __global__ __launch_bounds__(1024) void k_gen_sort_list(int* __restrict__ list, 
 extern "C" {
 
 size_t mvsdf_trace_workspace_bytes_n(int R, int n_steps) { return mv_trace_ws(R, n_steps).total; }
+size_t mvsdf_trace_cut_workspace_bytes(int R, int n_steps) { return mv_trace_cut_ws(R, n_steps).total; }   // the same regions + the sphere cut's behind them
 size_t mvsdf_trace_workspace_bytes(int R) { return mvsdf_trace_workspace_bytes_n(R, 128); }
 
 static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
-                      size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+                      size_t workspace_bytes, int mt, int mt_samples, void* stream, int cut_rounds = 0) {
     const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, false);
     if (ec.rc) return mv_fail(ec.rc, ec.why);
     return mv_with_trace_net(desc, ec.engine, [&](const auto& net) {
@@ -1125,12 +1202,14 @@ static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTracePara
             return mv_fail(-1, "mvsdf_trace: tracer parameters out of range");
         const int R = B * P;
         if (workspace_bytes < mvsdf_trace_workspace_bytes_n(R, tp->n_steps)) return mv_fail(-1, "mvsdf_trace: workspace too small");
+        if ((cut_rounds > 0 || (stages & (0x400 | 64))) && workspace_bytes < mvsdf_trace_cut_workspace_bytes(R, tp->n_steps))
+            return mv_fail(-1, "mvsdf_trace_cut_stage: workspace too small (mvsdf_trace_cut_workspace_bytes)");
         hipStream_t s = (hipStream_t)stream;
         hipError_t e = hipSuccess;
-        if ((stages & 1) && !(stages & 0x100)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them
+        if ((stages & 1) && !(stages & 0x500)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them; 0x400: the resume launch of the sphere cut goes on counting
         if (e != hipSuccess) return mv_check(e, "mvsdf_trace: memset");
         // 0x200: no tail filling in this call -- the caller keeps the min-sdf rows out of its forward (k_sphere_trace still writes their work list and ranges)
-        const TraceCall t = {ec.engine, R, P, training, false, (stages & 0x200) != 0, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
+        const TraceCall t = {ec.engine, R, P, training, false, (stages & 0x200) != 0, cut_rounds, (stages & 0x400) != 0, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
                              points, dists, mask, workspace, counters, s};
         return mv_check(mv_trace_launch(stages, net, t, mt, mt_samples), "mvsdf_trace");
     });
@@ -1174,6 +1253,34 @@ int mv_trace_stage_notail(int stage, const MvsdfNetDesc* desc, const MvsdfTraceP
     if (stage < 1 || stage > 7 || !bits[stage]) return mv_fail(-1, "mv_trace_stage_notail: stage must be 1, 5, 6 or 7");
     return trace_impl(bits[stage] | 0x200, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
                       workspace, workspace_bytes, mt, mt_samples, stream);
+}
+
+// The sphere cut, launch by launch (no tail filling in any of them).  stage 1: the sphere launch with a limit of max_rounds evaluations per workgroup (<= 0: st_iters + 1,
+// what a ray without an unspeculated back-off needs) -- rays that still want one go to the spill list; 2: the resume launch over that list (its sampler rays on the late
+// list); 3: the late list's sample rows in one pass + their reduction.  Stages 2 and 3 read nothing the launches of mvsdf_trace_stage 3 write and may run beside them on
+// another stream; mvsdf_trace_stage 4 / 6 / 7 behind both see ONE secant list.  prezeroed: the caller's previous launch zeroed the counters (stage 1).
+int mv_trace_cut_stage(int stage, int max_rounds, int prezeroed, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask, float* dists,
+                       unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+    if (stage < 1 || stage > 3 || !tp) return mv_fail(-1, "mvsdf_trace_cut_stage: stage must be 1..3");
+    const int bits[4] = {0, 1 | (prezeroed ? 0x100 : 0), 1 | 0x400, 64};
+    return trace_impl(bits[stage] | 0x200, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
+                      workspace, workspace_bytes, mt, mt_samples, stream, stage == 1 ? (max_rounds > 0 ? max_rounds : tp->st_iters + 1) : 0);
+}
+int mvsdf_trace_cut_stage(int stage, int max_rounds, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                          const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
+                          float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+    return mv_trace_cut_stage(stage, max_rounds, 0, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
+                              workspace, workspace_bytes, mt, mt_samples, stream);
+}
+// the rule of trace_route.h::mv_sphere_cut_on for a network and ray count on the current device (the step driver asks once per step object)
+int mv_trace_cut_pays(const MvsdfNetDesc* desc, int R, int mt) {
+    const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, false);
+    if (ec.rc || !desc) return 0;
+    int maxnt = 0;
+    for (int l = 0; l + 1 < desc->n_layers && l < MVSDF_MAX_LAYERS; ++l) { const int nt = (desc->N[l] + 15) / 16; maxnt = nt > maxnt ? nt : maxnt; }   // (capi_util.h::mv_hidden_nt)
+    const MvInst s1 = mv_route_sphere(ec.engine, maxnt, mt);
+    return (s1.rc == 0 && mv_sphere_cut_on(ec.engine, R, s1.mt, mv_cu_count())) ? 1 : 0;
 }
 
 /* ---- generic tracer for an opaque SDF callable (see the kernel comments above) ---- */

@@ -154,4 +154,29 @@ inline MvTraceWs mv_trace_ws(int R, int n_steps) {
     const size_t r = 4 * (size_t)(R > 0 ? R : 0), n = n_steps > 0 ? n_steps : 0;
     return {0, r, 2 * r, 6 * r, 7 * r, 8 * r, 9 * r, (9 + n) * r, (10 + n) * r, (11 + n) * r, (11 + 2 * n) * r + 256};
 }
+// ---- the sphere cut ----
+// k_sphere_trace's rounds wait for each other, and the whole rest of the tracer waits for its slowest workgroup: at c2 most workgroups are done after st_iters + 1
+// evaluations (no unspeculated back-off), a few need three more.  The cut stops the launch after that many; the rays that still want an evaluation go to a spill list
+// and finish in a resume launch of the same kernel on a second stream, regrouped eight * mt per workgroup, beside the sampler windows of the rays that are final.
+// On where it was measured to pay (profiles/sphere_cut_ab.txt): the three-weight-term engine, ONE row tile per sphere workgroup, at most one workgroup per compute unit and
+// more than one per two -- 4 * cus < R <= 8 * cus, 1025 .. 2048 rays on an unpartitioned MI355X (c2: 1.329 -> 1.301 ms).  Below that the sampler windows it hides the late
+// branch under shrink towards one evaluation each, while the branch keeps its fixed cost (two event hand-offs, a dependent row evaluation, a reduction: ~100 us), and a
+// step of a few hundred rays is bound by its launches, of which the cut adds three.  With more row tiles per workgroup a round costs more and 32 rays seldom finish together
+// (c3, 4 tiles x 256 workgroups: 3.075 -> 3.092 ms with the cut); with more workgroups than compute units the grid runs in waves, a finished workgroup's CU goes to the next
+// one and there is no idle tail to move; the bf16-weight engines' rounds take half the time and their tail with them (c5share bf16x2 forced on: 1.388 -> 1.416 ms).
+inline bool mv_sphere_cut_on(int engine, int R, int mt1, int cus) {
+    const int grid = mv_sphere_grid(R, mt1);
+    return engine == MV_ENG_X3 && mt1 == 1 && grid <= cus && 2 * grid > cus;
+}
+// its regions, BEHIND mv_trace_ws(R, n_steps) (mvsdf_trace_cut_workspace_bytes covers both; mvsdf_trace_workspace_bytes_n stays what mvsdf_trace needs): the spill list (16 words per ray), the late sampler list and its sample values
+struct MvTraceCutWs {
+    size_t spill;                      // [R][16] state of the rays the cut launch left unfinished (trace.hip: CutCtx)
+    size_t list_late;                  // [R] sampler rays of the resume launch (the first list is being read beside it)
+    size_t sv_late;                    // [R][n_steps] their sample values
+    size_t total;
+};
+inline MvTraceCutWs mv_trace_cut_ws(int R, int n_steps) {
+    const size_t r = 4 * (size_t)(R > 0 ? R : 0), n = n_steps > 0 ? n_steps : 0, b = (mv_trace_ws(R, n_steps).total + 255) & ~(size_t)255;
+    return {b, b + 16 * r, b + 17 * r, b + (17 + n) * r + 256};
+}
 template <class T> inline T* mv_ws_at(void* ws, size_t offset) { return (T*)((char*)ws + offset); }

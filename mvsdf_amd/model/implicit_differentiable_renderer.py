@@ -360,6 +360,11 @@ class IDRNetwork(nn.Module):
         # first reader of `points` / `sdf_output` (mvsdf_step_resolve_unhit: nothing in a training step reads them; no expiry, same values).  True, or MVSDF_EAGER_UNHIT=1:
         # everything inside the forward, the launch sequence up to round 6.
         self.eager_unhit_rows = os.environ.get('MVSDF_EAGER_UNHIT', '0') not in ('', '0')
+        # The deferring forward cuts the sphere launch after st_iters + 1 rounds: the few rays that need more finish on a second stream beside the sampler windows of
+        # the others (mvsdf_trace_cut_stage; same values).  True: where the tracer's route says it pays; False, or MVSDF_SPHERE_CUT=0: the launch sequence without it;
+        # 2: always.  sphere_cut_rounds > 0: another round limit (development: a small one makes small batches spill).
+        self.sphere_cut = {'0': False, '': False, '2': 2}.get(os.environ.get('MVSDF_SPHERE_CUT', '1'), True)
+        self.sphere_cut_rounds = 0
         self._steps = {}                                         # NativeStep per batch shape / phase configuration
         self._ones = None                                        # all-ones object mask handed to the tracer when conf.use_mask is off
 
@@ -656,6 +661,7 @@ class IDRNetwork(nn.Module):
         rec.use_geo = not bool(train_progress < conf.phase[0] or conf.disable_rgb_grad)                       # idr.py:331-334
         rec.inputs_keep = keep                                   # the inputs stay alive as long as the step's record does
         rec.eager_unhit = bool(self.eager_unhit_rows) or not st.can_defer_unhit
+        st.set_sphere_cut(self.sphere_cut, self.sphere_cut_rounds)
         NS.enqueue_forward(rec)                                  # everything of this forward is on the stream now; nothing waited for
         if stage_slot is not None:                               # the pinned draws may be rewritten once this forward's first kernel has read them
             stage_slot[2] = (st, rec.seq)

@@ -74,6 +74,7 @@ def _bind():
         L.mvsdf_step_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.mvsdf_step_resolve_unhit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mvsdf_step_can_defer_unhit.argtypes = [C.c_void_p]
+        L.mvsdf_step_set_sphere_cut.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mvsdf_step_last_tracer_grid.argtypes = [C.c_void_p, C.c_void_p]
         L.mvsdf_step_wait_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.mvsdf_step_seq.argtypes = [C.c_void_p]
@@ -171,6 +172,7 @@ class NativeStep:
         self.can_defer = bool(L.mvsdf_step_can_defer(h))          # every launch of the backward has a device-count form (the deferred step)
         self.counts_off = int(L.mvsdf_step_counts_offset(h))      # int64 counts[4] inside a forward block
         self.can_defer_unhit = bool(L.mvsdf_step_can_defer_unhit(h))   # the rows of the rays without a hit can wait until `points` / `sdf_output` are read
+        self._cut = (1, 0)                                        # (sphere_cut, max_rounds) as last handed to mvsdf_step_set_sphere_cut (its default)
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -230,6 +232,14 @@ class NativeStep:
         check(lib().mvsdf_step_forward(self._h, C.byref(prm), C.byref(self.inputs), d_mask, e_mask, 1 if eager_unhit else 0, fwd.data_ptr(),
                                        _stream(self.device)), 'mvsdf_step_forward')
         return fwd
+
+    def set_sphere_cut(self, mode, max_rounds=0):
+        """mvsdf_step_set_sphere_cut for the forwards that follow: mode 0 / False: the launch sequence without the cut, 1 / True: the cut where the tracer's route
+        says it pays, 2: always; max_rounds > 0: another round limit than st_iters + 1 (tests: small shapes spill only under a small limit)."""
+        key = (int(mode), int(max_rounds))
+        if key != self._cut:
+            check(lib().mvsdf_step_set_sphere_cut(self._h, {0: 0, 1: -1}.get(key[0], 1), key[1]), 'mvsdf_step_set_sphere_cut')
+            self._cut = key
 
     def resolve_unhit(self, fwd):
         """mvsdf_step_resolve_unhit: min-sdf rows, evaluation rows and sdf_output of the rays without a hit, from the forward block alone (once per block)."""
