@@ -694,6 +694,29 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
                       size_t ws_bytes, float* masked, float* fused, int32_t* counts, void* stream);
 int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, int64_t npairs, void* ws, size_t ws_bytes, double* points,
                       uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
+/* Normals of fused points (fusion.py: depth_normals): one lane per point reads fused fp32 [V][H][W] and view / pixel int32 [n] (device) and writes
+ * normals fp64 [n][3].  mats: HOST fp64 [V][19], Pinv of the view (row-major 4x4) then its camera centre; it must stay alive until the caller has
+ * read the header.  Leaves int64 {0, error bits} at the start of the workspace, no host wait.  Error bits: 1 a non-finite matrix entry, a NaN or
+ * negative jump; 8 shapes (V < 1, H or W < 2, H*W > INT32_MAX, n < 1); 16 a view / pixel index outside the maps (found on the device; that point's
+ * normal is 0). */
+size_t mvsdf_fusion_normals_workspace_bytes(int64_t V);
+int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, const int32_t* view, const int32_t* pixel, int64_t n, const double* mats,
+                         double jump, void* ws, size_t ws_bytes, double* normals, void* stream);
+
+/* ---- Poisson surface reconstruction (poisson.hip; Python: mvsdf_amd/poisson.py, which states the definition) ----
+ * mvsdf_poisson_reconstruct validates its scalar arguments on the host, then (no host wait) runs the stages whose bits are set in `stages` (1 the
+ * splat and the right-hand side, 2 the multigrid solve, 4 the isovalue; a later stage needs the earlier ones to have run on the same workspace; 7 =
+ * everything) and leaves int64 {points used, error bits, T, residual0, residual} (the last three: fp64 bit patterns) at the start of the workspace.
+ * Error bits: 1 a non-finite coordinate, normal (found on the device), origin or voxel; 2 depth outside [2, 10], cycles < 0, sweeps < 1 or voxel <= 0;
+ * 4 n < 1 or n > INT32_MAX.  points / normals fp64 [n][3] on the device; origin: HOST fp64 [3]; N = 2^depth + 1; chi and density fp64 [N][N][N],
+ * values fp64 [n] (the first `points used` rows are the c_i, the rest 0).  workspace bytes: about 43 per lattice point + 9 per point; 0 = refused.
+ * mvsdf_poisson_valid: valid uint8 [N][N][N] = density > min_density dilated `dilate` times over the 6-neighbourhood (tmp: uint8 [N][N][N], needed
+ * when dilate > 0).  mvsdf_poisson_volume: out[i] = (float)(chi[i] - iso) for count values.  Neither waits. */
+size_t mvsdf_poisson_workspace_bytes(int64_t n, int32_t depth);
+int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64_t n, const double* origin, double voxel, int32_t depth, int32_t cycles,
+                              int32_t sweeps, int32_t stages, void* ws, size_t ws_bytes, double* chi, double* density, double* values, void* stream);
+int mvsdf_poisson_valid(const double* density, int32_t depth, double min_density, int32_t dilate, uint8_t* tmp, uint8_t* valid, void* stream);
+int mvsdf_poisson_volume(const double* chi, int64_t count, double iso, float* out, void* stream);
 
 /* ---- TSDF fusion (tsdf.hip; Python: mvsdf_amd/tsdf.py, which states the definition) ----
  * mvsdf_tsdf_integrate validates every argument on the host, then (no host wait) writes tsdf fp32, weight int32 and valid uint8, each

@@ -100,6 +100,14 @@ def lib():
         L.mvsdf_fusion_workspace_bytes.argtypes = [i64] * 4
         L.mvsdf_fusion_fuse.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, f64, f64, vp, sz, vp, vp, vp, vp]
         L.mvsdf_fusion_emit.argtypes = [vp, i64, i64, i64, i64, vp, sz, vp, vp, vp, vp, i64, vp]
+        L.mvsdf_fusion_normals_workspace_bytes.restype = sz
+        L.mvsdf_fusion_normals_workspace_bytes.argtypes = [i64]
+        L.mvsdf_fusion_normals.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, f64, vp, sz, vp, vp]
+        L.mvsdf_poisson_workspace_bytes.restype = sz
+        L.mvsdf_poisson_workspace_bytes.argtypes = [i64, i32]
+        L.mvsdf_poisson_reconstruct.argtypes = [vp, vp, i64, vp, f64, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_poisson_valid.argtypes = [vp, i32, f64, i32, vp, vp, vp]
+        L.mvsdf_poisson_volume.argtypes = [vp, i64, f64, vp, vp]
         L.mvsdf_tsdf_workspace_bytes.restype = sz
         L.mvsdf_tsdf_workspace_bytes.argtypes = [i64] * 4
         L.mvsdf_tsdf_integrate.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, f64, vp, f64, f64, i32, vp, sz, vp, vp, vp, vp]
@@ -188,7 +196,8 @@ EXPORTS = [
     'mvsdf_chamfer_key', 'mvsdf_chamfer_sample_workspace_bytes', 'mvsdf_chamfer_sample_count', 'mvsdf_chamfer_sample_emit',
     'mvsdf_chamfer_downsample_workspace_bytes', 'mvsdf_chamfer_downsample', 'mvsdf_chamfer_mask_workspace_bytes', 'mvsdf_chamfer_mask',
     'mvsdf_chamfer_nearest_workspace_bytes', 'mvsdf_chamfer_nearest',
-    'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit',
+    'mvsdf_fusion_workspace_bytes', 'mvsdf_fusion_fuse', 'mvsdf_fusion_emit', 'mvsdf_fusion_normals_workspace_bytes', 'mvsdf_fusion_normals',
+    'mvsdf_poisson_workspace_bytes', 'mvsdf_poisson_reconstruct', 'mvsdf_poisson_valid', 'mvsdf_poisson_volume',
     'mvsdf_tsdf_workspace_bytes', 'mvsdf_tsdf_integrate', 'mvsdf_mcm_workspace_bytes', 'mvsdf_mcm_count', 'mvsdf_mcm_emit',
     'mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes', 'mvsdf_cloud_knn', 'mvsdf_cloud_components', 'mvsdf_cloud_clean',
     'mvsdf_cloud_compact',

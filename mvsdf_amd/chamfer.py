@@ -246,3 +246,15 @@ def load_points(path):
     if vert is None or not all(k in vert.dtype.names for k in 'xyz'):
         raise ValueError('load_points: %s has no vertex x / y / z' % path)
     return np.stack([vert[k].astype(np.float64) for k in 'xyz'], 1)
+
+
+def load_oriented_points(path):
+    """load_points and the file's normals -> (points fp64 numpy [N, 3], normals fp64 numpy [N, 3] or None when the vertices carry no nx / ny / nz)"""
+    arrays = _ply_elements(path, 'load_oriented_points')
+    vert = arrays.get('vertex')
+    if vert is None or not all(k in vert.dtype.names for k in 'xyz'):
+        raise ValueError('load_oriented_points: %s has no vertex x / y / z' % path)
+    pts = np.stack([vert[k].astype(np.float64) for k in 'xyz'], 1)
+    if not all(k in vert.dtype.names for k in ('nx', 'ny', 'nz')):
+        return pts, None
+    return pts, np.stack([vert[k].astype(np.float64) for k in ('nx', 'ny', 'nz')], 1)

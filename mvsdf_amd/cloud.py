@@ -197,7 +197,7 @@ def clean_points(points, colors=None, nb_neighbors=20, knn_ratio=3.0, eps_ratio=
 
 
 def clean_fused(fused, **kw):
-    """fusion.Fused -> a new Fused: points / colors / view / pixel compacted, fused_depths set to 0 at every removed (view, pixel), counts and
+    """fusion.Fused -> a new Fused: points / colors / view / pixel (/ normals) compacted, fused_depths set to 0 at every removed (view, pixel), counts and
     masked_depths as they were; its attribute `cleaned` is the Cleaned of the whole cloud.  kw: clean_points' keywords."""
     from .fusion import Fused
     what = 'clean_fused'
@@ -211,6 +211,7 @@ def clean_fused(fused, **kw):
     gone = c.keep == 0
     hw = depths.shape[1] * depths.shape[2]
     depths.view(-1)[fused.view[gone].long() * hw + fused.pixel[gone].long()] = 0
-    out = Fused(c.points, c.colors, view, pixel, fused.masked_depths, depths, fused.counts)
+    out = Fused(c.points, c.colors, view, pixel, fused.masked_depths, depths, fused.counts,
+                None if fused.normals is None else fused.normals[c.keep != 0])      # the keep mask is in input order, as the compaction
     out.cleaned = c
     return out

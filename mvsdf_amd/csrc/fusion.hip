@@ -9,6 +9,8 @@
 //   fp32 fused depth, the fp64 fused depth (the emit pass back-projects at it) and a keep flag.
 // * an int64 exclusive scan of the keep flags over all views (geom_prims.h: mv_scan_blocks, i.e. k_scan_block_sum and k_scan_top); the emit pass ranks
 //   its own chunk (mv_chunk_rank), so no per-pixel offset is stored.  Points come out in (view, y, x) order.  No float atomics anywhere.
+// * k_fu_normals (fusion.py: depth_normals): one lane per fused point; the tangents are differences of back-projected neighbour texels of the fused
+//   depth map, never taken across a hole or a depth edge, their cross product is oriented towards the camera.
 //
 // Every argument is validated on the host before anything is launched: an error leaves {0, error bits} in the header and the device untouched.
 #include "geom_prims.h"
@@ -22,6 +24,7 @@ enum {
     FU_ERR_PAIR = 2,        // a pair index outside [0, V)
     FU_ERR_VIEW = 4,        // view < 1
     FU_ERR_SHAPE = 8,       // V < 1, H or W < 2, a pair list that disagrees with V or is longer than view, sizes beyond the limits
+    FU_ERR_INDEX = 16,      // k_fu_normals: a point's view or pixel index lies outside the maps
 };
 
 struct FuLayout {
@@ -137,7 +140,103 @@ __global__ __launch_bounds__(MV_THREADS) void k_fu_emit(const unsigned char* __r
     }
 }
 
+// ---- normals of the fused points (fusion.py: depth_normals) ----
+#define FU_NM_ROW 19                                  // doubles per view: Pinv (16), the camera centre (3)
+
+// Q(x, y): rows 0..2 of Pinv applied to (X d, Y d, d, 1)
+__device__ __forceinline__ void fu_backproject(const double* __restrict__ T, int x, int y, double d, double* q) {
+    const double q0 = ((double)x + 0.5) * d, q1 = ((double)y + 0.5) * d;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = mv_row4(T + 4 * c, q0, q1, d, 1.0);
+}
+
+// the tangent along one image axis from the neighbours at -step / +step texels: central, else forward, else backward; false when neither is usable
+__device__ __forceinline__ bool fu_tangent(const float* __restrict__ map, const double* __restrict__ T, int W, int x, int y, int dx, int dy, bool in_lo, bool in_hi,
+                                           double d, const double* qc, double jump, double* t) {
+    double ql[3], qh[3];
+    bool lo = false, hi = false;
+    if (in_lo) {
+        const double dn = (double)map[(long long)(y - dy) * W + (x - dx)];
+        lo = dn > 0.0 && fabs(dn - d) <= jump * d;
+        if (lo) fu_backproject(T, x - dx, y - dy, dn, ql);
+    }
+    if (in_hi) {
+        const double dn = (double)map[(long long)(y + dy) * W + (x + dx)];
+        hi = dn > 0.0 && fabs(dn - d) <= jump * d;
+        if (hi) fu_backproject(T, x + dx, y + dy, dn, qh);
+    }
+    if (!lo && !hi) return false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = (hi ? qh[c] : qc[c]) - (lo ? ql[c] : qc[c]);
+    return true;
+}
+
+// one lane per point; an index outside the maps sets FU_ERR_INDEX and gives a zero normal
+__global__ __launch_bounds__(FU_THREADS) void k_fu_normals(const float* __restrict__ fused, int V, int H, int W, const int* __restrict__ view,
+                                                            const int* __restrict__ pixel, long long n, const double* __restrict__ mats, double jump,
+                                                            double* __restrict__ normals, unsigned long long* __restrict__ word) {
+    const long long i = (long long)blockIdx.x * FU_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int r = view[i], p = pixel[i];
+    double o[3] = {0.0, 0.0, 0.0};
+    if (r < 0 || r >= V || p < 0 || p >= H * W) {
+        atomicOr(word, (unsigned long long)FU_ERR_INDEX);
+    } else {
+        const int y = p / W, x = p - y * W;
+        const float* __restrict__ map = fused + (long long)r * H * W;
+        const double* __restrict__ T = mats + (long long)r * FU_NM_ROW;
+        const double d = (double)map[p];
+        double qc[3], tx[3], ty[3];
+        fu_backproject(T, x, y, d, qc);
+        if (fu_tangent(map, T, W, x, y, 1, 0, x > 0, x < W - 1, d, qc, jump, tx) && fu_tangent(map, T, W, x, y, 0, 1, y > 0, y < H - 1, d, qc, jump, ty)) {
+            const double m0 = tx[1] * ty[2] - tx[2] * ty[1], m1 = tx[2] * ty[0] - tx[0] * ty[2], m2 = tx[0] * ty[1] - tx[1] * ty[0];
+            const double len = sqrt((m0 * m0 + m1 * m1) + m2 * m2);
+            if (len > 0.0 && len < (double)INFINITY) {
+                const double n0 = m0 / len, n1 = m1 / len, n2 = m2 / len;
+                const double c0 = T[16] - qc[0], c1 = T[17] - qc[1], c2 = T[18] - qc[2];
+                const bool flip = ((n0 * c0 + n1 * c1) + n2 * c2) < 0.0;
+                o[0] = flip ? -n0 : n0;
+                o[1] = flip ? -n1 : n1;
+                o[2] = flip ? -n2 : n2;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) normals[i * 3 + c] = o[c];
+}
+
 extern "C" {
+
+size_t mvsdf_fusion_normals_workspace_bytes(int64_t V) {
+    if (V < 1 || V > INT_MAX) return 0;
+    return FU_HDR + mv_align256((size_t)V * FU_NM_ROW * 8);
+}
+
+// mats: host, [V][19] = Pinv_v row-major, then the camera centre.  Leaves int64 {0, error bits} at the start of the workspace; no host wait.
+int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, const int32_t* view, const int32_t* pixel, int64_t n, const double* mats,
+                         double jump, void* ws, size_t ws_bytes, double* normals, void* stream) {
+    const char* what = "mvsdf_fusion_normals";
+    if (!fused || !view || !pixel || !mats || !ws || !normals || ws_bytes < FU_HDR) return mv_fail(-1, "mvsdf_fusion_normals: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    long long err = 0;
+    if (V < 1 || H < 2 || W < 2 || V > INT_MAX || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || n < 1 || n > FU_MAX_PIXELS) err |= FU_ERR_SHAPE;
+    if (!(err & FU_ERR_SHAPE))
+        for (long long k = 0; k < V * FU_NM_ROW; ++k)
+            if (!isfinite(mats[k])) err |= FU_ERR_FINITE;
+    if (isnan(jump) || jump < 0.0) err |= FU_ERR_FINITE;
+    if (err) {
+        const long long hdr[2] = {0, err};
+        return mv_write_header(ws, hdr, 2, s, what);
+    }
+    if (ws_bytes < mvsdf_fusion_normals_workspace_bytes(V)) return mv_fail(-1, "mvsdf_fusion_normals: workspace too small (mvsdf_fusion_normals_workspace_bytes)");
+    char* w = (char*)ws;
+    int rc;
+    if ((rc = mv_check(hipMemsetAsync(ws, 0, FU_HDR, s), what))) return rc;
+    if ((rc = mv_check(hipMemcpyAsync(w + FU_HDR, mats, (size_t)V * FU_NM_ROW * 8, hipMemcpyHostToDevice, s), what))) return rc;
+    hipLaunchKernelGGL(k_fu_normals, dim3(mv_grid(n, FU_THREADS)), dim3(FU_THREADS), 0, s, fused, (int)V, (int)H, (int)W, view, pixel, (long long)n,
+                       (const double*)(w + FU_HDR), jump, normals, (unsigned long long*)(w + 8));
+    return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps mats until it has read the header
+}
 
 size_t mvsdf_fusion_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t npairs) {
     FuLayout L;

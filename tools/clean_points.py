@@ -2,7 +2,7 @@
 
     python tools/clean_points.py IN.ply OUT.ply [--nb_neighbors 20] [--knn_ratio 3] [--eps_ratio 3] [--cluster_frac 1]
 
-IN.ply: a binary or ASCII PLY point cloud (datasets/prepare.read_points); red / green / blue of a binary file are kept.  Prints `N -> n_kept`, the
+IN.ply: a binary or ASCII PLY point cloud (datasets/prepare.read_points); red / green / blue and nx / ny / nz of a binary file are kept.  Prints `N -> n_kept`, the
 median neighbour distance, both radii and the cluster count.
 """
 import argparse
@@ -48,14 +48,24 @@ def read_colors(path):
     return np.ascontiguousarray(np.stack([vert[k] for k in ('red', 'green', 'blue')], 1).astype(np.uint8))
 
 
+def read_normals(path):
+    """fp64 [N,3] of a binary PLY with nx / ny / nz, else None"""
+    with open(path, 'rb') as fh:
+        if b'format ascii' in fh.read(4096).split(b'end_header')[0]:
+            return None
+    from mvsdf_amd.chamfer import load_oriented_points
+    return load_oriented_points(path)[1]
+
+
 def main(argv=None):
     a = parse_args(argv)
     from mvsdf_amd import cloud, fusion
     from mvsdf_amd.datasets import prepare
     pts = prepare.read_points(a.input)
+    normals = read_normals(a.input)
     c = cloud.clean_points(pts, read_colors(a.input), nb_neighbors=a.nb_neighbors, knn_ratio=a.knn_ratio, eps_ratio=a.eps_ratio,
                            cluster_frac=a.cluster_frac)
-    fusion.save_points(a.output, c.points, c.colors)
+    fusion.save_points(a.output, c.points, c.colors, normals=None if normals is None else normals[c.keep.cpu().numpy() != 0])
     print('%d -> %d points' % (len(pts), len(c)))
     print('median neighbour distance %.9g, sparse above %.9g, cluster radius %.9g' % (c.median, c.threshold, c.eps))
     print('%d points passed, %d clusters, the largest of %d points' % (c.n_passed, c.n_clusters, c.largest))
