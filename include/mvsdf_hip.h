@@ -142,7 +142,8 @@ int mvsdf_pack_bf16w_net(int n_layers, const float* const* w, const int* N, cons
  * every other activation); wp16[l]: mvsdf_packed_bf16_bytes(N, K, 0) bytes.  idr.py:77-94 on bf16-rounded weights. */
 int mvsdf_pack_bf16s_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wp16, void* stream);
 /* trace_dtype = 5: the folded fp32 weights as three bf16 terms (t0 = bf16(w), t1 = bf16(w - t0), t2 = bf16(w - t0 - t1)), layout of mvsdf_pack_bf16s_net
- * with a k-block's three term fragments behind each other; wp16[l]: 3 * mvsdf_packed_bf16_bytes(N, K, 0) bytes.  idr.py:77-94 on the fp32 weights. */
+ * with a k-block's three term fragments behind each other; wp16[l]: 3 * mvsdf_packed_bf16_bytes(N, K, 0) bytes.  idr.py:77-94 on the fp32 weights.
+ * The weights must be finite with |w| <= 0x7f7f7fff as a bit pattern (the largest float whose bf16 rounding stays finite); |w| < 2^-40 packs as +0. */
 int mvsdf_pack_bf16x3_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wp16, void* stream);
 /* the same three-term pack of W_l^T (N, K are W_l's dims): 3 * mvsdf_packed_bf16_bytes(K, N, 0) bytes per layer -- MvsdfNetDesc.wx3 of the transposed descriptor */
 int mvsdf_pack_bf16x3t_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wx3t, void* stream);
@@ -507,6 +508,12 @@ int mvsdf_step_can_defer(void* step);
  * render_ctx (mvsdf_render_forward's context for R rows: the input [R][K_0], then the post-ReLU activations [R][K_l] of layers 1.., then rgb),
  * rgb_sorted [R][3]} */
 int mvsdf_step_saved_offsets(void* step, size_t out[6]);
+/* byte offsets inside `fwd` of what the prologue of the forward prepared for layer `layer` (SDF layers first, then the rendering net's), for inspection
+ * (tests compare the block's packs with the stand-alone pack entry points): out[7] = {w [N][K] folded weights, wp (the pack of W), wpT (of W^T),
+ * wp16 (the tracing MLP's pack under trace_dtype 2..5: fp32 pack of the bf16-rounded weights / bf16 pack / three-term bf16 pack), wx3, wx3T (three-term
+ * bf16 packs of W and W^T for the differentiable chains; wx3 == wp16 under trace_dtype 5), bias copy [N] (SDF layers; written by a forward in mode
+ * MVSDF_STEP_UNHIT_DEFER only)}; (size_t)-1 where the block holds none for this layer and trace_dtype. */
+int mvsdf_step_pack_offsets(void* step, int layer, size_t out[7]);
 /* backward of mvsdf_step_forward: upstream gradients of diff_surf_pts [N][3], rgb_values [R][3], grad_theta, eikonal_output,
  * surf_indicator_output (any may be NULL = zero) -> gradient of every raw parameter.  N, n_true: the counts mvsdf_step_wait_counts returned;
  * N < 0: the deferred step -- both counts are read on the device from `fwd`, the upstream tensors hold their valid rows first (sized for N = R),

@@ -186,7 +186,7 @@ EXPORTS = [
     'mvsdf_partition_rays', 'mvsdf_step_outputs', 'mvsdf_step_backward_inputs', 'mvsdf_step_backward_fbar', 'mvsdf_dsurf_select', 'mvsdf_dsurf_points',
     'mvsdf_render_ctx_floats', 'mvsdf_render_bwd_ws_floats', 'mvsdf_render_forward', 'mvsdf_render_backward',
     'mvsdf_step_create', 'mvsdf_step_destroy', 'mvsdf_step_forward', 'mvsdf_step_resolve_unhit', 'mvsdf_step_can_defer_unhit', 'mvsdf_step_set_sphere_cut', 'mvsdf_step_last_tracer_grid', 'mvsdf_step_wait_counts', 'mvsdf_step_backward', 'mvsdf_step_set_timing', 'mvsdf_step_trace_times', 'mvsdf_step_times',
-    'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets',
+    'mvsdf_step_seq', 'mvsdf_step_counts_offset', 'mvsdf_step_wait_counts_seq', 'mvsdf_step_done_seq', 'mvsdf_step_can_defer', 'mvsdf_step_saved_offsets', 'mvsdf_step_pack_offsets',
     'mvsdf_loss_layout', 'mvsdf_loss_forward', 'mvsdf_loss_backward',
     'mvsdf_mc_workspace_bytes', 'mvsdf_mc_count', 'mvsdf_mc_emit', 'mvsdf_mesh_cc_workspace_bytes', 'mvsdf_mesh_components', 'mvsdf_mesh_select',
     'mvsdf_smc_workspace_bytes', 'mvsdf_smc_emit_workspace_bytes', 'mvsdf_smc_coarse_points', 'mvsdf_smc_seed', 'mvsdf_smc_brick_points',

@@ -569,6 +569,19 @@ int mvsdf_step_saved_offsets(void* step, size_t out[6]) {
     out[0] = st->fo.x_eval; out[1] = st->fo.y_eval; out[2] = st->fo.n_eval; out[3] = st->fo.view_sorted; out[4] = st->fo.render_ctx; out[5] = st->fo.rgb_sorted;
     return 0;
 }
+int mvsdf_step_pack_offsets(void* step, int layer, size_t out[7]) {
+    Step* st = (Step*)step;
+    if (!st || !out || layer < 0 || layer >= st->nl) return mv_fail(-1, "mvsdf_step_pack_offsets: null argument / no such layer");
+    const FwdOffsets& fo = st->fo;
+    const int l = layer, td = st->d.trace_dtype;
+    const bool sdf = l < st->d.n_sdf, x3 = sdf && fo.chain_x3;
+    const size_t none = (size_t)-1;
+    out[0] = fo.w[l]; out[1] = fo.wp[l]; out[2] = fo.wpT[l];
+    out[3] = (sdf && td >= 2 && td <= 5) ? fo.wp16[l] : none;
+    out[4] = x3 ? fo.wx3[l] : none; out[5] = x3 ? fo.wx3T[l] : none;
+    out[6] = sdf ? fo.bias[l] : none;
+    return 0;
+}
 
 int mvsdf_step_wait_counts_seq(void* step, long long seq, long long counts[4]) {
     Step* st = (Step*)step;

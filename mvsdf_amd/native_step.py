@@ -86,6 +86,7 @@ def _bind():
         L.mvsdf_step_done_seq.restype = C.c_longlong
         L.mvsdf_step_can_defer.argtypes = [C.c_void_p]
         L.mvsdf_step_saved_offsets.argtypes = [C.c_void_p, C.c_void_p]
+        L.mvsdf_step_pack_offsets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mvsdf_step_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]
         L.mvsdf_step_set_timing.argtypes = [C.c_void_p, C.c_int]
         L.mvsdf_step_trace_times.argtypes = [C.c_void_p, C.c_void_p]
@@ -280,6 +281,14 @@ class NativeStep:
         out = (C.c_size_t * 6)()
         check(lib().mvsdf_step_saved_offsets(self._h, out), 'mvsdf_step_saved_offsets')
         return dict(zip(('x_eval', 'y_eval', 'n_eval', 'view_sorted', 'render_ctx', 'rgb_sorted'), (int(v) for v in out)))
+
+    def pack_offsets(self, layer):
+        """Byte offsets inside a forward block of layer `layer`'s {w, wp, wpT, wp16, wx3, wx3T, bias} (mvsdf_step_pack_offsets), None where the block
+        holds none for this layer and trace dtype: inspection only."""
+        out = (C.c_size_t * 7)()
+        check(lib().mvsdf_step_pack_offsets(self._h, int(layer), out), 'mvsdf_step_pack_offsets')
+        none = C.c_size_t(-1).value
+        return {k: (None if int(v) == none else int(v)) for k, v in zip(('w', 'wp', 'wpT', 'wp16', 'wx3', 'wx3T', 'bias'), out)}
 
     def hint_N(self):
         """N of the newest forward whose counts have arrived (no waiting), or -1: only selects kernel forms of a deferred backward."""

@@ -307,7 +307,9 @@ def test_render_ignores_unwritten_allocations(nan_workspace):
 
 
 # ------------------------------------------------------------------------------------------------ weight-norm fold backward
-FOLD_SHAPES = [(1, 3), (63, 39), (257, 289), (512, 512)]
+# (5, 575) / (5, 576) / (5, 577): the last K of k_fold_bwd_net's register path (K <= 576), with a partial and a full ninth chunk, and the first K of its
+# strided path; (3, 640): ten full chunks on that path
+FOLD_SHAPES = [(1, 3), (63, 39), (257, 289), (512, 512), (5, 575), (5, 576), (5, 577), (3, 640)]
 
 
 def _fold_case(N, K):
@@ -331,7 +333,7 @@ def test_fold_backward(N, K):
 
 
 def test_fold_backward_net(nan_workspace):
-    """all four shapes in one launch, then again with every allocation poisoned"""
+    """all shapes in one launch, then again with every allocation poisoned"""
     cases = [_fold_case(N, K) for N, K in FOLD_SHAPES]
     run = lambda: ops.fold_backward_net([c[0].cuda() for c in cases], [c[1].cuda() for c in cases], [c[2].cuda() for c in cases])
     dvs, dgs = _twice(run)
@@ -341,3 +343,34 @@ def test_fold_backward_net(nan_workspace):
     with nan_workspace():
         got = run()
     _same(got, (dvs, dgs))
+
+
+def test_fold_backward_net_adds_into_sinks():
+    """The accumulating form (the parameters' .grad buffers as targets): every target starts from random values, one layer has no weight norm (g None:
+    dv = dW, no dg), the bias gradients are routed to their targets.  Result = pre-fill + the gradient, held to the float64 sum under the file's rule (the
+    kernel adds in float32)."""
+    no_g = 2
+    cases = [_fold_case(N, K) for N, K in FOLD_SHAPES]
+    gen = torch.Generator().manual_seed(77)
+    pre_v = [torch.randn(N, K, generator=gen) for N, K in FOLD_SHAPES]
+    pre_g = [None if l == no_g else torch.randn(N, generator=gen) for l, (N, K) in enumerate(FOLD_SHAPES)]
+    pre_b = [torch.randn(N, generator=gen) for N, K in FOLD_SHAPES]
+    dbs = [torch.randn(N, generator=gen) for N, K in FOLD_SHAPES]
+    vs, dWs = [c[0].cuda() for c in cases], [c[2].cuda() for c in cases]
+    gs = [None if l == no_g else c[1].cuda() for l, c in enumerate(cases)]
+    dbd = [d.cuda() for d in dbs]
+
+    def run():
+        tv, tb = [p.cuda() for p in pre_v], [p.cuda() for p in pre_b]
+        tg = [None if p is None else p.cuda() for p in pre_g]
+        assert ops.fold_backward_net(vs, gs, dWs, dbs=dbd, sinks=(tv, tg, tb)) is None
+        return tv, tg, tb
+    tv, tg, tb = _twice(run)
+    for l, (v, g, dW, ((dv64, dg64), (dv32, dg32))) in enumerate(cases):
+        if l == no_g:
+            dv64, dv32 = dW.double(), dW
+            assert tg[l] is None
+        else:
+            _check('fold_backward_net+', 'dg', tg[l], pre_g[l].double() + dg64.reshape(-1), pre_g[l] + dg32.reshape(-1))
+        _check('fold_backward_net+', 'dv', tv[l], pre_v[l].double() + dv64, pre_v[l] + dv32)
+        _check('fold_backward_net+', 'db', tb[l], pre_b[l].double() + dbs[l].double(), pre_b[l] + dbs[l])
