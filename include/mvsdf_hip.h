@@ -851,6 +851,38 @@ int mvsdf_raster_colors(const float* verts, const float* normals, int64_t nv, co
                         double cos_min, int32_t ignore_normals, float fallback_r, float fallback_g, float fallback_b, void* ws, size_t ws_bytes,
                         float* colors, int32_t* n_views, void* stream);
 
+/* ---- Texture atlases (texture.hip; Python: mvsdf_amd/texture.py, which states the definition) ----
+ * A texture image for a mesh from the photographs: every face labelled with the view that sees it largest, one patch per face (a half of a square
+ * cell of edge n = 4 << class, class 0 .. 6) packed along a Morton curve over blocks of 4 x 4 texels, the classes in descending order, and the
+ * texels filled by an affine copy of the face's image triangle.  Mesh, P, centers, depth, masks, images and pixel_center as in the raster calls,
+ * all on the device; fp64 throughout; 0 <= nf <= 2^28.  Every call starts by zeroing the 256-byte header of its workspace; no call waits.
+ * mvsdf_texture_face_views: label int32 [nf] (-1: no view), score fp64 [nf] (|A| in that view, 0 without one) and screen fp64 [nf][6] (sx, sy of
+ * the three corners in that view, 0 without one).  Header: int64 {error bits}: 1 a camera or centre entry is NaN or infinite, 2 a face refers to a
+ * vertex outside [0, nv) (it stays unlabelled).
+ * mvsdf_texture_classify: cls uint8 [nf] at a texel density (finite, > 0).  Header: int64 {0, counts[7]}, the faces per class.
+ * The atlas follows from the counts alone: T = sum over the classes of ceil(count / 2) * 4^class blocks, B the smallest integer with T <= 2^B,
+ * Wt = 4 << ceil(B / 2) by Ht = 4 << floor(B / 2) texels; Wt beyond 32768 is refused.
+ * mvsdf_texture_pack (workspace: mvsdf_texture_workspace_bytes(nf), 0 beyond the limit; counts int64 [7] on the HOST, as classify left them): order int32
+ * [nf] (the faces by class descending, index ascending), patch int32 [nf][4] = {x0, y0, n, half}, uv fp32 [nf][3][2].  Header: int64 {error bits,
+ * flagged total}: 4 the counts are not those of cls (nothing else is valid).
+ * mvsdf_texture_fill: texture uint8 [Ht][Wt][3] and valid uint8 [Ht][Wt] of the atlas those counts give (another Ht x Wt is refused), both
+ * 4-byte aligned; texels nobody owns, and those of
+ * unlabelled faces, get the fallback (each 0 .. 255) and valid 0.  flags 1: the screen coordinates are projected again from verts / faces / P
+ * (the same bits) instead of read from `screen`; without it verts, faces and P may be NULL. */
+size_t mvsdf_texture_workspace_bytes(int64_t nf);
+int mvsdf_texture_face_views(const float* verts, const float* normals, const int32_t* faces, int64_t nv, int64_t nf, const double* P,
+                             const double* centers, int64_t views, int64_t H, int64_t W, double pixel_center, const float* depth, const uint8_t* masks,
+                             double depth_tol, double cos_min, int32_t ignore_normals, void* ws, size_t ws_bytes, int32_t* label, double* score,
+                             double* screen, void* stream);
+int mvsdf_texture_classify(const int32_t* label, const double* screen, int64_t nf, double density, void* ws, size_t ws_bytes, uint8_t* cls,
+                           void* stream);
+int mvsdf_texture_pack(const uint8_t* cls, int64_t nf, const int64_t* counts, void* ws, size_t ws_bytes, int32_t* order, int32_t* patch, float* uv,
+                       void* stream);
+int mvsdf_texture_fill(const uint8_t* images, int64_t views, int64_t H, int64_t W, double pixel_center, const int32_t* label, const double* screen,
+                       const int32_t* order, int64_t nf, const int64_t* counts, const float* verts, const int32_t* faces, int64_t nv, const double* P,
+                       int32_t flags, int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, int64_t Ht, int64_t Wt, uint8_t* texture,
+                       uint8_t* valid, void* stream);
+
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.
  * raw: fp32 [mvsdf_featext_raw_floats()] on the device, the layers in the order of mvsdf_amd/features.py::LAYERS, each its weight in PyTorch layout

@@ -128,6 +128,12 @@ def lib():
         L.mvsdf_raster_resolve.argtypes = [i64, i64, i64, vp, sz, vp, vp, vp]
         L.mvsdf_raster_visibility.argtypes = [vp, i64, vp, i64, i64, i64, f64, vp, vp, f64, vp, sz, vp, vp]
         L.mvsdf_raster_colors.argtypes = [vp, vp, i64, vp, vp, i64, i64, i64, f64, vp, vp, vp, f64, f64, i32, f32, f32, f32, vp, sz, vp, vp, vp]
+        L.mvsdf_texture_workspace_bytes.restype = sz
+        L.mvsdf_texture_workspace_bytes.argtypes = [i64]
+        L.mvsdf_texture_face_views.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i64, i64, f64, vp, vp, f64, f64, i32, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_texture_classify.argtypes = [vp, vp, i64, f64, vp, sz, vp, vp]
+        L.mvsdf_texture_pack.argtypes = [vp, i64, vp, vp, sz, vp, vp, vp, vp]
+        L.mvsdf_texture_fill.argtypes = [vp, i64, i64, i64, f64, vp, vp, vp, i64, vp, vp, vp, i64, vp, i32, i32, i32, i32, i64, i64, vp, vp, vp]
         for fn in ('mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_layer_workspace_bytes'):
             getattr(L, fn).restype = sz
         L.mvsdf_featext_raw_floats.argtypes = []
@@ -202,6 +208,8 @@ EXPORTS = [
     'mvsdf_cloud_clean_workspace_bytes', 'mvsdf_cloud_compact_workspace_bytes', 'mvsdf_cloud_knn', 'mvsdf_cloud_components', 'mvsdf_cloud_clean',
     'mvsdf_cloud_compact',
     'mvsdf_raster_workspace_bytes', 'mvsdf_raster_draw', 'mvsdf_raster_resolve', 'mvsdf_raster_visibility', 'mvsdf_raster_colors',
+    'mvsdf_texture_workspace_bytes', 'mvsdf_texture_face_views', 'mvsdf_texture_classify', 'mvsdf_texture_pack',
+    'mvsdf_texture_fill',
     'mvsdf_featext_raw_floats', 'mvsdf_featext_pack_bytes', 'mvsdf_featext_pack', 'mvsdf_featext_workspace_bytes', 'mvsdf_featext_forward',
     'mvsdf_featext_layer_workspace_bytes', 'mvsdf_featext_layer',
     'mvsdf_stereo_workspace_bytes', 'mvsdf_stereo_volume_offset', 'mvsdf_stereo_normalize', 'mvsdf_stereo_patches', 'mvsdf_stereo_sweep',

@@ -79,7 +79,7 @@ def write_simplified_mesh(mesh, path, epoch, cell=None, target_faces=None):
 
 def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
              eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None,
-             color_mesh=False, simplify_cell=None, simplify_faces=None):
+             color_mesh=False, simplify_cell=None, simplify_faces=None, texture_mesh=False):
     """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
     -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
     view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
@@ -87,7 +87,9 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     mesh in the colours of the input photographs as surface_world_coordinates_<epoch>_color.ply (raster.color_mesh_from_scene: image_hd/, the
     world_mat_i of cameras_hd.npz at pixel_center 0, visibility masked by mask_hd/).  -> {'epoch', 'evaldir', 'mesh', 'psnrs'} (+ 'color_mesh', the
     coloured Mesh or None, with color_mesh).  simplify_cell / simplify_faces (one of them): besides the OBJ (written as
-    without them), write_simplified_mesh's surface_world_coordinates_<epoch>_simplified.obj; the result gets 'simplified_mesh'."""
+    without them), write_simplified_mesh's surface_world_coordinates_<epoch>_simplified.obj; the result gets 'simplified_mesh'.  texture_mesh:
+    also surface_world_coordinates_<epoch>_textured.{obj,mtl,png}, texture.texture_mesh_from_scene of the simplified mesh when a simplify option is
+    given, else of the world mesh; the result gets 'textured_mesh' (the TexturedMesh, or None without a mesh)."""
     from PIL import Image
     from .checkpoint import MODEL_SUBDIR
     from .datasets.device_batches import DeviceBatches
@@ -131,6 +133,13 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
         simplified = write_simplified_mesh(mesh, evaldir, epoch, cell=simplify_cell, target_faces=simplify_faces)
         if simplified is not None:
             printer('simplified: %d -> %d faces (cell %.6g)' % (len(mesh), len(simplified), mesh.simplify_stats['cell'] or 0.0))
+    textured = None
+    if texture_mesh and (simplified if simplify else mesh) is not None:
+        from . import texture
+        textured = texture.texture_mesh_from_scene(simplified if simplify else mesh, data_dir)
+        textured.export(os.path.join(evaldir, 'surface_world_coordinates_{0}_textured.obj'.format(epoch)))
+        printer('textured: %d faces, atlas %d x %d at %.6g texels per pixel' % (len(textured.mesh), textured.texture.shape[1], textured.texture.shape[0],
+                                                                              textured.density))
     psnrs = None
     if eval_rendering:
         images_dir = os.path.join(evaldir, 'rendering')
@@ -153,6 +162,8 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
         res['color_mesh'] = colored
     if simplify:
         res['simplified_mesh'] = simplified
+    if texture_mesh:
+        res['textured_mesh'] = textured
     return res
 
 
@@ -181,6 +192,9 @@ def eval_parser():
     g.add_argument('--simplify_cell', default=None, type=float,
                    help='Also write surface_world_coordinates_<epoch>_simplified.obj: Mesh.simplify on a grid of this edge (world units).')
     g.add_argument('--simplify_faces', default=None, type=int, help='The same with Mesh.simplify(target_faces=N): at most N faces.')
+    p.add_argument('--texture_mesh', default=False, action='store_true',
+                   help='Also write surface_world_coordinates_<epoch>_textured.obj / .mtl / .png: the simplified mesh (with a simplify option, else the '
+                        'world mesh) with a texture atlas from image_hd/ (mvsdf_amd/texture.py).')
     return p
 
 
@@ -191,4 +205,5 @@ def main(argv=None, printer=print):
     return evaluate(data_dir=opt.data_dir, conf=opt.conf, expname=opt.expname, exps_folder_name=opt.exps_folder, evals_folder_name='evals',
                     timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
                     exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer, sparse_mesh=opt.sparse_mesh, mesh_block=opt.mesh_block,
-                    mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh, simplify_cell=opt.simplify_cell, simplify_faces=opt.simplify_faces)
+                    mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh, simplify_cell=opt.simplify_cell, simplify_faces=opt.simplify_faces,
+                    texture_mesh=opt.texture_mesh)

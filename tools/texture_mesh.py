@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Give a mesh a texture atlas from the input photographs of a scene, on the GPU:
+
+    python tools/texture_mesh.py IN OUT.obj --data_dir SCENE [--density D] [--max_size S] [--faces N | --cell C] [--no_masks]
+
+IN is any mesh in world coordinates that load_mesh reads (OBJ / PLY), for example the evaluation's surface_world_coordinates_<epoch>.obj.  With
+--faces N or --cell C it is simplified first (Mesh.simplify(target_faces=N) / (cell=C)).  The mesh is drawn into the cameras of
+SCENE/cameras_hd.npz (world_mat_i, pixel centres at integer coordinates); every face takes the view of SCENE/image_hd/ that sees it largest and
+gets a patch of the atlas at --density texels per image pixel (mvsdf_amd/texture.py states the definition).  Visibility is also masked by
+SCENE/mask_hd/ unless --no_masks.  Faces that no view sees are grey.  Written: OUT.obj with vt / mtllib, OUT.mtl and OUT.png beside it."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+
+def parser():
+    p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    p.add_argument('in_file', type=str)
+    p.add_argument('out_file', type=str)
+    p.add_argument('--data_dir', type=str, required=True, help='scene directory with image_hd/, mask_hd/ and cameras_hd.npz')
+    p.add_argument('--density', type=float, default=1.0, help='texels per image pixel along a face\'s longest edge')
+    p.add_argument('--max_size', type=int, default=8192, help='the atlas is at most this many texels wide; the density is halved until it fits')
+    g = p.add_mutually_exclusive_group()
+    g.add_argument('--faces', type=int, default=None, help='simplify to at most N faces first (Mesh.simplify(target_faces=N))')
+    g.add_argument('--cell', type=float, default=None, help='simplify on a grid of this edge first (Mesh.simplify(cell=C))')
+    p.add_argument('--no_masks', default=False, action='store_true', help='do not restrict visibility to mask_hd/')
+    p.add_argument('--depth_tol', type=float, default=0.01, help='a vertex is visible when its depth is within (1 + depth_tol) of the drawn depth')
+    p.add_argument('--cos_min', type=float, default=0.0, help='views whose ray meets the face normal at a cosine not above this are left out')
+    p.add_argument('--ignore_normals', default=False, action='store_true', help='faces with a zero normal take every view that sees them')
+    return p
+
+
+def main(argv=None):
+    p = parser()
+    args = p.parse_args(argv)
+    if not os.path.exists(args.in_file):
+        p.exit(1, 'texture_mesh.py: %s: no such file\n' % args.in_file)
+    if os.path.splitext(args.out_file)[1].lower() != '.obj':
+        p.exit(1, 'texture_mesh.py: %s: the output is an .obj (with its .mtl and .png beside it)\n' % args.out_file)
+    from mvsdf_amd import texture
+    from mvsdf_amd.mesh import load_mesh
+    mesh = load_mesh(args.in_file).to('cuda')
+    if args.faces is not None or args.cell is not None:
+        n = len(mesh)
+        mesh = mesh.simplify(cell=args.cell, target_faces=args.faces)
+        if mesh is None:
+            p.exit(1, 'texture_mesh.py: no face survives the simplification\n')
+        print('[texture] simplified: %d -> %d faces' % (n, len(mesh)))
+    out = texture.texture_mesh_from_scene(mesh, args.data_dir, masks=not args.no_masks, texel_density=args.density, max_size=args.max_size,
+                                          depth_tol=args.depth_tol, cos_min=args.cos_min, ignore_normals=args.ignore_normals)
+    seen = int((out.face_view >= 0).sum())
+    print('[texture] %d of %d faces textured from %d views; atlas %d x %d at %.6g texels per pixel, %.1f%% of its texels from photographs'
+          % (seen, len(mesh), out.raster.depth.shape[0], out.texture.shape[1], out.texture.shape[0], out.density, 100.0 * float(out.valid.float().mean())))
+    out.export(args.out_file)
+    return out
+
+
+if __name__ == '__main__':
+    main()

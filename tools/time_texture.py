@@ -1,0 +1,123 @@
+"""Device time of the texture atlas stages (mvsdf_amd/texture.py, csrc/texture.hip): face labels, the class count pass, the packing and the
+texel fill, each between two device events after a warm-up, the work ending in a synchronise; the median of --repeats runs, one JSON line.
+
+The scene is synthetic and its size is stated in the output: mesh.sparse_marching_cubes of the synthetic model (--width) at --resolution,
+simplified to --faces faces (Mesh.simplify), drawn into --views cameras on three rings around the origin at --hw pixels (pixel centres at +0.5),
+textured from random images at --density texels per pixel.  The fill is timed twice within every repeat, alternating: reading the per-face table
+of screen coordinates that the label pass wrote, and projecting the three corners again per texel (the A/B behind DESIGN.md's choice); the two
+atlases are compared.  For the fill the bytes written (4 per texel: colour and valid) plus gathered (12 per valid texel: 2 x 2 pixels of 3
+bytes) over its time are also given as a share of the 6.3e12 B/s that tools/time_poisson.py uses.  The count and pack stages include the read
+of their header, which waits for the stream.  For the split by kernel run the script under rocprofv3 --kernel-trace --stats in a run of its
+own (--repeats 1).
+
+    python tools/time_texture.py [--resolution 512 --faces 50000 --views 49 --hw 1200,1600 --density 1.0 --max_size 8192 --repeats 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))                       # time_raster's cameras
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+PEAK_BYTES_PER_S = 6.3e12
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('--resolution', type=int, default=512)
+    ap.add_argument('--faces', type=int, default=50000, help='simplify the extracted mesh to at most this many faces (0: not at all)')
+    ap.add_argument('--views', type=int, default=49)
+    ap.add_argument('--hw', type=str, default='1200,1600')
+    ap.add_argument('--density', type=float, default=1.0)
+    ap.add_argument('--max_size', type=int, default=8192)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--width', type=int, default=256, help='hidden width of the synthetic model')
+    return ap
+
+
+def _events(n):
+    return [torch.cuda.Event(enable_timing=True) for _ in range(n)]
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    assert torch.cuda.is_available(), 'time_texture.py measures on the GPU'
+    from time_raster import ring_cameras
+    from mvsdf_amd import mesh as M
+    from mvsdf_amd import raster as R
+    from mvsdf_amd import texture as X
+    from mvsdf_amd._lib import lib
+    from mvsdf_amd.model.implicit_differentiable_renderer import IDRNetwork
+    from mvsdf_amd.utils import synth
+    from mvsdf_amd.utils.config import ConfigDict
+    hw = tuple(int(v) for v in a.hw.split(','))
+    m = IDRNetwork(ConfigDict(synth.model_conf(a.width)))
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(a.width, 0).items()})
+    m = m.cuda().eval()
+    mesh = M.sparse_marching_cubes(m.implicit_network.native_sdf(), a.resolution, 0.0)
+    extracted = len(mesh)
+    if a.faces and a.faces < extracted:
+        mesh = mesh.simplify(target_faces=a.faces)
+    P = ring_cameras(a.views, hw)
+    g = torch.Generator(device='cuda').manual_seed(0)
+    images = torch.randint(0, 256, (a.views, hw[0], hw[1], 3), dtype=torch.uint8, device='cuda', generator=g)
+    raster = R.rasterize(mesh, P=P, hw=hw)
+    nf = len(mesh)
+    ws = torch.empty(lib().mvsdf_texture_workspace_bytes(nf), dtype=torch.uint8, device='cuda')
+    cls = torch.empty(nf, dtype=torch.uint8, device='cuda')
+    v, f = mesh.vertices.contiguous(), mesh.faces.contiguous()
+    Pd = torch.from_numpy(P).cuda()
+    names = ('face_views_ms', 'count_pass_ms', 'pack_ms', 'fill_table_ms', 'fill_recompute_ms')
+    runs = {k: [] for k in names}
+    passes = 0
+    for rep in range(a.repeats + 1):                                  # the first round warms up
+        ev = _events(6)
+        ev[0].record()
+        label, score, screen = X._face_views(mesh, raster, None, 0.01, 0.0, False, 'time_texture')
+        ev[1].record()
+        d, passes = a.density, 0
+        while True:                                                   # build_atlas's loop; the event pair spans its last pass only
+            ev[1].record()
+            counts = X._classify(label, screen, d, ws, cls)
+            passes += 1
+            if X.atlas_size(counts)[0] <= a.max_size:
+                break
+            d = d / 2.0
+        ev[2].record()
+        order, patch, uv = X._pack(cls, counts, ws)
+        ev[3].record()
+        tex, valid = X._fill(images, 0.5, label, screen, order, counts, v, f, Pd, (128, 128, 128), False)
+        ev[4].record()
+        tex2, valid2 = X._fill(images, 0.5, label, screen, order, counts, v, f, Pd, (128, 128, 128), True)
+        ev[5].record()
+        torch.cuda.synchronize()
+        assert torch.equal(tex, tex2) and torch.equal(valid, valid2)
+        if rep:
+            for k, name in enumerate(names):
+                runs[name].append(ev[k].elapsed_time(ev[k + 1]))
+    med = lambda x: round(float(np.median(x)), 3)                     # noqa: E731
+    Wt, Ht, T = X.atlas_size(counts)
+    n_valid = int(valid.sum())
+    nbytes = 4 * Wt * Ht + 12 * n_valid
+    res = {'resolution': a.resolution, 'extracted_faces': extracted, 'faces': nf, 'views': a.views, 'hw': hw, 'repeats': a.repeats,
+           'density_asked': a.density, 'density_used': d, 'count_passes': passes, 'class_counts': [int(c) for c in counts], 'atlas': [Wt, Ht],
+           'blocks_used_fraction': round(T / ((Wt // 4) * (Ht // 4)), 4), 'labelled_fraction': round(float((label >= 0).float().mean()), 4),
+           'valid_texels': n_valid, 'valid_fraction': round(n_valid / (Wt * Ht), 4), 'fill_bytes': nbytes}
+    for name in names:
+        res[name] = {'median': med(runs[name]), 'runs': [round(x, 3) for x in runs[name]]}
+    for name in ('fill_table_ms', 'fill_recompute_ms'):
+        rate = nbytes / (res[name]['median'] * 1e-3)
+        res[name]['bytes_per_s'] = float('%.4g' % rate)
+        res[name]['share_of_6.3e12'] = round(rate / PEAK_BYTES_PER_S, 4)
+        res[name]['texels_per_s'] = float('%.4g' % (Wt * Ht / (res[name]['median'] * 1e-3)))
+    print(json.dumps(res), flush=True)
+    return res
+
+
+if __name__ == '__main__':
+    main()
