@@ -61,43 +61,6 @@ class LossLayout(C.Structure):
                                           'd_eo', 'd_sf', 's_rgb', 's_grad', 's_eo', 's_sf', 's_diff')]
 
 
-_bound = False
-
-
-def _bind():
-    global _bound
-    L = lib()
-    if not _bound:
-        L.mvsdf_step_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-        L.mvsdf_step_destroy.argtypes = [C.c_void_p]
-        L.mvsdf_step_destroy.restype = None
-        L.mvsdf_step_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.mvsdf_step_resolve_unhit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mvsdf_step_can_defer_unhit.argtypes = [C.c_void_p]
-        L.mvsdf_step_set_sphere_cut.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.mvsdf_step_last_tracer_grid.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_step_wait_counts.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_step_seq.argtypes = [C.c_void_p]
-        L.mvsdf_step_seq.restype = C.c_longlong
-        L.mvsdf_step_counts_offset.argtypes = [C.c_void_p]
-        L.mvsdf_step_counts_offset.restype = C.c_size_t
-        L.mvsdf_step_wait_counts_seq.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
-        L.mvsdf_step_done_seq.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_step_done_seq.restype = C.c_longlong
-        L.mvsdf_step_can_defer.argtypes = [C.c_void_p]
-        L.mvsdf_step_saved_offsets.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_step_pack_offsets.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.mvsdf_step_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]
-        L.mvsdf_step_set_timing.argtypes = [C.c_void_p, C.c_int]
-        L.mvsdf_step_trace_times.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_step_times.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_loss_layout.argtypes = [C.c_void_p, C.c_void_p]
-        L.mvsdf_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mvsdf_loss_backward.argtypes = [C.c_void_p] * 9
-        _bound = True
-    return L
-
-
 loss_timing = None                                             # bench.py sets a list: (start, end) events around every mvsdf_loss_forward are appended
 
 
@@ -154,7 +117,7 @@ class NativeStep:
     parameters and the backward's scratch block."""
 
     def __init__(self, desc, device):
-        L = _bind()
+        L = lib()
         self.desc, self.device = desc, device
         self.layout = StepLayout()
         h = C.c_void_p()
@@ -445,7 +408,7 @@ class _NativeLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, args, keep, rgb, grad_theta, eik_out, surf, diff_pts):
-        L = _bind()
+        L = lib()
         lo = LossLayout()
         check(L.mvsdf_loss_layout(C.byref(args), C.byref(lo)), 'mvsdf_loss_layout')
         dev = rgb.device
@@ -495,7 +458,7 @@ class _DeferredStepLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rec, args, keep, *params):
-        L = _bind()
+        L = lib()
         lo = LossLayout()
         check(L.mvsdf_loss_layout(C.byref(args), C.byref(lo)), 'mvsdf_loss_layout')
         st = rec.step

@@ -330,7 +330,7 @@ def sphere_intersection(cam_loc, ray_dirs, r=1.0):
     B, P = ray_dirs.shape[:2]
     t = torch.empty(B, P, 2, dtype=torch.float32, device=ray_dirs.device)
     m = torch.empty(B, P, dtype=torch.uint8, device=ray_dirs.device)
-    check(lib().mvsdf_sphere_intersection(ptr(cam_loc), ptr(ray_dirs), B, P, C.c_float(r), ptr(t), ptr(m), stream_of(ray_dirs)),
+    check(lib().mvsdf_sphere_intersection(ptr(cam_loc), ptr(ray_dirs), B, P, r, ptr(t), ptr(m), stream_of(ray_dirs)),
           'mvsdf_sphere_intersection')
     return t, m.bool()
 
@@ -373,7 +373,7 @@ def trace(net, cam_loc, ray_dirs, object_mask, params, training, intervals, mins
     iv = _f32(intervals)
     st = _f32(minsdf_steps) if minsdf_steps is not None else None
     args = (C.byref(d), C.byref(tp), ptr(cam_loc), ptr(ray_dirs), ptr(om), B, P, 1 if training else 0, ptr(iv), ptr(st),
-            ptr(pts), ptr(mask), ptr(dists), ptr(counters), ptr(ws), C.c_size_t(wsb), mt, mt_samples, stream_of(ray_dirs))
+            ptr(pts), ptr(mask), ptr(dists), ptr(counters), ptr(ws), wsb, mt, mt_samples, stream_of(ray_dirs))
     if mask_ready is not None:
         # events: (start, after sphere tracing, after the sampler rows, before secant / min-sdf, end)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if events is not None else None
@@ -591,8 +591,8 @@ def depth_carve(pts, depths, cams, size, center, out_thresh_perc, far_thresh, fa
     dist_r = torch.empty(M, dtype=torch.float32, device=dev)
     weight = torch.empty(M, dtype=torch.float32, device=dev)
     check(lib().mvsdf_depth_carve(ptr(pts), pts.shape[1], M, ptr(depths), B, h, w, ptr(cams), ptr(_f32(size).reshape(-1)),
-                                  ptr(_f32(center).reshape(-1)), C.c_float(out_thresh_perc), C.c_float(far_thresh), C.c_float(far_att),
-                                  C.c_float(near_thresh), C.c_float(near_att), 1 if use_invalid else 0, ptr(dist_r), ptr(weight), ptr(pts) if world_inplace else None,
+                                  ptr(_f32(center).reshape(-1)), out_thresh_perc, far_thresh, far_att, near_thresh, near_att,
+                                  1 if use_invalid else 0, ptr(dist_r), ptr(weight), ptr(pts) if world_inplace else None,
                                   stream_of(pts)), 'mvsdf_depth_carve')
     return dist_r, weight
 
@@ -619,8 +619,7 @@ def loss_terms(rgb, rgb_gt, rgb_mask, grad_theta, eik_out, dist_r, dweight, surf
     w = [float(x) for x in weights] + [0.0]                       # weights[5] (optional): conf.smooth of the depth term, 0 / None = L1
     check(lib().mvsdf_loss_terms(ptr(rgb), ptr(rgb_gt), ptr(m), R, ptr(gt_), gt_.shape[0] if gt_ is not None else 0, ptr(eo), ptr(_f32(dist_r)),
                                  ptr(_f32(dweight)), eo.numel(), ptr(sf), sf.numel() if sf is not None else 0, ptr(npos), ptr(fp),
-                                 fp.numel() if fp is not None else 0, C.c_float(w[0]), C.c_float(w[1]), C.c_float(w[2]), C.c_float(w[3]),
-                                 C.c_float(w[4]), C.c_float(w[5]), 1 if surf_on else 0, 1 if feat_on else 0, ptr(_f32(inv_counts)) if inv_counts is not None else None,
+                                 fp.numel() if fp is not None else 0, *w[:6], 1 if surf_on else 0, 1 if feat_on else 0, ptr(_f32(inv_counts)) if inv_counts is not None else None,
                                  ptr(out), ptr(d_rgb), ptr(d_grad), ptr(d_eo), ptr(d_sf), stream_of(rgb)), 'mvsdf_loss_terms')
     return out, d_rgb, d_grad, d_eo, d_sf
 
@@ -675,7 +674,7 @@ def dsurf_samples(depths, depth_cams, size, center, bb, jitter_rad, seed, n):
     size, center = _f32(size.reshape(-1)[:1]), _f32(center.reshape(-1)[:3])
     idx = torch.full((2, n), 1 << 62, dtype=torch.int64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    geo = (ptr(depths), ptr(kinv), ptr(einv), N, H, W, ptr(size), ptr(center), C.c_float(bb), C.c_float(jitter_rad), C.c_ulonglong(seed), n)
+    geo = (ptr(depths), ptr(kinv), ptr(einv), N, H, W, ptr(size), ptr(center), bb, jitter_rad, seed, n)
     check(lib().mvsdf_dsurf_select(*geo, ptr(idx), ptr(counts), stream_of(depths)), 'mvsdf_dsurf_select')
     idx_sorted = torch.sort(idx, dim=1).values                                    # reference: np.sort(sample_idx)
     pts_on = torch.empty(n, 3, dtype=torch.float32, device=dev)
@@ -755,7 +754,7 @@ def trace_generic(sdf, cam_loc, ray_dirs, object_mask, params, training, interva
         flat_vals[idx] = call(flat_pts[idx])
         check(L.mvsdf_tracegen_step(C.byref(tp), *geo, B, P, ptr(state), ptr(vals), ptr(req), ptr(rpts), ptr(counters), st), 'mvsdf_tracegen_step')
     check(L.mvsdf_tracegen_finish(C.byref(tp), *geo, B, P, 1 if training else 0, ptr(state), ptr(pts), ptr(mask), ptr(dists), ptr(counters),
-                                  ptr(ws), C.c_size_t(wsb), st), 'mvsdf_tracegen_finish')
+                                  ptr(ws), wsb, st), 'mvsdf_tracegen_finish')
     cnt = counters.tolist()
     n_s, n_m = cnt[5], cnt[6]                                     # MVSDF_CNT_N_SAMPLER, MVSDF_CNT_N_MINSDF
     marks = torch.empty(R, dtype=torch.uint8, device=dev)

@@ -12,10 +12,20 @@ def test_header_matches_exports_and_so():
     hdr = open(os.path.join(ROOT, 'include', 'mvsdf_hip.h')).read()
     hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     declared = sorted(set(re.findall(r'\b(mvsdf_\w+)\s*\(', hdr)))
-    assert declared == sorted(_lib.EXPORTS), (set(declared) ^ set(_lib.EXPORTS))
+    assert declared == sorted(_lib.EXPORTS), (set(declared) ^ set(_lib.EXPORTS))      # (EXPORTS is derived from the header: the parser missed nothing)
     L = ctypes.CDLL(so)
     for name in declared:
         assert getattr(L, name) is not None
+    # the other direction from the sources: every mvsdf_* function DEFINED under csrc/ (a definition starts its line, with or without extern "C") is declared
+    defined = set()
+    csrc = os.path.join(ROOT, 'mvsdf_amd', 'csrc')
+    for dp, _, fns in os.walk(csrc):
+        for fn in fns:
+            if fn.endswith(('.hip', '.h', '.cpp')):
+                src = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', open(os.path.join(dp, fn), errors='ignore').read(), flags=re.S)
+                defined |= set(re.findall(r'^(?:extern\s+"C"\s+)?(?:[\w*]+[ \t]+)+\**(mvsdf_\w+)\s*\([^(){};]*\)\s*\{', src, flags=re.M))
+    assert defined <= set(declared), 'defined under csrc/ but not declared in the header: %s' % sorted(defined - set(declared))
+    assert set(declared) <= defined, 'the scan of csrc/ did not find the definition of: %s' % sorted(set(declared) - defined)
     assert _lib.lib().mvsdf_version() >= 100
     assert _lib.lib().mvsdf_packed_floats(258, 256) == 272 * 256
     assert _lib.lib().mvsdf_packed_floats(256, 39) == 256 * 64          # K padded to 32
@@ -38,7 +48,6 @@ def test_ctypes_structs_have_the_sizes_the_library_was_compiled_with():
     side only shows up here instead of as silently shifted arguments."""
     from mvsdf_amd import _lib, native_step as ns
     out = (ctypes.c_size_t * 8)()
-    _lib.lib().mvsdf_abi_struct_sizes.argtypes = [ctypes.POINTER(ctypes.c_size_t)]
     assert _lib.lib().mvsdf_abi_struct_sizes(out) == 8
     mirrors = [_lib.NetDesc, _lib.TraceParams, ns.StepDesc, ns.StepParams, ns.StepInputs, ns.StepLayout, ns.LossArgs, ns.LossLayout]
     for cls, size in zip(mirrors, list(out)):

@@ -31,8 +31,6 @@ SCALES = (-40, -10, 0, 10, 40)
 
 
 def _bf16_bytes(N, K):
-    lib().mvsdf_packed_bf16_bytes.restype = C.c_size_t
-    lib().mvsdf_packed_bf16_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     return int(lib().mvsdf_packed_bf16_bytes(N, K, 0))
 
 

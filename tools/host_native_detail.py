@@ -29,7 +29,7 @@ def wrap(obj, name, label):
         finally:
             acc[label] = acc.get(label, 0.0) + time.perf_counter() - t0
     setattr(obj, name, g)
-L = NS._bind()
+L = NS.lib()
 class LibProxy:
     def __init__(self, lib): self._lib = lib
     def __getattr__(self, n):
@@ -40,7 +40,6 @@ class LibProxy:
         return g
 proxy = LibProxy(L)
 NS.lib = lambda: proxy
-NS._bind = lambda: proxy
 import mvsdf_amd.optim as OPT
 OPT.lib = lambda: proxy
 wrap(NS._NativeStepFn, 'forward', 'py _NativeStepFn.forward (incl. C + wait)')
