@@ -199,6 +199,15 @@ size_t mvsdf_trace_cut_workspace_bytes(int R, int n_steps);
 int mvsdf_trace_cut_stage(int stage, int max_rounds, const MvsdfNetDesc* net, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                           const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
                           float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
+/* The sample rows of such a sequence in the sixteen-wave form (k_row_chunks: sixteen waves x one column tile over the two row tiles of a chunk, the sphere tracer's
+ * carried weight ring and ping-pong tiles; one workgroup per compute unit at most, each taking every grid-th chunk) -- for launches of about one chunk per compute unit,
+ * which are one dependent evaluation.  part 1: mvsdf_trace_stage 3 with the FIRST sampler window in that form (the rest of the samples keeps its launch); part 2:
+ * mvsdf_trace_cut_stage 3 with the late list's rows in that form.  rows16 == 0: exactly the launches of those stages.  grid_cap > 0: at most that many workgroups
+ * (tests: the stride loop at small sizes).  The form exists for the three-weight-term engine (trace_dtype 5) up to hidden width 256 with mt_samples >= 2; -3 elsewhere.
+ * Same values as the stages it stands for, bit for bit. */
+int mvsdf_trace_rows_stage(int part, int rows16, int grid_cap, const MvsdfNetDesc* net, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                           const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
+                           float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
 
 /* ---- RayTracing.forward for an OPAQUE `sdf` callable (ray_tracing.py:27-32, called with a lambda at idr.py:194) ----
  * The per-ray state machine of mvsdf_trace split at its evaluation points, so that a host-side callable can be run between the launches:
@@ -479,6 +488,14 @@ int mvsdf_step_can_defer_unhit(void* step);
  * partition; no host wait).  enable < 0 (the default): where it pays (three-weight-term engine, one row tile per sphere workgroup, between half a workgroup and one per compute unit); 0: never -- the launch
  * sequence without it; > 0: always.  max_rounds <= 0: st_iters + 1.  Same values with and without. */
 int mvsdf_step_set_sphere_cut(void* step, int enable, int max_rounds);
+/* The fork of a forward that takes the sphere cut, part by part (each: < 0 by its rule, 0 the launch sequence without that part exactly, > 0 on wherever the cut is on;
+ * none of them touches a forward without the cut).  late_on_main: the late branch (resume launch, late rows, their reduction) stays on the forward's stream with no
+ * event in front of it and the sampler windows go to the second stream.  partition_beside_secant: the ray partition (and the count record it sends to the host) runs on
+ * the second stream beside the secant chains; the forward's stream waits for it in front of the fused evaluation.  rows16: the late list's rows and the first
+ * sampler window in the sixteen-wave form (mvsdf_trace_rows_stage; 1: both, 2: the late rows alone, 3: the first window alone); -3 from the forward where it is
+ * forced on for a network without that form.  rows16_grid_cap > 0:
+ * at most that many workgroups in those launches.  Same values in every combination. */
+int mvsdf_step_set_fork(void* step, int late_on_main, int partition_beside_secant, int rows16, int rows16_grid_cap);
 int mvsdf_step_last_tracer_grid(void* step, int out[2]);
 /* blocks until the counts of the last mvsdf_step_forward are on the host: {N hit, N hit & true mask, depth-surface samples found per set x 2}.
  * The one host wait of a CLASSIC training step (the fused evaluation enqueued behind the count record keeps the GPU busy meanwhile); a DEFERRED

@@ -58,6 +58,10 @@ struct Step {
     int cut_enable, cut_rounds, cut_on;              // cut_enable < 0: by the route's rule; cut_on: -1 undecided, 0 / 1 (streams and events exist)
     hipStream_t late;                                // normal priority: its few workgroups are latency chains like the main stream's
     hipEvent_t ev_cut, ev_late;
+    // the fork of a forward with the cut, part by part (mvsdf_step_set_fork; < 0: by rule): the late branch on the launch stream and the windows on `late`, the ray
+    // partition on `late` beside the secant chains, the sixteen-wave rows form (0 / 1 both uses / 2 late rows / 3 first window)
+    int fork_late_main, fork_part_side, fork_rows16, fork_rows16_cap;
+    hipEvent_t ev_main, ev_part;                     // launch stream -> `late` in front of the partition; the partition's record
 };
 
 // descriptors of the two networks over the packs inside a forward block
@@ -142,6 +146,7 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
     st->Nout = d.N[d.n_sdf - 1]; st->K0r = d.K[d.n_sdf];
     st->split_rows = -1;
     st->cut_enable = -1; st->cut_on = -1;
+    st->fork_late_main = st->fork_part_side = st->fork_rows16 = -1;
     const int R = st->R, M = st->M;
     // probe descriptors (sizes only; the size functions do not dereference the pack pointers but the validity checks want non-null ones)
     MvsdfNetDesc sdf, sdfT, rnd, rndT;
@@ -231,7 +236,7 @@ void mvsdf_step_destroy(void* step) {
     if (st->timing) for (int i = 0; i < 9; ++i) hipEventDestroy(st->ev_t[i]);
     if (st->counts_host) { hipEventDestroy(st->ev_counts); hipHostFree(st->counts_host); }
     if (st->side) { hipStreamSynchronize(st->side); hipEventDestroy(st->ev_fork); hipEventDestroy(st->ev_join); hipStreamDestroy(st->side); }
-    if (st->late) { hipStreamSynchronize(st->late); hipEventDestroy(st->ev_cut); hipEventDestroy(st->ev_late); hipStreamDestroy(st->late); }
+    if (st->late) { hipStreamSynchronize(st->late); hipEventDestroy(st->ev_cut); hipEventDestroy(st->ev_late); hipEventDestroy(st->ev_main); hipEventDestroy(st->ev_part); hipStreamDestroy(st->late); }
     delete st;
 }
 
@@ -255,6 +260,17 @@ int mvsdf_step_set_sphere_cut(void* step, int enable, int max_rounds) {
     st->cut_enable = enable < 0 ? -1 : (enable ? 1 : 0);
     st->cut_rounds = max_rounds > 0 ? max_rounds : 0;
     st->cut_on = -1;                                              // decided again by the next forward (a stream that exists stays)
+    return 0;
+}
+
+int mvsdf_step_set_fork(void* step, int late_on_main, int partition_beside_secant, int rows16, int rows16_grid_cap) {
+    Step* st = (Step*)step;
+    if (!st) return mv_fail(-1, "mvsdf_step_set_fork: null step");
+    if (rows16 > 3) return mv_fail(-1, "mvsdf_step_set_fork: rows16 must be < 0 (rule), 0, 1 (both uses), 2 (late rows) or 3 (first window)");
+    st->fork_late_main = late_on_main < 0 ? -1 : (late_on_main ? 1 : 0);
+    st->fork_part_side = partition_beside_secant < 0 ? -1 : (partition_beside_secant ? 1 : 0);
+    st->fork_rows16 = rows16 < 0 ? -1 : rows16;
+    st->fork_rows16_cap = rows16_grid_cap > 0 ? rows16_grid_cap : 0;
     return 0;
 }
 
@@ -378,15 +394,18 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     } side_guard{st->side, false};
     if (split) ST_HIP(hipEventRecord(st->ev_fork, s));             // (the folded weights are ready here)
     // 1c. the sphere cut (deferring forward only: the eager sequence keeps its launches).  The sphere launch stops after st_iters + 1 evaluations; the rays that
-    // are not done finish on `late`, with their sampler rows, beside the sampler windows of the others; the streams join in front of the ray partition.
+    // are not done finish, with their sampler rows, beside the sampler windows of the others (on two streams: 1d); the streams join in front of the secant chains.
     if (st->cut_on < 0) {
         st->cut_on = st->cut_enable > 0 || (st->cut_enable < 0 && mv_trace_cut_pays(&sdf, R, d.mt));
         if (st->cut_on && !st->late) {
             if (hipStreamCreateWithFlags(&st->late, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); st->late = nullptr; st->cut_on = 0; }
-            else if (hipEventCreateWithFlags(&st->ev_cut, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st->ev_late, hipEventDisableTiming) != hipSuccess) {
+            else if (hipEventCreateWithFlags(&st->ev_cut, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st->ev_late, hipEventDisableTiming) != hipSuccess ||
+                     hipEventCreateWithFlags(&st->ev_main, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&st->ev_part, hipEventDisableTiming) != hipSuccess) {
                 (void)hipGetLastError();
                 if (st->ev_cut) { (void)hipEventDestroy(st->ev_cut); st->ev_cut = nullptr; }
                 if (st->ev_late) { (void)hipEventDestroy(st->ev_late); st->ev_late = nullptr; }
+                if (st->ev_main) { (void)hipEventDestroy(st->ev_main); st->ev_main = nullptr; }
+                if (st->ev_part) { (void)hipEventDestroy(st->ev_part); st->ev_part = nullptr; }
                 (void)hipStreamDestroy(st->late);
                 st->late = nullptr; st->cut_on = 0;
             }
@@ -394,6 +413,17 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     }
     const bool cut = lazy && st->cut_on == 1;
     SideGuard late_guard{st->late, false};
+    // 1d. the fork of a forward with the cut (mvsdf_step_set_fork; every other forward keeps its launches).  The late branch -- resume launch, late rows, their
+    // reduction -- is the longer one and paid both event hand-offs: it stays on the launch stream behind the cut launch, with no event, and the sampler windows, which
+    // have the slack, go to `late`.  The ray partition feeds the fused evaluation, not the secant chains: it runs on `late` beside them.  The late list's rows (and,
+    // where measured to pay, the first window) are one chunk per compute unit at most: the sixteen-wave rows form (trace_route.h: mv_rows16_on).
+    const bool late_main = cut && st->fork_late_main != 0, part_side = cut && st->fork_part_side != 0;
+    int rows16 = 0;                                               // bit 0: first window, bit 1: late rows (the parts of mvsdf_trace_rows_stage)
+    if (cut && st->fork_rows16 != 0) {
+        if (st->fork_rows16 < 0) rows16 = mv_trace_rows16_pays(&sdf, R, d.mt, d.mt_samples) ? mv_rows16_uses() : 0;
+        else if (!mv_trace_rows16_has(&sdf, d.mt_samples)) return mv_fail(-3, "mvsdf_step_forward: the sixteen-wave rows form was forced on for a network without it (mvsdf_step_set_fork)");
+        else rows16 = st->fork_rows16 == 1 ? 3 : (st->fork_rows16 == 2 ? 2 : 1);
+    }
     // 2. rays + RayTracing.forward (idr.py:190-199)
     float* points = (float*)(fwd + L.points); uint8_t* mask = (uint8_t*)(fwd + L.mask); float* dists = (float*)(fwd + L.dists);
     unsigned long long* counters = (unsigned long long*)(fwd + L.counters);
@@ -409,19 +439,34 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
         return mv_trace_cut_stage(which, st->cut_rounds, 1, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
                                   counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, strm);
     };
+    // the sampler windows (stage 3) and the late list's rows + reduction (cut stage 3), each with its rows in the sixteen-wave form where `rows16` says so
+    auto windows = [&](void* strm) {
+        if (rows16 & 1) return mvsdf_trace_rows_stage(1, 1, st->fork_rows16_cap, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points,
+                                                      mask, dists, counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, strm);
+        return mvsdf_trace_stage(3, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
+                                 counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, strm);
+    };
+    auto late_rows = [&](void* strm) {
+        if (rows16 & 2) return mvsdf_trace_rows_stage(2, 1, st->fork_rows16_cap, &sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points,
+                                                      mask, dists, counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, strm);
+        return cut_stage(3, strm);
+    };
     if (cut) {
-        // the resume launch goes on its stream BEFORE the first sampler window is enqueued: its few one-per-CU workgroups are placed first
+        // the resume launch is enqueued BEFORE the first sampler window: its few one-per-CU workgroups are placed first.  late_main: it follows the cut launch on the
+        // launch stream (no event in between) and `late` takes the windows; else it is the late branch that waits for ev_cut on `late`
         ST_TRY(cut_stage(1, stream));
         ST_HIP(hipEventRecord(st->ev_cut, s));
+        if (late_main && st->timing) ST_HIP(hipEventRecord(st->ev_t[1], s));   // (behind the cut launch, as without the fork)
         ST_HIP(hipStreamWaitEvent(st->late, st->ev_cut, 0));
         late_guard.armed = true;
-        ST_TRY(cut_stage(2, (void*)st->late));
-        ST_TRY(cut_stage(3, (void*)st->late));
-        ST_HIP(hipEventRecord(st->ev_late, st->late));
+        void* branch = late_main ? stream : (void*)st->late;
+        ST_TRY(cut_stage(2, branch));
+        ST_TRY(late_rows(branch));
+        if (!late_main) ST_HIP(hipEventRecord(st->ev_late, st->late));
     } else if (lazy) ST_TRY(stage(1));
     else ST_TRY(mv_trace_stage1_prezeroed(&sdf, &d.tp, cam_loc, ray_dirs, in->object_mask, d.B, d.P, 1, in->intervals, in->minsdf_steps, points, mask, dists,
                                      counters, fwd + fo.trace_ws, fo.trace_ws_bytes, d.mt, d.mt_samples, stream));   // counters zeroed by the prologue
-    if (st->timing) ST_HIP(hipEventRecord(st->ev_t[1], s));
+    if (st->timing && !late_main) ST_HIP(hipEventRecord(st->ev_t[1], s));
     if (split) {                                                  // enqueued AFTER the sphere tracer: its workgroups take the CUs first
         ST_HIP(hipStreamWaitEvent(st->side, st->ev_fork, 0));
         side_guard.armed = true;
@@ -430,21 +475,29 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
         else if (rcs) return rcs;
         else ST_HIP(hipEventRecord(st->ev_join, st->side));
     }
-    ST_TRY(stage(3));                                             // the hit mask is final here (ray_tracing.py:61)
-    if (cut) { ST_HIP(hipStreamWaitEvent(s, st->ev_late, 0)); late_guard.armed = false; }   // ... with the late rays' share of it
+    ST_TRY(windows(late_main ? (void*)st->late : stream));        // the hit mask is final here (ray_tracing.py:61)
+    if (late_main) ST_HIP(hipEventRecord(st->ev_late, st->late));
+    // the partition beside the secant chains: `late` gets the launch stream's share of the mask (ev_main) behind its own and runs it; the launch stream goes on to the
+    // secant chains, which read the lists both branches appended to and nothing the partition writes, and waits for ev_part in front of the fused evaluation
+    if (part_side) { ST_HIP(hipEventRecord(st->ev_main, s)); ST_HIP(hipStreamWaitEvent(st->late, st->ev_main, 0)); }
+    if (cut) { ST_HIP(hipStreamWaitEvent(s, st->ev_late, 0)); late_guard.armed = part_side; }   // ... with the other branch's share of it (`late` is still written to while it owes the partition)
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[2], s));
+    hipStream_t ps = part_side ? st->late : s;                    // the partition's stream
     // 3. stable partition (hit rays first) + both counts; they start travelling to the host while the rest of the forward runs
     long long* perm = (long long*)(fwd + L.perm); long long* inv = (long long*)(fwd + fo.inv); long long* true_rows = (long long*)(fwd + fo.true_rows);
     long long* counts = (long long*)(fwd + fo.counts); float* view_sorted = (float*)(fwd + fo.view_sorted);
     ST_TRY(mv_partition_rays_step(mask, d.use_object_mask ? in->object_mask : nullptr, in->object_mask_true, ray_dirs, R, perm, inv, true_rows, counts,
                                   view_sorted, (int*)(fwd + fo.true_rank), d.n_ds > 0 ? in->ds_counts : nullptr,
                                   st->counts_host_dev ? st->counts_host_dev + 8 * ((st->counts_seq + 1) % MVSDF_STEP_COUNT_RING) : nullptr, st->counts_seq + 1,
-                                  (float*)(fwd + fo.counts + 32), d.n_eik, d.n_ds, d_mask, e_mask, stream));
+                                  (float*)(fwd + fo.counts + 32), d.n_eik, d.n_ds, d_mask, e_mask, (void*)ps));
     ++st->counts_seq;
     if (!st->counts_host_dev) {                                   // (pinned memory not mapped: a copy and an event)
-        ST_HIP(hipMemcpyAsync(st->counts_host, counts, 4 * sizeof(long long), hipMemcpyDeviceToHost, s));
-        ST_HIP(hipEventRecord(st->ev_counts, s));
+        ST_HIP(hipMemcpyAsync(st->counts_host, counts, 4 * sizeof(long long), hipMemcpyDeviceToHost, ps));
+        ST_HIP(hipEventRecord(st->ev_counts, ps));
     }
+    if (part_side) ST_HIP(hipEventRecord(st->ev_part, st->late));
+    // counts_stream: a stream whose completion implies that the partition has run.  The launch stream is one also when the partition runs on `late`: it waits for
+    // ev_part below, inside this forward
     st->counts_pending = true; st->counts_stream = s;
     if (st->timing) ST_HIP(hipEventRecord(st->ev_t[3], s));
     ST_TRY(stage(lazy ? 7 : 4));                                  // secant (+ min-sdf rows unless they are left to mvsdf_step_resolve_unhit): only points / dists still move
@@ -454,6 +507,7 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     {
         // (the rows are gathered inside the chain kernel, which also leaves them in x_eval)
         if (split) { ST_HIP(hipStreamWaitEvent(s, st->ev_join, 0)); side_guard.armed = false; }   // the main stream is ordered behind the side work from here on
+        if (part_side) { ST_HIP(hipStreamWaitEvent(s, st->ev_part, 0)); late_guard.armed = false; }   // perm / inv / counts / view_sorted are read from here on
         // lazy: the rays' rows end at E + N on the device (cnt_mode 1); workgroups wholly beyond leave at once
         int rcf = mv_sdf_forward_gather_cnt(&sdf, &sdfT, nullptr, &g, M, M, split ? E : 0, M, lazy ? counts : nullptr, E, 1, y_eval, n_eval, (float*)(fwd + fo.sdf_ctx), stream);
         if (rcf == 1 && lazy) return mv_fail(-3, "mvsdf_step_forward: the fused forward chain refused a step it was said to cover");

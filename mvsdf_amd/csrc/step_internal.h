@@ -90,5 +90,8 @@ extern "C" int mv_trace_cut_stage(int stage, int max_rounds, int prezeroed, cons
                               const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
                               float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream);
 extern "C" int mv_trace_cut_pays(const MvsdfNetDesc* desc, int R, int mt);
+// the sixteen-wave rows form (mvsdf_trace_rows_stage): whether it exists for this network, and trace_route.h::mv_rows16_on for it on the current device
+extern "C" int mv_trace_rows16_has(const MvsdfNetDesc* desc, int mt_samples);
+extern "C" int mv_trace_rows16_pays(const MvsdfNetDesc* desc, int R, int mt, int mt_samples);
 // {secant workgroups, sample-row workgroups} of the last secant / min-sdf launch this thread enqueued (trace.hip)
 void mv_trace_last_grid(int out[2]);

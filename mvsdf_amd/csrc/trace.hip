@@ -508,7 +508,8 @@ struct RowSeg { const int* list; const int* src; int cnt_index, i0, ni, blocks; 
 // Sample rows of a work list, FLATTENED over rays: global row q = item * ni + j (sample i0 + j).  A workgroup evaluates one chunk
 // of 16*MT consecutive rows (always full tiles, evenly spread over the chip) and stores the SDF values; the per-ray logic runs
 // in k_reduce_items.  Sampler rays: ray_tracing.py:206-219; min-sdf rays: ray_tracing.py:287-301.
-template <int MT, int NTW, int NW, class NET>
+// SPHERE: k_sphere_trace's form of the evaluation, as in mv_secant_rays below (k_row_chunks)
+template <int MT, int NTW, int NW, class NET, bool SPHERE = false>
 __device__ void mv_eval_rows(const NET& net, const MvTraceParams& tp, const SampleCtx& c, const RowSeg& sg, long long q0, float* smem, int n_list) {
     constexpr int ROWS = 16 * MT;
     const int tid = threadIdx.x;
@@ -516,7 +517,7 @@ __device__ void mv_eval_rows(const NET& net, const MvTraceParams& tp, const Samp
     const long long total = (long long)n_list * ni;
     if (q0 >= total) return;
     const int nr = (int)min((long long)ROWS, total - q0);
-    TraceLds lds = mv_carve<NET>(smem, ROWS, net.S, 3 + 6 * net.multires, 0);
+    TraceLds lds = mv_carve<NET, (SPHERE && NTW < 4)>(smem, ROWS, net.S, 3 + 6 * net.multires, 0);
     long long svi = 0;
     if (tid < ROWS) {
         float* p = lds.pts + tid * 3;
@@ -536,7 +537,7 @@ __device__ void mv_eval_rows(const NET& net, const MvTraceParams& tp, const Samp
         } else { p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; }
     }
     __syncthreads();
-    mv_eval_dispatch<MT, NTW, NW>(net, (nr + 15) >> 4, lds.act, lds.pe, lds.pts, lds.sdfv, tid);
+    mv_eval_dispatch<MT, NTW, NW, NET, SPHERE>(net, (nr + 15) >> 4, lds.act, lds.pe, lds.pts, lds.sdfv, tid);
     if (tid < nr) c.sv[svi] = lds.sdfv[tid];
 }
 
@@ -767,6 +768,20 @@ __global__ __launch_bounds__(64 * NW) void k_secant_chains(NET net, MvTraceParam
     extern __shared__ __attribute__((aligned(16))) float smem[];
     mv_secant_rays<MT, NTW, NW, NET, true>(net, tp, c, (int)c.counters[MV_CNT_N_SECANT], blockIdx.x, smem);
 }
+// Sample rows of ONE segment in k_sphere_trace's engine form (trace_route.h: mv_rows16_on): for launches with at most about one chunk per compute unit, where a chunk
+// is one dependent evaluation that nothing shares the CU with -- sixteen waves x one column tile over the chunk's two row tiles, ping-pong activation tiles, the weight
+// ring carried across layers.  NOT an instance of k_ray_samples: that kernel's launch bounds ask for NW / 4 workgroups per CU.  Workgroup b takes the chunks b,
+// b + gridDim.x, ...: a static stride, no claim and no wait, so a list longer than the grid costs a second trip.  Same instruction sequence per output column as
+// k_ray_samples<2, 2, 8>, rows independent of their chunk: same bits.  (A trip's last read of the value tile and the next trip's first write of the point tile are
+// separated by the barriers of the evaluation in between, as between two rounds of k_sphere_trace.)
+template <int MT, int NTW, int NW, class NET>
+__global__ __launch_bounds__(64 * NW) void k_row_chunks(NET net, MvTraceParams tp, SampleCtx c, RowSeg sg) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int n_list = (int)c.counters[sg.cnt_index];
+    const long long total = (long long)n_list * sg.ni, stride = (long long)gridDim.x * (16 * MT);
+    for (long long q0 = (long long)blockIdx.x * (16 * MT); q0 < total; q0 += stride)
+        mv_eval_rows<MT, NTW, NW, NET, true>(net, tp, c, sg, q0, smem, n_list);
+}
 // ---------------------------------------------------------------------------------------------------------------
 // the tracer's switches (trace_route.h), read once per process; the development ones only by a library built with them (capi_util.h::mv_dev_env)
 const MvTraceSwitches& mv_trace_switches() {
@@ -791,6 +806,7 @@ struct TraceCall {
     int engine, R, P, training;
     bool tail, no_tail;                                            // no_tail: the caller keeps the min-sdf rows out of this forward (stage flag 0x200)
     int cut_rounds; bool resume;                                   // the sphere cut: round limit of the sphere launch (0: none); stage flag 0x400: the sphere launch resumes the spilled rays
+    int rows16, rows16_cap;                                        // mvsdf_trace_rows_stage: the sixteen-wave rows form (k_row_chunks) for the first sampler window / the late list's rows; its grid cap (<= 0: the compute units)
     const MvTraceParams* tp;
     const float *cam_loc, *dirs, *intervals, *steps;
     const uint8_t* om;
@@ -826,6 +842,24 @@ static hipError_t launch_stage1(const NET& net, const TraceCall& t) {
     return hipGetLastError();
 }
 
+// the sixteen-wave rows form exists where the route's sample-row instance is <2, 2, 8> of the three-weight-term engine (trace_route.h: mv_rows16_on is the rule for using it)
+template <int MT, int NTW, int NW, class NET> struct mv_has_rows16 { static constexpr bool v = MV_SPHERE_NW16 != 0 && mv_net_wt<NET>::v == 3 && MT == 2 && NTW == 2 && NW == 8; };
+// one segment's rows as k_row_chunks<2, 1, 16> (grid: trace_route.h::mv_rows16_grid; LDS: mv_rows16_lds_bytes = the sphere kernel's formula)
+template <class NET>
+static hipError_t launch_rows16(const NET& net, const TraceCall& t, const SampleCtx& c, const RowSeg& sg) {
+    static_assert(mv_act_rows<NET>(32, true) == 64, "mv_rows16_lds_bytes assumes the second pair of activation tiles");
+    const size_t lds = mv_rows16_lds_bytes(net.S, net.multires);
+    static size_t set = 0;
+    if (lds > set) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_row_chunks<2, 1, 16, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        set = lds;
+    }
+    const int grid = mv_rows16_grid(t.R, sg.ni, mv_cu_count(), t.rows16_cap);
+    hipLaunchKernelGGL((k_row_chunks<2, 1, 16, NET>), dim3(grid), dim3(1024), lds, t.stream, net, *t.tp, c, sg);
+    return hipGetLastError();
+}
+
 // part 1: sampler rows + their reduction (the hit mask is FINAL after it); 2: secant + min-sdf rows in one launch; 4: min-sdf rows + their reduction alone (own
 // sample-value buffer: may run concurrently with part 1 on another stream); 8: secant alone
 template <int MT, int NTW, int NW, class NET>
@@ -852,6 +886,10 @@ static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
     if (part == 1) {
         // sampler rays: first window of nf samples, then the other samples of the rays the window left open
         const RowSeg first = {w_list, nullptr, (int)MV_CNT_N_SAMPLER, 0, nf, g.first, 0};
+        if (t.rows16 & 1) {                                         // the first window in the sixteen-wave form (the rest keeps this instance)
+            if constexpr (mv_has_rows16<MT, NTW, NW, NET>::v) { const hipError_t e = launch_rows16(net, t, c, first); if (e != hipSuccess) return e; }
+            else return hipErrorInvalidValue;
+        } else
         hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(g.first), wg, lds2, t.stream, net, tp, c, first, none, 0);
         hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, w_list, (const int*)nullptr, (int)MV_CNT_N_SAMPLER, 0);
         if (nf < n) {
@@ -867,6 +905,10 @@ static hipError_t launch_stage2(const NET& net, const TraceCall& t, int part) {
         c.sv = mv_ws_at<float>(t.ws, cw.sv_late); c.n_first = n;
         const int blocks = mv_row_blocks(t.R, n, MT);
         const RowSeg all = {list_late, nullptr, (int)MV_CNT_N_SAMPLER_LATE, 0, n, blocks, 0};
+        if (t.rows16 & 2) {
+            if constexpr (mv_has_rows16<MT, NTW, NW, NET>::v) { const hipError_t e = launch_rows16(net, t, c, all); if (e != hipSuccess) return e; }
+            else return hipErrorInvalidValue;
+        } else
         hipLaunchKernelGGL((k_ray_samples<MT, NTW, NW, NET>), dim3(blocks), wg, lds2, t.stream, net, tp, c, all, none, 0);
         hipLaunchKernelGGL(k_reduce_items, dim3(g.red), red_wg, 0, t.stream, tp, c, list_late, (const int*)nullptr, (int)MV_CNT_N_SAMPLER_LATE, 0);
     } else if (part == 8) {
@@ -1190,7 +1232,7 @@ size_t mvsdf_trace_workspace_bytes(int R) { return mvsdf_trace_workspace_bytes_n
 static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
                       const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps,
                       float* points, uint8_t* mask, float* dists, unsigned long long* counters, void* workspace,
-                      size_t workspace_bytes, int mt, int mt_samples, void* stream, int cut_rounds = 0) {
+                      size_t workspace_bytes, int mt, int mt_samples, void* stream, int cut_rounds = 0, int rows16 = 0, int rows16_cap = 0) {
     const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, false);
     if (ec.rc) return mv_fail(ec.rc, ec.why);
     return mv_with_trace_net(desc, ec.engine, [&](const auto& net) {
@@ -1209,7 +1251,7 @@ static int trace_impl(int stages, const MvsdfNetDesc* desc, const MvsdfTracePara
         if ((stages & 1) && !(stages & 0x500)) e = hipMemsetAsync(counters, 0, 16 * sizeof(unsigned long long), s);   // 0x100: the caller's previous launch zeroed them; 0x400: the resume launch of the sphere cut goes on counting
         if (e != hipSuccess) return mv_check(e, "mvsdf_trace: memset");
         // 0x200: no tail filling in this call -- the caller keeps the min-sdf rows out of its forward (k_sphere_trace still writes their work list and ranges)
-        const TraceCall t = {ec.engine, R, P, training, false, (stages & 0x200) != 0, cut_rounds, (stages & 0x400) != 0, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
+        const TraceCall t = {ec.engine, R, P, training, false, (stages & 0x200) != 0, cut_rounds, (stages & 0x400) != 0, rows16, rows16_cap, tp, cam_loc, ray_dirs, intervals, minsdf_steps ? minsdf_steps : intervals, object_mask,
                              points, dists, mask, workspace, counters, s};
         return mv_check(mv_trace_launch(stages, net, t, mt, mt_samples), "mvsdf_trace");
     });
@@ -1272,6 +1314,35 @@ int mvsdf_trace_cut_stage(int stage, int max_rounds, const MvsdfNetDesc* desc, c
                           float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
     return mv_trace_cut_stage(stage, max_rounds, 0, desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
                               workspace, workspace_bytes, mt, mt_samples, stream);
+}
+static int mv_desc_maxnt(const MvsdfNetDesc* desc) {                // (capi_util.h::mv_hidden_nt)
+    int maxnt = 0;
+    for (int l = 0; l + 1 < desc->n_layers && l < MVSDF_MAX_LAYERS; ++l) { const int nt = (desc->N[l] + 15) / 16; maxnt = nt > maxnt ? nt : maxnt; }
+    return maxnt;
+}
+// whether the sixteen-wave rows form exists for this network: the route's sample-row instance of part 1 is <2, 2, 8> of the three-weight-term engine
+int mv_trace_rows16_has(const MvsdfNetDesc* desc, int mt_samples) {
+    const MvEngineClass ec = mv_trace_engine(desc ? desc->trace_dtype : 0, false);
+    if (ec.rc || !desc || MV_SPHERE_NW16 == 0 || ec.engine != MV_ENG_X3) return 0;
+    const MvInst r = mv_route_samples(ec.engine, mv_desc_maxnt(desc), mt_samples, 1, 1, mv_trace_switches());
+    return (r.rc == 0 && r.mt == 2 && r.ntw == 2 && r.nw == 8) ? 1 : 0;
+}
+// the rule of trace_route.h::mv_rows16_on for a network and ray count on the current device, where the form exists
+int mv_trace_rows16_pays(const MvsdfNetDesc* desc, int R, int mt, int mt_samples) {
+    if (!mv_trace_rows16_has(desc, mt_samples)) return 0;
+    const int maxnt = mv_desc_maxnt(desc);
+    const MvInst s1 = mv_route_sphere(MV_ENG_X3, maxnt, mt);
+    return (s1.rc == 0 && mv_rows16_on(MV_ENG_X3, maxnt, R, s1.mt, mv_cu_count())) ? 1 : 0;
+}
+// The sampler windows of the first list (part 1 = mvsdf_trace_stage 3) or the late list's rows + their reduction (part 2 = mvsdf_trace_cut_stage 3) with the sample rows
+// of the first window / the late list in the sixteen-wave form (rows16 != 0; grid_cap > 0: at most that many workgroups) or exactly as those stages launch them (0)
+int mvsdf_trace_rows_stage(int part, int rows16, int grid_cap, const MvsdfNetDesc* desc, const MvsdfTraceParams* tp, const float* cam_loc, const float* ray_dirs,
+                           const uint8_t* object_mask, int B, int P, int training, const float* intervals, const float* minsdf_steps, float* points, uint8_t* mask,
+                           float* dists, unsigned long long* counters, void* workspace, size_t workspace_bytes, int mt, int mt_samples, void* stream) {
+    if (part != 1 && part != 2) return mv_fail(-1, "mvsdf_trace_rows_stage: part must be 1 (the sampler windows) or 2 (the late list)");
+    if (rows16 && !mv_trace_rows16_has(desc, mt_samples)) return mv_fail(-3, "mvsdf_trace_rows_stage: no sixteen-wave rows form for this network / mt_samples (mv_trace_rows16_has)");
+    return trace_impl(part == 1 ? 2 : (64 | 0x200), desc, tp, cam_loc, ray_dirs, object_mask, B, P, training, intervals, minsdf_steps, points, mask, dists, counters,
+                      workspace, workspace_bytes, mt, mt_samples, stream, 0, rows16 ? part : 0, grid_cap);
 }
 // the rule of trace_route.h::mv_sphere_cut_on for a network and ray count on the current device (the step driver asks once per step object)
 int mv_trace_cut_pays(const MvsdfNetDesc* desc, int R, int mt) {

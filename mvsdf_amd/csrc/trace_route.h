@@ -179,4 +179,21 @@ inline MvTraceCutWs mv_trace_cut_ws(int R, int n_steps) {
     const size_t r = 4 * (size_t)(R > 0 ? R : 0), n = n_steps > 0 ? n_steps : 0, b = (mv_trace_ws(R, n_steps).total + 255) & ~(size_t)255;
     return {b, b + 16 * r, b + 17 * r, b + (17 + n) * r + 256};
 }
+// ---- the sixteen-wave rows form (trace.hip: k_row_chunks<2, 1, 16>) ----
+// Sample rows of a launch with at most about one 32-row chunk per compute unit are ONE dependent evaluation that nothing shares the CU with: a latency launch, like a
+// round of k_sphere_trace.  Such a launch takes that kernel's shape -- sixteen waves x one column tile, ping-pong tiles, the weight ring carried across layers -- over the
+// two row tiles of mv_route_samples' <2, 2, 8> instance.  Only the step's sphere-cut sequence has such launches (the late list's rows, the first sampler window), and the
+// form exists for the three-weight-term engine up to hidden width 256: the rule is the cut's rule and the width.  The step consults it; mv_route_samples keeps its answers.
+inline bool mv_rows16_on(int engine, int maxnt, int R, int mt1, int cus) { return mv_sphere_cut_on(engine, R, mt1, cus) && maxnt <= 16; }
+// which of its two uses the rule turns on (bit 0: the first sampler window, bit 1: the late list's rows): each by its own A/B at c2 (profiles/fork_ab.txt, medians of
+// three against the fork switched off, 1.2940 ms).  The late rows: 1.2820, every run faster -- on.  The first window: 1.2968, every run SLOWER -- off (the windows' own event slot
+// falls, 0.4415 -> 0.4228 ms, and the step still loses: the window shares the chip with the resume launch, whose rounds are the critical path; not looked into further).
+inline int mv_rows16_uses() { return 2; }
+// its grid: worst-case chunks of 32 rows, at most one workgroup per compute unit (cap > 0: at most cap); workgroup b takes the chunks b, b + grid, ... -- a static stride
+inline int mv_rows16_grid(int R, int per_item, int cus, int cap) {
+    const int chunks = mv_row_blocks(R, per_item, 2), lim = cap > 0 ? cap : (cus > 0 ? cus : 1);
+    return chunks < lim ? chunks : lim;
+}
+// its dynamic LDS: the sphere kernel's formula for two row tiles with the second pair of activation tiles (trace.hip: mv_act_rows<NET>(32, true) = 64 rows)
+inline size_t mv_rows16_lds_bytes(int S, int multires) { return mv_trace_lds_bytes(S, multires, 2, 64); }
 template <class T> inline T* mv_ws_at(void* ws, size_t offset) { return (T*)((char*)ws + offset); }

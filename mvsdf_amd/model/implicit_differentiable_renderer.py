@@ -365,6 +365,11 @@ class IDRNetwork(nn.Module):
         # 2: always.  sphere_cut_rounds > 0: another round limit (development: a small one makes small batches spill).
         self.sphere_cut = {'0': False, '': False, '2': 2}.get(os.environ.get('MVSDF_SPHERE_CUT', '1'), True)
         self.sphere_cut_rounds = 0
+        # The fork of a forward with the cut (mvsdf_step_set_fork; same values): (late branch on the launch stream, ray partition beside the secant chains, sixteen-wave
+        # rows form, its grid cap), each -1: by its rule, 0: the launch sequence without it, 1: on wherever the cut is on.  MVSDF_FORK=0: all three off;
+        # MVSDF_FORK=a,b,c: the three parts as given (A/B runs of one part: profiles/fork_ab.txt).
+        e = os.environ.get('MVSDF_FORK', '1')
+        self.fork = (tuple(int(v) for v in e.split(',')) + (0,))[:4] if e.count(',') == 2 else ((0, 0, 0, 0) if e in ('', '0') else (-1, -1, -1, 0))
         self._steps = {}                                         # NativeStep per batch shape / phase configuration
         self._ones = None                                        # all-ones object mask handed to the tracer when conf.use_mask is off
 
@@ -662,7 +667,8 @@ class IDRNetwork(nn.Module):
         rec.inputs_keep = keep                                   # the inputs stay alive as long as the step's record does
         rec.eager_unhit = bool(self.eager_unhit_rows) or not st.can_defer_unhit
         st.set_sphere_cut(self.sphere_cut, self.sphere_cut_rounds)
-        NS.enqueue_forward(rec)                                  # everything of this forward is on the stream now; nothing waited for
+        st.set_fork(*self.fork)
+        NS.enqueue_forward(rec)                                 # everything of this forward is on the stream now; nothing waited for
         if stage_slot is not None:                               # the pinned draws may be rewritten once this forward's first kernel has read them
             stage_slot[2] = (st, rec.seq)
         L, f = st.layout, rec.fwd

@@ -137,6 +137,7 @@ class NativeStep:
         self.counts_off = int(L.mvsdf_step_counts_offset(h))      # int64 counts[4] inside a forward block
         self.can_defer_unhit = bool(L.mvsdf_step_can_defer_unhit(h))   # the rows of the rays without a hit can wait until `points` / `sdf_output` are read
         self._cut = (1, 0)                                        # (sphere_cut, max_rounds) as last handed to mvsdf_step_set_sphere_cut (its default)
+        self._fork = (-1, -1, -1, 0)                              # ... to mvsdf_step_set_fork (its default)
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -204,6 +205,13 @@ class NativeStep:
         if key != self._cut:
             check(lib().mvsdf_step_set_sphere_cut(self._h, {0: 0, 1: -1}.get(key[0], 1), key[1]), 'mvsdf_step_set_sphere_cut')
             self._cut = key
+
+    def set_fork(self, late_on_main=-1, partition_beside_secant=-1, rows16=-1, rows16_grid_cap=0):
+        """mvsdf_step_set_fork for the forwards that follow (each part -1: by its rule, 0: the launch sequence without it, 1: on wherever the cut is on)."""
+        key = (int(late_on_main), int(partition_beside_secant), int(rows16), int(rows16_grid_cap))
+        if key != self._fork:
+            check(lib().mvsdf_step_set_fork(self._h, *key), 'mvsdf_step_set_fork')
+            self._fork = key
 
     def resolve_unhit(self, fwd):
         """mvsdf_step_resolve_unhit: min-sdf rows, evaluation rows and sdf_output of the rays without a hit, from the forward block alone (once per block)."""
