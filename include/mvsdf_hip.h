@@ -1004,6 +1004,44 @@ typedef struct {
 size_t mvsdf_batch_args_bytes(void);     /* sizeof(MvsdfBatchArgs) as compiled: the binding checks its mirror against it */
 int mvsdf_batch_gather(const MvsdfBatchArgs* a, void* stream);
 
+/* ---- Registration and F-score evaluation (registration.hip; Python: mvsdf_amd/registration.py, which states the definitions) ----
+ * Points are fp64 [n][3] on the device; fp64 throughout, no contraction, every sum in a written order.  Error bits are the Chamfer calls':
+ * 4 a non-finite coordinate, 8 a voxel index of 2^21 or more, 64 a tree-walk bound.
+ * The kept tree: mvsdf_reg_tree_build sorts refs [nr][3] by Morton code and builds the box tree once, inside the workspace
+ * (mvsdf_reg_tree_workspace_bytes; 0 unless 1 <= nr <= INT32_MAX).  It waits for the stream once (the coordinate check) and leaves int64 {error bits,
+ * the centre of the references' box (3 fp64 as bits)} at the start of the workspace, which IS the tree from then on: keep it, pass it as `tree`.
+ * mvsdf_reg_tree_query (no host wait): per query q (first moved by transform, HOST fp64 [16] row-major or NULL, row a =
+ * ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3]) the minimum of (dx dx + dy dy) + dz dz over the references and the smallest input index that
+ * attains it: index int32 [nq], d2 (the minimum) and dist (its sqrt), each fp64 [nq] or NULL.  Where sqrt(d2) is not < max_dist (> 0, may be
+ * +inf): dist = d2 = +inf, index = -1.  Error bits are ORed into the device word *err (the caller zeroes it), with them nothing else is valid.
+ * mvsdf_reg_icp_step: that query of src under transform, then the 17 sums of one ICP iteration over the matched pairs in source order (a lane sums
+ * 8 consecutive items from 0, a 256-lane halving tree, block partials, a 1024-lane final): with c the tree's centre, p = T src - c and
+ * q = refs[index] - c (refs: the array the tree was built from).  Waits for the stream -> int64 {n, then as fp64 bits: sum d2, sum p [3], sum q [3],
+ * sum p_a q_b [9] (a major), error bits} at the start of the workspace (mvsdf_reg_pairs_workspace_bytes(ns), ns >= 1). */
+size_t mvsdf_reg_tree_workspace_bytes(int64_t nr);
+int mvsdf_reg_tree_build(const double* refs, int64_t nr, void* ws, size_t ws_bytes, void* stream);
+int mvsdf_reg_tree_query(const void* tree, size_t tree_bytes, int64_t nr, const double* queries, int64_t nq, const double* transform, double max_dist,
+                         double* dist, double* d2, int32_t* index, int32_t* err, void* stream);
+size_t mvsdf_reg_pairs_workspace_bytes(int64_t ns);
+int mvsdf_reg_icp_step(const void* tree, size_t tree_bytes, int64_t nr, const double* refs, const double* src, int64_t ns, const double* transform,
+                       double max_dist, void* ws, size_t ws_bytes, double* d2, int32_t* index, void* stream);
+/* No host wait in any of these.  mvsdf_reg_transform: out = the points under transform (HOST fp64 [16], as above); out may be pts.
+ * mvsdf_reg_crop: keep uint8 [n] and out (capacity n rows, input order) = the points inside the prism whose axis is `axis` (0 X, 1 Y, 2 Z) between
+ * axis_min and axis_max (inclusive) and whose section is the polygon fp64 [nverts][3] on the DEVICE, 3 <= nverts <= 4096, by the crossing rule
+ * registration.py writes out -> int64 {rows kept}.  Workspace: mvsdf_reg_crop_workspace_bytes(n), n >= 1.
+ * mvsdf_reg_voxel: the voxel filter at edge `voxel` (finite, > 0): origin o = min - voxel / 2 per axis, cell g = floor((p - o) / voxel), key
+ * gx | gy << 21 | gz << 42; means (capacity n rows) = per occupied voxel in ascending key the sum of its points in ascending input index from 0,
+ * divided by their count; counts int32 -> int64 {voxels, error bits}.  Workspace: mvsdf_reg_voxel_workspace_bytes(n), 1 <= n <= INT32_MAX.
+ * mvsdf_reg_hist: out int64 [1 + nedges - 1] on the device = {the distances < tau, then the histogram: the bin of d is the number of edges[1..]
+ * that are <= d, a d at or beyond the last edge is dropped}; edges fp64 [nedges] ascending on the DEVICE, 2 <= nedges <= 4097; n >= 0. */
+int mvsdf_reg_transform(const double* pts, int64_t n, const double* transform, double* out, void* stream);
+size_t mvsdf_reg_crop_workspace_bytes(int64_t n);
+int mvsdf_reg_crop(const double* pts, int64_t n, int32_t axis, double axis_min, double axis_max, const double* polygon, int32_t nverts, void* ws,
+                   size_t ws_bytes, uint8_t* keep, double* out, void* stream);
+size_t mvsdf_reg_voxel_workspace_bytes(int64_t n);
+int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t ws_bytes, double* means, int32_t* counts, void* stream);
+int mvsdf_reg_hist(const double* dist, int64_t n, const double* edges, int32_t nedges, double tau, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
