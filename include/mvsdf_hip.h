@@ -1042,6 +1042,31 @@ size_t mvsdf_reg_voxel_workspace_bytes(int64_t n);
 int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t ws_bytes, double* means, int32_t* counts, void* stream);
 int mvsdf_reg_hist(const double* dist, int64_t n, const double* edges, int32_t nedges, double tau, int64_t* out, void* stream);
 
+/* ---- Normals of unoriented clouds (normals.hip; Python: mvsdf_amd/normals.py, which states the definition) ----
+ * pts fp64 [n][3] on the device, fp64 throughout.  Error bits: 4 a non-finite coordinate (or view centre), 32 the round limit, 64 a tree-walk bound,
+ * 128 a non-finite normal, 256 a neighbour index outside [0, n); with any set nothing else is valid.  Every argument is validated before the first
+ * launch.
+ * mvsdf_normals_knn: idx int32 [n][k] = per point the k other points (by index) smallest under (d2, index), d2 = (dx dx + dy dy) + dz dz, ascending;
+ * d2 fp64 [n][k] (may be NULL) their squared distances.  normals fp64 [n][3] and variation fp64 [n] (both or neither NULL): the eigenvector of the
+ * smallest eigenvalue of each neighbourhood's covariance by cyclic Jacobi, in its canonical sign, and l_min / (l_0 + l_1 + l_2).  1 <= k <= 32,
+ * k + 1 <= n <= INT32_MAX.  Workspace: mvsdf_normals_knn_workspace_bytes(n) (0 unless 2 <= n <= INT32_MAX) -> int64 {error bits}; waits for the
+ * stream once for the coordinate check.
+ * mvsdf_normals_orient: out fp64 [n][3] (not normals itself) = the normals with their signs made consistent along the spanning forest of largest
+ * |n_i . n_j| over the edges of neighbors int32 [n][k], each component signed by (ux, uy, uz) at its highest point or, with centers fp64 [V][3] and
+ * bits uint64 [n][ceil(V / 64)] (mvsdf_viewsel_pack_*; both or neither NULL, 1 <= V <= 65535), by the votes of the views that see its points;
+ * labels int32 [n] = the smallest index of each point's component.  Workspace: mvsdf_normals_orient_workspace_bytes(n) (0 unless
+ * 1 <= n <= INT32_MAX) -> int64 {n_components, rounds, error bits}; waits for the stream once per round.
+ * mvsdf_normals_to_views (no host wait): out = each normal, negated iff more of the views that see its point have n . (c - p) < 0 than > 0 ->
+ * hdr (256 bytes on the device): int64 {error bits}. */
+size_t mvsdf_normals_knn_workspace_bytes(int64_t n);
+size_t mvsdf_normals_orient_workspace_bytes(int64_t n);
+int mvsdf_normals_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t ws_bytes, int32_t* idx, double* d2, double* normals, double* variation,
+                      void* stream);
+int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t* neighbors, int64_t n, int32_t k, double ux, double uy, double uz,
+                         const double* centers, const void* bits, int64_t V, void* ws, size_t ws_bytes, double* out, int32_t* labels, void* stream);
+int mvsdf_normals_to_views(const double* pts, const double* normals, int64_t n, const double* centers, const void* bits, int64_t V, double* out, void* hdr,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,11 +3,14 @@
 tools/eval_dtu.py scores the result.
 
     python tools/poisson_mesh.py IN.ply OUT.(ply|obj) [--depth 8] [--cycles 8] [--scale 1.1] [--no_trim] [--min_density D] [--dilate K] [--largest]
+                                 [--estimate_normals [K]]
     python tools/poisson_mesh.py --data DIR OUT.(ply|obj) [--pair DIR/pair.txt] [--normal_jump 0.05] [fuse_depths' options] ...
 
 IN.ply: a binary PLY point cloud with nx ny nz (tools/fusion.py --normals writes one; tools/clean_points.py keeps them).  --data DIR fuses DIR's
 Vis-MVSNet depth maps with normals=True (tools/fusion.py's inputs and options) and reconstructs in one command.  The grid is a cube of 2^depth cells
-per axis, --scale times the cloud's longest box edge, centred on the box.  Prints points used and outside, residual / residual0, the isovalue and the
+per axis, --scale times the cloud's longest box edge, centred on the box.  --estimate_normals [K]: an IN.ply without nx ny nz gets normals from its K
+(default 16) nearest neighbours and the spanning-tree orientation (mvsdf_amd/normals.py: estimate_normals + orient_normals, up = +z) instead of the
+exit (give the flag after the paths, or as --estimate_normals=K); tools/estimate_normals.py has the other orientations.  Prints points used and outside, residual / residual0, the isovalue and the
 face count.
 """
 import argparse
@@ -30,6 +33,8 @@ def parse_args(argv=None):
     ap.add_argument('--min_density', type=float, default=0.0)
     ap.add_argument('--dilate', type=int, default=1)
     ap.add_argument('--largest', action='store_true', default=False, help='keep the largest connected component')
+    ap.add_argument('--estimate_normals', type=int, nargs='?', const=16, default=None, metavar='K',
+                    help='IN.ply without nx ny nz: estimate them from K neighbours (default 16) and orient them')
     ap.add_argument('--pair', type=str, default=None, help='--data: default DATA/pair.txt')
     ap.add_argument('--normal_jump', type=float, default=0.05)
     ap.add_argument('--view', type=int, default=10, help='--data: fuse_depths\' sources per view')
@@ -47,6 +52,8 @@ def parse_args(argv=None):
         ap.error('OUT must not be IN.ply')
     if not 2 <= a.depth <= 10:
         ap.error('--depth must be in 2 .. 10')
+    if a.estimate_normals is not None and not 1 <= a.estimate_normals <= 32:
+        ap.error('--estimate_normals K must be in 1 .. 32')
     if a.cycles < 0 or a.sweeps < 1 or a.dilate < 0:
         ap.error('--cycles must be >= 0, --sweeps >= 1, --dilate >= 0')
     if not a.scale >= 1 or a.scale == float('inf'):
@@ -68,6 +75,12 @@ def main(argv=None):
         points, normals = fused.points, fused.normals
     else:
         points, normals = chamfer.load_oriented_points(a.input)
+        if normals is None and a.estimate_normals is not None and len(points) > a.estimate_normals:
+            from mvsdf_amd import normals as nrm
+            est, _, neighbors = nrm.estimate_normals(points, a.estimate_normals)
+            o = nrm.orient_normals(points, est, neighbors)
+            normals = o.normals
+            print('normals: estimated from %d neighbours, %d components oriented in %d rounds' % (a.estimate_normals, o.n_components, o.rounds))
         if normals is None:
             sys.exit('poisson_mesh: %s has no nx / ny / nz (tools/fusion.py --normals writes them)' % a.input)
     if len(points) == 0:
