@@ -8,11 +8,11 @@
 //   independent set under the keys splitmix64(seed ^ i): synchronous rounds (states ping-pong) keep a point once every lower-key neighbour is
 //   removed and remove it once one is kept.  The lowest undecided key is decided in every round, so N rounds always suffice.
 // * Masks: flags, int64 scans and an order-preserving scatter.
-// * Nearest distance (the sort and the tree live in nn_tree.h, shared with cloud.hip): the references are sorted by a 63-bit Morton code
-//   (stable LSD radix sort, 4 bits per pass), cut into leaves of CH_LEAF consecutive points, and an implicit 8-ary tree of fp64 boxes is built
-//   over the leaves.  A query descends greedily to one leaf for a first bound, then walks the tree without a stack, pruning a box only when its
-//   lower bound exceeds min(best, max_dist)^2 by a relative 4e-9.  The minimum squared distance is exact (every point not pruned is compared
-//   with the metric's formula) and sqrt is monotonic, so the result is sqrt(min d^2) bit for bit.  A query with nothing within max_dist only
+// * Nearest distance (the sort, the tree and its traversals live in nn_tree.h, shared with the other point-cloud files): the references are sorted
+//   by a 63-bit Morton code (stable LSD radix sort, 4 bits per pass), cut into leaves of CH_LEAF consecutive points, and an implicit 8-ary tree of
+//   fp64 boxes is built over the leaves.  A query descends greedily to one leaf for a first bound (ch_descend), then walks the tree without a stack
+//   (ch_walk), pruning a box only when its lower bound exceeds min(best, max_dist)^2 by a relative 4e-9.  The minimum squared distance is exact
+//   (every point not pruned is compared with the metric's formula) and sqrt is monotonic, so the result is sqrt(min d^2) bit for bit.  A query with nothing within max_dist only
 //   meets boxes farther than the cut-off, which stops it near the root.
 // * Sums: fixed-order block reductions in fp64, no float atomics.
 //
@@ -371,47 +371,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_nn_query(const double* __restric
     }
     const double cut2 = max_dist * max_dist;
     double best = INFINITY;
-    // a first bound: follow the nearest child from the root to one leaf
-    {
-        long long i = 0;
-        for (int k = T.top; k > 0; --k) {
-            const long long b = i * CH_ARITY, e = min(T.cnt[k - 1], b + CH_ARITY);
-            long long pick = b;
-            double lbest = INFINITY;
-            for (long long c = b; c < e; ++c) {
-                const double lb = ch_box_lb2(box + (T.off[k - 1] + c) * 6, x, y, z);
-                if (lb < lbest) {
-                    lbest = lb;
-                    pick = c;
-                }
-            }
-            i = pick;
-        }
-        if (ch_box_lb2(box + i * 6, x, y, z) <= cut2 * CH_MARGIN2) best = ch_leaf_min(sp, T.n, i, x, y, z, best);
-    }
-    // the full walk: depth first over the implicit tree, children in index order, no stack (parent = i / 8, next sibling = i + 1)
-    int k = T.top;
-    long long i = 0;
-    const long long max_steps = 2 * T.nodes + 4;
-    long long step = 0;
-    for (; step < max_steps; ++step) {
-        const double bound = fmin(best, cut2) * CH_MARGIN2;
-        if (ch_box_lb2(box + (T.off[k] + i) * 6, x, y, z) <= bound) {
-            if (k > 0) {
-                --k;
-                i *= CH_ARITY;
-                continue;
-            }
-            best = ch_leaf_min(sp, T.n, i, x, y, z, best);
-        }
-        while (k < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[k])) {
-            i /= CH_ARITY;
-            ++k;
-        }
-        if (k == T.top) break;
-        ++i;
-    }
-    if (step >= max_steps) atomicOr(err, CH_ERR_WALK);
+    const long long first = ch_descend<false>(box, T, x, y, z);   // a first bound from one leaf, then the full walk
+    if (ch_box_lb2(box + first * 6, x, y, z) <= cut2 * CH_MARGIN2) best = ch_leaf_min(sp, T.n, first, x, y, z, best);
+    if (!ch_walk(
+            box, T, x, y, z, [&] { return fmin(best, cut2) * CH_MARGIN2; }, [&](long long l) { best = ch_leaf_min(sp, T.n, l, x, y, z, best); }))
+        atomicOr(err, CH_ERR_WALK);
     const double d = sqrt(best);
     dist[qi] = d < max_dist ? d : INFINITY;
 }
@@ -669,13 +633,10 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
     long long hdr[3] = {0, 0, 0};                                 // distances below the cut-off, their fp64 sum (bits), error bits
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_nearest"))) return rc;
-    ch_tree_frame(refs, (long long)nr, w, L.t, fl, s);
-    if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
-    int e = 0;
-    if ((rc = mv_read(&e, fl, 4, s, "mvsdf_chamfer_nearest"))) return rc;
-    hdr[2] = e;
-    if (!e) {
-        ch_tree_build(refs, (long long)nr, w, L.t, s);
+    const ChBuilt tree = ch_tree_begin(refs, (long long)nr, w, L.t, fl, s, "mvsdf_chamfer_nearest");
+    if (tree.rc) return tree.rc;
+    hdr[2] = tree.err;
+    if (!tree.err) {
         const double* sp = (const double*)(w + L.t.sp);
         const double* box = (const double*)(w + L.t.box);
         const ChTree& T = L.t.T;

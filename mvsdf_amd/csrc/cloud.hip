@@ -2,13 +2,13 @@
 // test on it, fixed-radius connected components over the points that pass and an order-preserving compaction.  Python: mvsdf_amd/cloud.py, which
 // states the definition; tests/cloud_ref.py restates it in numpy.  All arithmetic is fp64 without contraction, in the order the definition writes it.
 //
-// * Tree: the Morton-sorted points and the implicit 8-ary box tree of nn_tree.h (shared with chamfer.hip), built over the cloud itself.
+// * Tree: the Morton-sorted points and the implicit 8-ary box tree of nn_tree.h, built over the cloud itself, and that header's traversals.
 // * k_cl_knn: one lane per point, lanes in Morton order (lane t of workgroup b owns sorted point b * 256 + t), so a wave walks nearly the same
 //   boxes.  The lane keeps its k smallest squared distances as a sorted list of CAP registers (CAP = 8 / 16 / 24 / 32, a template argument; the CAP - k
 //   slots in front hold -1, below every distance, so the k-th smallest is always the last register and no index is computed at run time).  The list
-//   is seeded from the point's own leaf and the two beside it, then the tree is walked without a stack; a box is pruned when its lower bound exceeds
-//   the k-th smallest by the relative CH_MARGIN2, every other point is compared with the metric's formula.  The k smallest values are a multiset
-//   and sqrt is correctly rounded, so d has one possible bit pattern.
+//   goes through ch_knn_lane: seeded from the point's own leaf and the two beside it, then the tree is walked without a stack; a box is pruned when
+//   its lower bound exceeds the k-th smallest by the relative CH_MARGIN2, every other point is compared with the metric's formula.  The k smallest
+//   values are a multiset and sqrt is correctly rounded, so d has one possible bit pattern.
 // * Median: the bit patterns of d (non-negative doubles order as their bits) through the 64-bit radix sort; one lane reads rank (N - 1) / 2 and
 //   forms threshold = knn_ratio * m, eps = eps_ratio * m, eps * eps on the device.
 // * Components: a union-find forest over sorted positions in a 32-bit parent word.  Every passed point walks the tree with the fixed bound
@@ -45,15 +45,15 @@ __device__ __forceinline__ void cl_insert(double (&best)[CAP], double v) {
     best[0] = v < best[0] ? v : best[0];
 }
 
+// ch_knn_lane's list: the k smallest squared distances, a multiset
 template <int CAP>
-__device__ __forceinline__ void cl_leaf_knn(const double* __restrict__ sp, long long b, long long e, long long self, double x, double y, double z,
-                                            double (&best)[CAP]) {
-    for (long long q = b; q < e; ++q) {
-        if (q == self) continue;
-        const double v = ch_d2(x, y, z, sp[q * 3], sp[q * 3 + 1], sp[q * 3 + 2]);
+struct ClList {
+    double best[CAP];
+    __device__ __forceinline__ double kth() const { return best[CAP - 1]; }
+    __device__ __forceinline__ void offer(double v, long long) {
         if (v < best[CAP - 1]) cl_insert<CAP>(best, v);
     }
-}
+};
 
 // d[perm[p]] = (sqrt(s_1) + ... + sqrt(s_k)) / k over the k smallest d2 from sorted point p to every other point
 template <int CAP>
@@ -61,39 +61,14 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_knn(const double* __restrict_
                                                         int k, double* __restrict__ d, int* err) {
     const long long p = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
     if (p >= T.n) return;
-    const double x = sp[p * 3], y = sp[p * 3 + 1], z = sp[p * 3 + 2];
-    double best[CAP];
+    ClList<CAP> list;
 #pragma unroll
-    for (int j = 0; j < CAP; ++j) best[j] = j < CAP - k ? -1.0 : INFINITY;
-    // seeds: the point's own leaf and the leaves beside it
-    const long long leaf = p / CH_LEAF, l0 = leaf > 0 ? leaf - 1 : 0, l1 = min(leaf + 1, T.cnt[0] - 1);
-    cl_leaf_knn<CAP>(sp, l0 * CH_LEAF, min(T.n, (l1 + 1) * CH_LEAF), p, x, y, z, best);
-    // the walk of k_nn_query, with the k-th smallest as its bound; the seeded leaves are passed over
-    int lv = T.top;
-    long long i = 0;
-    const long long max_steps = 2 * T.nodes + 4;
-    long long step = 0;
-    for (; step < max_steps; ++step) {
-        if (ch_box_lb2(box + (T.off[lv] + i) * 6, x, y, z) <= best[CAP - 1] * CH_MARGIN2) {
-            if (lv > 0) {
-                --lv;
-                i *= CH_ARITY;
-                continue;
-            }
-            if (i < l0 || i > l1) cl_leaf_knn<CAP>(sp, i * CH_LEAF, min(T.n, (i + 1) * CH_LEAF), -1, x, y, z, best);
-        }
-        while (lv < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[lv])) {
-            i /= CH_ARITY;
-            ++lv;
-        }
-        if (lv == T.top) break;
-        ++i;
-    }
-    if (step >= max_steps) atomicOr(err, CH_ERR_WALK);
+    for (int j = 0; j < CAP; ++j) list.best[j] = j < CAP - k ? -1.0 : INFINITY;
+    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, CH_ERR_WALK);
     double s = 0.0;
 #pragma unroll
     for (int j = 0; j < CAP; ++j)
-        if (j >= CAP - k) s += sqrt(best[j]);
+        if (j >= CAP - k) s += sqrt(list.best[j]);
     d[perm[p]] = s / (double)k;
 }
 
@@ -180,33 +155,18 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_hook(const double* __restrict
     if (p >= T.n || cl_ld(parent + p) < 0) return;
     const double x = sp[p * 3], y = sp[p * 3 + 1], z = sp[p * 3 + 2];
     const double eps2 = par[3], bound = eps2 * CH_MARGIN2;
-    bool ok = true;
-    int lv = T.top;
-    long long i = 0;
-    const long long max_steps = 2 * T.nodes + 4;
-    long long step = 0;
-    for (; step < max_steps; ++step) {
-        if ((i << (3 * lv)) * CH_LEAF > p) break;                 // this node and every later one hold higher positions only
-        if (ch_box_lb2(box + (T.off[lv] + i) * 6, x, y, z) <= bound) {
-            if (lv > 0) {
-                --lv;
-                i *= CH_ARITY;
-                continue;
+    int bad = 0;                                                  // a union gave up (an or, not `ok = union && ok`: that form compiles 1.4 % slower here)
+    const bool walked = ch_walk(
+        box, T, x, y, z, [=] { return bound; },
+        [&](long long l) {
+            const long long e = min(p, (l + 1) * CH_LEAF);
+            for (long long q = l * CH_LEAF; q < e; ++q) {
+                if (ch_d2(x, y, z, sp[q * 3], sp[q * 3 + 1], sp[q * 3 + 2]) <= eps2 && cl_ld(parent + q) >= 0) bad |= !cl_union(parent, (int)p, (int)q);
             }
-            const long long e = min(p, (i + 1) * CH_LEAF);
-            for (long long q = i * CH_LEAF; q < e; ++q) {
-                if (ch_d2(x, y, z, sp[q * 3], sp[q * 3 + 1], sp[q * 3 + 2]) <= eps2 && cl_ld(parent + q) >= 0) ok = cl_union(parent, (int)p, (int)q) && ok;
-            }
-        }
-        while (lv < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[lv])) {
-            i /= CH_ARITY;
-            ++lv;
-        }
-        if (lv == T.top) break;
-        ++i;
-    }
-    if (step >= max_steps) atomicOr(flags + CL_F_ERR, CH_ERR_WALK);
-    if (!ok) atomicOr(flags + CL_F_PENDING, 1);
+        },
+        p);                                                       // nodes that hold positions above p only end the walk
+    if (!walked) atomicOr(flags + CL_F_ERR, CH_ERR_WALK);
+    if (bad) atomicOr(flags + CL_F_PENDING, 1);
 }
 
 // parent[p] = its root; the root learns the smallest input index and the size of its component.  Neighbours in Morton order mostly share a root
@@ -311,7 +271,7 @@ static bool cl_layout(long long n, ClLayout* L) {
     if (n < 2 || n > INT_MAX) return false;
     WsCursor c{CH_HDR};
     if (!ch_tree_layout(n, c, &L->t)) return false;
-    L->v2 = c.take((size_t)n * 4);  // the median sort carries values nobody reads: v1 and this
+    L->v2 = c.take((size_t)n * 4);  // the median sort carries values nobody reads: the one of v0 / v1 without the permutation and this
     L->parent = c.take((size_t)n * 4);
     L->minidx = c.take((size_t)n * 4);
     L->count = c.take((size_t)n * 4);
@@ -346,14 +306,12 @@ static int cl_begin(const double* pts, long long n, char* w, const ClLayout& L, 
     int rc;
     *done = true;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, CL_F_WORDS * 4, s), what))) return rc;
-    ch_tree_frame(pts, n, w, L.t, fl + CL_F_ERR, s);
-    if ((rc = mv_check(hipGetLastError(), what))) return rc;
-    int e = 0;
-    if ((rc = mv_read(&e, fl, 4, s, what))) return rc;
-    if (e) return cl_fail_header(w, e, s, what);
-    *perm = ch_tree_build(pts, n, w, L.t, s);
+    const ChBuilt tree = ch_tree_begin(pts, n, w, L.t, fl + CL_F_ERR, s, what);
+    if (tree.rc) return tree.rc;
+    if (tree.err) return cl_fail_header(w, tree.err, s, what);
+    *perm = tree.perm;
     *done = false;
-    return mv_check(hipGetLastError(), what);
+    return 0;
 }
 
 static void cl_knn(long long n, int k, char* w, const ClLayout& L, const int* perm, double* d, hipStream_t s) {
@@ -361,14 +319,7 @@ static void cl_knn(long long n, int k, char* w, const ClLayout& L, const int* pe
     const double* box = (const double*)(w + L.t.box);
     int* err = (int*)(w + L.flags) + CL_F_ERR;
     const dim3 g(mv_grid(n, CH_THREADS)), b(CH_THREADS);
-    if (k <= 8)
-        hipLaunchKernelGGL(k_cl_knn<8>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err);
-    else if (k <= 16)
-        hipLaunchKernelGGL(k_cl_knn<16>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err);
-    else if (k <= 24)
-        hipLaunchKernelGGL(k_cl_knn<24>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err);
-    else
-        hipLaunchKernelGGL(k_cl_knn<32>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err);
+    ch_knn_dispatch(k, [&](auto cap) { hipLaunchKernelGGL(k_cl_knn<decltype(cap)::value>, g, b, 0, s, sp, box, L.t.T, perm, k, d, err); });
 }
 
 // stages B (d == NULL: every point passes) and C with par already on the device; leaves the header.  One header read per round.
@@ -464,12 +415,11 @@ int mvsdf_cloud_clean(const double* pts, int64_t n, int32_t k, double knn_ratio,
     int rc = cl_begin(pts, n, w, L, s, what, &perm, &done);
     if (rc || done) return rc;
     cl_knn(n, k, w, L, perm, d, s);
-    // the median: perm lives in v0 (the Morton sort makes an even number of passes), so the sort of d's bits carries v1 / v2 along
+    // the median: perm lives in one of v0 / v1, so the sort of d's bits carries the other and v2 along
     unsigned long long* keys[2] = {(unsigned long long*)(w + L.t.k0), (unsigned long long*)(w + L.t.k1)};
-    int* vals[2] = {(int*)(w + L.t.v1), (int*)(w + L.v2)};
-    if (perm != (const int*)(w + L.t.v0)) return mv_fail(-1, "mvsdf_cloud_clean: the permutation is not where the layout expects it");
+    int* vals[2] = {(int*)(w + (L.t.perm == L.t.v0 ? L.t.v1 : L.t.v0)), (int*)(w + L.v2)};
     hipLaunchKernelGGL(k_cl_keys, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)d, (long long)n, keys[0]);
-    const int cur = ch_radix_sort(keys, vals, n, 64, w, L.t, s);
+    const int cur = ch_radix_sort(keys, vals, n, 64, w, L.t.rs, s);
     hipLaunchKernelGGL(k_cl_median, dim3(1), dim3(64), 0, s, (const unsigned long long*)keys[cur], (long long)n, knn_ratio, eps_ratio, (double*)(w + L.par));
     return cl_components(d, n, cluster_frac, w, L, perm, labels, keep, s, what);
 }

@@ -331,7 +331,7 @@ static __global__ __launch_bounds__(SP_THREADS) void k_sp_emit_faces(const int* 
 // ---- workspace layout ----
 struct SpLayout {
     long long n, nbv;                                             // items of the sort buffers; bbox workgroups
-    ChTreeLayout S;                                               // the radix sort's part of it: rs_nb, hist, tmp, tot (tmp also serves the other scans)
+    ChSortLayout S;                                               // the radix sort's part of it (tmp also serves the other scans)
     size_t cnt, part, box, k0, k1, v0, v1, hs, headv, segidx, vrank, segstart, cseg, vcl, vsort, keep, frank, used, urank, cbeg, cend, cpos, cnrm, ccol, total;
 };
 
@@ -341,7 +341,6 @@ static bool sp_layout(long long nv, long long nf, SpLayout* L) {
     const long long n = nv > 3 * nf ? nv : 3 * nf;
     L->n = n;
     L->nbv = mv_ceil_div(nv, CH_CHUNK);
-    L->S.rs_nb = mv_ceil_div(n, CH_RS_CHUNK);
     WsCursor c{SP_HDR};
     L->cnt = c.take(SP_C_WORDS * 8);
     L->part = c.take((size_t)L->nbv * 48);
@@ -350,10 +349,7 @@ static bool sp_layout(long long nv, long long nf, SpLayout* L) {
     L->k1 = c.take((size_t)n * 8);
     L->v0 = c.take((size_t)n * 4);
     L->v1 = c.take((size_t)n * 4);
-    L->S.hist = c.take((size_t)L->S.rs_nb * CH_RS_BINS * 8);
-    const long long scan_n = n > L->S.rs_nb * CH_RS_BINS ? n : L->S.rs_nb * CH_RS_BINS;
-    L->S.tmp = c.take(mv_scan_tmp_bytes(scan_n));
-    L->S.tot = c.take(8);
+    ch_sort_layout(n, n, c, &L->S);
     L->hs = c.take((size_t)nv);
     L->headv = c.take((size_t)nv);
     L->segidx = c.take((size_t)nv * 8);
@@ -373,13 +369,6 @@ static bool sp_layout(long long nv, long long nf, SpLayout* L) {
     L->ccol = c.take((size_t)nv * 12);
     L->total = c.o;
     return true;
-}
-
-// nn_tree.h's sort over `count` items of the shared buffers (its layout argument carries the histogram, the scan's scratch and the workgroup count)
-static int sp_sort(unsigned long long* const k[2], int* const v[2], long long count, int bits, char* w, const SpLayout& L, hipStream_t s) {
-    ChTreeLayout S = L.S;
-    S.rs_nb = mv_ceil_div(count, CH_RS_CHUNK);
-    return ch_radix_sort(k, v, count, bits, w, S, s);
 }
 
 static int sp_bits(long long x) {                                 // bits that hold 0 .. x
@@ -456,7 +445,7 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
     g.sh0 = bits[2] + bits[1];
     // ---- 2: the vertices by cell ----
     hipLaunchKernelGGL(k_sp_vkeys, dim3(gv), dim3(SP_THREADS), 0, s, verts, V, g, k[0], v[0]);
-    int cur = sp_sort(k, v, V, bits[0] + bits[1] + bits[2], w, L, s);
+    int cur = ch_radix_sort(k, v, V, bits[0] + bits[1] + bits[2], w, L.S, s);
     // ---- 3: segments and clusters ----
     if ((rc = mv_check(hipMemsetAsync(headv, 0, (size_t)V, s), what))) return rc;
     hipLaunchKernelGGL(k_sp_heads, dim3(gv), dim3(SP_THREADS), 0, s, (const unsigned long long*)k[cur], (const int*)v[cur], V, hs, headv);
@@ -472,12 +461,12 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
     const int b = sp_bits(nc - 1);
     // ---- 4: duplicate faces by two stable sorts, kept faces, used clusters ----
     hipLaunchKernelGGL(k_sp_fkeys_lo, dim3(gf), dim3(SP_THREADS), 0, s, faces, (const int*)vcl, F, k[0], v[0]);
-    cur = sp_sort(k, v, F, b, w, L, s);
+    cur = ch_radix_sort(k, v, F, b, w, L.S, s);
     hipLaunchKernelGGL(k_sp_fkeys_hi, dim3(gf), dim3(SP_THREADS), 0, s, faces, (const int*)vcl, F, b, (const int*)v[cur], k[cur]);
     {
         unsigned long long* k2[2] = {k[cur], k[cur ^ 1]};
         int* v2[2] = {v[cur], v[cur ^ 1]};
-        cur ^= sp_sort(k2, v2, F, 2 * b, w, L, s);
+        cur ^= ch_radix_sort(k2, v2, F, 2 * b, w, L.S, s);
     }
     if ((rc = mv_check(hipMemsetAsync(used, 0, (size_t)V, s), what))) return rc;
     hipLaunchKernelGGL(k_sp_dups, dim3(gf), dim3(SP_THREADS), 0, s, faces, (const int*)vcl, F, (const int*)v[cur], keep, used, cnt);
@@ -486,7 +475,7 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
     // ---- 5: the corners by cluster, the cluster walk ----
     if (!counts_only) {
         hipLaunchKernelGGL(k_sp_ckeys, dim3(gc), dim3(SP_THREADS), 0, s, faces, (const int*)vcl, C, k[0], v[0]);
-        cur = sp_sort(k, v, C, b, w, L, s);
+        cur = ch_radix_sort(k, v, C, b, w, L.S, s);
         if ((rc = mv_check(hipMemsetAsync(w + L.cbeg, 0, (size_t)nc * 4, s), what))) return rc;
         if ((rc = mv_check(hipMemsetAsync(w + L.cend, 0, (size_t)nc * 4, s), what))) return rc;
         hipLaunchKernelGGL(k_sp_cseg, dim3(gc), dim3(SP_THREADS), 0, s, (const unsigned long long*)k[cur], C, (int*)(w + L.cbeg), (int*)(w + L.cend));

@@ -1,7 +1,14 @@
-// nn_tree.h -- what chamfer.hip and cloud.hip share: the constants and error bits, the 64-bit LSD radix sort passes (their int64 scan is geom_prims.h's mv_scan) and the
-// Morton-sorted points with their implicit 8-ary tree of fp64 boxes (built by ch_tree_frame + ch_tree_build, walked without a stack by the
-// query kernels of either file).  Kernels are static: each including file gets its own copies.
+// nn_tree.h -- what the point-cloud files share (chamfer.hip, cloud.hip, normals.hip, registration.hip; mesh_simplify.hip takes the sort alone):
+// * the constants and the error bits;
+// * the stable 64-bit LSD radix sort (ChSortLayout, ch_radix_sort; its int64 scan is geom_prims.h's mv_scan);
+// * the Morton-sorted points with their implicit 8-ary tree of fp64 boxes (ChTreeLayout, ch_tree_begin = ch_tree_frame + one read of the error
+//   word + ch_tree_build), which also says where the permutation sorted position -> input index lies;
+// * the traversals, each written once: ch_walk (depth first without a stack, over a bound and a leaf visitor the caller gives), ch_descend (the
+//   greedy way to one leaf for a first bound) and ch_knn_lane (the k nearest of a sorted point into a list the caller gives), with ch_knn_dispatch
+//   for the list capacities.  The bit-for-bit results of every file above rest on these.
+// Kernels are static: each including file gets its own copies.
 #pragma once
+#include <type_traits>
 #include "geom_prims.h"
 
 #define CH_THREADS 256
@@ -205,10 +212,121 @@ __device__ __forceinline__ double ch_box_lb2(const double* __restrict__ b, doubl
     return (gx * gx + gy * gy) + gz * gz;
 }
 
+// ---- the traversals ----
+// Depth first over the implicit tree, children in index order, no stack (parent = i / 8, next sibling = i + 1).  A node is entered when the lower
+// bound of its box is <= bound() -- the caller's current bound on squared distances, CH_MARGIN2 already in it; inclusive, so a box that may hold an
+// equal distance is never passed over -- and leaf(l) is called for every leaf entered.  The walk ends at the first node whose sorted positions all
+// lie above `last` (every later node's do too).  false: the step bound was reached (cannot happen; the caller raises CH_ERR_WALK).
+template <class Bound, class Leaf>
+__device__ __forceinline__ bool ch_walk(const double* __restrict__ box, const ChTree& T, double x, double y, double z, Bound bound, Leaf leaf,
+                                        long long last = LLONG_MAX) {
+    int lv = T.top;
+    long long i = 0;
+    const long long max_steps = 2 * T.nodes + 4;
+    long long step = 0;
+    for (; step < max_steps; ++step) {
+        if ((i << (3 * lv)) * CH_LEAF > last) break;
+        const double b = bound();
+        if (ch_box_lb2(box + (T.off[lv] + i) * 6, x, y, z) <= b) {
+            if (lv > 0) {
+                --lv;
+                i *= CH_ARITY;
+                continue;
+            }
+            leaf(i);
+        }
+        while (lv < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[lv])) {
+            i /= CH_ARITY;
+            ++lv;
+        }
+        if (lv == T.top) break;
+        ++i;
+    }
+    return step < max_steps;
+}
+
+// A first bound: from the root to one leaf by the child of the nearest box.  CENTRE: among children as near (the query lies inside several boxes: all
+// 0) the one whose centre is nearest, which only makes the bound better -- the walk decides the result either way.
+template <bool CENTRE>
+__device__ __forceinline__ long long ch_descend(const double* __restrict__ box, const ChTree& T, double x, double y, double z) {
+    long long i = 0;
+    for (int k = T.top; k > 0; --k) {
+        const long long b = i * CH_ARITY, e = min(T.cnt[k - 1], b + CH_ARITY);
+        long long pick = b;
+        double lbest = INFINITY, cbest = INFINITY;
+        for (long long c = b; c < e; ++c) {
+            const double* __restrict__ bx = box + (T.off[k - 1] + c) * 6;
+            const double lb = ch_box_lb2(bx, x, y, z);
+            double cd = 0.0;
+            if constexpr (CENTRE) cd = ch_d2(x, y, z, (bx[0] + bx[3]) * 0.5, (bx[1] + bx[4]) * 0.5, (bx[2] + bx[5]) * 0.5);
+            if (lb < lbest || (CENTRE && lb == lbest && cd < cbest)) {
+                lbest = lb;
+                cbest = cd;
+                pick = c;
+            }
+        }
+        i = pick;
+    }
+    return i;
+}
+
+// The k nearest of sorted point p, one lane: `list` (kept in registers by its owner) answers kth(), the squared distance of its k-th entry, and
+// takes offer(d2, q), the candidate at sorted position q.  Seeds are the point's own leaf and the two beside it; the walk passes those over, so
+// every other point is offered once.  false: see ch_walk.
+template <class List>
+__device__ __forceinline__ bool ch_knn_lane(const double* __restrict__ sp, const double* __restrict__ box, const ChTree& T, long long p, List& list) {
+    const double x = sp[p * 3], y = sp[p * 3 + 1], z = sp[p * 3 + 2];
+    auto offer = [&](long long b, long long e, long long self) {
+        for (long long q = b; q < e; ++q) {
+            if (q == self) continue;
+            list.offer(ch_d2(x, y, z, sp[q * 3], sp[q * 3 + 1], sp[q * 3 + 2]), q);
+        }
+    };
+    const long long leaf = p / CH_LEAF, l0 = leaf > 0 ? leaf - 1 : 0, l1 = min(leaf + 1, T.cnt[0] - 1);
+    offer(l0 * CH_LEAF, min(T.n, (l1 + 1) * CH_LEAF), p);
+    return ch_walk(
+        box, T, x, y, z, [&] { return list.kth() * CH_MARGIN2; },
+        [&](long long i) {
+            if (i < l0 || i > l1) offer(i * CH_LEAF, min(T.n, (i + 1) * CH_LEAF), -1);
+        });
+}
+
+// launch(std::integral_constant<int, CAP>) for the smallest list capacity CAP = 8 / 16 / 24 / 32 that holds k
+template <class Launch>
+static void ch_knn_dispatch(int k, Launch launch) {
+    if (k <= 8)
+        launch(std::integral_constant<int, 8>());
+    else if (k <= 16)
+        launch(std::integral_constant<int, 16>());
+    else if (k <= 24)
+        launch(std::integral_constant<int, 24>());
+    else
+        launch(std::integral_constant<int, 32>());
+}
+
+// ---- the workspace ----
+// what a radix sort of up to nb * CH_RS_CHUNK keys needs beside the keys and values
+struct ChSortLayout {
+    long long nb;
+    size_t hist, tmp, tot;
+};
+
+// scan_n: the scratch also serves the owner's other scans of up to scan_n items (0: the sort's alone)
+static void ch_sort_layout(long long n, long long scan_n, WsCursor& c, ChSortLayout* S) {
+    S->nb = mv_ceil_div(n, CH_RS_CHUNK);
+    S->hist = c.take((size_t)S->nb * CH_RS_BINS * 8);
+    S->tmp = c.take(mv_scan_tmp_bytes(scan_n > S->nb * CH_RS_BINS ? scan_n : S->nb * CH_RS_BINS));
+    S->tot = c.take(8);                                           // the scan's total, which nobody reads
+}
+
+static int ch_sort_passes(int bits) { return (bits + 3) / 4; }
+
 struct ChTreeLayout {
     ChTree T;
-    long long nbr, rs_nb;
-    size_t part, frame, k0, k1, v0, v1, hist, tmp, tot, sp, box;
+    long long nbr;
+    ChSortLayout rs;
+    size_t part, frame, k0, k1, v0, v1, sp, box;
+    size_t perm;                                      // v0 or v1: where ch_tree_build leaves the permutation (sorted position -> input index)
 };
 
 // the tree's shape over nr points and its buffers from the cursor on
@@ -227,18 +345,16 @@ static bool ch_tree_layout(long long nr, WsCursor& c, ChTreeLayout* L) {
     }
     T.nodes = T.off[T.top] + 1;
     L->nbr = mv_ceil_div(nr, CH_CHUNK);
-    L->rs_nb = mv_ceil_div(nr, CH_RS_CHUNK);
     L->part = c.take((size_t)L->nbr * 48);
     L->frame = c.take(6 * 8);
     L->k0 = c.take((size_t)nr * 8);
     L->k1 = c.take((size_t)nr * 8);
     L->v0 = c.take((size_t)nr * 4);
     L->v1 = c.take((size_t)nr * 4);
-    L->hist = c.take((size_t)L->rs_nb * CH_RS_BINS * 8);
-    L->tmp = c.take(mv_scan_tmp_bytes(L->rs_nb * CH_RS_BINS));
-    L->tot = c.take(8);                                           // the scan's total, which nobody reads
+    ch_sort_layout(nr, 0, c, &L->rs);
     L->sp = c.take((size_t)nr * 24);
     L->box = c.take((size_t)T.nodes * 48);
+    L->perm = ch_sort_passes(3 * CH_MORTON_BITS) % 2 ? L->v1 : L->v0;   // the sort ping-pongs from v0 once per pass
     return true;
 }
 
@@ -249,15 +365,16 @@ static void ch_tree_frame(const double* refs, long long nr, char* w, const ChTre
 }
 
 // stable LSD radix sort of n 64-bit keys (bits [0, bits), 4 per pass) with their int values, ping-pong between k / v [0] and [1] -> the index
-// (0 / 1) that holds the sorted arrays
-static int ch_radix_sort(unsigned long long* const k[2], int* const v[2], long long n, int bits, char* w, const ChTreeLayout& L, hipStream_t s) {
-    const int nb = (int)L.rs_nb;
-    long long* hist = (long long*)(w + L.hist);
-    long long* tot = (long long*)(w + L.tot);
+// (0 / 1) that holds the sorted arrays.  n is at most what S was laid out for; the histogram is as wide as n's own workgroups (<= S.nb).
+static int ch_radix_sort(unsigned long long* const k[2], int* const v[2], long long n, int bits, char* w, const ChSortLayout& S, hipStream_t s) {
+    const int nb = (int)mv_ceil_div(n, CH_RS_CHUNK);
+    long long* hist = (long long*)(w + S.hist);
+    long long* tot = (long long*)(w + S.tot);
     int cur = 0;
-    for (int shift = 0; shift < bits; shift += 4) {
+    for (int pass = 0; pass < ch_sort_passes(bits); ++pass) {
+        const int shift = 4 * pass;
         hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], n, shift, hist, nb);
-        mv_scan(hist, L.rs_nb * CH_RS_BINS, hist, w + L.tmp, tot, s);
+        mv_scan(hist, (long long)nb * CH_RS_BINS, hist, w + S.tmp, tot, s);
         hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (const int*)v[cur], n, shift,
                            (const long long*)hist, nb, k[cur ^ 1], v[cur ^ 1]);
         cur ^= 1;
@@ -265,21 +382,38 @@ static int ch_radix_sort(unsigned long long* const k[2], int* const v[2], long l
     return cur;
 }
 
-// after ch_tree_frame found no error: Morton keys, the sort, the sorted points (w + L.sp) and the boxes (w + L.box) -> the permutation
-// (sorted position -> input index)
+// after ch_tree_frame found no error: Morton keys, the sort, the sorted points (w + L.sp) and the boxes (w + L.box) -> the permutation at w + L.perm
 static const int* ch_tree_build(const double* refs, long long nr, char* w, const ChTreeLayout& L, hipStream_t s) {
     unsigned long long* k[2] = {(unsigned long long*)(w + L.k0), (unsigned long long*)(w + L.k1)};
     int* v[2] = {(int*)(w + L.v0), (int*)(w + L.v1)};
+    const int* perm = (const int*)(w + L.perm);
     const unsigned gr = mv_grid(nr, CH_THREADS);
     hipLaunchKernelGGL(k_nn_morton, dim3(gr), dim3(CH_THREADS), 0, s, refs, nr, (const double*)(w + L.frame), k[0], v[0]);
-    const int cur = ch_radix_sort(k, v, nr, 3 * CH_MORTON_BITS, w, L, s);
+    ch_radix_sort(k, v, nr, 3 * CH_MORTON_BITS, w, L.rs, s);
     double* sp = (double*)(w + L.sp);
     double* box = (double*)(w + L.box);
     const ChTree& T = L.T;
-    hipLaunchKernelGGL(k_nn_gather, dim3(gr), dim3(CH_THREADS), 0, s, refs, nr, (const int*)v[cur], sp);
+    hipLaunchKernelGGL(k_nn_gather, dim3(gr), dim3(CH_THREADS), 0, s, refs, nr, perm, sp);
     hipLaunchKernelGGL(k_nn_leaf_box, dim3(mv_grid(T.cnt[0], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)sp, nr, T.cnt[0], box);
     for (int lv = 1; lv <= T.top; ++lv)
         hipLaunchKernelGGL(k_nn_node_box, dim3(mv_grid(T.cnt[lv], CH_THREADS)), dim3(CH_THREADS), 0, s, (const double*)(box + T.off[lv - 1] * 6),
                            T.cnt[lv - 1], T.cnt[lv], box + T.off[lv] * 6);
-    return v[cur];
+    return perm;
+}
+
+struct ChBuilt {
+    int rc, err;                                      // the HIP status (mv_check's); the error bits the frame raised
+    const int* perm;                                  // the permutation, once rc == 0 && err == 0
+};
+
+// The frame, its launch check, the one 4-byte read of *err (which the caller has zeroed), and where that is 0 the tree and its launch check.  The
+// caller writes its own header for rc == 0 && err != 0: nothing was built.
+static ChBuilt ch_tree_begin(const double* pts, long long n, char* w, const ChTreeLayout& L, int* err, hipStream_t s, const char* what) {
+    ChBuilt b = {0, 0, nullptr};
+    ch_tree_frame(pts, n, w, L, err, s);
+    if ((b.rc = mv_check(hipGetLastError(), what))) return b;
+    if ((b.rc = mv_read(&b.err, err, 4, s, what)) || b.err) return b;
+    b.perm = ch_tree_build(pts, n, w, L, s);
+    b.rc = mv_check(hipGetLastError(), what);
+    return b;
 }

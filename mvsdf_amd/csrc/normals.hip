@@ -2,10 +2,10 @@
 // globally consistent sign.  Python: mvsdf_amd/normals.py, which states the definition; tests/normals_ref.py restates it in numpy.  All arithmetic is
 // fp64 without contraction, in the order the definition writes it.
 //
-// * k_nr_knn: k_cl_knn's design (cloud.hip) with a list of pairs.  One lane per Morton-sorted point; the list is CAP doubles and CAP ints
-//   (CAP = 8 / 16 / 24 / 32, a template argument) ordered by (d2, input index), the CAP - k slots in front hold (-1, -1), below every pair, so the
-//   k-th pair is always the last slot and every list index is a compile-time one.  The seeds are the point's own leaf and the two beside it, the walk
-//   is stackless; a box is pruned when its lower bound exceeds the last slot's d2 by the relative CH_MARGIN2 (inclusive: a box at exactly that
+// * k_nr_knn: k_cl_knn's lane (cloud.hip; both go through nn_tree.h's ch_knn_lane) with a list of pairs.  One lane per Morton-sorted point; the list
+//   is CAP doubles and CAP ints (CAP = 8 / 16 / 24 / 32, a template argument) ordered by (d2, input index), the CAP - k slots in front hold (-1, -1),
+//   below every pair, so the k-th pair is always the last slot and every list index is a compile-time one.  The seeds are the point's own leaf and
+//   the two beside it, the walk is stackless; a box is pruned when its lower bound exceeds the last slot's d2 by the relative CH_MARGIN2 (inclusive: a box at exactly that
 //   distance may hold a tie of lower index), every other point is compared as a pair.  Each point is met once, so no pair is inserted twice and the
 //   row is one array, not a multiset.
 // * k_nr_pca: one lane per point in input order reads its row: mean and covariance of the offsets, NR_SWEEPS cyclic Jacobi sweeps over a full
@@ -56,18 +56,20 @@ __device__ __forceinline__ void nr_insert(double (&bd)[CAP], int (&bi)[CAP], dou
     bi[0] = first ? id : bi[0];
 }
 
+// ch_knn_lane's list: the k smallest pairs (d2, input index); the permutation is read only for a candidate not above the k-th distance
 template <int CAP>
-__device__ __forceinline__ void nr_leaf_knn(const double* __restrict__ sp, const int* __restrict__ perm, long long b, long long e, long long self, double x,
-                                            double y, double z, double (&bd)[CAP], int (&bi)[CAP]) {
-    for (long long q = b; q < e; ++q) {
-        if (q == self) continue;
-        const double v = ch_d2(x, y, z, sp[q * 3], sp[q * 3 + 1], sp[q * 3 + 2]);
+struct NrList {
+    double bd[CAP];
+    int bi[CAP];
+    const int* __restrict__ perm;
+    __device__ __forceinline__ double kth() const { return bd[CAP - 1]; }
+    __device__ __forceinline__ void offer(double v, long long q) {
         if (v <= bd[CAP - 1]) {
             const int id = perm[q];
             if (nr_less(v, id, bd[CAP - 1], bi[CAP - 1])) nr_insert<CAP>(bd, bi, v, id);
         }
     }
-}
+};
 
 // row perm[p] of idx (and of d2 when given) = the k pairs (d2, input index) smallest from sorted point p to every other point, ascending
 template <int CAP>
@@ -75,43 +77,20 @@ __global__ __launch_bounds__(CH_THREADS) void k_nr_knn(const double* __restrict_
                                                         int k, int* __restrict__ idx, double* __restrict__ d2, int* err) {
     const long long p = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
     if (p >= T.n) return;
-    const double x = sp[p * 3], y = sp[p * 3 + 1], z = sp[p * 3 + 2];
-    double bd[CAP];
-    int bi[CAP];
+    NrList<CAP> list;
+    list.perm = perm;
 #pragma unroll
     for (int j = 0; j < CAP; ++j) {
-        bd[j] = j < CAP - k ? -1.0 : INFINITY;
-        bi[j] = j < CAP - k ? -1 : INT_MAX;
+        list.bd[j] = j < CAP - k ? -1.0 : INFINITY;
+        list.bi[j] = j < CAP - k ? -1 : INT_MAX;
     }
-    const long long leaf = p / CH_LEAF, l0 = leaf > 0 ? leaf - 1 : 0, l1 = min(leaf + 1, T.cnt[0] - 1);
-    nr_leaf_knn<CAP>(sp, perm, l0 * CH_LEAF, min(T.n, (l1 + 1) * CH_LEAF), p, x, y, z, bd, bi);
-    int lv = T.top;
-    long long i = 0;
-    const long long max_steps = 2 * T.nodes + 4;
-    long long step = 0;
-    for (; step < max_steps; ++step) {
-        if (ch_box_lb2(box + (T.off[lv] + i) * 6, x, y, z) <= bd[CAP - 1] * CH_MARGIN2) {
-            if (lv > 0) {
-                --lv;
-                i *= CH_ARITY;
-                continue;
-            }
-            if (i < l0 || i > l1) nr_leaf_knn<CAP>(sp, perm, i * CH_LEAF, min(T.n, (i + 1) * CH_LEAF), -1, x, y, z, bd, bi);
-        }
-        while (lv < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[lv])) {
-            i /= CH_ARITY;
-            ++lv;
-        }
-        if (lv == T.top) break;
-        ++i;
-    }
-    if (step >= max_steps) atomicOr(err, CH_ERR_WALK);
+    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, CH_ERR_WALK);
     const long long row = (long long)perm[p] * k;
 #pragma unroll
     for (int j = 0; j < CAP; ++j)
         if (j >= CAP - k) {
-            idx[row + (j - (CAP - k))] = bi[j];
-            if (d2) d2[row + (j - (CAP - k))] = bd[j];
+            idx[row + (j - (CAP - k))] = list.bi[j];
+            if (d2) d2[row + (j - (CAP - k))] = list.bd[j];
         }
 }
 
@@ -516,12 +495,6 @@ static int nr_fail_header(void* ws, int words, long long err, hipStream_t s, con
     return mv_write_header(ws, hdr, words, s, what);
 }
 
-template <int CAP>
-static void nr_launch_knn(long long n, int k, const double* sp, const double* box, const ChTree& T, const int* perm, int* idx, double* d2, int* err,
-                          hipStream_t s) {
-    hipLaunchKernelGGL(k_nr_knn<CAP>, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, sp, box, T, perm, k, idx, d2, err);
-}
-
 static int nr_words(long long V) { return (int)((V + 63) / 64); }
 
 extern "C" {
@@ -548,23 +521,15 @@ int mvsdf_normals_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t 
     int* fl = (int*)(w + L.flags);
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, NR_F_WORDS * 4, s), what))) return rc;
-    ch_tree_frame(pts, n, w, L.t, fl + NR_F_ERR, s);
-    if ((rc = mv_check(hipGetLastError(), what))) return rc;
-    int e = 0;
-    if ((rc = mv_read(&e, fl, 4, s, what))) return rc;
-    if (e) return nr_fail_header(w, 1, e, s, what);
-    const int* perm = ch_tree_build(pts, n, w, L.t, s);
-    if ((rc = mv_check(hipGetLastError(), what))) return rc;
+    const ChBuilt tree = ch_tree_begin(pts, n, w, L.t, fl + NR_F_ERR, s, what);
+    if (tree.rc) return tree.rc;
+    if (tree.err) return nr_fail_header(w, 1, tree.err, s, what);
     const double* sp = (const double*)(w + L.t.sp);
     const double* box = (const double*)(w + L.t.box);
-    if (k <= 8)
-        nr_launch_knn<8>(n, k, sp, box, L.t.T, perm, idx, d2, fl + NR_F_ERR, s);
-    else if (k <= 16)
-        nr_launch_knn<16>(n, k, sp, box, L.t.T, perm, idx, d2, fl + NR_F_ERR, s);
-    else if (k <= 24)
-        nr_launch_knn<24>(n, k, sp, box, L.t.T, perm, idx, d2, fl + NR_F_ERR, s);
-    else
-        nr_launch_knn<32>(n, k, sp, box, L.t.T, perm, idx, d2, fl + NR_F_ERR, s);
+    ch_knn_dispatch(k, [&](auto cap) {
+        hipLaunchKernelGGL(k_nr_knn<decltype(cap)::value>, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, sp, box, L.t.T, tree.perm, (int)k, idx, d2,
+                           fl + NR_F_ERR);
+    });
     if (normals)
         hipLaunchKernelGGL(k_nr_pca, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const int*)idx, (int)k, normals, variation);
     hipLaunchKernelGGL(k_nr_knn_header, dim3(1), dim3(64), 0, s, (const int*)fl, (long long*)w);

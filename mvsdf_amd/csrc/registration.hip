@@ -5,8 +5,8 @@
 //
 // * The tree is nn_tree.h's (Morton sort, leaves of CH_LEAF points, implicit 8-ary tree of fp64 boxes), built once into a workspace the caller
 //   keeps: the sorted points, the boxes and the permutation sorted position -> input index stay resident, so a query sorts nothing.
-// * The query is chamfer.hip's stackless one-lane-per-query walk with a leaf visitor that orders candidates by (d2, input index): a box is pruned
-//   only when its lower bound exceeds min(best, max_dist^2) by a relative 4e-9, so every box that could hold an equal distance is visited and the
+// * The query is one lane per query over nn_tree.h's traversals (ch_descend, ch_walk), as in chamfer.hip, with a leaf visitor that orders
+//   candidates by (d2, input index): a box is pruned only when its lower bound exceeds min(best, max_dist^2) by a relative 4e-9, so every box that could hold an equal distance is visited and the
 //   smallest input index among the references at the exact minimum wins, whatever the visiting order.  The visitor keeps the sorted position of
 //   the best candidate and reads the permutation only on an exact tie; the first bound comes from the leaf under the nearest box centres.
 // * The ICP sums follow k_nn_sum_part / k_nn_sum_final: source order, 8 consecutive items per lane from 0, a 256-lane halving tree, block partials,
@@ -22,7 +22,6 @@
 #define RG_MAX_EDGES 4097
 #define RG_SUMS 16                                    // fp64 sums of an ICP iteration (the 17th quantity is the int64 pair count)
 #define RG_VOXEL_BITS 21
-#define RG_SORT_PASSES ((3 * CH_MORTON_BITS + 3) / 4)
 
 struct RgXform {
     double m[12];
@@ -60,9 +59,6 @@ static bool rg_tree_layout(long long nr, RgTreeLayout* L) {
     L->total = c.o;
     return true;
 }
-
-// where ch_tree_build leaves the permutation: the radix sort ping-pongs once per pass
-static size_t rg_perm_off(const RgTreeLayout& L) { return RG_SORT_PASSES % 2 ? L.t.v1 : L.t.v0; }
 
 // the centre of the root box, as three fp64 words behind the error word of the header
 static __global__ __launch_bounds__(64) void k_rg_centre(const double* __restrict__ root, double* __restrict__ hdr) {
@@ -106,52 +102,13 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_query(const double* __
     const double cut2 = max_dist * max_dist;
     double best = INFINITY;
     int bi = -1;
-    // a first bound: follow the nearest child from the root to one leaf; among children as near (the query lies inside several boxes: all 0) the one
-    // whose centre is nearest, which only makes the bound better -- the walk below decides the result
-    {
-        long long i = 0;
-        for (int k = T.top; k > 0; --k) {
-            const long long b = i * CH_ARITY, e = min(T.cnt[k - 1], b + CH_ARITY);
-            long long pick = b;
-            double lbest = INFINITY, cbest = INFINITY;
-            for (long long c = b; c < e; ++c) {
-                const double* __restrict__ bx = box + (T.off[k - 1] + c) * 6;
-                const double lb = ch_box_lb2(bx, x, y, z);
-                const double cd = ch_d2(x, y, z, (bx[0] + bx[3]) * 0.5, (bx[1] + bx[4]) * 0.5, (bx[2] + bx[5]) * 0.5);
-                if (lb < lbest || (lb == lbest && cd < cbest)) {
-                    lbest = lb;
-                    cbest = cd;
-                    pick = c;
-                }
-            }
-            i = pick;
-        }
-        if (ch_box_lb2(box + i * 6, x, y, z) <= cut2 * CH_MARGIN2) rg_leaf_min(sp, perm, T.n, i, x, y, z, best, bi);
-    }
-    // the full walk: depth first over the implicit tree, children in index order, no stack (parent = i / 8, next sibling = i + 1).  `<=` keeps a
-    // box whose lower bound equals the best distance: it may hold an equal distance under a smaller input index.
-    int k = T.top;
-    long long i = 0;
-    const long long max_steps = 2 * T.nodes + 4;
-    long long step = 0;
-    for (; step < max_steps; ++step) {
-        const double bound = fmin(best, cut2) * CH_MARGIN2;
-        if (ch_box_lb2(box + (T.off[k] + i) * 6, x, y, z) <= bound) {
-            if (k > 0) {
-                --k;
-                i *= CH_ARITY;
-                continue;
-            }
-            rg_leaf_min(sp, perm, T.n, i, x, y, z, best, bi);
-        }
-        while (k < T.top && (i % CH_ARITY == CH_ARITY - 1 || i + 1 >= T.cnt[k])) {
-            i /= CH_ARITY;
-            ++k;
-        }
-        if (k == T.top) break;
-        ++i;
-    }
-    if (step >= max_steps) atomicOr(err, CH_ERR_WALK);
+    // a first bound from the leaf under the nearest boxes (ties by the nearest centre), then the full walk: its inclusive prune keeps a box whose
+    // lower bound equals the best distance, which may hold an equal distance under a smaller input index
+    const long long first = ch_descend<true>(box, T, x, y, z);
+    if (ch_box_lb2(box + first * 6, x, y, z) <= cut2 * CH_MARGIN2) rg_leaf_min(sp, perm, T.n, first, x, y, z, best, bi);
+    if (!ch_walk(
+            box, T, x, y, z, [&] { return fmin(best, cut2) * CH_MARGIN2; }, [&](long long l) { rg_leaf_min(sp, perm, T.n, l, x, y, z, best, bi); }))
+        atomicOr(err, CH_ERR_WALK);
     const double d = sqrt(best);
     const bool hit = d < max_dist && bi >= 0;                     // (a finite best always has its position)
     if (dist) dist[qi] = hit ? d : INFINITY;
@@ -162,7 +119,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_query(const double* __
 static void rg_launch_query(const char* tree, const RgTreeLayout& L, const double* queries, long long nq, const double* transform, double max_dist,
                             double* dist, double* d2, int* index, int* err, hipStream_t s) {
     hipLaunchKernelGGL(k_rg_query, dim3(mv_grid(nq, CH_THREADS)), dim3(CH_THREADS), 0, s, queries, nq, rg_xform(transform), (const double*)(tree + L.t.sp),
-                       (const double*)(tree + L.t.box), (const int*)(tree + rg_perm_off(L)), L.t.T, max_dist, dist, d2, index, err);
+                       (const double*)(tree + L.t.box), (const int*)(tree + L.t.perm), L.t.T, max_dist, dist, d2, index, err);
 }
 
 // ================================================================ the sums of an ICP iteration ================================================================
@@ -418,16 +375,12 @@ int mvsdf_reg_tree_build(const double* refs, int64_t nr, void* ws, size_t ws_byt
     long long hdr[4] = {0, 0, 0, 0};                              // error bits, the box centre (fp64 bits)
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_reg_tree_build"))) return rc;
-    ch_tree_frame(refs, (long long)nr, w, L.t, fl, s);
-    if ((rc = mv_check(hipGetLastError(), "mvsdf_reg_tree_build"))) return rc;
-    int e = 0;
-    if ((rc = mv_read(&e, fl, 4, s, "mvsdf_reg_tree_build"))) return rc;
-    if (e) {
-        hdr[0] = e;
+    const ChBuilt tree = ch_tree_begin(refs, (long long)nr, w, L.t, fl, s, "mvsdf_reg_tree_build");
+    if (tree.rc) return tree.rc;
+    if (tree.err) {
+        hdr[0] = tree.err;
         return mv_write_header(ws, hdr, 4, s, "mvsdf_reg_tree_build");
     }
-    const int* perm = ch_tree_build(refs, (long long)nr, w, L.t, s);
-    if ((const char*)perm != w + rg_perm_off(L)) return mv_fail(-2, "mvsdf_reg_tree_build: the permutation is not where the query reads it");
     const ChTree& T = L.t.T;
     hipLaunchKernelGGL(k_rg_centre, dim3(1), dim3(64), 0, s, (const double*)(w + L.t.box) + T.off[T.top] * 6, (double*)w);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_reg_tree_build"))) return rc;
@@ -523,7 +476,7 @@ int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_reg_voxel"))) return rc;
     ch_tree_frame(pts, (long long)n, w, L.t, (int*)(fl + 1), s);
     hipLaunchKernelGGL(k_rg_voxel_key, dim3(g), dim3(CH_THREADS), 0, s, pts, (long long)n, (const double*)(w + L.t.frame), voxel, k[0], v[0], (int*)(fl + 1));
-    const int cur = ch_radix_sort(k, v, (long long)n, 3 * RG_VOXEL_BITS, w, L.t, s);
+    const int cur = ch_radix_sort(k, v, (long long)n, 3 * RG_VOXEL_BITS, w, L.t.rs, s);
     hipLaunchKernelGGL(k_rg_heads, dim3(g), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (long long)n, head);
     mv_scan((const unsigned char*)head, (long long)n, off, w + L.tmp2, fl, s);
     hipLaunchKernelGGL(k_rg_voxel_mean, dim3(g), dim3(CH_THREADS), 0, s, pts, (const unsigned long long*)k[cur], (const int*)v[cur], (const unsigned char*)head,

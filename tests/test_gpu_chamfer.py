@@ -124,6 +124,25 @@ def test_nearest_bit_identical(seed):
     assert np.array_equal(got.view(np.int64), got2.view(np.int64))
 
 
+@pytest.mark.parametrize('nr', [1, 15, 16, 17, 129, 2049])
+def test_nearest_at_the_tree_shape_edges(nr):
+    """one leaf, a leaf's edge, a partly filled last child at two and at three levels: the descent and the walk where the tree is smallest"""
+    from mvsdf_amd import chamfer as C
+    rs = np.random.RandomState(100 + nr)
+    refs = rs.uniform(-1, 1, (nr, 3)) * [1.0, 0.6, 0.3]
+    max_dist = 0.5
+    around = rs.uniform(-1.3, 1.3, (180, 3)) * [1.0, 0.6, 0.3]
+    own = refs[rs.permutation(nr)[:100]]
+    beyond = rs.uniform(-1, 1, (20, 3)) + [5.0, -4.0, 3.0]
+    q = np.concatenate([around, own, beyond])
+    got = _np(C.nearest_distance(torch.from_numpy(q).cuda(), torch.from_numpy(refs).cuda(), max_dist))
+    want = chamfer_ref.nearest(q, refs, max_dist, chunk=64)
+    assert _same_dist(got, want)
+    assert (got[180:180 + len(own)] == 0).all() and np.isinf(got[-20:]).all()
+    got2 = _np(C.nearest_distance(torch.from_numpy(q).cuda(), torch.from_numpy(refs).cuda(), max_dist))
+    assert np.array_equal(got.view(np.int64), got2.view(np.int64))
+
+
 def test_nearest_duplicates_and_one_reference():
     from mvsdf_amd import chamfer as C
     refs = np.array([[1.0, 2.0, 3.0]] * 40)

@@ -112,6 +112,24 @@ def test_radius_components_on_lattices_is_inclusive_at_eps():
     assert len(np.unique(_labels(P, step))) == 2                             # exactly at it: the two lattices
 
 
+@pytest.mark.parametrize('kind', ['uniform', 'lattice'])
+@pytest.mark.parametrize('n', [2, 16, 17, 129, 2049])
+def test_radius_components_at_the_tree_shape_edges(kind, n):
+    """one leaf, a leaf's edge, a partly filled last child at two and at three levels: the walk that stops at the point's own position.  eps: the
+    lattice's step; for the uniform cloud the median nearest-neighbour distance, which joins about half the points to their nearest one"""
+    P = make_cloud(kind, n)
+    if kind == 'lattice':
+        eps = 0.125
+    else:
+        d = np.sqrt(((P[:, None] - P[None]) ** 2).sum(-1))
+        np.fill_diagonal(d, np.inf)
+        eps = float(np.median(d.min(1)))
+    want = R.radius_components(P, eps)
+    if kind == 'uniform' and n > 2:
+        assert 1 < len(np.unique(want)) < n
+    assert np.array_equal(_labels(P, eps), want)
+
+
 def test_radius_components_on_blobs():
     rs = np.random.RandomState(4)
     centres = rs.uniform(-2, 2, size=(12, 3))
