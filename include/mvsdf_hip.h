@@ -1067,6 +1067,32 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
 int mvsdf_normals_to_views(const double* pts, const double* normals, int64_t n, const double* centers, const void* bits, int64_t V, double* out, void* hdr,
                            void* stream);
 
+/* ---- Global registration (global_reg.hip; Python: mvsdf_amd/global_reg.py, which states the definition) ----
+ * No host wait in any of these.  Error bits: 4 a non-finite coordinate, 128 a non-finite normal, 256 a neighbour / correspondence index out of range,
+ * 512 a code outside 0 .. 127.  err: int32 [1] on the device, zeroed by the caller, the bits are OR-ed into it.  radius2: the squared feature
+ * radius, +inf for none.  1 <= n <= INT32_MAX, 1 <= k <= 32.
+ * mvsdf_greg_spfh: hist int32 [n][33] and count int32 [n] = the binned pair features of every point's neighbour row (neighbors int32 [n][k]).
+ * mvsdf_greg_fpfh: features fp64 [n][33] = the rows' sums of hist / count weighted by 1 / d2, each group of 11 scaled to a sum of 100; codes int8
+ * [n][33] = min(127, floor(1.27 features)).
+ * mvsdf_greg_match: index int32 [ns] = the target code row nearest to each source row under (D, j), D = the squared difference summed over the 33
+ * codes, dist int32 [ns] = that D; with mutual, index = -1 where the nearest source of that target is another row.  On the int8 matrix cores.
+ * Workspace: mvsdf_greg_match_workspace_bytes(ns, nt) (0 unless 1 <= ns, nt <= INT32_MAX) -> int64 {error bits}.  mvsdf_greg_match_splits: over how
+ * many workgroups the walk over the targets is split at these sizes (they combine by a 64-bit atomicMin).
+ * mvsdf_greg_ransac: corr int32 [m][2] (source index, target index), m >= 3; 1 <= hypotheses <= 2^22; mask uint8 [m] = the winner's inliers.
+ * Workspace: mvsdf_greg_ransac_workspace_bytes(m, hypotheses) -> int64 {hypothesis or -1, inliers, checked, error bits, then the 12 entries of the
+ * winner's 3 x 4 transformation as fp64 bits}. */
+int mvsdf_greg_spfh(const double* pts, const double* normals, const int32_t* neighbors, int64_t n, int32_t k, double radius2, int32_t* hist,
+                    int32_t* count, int32_t* err, void* stream);
+int mvsdf_greg_fpfh(const double* pts, const int32_t* neighbors, const int32_t* hist, const int32_t* count, int64_t n, int32_t k, double radius2,
+                    double* features, int8_t* codes, int32_t* err, void* stream);
+size_t mvsdf_greg_match_workspace_bytes(int64_t ns, int64_t nt);
+int32_t mvsdf_greg_match_splits(int64_t ns, int64_t nt);
+int mvsdf_greg_match(const int8_t* src, int64_t ns, const int8_t* dst, int64_t nt, int32_t mutual, void* ws, size_t ws_bytes, int32_t* index,
+                     int32_t* dist, void* stream);
+size_t mvsdf_greg_ransac_workspace_bytes(int64_t m, int64_t hypotheses);
+int mvsdf_greg_ransac(const double* src, int64_t ns, const double* dst, int64_t nd, const int32_t* corr, int64_t m, int64_t hypotheses, uint64_t seed,
+                      double edge_ratio, double max_dist, void* ws, size_t ws_bytes, uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
