@@ -590,21 +590,56 @@ int mvsdf_loss_forward(const MvsdfLossArgs* a, void* blk, void* stream);
 int mvsdf_loss_backward(const MvsdfLossArgs* a, const void* blk, const float* const* g, float* g_rgb, float* g_grad, float* g_eo, float* g_sf,
                         float* g_diff, void* stream);
 
+/* ==== the scene-side calls: result words, error bits and limits ====
+ * Most calls below leave int64 result words at the start of their workspace (or of a 256-byte `hdr`), one of them an error word.  The enum blocks
+ * beside the calls name the word indices (MVSDF_<CALL>_H_<WORD>; _H_WORDS = the words a host may read; a run of words is named by its first index
+ * and ends at the next enumerator), the bits of the error word (MVSDF_<MOD>_ERR_<WHAT>) and the argument limits both sides check
+ * (MVSDF_<MOD>_MAX_<WHAT>; a limit beyond int is given as its exponent, _LOG2).  mvsdf_amd/_lib.py reads them from this file. */
+/* the calls that say they leave {0, error bits}, and mvsdf_fusion_fuse */
+enum {
+    MVSDF_RES_H_COUNT = 0,  /* mvsdf_fusion_fuse: the points kept; 0 from every other call */
+    MVSDF_RES_H_ERR = 1,    /* the error bits of the call's module */
+    MVSDF_RES_H_WORDS = 2
+};
+/* the calls that say they leave {error bits} alone */
+enum {
+    MVSDF_ERRW_H_ERR = 0,   /* the error bits of the call's module */
+    MVSDF_ERRW_H_WORDS = 1
+};
+/* the calls that say they leave {rows kept} (mvsdf_cloud_compact, mvsdf_reg_crop) */
+enum {
+    MVSDF_ROWS_H_ROWS = 0,  /* the rows kept */
+    MVSDF_ROWS_H_WORDS = 1
+};
+
 /* ---- mesh extraction (mesh_kernels.hip; Python: mvsdf_amd/mesh.py, which states the vertex / face conventions) ----
  * Marching cubes of an fp32 volume vol[i][j][k] = vol[i * strides[0] + j * strides[1] + k * strides[2]] (element strides, host arrays shape[3] /
- * strides[3]) at `level`; a corner is inside when its value is < level.  Two calls: mvsdf_mc_count classifies the grid and leaves int64
- * {vertices, faces, non-finite value seen} at the start of the workspace; the caller reads them (the one host synchronisation), allocates and calls
+ * strides[3]) at `level`; a corner is inside when its value is < level.  Two calls: mvsdf_mc_count classifies the grid and leaves the
+ * MVSDF_MC_H_* words at the start of the workspace; the caller reads them (the one host synchronisation), allocates and calls
  * mvsdf_mc_emit with the same volume and workspace.  Every extent must be >= 2.
  * workspace bytes: 4 per grid point + O(points / 1024); 0 = refused (an extent below 2 or a grid the kernels cannot index).
  * nv_cap / nf_cap: the rows verts / normals and faces can hold (nothing is written beyond them).  Vertex ids are int32: a caller refuses a
  * volume whose counts exceed INT32_MAX. */
+enum {                          /* mvsdf_mc_count, mvsdf_mcm_count */
+    MVSDF_MC_H_VERTS = 0,       /* vertices of the mesh */
+    MVSDF_MC_H_FACES = 1,       /* faces of the mesh */
+    MVSDF_MC_H_BAD = 2,         /* non-zero: a non-finite value was seen (mvsdf_mcm_count: a non-finite VALID value) */
+    MVSDF_MC_H_WORDS = 3
+};
 size_t mvsdf_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
 int mvsdf_mc_count(const float* vol, const int64_t* shape, const int64_t* strides, float level, void* ws, size_t ws_bytes, void* stream);
 int mvsdf_mc_emit(const float* vol, const int64_t* shape, const int64_t* strides, float level, const float* spacing, const float* origin, void* ws,
                   size_t ws_bytes, float* verts, float* normals, int32_t* faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 /* Connected components of a mesh (vertex connectivity through faces, union-find) -> vert_label[nv], face_label[nf]: components numbered by their lowest
- * vertex id; the workspace starts with int64 {components, label of the largest by area (ties: the lowest face index), its vertices, its faces,
- * 1 if a union-find loop hit its bound}.  1 <= nv, nf <= INT32_MAX, else the workspace query gives 0. */
+ * vertex id; the workspace starts with the MVSDF_CC_H_* words.  1 <= nv, nf <= INT32_MAX, else the workspace query gives 0. */
+enum {
+    MVSDF_CC_H_COMPONENTS = 0,  /* components */
+    MVSDF_CC_H_LABEL = 1,       /* label of the largest by area (ties: the lowest face index) */
+    MVSDF_CC_H_VERTS = 2,       /* its vertices */
+    MVSDF_CC_H_FACES = 3,       /* its faces */
+    MVSDF_CC_H_BOUND = 4,       /* 1 if a union-find loop hit its bound */
+    MVSDF_CC_H_WORDS = 5
+};
 size_t mvsdf_mesh_cc_workspace_bytes(int64_t nv, int64_t nf);
 int mvsdf_mesh_components(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes, int32_t* vert_label,
                           int32_t* face_label, void* stream);
@@ -623,10 +658,19 @@ int mvsdf_mesh_select(const int32_t* vert_label, const int32_t* face_label, int6
  *   mvsdf_smc_closure: values of the slots [slot0, slot0 + count) (values[slot * (B + 3)^3 + local]) -> inactive neighbours across a face with a
  *     crossing grid edge get the next slots, from slot0 + count on;
  *   mvsdf_smc_count / mvsdf_smc_emit: the values of all `nactive` slots -> the mesh (like mvsdf_mc_count / mvsdf_mc_emit).
- * The workspace starts with int64 {last seed / closure count, 0, 0, non-finite value seen, closure flag stores, missing vertex owner (never expected),
- * 0, 0, vertices, faces} (mvsdf_smc_count writes the last two): the caller reads the count after each seed / closure call and the totals after
- * mvsdf_smc_count.  Workspace queries give 0 for n < 3, B < 2 (or > 1024) or sizes the kernels cannot index; the emit workspace holds (B + 1)^3
- * int32 per active block. */
+ * The workspace starts with the MVSDF_SMC_H_* words (the words between them are 0): the caller reads the count after each seed / closure call and
+ * the totals after mvsdf_smc_count.  Workspace queries give 0 for n < 3, B < 2 (or > 1024) or sizes the kernels cannot index; the emit workspace
+ * holds (B + 1)^3 int32 per active block. */
+enum {
+    MVSDF_SMC_H_COUNT = 0,      /* the last seed / closure count; after mvsdf_smc_count the active blocks it listed */
+    MVSDF_SMC_H_BAD = 3,        /* 1 once a non-finite evaluated value was seen */
+    MVSDF_SMC_H_STORES = 4,     /* closure flag stores (per-wave sums; a block can be flagged by several faces) */
+    MVSDF_SMC_H_OWNER = 5,      /* 1 if a face's edge has no active vertex owner (the closure did not close: never expected) */
+    MVSDF_SMC_H_VERTS = 8,      /* mvsdf_smc_count: vertices */
+    MVSDF_SMC_H_FACES = 9,      /* mvsdf_smc_count: faces */
+    MVSDF_SMC_H_NEGATIVE = 10,  /* mvsdf_smc_count: 1 if a per-workgroup count was negative (never expected) */
+    MVSDF_SMC_H_WORDS = 11
+};
 size_t mvsdf_smc_workspace_bytes(int64_t n, int64_t block);
 size_t mvsdf_smc_emit_workspace_bytes(int64_t n, int64_t block, int64_t nactive);
 int mvsdf_smc_coarse_points(const float* axis, int64_t n, int64_t block, int64_t start, int64_t count, float* pts, void* stream);
@@ -643,10 +687,25 @@ int mvsdf_smc_emit(const float* values, int64_t n, int64_t block, float level, c
  * The minimum cut of reference code/mesh_cut/mesh_cut.py over the faces: S* = the faces reachable from the source in the residual graph of a maximum
  * flow (bright faces, red > thresh / 255 on average, tie to the source; faces sharing an edge are joined by 2 * smooth).  1 <= nv <= INT32_MAX,
  * 1 <= nf <= INT32_MAX / 8, else the workspace query gives 0.  colors: fp32 [nv][3] (only the red channel is read).
- * mvsdf_mesh_cut waits for the stream (its round loop reads flags from the device) -> removed[nf] (1 = in S*) and int64 {flow value, removed faces,
- * vertices the kept faces use, error bits (1 duplicate directed edge, 2 repeated vertex id in a face, 4 vertex id out of range, 8 table overflow,
- * 16 round limit, 32 relabel limit), push rounds, relabel launches} at the start of the workspace.  With error bits set nothing else is valid.
- * smooth in [0, INT32_MAX / 6]. */
+ * mvsdf_mesh_cut waits for the stream (its round loop reads flags from the device) -> removed[nf] (1 = in S*) and the MVSDF_CUT_H_* words
+ * at the start of the workspace.  With error bits (MVSDF_CUT_ERR_*) set nothing else is valid.  smooth in [0, INT32_MAX / 6]. */
+enum {
+    MVSDF_CUT_H_FLOW = 0,           /* the flow value */
+    MVSDF_CUT_H_REMOVED = 1,        /* removed faces */
+    MVSDF_CUT_H_KEPT_VERTS = 2,     /* vertices the kept faces use */
+    MVSDF_CUT_H_ERR = 3,            /* error bits */
+    MVSDF_CUT_H_ROUNDS = 4,         /* push rounds */
+    MVSDF_CUT_H_RELABELS = 5,       /* relabel launches */
+    MVSDF_CUT_H_WORDS = 6
+};
+enum {
+    MVSDF_CUT_ERR_DUP_EDGE = 1,     /* a directed edge in two faces (non-manifold edge or inconsistent winding) */
+    MVSDF_CUT_ERR_REPEATED = 2,     /* a face repeats a vertex id */
+    MVSDF_CUT_ERR_RANGE = 4,        /* a vertex id outside [0, nv) */
+    MVSDF_CUT_ERR_HASH = 8,         /* the half-edge table's probe bound (cannot happen at load factor 1/2) */
+    MVSDF_CUT_ERR_ROUNDS = 16,      /* the round limit was reached */
+    MVSDF_CUT_ERR_RELABEL = 32      /* a global relabel did not settle within its launch limit */
+};
 size_t mvsdf_mesh_cut_workspace_bytes(int64_t nv, int64_t nf);
 int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_t nf, int32_t thresh, int32_t smooth, void* ws, size_t ws_bytes,
                    uint8_t* removed, void* stream);
@@ -659,12 +718,26 @@ int mvsdf_mesh_trim(const float* verts, const float* normals, const float* color
  * Vertex clustering on the uniform grid of edge `cell` from `origin` (a HOST array of 3 doubles, or NULL = the low corner of the vertices' box) with
  * quadric-error placement (quadric != 0) or the clusters' means (0).  1 <= nv <= INT32_MAX, 1 <= nf <= INT32_MAX / 3, else the workspace query gives 0.
  * normals / colors ([nv][3] fp32) may be NULL.  mvsdf_mesh_simplify is the count pass: it waits for the stream (the host reads the box and the cluster
- * count) and leaves int64 {clusters, output vertices, output faces, degenerate faces, duplicate faces, vertices placed by the quadric, error bits
- * (1 non-finite vertex, 2 vertex id out of range, 4 cell index outside [0, 2^21))} at the start of the workspace.  With error bits set nothing else
+ * count) and leaves the MVSDF_SP_H_* words at the start of the workspace.  With error bits (MVSDF_SP_ERR_*) set nothing else
  * is valid.  counts_only != 0 skips the per-cluster sums and the placement: the counts are the same (quadric-placed stays 0), and no emit may follow.
  * mvsdf_mesh_simplify_emit, after a successful full count with the same workspace: the used clusters ascending, and the kept faces in their original
  * order and corner order, re-indexed.  out_normals / out_colors may be NULL (colours are 0 when the count pass got none); nv_cap / nf_cap bound
  * what is written. */
+enum {
+    MVSDF_SP_H_CLUSTERS = 0,    /* occupied clusters */
+    MVSDF_SP_H_VERTS = 1,       /* output vertices */
+    MVSDF_SP_H_FACES = 2,       /* output faces */
+    MVSDF_SP_H_DEGENERATE = 3,  /* degenerate faces */
+    MVSDF_SP_H_DUPLICATES = 4,  /* duplicate faces */
+    MVSDF_SP_H_PLACED = 5,      /* vertices placed by the quadric */
+    MVSDF_SP_H_ERR = 6,         /* error bits */
+    MVSDF_SP_H_WORDS = 7
+};
+enum {
+    MVSDF_SP_ERR_FINITE = 1,    /* a non-finite vertex */
+    MVSDF_SP_ERR_RANGE = 2,     /* a vertex id outside [0, nv) */
+    MVSDF_SP_ERR_CELLS = 4      /* a cell index outside [0, 2^21) */
+};
 size_t mvsdf_mesh_simplify_workspace_bytes(int64_t nv, int64_t nf);
 int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, double cell,
                         const double* origin, int32_t quadric, int32_t counts_only, void* ws, size_t ws_bytes, void* stream);
@@ -672,13 +745,50 @@ int mvsdf_mesh_simplify_emit(const int32_t* faces, int64_t nv, int64_t nf, void*
                              float* out_colors, int32_t* out_faces, int64_t nv_cap, int64_t nf_cap, void* stream);
 
 /* ---- DTU Chamfer evaluation (chamfer.hip; Python: mvsdf_amd/chamfer.py, which states the metric) ----
- * All four operations leave int64 results at the start of their workspace; fp64 throughout.  Error bits: 1 more points than max_points,
- * 2 vertex id out of range, 4 non-finite coordinate, 8 coordinate too far from the origin for the downsampling grid, 16 cell-table overflow,
- * 32 round limit reached, 64 tree-walk bound.  With error bits set nothing else is valid.
+ * All four operations leave int64 results at the start of their workspace; fp64 throughout.  Error bits: MVSDF_PC_ERR_*, the one numbering of
+ * the point-cloud modules (Chamfer, cloud cleaning, registration, normals, global registration).  With error bits set nothing else is valid.
  * mvsdf_chamfer_key: the visiting key splitmix64(seed ^ i) of point i.
- * Sampling, two calls: mvsdf_chamfer_sample_count waits for the stream -> {points (nv + samples), samples, error bits}; the caller allocates
+ * Sampling, two calls: mvsdf_chamfer_sample_count waits for the stream -> MVSDF_CH_SAMPLE_H_*; the caller allocates
  * out[points][3] and calls mvsdf_chamfer_sample_emit with the same workspace (out = the vertices, then the samples in face order; cap bounds the rows
  * written).  1 <= nv, nf <= INT32_MAX, else the workspace query gives 0. */
+enum {
+    MVSDF_PC_ERR_POINTS = 1,    /* sampling: more points than max_points */
+    MVSDF_PC_ERR_RANGE = 2,     /* sampling: a vertex id outside [0, nv) */
+    MVSDF_PC_ERR_FINITE = 4,    /* a non-finite coordinate (normals: or view centre) */
+    MVSDF_PC_ERR_COORD = 8,     /* a coordinate too far from the origin for the cell grid: downsampling; the voxel filter (an index of 2^21 or more) */
+    MVSDF_PC_ERR_HASH = 16,     /* the cell table's probe bound (cannot happen at load factor 1/2) */
+    MVSDF_PC_ERR_ROUNDS = 32,   /* the round limit of a host round loop (downsampling, components, orientation) was reached */
+    MVSDF_PC_ERR_WALK = 64,     /* a tree walk hit its bound (cannot happen) */
+    MVSDF_PC_ERR_NORMAL = 128,  /* a non-finite normal */
+    MVSDF_PC_ERR_INDEX = 256,   /* a neighbour or correspondence index out of range */
+    MVSDF_PC_ERR_CODE = 512     /* global registration: a code outside 0 .. 127 */
+};
+enum { MVSDF_PC_MAX_K = 32 };   /* the most neighbours per point (cloud cleaning, normals, global registration) */
+enum {
+    MVSDF_CH_SAMPLE_H_POINTS = 0,   /* points (nv + samples) */
+    MVSDF_CH_SAMPLE_H_SAMPLES = 1,  /* samples */
+    MVSDF_CH_SAMPLE_H_ERR = 2,      /* error bits */
+    MVSDF_CH_SAMPLE_H_WORDS = 3
+};
+enum {
+    MVSDF_CH_DOWN_H_KEPT = 0,       /* points kept */
+    MVSDF_CH_DOWN_H_ROUNDS = 1,     /* rounds run */
+    MVSDF_CH_DOWN_H_ERR = 2,        /* error bits */
+    MVSDF_CH_DOWN_H_WORDS = 3
+};
+enum {
+    MVSDF_CH_MASK_H_IN = 0,         /* rows of d_in */
+    MVSDF_CH_MASK_H_OBS = 1,        /* rows of d_obs */
+    MVSDF_CH_MASK_H_ABOVE = 2,      /* rows of s_above */
+    MVSDF_CH_MASK_H_ERR = 3,        /* error bits (MVSDF_PC_ERR_FINITE: a non-finite stl point) */
+    MVSDF_CH_MASK_H_WORDS = 4
+};
+enum {
+    MVSDF_CH_NEAR_H_COUNT = 0,      /* distances below the cut-off */
+    MVSDF_CH_NEAR_H_SUM = 1,        /* their fp64 sum (bits, fixed order) */
+    MVSDF_CH_NEAR_H_ERR = 2,        /* error bits */
+    MVSDF_CH_NEAR_H_WORDS = 3
+};
 uint64_t mvsdf_chamfer_key(uint64_t seed, int64_t i);
 size_t mvsdf_chamfer_sample_workspace_bytes(int64_t nv, int64_t nf);
 int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, int64_t max_points, void* ws, size_t ws_bytes,
@@ -686,32 +796,38 @@ int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t
 int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, void* ws, size_t ws_bytes, double* out,
                               int64_t cap, void* stream);
 /* The greedy radius filter: kept[n] (1 = kept) is the lexicographically-first maximal set with no two points within density (d^2 <= density^2) under
- * ascending keys.  Waits for the stream (its round loop reads counts) -> {kept, rounds, error bits}; stops with bit 32 after max_rounds rounds
+ * ascending keys.  Waits for the stream (its round loop reads counts) -> MVSDF_CH_DOWN_H_*; stops with MVSDF_PC_ERR_ROUNDS after max_rounds rounds
  * (n rounds always suffice).  1 <= n <= INT32_MAX / 4. */
 size_t mvsdf_chamfer_downsample_workspace_bytes(int64_t n);
 int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint64_t seed, int64_t max_rounds, void* ws, size_t ws_bytes, uint8_t* kept,
                              void* stream);
 /* The masks, no host wait: d_in / d_obs (capacity n rows) = the kept points inside the box / also observed, s_above (capacity m rows) = the stl points
- * above the plane, each in input order -> {rows of d_in, of d_obs, of s_above, error bits (4: a non-finite stl point)}.  box: HOST fp32 [9] = lo[3], hi[3], bb[0][3]; obs: uint8
+ * above the plane, each in input order -> MVSDF_CH_MASK_H_*.  box: HOST fp32 [9] = lo[3], hi[3], bb[0][3]; obs: uint8
  * [X][Y][Z] on the device, obs_shape: HOST int64 [3]; plane: HOST fp64 [4]. */
 size_t mvsdf_chamfer_mask_workspace_bytes(int64_t n, int64_t m);
 int mvsdf_chamfer_mask(const double* pts, const uint8_t* kept, int64_t n, const double* stl, int64_t m, const float* box, double res, const uint8_t* obs,
                        const int64_t* obs_shape, const double* plane, void* ws, size_t ws_bytes, double* d_in, double* d_obs, double* s_above, void* stream);
-/* dist[q] = min over refs of sqrt((dx dx + dy dy) + dz dz), exact, +inf where it is not < max_dist.  Waits for the stream -> {distances below the
- * cut-off, their fp64 sum (bits, fixed order), error bits}.  0 <= nq, 1 <= nr <= INT32_MAX. */
+/* dist[q] = min over refs of sqrt((dx dx + dy dy) + dz dz), exact, +inf where it is not < max_dist.  Waits for the stream -> MVSDF_CH_NEAR_H_*.
+ * 0 <= nq, 1 <= nr <= INT32_MAX. */
 size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr);
 int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs, int64_t nr, double max_dist, void* ws, size_t ws_bytes, double* dist,
                           void* stream);
 
 /* ---- Depth-map fusion (fusion.hip; Python: mvsdf_amd/fusion.py, which states the definition) ----
  * Two calls.  mvsdf_fusion_fuse validates every argument on the host, then (no host wait) writes masked[V][H][W], fused[V][H][W], counts[V][H][W]
- * and leaves int64 {points kept, error bits} at the start of the workspace.  Error bits: 1 a non-finite matrix or threshold, 2 a pair index outside
- * [0, V), 4 view < 1, 8 shapes (V < 1, H or W < 2, V*H*W > 2^40, H*W > INT32_MAX, a pair list longer than view); with any set nothing is launched.
+ * and leaves MVSDF_RES_H_* at the start of the workspace.  Error bits: MVSDF_FU_ERR_*; with any set nothing is launched.
  * depths fp32 [V][H][W] and probs fp32 [V][3][H][W] (or NULL) on the device; pthresh: HOST fp32 [3]; pair_off: HOST int32 [V + 1] (pair_off[0] = 0),
  * pair_src: HOST int32 [pair_off[V]], the source views of every view already cut to its first `view` entries; mats: HOST fp64, per pair slot T_rs
  * then T_sr (row-major 4x4 each), followed by Pinv of every view.  The host arrays must stay alive until the caller has read the header.
  * mvsdf_fusion_emit (same workspace, same V, H, W, npairs = pair_off[V]) writes the kept pixels in (view, y, x) order: points fp64 [cap][3],
  * colors uint8 [cap][3] from images uint8 [V][H][W][3] (both NULL: no colours), view / pixel int32 [cap]; rows at or beyond cap are not written. */
+enum {
+    MVSDF_FU_ERR_FINITE = 1,    /* a non-finite matrix entry or threshold; mvsdf_fusion_normals: or a NaN or negative jump */
+    MVSDF_FU_ERR_PAIR = 2,      /* a pair index outside [0, V) */
+    MVSDF_FU_ERR_VIEW = 4,      /* view < 1 */
+    MVSDF_FU_ERR_SHAPE = 8,     /* V < 1, H or W < 2, V*H*W > 2^40, H*W > INT32_MAX, a pair list longer than view; mvsdf_fusion_normals: or n < 1 */
+    MVSDF_FU_ERR_INDEX = 16     /* mvsdf_fusion_normals: a view / pixel index outside the maps (found on the device; that point's normal is 0) */
+};
 size_t mvsdf_fusion_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t npairs);
 int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthresh, int64_t V, int64_t H, int64_t W, const int32_t* pair_off,
                       const int32_t* pair_src, const double* mats, int32_t view, int32_t vthresh, double pix_thresh, double dep_thresh, void* ws,
@@ -720,9 +836,8 @@ int mvsdf_fusion_emit(const uint8_t* images, int64_t V, int64_t H, int64_t W, in
                       uint8_t* colors, int32_t* view, int32_t* pixel, int64_t cap, void* stream);
 /* Normals of fused points (fusion.py: depth_normals): one lane per point reads fused fp32 [V][H][W] and view / pixel int32 [n] (device) and writes
  * normals fp64 [n][3].  mats: HOST fp64 [V][19], Pinv of the view (row-major 4x4) then its camera centre; it must stay alive until the caller has
- * read the header.  Leaves int64 {0, error bits} at the start of the workspace, no host wait.  Error bits: 1 a non-finite matrix entry, a NaN or
- * negative jump; 8 shapes (V < 1, H or W < 2, H*W > INT32_MAX, n < 1); 16 a view / pixel index outside the maps (found on the device; that point's
- * normal is 0). */
+ * read the header.  Leaves MVSDF_RES_H_* at the start of the workspace, no host wait.  Error bits: MVSDF_FU_ERR_FINITE, _SHAPE
+ * and _INDEX. */
 size_t mvsdf_fusion_normals_workspace_bytes(int64_t V);
 int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, const int32_t* view, const int32_t* pixel, int64_t n, const double* mats,
                          double jump, void* ws, size_t ws_bytes, double* normals, void* stream);
@@ -730,12 +845,24 @@ int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, co
 /* ---- Poisson surface reconstruction (poisson.hip; Python: mvsdf_amd/poisson.py, which states the definition) ----
  * mvsdf_poisson_reconstruct validates its scalar arguments on the host, then (no host wait) runs the stages whose bits are set in `stages` (1 the
  * splat and the right-hand side, 2 the multigrid solve, 4 the isovalue; a later stage needs the earlier ones to have run on the same workspace; 7 =
- * everything) and leaves int64 {points used, error bits, T, residual0, residual} (the last three: fp64 bit patterns) at the start of the workspace.
- * Error bits: 1 a non-finite coordinate, normal (found on the device), origin or voxel; 2 depth outside [2, 10], cycles < 0, sweeps < 1 or voxel <= 0;
- * 4 n < 1 or n > INT32_MAX.  points / normals fp64 [n][3] on the device; origin: HOST fp64 [3]; N = 2^depth + 1; chi and density fp64 [N][N][N],
+ * everything) and leaves MVSDF_PO_H_* at the start of the workspace.  Error bits: MVSDF_PO_ERR_*.  points / normals fp64 [n][3] on the device; origin: HOST fp64 [3]; N = 2^depth + 1; chi and density fp64 [N][N][N],
  * values fp64 [n] (the first `points used` rows are the c_i, the rest 0).  workspace bytes: about 43 per lattice point + 9 per point; 0 = refused.
  * mvsdf_poisson_valid: valid uint8 [N][N][N] = density > min_density dilated `dilate` times over the 6-neighbourhood (tmp: uint8 [N][N][N], needed
  * when dilate > 0).  mvsdf_poisson_volume: out[i] = (float)(chi[i] - iso) for count values.  Neither waits. */
+enum {
+    MVSDF_PO_H_USED = 0,        /* points used */
+    MVSDF_PO_H_ERR = 1,         /* error bits */
+    MVSDF_PO_H_T = 2,           /* T (fp64 bits) */
+    MVSDF_PO_H_RESIDUAL0 = 3,   /* the solve's first residual (fp64 bits) */
+    MVSDF_PO_H_RESIDUAL = 4,    /* its last residual (fp64 bits) */
+    MVSDF_PO_H_WORDS = 5
+};
+enum {
+    MVSDF_PO_ERR_FINITE = 1,    /* a non-finite coordinate, normal (found on the device), origin or voxel */
+    MVSDF_PO_ERR_RANGE = 2,     /* depth outside [MVSDF_PO_MIN_DEPTH, MVSDF_PO_MAX_DEPTH], cycles < 0, sweeps < 1 or voxel <= 0 */
+    MVSDF_PO_ERR_SHAPE = 4      /* n < 1 or n > INT32_MAX */
+};
+enum { MVSDF_PO_MIN_DEPTH = 2, MVSDF_PO_MAX_DEPTH = 10 };
 size_t mvsdf_poisson_workspace_bytes(int64_t n, int32_t depth);
 int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64_t n, const double* origin, double voxel, int32_t depth, int32_t cycles,
                               int32_t sweeps, int32_t stages, void* ws, size_t ws_bytes, double* chi, double* density, double* values, void* stream);
@@ -744,15 +871,19 @@ int mvsdf_poisson_volume(const double* chi, int64_t count, double iso, float* ou
 
 /* ---- TSDF fusion (tsdf.hip; Python: mvsdf_amd/tsdf.py, which states the definition) ----
  * mvsdf_tsdf_integrate validates every argument on the host, then (no host wait) writes tsdf fp32, weight int32 and valid uint8, each
- * [dims[0]][dims[1]][dims[2]] on the device, and leaves int64 {0, error bits} at the start of the workspace.  Error bits: 1 a non-finite matrix,
- * origin, voxel or trunc, or a NaN jump; 2 a view index outside [0, V); 4 voxel <= 0, trunc <= 0, jump < 0 or min_views < 1; 8 shapes (V < 1, H or
- * W < 2, H*W > INT32_MAX, nviews < 1, a dim below 2 or above INT32_MAX, more than 2^40 lattice points); with any set nothing is launched.
+ * [dims[0]][dims[1]][dims[2]] on the device, and leaves MVSDF_RES_H_* at the start of the workspace.  Error bits: MVSDF_TS_ERR_*; with any set nothing is launched.
  * depths fp32 [V][H][W] on the device (a texel that is <= 0 or not finite is a hole); mats: HOST fp64 [nviews][16], P of the q-th visited view
  * (row-major 4x4); views: HOST int32 [nviews], the depth map of the q-th visited view; origin: HOST fp64 [3]; dims: HOST int64 [3].  The host
  * arrays must stay alive until the caller has read the header.
  * Marching cubes under a validity mask (conventions: mvsdf_amd/mesh.py): like mvsdf_mc_count / mvsdf_mc_emit with valid uint8
- * [shape[0]][shape[1]][shape[2]] (contiguous) beside the volume; the workspace starts with int64 {vertices, faces, non-finite VALID value seen}.
+ * [shape[0]][shape[1]][shape[2]] (contiguous) beside the volume; the workspace starts with MVSDF_MC_H_*.
  * workspace bytes: 6 per grid point + O(points / 1024); 0 = refused. */
+enum {
+    MVSDF_TS_ERR_FINITE = 1,    /* a non-finite matrix, origin, voxel or trunc, or a NaN jump */
+    MVSDF_TS_ERR_VIEW = 2,      /* a view index outside [0, V) */
+    MVSDF_TS_ERR_RANGE = 4,     /* voxel <= 0, trunc <= 0, jump < 0 or min_views < 1 */
+    MVSDF_TS_ERR_SHAPE = 8      /* V < 1, H or W < 2, H*W > INT32_MAX, nviews < 1, a dim below 2 or above INT32_MAX, more than 2^40 lattice points */
+};
 size_t mvsdf_tsdf_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t nviews);
 int mvsdf_tsdf_integrate(const float* depths, int64_t V, int64_t H, int64_t W, const double* mats, const int32_t* views, int64_t nviews,
                          const double* origin, double voxel, const int64_t* dims, double trunc, double jump, int32_t min_views, void* ws,
@@ -766,18 +897,32 @@ int mvsdf_mcm_emit(const float* vol, const uint8_t* valid, const int64_t* shape,
 
 /* ---- Plane-sweep stereo (stereo.hip; Python: mvsdf_amd/stereo.py, which states the definition) ----
  * mvsdf_stereo_normalize: feats fp32 [n][C] on the device -> out fp32 [n][C], every texel divided by its fp64 norm (0 where the norm is 0); hdr: 16
- * device bytes that receive int64 {0, error bits} (bit 1: a non-finite feature).  mvsdf_stereo_patches: images uint8 [V][H][W][3] -> out fp32
+ * device bytes that receive MVSDF_RES_H_* (MVSDF_PS_ERR_FINITE: a non-finite feature).  mvsdf_stereo_patches: images uint8 [V][H][W][3] -> out fp32
  * [V][H][W][(2 radius + 1)^2], the mean-free grey patch with a clamped border (0 <= radius <= 15).  Neither waits for the host.
  * mvsdf_stereo_sweep validates every argument on the host, then (no host wait) sweeps the views views[0 .. nviews) in turn over desc fp32
  * [V][R][S][C] (device) and writes, for each of them, depths[view][R][S], probs[view][3][R][S], best_k[view][R][S] (-1: no valid hypothesis) and
- * counts[view][R][S]; other views' outputs are not touched.  It leaves int64 {0, error bits} at the start of the workspace.  Error bits: 1 a
- * non-finite descriptor, matrix entry, depth_min or interval, 2 a view or pair index outside [0, V), 4 a hypothesis count outside [1, 65535], 8 shapes
- * (V < 1, R or S < 2, C < 1, R*S > INT32_MAX, R*S*D or V*R*S*C > 2^40, more than 255 sources for a view); with any but a non-finite descriptor set
+ * counts[view][R][S]; other views' outputs are not touched.  It leaves MVSDF_RES_H_* at the start of the workspace.  Error bits: MVSDF_PS_ERR_*; with any but a non-finite descriptor set
  * nothing is launched.  HOST arrays, alive until the caller has read the header: views int32 [nviews]; pair_off int32 [nviews + 1] (pair_off[0] = 0)
  * and pair_src int32 [pair_off[nviews]], the sources of views[i]; mats fp64 [pair_off[nviews]][16], T_rs per pair slot (row-major 4x4); ranges fp64
  * [nviews][2] = {depth_min, interval}; nhyp int32 [nviews].  The workspace (mvsdf_stereo_workspace_bytes with D = the largest nhyp and npairs =
  * pair_off[nviews]; 0 beyond the limits) afterwards holds the last view's score volume, fp64 [D][R][S] with a quiet NaN where a hypothesis is
  * invalid, at byte offset mvsdf_stereo_volume_offset (same arguments). */
+enum {
+    MVSDF_PS_ERR_FINITE = 1,    /* a non-finite descriptor / feature, matrix entry, depth_min or interval; mvsdf_stereo_regularize: an infinite score */
+    MVSDF_PS_ERR_PAIR = 2,      /* a view or pair index outside [0, V) */
+    MVSDF_PS_ERR_DEPTHS = 4,    /* a hypothesis count outside [1, MVSDF_PS_MAX_D] */
+    MVSDF_PS_ERR_SHAPE = 8,     /* V < 1, R or S < 2, C < 1, R*S > INT32_MAX, R*S*D or V*R*S*C > 2^40, more than MVSDF_PS_MAX_SRC sources for a view */
+    MVSDF_PS_ERR_SGM = 16,      /* the regularisation's p1, p2 or paths refused, or a hypothesis count above MVSDF_PS_MAX_D_SGM */
+    MVSDF_PS_ERR_BAND = 32,     /* the band's depth_num outside [1, MVSDF_PS_MAX_D_BAND], a step that is not finite and positive, a view listed twice */
+    MVSDF_PS_ERR_CENTRE = 64    /* an infinite centre (found on the device) */
+};
+enum {
+    MVSDF_PS_MAX_D = 65535,     /* hypotheses of a sweep */
+    MVSDF_PS_MAX_SRC = 255,     /* sources of a view: n_k travels as a byte */
+    MVSDF_PS_MAX_D_SGM = 4096,  /* the most hypotheses the regularisation takes */
+    MVSDF_PS_MAX_D_BAND = 64,   /* the most hypotheses of a band: the tile's scores and counts are then 36 KB of LDS */
+    MVSDF_PS_MAX_ELEMS_LOG2 = 40    /* elements of a score volume or a descriptor array: 2^40 */
+};
 size_t mvsdf_stereo_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs);
 size_t mvsdf_stereo_volume_offset(int64_t R, int64_t S, int64_t D, int64_t npairs);
 int mvsdf_stereo_normalize(const float* feats, int64_t n, int64_t C, float* out, void* hdr, void* stream);
@@ -787,12 +932,12 @@ int mvsdf_stereo_sweep(const float* desc, int64_t V, int64_t R, int64_t S, int64
                        float* probs, int32_t* best_k, int32_t* counts, void* stream);
 /* Semi-global regularisation of a score volume (the definition: mvsdf_amd/stereo.py).  mvsdf_stereo_regularize: score fp64 [D][R][S] on the device
  * (a NaN = an invalid hypothesis) -> out fp64 [D][R][S], the regularised scores A (NaN where the input is); out must not overlap score.  paths is 4 or
- * 8, 0 <= p1 <= p2 finite, R and S >= 1, 1 <= D <= 4096 (MAX_D_SGM), R*S <= INT32_MAX, R*S*D <= 2^40.  ws: mvsdf_stereo_sgm_workspace_bytes (0
- * beyond the limits) device bytes; they receive int64 {0, error bits}: 1 an infinite score (out is then not valid), 16 a refused argument (nothing is
- * launched).  No host wait unless an argument is refused.
+ * 8, 0 <= p1 <= p2 finite, R and S >= 1, 1 <= D <= MVSDF_PS_MAX_D_SGM, R*S <= INT32_MAX, R*S*D <= 2^40.  ws: mvsdf_stereo_sgm_workspace_bytes (0
+ * beyond the limits) device bytes; they receive MVSDF_RES_H_*: MVSDF_PS_ERR_FINITE an infinite score (out is then not valid), MVSDF_PS_ERR_SGM a
+ * refused argument (nothing is launched).  No host wait unless an argument is refused.
  * mvsdf_stereo_sweep_sgm is mvsdf_stereo_sweep with the regularisation between the scores and the pick of every view: the winner, the refinement and
- * prob2 come from A, prob1 is the raw score at the winner, prob3 and counts its n_k.  Error bit 16: p1, p2 or paths refused, or a hypothesis count
- * above 4096.  Its workspace is mvsdf_stereo_sweep_sgm_workspace_bytes (same arguments as mvsdf_stereo_workspace_bytes); afterwards the last view's raw
+ * prob2 come from A, prob1 is the raw score at the winner, prob3 and counts its n_k.  MVSDF_PS_ERR_SGM: p1, p2 or paths refused, or a hypothesis count
+ * above MVSDF_PS_MAX_D_SGM.  Its workspace is mvsdf_stereo_sweep_sgm_workspace_bytes (same arguments as mvsdf_stereo_workspace_bytes); afterwards the last view's raw
  * volume is at mvsdf_stereo_volume_offset and its regularised volume, fp64 [D][R][S], at byte offset mvsdf_stereo_workspace_bytes. */
 size_t mvsdf_stereo_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D);
 int mvsdf_stereo_regularize(const double* score, int64_t R, int64_t S, int64_t D, double p1, double p2, int32_t paths, void* ws, size_t ws_bytes,
@@ -804,11 +949,11 @@ int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, i
                            void* stream);
 /* The cascade (mvsdf_amd/stereo.py, "Cascade").  mvsdf_stereo_upsample: depth fp32 [V][r][s] and best_k int32 [V][r][s] of a coarser sweep (device)
  * -> out fp64 [V][R][S], the centres at the finer size (a quiet NaN where no parent of a pixel has a winner); r and s >= 2, R and S >= 1; no host wait.
- * mvsdf_stereo_band is mvsdf_stereo_sweep over a band of depth_num hypotheses (1 .. 64, MAX_D_BAND) per pixel, centres[view][R][S] fp64 on the device
+ * mvsdf_stereo_band is mvsdf_stereo_sweep over a band of depth_num hypotheses (1 .. MVSDF_PS_MAX_D_BAND) per pixel, centres[view][R][S] fp64 on the device
  * (NaN: no centre) + (k - depth_num / 2) * steps[i]: all of views[0 .. nviews) in one launch (1 <= nviews <= 65535, no view twice), no score volume
  * in global memory, best_k = the index within the band.  steps: HOST fp64 [nviews], finite and positive; the other host arrays as
- * mvsdf_stereo_sweep's.  Further error bits: 32 depth_num, a step or a repeated view refused (nothing is launched), 64 an infinite centre (found on
- * the device; the outputs are then not valid).  The workspace (mvsdf_stereo_band_workspace_bytes, 0 beyond the limits) holds the header, the per-view
+ * mvsdf_stereo_sweep's.  Further error bits: MVSDF_PS_ERR_BAND (nothing is launched) and MVSDF_PS_ERR_CENTRE
+ * (the outputs are then not valid).  The workspace (mvsdf_stereo_band_workspace_bytes, 0 beyond the limits) holds the header, the per-view
  * arrays, the matrices and the source indices: it depends on nviews and npairs = pair_off[nviews] only, not on depth_num, R or S. */
 int mvsdf_stereo_upsample(const float* depth, const int32_t* best_k, int64_t V, int64_t r, int64_t s, int64_t R, int64_t S, double* out, void* stream);
 size_t mvsdf_stereo_band_workspace_bytes(int64_t R, int64_t S, int64_t depth_num, int64_t nviews, int64_t npairs);
@@ -818,18 +963,29 @@ int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_
 
 /* ---- Point-cloud cleaning (cloud.hip; Python: mvsdf_amd/cloud.py, which states the definition) ----
  * pts fp64 [n][3] on the device, fp64 throughout.  mvsdf_cloud_knn, _components and _clean share one workspace (mvsdf_cloud_clean_workspace_bytes,
- * 0 unless 2 <= n <= INT32_MAX) and leave int64 {n_passed, n_clusters, largest, n_kept, m (fp64 bits), threshold (bits), eps (bits), rounds,
- * error bits} at its start; entries a call does not compute are 0.  Error bits as the Chamfer calls: 4 a non-finite coordinate, 32 the round
- * limit of the components loop, 64 a tree-walk bound; with any set nothing else is valid.  Every argument is validated before the first launch;
+ * 0 unless 2 <= n <= INT32_MAX) and leave MVSDF_CLOUD_H_* at its start; entries a call does not compute are 0.  Error bits: MVSDF_PC_ERR_FINITE, _ROUNDS (the
+ * components loop) and _WALK; with any set nothing else is valid.  Every argument is validated before the first launch;
  * each call waits for the stream once for the coordinate check, _components and _clean once more per round of the components loop (normally one).
  * mvsdf_cloud_knn: d[i] = the mean of sqrt over the k smallest (dx dx + dy dy) + dz dz from point i to every other point (by index), summed in
- * ascending order.  1 <= k <= 32, n >= k + 1.
+ * ascending order.  1 <= k <= MVSDF_PC_MAX_K, n >= k + 1.
  * mvsdf_cloud_components: labels[i] = the smallest index in i's connected component under d2 <= eps * eps (every point takes part).
  * mvsdf_cloud_clean: d as above; m = the element of rank (n - 1) / 2 of d; a point passes iff d <= knn_ratio * m; eps = eps_ratio * m; labels over
  * the passed points (-1 elsewhere); keep[i] = 1 iff i passed and its component holds >= cluster_frac * (the largest component's count) points.
  * Ratios finite and > 0, cluster_frac <= 1.
  * mvsdf_cloud_compact (no host wait): the rows with keep != 0 of pts, colors uint8 [n][3], a and b int32 [n] (each of the three may be NULL with
- * its output) in input order; rows at or beyond cap are not written -> int64 {rows kept}. */
+ * its output) in input order; rows at or beyond cap are not written -> MVSDF_ROWS_H_*. */
+enum {
+    MVSDF_CLOUD_H_PASSED = 0,       /* points that passed the k-NN test */
+    MVSDF_CLOUD_H_CLUSTERS = 1,     /* components */
+    MVSDF_CLOUD_H_LARGEST = 2,      /* the largest component's count */
+    MVSDF_CLOUD_H_KEPT = 3,         /* points kept */
+    MVSDF_CLOUD_H_M = 4,            /* m (fp64 bits) */
+    MVSDF_CLOUD_H_THRESHOLD = 5,    /* knn_ratio * m (fp64 bits) */
+    MVSDF_CLOUD_H_EPS = 6,          /* eps (fp64 bits) */
+    MVSDF_CLOUD_H_ROUNDS = 7,       /* rounds of the components loop */
+    MVSDF_CLOUD_H_ERR = 8,          /* error bits */
+    MVSDF_CLOUD_H_WORDS = 9
+};
 size_t mvsdf_cloud_clean_workspace_bytes(int64_t n);
 size_t mvsdf_cloud_compact_workspace_bytes(int64_t n);
 int mvsdf_cloud_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t ws_bytes, double* d, void* stream);
@@ -843,20 +999,34 @@ int mvsdf_cloud_compact(const double* pts, const uint8_t* colors, const int32_t*
  * A triangle mesh (verts fp32 [nv][3], faces int32 [nf][3], on the device) drawn into `views` cameras of H x W pixels.  P: fp64 [views][4][4] on the
  * DEVICE, world -> pixels, rows 0..2 used, row 2 the camera depth; pixel (x, y) has its centre at (x + pixel_center, y + pixel_center), pixel_center
  * 0.5 or 0.0.  fp64 throughout, no clipping (a face with a vertex not in front of its camera is skipped), no back-face culling.
- * mvsdf_raster_draw fills the workspace's key buffer (mvsdf_raster_workspace_bytes; 0 unless 0 <= nv, nf <= INT32_MAX, 1 <= views <= 65535, H and W
+ * mvsdf_raster_draw fills the workspace's key buffer (mvsdf_raster_workspace_bytes; 0 unless 0 <= nv, nf <= INT32_MAX, 1 <= views <= MVSDF_RA_MAX_VIEWS, H and W
  * >= 2, H * W and nf * views <= INT32_MAX, views * H * W <= 2^40): per pixel the minimum of (bits(fp32 depth) << 32) | face id over the faces that
  * cover the pixel centre, so the result does not depend on the schedule.  Faces whose clamped pixel box holds more than large_face_pixels pixels
  * are compacted to a list and drawn by one wave each; the others by one lane each.  flags: 1 = issue every atomic (no plain-load test before it),
- * 2 = count the atomics issued and the covered pixels (measurement builds of the call; slower).  The workspace starts with int64 {error bits,
- * listed (face, view) items, atomics issued, covered pixels}.  Error bits: 1 a camera entry is NaN or infinite, 2 a face refers to a vertex
- * outside [0, nv) (such a face is not drawn); with any set nothing else is valid.  A chunk of the views is drawn by passing P + 16 * first.
+ * 2 = count the atomics issued and the covered pixels (measurement builds of the call; slower).  The workspace starts with MVSDF_RA_H_*.
+ * Error bits: MVSDF_RA_ERR_*; with any set nothing else is valid.  A chunk of the views is drawn by passing P + 16 * first.
  * mvsdf_raster_resolve (same workspace, views, H, W) writes depth fp32 [views][H][W] (0 where nothing was drawn) and face int32 (-1).
  * mvsdf_raster_visibility: vis uint8 [views][nv] = the vertex is in front, the pixel whose centre is nearest lies in the image, holds a depth
- * D > 0 with z <= D * (1 + depth_tol), and (masks uint8 [views][H][W] or NULL) its mask is set.  The workspace is its 256-byte header (error bit 1).
+ * D > 0 with z <= D * (1 + depth_tol), and (masks uint8 [views][H][W] or NULL) its mask is set.  The workspace is its 256-byte header (MVSDF_RA_H_ERR: MVSDF_RA_ERR_FINITE).
  * mvsdf_raster_colors: per vertex, over the views in order, where visible as above: weight (n . g) / |g| with g = centers[v] - X (fp64 [views][3] on
  * the device) if above cos_min, a zero normal weighing 1 with ignore_normals and skipping the vertex without; images uint8 [views][H][W][3]
  * sampled bilinearly at (sx - pixel_center, sy - pixel_center); colors fp32 [nv][3] = sum / weights / 255 or the fallback, n_views int32 [nv] the
  * views that contributed.  No call waits for the host. */
+enum {
+    MVSDF_RA_H_ERR = 0,         /* error bits */
+    MVSDF_RA_H_ITEMS = 1,       /* listed (face, view) items */
+    MVSDF_RA_H_ATOMICS = 2,     /* atomics issued (flags 2) */
+    MVSDF_RA_H_COVERED = 3,     /* covered pixels (flags 2) */
+    MVSDF_RA_H_WORDS = 4
+};
+enum {
+    MVSDF_RA_ERR_FINITE = 1,    /* a camera entry is NaN or infinite */
+    MVSDF_RA_ERR_INDEX = 2      /* a face refers to a vertex outside [0, nv) (such a face is not drawn) */
+};
+enum {
+    MVSDF_RA_MAX_VIEWS = 65535,     /* cameras of a raster or texture call */
+    MVSDF_RA_MAX_PIXELS_LOG2 = 40   /* views * H * W: 2^40 */
+};
 size_t mvsdf_raster_workspace_bytes(int64_t nv, int64_t nf, int64_t views, int64_t H, int64_t W);
 int mvsdf_raster_draw(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, const double* P, int64_t views, int64_t H, int64_t W,
                       double pixel_center, int64_t large_face_pixels, int32_t flags, void* ws, size_t ws_bytes, void* stream);
@@ -872,20 +1042,34 @@ int mvsdf_raster_colors(const float* verts, const float* normals, int64_t nv, co
  * A texture image for a mesh from the photographs: every face labelled with the view that sees it largest, one patch per face (a half of a square
  * cell of edge n = 4 << class, class 0 .. 6) packed along a Morton curve over blocks of 4 x 4 texels, the classes in descending order, and the
  * texels filled by an affine copy of the face's image triangle.  Mesh, P, centers, depth, masks, images and pixel_center as in the raster calls,
- * all on the device; fp64 throughout; 0 <= nf <= 2^28.  Every call starts by zeroing the 256-byte header of its workspace; no call waits.
+ * all on the device; fp64 throughout; 0 <= nf <= 2^MVSDF_TX_MAX_FACES_LOG2.  Every call starts by zeroing the 256-byte header of its workspace; no call waits.
  * mvsdf_texture_face_views: label int32 [nf] (-1: no view), score fp64 [nf] (|A| in that view, 0 without one) and screen fp64 [nf][6] (sx, sy of
- * the three corners in that view, 0 without one).  Header: int64 {error bits}: 1 a camera or centre entry is NaN or infinite, 2 a face refers to a
- * vertex outside [0, nv) (it stays unlabelled).
- * mvsdf_texture_classify: cls uint8 [nf] at a texel density (finite, > 0).  Header: int64 {0, counts[7]}, the faces per class.
+ * the three corners in that view, 0 without one).  Header: MVSDF_TX_H_ERR: MVSDF_TX_ERR_FINITE, MVSDF_TX_ERR_INDEX (the face stays
+ * unlabelled).
+ * mvsdf_texture_classify: cls uint8 [nf] at a texel density (finite, > 0).  Header: the seven words from MVSDF_TX_H_COUNTS.
  * The atlas follows from the counts alone: T = sum over the classes of ceil(count / 2) * 4^class blocks, B the smallest integer with T <= 2^B,
- * Wt = 4 << ceil(B / 2) by Ht = 4 << floor(B / 2) texels; Wt beyond 32768 is refused.
+ * Wt = 4 << ceil(B / 2) by Ht = 4 << floor(B / 2) texels; Wt beyond MVSDF_TX_MAX_SIDE is refused.
  * mvsdf_texture_pack (workspace: mvsdf_texture_workspace_bytes(nf), 0 beyond the limit; counts int64 [7] on the HOST, as classify left them): order int32
- * [nf] (the faces by class descending, index ascending), patch int32 [nf][4] = {x0, y0, n, half}, uv fp32 [nf][3][2].  Header: int64 {error bits,
- * flagged total}: 4 the counts are not those of cls (nothing else is valid).
+ * [nf] (the faces by class descending, index ascending), patch int32 [nf][4] = {x0, y0, n, half}, uv fp32 [nf][3][2].  Header: MVSDF_TX_H_ERR, the flagged total behind it:
+ * MVSDF_TX_ERR_COUNTS (nothing else is valid).
  * mvsdf_texture_fill: texture uint8 [Ht][Wt][3] and valid uint8 [Ht][Wt] of the atlas those counts give (another Ht x Wt is refused), both
  * 4-byte aligned; texels nobody owns, and those of
  * unlabelled faces, get the fallback (each 0 .. 255) and valid 0.  flags 1: the screen coordinates are projected again from verts / faces / P
  * (the same bits) instead of read from `screen`; without it verts, faces and P may be NULL. */
+enum {
+    MVSDF_TX_H_ERR = 0,         /* error bits */
+    MVSDF_TX_H_COUNTS = 1,      /* mvsdf_texture_classify: the faces per class, seven words; mvsdf_texture_pack: the flagged total in the first */
+    MVSDF_TX_H_WORDS = 8
+};
+enum {                          /* bits 1 and 2 are MVSDF_RA_ERR_*'s */
+    MVSDF_TX_ERR_FINITE = 1,    /* a camera or centre entry is NaN or infinite */
+    MVSDF_TX_ERR_INDEX = 2,     /* a face refers to a vertex outside [0, nv) */
+    MVSDF_TX_ERR_COUNTS = 4     /* the class counts passed to the pack are not those of cls */
+};
+enum {
+    MVSDF_TX_MAX_SIDE = 32768,      /* texels: block coordinates fit 13 bits, block indices 26 */
+    MVSDF_TX_MAX_FACES_LOG2 = 28    /* faces: 2^28 */
+};
 size_t mvsdf_texture_workspace_bytes(int64_t nf);
 int mvsdf_texture_face_views(const float* verts, const float* normals, const int32_t* faces, int64_t nv, int64_t nf, const double* P,
                              const double* centers, int64_t views, int64_t H, int64_t W, double pixel_center, const float* depth, const uint8_t* masks,
@@ -926,18 +1110,23 @@ int mvsdf_featext_layer(int kind, const float* weight, const float* bias, int co
 
 /* ---- View selection (viewsel.hip; Python: mvsdf_amd/viewsel.py, which states the definition) ----
  * The pairwise score behind pair.txt from points fp64 [P][3], camera centres fp64 [V][3] and visibility, all on the device; fp64 throughout with the
- * written-out atan2 / exp of csrc/det_math64.h.  1 <= V <= 65535, 0 <= P <= INT32_MAX.  hdr: 256 device bytes, int64 {0, error bits}; the two pack
- * calls reset it, the other calls OR into it, and the caller reads it once at the end.  Error bits: 1 a non-finite point, centre or extrinsic entry,
- * 2 a track entry outside [0, V) (or track offsets that do not ascend within [0, nnz]), 4 V or P outside the limits above (nothing is launched).
+ * written-out atan2 / exp of csrc/det_math64.h.  1 <= V <= MVSDF_VS_MAX_VIEWS, 0 <= P <= INT32_MAX.  hdr: 256 device bytes, MVSDF_RES_H_*; the two pack
+ * calls reset it, the other calls OR into it, and the caller reads it once at the end.  Error bits: MVSDF_VS_ERR_*.
  * mvsdf_viewsel_pack_dense: vis uint8 [V][P] (non-zero = seen) -> bits uint64 [P][ceil(V / 64)] (mvsdf_viewsel_bits_bytes; 0 beyond the limits), bit
  * v mod 64 of word v / 64 of row p.  mvsdf_viewsel_pack_tracks: the same from CSR tracks, track_off int64 [P + 1] and track_view int32 [nnz]; a
  * duplicate entry counts once.
  * mvsdf_viewsel_scores: scores fp64 [V][V] (symmetric, zero diagonal) and counts int64 [V][V] (common points; the diagonal: the points a view sees);
  * the workspace (mvsdf_viewsel_workspace_bytes) holds the int64 sums of the quantised weights.  theta0 finite, sigma1 and sigma2 finite and > 0.
  * mvsdf_viewsel_depths: z fp64 [nviews][P] for the views first .. first + nviews: ((e0*x + e1*y) + e2*z) + e3 with e = ext_row2[v] (fp64 [V][4] on the
- * device, row 2 of the extrinsic) where view v sees the point, +inf elsewhere.  P >= 1.  No call waits for the host (but for error bit 4).
+ * device, row 2 of the extrinsic) where view v sees the point, +inf elsewhere.  P >= 1.  No call waits for the host (but for MVSDF_VS_ERR_SHAPE).
  * mvsdf_viewsel_weights_host is a HOST function (no GPU needed): theta [n] in degrees and the quantised weight wq [n] of the definition for n pairs
  * of vectors a = c_i - p, b = c_j - p (fp64 [n][3], host memory), evaluated by the functions the kernel runs. */
+enum {
+    MVSDF_VS_ERR_FINITE = 1,    /* a non-finite point, centre or extrinsic entry */
+    MVSDF_VS_ERR_TRACK = 2,     /* a track entry outside [0, V) (or track offsets that do not ascend within [0, nnz]) */
+    MVSDF_VS_ERR_SHAPE = 4      /* V or P outside the limits above (nothing is launched) */
+};
+enum { MVSDF_VS_MAX_VIEWS = 65535 };    /* views of a visibility bit matrix (view selection, normals) */
 size_t mvsdf_viewsel_bits_bytes(int64_t V, int64_t P);
 size_t mvsdf_viewsel_workspace_bytes(int64_t V);
 int mvsdf_viewsel_pack_dense(const uint8_t* vis, int64_t V, int64_t P, void* bits, void* hdr, void* stream);
@@ -955,11 +1144,15 @@ int mvsdf_viewsel_weights_host(const double* a, const double* b, int64_t n, doub
  * distorted camera and the model's coefficients, the unused ones 0.  pinhole / out_pinhole: HOST fp64 [4] = fx, fy, cx, cy of the undistorted view.
  * Every value must be finite and the focal lengths > 0.
  * mvsdf_undistort_points: points fp64 [n][2] on the device.  inverse != 0: source pixels -> pixels of the pinhole through the Newton iteration of the
- * inverse map; inverse == 0: pixels of the pinhole -> source pixels through the forward map.  hdr: 256 device bytes, int64 {0, error bits}, reset by
- * the call and read by the caller: 1 a non-finite value or a zero determinant, 2 an iteration that ended above 1e-10 px.
+ * inverse map; inverse == 0: pixels of the pinhole -> source pixels through the forward map.  hdr: 256 device bytes, MVSDF_RES_H_*, reset by
+ * the call and read by the caller; error bits: MVSDF_UD_ERR_*.
  * mvsdf_undistort_images: src [views][H][W][C] -> dst [views][oH][oW][C] on the device, C in 1 .. 4, dtype 0 uint8 or 1 float32, bilinear; pixels that
  * look outside the source are 0.  mask: uint8 [oH][oW] (1 = looks inside) or NULL.  Sides up to 2^24; all offsets are 64-bit.  No call waits.
  * The _host functions run the same arithmetic on the CPU over host memory (no GPU needed); *err receives the error bits. */
+enum {
+    MVSDF_UD_ERR_FINITE = 1,    /* a non-finite value or a zero determinant */
+    MVSDF_UD_ERR_CONVERGE = 2   /* an iteration that ended above 1e-10 px */
+};
 int mvsdf_undistort_points(const double* points, int64_t n, int model, const double* params, const double* pinhole, int inverse, double* out, void* hdr,
                            void* stream);
 int mvsdf_undistort_images(const void* src, int64_t views, int64_t H, int64_t W, int64_t C, int dtype, int model, const double* params,
@@ -1005,19 +1198,36 @@ size_t mvsdf_batch_args_bytes(void);     /* sizeof(MvsdfBatchArgs) as compiled: 
 int mvsdf_batch_gather(const MvsdfBatchArgs* a, void* stream);
 
 /* ---- Registration and F-score evaluation (registration.hip; Python: mvsdf_amd/registration.py, which states the definitions) ----
- * Points are fp64 [n][3] on the device; fp64 throughout, no contraction, every sum in a written order.  Error bits are the Chamfer calls':
- * 4 a non-finite coordinate, 8 a voxel index of 2^21 or more, 64 a tree-walk bound.
+ * Points are fp64 [n][3] on the device; fp64 throughout, no contraction, every sum in a written order.  Error bits: MVSDF_PC_ERR_FINITE,
+ * _COORD (a voxel index of 2^21 or more) and _WALK.
  * The kept tree: mvsdf_reg_tree_build sorts refs [nr][3] by Morton code and builds the box tree once, inside the workspace
- * (mvsdf_reg_tree_workspace_bytes; 0 unless 1 <= nr <= INT32_MAX).  It waits for the stream once (the coordinate check) and leaves int64 {error bits,
- * the centre of the references' box (3 fp64 as bits)} at the start of the workspace, which IS the tree from then on: keep it, pass it as `tree`.
+ * (mvsdf_reg_tree_workspace_bytes; 0 unless 1 <= nr <= INT32_MAX).  It waits for the stream once (the coordinate check) and leaves
+ * MVSDF_REG_TREE_H_* at the start of the workspace, which IS the tree from then on: keep it, pass it as `tree`.
  * mvsdf_reg_tree_query (no host wait): per query q (first moved by transform, HOST fp64 [16] row-major or NULL, row a =
  * ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3]) the minimum of (dx dx + dy dy) + dz dz over the references and the smallest input index that
  * attains it: index int32 [nq], d2 (the minimum) and dist (its sqrt), each fp64 [nq] or NULL.  Where sqrt(d2) is not < max_dist (> 0, may be
  * +inf): dist = d2 = +inf, index = -1.  Error bits are ORed into the device word *err (the caller zeroes it), with them nothing else is valid.
  * mvsdf_reg_icp_step: that query of src under transform, then the 17 sums of one ICP iteration over the matched pairs in source order (a lane sums
  * 8 consecutive items from 0, a 256-lane halving tree, block partials, a 1024-lane final): with c the tree's centre, p = T src - c and
- * q = refs[index] - c (refs: the array the tree was built from).  Waits for the stream -> int64 {n, then as fp64 bits: sum d2, sum p [3], sum q [3],
- * sum p_a q_b [9] (a major), error bits} at the start of the workspace (mvsdf_reg_pairs_workspace_bytes(ns), ns >= 1). */
+ * q = refs[index] - c (refs: the array the tree was built from).  Waits for the stream -> MVSDF_REG_ICP_H_* at the start of the workspace
+ * (mvsdf_reg_pairs_workspace_bytes(ns), ns >= 1). */
+enum {
+    MVSDF_REG_TREE_H_ERR = 0,       /* error bits */
+    MVSDF_REG_TREE_H_CENTRE = 1,    /* the centre of the references' box: 3 fp64 as bits */
+    MVSDF_REG_TREE_H_WORDS = 4
+};
+enum {
+    MVSDF_REG_ICP_H_N = 0,          /* matched pairs */
+    MVSDF_REG_ICP_H_SUMS = 1,       /* 16 fp64 as bits: sum d2, sum p [3], sum q [3], sum p_a q_b [9] (a major) */
+    MVSDF_REG_ICP_H_ERR = 17,       /* error bits */
+    MVSDF_REG_ICP_H_WORDS = 18
+};
+enum {
+    MVSDF_REG_VOXEL_H_VOXELS = 0,   /* occupied voxels */
+    MVSDF_REG_VOXEL_H_ERR = 1,      /* error bits */
+    MVSDF_REG_VOXEL_H_WORDS = 2
+};
+enum { MVSDF_REG_MAX_POLYGON = 4096 };  /* vertices of mvsdf_reg_crop's polygon */
 size_t mvsdf_reg_tree_workspace_bytes(int64_t nr);
 int mvsdf_reg_tree_build(const double* refs, int64_t nr, void* ws, size_t ws_bytes, void* stream);
 int mvsdf_reg_tree_query(const void* tree, size_t tree_bytes, int64_t nr, const double* queries, int64_t nq, const double* transform, double max_dist,
@@ -1027,11 +1237,11 @@ int mvsdf_reg_icp_step(const void* tree, size_t tree_bytes, int64_t nr, const do
                        double max_dist, void* ws, size_t ws_bytes, double* d2, int32_t* index, void* stream);
 /* No host wait in any of these.  mvsdf_reg_transform: out = the points under transform (HOST fp64 [16], as above); out may be pts.
  * mvsdf_reg_crop: keep uint8 [n] and out (capacity n rows, input order) = the points inside the prism whose axis is `axis` (0 X, 1 Y, 2 Z) between
- * axis_min and axis_max (inclusive) and whose section is the polygon fp64 [nverts][3] on the DEVICE, 3 <= nverts <= 4096, by the crossing rule
- * registration.py writes out -> int64 {rows kept}.  Workspace: mvsdf_reg_crop_workspace_bytes(n), n >= 1.
+ * axis_min and axis_max (inclusive) and whose section is the polygon fp64 [nverts][3] on the DEVICE, 3 <= nverts <= MVSDF_REG_MAX_POLYGON, by the crossing rule
+ * registration.py writes out -> MVSDF_ROWS_H_*.  Workspace: mvsdf_reg_crop_workspace_bytes(n), n >= 1.
  * mvsdf_reg_voxel: the voxel filter at edge `voxel` (finite, > 0): origin o = min - voxel / 2 per axis, cell g = floor((p - o) / voxel), key
  * gx | gy << 21 | gz << 42; means (capacity n rows) = per occupied voxel in ascending key the sum of its points in ascending input index from 0,
- * divided by their count; counts int32 -> int64 {voxels, error bits}.  Workspace: mvsdf_reg_voxel_workspace_bytes(n), 1 <= n <= INT32_MAX.
+ * divided by their count; counts int32 -> MVSDF_REG_VOXEL_H_*.  Workspace: mvsdf_reg_voxel_workspace_bytes(n), 1 <= n <= INT32_MAX.
  * mvsdf_reg_hist: out int64 [1 + nedges - 1] on the device = {the distances < tau, then the histogram: the bin of d is the number of edges[1..]
  * that are <= d, a d at or beyond the last edge is dropped}; edges fp64 [nedges] ascending on the DEVICE, 2 <= nedges <= 4097; n >= 0. */
 int mvsdf_reg_transform(const double* pts, int64_t n, const double* transform, double* out, void* stream);
@@ -1043,21 +1253,27 @@ int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t
 int mvsdf_reg_hist(const double* dist, int64_t n, const double* edges, int32_t nedges, double tau, int64_t* out, void* stream);
 
 /* ---- Normals of unoriented clouds (normals.hip; Python: mvsdf_amd/normals.py, which states the definition) ----
- * pts fp64 [n][3] on the device, fp64 throughout.  Error bits: 4 a non-finite coordinate (or view centre), 32 the round limit, 64 a tree-walk bound,
- * 128 a non-finite normal, 256 a neighbour index outside [0, n); with any set nothing else is valid.  Every argument is validated before the first
+ * pts fp64 [n][3] on the device, fp64 throughout.  Error bits: MVSDF_PC_ERR_FINITE, _ROUNDS, _WALK, _NORMAL and _INDEX (a neighbour index
+ * outside [0, n)); with any set nothing else is valid.  Every argument is validated before the first
  * launch.
  * mvsdf_normals_knn: idx int32 [n][k] = per point the k other points (by index) smallest under (d2, index), d2 = (dx dx + dy dy) + dz dz, ascending;
  * d2 fp64 [n][k] (may be NULL) their squared distances.  normals fp64 [n][3] and variation fp64 [n] (both or neither NULL): the eigenvector of the
- * smallest eigenvalue of each neighbourhood's covariance by cyclic Jacobi, in its canonical sign, and l_min / (l_0 + l_1 + l_2).  1 <= k <= 32,
- * k + 1 <= n <= INT32_MAX.  Workspace: mvsdf_normals_knn_workspace_bytes(n) (0 unless 2 <= n <= INT32_MAX) -> int64 {error bits}; waits for the
+ * smallest eigenvalue of each neighbourhood's covariance by cyclic Jacobi, in its canonical sign, and l_min / (l_0 + l_1 + l_2).  1 <= k <= MVSDF_PC_MAX_K,
+ * k + 1 <= n <= INT32_MAX.  Workspace: mvsdf_normals_knn_workspace_bytes(n) (0 unless 2 <= n <= INT32_MAX) -> MVSDF_ERRW_H_*; waits for the
  * stream once for the coordinate check.
  * mvsdf_normals_orient: out fp64 [n][3] (not normals itself) = the normals with their signs made consistent along the spanning forest of largest
  * |n_i . n_j| over the edges of neighbors int32 [n][k], each component signed by (ux, uy, uz) at its highest point or, with centers fp64 [V][3] and
- * bits uint64 [n][ceil(V / 64)] (mvsdf_viewsel_pack_*; both or neither NULL, 1 <= V <= 65535), by the votes of the views that see its points;
+ * bits uint64 [n][ceil(V / 64)] (mvsdf_viewsel_pack_*; both or neither NULL, 1 <= V <= MVSDF_VS_MAX_VIEWS), by the votes of the views that see its points;
  * labels int32 [n] = the smallest index of each point's component.  Workspace: mvsdf_normals_orient_workspace_bytes(n) (0 unless
- * 1 <= n <= INT32_MAX) -> int64 {n_components, rounds, error bits}; waits for the stream once per round.
+ * 1 <= n <= INT32_MAX) -> MVSDF_NR_ORIENT_H_*; waits for the stream once per round.
  * mvsdf_normals_to_views (no host wait): out = each normal, negated iff more of the views that see its point have n . (c - p) < 0 than > 0 ->
- * hdr (256 bytes on the device): int64 {error bits}. */
+ * hdr (256 bytes on the device): MVSDF_ERRW_H_*. */
+enum {
+    MVSDF_NR_ORIENT_H_COMPONENTS = 0,   /* components of the neighbour graph */
+    MVSDF_NR_ORIENT_H_ROUNDS = 1,       /* rounds run */
+    MVSDF_NR_ORIENT_H_ERR = 2,          /* error bits */
+    MVSDF_NR_ORIENT_H_WORDS = 3
+};
 size_t mvsdf_normals_knn_workspace_bytes(int64_t n);
 size_t mvsdf_normals_orient_workspace_bytes(int64_t n);
 int mvsdf_normals_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t ws_bytes, int32_t* idx, double* d2, double* normals, double* variation,
@@ -1068,19 +1284,26 @@ int mvsdf_normals_to_views(const double* pts, const double* normals, int64_t n, 
                            void* stream);
 
 /* ---- Global registration (global_reg.hip; Python: mvsdf_amd/global_reg.py, which states the definition) ----
- * No host wait in any of these.  Error bits: 4 a non-finite coordinate, 128 a non-finite normal, 256 a neighbour / correspondence index out of range,
- * 512 a code outside 0 .. 127.  err: int32 [1] on the device, zeroed by the caller, the bits are OR-ed into it.  radius2: the squared feature
- * radius, +inf for none.  1 <= n <= INT32_MAX, 1 <= k <= 32.
+ * No host wait in any of these.  Error bits: MVSDF_PC_ERR_FINITE, _NORMAL, _INDEX and _CODE.  err: int32 [1] on the device, zeroed by the caller, the bits are OR-ed into it.  radius2: the squared feature
+ * radius, +inf for none.  1 <= n <= INT32_MAX, 1 <= k <= MVSDF_PC_MAX_K.
  * mvsdf_greg_spfh: hist int32 [n][33] and count int32 [n] = the binned pair features of every point's neighbour row (neighbors int32 [n][k]).
  * mvsdf_greg_fpfh: features fp64 [n][33] = the rows' sums of hist / count weighted by 1 / d2, each group of 11 scaled to a sum of 100; codes int8
  * [n][33] = min(127, floor(1.27 features)).
  * mvsdf_greg_match: index int32 [ns] = the target code row nearest to each source row under (D, j), D = the squared difference summed over the 33
  * codes, dist int32 [ns] = that D; with mutual, index = -1 where the nearest source of that target is another row.  On the int8 matrix cores.
- * Workspace: mvsdf_greg_match_workspace_bytes(ns, nt) (0 unless 1 <= ns, nt <= INT32_MAX) -> int64 {error bits}.  mvsdf_greg_match_splits: over how
+ * Workspace: mvsdf_greg_match_workspace_bytes(ns, nt) (0 unless 1 <= ns, nt <= INT32_MAX) -> MVSDF_ERRW_H_*.  mvsdf_greg_match_splits: over how
  * many workgroups the walk over the targets is split at these sizes (they combine by a 64-bit atomicMin).
- * mvsdf_greg_ransac: corr int32 [m][2] (source index, target index), m >= 3; 1 <= hypotheses <= 2^22; mask uint8 [m] = the winner's inliers.
- * Workspace: mvsdf_greg_ransac_workspace_bytes(m, hypotheses) -> int64 {hypothesis or -1, inliers, checked, error bits, then the 12 entries of the
- * winner's 3 x 4 transformation as fp64 bits}. */
+ * mvsdf_greg_ransac: corr int32 [m][2] (source index, target index), m >= 3; 1 <= hypotheses <= MVSDF_GREG_MAX_HYPOTHESES; mask uint8 [m] = the winner's inliers.
+ * Workspace: mvsdf_greg_ransac_workspace_bytes(m, hypotheses) -> MVSDF_GREG_RANSAC_H_*. */
+enum {
+    MVSDF_GREG_RANSAC_H_HYP = 0,        /* the winning hypothesis, or -1 */
+    MVSDF_GREG_RANSAC_H_INLIERS = 1,    /* its inliers */
+    MVSDF_GREG_RANSAC_H_CHECKED = 2,    /* hypotheses that passed the pre-checks */
+    MVSDF_GREG_RANSAC_H_ERR = 3,        /* error bits */
+    MVSDF_GREG_RANSAC_H_T = 4,          /* the 12 entries of the winner's 3 x 4 transformation as fp64 bits */
+    MVSDF_GREG_RANSAC_H_WORDS = 16
+};
+enum { MVSDF_GREG_MAX_HYPOTHESES = 1 << 22 };
 int mvsdf_greg_spfh(const double* pts, const double* normals, const int32_t* neighbors, int64_t n, int32_t k, double radius2, int32_t* hist,
                     int32_t* count, int32_t* err, void* stream);
 int mvsdf_greg_fpfh(const double* pts, const int32_t* neighbors, const int32_t* hist, const int32_t* count, int64_t n, int32_t k, double radius2,

@@ -84,9 +84,32 @@ def parse_header(text):
     return protos
 
 
+def parse_constants(text):
+    """{name: value} of every enumerator of a C header's anonymous enums.  A value is a decimal or hex literal or a shift of two; anything else is an error."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    consts = {}
+    for body in re.findall(r'\benum\s*\{([^{}]*)\}\s*;', text):
+        for item in filter(None, (i.strip() for i in body.split(','))):
+            name, _, expr = (w.strip() for w in item.partition('='))
+            m = re.fullmatch(r'(0[xX][0-9a-fA-F]+|\d+)(?:\s*<<\s*(0[xX][0-9a-fA-F]+|\d+))?', expr)
+            if not m:
+                raise MvsdfError('enumerator %s: %s' % (name, 'cannot evaluate "%s"' % expr if expr else 'no explicit value'))
+            if name in consts:
+                raise MvsdfError('enumerator %s is declared twice' % name)
+            consts[name] = int(m.group(1), 0) << int(m.group(2) or '0', 0)
+    return consts
+
+
+class _Namespace:
+    def __init__(self, d):
+        self.__dict__.update(d)
+
+
 try:
     with open(HEADER_PATH) as _f:
-        PROTOTYPES = parse_header(_f.read())
+        _text = _f.read()
+    PROTOTYPES = parse_header(_text)
+    K = _Namespace(parse_constants(_text))                      # K.MVSDF_*: the result words, error bits and limits the header declares
 except OSError as e:
     raise MvsdfError('the C header %s cannot be read (%s): the ctypes prototypes are derived from it, the package needs include/ beside it' % (HEADER_PATH, e)) from None
 EXPORTS = list(PROTOTYPES)                                       # every symbol include/mvsdf_hip.h declares
@@ -95,6 +118,15 @@ EXPORTS = list(PROTOTYPES)                                       # every symbol 
 def check(rc, what=''):
     if rc != 0:
         raise MvsdfError('%s failed (code %d): %s' % (what or 'mvsdf call', rc, lib().mvsdf_last_error().decode()))
+
+
+def raise_for_bits(err, what, table):
+    """raise for the first row (bit, exception class, message) of `table` whose bit is set in the error word; any other bit is a library error"""
+    for bit, exc, message in table:
+        if err & bit:
+            raise exc('%s: %s' % (what, message))
+    if err:
+        raise MvsdfError('%s failed (error bits %d)' % (what, err))
 
 
 def ptr(t):

@@ -23,22 +23,16 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from ._lib import check, lib, K, MvsdfError, raise_for_bits, _header, _stream, _vp, f64_from_bits
 from .mesh import Mesh, _ply_elements
 
 U64 = 2 ** 64
 
 
-def _errors(err, what):
-    """raise for the error bits of a chamfer call (csrc/chamfer.hip)"""
-    if err & 4:
-        raise ValueError('%s: a coordinate is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: a face refers to a missing vertex' % what)
-    if err & 8:
-        raise ValueError('%s: a coordinate is more than 2^31 cells (of edge density) from the origin' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a chamfer call (csrc/chamfer.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PC_ERR_FINITE, ValueError, 'a coordinate is NaN or infinite'),
+          (K.MVSDF_PC_ERR_RANGE, ValueError, 'a face refers to a missing vertex'),
+          (K.MVSDF_PC_ERR_COORD, ValueError, 'a coordinate is more than 2^31 cells (of edge density) from the origin')]
 
 
 def _points(x, what, name='points'):
@@ -57,12 +51,6 @@ def _positive(name, x, what):
     if not (x > 0 and np.isfinite(x)):
         raise ValueError('%s: %s must be a positive finite number, got %r' % (what, name, x))
     return x
-
-
-def _header_f64(ws, n):
-    """the int64 header, with entry 1 (an fp64 sum stored as its bits) decoded"""
-    h = _header(ws, n)
-    return h, f64_from_bits(h[1])
 
 
 def sample_mesh(mesh, density=0.2, max_points=2 ** 31 - 1):
@@ -88,10 +76,9 @@ def sample_mesh(mesh, density=0.2, max_points=2 ** 31 - 1):
     ws = torch.empty(size, dtype=torch.uint8, device=dev)
     st = _stream(v)
     check(lib().mvsdf_chamfer_sample_count(_vp(v), _vp(f), nv, nf, density, int(max_points), _vp(ws), size, st), 'mvsdf_chamfer_sample_count')
-    total, _, err = _header(ws, 3)
-    if err & 1:
-        raise ValueError('%s: the mesh gives more than max_points = %d points at density %g' % (what, int(max_points), density))
-    _errors(err, what)
+    total, _, err = _header(ws, K.MVSDF_CH_SAMPLE_H_WORDS)
+    raise_for_bits(err, what, [(K.MVSDF_PC_ERR_POINTS, ValueError,
+                                'the mesh gives more than max_points = %d points at density %g' % (int(max_points), density))] + ERRORS)
     out = torch.empty(total, 3, dtype=torch.float64, device=dev)
     check(lib().mvsdf_chamfer_sample_emit(_vp(v), _vp(f), nv, nf, density, _vp(ws), size, _vp(out), total, st), 'mvsdf_chamfer_sample_emit')
     return out
@@ -113,10 +100,8 @@ def _downsample(p, density, seed, max_rounds):
     ws = torch.empty(size, dtype=torch.uint8, device=p.device)
     kept = torch.empty(n, dtype=torch.uint8, device=p.device)
     check(lib().mvsdf_chamfer_downsample(_vp(p), n, density, seed, max_rounds, _vp(ws), size, _vp(kept), _stream(p)), 'mvsdf_chamfer_downsample')
-    n_kept, rounds, err = _header(ws, 3)
-    if err & 32:
-        raise MvsdfError('%s: not decided after %d rounds (the limit)' % (what, rounds))
-    _errors(err, what)
+    n_kept, rounds, err = _header(ws, K.MVSDF_CH_DOWN_H_WORDS)
+    raise_for_bits(err, what, [(K.MVSDF_PC_ERR_ROUNDS, MvsdfError, 'not decided after %d rounds (the limit)' % rounds)] + ERRORS)
     return kept, n_kept, rounds
 
 
@@ -136,9 +121,9 @@ def _nearest(q, r, max_dist):
     ws = torch.empty(size, dtype=torch.uint8, device=r.device)
     dist = torch.empty(nq, dtype=torch.float64, device=r.device)
     check(lib().mvsdf_chamfer_nearest(_vp(q), nq, _vp(r), nr, float(max_dist), _vp(ws), size, _vp(dist), _stream(r)), 'mvsdf_chamfer_nearest')
-    (used, _, err), total = _header_f64(ws, 3)
-    _errors(err, what)
-    return dist, used, total
+    used, total, err = _header(ws, K.MVSDF_CH_NEAR_H_WORDS)
+    raise_for_bits(err, what, ERRORS)
+    return dist, used, f64_from_bits(total)
 
 
 def nearest_distance(queries, refs, max_dist=20.0):
@@ -175,8 +160,8 @@ def _masks(pts, kept, s, obs_mask, bb, res, plane, patch, what):
     s_above = torch.empty(m, 3, dtype=torch.float64, device=dev)
     check(lib().mvsdf_chamfer_mask(_vp(pts), _vp(kept), n, _vp(s), m, box.ctypes.data, res, _vp(obs), shape.ctypes.data, pl.ctypes.data, _vp(ws), size,
                                    _vp(d_in), _vp(d_obs), _vp(s_above), _stream(pts)), 'mvsdf_chamfer_mask')
-    n_in, n_obs, n_above, err = _header(ws, 4)
-    _errors(err, what)
+    n_in, n_obs, n_above, err = _header(ws, K.MVSDF_CH_MASK_H_WORDS)
+    raise_for_bits(err, what, ERRORS)
     return d_in[:n_in], d_obs[:n_obs], s_above[:n_above]
 
 

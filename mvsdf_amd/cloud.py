@@ -32,20 +32,15 @@ to be tolerated.  And self is excluded by index, not by distance.
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from ._lib import check, lib, K, MvsdfError, raise_for_bits, _header, _stream, _vp, f64_from_bits
 
-MAX_NEIGHBORS = 32
+MAX_NEIGHBORS = K.MVSDF_PC_MAX_K
 INT32_MAX = 2 ** 31 - 1
 
 
-def _errors(err, what):
-    """raise for the error bits of a cloud call (csrc/cloud.hip; the bits of csrc/nn_tree.h)"""
-    if err & 4:
-        raise ValueError('%s: a coordinate is NaN or infinite' % what)
-    if err & 32:
-        raise MvsdfError('%s: the components loop reached its round limit' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a cloud call (csrc/cloud.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PC_ERR_FINITE, ValueError, 'a coordinate is NaN or infinite'),
+          (K.MVSDF_PC_ERR_ROUNDS, MvsdfError, 'the components loop reached its round limit')]
 
 
 def _points(x, what):
@@ -101,7 +96,7 @@ def knn_mean_distance(points, nb_neighbors=20):
     ws, size = _workspace(p, what)
     d = torch.empty(n, dtype=torch.float64, device=p.device)
     check(lib().mvsdf_cloud_knn(_vp(p), n, k, _vp(ws), size, _vp(d), _stream(p)), 'mvsdf_cloud_knn')
-    _errors(_header(ws, 9)[8], what)
+    raise_for_bits(_header(ws, K.MVSDF_CLOUD_H_WORDS)[K.MVSDF_CLOUD_H_ERR], what, ERRORS)
     return d
 
 
@@ -118,7 +113,7 @@ def radius_components(points, eps):
     ws, size = _workspace(p, what)
     labels = torch.empty(n, dtype=torch.int32, device=p.device)
     check(lib().mvsdf_cloud_components(_vp(p), n, eps, _vp(ws), size, _vp(labels), _stream(p)), 'mvsdf_cloud_components')
-    _errors(_header(ws, 9)[8], what)
+    raise_for_bits(_header(ws, K.MVSDF_CLOUD_H_WORDS)[K.MVSDF_CLOUD_H_ERR], what, ERRORS)
     return labels
 
 
@@ -155,7 +150,7 @@ def compact(points, keep, colors=None, a=None, b=None, n_kept=None):
     check(lib().mvsdf_cloud_compact(_vp(points), _vp(colors), _vp(a), _vp(b), _vp(keep), n, _vp(ws), size, _vp(out[0]), _vp(out[1]), _vp(out[2]),
                                     _vp(out[3]), cap, _stream(points)), 'mvsdf_cloud_compact')
     if n_kept is None:
-        rows = _header(ws, 1)[0]
+        rows = _header(ws, K.MVSDF_ROWS_H_WORDS)[K.MVSDF_ROWS_H_ROWS]
         out = [None if t is None else t[:rows] for t in out]
     return tuple(out)
 
@@ -184,8 +179,8 @@ def _clean(p, colors, a, b, nb_neighbors, knn_ratio, eps_ratio, cluster_frac, wh
     keep = torch.empty(n, dtype=torch.uint8, device=dev)
     check(lib().mvsdf_cloud_clean(_vp(p), n, k, knn_ratio, eps_ratio, cluster_frac, _vp(ws), size, _vp(d), _vp(labels), _vp(keep), _stream(p)),
           'mvsdf_cloud_clean')
-    n_passed, n_clusters, largest, n_kept, m, thr, eps, rounds, err = _header(ws, 9)
-    _errors(err, what)
+    n_passed, n_clusters, largest, n_kept, m, thr, eps, rounds, err = _header(ws, K.MVSDF_CLOUD_H_WORDS)
+    raise_for_bits(err, what, ERRORS)
     pts, col, a, b = compact(p, keep, col, a, b, n_kept)
     return Cleaned(pts, col, keep, d, labels, f64_from_bits(m), f64_from_bits(thr), f64_from_bits(eps), n_passed, n_clusters, largest, rounds), a, b
 

@@ -19,6 +19,10 @@
 // Every device loop is bounded; the downsampling round loop on the host stops at the caller's limit and reports it.
 #include "nn_tree.h"
 
+static_assert(MVSDF_CH_SAMPLE_H_WORDS * 8 <= CH_HDR && MVSDF_CH_DOWN_H_WORDS * 8 <= CH_HDR && MVSDF_CH_MASK_H_WORDS * 8 <= CH_HDR &&
+                  MVSDF_CH_NEAR_H_WORDS * 8 <= CH_HDR,
+              "the result words fit the header");
+
 enum { DS_UNDECIDED = 0, DS_KEPT = 1, DS_REMOVED = 2 };
 
 __host__ __device__ __forceinline__ uint64_t ch_splitmix64(uint64_t x) {
@@ -33,19 +37,19 @@ struct ChFace {
     double a[3], v1[3], v2[3], n1, n2;
 };
 
-// the face's geometry; 0 = it samples nothing (zero area), else 1.  bad |= CH_ERR_RANGE / CH_ERR_FINITE.
+// the face's geometry; 0 = it samples nothing (zero area), else 1.  bad |= MVSDF_PC_ERR_RANGE / MVSDF_PC_ERR_FINITE.
 __device__ __forceinline__ int ch_face(const float* __restrict__ V, const int* __restrict__ F, long long f, long long nv, double density, ChFace* g,
                                        int* bad) {
     double p[3][3];
     for (int s = 0; s < 3; ++s) {
         const int id = F[f * 3 + s];
         if (id < 0 || id >= nv) {
-            *bad |= CH_ERR_RANGE;
+            *bad |= MVSDF_PC_ERR_RANGE;
             return 0;
         }
         for (int c = 0; c < 3; ++c) p[s][c] = (double)V[(long long)id * 3 + c];
         if (!ch_finite3(p[s])) {
-            *bad |= CH_ERR_FINITE;
+            *bad |= MVSDF_PC_ERR_FINITE;
             return 0;
         }
     }
@@ -91,7 +95,7 @@ __device__ __forceinline__ long long ch_face_samples(const ChFace& g, double* __
     return k;
 }
 
-// per-face sample counts; a face with more than max_points samples stops counting there and raises CH_ERR_POINTS
+// per-face sample counts; a face with more than max_points samples stops counting there and raises MVSDF_PC_ERR_POINTS
 __global__ __launch_bounds__(CH_THREADS) void k_ch_sample_count(const float* __restrict__ V, const int* __restrict__ F, long long nv, long long nf,
                                                                  double density, long long max_points, long long* __restrict__ cnt, int* err) {
     const long long f = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
@@ -102,7 +106,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_ch_sample_count(const float* __r
     if (ch_face(V, F, f, nv, density, &g, &bad)) {
         k = ch_face_samples(g, nullptr, 0, 0, max_points);
         if (k > max_points) {
-            bad |= CH_ERR_POINTS;
+            bad |= MVSDF_PC_ERR_POINTS;
             k = 0;
         }
     }
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_ch_vert_copy(const float* __rest
     for (int c = 0; c < 3; ++c) p[c] = (double)V[v * 3 + c];
     if (out)
         for (int c = 0; c < 3; ++c) out[v * 3 + c] = p[c];
-    if (!ch_finite3(p)) atomicOr(err, CH_ERR_FINITE);
+    if (!ch_finite3(p)) atomicOr(err, MVSDF_PC_ERR_FINITE);
 }
 
 __global__ __launch_bounds__(CH_THREADS) void k_ch_sample_emit(const float* __restrict__ V, const int* __restrict__ F, long long nv, long long nf,
@@ -183,12 +187,12 @@ __global__ __launch_bounds__(CH_THREADS) void k_ds_insert(const double* __restri
     pslot[i] = -1;
     const double* p = P + i * 3;
     if (!ch_finite3(p)) {
-        atomicOr(err, CH_ERR_FINITE);
+        atomicOr(err, MVSDF_PC_ERR_FINITE);
         return;
     }
     long long c[3];
     if (!ch_cell(p, h, c)) {
-        atomicOr(err, CH_ERR_COORD);
+        atomicOr(err, MVSDF_PC_ERR_COORD);
         return;
     }
     const unsigned long long key = ch_cell_key(c[0], c[1], c[2]);
@@ -202,7 +206,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_ds_insert(const double* __restri
         }
         slot = (slot + 1) & tmask;
     }
-    atomicOr(err, CH_ERR_HASH);
+    atomicOr(err, MVSDF_PC_ERR_HASH);
 }
 
 __global__ __launch_bounds__(CH_THREADS) void k_ds_fill(long long n, const int* __restrict__ pslot, const long long* __restrict__ start, unsigned long long* cur,
@@ -319,7 +323,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_mask_plane(const double* __restr
     const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
     if (i >= m) return;
     const double* p = S + i * 3;
-    if (!ch_finite3(p)) atomicOr((unsigned long long*)err, (unsigned long long)CH_ERR_FINITE);
+    if (!ch_finite3(p)) atomicOr((unsigned long long*)err, (unsigned long long)MVSDF_PC_ERR_FINITE);
     fab[i] = ((a.plane[0] * p[0] + a.plane[1] * p[1]) + a.plane[2] * p[2]) + a.plane[3] > 0.0;
 }
 
@@ -365,7 +369,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_nn_query(const double* __restric
     if (qi >= nq) return;
     const double x = Q[qi * 3], y = Q[qi * 3 + 1], z = Q[qi * 3 + 2];
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
-        atomicOr(err, CH_ERR_FINITE);
+        atomicOr(err, MVSDF_PC_ERR_FINITE);
         dist[qi] = INFINITY;
         return;
     }
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_nn_query(const double* __restric
     if (ch_box_lb2(box + first * 6, x, y, z) <= cut2 * CH_MARGIN2) best = ch_leaf_min(sp, T.n, first, x, y, z, best);
     if (!ch_walk(
             box, T, x, y, z, [&] { return fmin(best, cut2) * CH_MARGIN2; }, [&](long long l) { best = ch_leaf_min(sp, T.n, l, x, y, z, best); }))
-        atomicOr(err, CH_ERR_WALK);
+        atomicOr(err, MVSDF_PC_ERR_WALK);
     const double d = sqrt(best);
     dist[qi] = d < max_dist ? d : INFINITY;
 }
@@ -484,9 +488,11 @@ int mvsdf_chamfer_sample_count(const float* verts, const int32_t* faces, int64_t
     long long h[2];
     if ((rc = mv_read(h, fl, sizeof(h), s, "mvsdf_chamfer_sample_count"))) return rc;
     const long long err = (int)h[0], samples = h[1];
-    long long hdr[3] = {nv + samples, samples, err};
-    if (!err && nv + samples > max_points) hdr[2] |= CH_ERR_POINTS;
-    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_sample_count");
+    long long hdr[MVSDF_CH_SAMPLE_H_WORDS];
+    hdr[MVSDF_CH_SAMPLE_H_POINTS] = nv + samples;
+    hdr[MVSDF_CH_SAMPLE_H_SAMPLES] = samples;
+    hdr[MVSDF_CH_SAMPLE_H_ERR] = !err && nv + samples > max_points ? MVSDF_PC_ERR_POINTS : err;
+    return mv_write_header(ws, hdr, MVSDF_CH_SAMPLE_H_WORDS, s, "mvsdf_chamfer_sample_count");
 }
 
 int mvsdf_chamfer_sample_emit(const float* verts, const int32_t* faces, int64_t nv, int64_t nf, double density, void* ws, size_t ws_bytes, double* out,
@@ -524,7 +530,7 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
     long long* start = (long long*)(w + L.start);
     unsigned char* st[2] = {(unsigned char*)(w + L.st0), (unsigned char*)(w + L.st1)};
     int* fl = (int*)(w + L.flags);                                // [0]: error bits, [1]: kept (int64 at +8), [4..]: undecided after each round of a batch
-    long long hdr[3] = {0, 0, 0};                                 // kept, rounds, error bits
+    long long hdr[MVSDF_CH_DOWN_H_WORDS] = {};
     int rc;
     if ((rc = mv_check(hipMemsetAsync(keys, 0xff, L.tsize * 8, s), "mvsdf_chamfer_downsample"))) return rc;
     if ((rc = mv_check(hipMemsetAsync(cnt, 0, L.tsize * 8, s), "mvsdf_chamfer_downsample"))) return rc;
@@ -535,7 +541,7 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
     if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
     int e = 0;
     if ((rc = mv_read(&e, fl, 4, s, "mvsdf_chamfer_downsample"))) return rc;
-    hdr[2] = e;
+    hdr[MVSDF_CH_DOWN_H_ERR] = e;
     if (!e) {
         mv_scan((const long long*)cnt, (long long)L.tsize, start, w + L.tmp, (long long*)(fl + 2), s);
         hipLaunchKernelGGL(k_ds_fill, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const int*)(w + L.pslot), (const long long*)start,
@@ -543,11 +549,11 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
         int cur = 0;
         bool done = false;
         while (!done) {
-            if (hdr[1] >= max_rounds) {
-                hdr[2] |= CH_ERR_ROUNDS;
+            if (hdr[MVSDF_CH_DOWN_H_ROUNDS] >= max_rounds) {
+                hdr[MVSDF_CH_DOWN_H_ERR] |= MVSDF_PC_ERR_ROUNDS;
                 break;
             }
-            const int batch = (int)(max_rounds - hdr[1] < CH_DS_BATCH ? max_rounds - hdr[1] : CH_DS_BATCH);
+            const int batch = (int)(max_rounds - hdr[MVSDF_CH_DOWN_H_ROUNDS] < CH_DS_BATCH ? max_rounds - hdr[MVSDF_CH_DOWN_H_ROUNDS] : CH_DS_BATCH);
             if ((rc = mv_check(hipMemsetAsync(fl + 4, 0, CH_DS_BATCH * 4, s), "mvsdf_chamfer_downsample"))) return rc;
             for (int b = 0; b < batch; ++b) {
                 hipLaunchKernelGGL(k_ds_round, dim3(gn), dim3(CH_THREADS), 0, s, pts, (long long)n, h, r2, (unsigned long long)seed,
@@ -559,7 +565,7 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
             int left[CH_DS_BATCH];
             if ((rc = mv_read(left, fl + 4, sizeof(left), s, "mvsdf_chamfer_downsample"))) return rc;
             for (int b = 0; b < batch && !done; ++b) {
-                ++hdr[1];
+                ++hdr[MVSDF_CH_DOWN_H_ROUNDS];
                 done = left[b] == 0;
             }
         }
@@ -568,10 +574,10 @@ int mvsdf_chamfer_downsample(const double* pts, int64_t n, double density, uint6
             hipLaunchKernelGGL(k_ds_out, dim3(gn), dim3(CH_THREADS), 0, s, (long long)n, (const unsigned char*)st[cur], kept,
                                (unsigned long long*)(fl + 2));
             if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_downsample"))) return rc;
-            if ((rc = mv_read(&hdr[0], fl + 2, 8, s, "mvsdf_chamfer_downsample"))) return rc;
+            if ((rc = mv_read(&hdr[MVSDF_CH_DOWN_H_KEPT], fl + 2, 8, s, "mvsdf_chamfer_downsample"))) return rc;
         }
     }
-    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_downsample");
+    return mv_write_header(ws, hdr, MVSDF_CH_DOWN_H_WORDS, s, "mvsdf_chamfer_downsample");
 }
 
 size_t mvsdf_chamfer_mask_workspace_bytes(int64_t n, int64_t m) {
@@ -602,18 +608,18 @@ int mvsdf_chamfer_mask(const double* pts, const uint8_t* kept, int64_t n, const 
     long long* fab = (long long*)(w + L.fab);
     long long* tot = (long long*)(w + L.tot);
     hipLaunchKernelGGL(k_mask_flags, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, kept, (long long)n, a, obs, fin, fobs);
-    if (int rc = mv_check(hipMemsetAsync(tot, 0, 4 * 8, s), "mvsdf_chamfer_mask")) return rc;
-    hipLaunchKernelGGL(k_mask_plane, dim3(mv_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, a, fab, tot + 3);
-    mv_scan(fin, n, fin, w + L.tmp1, tot, s);
-    mv_scan(fobs, n, fobs, w + L.tmp2, tot + 1, s);
-    mv_scan(fab, m, fab, w + L.tmp3, tot + 2, s);
-    hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fin, (const long long*)tot, d_in);
+    if (int rc = mv_check(hipMemsetAsync(tot, 0, MVSDF_CH_MASK_H_WORDS * 8, s), "mvsdf_chamfer_mask")) return rc;
+    hipLaunchKernelGGL(k_mask_plane, dim3(mv_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, a, fab, tot + MVSDF_CH_MASK_H_ERR);
+    mv_scan(fin, n, fin, w + L.tmp1, tot + MVSDF_CH_MASK_H_IN, s);
+    mv_scan(fobs, n, fobs, w + L.tmp2, tot + MVSDF_CH_MASK_H_OBS, s);
+    mv_scan(fab, m, fab, w + L.tmp3, tot + MVSDF_CH_MASK_H_ABOVE, s);
+    hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fin, (const long long*)(tot + MVSDF_CH_MASK_H_IN), d_in);
     hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, (long long)n, (const long long*)fobs,
-                       (const long long*)(tot + 1), d_obs);
+                       (const long long*)(tot + MVSDF_CH_MASK_H_OBS), d_obs);
     hipLaunchKernelGGL(k_mask_scatter, dim3(mv_grid(m, CH_THREADS)), dim3(CH_THREADS), 0, s, stl, (long long)m, (const long long*)fab,
-                       (const long long*)(tot + 2), s_above);
+                       (const long long*)(tot + MVSDF_CH_MASK_H_ABOVE), s_above);
     if (int rc = mv_check(hipGetLastError(), "mvsdf_chamfer_mask")) return rc;
-    return mv_check(hipMemcpyAsync(ws, tot, 4 * 8, hipMemcpyDeviceToDevice, s), "mvsdf_chamfer_mask");
+    return mv_check(hipMemcpyAsync(ws, tot, MVSDF_CH_MASK_H_WORDS * 8, hipMemcpyDeviceToDevice, s), "mvsdf_chamfer_mask");
 }
 
 size_t mvsdf_chamfer_nearest_workspace_bytes(int64_t nq, int64_t nr) {
@@ -630,12 +636,12 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
     int* fl = (int*)(w + L.flags);
-    long long hdr[3] = {0, 0, 0};                                 // distances below the cut-off, their fp64 sum (bits), error bits
+    long long hdr[MVSDF_CH_NEAR_H_WORDS] = {};
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_chamfer_nearest"))) return rc;
     const ChBuilt tree = ch_tree_begin(refs, (long long)nr, w, L.t, fl, s, "mvsdf_chamfer_nearest");
     if (tree.rc) return tree.rc;
-    hdr[2] = tree.err;
+    hdr[MVSDF_CH_NEAR_H_ERR] = tree.err;
     if (!tree.err) {
         const double* sp = (const double*)(w + L.t.sp);
         const double* box = (const double*)(w + L.t.box);
@@ -650,11 +656,11 @@ int mvsdf_chamfer_nearest(const double* queries, int64_t nq, const double* refs,
         if ((rc = mv_check(hipGetLastError(), "mvsdf_chamfer_nearest"))) return rc;
         long long r[3];                                           // error bits (int) at byte 0, k_nn_sum_final's count and sum at bytes 8 and 16
         if ((rc = mv_read(r, fl, sizeof(r), s, "mvsdf_chamfer_nearest"))) return rc;
-        hdr[0] = nq > 0 ? r[1] : 0;
-        hdr[1] = nq > 0 ? r[2] : 0;
-        hdr[2] = (int)r[0];
+        hdr[MVSDF_CH_NEAR_H_COUNT] = nq > 0 ? r[1] : 0;
+        hdr[MVSDF_CH_NEAR_H_SUM] = nq > 0 ? r[2] : 0;
+        hdr[MVSDF_CH_NEAR_H_ERR] = (int)r[0];
     }
-    return mv_write_header(ws, hdr, 3, s, "mvsdf_chamfer_nearest");
+    return mv_write_header(ws, hdr, MVSDF_CH_NEAR_H_WORDS, s, "mvsdf_chamfer_nearest");
 }
 
 }  // extern "C"

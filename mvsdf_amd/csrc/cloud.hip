@@ -20,14 +20,13 @@
 //   graph, not of the schedule.
 // * Compaction: int64 flags, the house scan (geom_prims.h: mv_scan), a scatter in input order.
 //
-// Every device loop is bounded; the round loop on the host stops at CL_MAX_ROUNDS with CH_ERR_ROUNDS.
+// Every device loop is bounded; the round loop on the host stops at CL_MAX_ROUNDS with MVSDF_PC_ERR_ROUNDS.
 #include "nn_tree.h"
 
-#define CL_MAX_K 32
 #define CL_MAX_ROUNDS 64
 #define CL_FIND_STEPS 4096                            // parent hops of one find before it gives the round up
 #define CL_UNION_TRIES 64
-#define CL_HDR_WORDS 9
+static_assert(MVSDF_CLOUD_H_WORDS * 8 <= CH_HDR && MVSDF_ROWS_H_WORDS * 8 <= CH_HDR, "the result words fit the header");
 
 // flags (int): [0] error bits, [1] pending, [2] n_passed, [3] n_clusters, [4] largest, [5] n_kept
 // par (double): [0] m, [1] threshold, [2] eps, [3] eps * eps
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_knn(const double* __restrict_
     ClList<CAP> list;
 #pragma unroll
     for (int j = 0; j < CAP; ++j) list.best[j] = j < CAP - k ? -1.0 : INFINITY;
-    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, CH_ERR_WALK);
+    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, MVSDF_PC_ERR_WALK);
     double s = 0.0;
 #pragma unroll
     for (int j = 0; j < CAP; ++j)
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_hook(const double* __restrict
             }
         },
         p);                                                       // nodes that hold positions above p only end the walk
-    if (!walked) atomicOr(flags + CL_F_ERR, CH_ERR_WALK);
+    if (!walked) atomicOr(flags + CL_F_ERR, MVSDF_PC_ERR_WALK);
     if (bad) atomicOr(flags + CL_F_PENDING, 1);
 }
 
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_roots(const int* __restrict__
             if (px == x) break;
             x = px;
         }
-        if (step > n) atomicOr(flags + CL_F_ERR, CH_ERR_WALK);
+        if (step > n) atomicOr(flags + CL_F_ERR, MVSDF_PC_ERR_WALK);
         cl_st(parent + p, x);
         idx = perm[p];
     }
@@ -228,15 +227,15 @@ __global__ __launch_bounds__(CH_THREADS) void k_cl_out(const int* __restrict__ p
 
 __global__ __launch_bounds__(64) void k_cl_header(const int* __restrict__ flags, const double* __restrict__ par, long long rounds, long long* __restrict__ hdr) {
     if (threadIdx.x) return;
-    hdr[0] = flags[CL_F_PASSED];
-    hdr[1] = flags[CL_F_CLUSTERS];
-    hdr[2] = flags[CL_F_LARGEST];
-    hdr[3] = flags[CL_F_KEPT];
-    hdr[4] = __double_as_longlong(par[0]);
-    hdr[5] = __double_as_longlong(par[1]);
-    hdr[6] = __double_as_longlong(par[2]);
-    hdr[7] = rounds;
-    hdr[8] = flags[CL_F_ERR];
+    hdr[MVSDF_CLOUD_H_PASSED] = flags[CL_F_PASSED];
+    hdr[MVSDF_CLOUD_H_CLUSTERS] = flags[CL_F_CLUSTERS];
+    hdr[MVSDF_CLOUD_H_LARGEST] = flags[CL_F_LARGEST];
+    hdr[MVSDF_CLOUD_H_KEPT] = flags[CL_F_KEPT];
+    hdr[MVSDF_CLOUD_H_M] = __double_as_longlong(par[0]);
+    hdr[MVSDF_CLOUD_H_THRESHOLD] = __double_as_longlong(par[1]);
+    hdr[MVSDF_CLOUD_H_EPS] = __double_as_longlong(par[2]);
+    hdr[MVSDF_CLOUD_H_ROUNDS] = rounds;
+    hdr[MVSDF_CLOUD_H_ERR] = flags[CL_F_ERR];
 }
 
 // ================================================================ compaction ================================================================
@@ -296,11 +295,12 @@ static bool cl_compact_layout(long long n, ClCompactLayout* L) {
 }
 
 static int cl_fail_header(void* ws, long long err, hipStream_t s, const char* what) {
-    long long hdr[CL_HDR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, err};
-    return mv_write_header(ws, hdr, CL_HDR_WORDS, s, what);
+    long long hdr[MVSDF_CLOUD_H_WORDS] = {};
+    hdr[MVSDF_CLOUD_H_ERR] = err;
+    return mv_write_header(ws, hdr, MVSDF_CLOUD_H_WORDS, s, what);
 }
 
-// flags zeroed, the frame, one header read for CH_ERR_FINITE, the tree -> 0 and *perm, or nonzero after the failure header / a HIP error (*done set)
+// flags zeroed, the frame, one header read for MVSDF_PC_ERR_FINITE, the tree -> 0 and *perm, or nonzero after the failure header / a HIP error (*done set)
 static int cl_begin(const double* pts, long long n, char* w, const ClLayout& L, hipStream_t s, const char* what, const int** perm, bool* done) {
     int* fl = (int*)(w + L.flags);
     int rc;
@@ -337,7 +337,7 @@ static int cl_components(const double* d, long long n, double cluster_frac, char
     hipLaunchKernelGGL(k_cl_flag, g, b, 0, s, d, perm, n, par, parent, minidx, count, fl);
     long long rounds = 0;
     for (;;) {
-        if (rounds >= CL_MAX_ROUNDS) return cl_fail_header(w, CH_ERR_ROUNDS, s, what);
+        if (rounds >= CL_MAX_ROUNDS) return cl_fail_header(w, MVSDF_PC_ERR_ROUNDS, s, what);
         if ((rc = mv_check(hipMemsetAsync(fl + CL_F_PENDING, 0, 4, s), what))) return rc;
         hipLaunchKernelGGL(k_cl_hook, g, b, 0, s, sp, box, L.t.T, par, parent, fl);
         if ((rc = mv_check(hipGetLastError(), what))) return rc;
@@ -371,7 +371,7 @@ size_t mvsdf_cloud_compact_workspace_bytes(int64_t n) {
 int mvsdf_cloud_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t ws_bytes, double* d, void* stream) {
     const char* what = "mvsdf_cloud_knn";
     ClLayout L;
-    if (!pts || !ws || !d || k < 1 || k > CL_MAX_K || n < (int64_t)k + 1 || !cl_layout(n, &L)) return mv_fail(-1, "mvsdf_cloud_knn: bad arguments");
+    if (!pts || !ws || !d || k < 1 || k > MVSDF_PC_MAX_K || n < (int64_t)k + 1 || !cl_layout(n, &L)) return mv_fail(-1, "mvsdf_cloud_knn: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_cloud_knn: workspace too small (mvsdf_cloud_clean_workspace_bytes)");
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
@@ -404,7 +404,7 @@ int mvsdf_cloud_clean(const double* pts, int64_t n, int32_t k, double knn_ratio,
                       double* d, int32_t* labels, uint8_t* keep, void* stream) {
     const char* what = "mvsdf_cloud_clean";
     ClLayout L;
-    if (!pts || !ws || !d || !labels || !keep || k < 1 || k > CL_MAX_K || n < (int64_t)k + 1 || !cl_ratio(knn_ratio) || !cl_ratio(eps_ratio) ||
+    if (!pts || !ws || !d || !labels || !keep || k < 1 || k > MVSDF_PC_MAX_K || n < (int64_t)k + 1 || !cl_ratio(knn_ratio) || !cl_ratio(eps_ratio) ||
         !cl_ratio(cluster_frac) || cluster_frac > 1.0 || !cl_layout(n, &L))
         return mv_fail(-1, "mvsdf_cloud_clean: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_cloud_clean: workspace too small (mvsdf_cloud_clean_workspace_bytes)");
@@ -441,7 +441,7 @@ int mvsdf_cloud_compact(const double* pts, const uint8_t* colors, const int32_t*
     hipLaunchKernelGGL(k_cl_compact, g, blk, 0, s, pts, colors, a, b, keep, (long long)n, (const long long*)f, (long long)cap, out_pts, out_colors, out_a,
                        out_b);
     if (int rc = mv_check(hipGetLastError(), what)) return rc;
-    return mv_check(hipMemcpyAsync(ws, w + L.tot, 8, hipMemcpyDeviceToDevice, s), what);
+    return mv_check(hipMemcpyAsync(ws, w + L.tot, MVSDF_ROWS_H_WORDS * 8, hipMemcpyDeviceToDevice, s), what);
 }
 
 }  // extern "C"

@@ -16,16 +16,9 @@
 #include "geom_prims.h"
 
 #define FU_THREADS 256
-#define FU_HDR 256                                    // bytes at the start of the workspace: int64 {points, error bits}
+#define FU_HDR 256                                    // bytes at the start of the workspace: MVSDF_RES_H_*
+static_assert(MVSDF_RES_H_WORDS * 8 <= FU_HDR, "the result words fit the header");
 #define FU_MAX_PIXELS (1ll << 40)
-
-enum {
-    FU_ERR_FINITE = 1,      // a non-finite matrix entry (a camera entry was NaN or infinite, or a projection is singular)
-    FU_ERR_PAIR = 2,        // a pair index outside [0, V)
-    FU_ERR_VIEW = 4,        // view < 1
-    FU_ERR_SHAPE = 8,       // V < 1, H or W < 2, a pair list that disagrees with V or is longer than view, sizes beyond the limits
-    FU_ERR_INDEX = 16,      // k_fu_normals: a point's view or pixel index lies outside the maps
-};
 
 struct FuLayout {
     size_t mats, pinv, src, off, df, keep, bsum, total;
@@ -171,7 +164,7 @@ __device__ __forceinline__ bool fu_tangent(const float* __restrict__ map, const 
     return true;
 }
 
-// one lane per point; an index outside the maps sets FU_ERR_INDEX and gives a zero normal
+// one lane per point; an index outside the maps sets MVSDF_FU_ERR_INDEX and gives a zero normal
 __global__ __launch_bounds__(FU_THREADS) void k_fu_normals(const float* __restrict__ fused, int V, int H, int W, const int* __restrict__ view,
                                                             const int* __restrict__ pixel, long long n, const double* __restrict__ mats, double jump,
                                                             double* __restrict__ normals, unsigned long long* __restrict__ word) {
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_normals(const float* __restri
     const int r = view[i], p = pixel[i];
     double o[3] = {0.0, 0.0, 0.0};
     if (r < 0 || r >= V || p < 0 || p >= H * W) {
-        atomicOr(word, (unsigned long long)FU_ERR_INDEX);
+        atomicOr(word, (unsigned long long)MVSDF_FU_ERR_INDEX);
     } else {
         const int y = p / W, x = p - y * W;
         const float* __restrict__ map = fused + (long long)r * H * W;
@@ -219,22 +212,19 @@ int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, co
     if (!fused || !view || !pixel || !mats || !ws || !normals || ws_bytes < FU_HDR) return mv_fail(-1, "mvsdf_fusion_normals: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     long long err = 0;
-    if (V < 1 || H < 2 || W < 2 || V > INT_MAX || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || n < 1 || n > FU_MAX_PIXELS) err |= FU_ERR_SHAPE;
-    if (!(err & FU_ERR_SHAPE))
+    if (V < 1 || H < 2 || W < 2 || V > INT_MAX || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || n < 1 || n > FU_MAX_PIXELS) err |= MVSDF_FU_ERR_SHAPE;
+    if (!(err & MVSDF_FU_ERR_SHAPE))
         for (long long k = 0; k < V * FU_NM_ROW; ++k)
-            if (!isfinite(mats[k])) err |= FU_ERR_FINITE;
-    if (isnan(jump) || jump < 0.0) err |= FU_ERR_FINITE;
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+            if (!isfinite(mats[k])) err |= MVSDF_FU_ERR_FINITE;
+    if (isnan(jump) || jump < 0.0) err |= MVSDF_FU_ERR_FINITE;
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < mvsdf_fusion_normals_workspace_bytes(V)) return mv_fail(-1, "mvsdf_fusion_normals: workspace too small (mvsdf_fusion_normals_workspace_bytes)");
     char* w = (char*)ws;
     int rc;
     if ((rc = mv_check(hipMemsetAsync(ws, 0, FU_HDR, s), what))) return rc;
     if ((rc = mv_check(hipMemcpyAsync(w + FU_HDR, mats, (size_t)V * FU_NM_ROW * 8, hipMemcpyHostToDevice, s), what))) return rc;
     hipLaunchKernelGGL(k_fu_normals, dim3(mv_grid(n, FU_THREADS)), dim3(FU_THREADS), 0, s, fused, (int)V, (int)H, (int)W, view, pixel, (long long)n,
-                       (const double*)(w + FU_HDR), jump, normals, (unsigned long long*)(w + 8));
+                       (const double*)(w + FU_HDR), jump, normals, (unsigned long long*)w + MVSDF_RES_H_ERR);
     return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps mats until it has read the header
 }
 
@@ -252,31 +242,28 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
     hipStream_t s = (hipStream_t)stream;
     // ---- validation, all of it before the first launch ----
     long long err = 0;
-    if (view < 1) err |= FU_ERR_VIEW;
+    if (view < 1) err |= MVSDF_FU_ERR_VIEW;
     long long npairs = 0;
-    if (V < 1 || V > INT_MAX || pair_off[0] != 0) err |= FU_ERR_SHAPE;
+    if (V < 1 || V > INT_MAX || pair_off[0] != 0) err |= MVSDF_FU_ERR_SHAPE;
     else {
-        for (long long r = 0; r < V && !(err & FU_ERR_SHAPE); ++r) {
+        for (long long r = 0; r < V && !(err & MVSDF_FU_ERR_SHAPE); ++r) {
             const long long len = (long long)pair_off[r + 1] - pair_off[r];
-            if (len < 0 || (view >= 1 && len > view)) err |= FU_ERR_SHAPE;
+            if (len < 0 || (view >= 1 && len > view)) err |= MVSDF_FU_ERR_SHAPE;
         }
         npairs = pair_off[V];
     }
     FuLayout L;
-    if (!(err & FU_ERR_SHAPE) && (!fu_layout(V, H, W, npairs, &L) || (npairs > 0 && !pair_src))) err |= FU_ERR_SHAPE;
-    if (!(err & FU_ERR_SHAPE)) {
+    if (!(err & MVSDF_FU_ERR_SHAPE) && (!fu_layout(V, H, W, npairs, &L) || (npairs > 0 && !pair_src))) err |= MVSDF_FU_ERR_SHAPE;
+    if (!(err & MVSDF_FU_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
-            if (pair_src[k] < 0 || pair_src[k] >= V) err |= FU_ERR_PAIR;
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_FU_ERR_PAIR;
         const long long nm = npairs * 32 + V * 16;
         for (long long k = 0; k < nm; ++k)
-            if (!isfinite(mats[k])) err |= FU_ERR_FINITE;
-        if (!isfinite(pix_thresh) || !isfinite(dep_thresh)) err |= FU_ERR_FINITE;
-        if (probs && !(isfinite(pthresh[0]) && isfinite(pthresh[1]) && isfinite(pthresh[2]))) err |= FU_ERR_FINITE;
+            if (!isfinite(mats[k])) err |= MVSDF_FU_ERR_FINITE;
+        if (!isfinite(pix_thresh) || !isfinite(dep_thresh)) err |= MVSDF_FU_ERR_FINITE;
+        if (probs && !(isfinite(pthresh[0]) && isfinite(pthresh[1]) && isfinite(pthresh[2]))) err |= MVSDF_FU_ERR_FINITE;
     }
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_fusion_fuse: workspace too small (mvsdf_fusion_workspace_bytes)");
     // ---- uploads and launches ----
     char* w = (char*)ws;
@@ -295,7 +282,7 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
     hipLaunchKernelGGL(k_fu_fuse, dim3((unsigned)(V * tiles)), dim3(FU_THREADS), 0, s, (const float*)masked, (int)V, (int)H, (int)W, tiles,
                        (const int*)(w + L.off), (const int*)(w + L.src), (const double*)(w + L.mats), (int)vthresh, pix_thresh * pix_thresh, dep_thresh,
                        counts, fused, (double*)(w + L.df), (unsigned char*)(w + L.keep));
-    mv_scan_blocks((const unsigned char*)(w + L.keep), n, (long long*)(w + L.bsum), L.nb, (long long*)ws, s);
+    mv_scan_blocks((const unsigned char*)(w + L.keep), n, (long long*)(w + L.bsum), L.nb, (long long*)ws + MVSDF_RES_H_COUNT, s);
     return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
 }
 

@@ -38,6 +38,13 @@ static inline int mv_write_header(void* ws, const long long* hdr, int n, hipStre
     return mv_check(hipStreamSynchronize(s), what);
 }
 
+// the header of a call that leaves MVSDF_RES_H_* and stops at its argument checks: {0, error bits}, then a wait
+static inline int mv_refuse_header(void* ws, long long err, hipStream_t s, const char* what) {
+    long long hdr[MVSDF_RES_H_WORDS] = {};
+    hdr[MVSDF_RES_H_ERR] = err;
+    return mv_write_header(ws, hdr, MVSDF_RES_H_WORDS, s, what);
+}
+
 // bytes from the device, then a wait
 static inline int mv_read(void* host, const void* dev, size_t bytes, hipStream_t s, const char* what) {
     if (int rc = mv_check(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s), what)) return rc;

@@ -28,17 +28,12 @@
 #define GG_DIM 33
 #define GG_BINS 11
 #define GG_ROW 48                                     // bytes of a packed code row: three 16-byte operand chunks
-#define GG_MAX_K 32
 #define GG_WAVES 4                                    // waves of a matcher workgroup, 16 sources each
 #define GG_UNROLL 4                                   // target tiles whose loads a wave keeps in flight
 #define GG_TARGET_BLOCKS 2048                         // the matcher splits the targets until about this many workgroups exist (8 waves per SIMD) ...
 #define GG_MIN_TILES 64                               // ... but no split walks fewer than this many 16-target tiles
 #define GG_PAD_NORM (-0x3fffffff)                      // the "norm" of a padding row: below every 2 s.t - |t|^2, and |s|^2 minus it still fits an int
-#define GG_MAX_HYP (1 << 22)
 #define GG_SCORE_BLOCKS 2048
-#define GG_ERR_NORMAL 128                             // a non-finite normal
-#define GG_ERR_INDEX 256                              // a neighbour or correspondence index out of range
-#define GG_ERR_CODE 512                               // a code outside 0 .. 127
 
 typedef int gg_v4i __attribute__((ext_vector_type(4)));
 typedef unsigned long long gg_u64;
@@ -74,13 +69,13 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_spfh(const double* __r
     int* h = hist + i * GG_DIM;
     for (int c = 0; c < GG_DIM; ++c) h[c] = 0;
     int bad = 0, cnt = 0;
-    if (!ch_finite3(P + i * 3)) bad |= CH_ERR_FINITE;
-    if (!ch_finite3(Nrm + i * 3)) bad |= GG_ERR_NORMAL;
+    if (!ch_finite3(P + i * 3)) bad |= MVSDF_PC_ERR_FINITE;
+    if (!ch_finite3(Nrm + i * 3)) bad |= MVSDF_PC_ERR_NORMAL;
     const double ni[3] = {Nrm[i * 3], Nrm[i * 3 + 1], Nrm[i * 3 + 2]};
     for (int t = 0; t < k; ++t) {
         const long long j = nb[i * k + t];
         if (j < 0 || j >= n) {
-            bad |= GG_ERR_INDEX;
+            bad |= MVSDF_PC_ERR_INDEX;
             continue;
         }
         double d[3], d2;
@@ -123,14 +118,14 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_fpfh(const double* __r
     const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
     if (i >= n) return;
     int bad = 0;
-    if (!ch_finite3(P + i * 3)) bad |= CH_ERR_FINITE;
+    if (!ch_finite3(P + i * 3)) bad |= MVSDF_PC_ERR_FINITE;
     double acc[GG_DIM];
 #pragma unroll
     for (int c = 0; c < GG_DIM; ++c) acc[c] = 0.0;
     for (int t = 0; t < k; ++t) {
         const long long j = nb[i * k + t];
         if (j < 0 || j >= n) {
-            bad |= GG_ERR_INDEX;
+            bad |= MVSDF_PC_ERR_INDEX;
             continue;
         }
         double d[3], d2;
@@ -173,7 +168,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_pack(const signed char
 #pragma unroll
         for (int c = 0; c < GG_DIM; ++c) {
             const int v = codes[i * GG_DIM + c];
-            if (v < 0) bad = GG_ERR_CODE;
+            if (v < 0) bad = MVSDF_PC_ERR_CODE;
             const int u = v & 127;
             word[c >> 2] |= u << (8 * (c & 3));
             s += u * u;
@@ -418,7 +413,7 @@ __device__ __forceinline__ void gg_fit3(const double (&s)[3][3], const double (&
     }
 }
 
-// every correspondence: its indices in range (GG_ERR_INDEX), its two points finite (CH_ERR_FINITE)
+// every correspondence: its indices in range (MVSDF_PC_ERR_INDEX), its two points finite (MVSDF_PC_ERR_FINITE)
 static __global__ __launch_bounds__(CH_THREADS) void k_gg_corr_check(const double* __restrict__ src, long long ns, const double* __restrict__ dst, long long nd,
                                                                      const int* __restrict__ corr, long long m, long long* err) {
     const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
@@ -426,14 +421,17 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_corr_check(const doubl
     const long long a = corr[2 * i], b = corr[2 * i + 1];
     int bad = 0;
     if (a < 0 || a >= ns || b < 0 || b >= nd)
-        bad = GG_ERR_INDEX;
+        bad = MVSDF_PC_ERR_INDEX;
     else if (!ch_finite3(src + a * 3) || !ch_finite3(dst + b * 3))
-        bad = CH_ERR_FINITE;
+        bad = MVSDF_PC_ERR_FINITE;
     if (bad) atomicOr((gg_u64*)err, (gg_u64)bad);
 }
 
-// the workspace header (int64 words): the results the host reads, then the two words the kernels combine into
-enum { GG_H_HYP = 0, GG_H_INLIERS = 1, GG_H_CHECKED = 2, GG_H_ERR = 3, GG_H_T = 4, GG_H_BEST = 16, GG_H_COUNT = 17 };
+// the workspace header (int64 words): the results the host reads (MVSDF_GREG_RANSAC_H_*), then the two words the kernels combine into
+enum { GG_H_BEST = 16, GG_H_COUNT = 17 };
+static_assert(GG_H_BEST >= MVSDF_GREG_RANSAC_H_WORDS && GG_H_COUNT >= MVSDF_GREG_RANSAC_H_WORDS && (GG_H_COUNT + 1) * 8 <= CH_HDR &&
+                  MVSDF_GREG_RANSAC_H_WORDS * 8 <= CH_HDR && MVSDF_ERRW_H_WORDS * 8 <= CH_HDR,
+              "the private words lie behind the public ones, inside the header");
 
 static __global__ __launch_bounds__(CH_THREADS) void k_gg_hyp(const double* __restrict__ src, long long ns, const double* __restrict__ dst, long long nd,
                                                               const int* __restrict__ corr, long long m, long long hyps, gg_u64 seed, double ratio,
@@ -506,14 +504,14 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_winner(const int* __re
     const long long entries = hdr[GG_H_COUNT] & 0xffffffffll;
     const int h = best ? (int)~(unsigned)best : -1;
     if (e == 0) {
-        hdr[GG_H_HYP] = h;
-        hdr[GG_H_INLIERS] = (long long)(best >> 32);
-        hdr[GG_H_CHECKED] = entries;
+        hdr[MVSDF_GREG_RANSAC_H_HYP] = h;
+        hdr[MVSDF_GREG_RANSAC_H_INLIERS] = (long long)(best >> 32);
+        hdr[MVSDF_GREG_RANSAC_H_CHECKED] = entries;
         if (!best)
-            for (int q = 0; q < 12; ++q) hdr[GG_H_T + q] = __double_as_longlong(q % 5 == 0 ? 1.0 : 0.0);
+            for (int q = 0; q < 12; ++q) hdr[MVSDF_GREG_RANSAC_H_T + q] = __double_as_longlong(q % 5 == 0 ? 1.0 : 0.0);
     }
     if (best && e < entries && list[e] == h)
-        for (int q = 0; q < 12; ++q) hdr[GG_H_T + q] = __double_as_longlong(Ts[e * 12 + q]);
+        for (int q = 0; q < 12; ++q) hdr[MVSDF_GREG_RANSAC_H_T + q] = __double_as_longlong(Ts[e * 12 + q]);
 }
 
 static __global__ __launch_bounds__(CH_THREADS) void k_gg_mask(const double* __restrict__ src, long long ns, const double* __restrict__ dst, long long nd,
@@ -525,7 +523,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_gg_mask(const double* __r
     const long long a = corr[2 * i], b = corr[2 * i + 1];
     if (hdr[GG_H_BEST] && a >= 0 && a < ns && b >= 0 && b < nd) {
         double T[12], moved[3];
-        for (int q = 0; q < 12; ++q) T[q] = __longlong_as_double(hdr[GG_H_T + q]);
+        for (int q = 0; q < 12; ++q) T[q] = __longlong_as_double(hdr[MVSDF_GREG_RANSAC_H_T + q]);
         gg_move(T, src + a * 3, moved);
         in = gg_d2(moved, dst + b * 3) < max_dist * max_dist ? 1 : 0;
     }
@@ -537,7 +535,7 @@ struct GgRansacLayout {
 };
 
 static bool gg_ransac_layout(long long m, long long hyps, GgRansacLayout* L) {
-    if (m < 3 || m > INT_MAX || hyps < 1 || hyps > GG_MAX_HYP) return false;
+    if (m < 3 || m > INT_MAX || hyps < 1 || hyps > MVSDF_GREG_MAX_HYPOTHESES) return false;
     WsCursor c{CH_HDR};
     L->list = c.take((size_t)hyps * 4);
     L->Ts = c.take((size_t)hyps * 12 * 8);
@@ -549,7 +547,7 @@ extern "C" {
 
 int mvsdf_greg_spfh(const double* pts, const double* normals, const int32_t* neighbors, int64_t n, int32_t k, double radius2, int32_t* hist,
                     int32_t* count, int32_t* err, void* stream) {
-    if (!pts || !normals || !neighbors || !hist || !count || !err || n < 1 || n > INT_MAX || k < 1 || k > GG_MAX_K || !(radius2 > 0))
+    if (!pts || !normals || !neighbors || !hist || !count || !err || n < 1 || n > INT_MAX || k < 1 || k > MVSDF_PC_MAX_K || !(radius2 > 0))
         return mv_fail(-1, "mvsdf_greg_spfh: bad arguments");
     hipLaunchKernelGGL(k_gg_spfh, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, (hipStream_t)stream, pts, normals, (const int*)neighbors, (long long)n,
                        (int)k, radius2, (int*)hist, (int*)count, (int*)err);
@@ -558,7 +556,7 @@ int mvsdf_greg_spfh(const double* pts, const double* normals, const int32_t* nei
 
 int mvsdf_greg_fpfh(const double* pts, const int32_t* neighbors, const int32_t* hist, const int32_t* count, int64_t n, int32_t k, double radius2,
                     double* features, int8_t* codes, int32_t* err, void* stream) {
-    if (!pts || !neighbors || !hist || !count || !features || !codes || !err || n < 1 || n > INT_MAX || k < 1 || k > GG_MAX_K || !(radius2 > 0))
+    if (!pts || !neighbors || !hist || !count || !features || !codes || !err || n < 1 || n > INT_MAX || k < 1 || k > MVSDF_PC_MAX_K || !(radius2 > 0))
         return mv_fail(-1, "mvsdf_greg_fpfh: bad arguments");
     hipLaunchKernelGGL(k_gg_fpfh, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, (hipStream_t)stream, pts, (const int*)neighbors, (const int*)hist,
                        (const int*)count, (long long)n, (int)k, radius2, features, (signed char*)codes, (int*)err);
@@ -623,7 +621,7 @@ int mvsdf_greg_ransac(const double* src, int64_t ns, const double* dst, int64_t 
     int rc;
     if ((rc = mv_check(hipMemsetAsync(w, 0, CH_HDR, s), "mvsdf_greg_ransac"))) return rc;
     hipLaunchKernelGGL(k_gg_corr_check, dim3(mv_grid(M, CH_THREADS)), dim3(CH_THREADS), 0, s, src, (long long)ns, dst, (long long)nd, (const int*)corr, M,
-                       hdr + GG_H_ERR);
+                       hdr + MVSDF_GREG_RANSAC_H_ERR);
     hipLaunchKernelGGL(k_gg_hyp, dim3(mv_grid(H, CH_THREADS)), dim3(CH_THREADS), 0, s, src, (long long)ns, dst, (long long)nd, (const int*)corr, M, H,
                        (gg_u64)seed, edge_ratio, max_dist, list, Ts, (unsigned int*)(hdr + GG_H_COUNT));
     const unsigned blocks = (unsigned)(H < GG_SCORE_BLOCKS ? H : GG_SCORE_BLOCKS);

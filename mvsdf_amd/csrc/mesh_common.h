@@ -17,6 +17,8 @@
 #define MESH_CHUNK (MESH_THREADS * MESH_ROUNDS)
 #define MESH_SCAN_THREADS 1024
 #define MESH_HDR 256                                  // bytes at the start of every workspace: int64 results the host reads
+static_assert(MVSDF_MC_H_VERTS == 0 && MVSDF_MC_H_FACES == 1 && MVSDF_MC_H_BAD == 2 && MVSDF_MC_H_WORDS * 8 <= MESH_HDR && MVSDF_CC_H_WORDS * 8 <= MESH_HDR,
+              "k_mesh_scan's totals are the words of mvsdf_mc_count");
 
 static_assert(MC_MAX_TRIS < 8, "k_mc_* count triangles per cell with 3 ballots");
 

@@ -24,16 +24,8 @@
 #define CUT_GR_BATCH 4                                // relabel launches per host check
 #define CUT_PUSH_ITERS 64
 #define CUT_HDR 256                                   // bytes at the start of the workspace: int64 results the host reads
+static_assert(MVSDF_CUT_H_WORDS * 8 <= CUT_HDR, "the result words fit the header");
 #define CUT_EMPTY 0xffffffffffffffffull
-
-enum {
-    CUT_ERR_DUP_EDGE = 1,        // a directed edge in two faces (non-manifold edge or inconsistent winding)
-    CUT_ERR_REPEATED = 2,        // a face repeats a vertex id
-    CUT_ERR_RANGE = 4,           // a vertex id outside [0, nv)
-    CUT_ERR_HASH = 8,            // the half-edge table's probe bound (cannot happen at load factor 1/2)
-    CUT_ERR_ROUNDS = 16,         // the round limit was reached
-    CUT_ERR_RELABEL = 32,        // a global relabel did not settle within its launch limit
-};
 
 #define RLX(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define RLX_ST(p, x) __hip_atomic_store((p), (x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -53,13 +45,13 @@ __device__ __forceinline__ int face_ids(const int* __restrict__ faces, long long
     int bad = 0;
     for (int s = 0; s < 3; ++s) {
         id[s] = faces[f * 3 + s];
-        if (id[s] < 0 || id[s] >= nv) bad |= CUT_ERR_RANGE;
+        if (id[s] < 0 || id[s] >= nv) bad |= MVSDF_CUT_ERR_RANGE;
     }
-    if (!bad && (id[0] == id[1] || id[1] == id[2] || id[0] == id[2])) bad |= CUT_ERR_REPEATED;
+    if (!bad && (id[0] == id[1] || id[1] == id[2] || id[0] == id[2])) bad |= MVSDF_CUT_ERR_REPEATED;
     return bad;
 }
 
-// ---- adjacency, pass 1: every half-edge (id[k], id[k + 1]) of every usable face into an open-addressing table (keys are unique, else CUT_ERR_DUP_EDGE) ----
+// ---- adjacency, pass 1: every half-edge (id[k], id[k + 1]) of every usable face into an open-addressing table (keys are unique, else MVSDF_CUT_ERR_DUP_EDGE) ----
 __global__ __launch_bounds__(CUT_THREADS) void k_cut_insert(const int* __restrict__ faces, int nf, int nv, unsigned long long* keys, int* __restrict__ vals,
                                                              unsigned long long tmask, int* err) {
     const long long f = (long long)blockIdx.x * CUT_THREADS + threadIdx.x;
@@ -82,13 +74,13 @@ __global__ __launch_bounds__(CUT_THREADS) void k_cut_insert(const int* __restric
                 break;
             }
             if (prev == key) {
-                atomicOr(err, CUT_ERR_DUP_EDGE);
+                atomicOr(err, MVSDF_CUT_ERR_DUP_EDGE);
                 done = true;
                 break;
             }
             slot = (slot + 1) & tmask;
         }
-        if (!done) atomicOr(err, CUT_ERR_HASH);
+        if (!done) atomicOr(err, MVSDF_CUT_ERR_HASH);
     }
 }
 
@@ -350,7 +342,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
     int* flags = (int*)(w + L.flags);                             // [0, B): changed per relabel launch, [B, 2B): active per launch
     int* err = flags + 2 * CUT_GR_BATCH;
     unsigned long long* sums = (unsigned long long*)(w + L.flags + 2 * CUT_GR_BATCH * 4 + 8);
-    long long hdr[6] = {0, 0, 0, 0, 0, 0};                        // flow, removed faces, kept vertices, error bits, rounds, relabel launches
+    long long hdr[MVSDF_CUT_H_WORDS] = {};
     const unsigned gf = mv_grid(F, CUT_THREADS), gr = mv_grid(F, CUT_GR_CHUNK);
     int rc;
     if ((rc = mv_check(hipMemsetAsync(keys, 0xff, L.tsize * 8, s), "mvsdf_mesh_cut"))) return rc;
@@ -361,7 +353,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
     if ((rc = mv_check(hipGetLastError(), "mvsdf_mesh_cut"))) return rc;
     int e = 0;
     if ((rc = mv_read(&e, err, 4, s, "mvsdf_mesh_cut"))) return rc;
-    hdr[3] = e;
+    hdr[MVSDF_CUT_H_ERR] = e;
     if (!e) {
         if ((rc = mv_check(hipMemcpyAsync(excess0, excess, (size_t)F * 4, hipMemcpyDeviceToDevice, s), "mvsdf_mesh_cut"))) return rc;
         // Each round either moves excess or raises a height; the limit is a safety net far above what the meshes we know need.
@@ -374,7 +366,7 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
             int active = 0;
             while (!settled) {
                 if (launches >= max_relabel) {
-                    hdr[3] |= CUT_ERR_RELABEL;
+                    hdr[MVSDF_CUT_H_ERR] |= MVSDF_CUT_ERR_RELABEL;
                     break;
                 }
                 if ((rc = mv_check(hipMemsetAsync(flags, 0, 2 * CUT_GR_BATCH * 4, s), "mvsdf_mesh_cut"))) return rc;
@@ -392,18 +384,18 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
                     }
                 }
             }
-            hdr[5] += launches;
+            hdr[MVSDF_CUT_H_RELABELS] += launches;
             if (!settled) break;
             if (!active) {
                 done = true;
                 break;
             }
-            if (hdr[4] >= max_rounds) {
-                hdr[3] |= CUT_ERR_ROUNDS;
+            if (hdr[MVSDF_CUT_H_ROUNDS] >= max_rounds) {
+                hdr[MVSDF_CUT_H_ERR] |= MVSDF_CUT_ERR_ROUNDS;
                 break;
             }
             hipLaunchKernelGGL(k_cut_push, dim3(gf), dim3(CUT_THREADS), 0, s, F, (const int*)twin, cf, tcap, excess, h, inf);
-            ++hdr[4];
+            ++hdr[MVSDF_CUT_H_ROUNDS];
         }
         if (done) {
             hipLaunchKernelGGL(k_cut_zero, dim3(mv_grid(V, CUT_THREADS)), dim3(CUT_THREADS), 0, s, V, (int*)(w + L.vlab));
@@ -414,12 +406,12 @@ int mvsdf_mesh_cut(const float* colors, const int32_t* faces, int64_t nv, int64_
             if ((rc = mv_check(hipGetLastError(), "mvsdf_mesh_cut"))) return rc;
             unsigned long long sm[3];
             if ((rc = mv_read(sm, sums, sizeof(sm), s, "mvsdf_mesh_cut"))) return rc;
-            hdr[0] = (long long)sm[0];
-            hdr[1] = (long long)sm[1];
-            hdr[2] = (long long)sm[2];
+            hdr[MVSDF_CUT_H_FLOW] = (long long)sm[0];
+            hdr[MVSDF_CUT_H_REMOVED] = (long long)sm[1];
+            hdr[MVSDF_CUT_H_KEPT_VERTS] = (long long)sm[2];
         }
     }
-    return mv_write_header(w, hdr, 6, s, "mvsdf_mesh_cut");
+    return mv_write_header(w, hdr, MVSDF_CUT_H_WORDS, s, "mvsdf_mesh_cut");
 }
 
 int mvsdf_mesh_trim(const float* verts, const float* normals, const float* colors, const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes,

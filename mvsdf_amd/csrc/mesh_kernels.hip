@@ -415,16 +415,16 @@ __global__ __launch_bounds__(MESH_THREADS) void k_cc_best_face(const unsigned lo
     if (c < ncomp[0] && acc[c] == scal[1]) atomicMax(scal + 2, ~0ull - (unsigned long long)minface[c]);
 }
 
-// results: out[0] = components, out[1] = the largest one's label, out[2] / out[3] = its vertex / face counts, out[4] = 1 if a union-find loop hit its bound
+// the results, MVSDF_CC_H_*
 __global__ void k_cc_result(const long long* __restrict__ ncomp, const unsigned long long* __restrict__ scal, const int* __restrict__ flab, const int* __restrict__ cv,
                             const int* __restrict__ cf, const int* __restrict__ err, int nf, long long* __restrict__ out) {
     const long long f = nf ? (long long)(~0ull - scal[2]) : -1;
     const int l = f >= 0 && f < nf ? flab[f] : -1;
-    out[0] = ncomp[0];
-    out[1] = l;
-    out[2] = l >= 0 ? cv[l] : 0;
-    out[3] = l >= 0 ? cf[l] : 0;
-    out[4] = *err;
+    out[MVSDF_CC_H_COMPONENTS] = ncomp[0];
+    out[MVSDF_CC_H_LABEL] = l;
+    out[MVSDF_CC_H_VERTS] = l >= 0 ? cv[l] : 0;
+    out[MVSDF_CC_H_FACES] = l >= 0 ? cf[l] : 0;
+    out[MVSDF_CC_H_BOUND] = *err;
 }
 
 // ---- compaction of one component: kept vertices / faces in their original order, faces re-indexed ----
@@ -538,7 +538,7 @@ static int mc_count(const MeshVol& v, const McLayout& L, M m, void* ws, void* st
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mc_count<M>, dim3((unsigned)L.nb), dim3(MESH_THREADS), 0, s, v, L.npts, m, (int*)(w + L.bv), (int*)(w + L.bf));
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(w + L.bv), (const int*)(w + L.bf), (int)L.nb,
-                       (long long*)(w + L.ov), (long long*)(w + L.of), (long long*)w);
+                       (long long*)(w + L.ov), (long long*)(w + L.of), (long long*)w + MVSDF_MC_H_VERTS);
     return mv_check(hipGetLastError(), what);
 }
 

@@ -29,14 +29,9 @@
 
 #define SP_THREADS 256
 #define SP_HDR 256                                    // bytes at the start of the workspace: int64 results the host reads
+static_assert(MVSDF_SP_H_WORDS * 8 <= SP_HDR, "the result words fit the header");
 #define SP_CELL_BITS 21
 #define SP_LAMBDA 1e-3
-
-enum {
-    SP_ERR_FINITE = 1,       // a non-finite vertex
-    SP_ERR_RANGE = 2,        // a vertex id outside [0, nv)
-    SP_ERR_CELLS = 4,        // a cell index outside [0, 2^21)
-};
 
 // words of the device counters (uint64 each)
 enum { SP_C_ERR = 0, SP_C_DEG, SP_C_DUP, SP_C_PLACED, SP_C_NC, SP_C_NC2, SP_C_NF_OUT, SP_C_NV_OUT, SP_C_WORDS };
@@ -60,7 +55,7 @@ static __global__ __launch_bounds__(SP_THREADS) void k_sp_bbox_part(const float*
             b[3 + a] = fmax(b[3 + a], p[a]);
         }
     }
-    if (bad) atomicOr(cnt + SP_C_ERR, (unsigned long long)SP_ERR_FINITE);
+    if (bad) atomicOr(cnt + SP_C_ERR, (unsigned long long)MVSDF_SP_ERR_FINITE);
     for (int a = 0; a < 6; ++a) sh[a][threadIdx.x] = b[a];
     __syncthreads();
     for (int d = SP_THREADS / 2; d; d >>= 1) {
@@ -84,7 +79,7 @@ static __global__ __launch_bounds__(64) void k_sp_bbox_final(const double* __res
 static __global__ __launch_bounds__(SP_THREADS) void k_sp_face_check(const int* __restrict__ faces, long long ncorner, int nv, unsigned long long* cnt) {
     const long long c = (long long)blockIdx.x * SP_THREADS + threadIdx.x;
     const bool bad = c < ncorner && (faces[c] < 0 || faces[c] >= nv);
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(cnt + SP_C_ERR, (unsigned long long)SP_ERR_RANGE);
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(cnt + SP_C_ERR, (unsigned long long)MVSDF_SP_ERR_RANGE);
 }
 
 // ---- pass 2 ----
@@ -411,7 +406,7 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
     unsigned char* used = (unsigned char*)(w + L.used);
     void* tmp = w + L.S.tmp;
     const unsigned gv = mv_grid(V, SP_THREADS), gf = mv_grid(F, SP_THREADS), gc = mv_grid(C, SP_THREADS);
-    long long hdr[7] = {0, 0, 0, 0, 0, 0, 0};                     // clusters, vertices, faces, degenerate, duplicates, quadric-placed, error bits
+    long long hdr[MVSDF_SP_H_WORDS] = {};
     int rc;
     // ---- 1: box, finite check, id check ----
     if ((rc = mv_check(hipMemsetAsync(cnt, 0, SP_C_WORDS * 8, s), what))) return rc;
@@ -432,14 +427,14 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
             // the index is monotone in the coordinate: the box's corners bound every vertex's
             const double lo = floor((box[a] - g.o[a]) / cell), hi = floor((box[3 + a] - g.o[a]) / cell);
             if (!(lo >= 0.0) || !(hi < (double)(1 << SP_CELL_BITS))) {
-                e |= SP_ERR_CELLS;
+                e |= MVSDF_SP_ERR_CELLS;
                 break;
             }
             bits[a] = sp_bits((long long)hi);
         }
     if (e) {
-        hdr[6] = (long long)e;
-        return mv_write_header(w, hdr, 7, s, what);
+        hdr[MVSDF_SP_H_ERR] = (long long)e;
+        return mv_write_header(w, hdr, MVSDF_SP_H_WORDS, s, what);
     }
     g.sh1 = bits[2];
     g.sh0 = bits[2] + bits[1];
@@ -487,14 +482,14 @@ int mvsdf_mesh_simplify(const float* verts, const float* normals, const float* c
     if ((rc = mv_check(hipGetLastError(), what))) return rc;
     unsigned long long res[SP_C_WORDS];
     if ((rc = mv_read(res, cnt, sizeof(res), s, what))) return rc;
-    hdr[0] = nc;
-    hdr[1] = (long long)res[SP_C_NV_OUT];
-    hdr[2] = (long long)res[SP_C_NF_OUT];
-    hdr[3] = (long long)res[SP_C_DEG];
-    hdr[4] = (long long)res[SP_C_DUP];
-    hdr[5] = (long long)res[SP_C_PLACED];
-    hdr[6] = (long long)res[SP_C_ERR];
-    return mv_write_header(w, hdr, 7, s, what);
+    hdr[MVSDF_SP_H_CLUSTERS] = nc;
+    hdr[MVSDF_SP_H_VERTS] = (long long)res[SP_C_NV_OUT];
+    hdr[MVSDF_SP_H_FACES] = (long long)res[SP_C_NF_OUT];
+    hdr[MVSDF_SP_H_DEGENERATE] = (long long)res[SP_C_DEG];
+    hdr[MVSDF_SP_H_DUPLICATES] = (long long)res[SP_C_DUP];
+    hdr[MVSDF_SP_H_PLACED] = (long long)res[SP_C_PLACED];
+    hdr[MVSDF_SP_H_ERR] = (long long)res[SP_C_ERR];
+    return mv_write_header(w, hdr, MVSDF_SP_H_WORDS, s, what);
 }
 
 int mvsdf_mesh_simplify_emit(const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes, float* out_verts, float* out_normals,

@@ -21,12 +21,10 @@
 
 #define SMC_THREADS 256
 
-// int64 slots of the workspace header
-#define SMC_COUNT 0             // the last compaction's count (k_mesh_scan's totals: [0..2])
-#define SMC_BAD 3               // 1 once a non-finite evaluated value was seen
-#define SMC_STORES 4            // closure flag stores (per-wave sums; a block can be flagged by several faces)
-#define SMC_ERR 5               // 1 if a face's edge has no active owner (the closure did not close: never expected)
-#define SMC_TOTALS 8            // the count pass's scan: [8] vertices, [9] faces, [10] 1 if a count was negative
+// the workspace header is MVSDF_SMC_H_*; k_mesh_scan leaves three totals from _COUNT on (compactions) and from _VERTS on (the count pass)
+static_assert(MVSDF_SMC_H_COUNT + 3 <= MVSDF_SMC_H_BAD && MVSDF_SMC_H_FACES == MVSDF_SMC_H_VERTS + 1 && MVSDF_SMC_H_NEGATIVE == MVSDF_SMC_H_VERTS + 2 &&
+                  MVSDF_SMC_H_WORDS * 8 <= MESH_HDR,
+              "k_mesh_scan's totals are header words");
 
 struct SmcGrid {
     long long n;                // lattice points per axis
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_seed(const float* __restric
         near |= fabsf(v - g.level) <= tol;
     }
     map[b] = (in_any && out_any) || near ? 1 : 0;
-    if (bad) atomicOr(hdr + SMC_BAD, 1ull);
+    if (bad) atomicOr(hdr + MVSDF_SMC_H_BAD, 1ull);
 }
 
 // ---- compaction: per-workgroup counts of flagged (mode 0: state 1) or active (mode 1: state >= 2) blocks ----
@@ -191,7 +189,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_closure(const float* __rest
         }
     }
     const unsigned long long m = __ballot(hit);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(hdr + SMC_STORES, (unsigned long long)__popcll(m));
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(hdr + MVSDF_SMC_H_STORES, (unsigned long long)__popcll(m));
 }
 
 // ---- row metadata: per place r of sblk, the active blocks of its i-slab [x, y) and of its (i, j)-column [z, w) ----
@@ -343,7 +341,7 @@ __device__ __forceinline__ int smc_edge_vertex(const float* __restrict__ vals, c
     for (int x = 0; x < 3; ++x) ob[x] = (int)min(q[x] / g.B, (long long)g.nb - 1);
     const int st = map[blk_lin(ob, g.nb)];
     if (st < 2) {
-        atomicOr(hdr + SMC_ERR, 1ull);
+        atomicOr(hdr + MVSDF_SMC_H_OWNER, 1ull);
         return -1;
     }
     const long long slot = st - 2;
@@ -449,7 +447,7 @@ static void smc_compact(const SmcLayout& L, char* w, int mode, long long base, h
     int* map = (int*)(w + L.map);
     hipLaunchKernelGGL(k_smc_flag_count, dim3((unsigned)L.nwg), dim3(MESH_THREADS), 0, s, (const int*)map, L.nblk, mode, (int*)(w + L.bc));
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(w + L.bc), (const int*)nullptr, (int)L.nwg, (long long*)(w + L.bo),
-                       (long long*)nullptr, (long long*)w + SMC_COUNT);
+                       (long long*)nullptr, (long long*)w + MVSDF_SMC_H_COUNT);
     hipLaunchKernelGGL(k_smc_compact, dim3((unsigned)L.nwg), dim3(MESH_THREADS), 0, s, map, L.nblk, mode, (const long long*)(w + L.bo), base,
                        (int*)(w + L.list), (int*)(w + L.sblk));
 }
@@ -533,11 +531,11 @@ int mvsdf_smc_count(const float* values, int64_t n, int64_t block, float level, 
     hipLaunchKernelGGL(k_smc_meta, dim3(mv_grid(nactive, SMC_THREADS)), dim3(SMC_THREADS), 0, s, (const int*)(w + L.sblk), (int)nactive, L.g.nb,
                        (int4*)(w + L.meta));
     const unsigned fin_wgs = mv_grid(nactive * P3, MV_THREADS) < 4096u ? mv_grid(nactive * P3, MV_THREADS) : 4096u;
-    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3(fin_wgs), dim3(MV_THREADS), 0, s, values, nactive * P3, (unsigned long long*)w + SMC_BAD, 1ull);   // one flag for the whole pool
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3(fin_wgs), dim3(MV_THREADS), 0, s, values, nactive * P3, (unsigned long long*)w + MVSDF_SMC_H_BAD, 1ull);   // one flag for the whole pool
     hipLaunchKernelGGL(k_smc_count, dim3((unsigned)E.nwg), dim3(MESH_THREADS), 0, s, values, L.g, (const int*)(w + L.map), (const int*)(w + L.sblk),
                        (const int4*)(w + L.meta), E.nrows, smc_bits(3ll * L.g.R), smc_bits((long long)MC_MAX_TRIS * L.g.B), (int*)(x + E.bv), (int*)(x + E.bf));
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, s, (const int*)(x + E.bv), (const int*)(x + E.bf), (int)E.nwg, (long long*)(x + E.ov),
-                       (long long*)(x + E.of), (long long*)w + SMC_TOTALS);
+                       (long long*)(x + E.of), (long long*)w + MVSDF_SMC_H_VERTS);
     return mv_check(hipGetLastError(), "mvsdf_smc_count");
 }
 

@@ -28,16 +28,6 @@
 #define CH_MARGIN2 (1.0 + 4e-9)                       // relative margin of a box prune on squared distances
 #define CH_CELL_LIMIT 2147483648.0                    // |coordinate / cell| bound that keeps the 27-cell search exact
 
-enum {
-    CH_ERR_POINTS = 1,      // sampling: more points than max_points
-    CH_ERR_RANGE = 2,       // sampling: a vertex id outside [0, nv)
-    CH_ERR_FINITE = 4,      // a non-finite coordinate
-    CH_ERR_COORD = 8,       // downsampling: a coordinate too far from the origin for the cell grid
-    CH_ERR_HASH = 16,       // the cell table's probe bound (cannot happen at load factor 1/2)
-    CH_ERR_ROUNDS = 32,     // downsampling: the round limit was reached
-    CH_ERR_WALK = 64,       // nearest: a tree walk hit its bound (cannot happen)
-};
-
 __device__ __forceinline__ double ch_d2(double ax, double ay, double az, double bx, double by, double bz) {
     const double dx = ax - bx, dy = ay - by, dz = az - bz;
     return (dx * dx + dy * dy) + dz * dz;
@@ -46,7 +36,7 @@ __device__ __forceinline__ double ch_d2(double ax, double ay, double az, double 
 __device__ __forceinline__ bool ch_finite3(const double* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
 // ================================================================ the tree ================================================================
-// per-workgroup box of the references (k_nn_bbox_final combines them); a non-finite coordinate raises CH_ERR_FINITE
+// per-workgroup box of the references (k_nn_bbox_final combines them); a non-finite coordinate raises MVSDF_PC_ERR_FINITE
 static __global__ __launch_bounds__(CH_THREADS) void k_nn_bbox_part(const double* __restrict__ R, long long n, double* __restrict__ part, int* err) {
     __shared__ double sh[6][CH_THREADS];
     const long long base = (long long)blockIdx.x * CH_CHUNK;
@@ -65,7 +55,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_nn_bbox_part(const double
             b[3 + a] = fmax(b[3 + a], p[a]);
         }
     }
-    if (bad) atomicOr(err, CH_ERR_FINITE);
+    if (bad) atomicOr(err, MVSDF_PC_ERR_FINITE);
     for (int a = 0; a < 6; ++a) sh[a][threadIdx.x] = b[a];
     __syncthreads();
     for (int d = CH_THREADS / 2; d; d >>= 1) {
@@ -216,7 +206,7 @@ __device__ __forceinline__ double ch_box_lb2(const double* __restrict__ b, doubl
 // Depth first over the implicit tree, children in index order, no stack (parent = i / 8, next sibling = i + 1).  A node is entered when the lower
 // bound of its box is <= bound() -- the caller's current bound on squared distances, CH_MARGIN2 already in it; inclusive, so a box that may hold an
 // equal distance is never passed over -- and leaf(l) is called for every leaf entered.  The walk ends at the first node whose sorted positions all
-// lie above `last` (every later node's do too).  false: the step bound was reached (cannot happen; the caller raises CH_ERR_WALK).
+// lie above `last` (every later node's do too).  false: the step bound was reached (cannot happen; the caller raises MVSDF_PC_ERR_WALK).
 template <class Bound, class Leaf>
 __device__ __forceinline__ bool ch_walk(const double* __restrict__ box, const ChTree& T, double x, double y, double z, Bound bound, Leaf leaf,
                                         long long last = LLONG_MAX) {
@@ -358,7 +348,7 @@ static bool ch_tree_layout(long long nr, WsCursor& c, ChTreeLayout* L) {
     return true;
 }
 
-// the box of the points -> frame; a non-finite coordinate raises CH_ERR_FINITE in *err
+// the box of the points -> frame; a non-finite coordinate raises MVSDF_PC_ERR_FINITE in *err
 static void ch_tree_frame(const double* refs, long long nr, char* w, const ChTreeLayout& L, int* err, hipStream_t s) {
     hipLaunchKernelGGL(k_nn_bbox_part, dim3((unsigned)L.nbr), dim3(CH_THREADS), 0, s, refs, nr, (double*)(w + L.part), err);
     hipLaunchKernelGGL(k_nn_bbox_final, dim3(1), dim3(64), 0, s, (const double*)(w + L.part), L.nbr, (double*)(w + L.frame));

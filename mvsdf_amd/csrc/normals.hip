@@ -20,19 +20,16 @@
 // * Component sign: smallest index, highest point along `up` (the bits of the height, then the index among those that reach it) and the view votes
 //   are integer atomics, the lanes of a wave that share a root combined first (k_cl_roots' scheme).
 //
-// Every device loop is bounded; the round loop on the host stops at NR_MAX_ROUNDS with CH_ERR_ROUNDS.  Integer atomics only.
+// Every device loop is bounded; the round loop on the host stops at NR_MAX_ROUNDS with MVSDF_PC_ERR_ROUNDS.  Integer atomics only.
 #include "nn_tree.h"
 
-#define NR_MAX_K 32
 #define NR_SWEEPS 6
 #define NR_MAX_ROUNDS 64
 #define NR_MAX_JUMPS 64                               // repeats of the jump launch in one round
 #define NR_JUMP_STEPS 4096                            // hops of one lane before it gives the launch up
-#define NR_MAX_VIEWS 65535
-#define NR_ERR_NORMAL 128                             // a non-finite normal
-#define NR_ERR_INDEX 256                              // a neighbour index outside [0, n)
 
 typedef unsigned long long nr_u64;
+static_assert(MVSDF_NR_ORIENT_H_WORDS * 8 <= CH_HDR && MVSDF_ERRW_H_WORDS <= MVSDF_NR_ORIENT_H_WORDS, "the result words fit the header");
 
 // flags (int): [0] error bits, [1] pending, [2] hooks of the round, [3] n_components
 enum { NR_F_ERR = 0, NR_F_PENDING = 1, NR_F_HOOKS = 2, NR_F_COMPONENTS = 3, NR_F_WORDS = 8 };
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_nr_knn(const double* __restrict_
         list.bd[j] = j < CAP - k ? -1.0 : INFINITY;
         list.bi[j] = j < CAP - k ? -1 : INT_MAX;
     }
-    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, CH_ERR_WALK);
+    if (!ch_knn_lane(sp, box, T, p, list)) atomicOr(err, MVSDF_PC_ERR_WALK);
     const long long row = (long long)perm[p] * k;
 #pragma unroll
     for (int j = 0; j < CAP; ++j)
@@ -213,11 +210,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_nr_init(const double* __restrict
     neg[i] = 0;
     pos[i] = 0;
     int bad = 0;
-    if (!ch_finite3(pts + i * 3)) bad |= CH_ERR_FINITE;
-    if (!ch_finite3(nrm + i * 3)) bad |= NR_ERR_NORMAL;
+    if (!ch_finite3(pts + i * 3)) bad |= MVSDF_PC_ERR_FINITE;
+    if (!ch_finite3(nrm + i * 3)) bad |= MVSDF_PC_ERR_NORMAL;
     for (int j = 0; j < k; ++j) {
         const int q = nbr[i * k + j];
-        if (q < 0 || q >= n) bad |= NR_ERR_INDEX;
+        if (q < 0 || q >= n) bad |= MVSDF_PC_ERR_INDEX;
     }
     if (bad) atomicOr(flags + NR_F_ERR, bad);
 }
@@ -422,25 +419,25 @@ __global__ __launch_bounds__(CH_THREADS) void k_nr_orient_out(const double* __re
 
 __global__ __launch_bounds__(64) void k_nr_orient_header(const int* __restrict__ flags, long long rounds, long long* __restrict__ hdr) {
     if (threadIdx.x) return;
-    hdr[0] = flags[NR_F_COMPONENTS];
-    hdr[1] = rounds;
-    hdr[2] = flags[NR_F_ERR];
+    hdr[MVSDF_NR_ORIENT_H_COMPONENTS] = flags[NR_F_COMPONENTS];
+    hdr[MVSDF_NR_ORIENT_H_ROUNDS] = rounds;
+    hdr[MVSDF_NR_ORIENT_H_ERR] = flags[NR_F_ERR];
 }
 
 __global__ __launch_bounds__(64) void k_nr_knn_header(const int* __restrict__ flags, long long* __restrict__ hdr) {
     if (threadIdx.x) return;
-    hdr[0] = flags[NR_F_ERR];
+    hdr[MVSDF_ERRW_H_ERR] = flags[NR_F_ERR];
 }
 
-// each normal flipped iff more of its own seeing views lie behind it than before it; hdr[0] = error bits
+// each normal flipped iff more of its own seeing views lie behind it than before it; hdr = the error word
 __global__ __launch_bounds__(CH_THREADS) void k_nr_to_views(const double* __restrict__ pts, const double* __restrict__ nrm, long long n,
                                                              const double* __restrict__ centers, const nr_u64* __restrict__ bits, int nw, int V,
                                                              double* __restrict__ out, nr_u64* hdr) {
     const long long i = (long long)blockIdx.x * CH_THREADS + threadIdx.x;
     if (i >= n) return;
     int bad = 0;
-    if (!ch_finite3(pts + i * 3)) bad |= CH_ERR_FINITE;
-    if (!ch_finite3(nrm + i * 3)) bad |= NR_ERR_NORMAL;
+    if (!ch_finite3(pts + i * 3)) bad |= MVSDF_PC_ERR_FINITE;
+    if (!ch_finite3(nrm + i * 3)) bad |= MVSDF_PC_ERR_NORMAL;
     if (bad) atomicOr(hdr, (nr_u64)bad);
     unsigned a, b;
     nr_votes(pts, nrm, centers, bits, nw, V, i, &a, &b);
@@ -449,7 +446,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_nr_to_views(const double* __rest
 
 __global__ __launch_bounds__(CH_THREADS) void k_nr_centers_finite(const double* __restrict__ centers, int V, nr_u64* err) {
     const int v = blockIdx.x * CH_THREADS + threadIdx.x;
-    if (v < V && !ch_finite3(centers + v * 3)) atomicOr(err, (nr_u64)CH_ERR_FINITE);
+    if (v < V && !ch_finite3(centers + v * 3)) atomicOr(err, (nr_u64)MVSDF_PC_ERR_FINITE);
 }
 
 // ================================================================ host ================================================================
@@ -489,9 +486,10 @@ static bool nr_orient_layout(long long n, NrOrientLayout* L) {
     return true;
 }
 
-static int nr_fail_header(void* ws, int words, long long err, hipStream_t s, const char* what) {
-    long long hdr[3] = {0, 0, 0};
-    hdr[words - 1] = err;
+// a header of zeros but for its error word
+static int nr_fail_header(void* ws, int words, int err_word, long long err, hipStream_t s, const char* what) {
+    long long hdr[MVSDF_NR_ORIENT_H_WORDS] = {};
+    hdr[err_word] = err;
     return mv_write_header(ws, hdr, words, s, what);
 }
 
@@ -513,7 +511,7 @@ int mvsdf_normals_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t 
                       void* stream) {
     const char* what = "mvsdf_normals_knn";
     NrKnnLayout L;
-    if (!pts || !ws || !idx || (!normals != !variation) || k < 1 || k > NR_MAX_K || n < (int64_t)k + 1 || !nr_knn_layout(n, &L))
+    if (!pts || !ws || !idx || (!normals != !variation) || k < 1 || k > MVSDF_PC_MAX_K || n < (int64_t)k + 1 || !nr_knn_layout(n, &L))
         return mv_fail(-1, "mvsdf_normals_knn: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_normals_knn: workspace too small (mvsdf_normals_knn_workspace_bytes)");
     char* w = (char*)ws;
@@ -523,7 +521,7 @@ int mvsdf_normals_knn(const double* pts, int64_t n, int32_t k, void* ws, size_t 
     if ((rc = mv_check(hipMemsetAsync(fl, 0, NR_F_WORDS * 4, s), what))) return rc;
     const ChBuilt tree = ch_tree_begin(pts, n, w, L.t, fl + NR_F_ERR, s, what);
     if (tree.rc) return tree.rc;
-    if (tree.err) return nr_fail_header(w, 1, tree.err, s, what);
+    if (tree.err) return nr_fail_header(w, MVSDF_ERRW_H_WORDS, MVSDF_ERRW_H_ERR, tree.err, s, what);
     const double* sp = (const double*)(w + L.t.sp);
     const double* box = (const double*)(w + L.t.box);
     ch_knn_dispatch(k, [&](auto cap) {
@@ -540,8 +538,8 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
                          const double* centers, const void* bits, int64_t V, void* ws, size_t ws_bytes, double* out, int32_t* labels, void* stream) {
     const char* what = "mvsdf_normals_orient";
     NrOrientLayout L;
-    if (!pts || !normals || !neighbors || !ws || !out || !labels || out == normals || k < 1 || k > NR_MAX_K || !isfinite(ux) || !isfinite(uy) ||
-        !isfinite(uz) || (!centers != !bits) || (centers && (V < 1 || V > NR_MAX_VIEWS)) || !nr_orient_layout(n, &L))
+    if (!pts || !normals || !neighbors || !ws || !out || !labels || out == normals || k < 1 || k > MVSDF_PC_MAX_K || !isfinite(ux) || !isfinite(uy) ||
+        !isfinite(uz) || (!centers != !bits) || (centers && (V < 1 || V > MVSDF_VS_MAX_VIEWS)) || !nr_orient_layout(n, &L))
         return mv_fail(-1, "mvsdf_normals_orient: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_normals_orient: workspace too small (mvsdf_normals_orient_workspace_bytes)");
     char* w = (char*)ws;
@@ -567,7 +565,7 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
     if (centers) hipLaunchKernelGGL(k_nr_centers_finite, dim3(mv_grid(V, CH_THREADS)), b, 0, s, centers, nv, err64);
     long long rounds = 0;
     for (int turn = 0;; ++turn) {
-        if (turn >= NR_MAX_ROUNDS) return nr_fail_header(w, 3, CH_ERR_ROUNDS, s, what);
+        if (turn >= NR_MAX_ROUNDS) return nr_fail_header(w, MVSDF_NR_ORIENT_H_WORDS, MVSDF_NR_ORIENT_H_ERR, MVSDF_PC_ERR_ROUNDS, s, what);
         if ((rc = mv_check(hipMemsetAsync(fl + NR_F_PENDING, 0, 8, s), what))) return rc;       // pending and hooks
         hipLaunchKernelGGL(k_nr_round_begin, g, b, 0, s, (const unsigned*)state, N, best_a, best_e);
         hipLaunchKernelGGL(k_nr_best_a, g, b, 0, s, normals, neighbors, N, K, (const unsigned*)state, best_a);
@@ -575,14 +573,14 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
         hipLaunchKernelGGL(k_nr_hook, g, b, 0, s, normals, N, (const unsigned*)state, (const nr_u64*)best_e, link, fl);
         int r[3];
         for (int jump = 0;; ++jump) {
-            if (jump >= NR_MAX_JUMPS) return nr_fail_header(w, 3, CH_ERR_ROUNDS, s, what);
+            if (jump >= NR_MAX_JUMPS) return nr_fail_header(w, MVSDF_NR_ORIENT_H_WORDS, MVSDF_NR_ORIENT_H_ERR, MVSDF_PC_ERR_ROUNDS, s, what);
             hipLaunchKernelGGL(k_nr_jump, g, b, 0, s, N, (const unsigned*)state, link, fl);
             if ((rc = mv_check(hipGetLastError(), what))) return rc;
             if ((rc = mv_read(r, fl, sizeof(r), s, what))) return rc;
             if (r[NR_F_ERR] || !r[NR_F_PENDING]) break;
             if ((rc = mv_check(hipMemsetAsync(fl + NR_F_PENDING, 0, 4, s), what))) return rc;
         }
-        if (r[NR_F_ERR]) return nr_fail_header(w, 3, r[NR_F_ERR], s, what);
+        if (r[NR_F_ERR]) return nr_fail_header(w, MVSDF_NR_ORIENT_H_WORDS, MVSDF_NR_ORIENT_H_ERR, r[NR_F_ERR], s, what);
         if (!r[NR_F_HOOKS]) break;
         ++rounds;
         hipLaunchKernelGGL(k_nr_apply, g, b, 0, s, N, state, (const unsigned*)link);
@@ -591,7 +589,7 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
     if (centers) {
         nr_u64 e = 0;
         if ((rc = mv_read(&e, err64, 8, s, what))) return rc;
-        if (e) return nr_fail_header(w, 3, (long long)e, s, what);
+        if (e) return nr_fail_header(w, MVSDF_NR_ORIENT_H_WORDS, MVSDF_NR_ORIENT_H_ERR, (long long)e, s, what);
     }
     hipLaunchKernelGGL(k_nr_gather, g, b, 0, s, pts, normals, N, (const unsigned*)state, ux, uy, uz, centers, (const nr_u64*)bits, nw, nv, minidx, hkey, neg,
                        pos, fl);
@@ -605,10 +603,10 @@ int mvsdf_normals_orient(const double* pts, const double* normals, const int32_t
 int mvsdf_normals_to_views(const double* pts, const double* normals, int64_t n, const double* centers, const void* bits, int64_t V, double* out, void* hdr,
                            void* stream) {
     const char* what = "mvsdf_normals_to_views";
-    if (!pts || !normals || !centers || !bits || !out || !hdr || out == normals || n < 1 || n > INT_MAX || V < 1 || V > NR_MAX_VIEWS)
+    if (!pts || !normals || !centers || !bits || !out || !hdr || out == normals || n < 1 || n > INT_MAX || V < 1 || V > MVSDF_VS_MAX_VIEWS)
         return mv_fail(-1, "mvsdf_normals_to_views: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = mv_check(hipMemsetAsync(hdr, 0, 8, s), what)) return rc;
+    if (int rc = mv_check(hipMemsetAsync(hdr, 0, MVSDF_ERRW_H_WORDS * 8, s), what)) return rc;
     hipLaunchKernelGGL(k_nr_centers_finite, dim3(mv_grid(V, CH_THREADS)), dim3(CH_THREADS), 0, s, centers, (int)V, (nr_u64*)hdr);
     hipLaunchKernelGGL(k_nr_to_views, dim3(mv_grid(n, CH_THREADS)), dim3(CH_THREADS), 0, s, pts, normals, (long long)n, centers, (const nr_u64*)bits,
                        nr_words(V), (int)V, out, (nr_u64*)hdr);

@@ -18,36 +18,30 @@
 // is found on the device (k_any_nonfinite) and comes back as an error bit too; the passes after it stay inside their arrays whatever the values are.
 #include "geom_prims.h"
 
-#define PO_HDR 256                                    // bytes at the start of the workspace: int64 {n_used, error bits, T, residual0, residual} (doubles as bits)
+#define PO_HDR 256                                    // bytes at the start of the workspace: MVSDF_PO_H_*
+static_assert(MVSDF_PO_H_WORDS * 8 <= PO_HDR && MVSDF_PO_H_ERR == MVSDF_RES_H_ERR, "the result words fit the header; mv_refuse_header writes its error word");
 #define PO_BK 64                                      // the workgroup of the stencil passes: PO_BK lattice points along k, PO_BJ along j
 #define PO_BJ 4
 #define PO_THREADS (PO_BK * PO_BJ)
 #define PO_TREE_ITEMS 8
 #define PO_TREE (PO_THREADS * PO_TREE_ITEMS)          // the chunk of the tree sum: a power of two
-#define PO_MIN_DEPTH 2
-#define PO_MAX_DEPTH 10
 #define PO_SCALE 4294967296.0                         // 2^32
 #define PO_UNSCALE (1.0 / 4294967296.0)
 static_assert((PO_TREE & (PO_TREE - 1)) == 0 && (PO_THREADS & (PO_THREADS - 1)) == 0, "the tree sum needs power-of-two chunks");
 
-enum {
-    PO_ERR_FINITE = 1,      // a non-finite coordinate, normal, origin or voxel
-    PO_ERR_RANGE = 2,       // depth outside [2, 10], cycles < 0, sweeps < 1, voxel <= 0
-    PO_ERR_SHAPE = 4,       // no points, or more than 2^31 - 1
-};
 enum { PO_STAGE_SPLAT = 1, PO_STAGE_SOLVE = 2, PO_STAGE_ISO = 4 };
 
 typedef unsigned long long po_u64;
 
 struct PoLayout {
-    size_t vq[4], b0, lx[PO_MAX_DEPTH], lb[PO_MAX_DEPTH], flags, off, scan, tree[2], total;
+    size_t vq[4], b0, lx[MVSDF_PO_MAX_DEPTH], lb[MVSDF_PO_MAX_DEPTH], flags, off, scan, tree[2], total;
     long long N, vol;
 };
 
 static inline long long po_side(int depth, int level) { return (1ll << (depth - level)) + 1; }
 
 static bool po_layout(long long n, int depth, PoLayout* L) {
-    if (depth < PO_MIN_DEPTH || depth > PO_MAX_DEPTH || n < 1 || n > INT_MAX) return false;
+    if (depth < MVSDF_PO_MIN_DEPTH || depth > MVSDF_PO_MAX_DEPTH || n < 1 || n > INT_MAX) return false;
     L->N = po_side(depth, 0);
     L->vol = L->N * L->N * L->N;
     WsCursor c{PO_HDR};
@@ -311,15 +305,12 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
     // ---- validation, all of it before the first launch ----
     long long err = 0;
     PoLayout L;
-    if (depth < PO_MIN_DEPTH || depth > PO_MAX_DEPTH || cycles < 0 || sweeps < 1) err |= PO_ERR_RANGE;
-    if (n < 1 || n > INT_MAX) err |= PO_ERR_SHAPE;
-    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2]) || !isfinite(voxel)) err |= PO_ERR_FINITE;
-    else if (!(voxel > 0.0)) err |= PO_ERR_RANGE;
-    if (!err && !po_layout(n, depth, &L)) err |= PO_ERR_SHAPE;
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (depth < MVSDF_PO_MIN_DEPTH || depth > MVSDF_PO_MAX_DEPTH || cycles < 0 || sweeps < 1) err |= MVSDF_PO_ERR_RANGE;
+    if (n < 1 || n > INT_MAX) err |= MVSDF_PO_ERR_SHAPE;
+    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2]) || !isfinite(voxel)) err |= MVSDF_PO_ERR_FINITE;
+    else if (!(voxel > 0.0)) err |= MVSDF_PO_ERR_RANGE;
+    if (!err && !po_layout(n, depth, &L)) err |= MVSDF_PO_ERR_SHAPE;
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_poisson_reconstruct: workspace too small (mvsdf_poisson_workspace_bytes)");
     char* w = (char*)ws;
     int rc;
@@ -334,19 +325,19 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
         if ((rc = mv_check(hipMemsetAsync(ws, 0, PO_HDR, s), what))) return rc;
         if ((rc = mv_check(hipMemsetAsync(w + L.vq[0], 0, L.b0 - L.vq[0], s), what))) return rc;   // the four int64 volumes are one run
         const unsigned cap = pgrid < 4096u ? pgrid : 4096u;
-        hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(cap), dim3(MV_THREADS), 0, s, points, (long long)n * 3, hdr + 1, (po_u64)PO_ERR_FINITE);
-        hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(cap), dim3(MV_THREADS), 0, s, normals, (long long)n * 3, hdr + 1, (po_u64)PO_ERR_FINITE);
+        hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(cap), dim3(MV_THREADS), 0, s, points, (long long)n * 3, hdr + MVSDF_PO_H_ERR, (po_u64)MVSDF_PO_ERR_FINITE);
+        hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(cap), dim3(MV_THREADS), 0, s, normals, (long long)n * 3, hdr + MVSDF_PO_H_ERR, (po_u64)MVSDF_PO_ERR_FINITE);
         hipLaunchKernelGGL(k_po_splat, dim3(pgrid), dim3(PO_THREADS), 0, s, points, normals, (long long)n, g, (po_u64*)(w + L.vq[0]), (po_u64*)(w + L.vq[1]),
                            (po_u64*)(w + L.vq[2]), (po_u64*)(w + L.vq[3]), (unsigned char*)(w + L.flags));
         hipLaunchKernelGGL(k_po_rhs, po_grid3(L.N), po_block3(), 0, s, (const long long*)(w + L.vq[0]), (const long long*)(w + L.vq[1]),
                            (const long long*)(w + L.vq[2]), (const long long*)(w + L.vq[3]), g.N, 2.0 * voxel, (double*)(w + L.b0), density);
-        mv_scan((const unsigned char*)(w + L.flags), (long long)n, (long long*)(w + L.off), w + L.scan, (long long*)ws, s);
+        mv_scan((const unsigned char*)(w + L.flags), (long long)n, (long long*)(w + L.off), w + L.scan, (long long*)ws + MVSDF_PO_H_USED, s);
     }
     if (stages & PO_STAGE_SOLVE) {
-        double* x[PO_MAX_DEPTH];
-        double* b[PO_MAX_DEPTH];
-        double h2[PO_MAX_DEPTH];
-        long long side[PO_MAX_DEPTH];
+        double* x[MVSDF_PO_MAX_DEPTH];
+        double* b[MVSDF_PO_MAX_DEPTH];
+        double h2[MVSDF_PO_MAX_DEPTH];
+        long long side[MVSDF_PO_MAX_DEPTH];
         for (int l = 0; l < depth; ++l) {
             x[l] = l ? (double*)(w + L.lx[l]) : chi;
             b[l] = l ? (double*)(w + L.lb[l]) : (double*)(w + L.b0);
@@ -358,7 +349,7 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
         if ((rc = mv_check(hipMemsetAsync(chi, 0, volb, s), what))) return rc;
         if ((rc = mv_check(hipMemsetAsync(x[depth - 1], 0, 27 * 8, s), what))) return rc;
         hipLaunchKernelGGL(k_po_resid, po_grid3(side[0]), po_block3(), 0, s, (const double*)x[0], (const double*)b[0], (int)side[0], h2[0], (double*)nullptr,
-                           hdr + 3);
+                           hdr + MVSDF_PO_H_RESIDUAL0);
         auto smooth = [&](int l) {
             for (int q = 0; q < sweeps; ++q)
                 for (int colour = 0; colour < 2; ++colour)
@@ -379,7 +370,7 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
             }
         }
         hipLaunchKernelGGL(k_po_resid, po_grid3(side[0]), po_block3(), 0, s, (const double*)x[0], (const double*)b[0], (int)side[0], h2[0], (double*)nullptr,
-                           hdr + 4);
+                           hdr + MVSDF_PO_H_RESIDUAL);
     }
     if (stages & PO_STAGE_ISO) {
         if ((rc = mv_check(hipMemsetAsync(values, 0, (size_t)n * 8, s), what))) return rc;
@@ -389,7 +380,7 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
         long long len = n;
         for (int turn = 0;; ++turn) {
             const long long nb = mv_ceil_div(len, PO_TREE);
-            double* out = nb == 1 ? (double*)(hdr + 2) : (double*)(w + L.tree[turn & 1]);
+            double* out = nb == 1 ? (double*)(hdr + MVSDF_PO_H_T) : (double*)(w + L.tree[turn & 1]);
             hipLaunchKernelGGL(k_po_tree, dim3((unsigned)nb), dim3(PO_THREADS), 0, s, in, len, out);
             if (nb == 1) break;
             in = out;
@@ -401,7 +392,7 @@ int mvsdf_poisson_reconstruct(const double* points, const double* normals, int64
 
 int mvsdf_poisson_valid(const double* density, int32_t depth, double min_density, int32_t dilate, uint8_t* tmp, uint8_t* valid, void* stream) {
     const char* what = "mvsdf_poisson_valid";
-    if (!density || !valid || depth < PO_MIN_DEPTH || depth > PO_MAX_DEPTH || dilate < 0 || (dilate > 0 && !tmp) || isnan(min_density))
+    if (!density || !valid || depth < MVSDF_PO_MIN_DEPTH || depth > MVSDF_PO_MAX_DEPTH || dilate < 0 || (dilate > 0 && !tmp) || isnan(min_density))
         return mv_fail(-1, "mvsdf_poisson_valid: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const long long N = po_side(depth, 0), vol = N * N * N;

@@ -19,16 +19,12 @@
 #include "geom_prims.h"
 
 #define RA_THREADS 256
-#define RA_HDR 256                                    // bytes at the start of the workspace: int64 {error bits, large items, atomics, covered}
+#define RA_HDR 256                                    // bytes at the start of the workspace: MVSDF_RA_H_*
+static_assert(MVSDF_RA_H_WORDS * 8 <= RA_HDR, "the result words fit the header");
 #define RA_WAVES (RA_THREADS / 64)
 #define RA_LARGE_BLOCKS 4096                          // workgroups of the large path (it strides over the list)
-#define RA_MAX_VIEWS 65535
-#define RA_MAX_PIXELS (1ll << 40)
+#define RA_MAX_PIXELS (1ll << MVSDF_RA_MAX_PIXELS_LOG2)
 
-enum {
-    RA_ERR_FINITE = 1,      // a camera entry is NaN or infinite
-    RA_ERR_INDEX = 2,       // a face refers to a vertex outside [0, nv)
-};
 enum { RA_FLAG_NO_PRETEST = 1, RA_FLAG_STATS = 2 };
 
 struct RaLayout {
@@ -37,7 +33,7 @@ struct RaLayout {
 };
 
 static bool ra_shape(long long views, long long H, long long W) {
-    return views >= 1 && views <= RA_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX && views * H * W <= RA_MAX_PIXELS;
+    return views >= 1 && views <= MVSDF_RA_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX && views * H * W <= RA_MAX_PIXELS;
 }
 
 static bool ra_layout(long long nv, long long nf, long long views, long long H, long long W, RaLayout* L) {
@@ -83,7 +79,7 @@ __device__ __forceinline__ bool ra_setup(const float* __restrict__ verts, const 
                                          const double* __restrict__ P, double o, int H, int W, RaFace& g, unsigned long long* hdr) {
     const int a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        atomicOr(hdr, (unsigned long long)RA_ERR_INDEX);
+        atomicOr(hdr + MVSDF_RA_H_ERR, (unsigned long long)MVSDF_RA_ERR_INDEX);
         return false;
     }
     if (!ra_project(P, verts + (long long)a * 3, g.ax, g.ay, g.az)) return false;
@@ -134,14 +130,14 @@ __device__ __forceinline__ void ra_pixel(const RaFace& g, int x, int y, double o
 }
 
 __device__ __forceinline__ void ra_stats(unsigned long long* hdr, unsigned n_atomic, unsigned n_covered) {
-    if (n_atomic) atomicAdd(hdr + 2, (unsigned long long)n_atomic);
-    if (n_covered) atomicAdd(hdr + 3, (unsigned long long)n_covered);
+    if (n_atomic) atomicAdd(hdr + MVSDF_RA_H_ATOMICS, (unsigned long long)n_atomic);
+    if (n_covered) atomicAdd(hdr + MVSDF_RA_H_COVERED, (unsigned long long)n_covered);
 }
 
 __global__ __launch_bounds__(RA_THREADS) void k_ra_check_cams(const double* __restrict__ P, long long n, unsigned long long* hdr) {
     bool bad = false;
     for (long long i = threadIdx.x; i < n; i += RA_THREADS) bad = bad || !isfinite(P[i]);
-    if (bad) atomicOr(hdr, (unsigned long long)RA_ERR_FINITE);
+    if (bad) atomicOr(hdr + MVSDF_RA_H_ERR, (unsigned long long)MVSDF_RA_ERR_FINITE);
 }
 
 // the small path.  blockIdx.y = view; flags[view * nf + f] = 1 where the face is left to the large path
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_draw_large(const float* __res
                                                                unsigned long long* __restrict__ keys, const int* __restrict__ list,
                                                                unsigned long long* hdr) {
     const int lane = threadIdx.x & 63;
-    const long long n = (long long)hdr[1], stride = (long long)gridDim.x * RA_WAVES;
+    const long long n = (long long)hdr[MVSDF_RA_H_ITEMS], stride = (long long)gridDim.x * RA_WAVES;
     unsigned na = 0, nc = 0;
     for (long long e = (long long)blockIdx.x * RA_WAVES + (threadIdx.x >> 6); e < n; e += stride) {
         const long long item = list[e];
@@ -305,7 +301,7 @@ static void ra_launch_draw(const float* verts, const int32_t* faces, long long n
     long long* bsum = (long long*)(w + L.bsum);
     hipLaunchKernelGGL((k_ra_draw_small<PRE, STATS>), dim3(mv_grid(nf, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, faces, nv,
                        nf, P, o, H, W, large, keys, flags, hdr);
-    mv_scan_blocks((const unsigned char*)flags, L.items, bsum, L.nb, (long long*)(hdr + 1), s);
+    mv_scan_blocks((const unsigned char*)flags, L.items, bsum, L.nb, (long long*)(hdr + MVSDF_RA_H_ITEMS), s);
     hipLaunchKernelGGL(k_ra_emit, dim3((unsigned)L.nb), dim3(MV_THREADS), 0, s, (const unsigned char*)flags, L.items, (const long long*)bsum, list);
     const long long waves = mv_ceil_div(L.items, RA_WAVES);
     hipLaunchKernelGGL((k_ra_draw_large<PRE, STATS>), dim3((unsigned)(waves < RA_LARGE_BLOCKS ? waves : RA_LARGE_BLOCKS)), dim3(RA_THREADS), 0, s, verts,

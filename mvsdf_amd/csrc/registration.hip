@@ -18,10 +18,13 @@
 // Every device loop is bounded; no kernel waits on another.
 #include "nn_tree.h"
 
-#define RG_MAX_POLY 4096
 #define RG_MAX_EDGES 4097
 #define RG_SUMS 16                                    // fp64 sums of an ICP iteration (the 17th quantity is the int64 pair count)
 #define RG_VOXEL_BITS 21
+static_assert(MVSDF_REG_TREE_H_ERR < MVSDF_REG_TREE_H_CENTRE && MVSDF_REG_ICP_H_ERR - MVSDF_REG_ICP_H_SUMS == RG_SUMS, "the header words as the kernels write them");
+static_assert(MVSDF_REG_TREE_H_WORDS * 8 <= CH_HDR && MVSDF_REG_ICP_H_WORDS * 8 <= CH_HDR && MVSDF_REG_VOXEL_H_WORDS * 8 <= CH_HDR &&
+                  MVSDF_ROWS_H_WORDS * 8 <= CH_HDR,
+              "the result words fit the header");
 
 struct RgXform {
     double m[12];
@@ -63,7 +66,7 @@ static bool rg_tree_layout(long long nr, RgTreeLayout* L) {
 // the centre of the root box, as three fp64 words behind the error word of the header
 static __global__ __launch_bounds__(64) void k_rg_centre(const double* __restrict__ root, double* __restrict__ hdr) {
     const int a = threadIdx.x;
-    if (a < 3) hdr[1 + a] = (root[a] + root[3 + a]) * 0.5;
+    if (a < 3) hdr[MVSDF_REG_TREE_H_CENTRE + a] = (root[a] + root[3 + a]) * 0.5;
 }
 
 // the leaf's candidates against (best, bi), bi = the sorted position of the best one: a smaller d2 wins without a look at the permutation; an equal
@@ -93,7 +96,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_query(const double* __
     rg_apply(X, Q + qi * 3, p);
     const double x = p[0], y = p[1], z = p[2];
     if (!ch_finite3(p)) {
-        atomicOr(err, CH_ERR_FINITE);
+        atomicOr(err, MVSDF_PC_ERR_FINITE);
         if (dist) dist[qi] = INFINITY;
         if (d2out) d2out[qi] = INFINITY;
         if (index) index[qi] = -1;
@@ -108,7 +111,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_query(const double* __
     if (ch_box_lb2(box + first * 6, x, y, z) <= cut2 * CH_MARGIN2) rg_leaf_min(sp, perm, T.n, first, x, y, z, best, bi);
     if (!ch_walk(
             box, T, x, y, z, [&] { return fmin(best, cut2) * CH_MARGIN2; }, [&](long long l) { rg_leaf_min(sp, perm, T.n, l, x, y, z, best, bi); }))
-        atomicOr(err, CH_ERR_WALK);
+        atomicOr(err, MVSDF_PC_ERR_WALK);
     const double d = sqrt(best);
     const bool hit = d < max_dist && bi >= 0;                     // (a finite best always has its position)
     if (dist) dist[qi] = hit ? d : INFINITY;
@@ -170,7 +173,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_sum_part(const double*
     if (t == 0) pcnt[blockIdx.x] = sc[0];
 }
 
-// hdr[0] = the count, hdr[1 + a] = sum a as its bits
+// the count and the sums (as their bits) of MVSDF_REG_ICP_H_*
 static __global__ __launch_bounds__(CH_TOP_THREADS) void k_rg_sum_final(const double* __restrict__ psum, const long long* __restrict__ pcnt, long long nb,
                                                                         long long* __restrict__ hdr) {
     __shared__ double ss[CH_TOP_THREADS];
@@ -186,7 +189,7 @@ static __global__ __launch_bounds__(CH_TOP_THREADS) void k_rg_sum_final(const do
         if (t < w) sc[t] += sc[t + w];
         __syncthreads();
     }
-    if (t == 0) hdr[0] = sc[0];
+    if (t == 0) hdr[MVSDF_REG_ICP_H_N] = sc[0];
     for (int a = 0; a < RG_SUMS; ++a) {
         double s = 0.0;
         for (long long q = lo; q < hi; ++q) s += psum[(long long)a * nb + q];
@@ -196,7 +199,7 @@ static __global__ __launch_bounds__(CH_TOP_THREADS) void k_rg_sum_final(const do
             if (t < w) ss[t] += ss[t + w];
             __syncthreads();
         }
-        if (t == 0) hdr[1 + a] = __double_as_longlong(ss[0]);
+        if (t == 0) hdr[MVSDF_REG_ICP_H_SUMS + a] = __double_as_longlong(ss[0]);
         __syncthreads();
     }
 }
@@ -265,7 +268,7 @@ static bool rg_crop_layout(long long n, RgCropLayout* L) {
 }
 
 // ================================================================ the voxel filter ================================================================
-// key = gx | gy << 21 | gz << 42 with g = floor((p - (min - voxel / 2)) / voxel); a g outside [0, 2^21) raises CH_ERR_COORD (CH_ERR_FINITE for a
+// key = gx | gy << 21 | gz << 42 with g = floor((p - (min - voxel / 2)) / voxel); a g outside [0, 2^21) raises MVSDF_PC_ERR_COORD (MVSDF_PC_ERR_FINITE for a
 // non-finite point) and counts as 0
 static __global__ __launch_bounds__(CH_THREADS) void k_rg_voxel_key(const double* __restrict__ P, long long n, const double* __restrict__ frame, double voxel,
                                                                     unsigned long long* __restrict__ key, int* __restrict__ val, int* err) {
@@ -278,7 +281,7 @@ static __global__ __launch_bounds__(CH_THREADS) void k_rg_voxel_key(const double
         const double o = frame[a] - voxel / 2;
         const double g = floor((p - o) / voxel);
         if (!(g >= 0.0 && g < (double)(1 << RG_VOXEL_BITS))) {
-            bad |= isfinite(p) ? CH_ERR_COORD : CH_ERR_FINITE;
+            bad |= isfinite(p) ? MVSDF_PC_ERR_COORD : MVSDF_PC_ERR_FINITE;
             continue;
         }
         k |= (unsigned long long)g << (RG_VOXEL_BITS * a);
@@ -372,19 +375,19 @@ int mvsdf_reg_tree_build(const double* refs, int64_t nr, void* ws, size_t ws_byt
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
     int* fl = (int*)(w + L.flags);
-    long long hdr[4] = {0, 0, 0, 0};                              // error bits, the box centre (fp64 bits)
+    long long hdr[MVSDF_REG_TREE_H_WORDS] = {};
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_reg_tree_build"))) return rc;
     const ChBuilt tree = ch_tree_begin(refs, (long long)nr, w, L.t, fl, s, "mvsdf_reg_tree_build");
     if (tree.rc) return tree.rc;
     if (tree.err) {
-        hdr[0] = tree.err;
-        return mv_write_header(ws, hdr, 4, s, "mvsdf_reg_tree_build");
+        hdr[MVSDF_REG_TREE_H_ERR] = tree.err;
+        return mv_write_header(ws, hdr, MVSDF_REG_TREE_H_WORDS, s, "mvsdf_reg_tree_build");
     }
     const ChTree& T = L.t.T;
     hipLaunchKernelGGL(k_rg_centre, dim3(1), dim3(64), 0, s, (const double*)(w + L.t.box) + T.off[T.top] * 6, (double*)w);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_reg_tree_build"))) return rc;
-    return mv_write_header(ws, hdr, 1, s, "mvsdf_reg_tree_build");
+    return mv_write_header(ws, hdr, MVSDF_REG_TREE_H_CENTRE, s, "mvsdf_reg_tree_build");   // the words in front of the centre the kernel wrote
 }
 
 int mvsdf_reg_tree_query(const void* tree, size_t tree_bytes, int64_t nr, const double* queries, int64_t nq, const double* transform, double max_dist,
@@ -413,10 +416,10 @@ int mvsdf_reg_icp_step(const void* tree, size_t tree_bytes, int64_t nr, const do
     if (ws_bytes < P.total) return mv_fail(-1, "mvsdf_reg_icp_step: workspace too small (mvsdf_reg_pairs_workspace_bytes)");
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
-    long long* hdr = (long long*)w;                               // the count, the 16 sums, the error bits
+    long long* hdr = (long long*)w;
     int rc;
     if ((rc = mv_check(hipMemsetAsync(w, 0, CH_HDR, s), "mvsdf_reg_icp_step"))) return rc;
-    rg_launch_query((const char*)tree, L, src, (long long)ns, transform, max_dist, nullptr, d2, index, (int*)(hdr + 1 + RG_SUMS), s);
+    rg_launch_query((const char*)tree, L, src, (long long)ns, transform, max_dist, nullptr, d2, index, (int*)(hdr + MVSDF_REG_ICP_H_ERR), s);
     hipLaunchKernelGGL(k_rg_sum_part, dim3((unsigned)P.nb), dim3(CH_THREADS), 0, s, src, (long long)ns, rg_xform(transform), refs, (const double*)d2,
                        (const int*)index, (const double*)tree + 1, (double*)(w + P.psum), (long long*)(w + P.pcnt), P.nb);
     hipLaunchKernelGGL(k_rg_sum_final, dim3(1), dim3(CH_TOP_THREADS), 0, s, (const double*)(w + P.psum), (const long long*)(w + P.pcnt), P.nb, hdr);
@@ -439,7 +442,7 @@ size_t mvsdf_reg_crop_workspace_bytes(int64_t n) {
 int mvsdf_reg_crop(const double* pts, int64_t n, int32_t axis, double axis_min, double axis_max, const double* polygon, int32_t nverts, void* ws,
                    size_t ws_bytes, uint8_t* keep, double* out, void* stream) {
     RgCropLayout L;
-    if (!pts || !polygon || !ws || !keep || !out || !rg_crop_layout(n, &L) || axis < 0 || axis > 2 || nverts < 3 || nverts > RG_MAX_POLY)
+    if (!pts || !polygon || !ws || !keep || !out || !rg_crop_layout(n, &L) || axis < 0 || axis > 2 || nverts < 3 || nverts > MVSDF_REG_MAX_POLYGON)
         return mv_fail(-1, "mvsdf_reg_crop: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_reg_crop: workspace too small (mvsdf_reg_crop_workspace_bytes)");
     static const int UV[3][2] = {{1, 2}, {0, 2}, {0, 1}};
@@ -452,7 +455,7 @@ int mvsdf_reg_crop(const double* pts, int64_t n, int32_t axis, double axis_min, 
     mv_scan((const unsigned char*)keep, (long long)n, off, w + L.tmp, (long long*)(w + L.tot), s);
     hipLaunchKernelGGL(k_rg_scatter, dim3(g), dim3(CH_THREADS), 0, s, pts, (long long)n, (const unsigned char*)keep, (const long long*)off, out);
     if (int rc = mv_check(hipGetLastError(), "mvsdf_reg_crop")) return rc;
-    return mv_check(hipMemcpyAsync(ws, w + L.tot, 8, hipMemcpyDeviceToDevice, s), "mvsdf_reg_crop");
+    return mv_check(hipMemcpyAsync(ws, w + L.tot, MVSDF_ROWS_H_WORDS * 8, hipMemcpyDeviceToDevice, s), "mvsdf_reg_crop");
 }
 
 size_t mvsdf_reg_voxel_workspace_bytes(int64_t n) {
@@ -466,7 +469,7 @@ int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_reg_voxel: workspace too small (mvsdf_reg_voxel_workspace_bytes)");
     char* w = (char*)ws;
     hipStream_t s = (hipStream_t)stream;
-    long long* fl = (long long*)(w + L.flags);                    // [0]: the voxels (the scan's total), [1]: error bits (int)
+    long long* fl = (long long*)(w + L.flags);                    // MVSDF_REG_VOXEL_H_*: the voxels (the scan's total), the error bits (int)
     unsigned long long* k[2] = {(unsigned long long*)(w + L.t.k0), (unsigned long long*)(w + L.t.k1)};
     int* v[2] = {(int*)(w + L.t.v0), (int*)(w + L.t.v1)};
     unsigned char* head = (unsigned char*)(w + L.head);
@@ -474,15 +477,15 @@ int mvsdf_reg_voxel(const double* pts, int64_t n, double voxel, void* ws, size_t
     const unsigned g = mv_grid(n, CH_THREADS);
     int rc;
     if ((rc = mv_check(hipMemsetAsync(fl, 0, 4 * 8, s), "mvsdf_reg_voxel"))) return rc;
-    ch_tree_frame(pts, (long long)n, w, L.t, (int*)(fl + 1), s);
-    hipLaunchKernelGGL(k_rg_voxel_key, dim3(g), dim3(CH_THREADS), 0, s, pts, (long long)n, (const double*)(w + L.t.frame), voxel, k[0], v[0], (int*)(fl + 1));
+    ch_tree_frame(pts, (long long)n, w, L.t, (int*)(fl + MVSDF_REG_VOXEL_H_ERR), s);
+    hipLaunchKernelGGL(k_rg_voxel_key, dim3(g), dim3(CH_THREADS), 0, s, pts, (long long)n, (const double*)(w + L.t.frame), voxel, k[0], v[0], (int*)(fl + MVSDF_REG_VOXEL_H_ERR));
     const int cur = ch_radix_sort(k, v, (long long)n, 3 * RG_VOXEL_BITS, w, L.t.rs, s);
     hipLaunchKernelGGL(k_rg_heads, dim3(g), dim3(CH_THREADS), 0, s, (const unsigned long long*)k[cur], (long long)n, head);
-    mv_scan((const unsigned char*)head, (long long)n, off, w + L.tmp2, fl, s);
+    mv_scan((const unsigned char*)head, (long long)n, off, w + L.tmp2, fl + MVSDF_REG_VOXEL_H_VOXELS, s);
     hipLaunchKernelGGL(k_rg_voxel_mean, dim3(g), dim3(CH_THREADS), 0, s, pts, (const unsigned long long*)k[cur], (const int*)v[cur], (const unsigned char*)head,
                        (const long long*)off, (long long)n, means, counts);
     if ((rc = mv_check(hipGetLastError(), "mvsdf_reg_voxel"))) return rc;
-    return mv_check(hipMemcpyAsync(ws, fl, 2 * 8, hipMemcpyDeviceToDevice, s), "mvsdf_reg_voxel");
+    return mv_check(hipMemcpyAsync(ws, fl, MVSDF_REG_VOXEL_H_WORDS * 8, hipMemcpyDeviceToDevice, s), "mvsdf_reg_voxel");
 }
 
 int mvsdf_reg_hist(const double* dist, int64_t n, const double* edges, int32_t nedges, double tau, int64_t* out, void* stream) {

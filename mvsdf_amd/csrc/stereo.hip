@@ -28,22 +28,10 @@
 #define PS_THREADS 256
 #define PS_TILE 16
 #define PS_KCHUNK 32
-#define PS_HDR 256                                    // bytes at the start of the workspace: int64 {0, error bits}
-#define PS_MAX_D 65535
-#define PS_MAX_SRC 255                                // n_k travels as a byte
-#define PS_MAX_ELEMS (1ll << 40)
+#define PS_HDR 256                                    // bytes at the start of the workspace: MVSDF_RES_H_*
+static_assert(MVSDF_RES_H_WORDS * 8 <= PS_HDR, "the result words fit the header");
+#define PS_MAX_ELEMS (1ll << MVSDF_PS_MAX_ELEMS_LOG2)
 
-enum {
-    PS_ERR_FINITE = 1,      // a non-finite feature, matrix entry, depth_min or interval
-    PS_ERR_PAIR = 2,        // a pair or view index outside [0, V)
-    PS_ERR_DEPTHS = 4,      // D < 1 (or beyond PS_MAX_D)
-    PS_ERR_SHAPE = 8,       // V < 1, R or S < 2, C < 1, a pair list longer than PS_MAX_SRC, sizes beyond the limits
-    PS_ERR_SGM = 16,        // the regularisation's p1, p2, paths, or D > SG_MAX_D
-    PS_ERR_BAND = 32,       // the band's number of hypotheses outside [1, PB_MAX_D], a step that is not finite and positive, a view listed twice
-    PS_ERR_CENTRE = 64,     // an infinite centre (found on the device)
-};
-
-#define SG_MAX_D 4096                                 // stereo.py: MAX_D_SGM
 #define SG_MAX_ITEMS 2048                             // G * D at most this where G > 1: the two LDS buffers then take 32 KB
 #define SG_MAX_G 8
 
@@ -52,7 +40,7 @@ struct PsLayout {
 };
 
 static bool ps_layout(long long R, long long S, long long D, long long npairs, PsLayout* L) {
-    if (R < 2 || S < 2 || D < 1 || D > PS_MAX_D || npairs < 0 || npairs > INT_MAX || R > INT_MAX || S > INT_MAX || R * S > INT_MAX) return false;
+    if (R < 2 || S < 2 || D < 1 || D > MVSDF_PS_MAX_D || npairs < 0 || npairs > INT_MAX || R > INT_MAX || S > INT_MAX || R * S > INT_MAX) return false;
     if (R * S * D > PS_MAX_ELEMS) return false;
     WsCursor c{PS_HDR};
     L->mats = c.take((size_t)(npairs > 0 ? npairs : 1) * 16 * 8);
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_normalize(const float* __rest
     }
     const double nrm = sqrt(s);
     for (int c = 0; c < C; ++c) o[c] = nrm > 0.0 ? (float)((double)p[c] / nrm) : 0.0f;
-    if (bad) atomicOr((unsigned long long*)(hdr + 1), (unsigned long long)PS_ERR_FINITE);
+    if (bad) atomicOr((unsigned long long*)(hdr + MVSDF_RES_H_ERR), (unsigned long long)MVSDF_PS_ERR_FINITE);
 }
 
 // grey = (299 R + 587 G + 114 B) / 1000; the (2 rad + 1)^2 patch around the pixel, border clamped, rows then columns, minus its mean
@@ -290,10 +278,9 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_upsample(const float* __restr
 // k_ps_band: a 256-lane workgroup owns an 8 x 8 tile of reference pixels of one view (blockIdx.z: the slot in the view list) and the whole band of Db
 // hypotheses around every pixel's centre.  Lane l of every wave owns pixel l of the tile; wave w scores the hypotheses w, w + 4, ... with ps_sample
 // (the four waves walk neighbouring depths at the same time, so their gathers meet in L1) into the tile's LDS image: score[k][pixel] fp64 and
-// n_k[k][pixel] as bytes, 9 * 64 * Db bytes, 36 KB at PB_MAX_D, conflict-free (consecutive lanes, consecutive words).  After the one barrier wave 0
+// n_k[k][pixel] as bytes, 9 * 64 * Db bytes, 36 KB at MVSDF_PS_MAX_D_BAND, conflict-free (consecutive lanes, consecutive words).  After the one barrier wave 0
 // picks from LDS (ps_pick) and writes the pixel's outputs: no score leaves the CU, every output element has one writer, no atomics but the error bit.
 #define PB_TILE 8
-#define PB_MAX_D 64                                   // stereo.py: MAX_D_BAND
 
 template <int CFIX>
 __global__ __launch_bounds__(PS_THREADS) void k_ps_band(const float* __restrict__ desc, int R, int S, int C, const int* __restrict__ views,
@@ -332,7 +319,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_band(const float* __restrict_
     }
     __syncthreads();
     if (w) return;
-    if (__ballot(inside && isinf(c)) && l == 0) atomicOr(errword, (unsigned long long)PS_ERR_CENTRE);
+    if (__ballot(inside && isinf(c)) && l == 0) atomicOr(errword, (unsigned long long)MVSDF_PS_ERR_CENTRE);
     if (!inside) return;
     const PsPick o = ps_pick<false>(pb_score + l, pb_score + l, pb_cnt + l, 64, Db, nsrc);
     const long long at = (long long)r * hw + pix;
@@ -444,12 +431,12 @@ __global__ __launch_bounds__(PS_THREADS) void k_sg_path(const double* __restrict
         cur ^= 1;
     }
 #undef SG_FETCH
-    if (__ballot(bad) && (t & 63) == 0) atomicOr(errword, (unsigned long long)PS_ERR_FINITE);
+    if (__ballot(bad) && (t & 63) == 0) atomicOr(errword, (unsigned long long)MVSDF_PS_ERR_FINITE);
 }
 
 // ---- host side of the regularisation ----
 static bool sg_limits(long long R, long long S, long long D) {
-    return R >= 1 && S >= 1 && D >= 1 && D <= SG_MAX_D && R <= INT_MAX && S <= INT_MAX && R * S <= INT_MAX && R * S * D <= PS_MAX_ELEMS;
+    return R >= 1 && S >= 1 && D >= 1 && D <= MVSDF_PS_MAX_D_SGM && R <= INT_MAX && S <= INT_MAX && R * S <= INT_MAX && R * S * D <= PS_MAX_ELEMS;
 }
 
 static bool sg_args(double p1, double p2, int paths) { return isfinite(p1) && isfinite(p2) && p1 >= 0.0 && p1 <= p2 && (paths == 4 || paths == 8); }
@@ -525,32 +512,29 @@ static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths,
     hipStream_t s = (hipStream_t)stream;
     // ---- validation, all of it before the first launch ----
     long long err = 0, npairs = 0, dmax = 1;
-    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > INT_MAX || pair_off[0] != 0) err |= PS_ERR_SHAPE;
+    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > INT_MAX || pair_off[0] != 0) err |= MVSDF_PS_ERR_SHAPE;
     else {
         for (long long i = 0; i < nviews; ++i) {
             const long long len = (long long)pair_off[i + 1] - pair_off[i];
-            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
-            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
-            if (nhyp[i] < 1 || nhyp[i] > PS_MAX_D) err |= PS_ERR_DEPTHS;
+            if (len < 0 || len > MVSDF_PS_MAX_SRC) err |= MVSDF_PS_ERR_SHAPE;
+            if (views[i] < 0 || views[i] >= V) err |= MVSDF_PS_ERR_PAIR;
+            if (nhyp[i] < 1 || nhyp[i] > MVSDF_PS_MAX_D) err |= MVSDF_PS_ERR_DEPTHS;
             else if (nhyp[i] > dmax) dmax = nhyp[i];
-            if (!isfinite(ranges[2 * i]) || !isfinite(ranges[2 * i + 1])) err |= PS_ERR_FINITE;
+            if (!isfinite(ranges[2 * i]) || !isfinite(ranges[2 * i + 1])) err |= MVSDF_PS_ERR_FINITE;
         }
         npairs = pair_off[nviews];
     }
     PsLayout L;
-    if (!(err & PS_ERR_SHAPE) && (!ps_layout(R, S, dmax, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
-        err |= PS_ERR_SHAPE;
-    if (sgm && (!sg_args(p1, p2, paths) || dmax > SG_MAX_D)) err |= PS_ERR_SGM;
-    if (!(err & PS_ERR_SHAPE)) {
+    if (!(err & MVSDF_PS_ERR_SHAPE) && (!ps_layout(R, S, dmax, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
+        err |= MVSDF_PS_ERR_SHAPE;
+    if (sgm && (!sg_args(p1, p2, paths) || dmax > MVSDF_PS_MAX_D_SGM)) err |= MVSDF_PS_ERR_SGM;
+    if (!(err & MVSDF_PS_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
-            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_PS_ERR_PAIR;
         for (long long k = 0; k < npairs * 16; ++k)
-            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
+            if (!isfinite(mats[k])) err |= MVSDF_PS_ERR_FINITE;
     }
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total + (sgm ? mv_align256((size_t)(R * S * dmax) * 8) : 0))
         return mv_fail(-1, "mvsdf_stereo_sweep: workspace too small (mvsdf_stereo_workspace_bytes / mvsdf_stereo_sweep_sgm_workspace_bytes)");
     // ---- uploads and launches ----
@@ -564,7 +548,7 @@ static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths,
     const long long hw = R * S, total = V * hw * C;
     long long fb = mv_ceil_div(total, MV_THREADS);
     if (fb > 2048) fb = 2048;
-    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + MVSDF_RES_H_ERR, (unsigned long long)MVSDF_PS_ERR_FINITE);
     const bool fast = C == 32 && ((uintptr_t)desc & 15) == 0;                 // 128-byte texels read as float4
     double* vol = (double*)(w + L.vol);
     unsigned char* cnt = (unsigned char*)(w + L.cnt);
@@ -582,7 +566,7 @@ static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths,
             hipLaunchKernelGGL(k_ps_score<0>, grid, dim3(PS_THREADS), 0, s, desc, (int)R, (int)S, (int)C, r, nsrc, src, T, ranges[2 * i], ranges[2 * i + 1], D,
                                vol, cnt);
         if (sgm) {
-            if ((rc = sg_run(vol, reg, R, S, D, p1, p2, paths, (unsigned long long*)ws + 1, s))) return rc;
+            if ((rc = sg_run(vol, reg, R, S, D, p1, p2, paths, (unsigned long long*)ws + MVSDF_RES_H_ERR, s))) return rc;
             hipLaunchKernelGGL(k_ps_pick<true>, dim3(mv_grid(hw, PS_THREADS)), dim3(PS_THREADS), 0, s, (const double*)reg, (const double*)vol,
                                (const unsigned char*)cnt, (int)hw, D, ranges[2 * i], ranges[2 * i + 1], nsrc, depths + (long long)r * hw,
                                probs + (long long)r * 3 * hw, best_k + (long long)r * hw, counts + (long long)r * hw);
@@ -602,7 +586,7 @@ struct PbLayout {
 
 // header, per view its index, first pair slot and step, matrices and source indices: nothing that grows with the band, R or S
 static bool pb_layout(long long R, long long S, long long Db, long long nviews, long long npairs, PbLayout* L) {
-    if (R < 2 || S < 2 || R > INT_MAX || S > INT_MAX || R * S > INT_MAX || Db < 1 || Db > PB_MAX_D || nviews < 0 || nviews > 65535 || npairs < 0 ||
+    if (R < 2 || S < 2 || R > INT_MAX || S > INT_MAX || R * S > INT_MAX || Db < 1 || Db > MVSDF_PS_MAX_D_BAND || nviews < 0 || nviews > 65535 || npairs < 0 ||
         npairs > INT_MAX)
         return false;
     WsCursor c{PS_HDR};
@@ -633,7 +617,7 @@ int mvsdf_stereo_normalize(const float* feats, int64_t n, int64_t C, float* out,
     if (!feats || !out || !hdr || n < 1 || C < 1 || C > INT_MAX || n > PS_MAX_ELEMS / C || mv_ceil_div(n, PS_THREADS) > INT_MAX)
         return mv_fail(-1, "mvsdf_stereo_normalize: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = mv_check(hipMemsetAsync(hdr, 0, 16, s), what)) return rc;
+    if (int rc = mv_check(hipMemsetAsync(hdr, 0, MVSDF_RES_H_WORDS * 8, s), what)) return rc;
     hipLaunchKernelGGL(k_ps_normalize, dim3(mv_grid(n, PS_THREADS)), dim3(PS_THREADS), 0, s, feats, (long long)n, (int)C, out, (long long*)hdr);
     return mv_check(hipGetLastError(), what);
 }
@@ -661,21 +645,18 @@ int mvsdf_stereo_regularize(const double* score, int64_t R, int64_t S, int64_t D
     const char* what = "mvsdf_stereo_regularize";
     if (!score || !out || !ws || ws_bytes < PS_HDR) return mv_fail(-1, "mvsdf_stereo_regularize: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (!sg_limits(R, S, D) || !sg_args(p1, p2, paths)) {
-        const long long hdr[2] = {0, PS_ERR_SGM};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (!sg_limits(R, S, D) || !sg_args(p1, p2, paths)) return mv_refuse_header(ws, MVSDF_PS_ERR_SGM, s, what);
     const size_t bytes = (size_t)(R * S * D) * 8;
     if ((const char*)score < (const char*)out + bytes && (const char*)out < (const char*)score + bytes)
         return mv_fail(-1, "mvsdf_stereo_regularize: out overlaps score");
     if (int rc = mv_check(hipMemsetAsync(ws, 0, PS_HDR, s), what)) return rc;
-    if (int rc = sg_run(score, out, R, S, D, p1, p2, paths, (unsigned long long*)ws + 1, s)) return rc;
+    if (int rc = sg_run(score, out, R, S, D, p1, p2, paths, (unsigned long long*)ws + MVSDF_RES_H_ERR, s)) return rc;
     return mv_check(hipGetLastError(), what);
 }
 
 size_t mvsdf_stereo_sweep_sgm_workspace_bytes(int64_t R, int64_t S, int64_t D, int64_t npairs) {
     PsLayout L;
-    return ps_layout(R, S, D, npairs, &L) && D <= SG_MAX_D ? L.total + mv_align256((size_t)(R * S * D) * 8) : 0;
+    return ps_layout(R, S, D, npairs, &L) && D <= MVSDF_PS_MAX_D_SGM ? L.total + mv_align256((size_t)(R * S * D) * 8) : 0;
 }
 
 int mvsdf_stereo_sweep_sgm(const float* desc, int64_t V, int64_t R, int64_t S, int64_t C, int64_t nviews, const int32_t* views,
@@ -709,33 +690,30 @@ int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_
     hipStream_t s = (hipStream_t)stream;
     // ---- validation, all of it before the first launch ----
     long long err = 0, npairs = 0;
-    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > 65535 || pair_off[0] != 0) err |= PS_ERR_SHAPE;
+    if (V < 1 || V > INT_MAX || R < 2 || S < 2 || C < 1 || C > INT_MAX || nviews > 65535 || pair_off[0] != 0) err |= MVSDF_PS_ERR_SHAPE;
     else {
         for (long long i = 0; i < nviews; ++i) {
             const long long len = (long long)pair_off[i + 1] - pair_off[i];
-            if (len < 0 || len > PS_MAX_SRC) err |= PS_ERR_SHAPE;
-            if (views[i] < 0 || views[i] >= V) err |= PS_ERR_PAIR;
+            if (len < 0 || len > MVSDF_PS_MAX_SRC) err |= MVSDF_PS_ERR_SHAPE;
+            if (views[i] < 0 || views[i] >= V) err |= MVSDF_PS_ERR_PAIR;
             for (long long j = 0; j < i; ++j)
-                if (views[j] == views[i]) err |= PS_ERR_BAND;                  // two workgroups would write the same maps
-            if (!(isfinite(steps[i]) && steps[i] > 0.0)) err |= PS_ERR_BAND;
+                if (views[j] == views[i]) err |= MVSDF_PS_ERR_BAND;                  // two workgroups would write the same maps
+            if (!(isfinite(steps[i]) && steps[i] > 0.0)) err |= MVSDF_PS_ERR_BAND;
         }
         npairs = pair_off[nviews];
     }
-    if (depth_num < 1 || depth_num > PB_MAX_D) err |= PS_ERR_BAND;
+    if (depth_num < 1 || depth_num > MVSDF_PS_MAX_D_BAND) err |= MVSDF_PS_ERR_BAND;
     PbLayout L;
-    if (!(err & (PS_ERR_SHAPE | PS_ERR_BAND)) &&
+    if (!(err & (MVSDF_PS_ERR_SHAPE | MVSDF_PS_ERR_BAND)) &&
         (!pb_layout(R, S, depth_num, nviews, npairs, &L) || (npairs > 0 && !pair_src) || R * S > PS_MAX_ELEMS / C || V > PS_MAX_ELEMS / (R * S * C)))
-        err |= PS_ERR_SHAPE;
-    if (!(err & PS_ERR_SHAPE)) {
+        err |= MVSDF_PS_ERR_SHAPE;
+    if (!(err & MVSDF_PS_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
-            if (pair_src[k] < 0 || pair_src[k] >= V) err |= PS_ERR_PAIR;
+            if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_PS_ERR_PAIR;
         for (long long k = 0; k < npairs * 16; ++k)
-            if (!isfinite(mats[k])) err |= PS_ERR_FINITE;
+            if (!isfinite(mats[k])) err |= MVSDF_PS_ERR_FINITE;
     }
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_band: workspace too small (mvsdf_stereo_band_workspace_bytes)");
     const dim3 grid((unsigned)mv_ceil_div(S, PB_TILE), (unsigned)mv_ceil_div(R, PB_TILE), (unsigned)nviews);
     if (grid.y > 65535) return mv_fail(-1, "mvsdf_stereo_band: R beyond the grid limit");
@@ -753,16 +731,16 @@ int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_
     const long long total = V * R * S * C;
     long long fb = mv_ceil_div(total, MV_THREADS);
     if (fb > 2048) fb = 2048;
-    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + 1, (unsigned long long)PS_ERR_FINITE);
+    hipLaunchKernelGGL(k_any_nonfinite<float>, dim3((unsigned)fb), dim3(MV_THREADS), 0, s, desc, total, (unsigned long long*)ws + MVSDF_RES_H_ERR, (unsigned long long)MVSDF_PS_ERR_FINITE);
     const size_t lds = (size_t)depth_num * 64 * 9;
     if (C == 32 && ((uintptr_t)desc & 15) == 0)                               // 128-byte texels read as float4
         hipLaunchKernelGGL(k_ps_band<32>, grid, dim3(PS_THREADS), lds, s, desc, (int)R, (int)S, (int)C, (const int*)(w + L.views), (const int*)(w + L.off),
                            (const double*)(w + L.steps), (const int*)(w + L.src),
-                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + 1);
+                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + MVSDF_RES_H_ERR);
     else
         hipLaunchKernelGGL(k_ps_band<0>, grid, dim3(PS_THREADS), lds, s, desc, (int)R, (int)S, (int)C, (const int*)(w + L.views), (const int*)(w + L.off),
                            (const double*)(w + L.steps), (const int*)(w + L.src),
-                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + 1);
+                           (const double*)(w + L.mats), centres, (int)depth_num, depths, probs, best_k, counts, (unsigned long long*)ws + MVSDF_RES_H_ERR);
     return mv_check(hipGetLastError(), what);                   // no wait here: the caller keeps the host arrays until it has read the header
 }
 

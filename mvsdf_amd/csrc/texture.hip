@@ -19,20 +19,14 @@
 #include "geom_prims.h"
 
 #define TX_THREADS 256
-#define TX_HDR 256                                    // bytes at the start of the workspace: int64 {error bits, counts[7] (classify) / flagged total (pack)}
+#define TX_HDR 256                                    // bytes at the start of the workspace: MVSDF_TX_H_*
 #define TX_CLASSES 7
+static_assert(MVSDF_TX_H_WORDS * 8 <= TX_HDR && MVSDF_TX_H_COUNTS + TX_CLASSES == MVSDF_TX_H_WORDS, "the result words fit the header");
 #define TX_NMIN 4
-#define TX_MAX_SIDE 32768                             // texels: block coordinates fit 13 bits, block indices 26
-#define TX_MAX_FACES (1ll << 28)
-#define TX_MAX_VIEWS 65535
+#define TX_MAX_FACES (1ll << MVSDF_TX_MAX_FACES_LOG2)
 #define TX_INSET 0.75                                 // the right-angle corner's distance from the cell's edges, in texels
 #define TX_LEG_LOSS 3.5                               // leg = n - TX_LEG_LOSS
 
-enum {
-    TX_ERR_FINITE = 1,      // a camera entry is NaN or infinite
-    TX_ERR_INDEX = 2,       // a face refers to a vertex outside [0, nv)
-    TX_ERR_COUNTS = 4,      // the class counts passed to the pack do not describe the classes
-};
 enum { TX_FLAG_RECOMPUTE = 1 };
 
 // where the classes lie, by value to the kernels.  Class k holds the patches of edge TX_NMIN << k; the classes follow each other in DESCENDING order
@@ -45,7 +39,7 @@ struct TxLayout {
     int Wt, Ht;
 };
 
-// false: counts that are negative, do not sum to nf, or an atlas beyond TX_MAX_SIDE
+// false: counts that are negative, do not sum to nf, or an atlas beyond MVSDF_TX_MAX_SIDE
 static bool tx_layout(const int64_t* counts, long long nf, TxLayout* L) {
     long long sum = 0, at = 0, blocks = 0;
     if (!counts || nf < 0 || nf > TX_MAX_FACES) return false;
@@ -65,7 +59,7 @@ static bool tx_layout(const int64_t* counts, long long nf, TxLayout* L) {
     int B = 0;
     while (B < 62 && (1ll << B) < blocks) ++B;
     const long long Wt = (long long)TX_NMIN << ((B + 1) / 2), Ht = (long long)TX_NMIN << (B / 2);
-    if (Wt > TX_MAX_SIDE) return false;
+    if (Wt > MVSDF_TX_MAX_SIDE) return false;
     L->Wt = (int)Wt;
     L->Ht = (int)Ht;
     return true;
@@ -88,7 +82,7 @@ static bool tx_ws(long long nf, TxWs* w) {
 }
 
 static bool tx_shape(long long views, long long H, long long W) {
-    return views >= 1 && views <= TX_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX;
+    return views >= 1 && views <= MVSDF_RA_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX;
 }
 
 static bool tx_center(double o) { return o == 0.5 || o == 0.0; }
@@ -130,7 +124,7 @@ __device__ __forceinline__ bool tx_in_image(double sx, double sy, double o, doub
 __global__ __launch_bounds__(TX_THREADS) void k_tx_check(const double* __restrict__ P, long long n, unsigned long long* hdr) {
     bool bad = false;
     for (long long i = threadIdx.x; i < n; i += TX_THREADS) bad = bad || !isfinite(P[i]);
-    if (bad) atomicOr(hdr, (unsigned long long)TX_ERR_FINITE);
+    if (bad) atomicOr(hdr + MVSDF_TX_H_ERR, (unsigned long long)MVSDF_TX_ERR_FINITE);
 }
 
 __global__ __launch_bounds__(TX_THREADS) void k_tx_face_views(const float* __restrict__ verts, const float* __restrict__ normals,
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_face_views(const float* __res
     int best = -1;
     double bs = 0.0, s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
-        atomicOr(hdr, (unsigned long long)TX_ERR_INDEX);
+        atomicOr(hdr + MVSDF_TX_H_ERR, (unsigned long long)MVSDF_TX_ERR_INDEX);
     } else {
         const float *Xa = verts + (long long)a * 3, *Xb = verts + (long long)b * 3, *Xc = verts + (long long)c * 3;
         const float *Na = normals + (long long)a * 3, *Nb = normals + (long long)b * 3, *Nc = normals + (long long)c * 3;
@@ -218,7 +212,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_classify(const int* __restric
         if (b && (threadIdx.x & 63) == 0) atomicAdd(&cnt[q], (unsigned)__popcll(b));
     }
     __syncthreads();
-    if (threadIdx.x < TX_CLASSES && cnt[threadIdx.x]) atomicAdd(hdr + 1 + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
+    if (threadIdx.x < TX_CLASSES && cnt[threadIdx.x]) atomicAdd(hdr + MVSDF_TX_H_COUNTS + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
 }
 
 // flags[r * nf + f] = the face is of class 6 - r
@@ -266,7 +260,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_tx_emit(const unsigned char* __r
         const int c = TX_CLASSES - 1 - (int)r;
         const long long rank = pos - L.start[c];
         if (rank < 0 || rank >= L.count[c]) {                     // the counts are not those of cls: nothing is written (start + count <= nf)
-            atomicOr(hdr, (unsigned long long)TX_ERR_COUNTS);
+            atomicOr(hdr + MVSDF_TX_H_ERR, (unsigned long long)MVSDF_TX_ERR_COUNTS);
             continue;
         }
         order[pos] = (int)f;
@@ -424,7 +418,7 @@ int mvsdf_texture_pack(const uint8_t* cls, int64_t nf, const int64_t* counts, vo
         unsigned char* flags = (unsigned char*)(b + w.flags);
         long long* bsum = (long long*)(b + w.bsum);
         hipLaunchKernelGGL(k_tx_flags, dim3(mv_grid(w.items, TX_THREADS)), dim3(TX_THREADS), 0, s, cls, (long long)nf, w.items, flags);
-        mv_scan_blocks((const unsigned char*)flags, w.items, bsum, w.nb, (long long*)ws + 1, s);
+        mv_scan_blocks((const unsigned char*)flags, w.items, bsum, w.nb, (long long*)ws + MVSDF_TX_H_COUNTS, s);   // the flagged total
         hipLaunchKernelGGL(k_tx_emit, dim3((unsigned)w.nb), dim3(MV_THREADS), 0, s, (const unsigned char*)flags, (long long)nf, w.items,
                            (const long long*)bsum, L, order, patch, uv, (unsigned long long*)ws);
     }

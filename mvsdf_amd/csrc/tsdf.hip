@@ -12,19 +12,13 @@
 // Every argument of the integration is validated on the host before anything is launched: an error leaves {0, error bits} in the header.
 #include "geom_prims.h"
 
-#define TS_HDR 256                                    // bytes at the start of the integration workspace: int64 {0, error bits}
+#define TS_HDR 256                                    // bytes at the start of the integration workspace: MVSDF_RES_H_*
+static_assert(MVSDF_RES_H_WORDS * 8 <= TS_HDR, "the result words fit the header");
 #define TS_BI 4                                       // the brick: TS_BI x TS_BJ x TS_BK lattice points, one per lane, k fastest
 #define TS_BJ 8
 #define TS_BK 8
 #define TS_THREADS (TS_BI * TS_BJ * TS_BK)
 static_assert(TS_BJ * TS_BK == 64, "a wave owns one j-k slab of the brick");
-
-enum {
-    TS_ERR_FINITE = 1,      // a non-finite matrix entry, origin, voxel, trunc, or a NaN jump
-    TS_ERR_VIEW = 2,        // a view index outside [0, V)
-    TS_ERR_RANGE = 4,       // voxel <= 0, trunc <= 0, jump < 0, min_views < 1
-    TS_ERR_SHAPE = 8,       // V < 1, H or W < 2, a dim below 2, no views, sizes beyond the limits
-};
 
 struct TsLayout {
     size_t mats, views, total;
@@ -108,20 +102,17 @@ int mvsdf_tsdf_integrate(const float* depths, int64_t V, int64_t H, int64_t W, c
     // ---- validation, all of it before the first launch ----
     long long err = 0;
     TsLayout L;
-    if (!ts_layout(V, H, W, nviews, dims, &L)) err |= TS_ERR_SHAPE;
-    if (!(err & TS_ERR_SHAPE)) {
+    if (!ts_layout(V, H, W, nviews, dims, &L)) err |= MVSDF_TS_ERR_SHAPE;
+    if (!(err & MVSDF_TS_ERR_SHAPE)) {
         for (long long q = 0; q < nviews; ++q)
-            if (views[q] < 0 || views[q] >= V) err |= TS_ERR_VIEW;
+            if (views[q] < 0 || views[q] >= V) err |= MVSDF_TS_ERR_VIEW;
         for (long long q = 0; q < nviews * 16; ++q)
-            if (!isfinite(mats[q])) err |= TS_ERR_FINITE;
+            if (!isfinite(mats[q])) err |= MVSDF_TS_ERR_FINITE;
     }
-    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2]) || !isfinite(voxel) || !isfinite(trunc) || isnan(jump)) err |= TS_ERR_FINITE;
-    if (!(err & TS_ERR_FINITE) && (!(voxel > 0.0) || !(trunc > 0.0) || !(jump >= 0.0))) err |= TS_ERR_RANGE;
-    if (min_views < 1) err |= TS_ERR_RANGE;
-    if (err) {
-        const long long hdr[2] = {0, err};
-        return mv_write_header(ws, hdr, 2, s, what);
-    }
+    if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2]) || !isfinite(voxel) || !isfinite(trunc) || isnan(jump)) err |= MVSDF_TS_ERR_FINITE;
+    if (!(err & MVSDF_TS_ERR_FINITE) && (!(voxel > 0.0) || !(trunc > 0.0) || !(jump >= 0.0))) err |= MVSDF_TS_ERR_RANGE;
+    if (min_views < 1) err |= MVSDF_TS_ERR_RANGE;
+    if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_tsdf_integrate: workspace too small (mvsdf_tsdf_workspace_bytes)");
     // ---- uploads and the launch ----
     char* w = (char*)ws;

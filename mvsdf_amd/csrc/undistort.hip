@@ -22,6 +22,7 @@
 
 #define UD_THREADS 256
 #define UD_HDR 256
+static_assert(MVSDF_RES_H_WORDS * 8 <= UD_HDR, "the result words fit the header");
 #define UD_MAX_UPDATES 32
 #define UD_STEP 1e-6                                  // the central differences' step, in normalised coordinates
 #define UD_STOP_PX 1e-13                              // a lane stops updating at a residual of at most this (pixels)
@@ -29,7 +30,6 @@
 #define UD_FISHEYE_EPS 1e-8
 
 enum { UD_PINHOLE = 0, UD_RADIAL = 1, UD_OPENCV = 2, UD_FISHEYE = 3 };
-enum { UD_ERR_FINITE = 1, UD_ERR_CONVERGE = 2 };
 enum { UD_U8 = 0, UD_F32 = 1 };
 
 struct UdCam {
@@ -94,19 +94,19 @@ __host__ __device__ static inline int ud_undistort(const UdCam& c, double xd, do
     for (int it = 0; it <= UD_MAX_UPDATES; ++it) {
         const UdXY f = ud_distort(c, x, y);
         const double ex = f.x - xd, ey = f.y - yd;
-        if (!ud_finite(ex) || !ud_finite(ey)) { err = UD_ERR_FINITE; break; }
+        if (!ud_finite(ex) || !ud_finite(ey)) { err = MVSDF_UD_ERR_FINITE; break; }
         const double rx = ud_abs(ex) * c.fx, ry = ud_abs(ey) * c.fy;
         res = rx > ry ? rx : ry;
         if (res <= UD_STOP_PX || it == UD_MAX_UPDATES) break;
         const UdXY a = ud_distort(c, x + h, y), b = ud_distort(c, x - h, y), p = ud_distort(c, x, y + h), q = ud_distort(c, x, y - h);
         const double j00 = (a.x - b.x) / h2, j01 = (p.x - q.x) / h2, j10 = (a.y - b.y) / h2, j11 = (p.y - q.y) / h2;
         const double det = j00 * j11 - j01 * j10;
-        if (!ud_finite(det) || det == 0.0) { err = UD_ERR_FINITE; break; }
+        if (!ud_finite(det) || det == 0.0) { err = MVSDF_UD_ERR_FINITE; break; }
         const double sx = (j11 * ex - j01 * ey) / det, sy = (j00 * ey - j10 * ex) / det;
         x = x - sx;
         y = y - sy;
     }
-    if (!err && res > UD_BOUND_PX) err = UD_ERR_CONVERGE;
+    if (!err && res > UD_BOUND_PX) err = MVSDF_UD_ERR_CONVERGE;
     o->x = x;
     o->y = y;
     return err;
@@ -124,7 +124,7 @@ __host__ __device__ static inline int ud_point(const UdCam& c, const UdPin& p, i
     const UdXY r = ud_distort(c, (X - p.cx) / p.fx, (Y - p.cy) / p.fy);
     o->x = c.fx * r.x + c.cx;
     o->y = c.fy * r.y + c.cy;
-    return ud_finite(o->x) && ud_finite(o->y) ? 0 : UD_ERR_FINITE;
+    return ud_finite(o->x) && ud_finite(o->y) ? 0 : MVSDF_UD_ERR_FINITE;
 }
 
 // where output pixel (x, y) of the pinhole p looks in the source image [H][W]: the first texel (y0 * W + x0, in pixels; -1 = invalid), the steps to
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(UD_THREADS) void k_undistort_points(const double* _
     const int err = ud_point(cam, pin, inverse, pts[2 * i], pts[2 * i + 1], &o);
     out[2 * i] = o.x;
     out[2 * i + 1] = o.y;
-    if (err) atomicOr(hdr + 1, (unsigned long long)err);
+    if (err) atomicOr(hdr + MVSDF_RES_H_ERR, (unsigned long long)err);
 }
 
 __device__ __forceinline__ double ud_shfl(double v, int lane) {

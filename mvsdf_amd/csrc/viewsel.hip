@@ -21,14 +21,8 @@
 #define VS_THREADS 256
 #define VS_TILE 64
 #define VS_HDR 256
-#define VS_MAX_V 65535
+static_assert(MVSDF_RES_H_WORDS * 8 <= VS_HDR, "the result words fit the header");
 #define VS_TARGET_WGS 1024                            // workgroups the score kernel aims for (4 per CU: three tiles of 48 KB fit a CU's LDS)
-
-enum {
-    VS_ERR_FINITE = 1,
-    VS_ERR_TRACK = 2,
-    VS_ERR_SHAPE = 4,
-};
 
 typedef unsigned long long vs_u64;
 
@@ -73,10 +67,10 @@ __host__ __device__ static inline long long vs_quantise(double w) { return (long
 
 // ---- kernels ----
 
-// ORs VS_ERR_FINITE into the header when an entry of f[n] is not finite
+// ORs MVSDF_VS_ERR_FINITE into the header when an entry of f[n] is not finite
 static void vs_finite(const double* f, long long n, void* hdr, hipStream_t s) {
-    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3((unsigned)vs_min(mv_ceil_div(n, MV_THREADS), 1024ll)), dim3(MV_THREADS), 0, s, f, n, (vs_u64*)hdr + 1,
-                       (vs_u64)VS_ERR_FINITE);
+    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3((unsigned)vs_min(mv_ceil_div(n, MV_THREADS), 1024ll)), dim3(MV_THREADS), 0, s, f, n, (vs_u64*)hdr + MVSDF_RES_H_ERR,
+                       (vs_u64)MVSDF_VS_ERR_FINITE);
 }
 
 // vis uint8 [V][P] -> bits [P][nw]; consecutive lanes take consecutive points of one word, so the 64 byte reads of a lane are coalesced over the wave
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_pack_tracks(const long long* 
             if (v < 0 || v >= V) { bad = true; continue; }
             row[v >> 6] |= 1ull << (v & 63);
         }
-    if (bad) atomicOr((vs_u64*)(hdr + 1), (vs_u64)VS_ERR_TRACK);
+    if (bad) atomicOr((vs_u64*)(hdr + MVSDF_RES_H_ERR), (vs_u64)MVSDF_VS_ERR_TRACK);
 }
 
 __device__ __forceinline__ vs_u64 vs_uniform(vs_u64 x) {
@@ -188,12 +182,7 @@ __global__ __launch_bounds__(VS_THREADS) void k_vs_depths(const double* __restri
     z[idx] = out;
 }
 
-static int vs_shape_header(void* hdr, hipStream_t s, const char* what) {
-    const long long h[2] = {0, VS_ERR_SHAPE};
-    return mv_write_header(hdr, h, 2, s, what);
-}
-
-static inline bool vs_shape_ok(int64_t V, int64_t P) { return V >= 1 && V <= VS_MAX_V && P >= 0 && P <= INT_MAX; }
+static inline bool vs_shape_ok(int64_t V, int64_t P) { return V >= 1 && V <= MVSDF_VS_MAX_VIEWS && P >= 0 && P <= INT_MAX; }
 static inline int vs_words(int64_t V) { return (int)((V + 63) / 64); }
 
 extern "C" {
@@ -205,7 +194,7 @@ size_t mvsdf_viewsel_bits_bytes(int64_t V, int64_t P) {
 }
 
 size_t mvsdf_viewsel_workspace_bytes(int64_t V) {
-    if (V < 1 || V > VS_MAX_V) return 0;
+    if (V < 1 || V > MVSDF_VS_MAX_VIEWS) return 0;
     return VS_HDR + (size_t)V * (size_t)V * 8;
 }
 
@@ -213,7 +202,7 @@ int mvsdf_viewsel_pack_dense(const uint8_t* vis, int64_t V, int64_t P, void* bit
     const char* what = "mvsdf_viewsel_pack_dense";
     if (!hdr || (P > 0 && (!bits || !vis))) return mv_fail(-1, "mvsdf_viewsel_pack_dense: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (!vs_shape_ok(V, P)) return vs_shape_header(hdr, s, what);
+    if (!vs_shape_ok(V, P)) return mv_refuse_header(hdr, MVSDF_VS_ERR_SHAPE, s, what);
     if (int rc = mv_check(hipMemsetAsync(hdr, 0, VS_HDR, s), what)) return rc;
     if (P == 0) return 0;
     const int nw = vs_words(V);
@@ -227,7 +216,7 @@ int mvsdf_viewsel_pack_tracks(const int64_t* track_off, const int32_t* track_vie
     const char* what = "mvsdf_viewsel_pack_tracks";
     if (!hdr || !track_off || (P > 0 && !bits) || nnz < 0 || (nnz > 0 && !track_view)) return mv_fail(-1, "mvsdf_viewsel_pack_tracks: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (!vs_shape_ok(V, P)) return vs_shape_header(hdr, s, what);
+    if (!vs_shape_ok(V, P)) return mv_refuse_header(hdr, MVSDF_VS_ERR_SHAPE, s, what);
     if (int rc = mv_check(hipMemsetAsync(hdr, 0, VS_HDR, s), what)) return rc;
     if (P == 0) return 0;
     hipLaunchKernelGGL(k_vs_pack_tracks, dim3(mv_grid(P, VS_THREADS)), dim3(VS_THREADS), 0, s, (const long long*)track_off, track_view,

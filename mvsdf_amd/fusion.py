@@ -50,7 +50,7 @@ script's text is not available to this project, so its agreement with this defin
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, raise_for_bits, _header, _stream, _vp
 
 
 class Fused:
@@ -86,19 +86,12 @@ def projection_matrices(cams):
     return P, Pinv
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a camera entry or a threshold is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: a pair index is outside [0, V)' % what)
-    if err & 4:
-        raise ValueError('%s: view must be >= 1' % what)
-    if err & 8:
-        raise ValueError('%s: shapes disagree or are out of range (V >= 1, H and W >= 2)' % what)
-    if err & 16:
-        raise ValueError('%s: a view or pixel index of a point lies outside the depth maps' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a fusion call (csrc/fusion.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_FU_ERR_FINITE, ValueError, 'a camera entry or a threshold is NaN or infinite'),
+          (K.MVSDF_FU_ERR_PAIR, ValueError, 'a pair index is outside [0, V)'),
+          (K.MVSDF_FU_ERR_VIEW, ValueError, 'view must be >= 1'),
+          (K.MVSDF_FU_ERR_SHAPE, ValueError, 'shapes disagree or are out of range (V >= 1, H and W >= 2)'),
+          (K.MVSDF_FU_ERR_INDEX, ValueError, 'a view or pixel index of a point lies outside the depth maps')]
 
 
 def _jump(jump, what):
@@ -141,7 +134,7 @@ def depth_normals(fused, cams, jump=0.05):
     ws = torch.empty(size, dtype=torch.uint8, device=d.device)
     check(lib().mvsdf_fusion_normals(_vp(d), V, H, W, _vp(view), _vp(pixel), n, mats.ctypes.data, jump, _vp(ws), size, _vp(normals), _stream(d)),
           'mvsdf_fusion_normals')
-    _errors(_header(ws, 2)[1], what)                                        # the one wait of the call; mats lives until here
+    raise_for_bits(_header(ws, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, ERRORS)   # the one wait of the call; mats lives until here
     return normals
 
 
@@ -216,8 +209,8 @@ def fuse_depths(cams, depths, pairs, probs=None, images=None, pthresh=(0.8, 0.7,
     check(lib().mvsdf_fusion_fuse(_vp(d), _vp(p), pt.ctypes.data, V, H, W, off.ctypes.data, src.ctypes.data if npairs else None, mats.ctypes.data,
                                   view, vthresh, float(pix_thresh), float(dep_thresh), _vp(ws), size, _vp(masked), _vp(fused), _vp(counts), st),
           'mvsdf_fusion_fuse')
-    total, err = _header(ws, 2)                                             # the one wait of the call; off / src / mats / pt live until here
-    _errors(err, what)
+    total, err = _header(ws, K.MVSDF_RES_H_WORDS)   # the one wait of the call; off / src / mats / pt live until here
+    raise_for_bits(err, what, ERRORS)
     points = torch.empty(total, 3, dtype=torch.float64, device=dev)
     colors = torch.empty(total, 3, dtype=torch.uint8, device=dev) if img is not None else None
     vw = torch.empty(total, dtype=torch.int32, device=dev)

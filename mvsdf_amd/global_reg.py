@@ -66,28 +66,22 @@ import torch
 
 from . import normals as _normals
 from . import registration as _reg
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from ._lib import check, lib, K, raise_for_bits, _header, _stream, _vp, f64_from_bits
 from .cloud import _device, _points
 
 DIM = 33
 BINS = 11
-MAX_HYPOTHESES = 1 << 22
+MAX_HYPOTHESES = K.MVSDF_GREG_MAX_HYPOTHESES
 
 GlobalRegistration = collections.namedtuple('GlobalRegistration', 'transformation inliers hypothesis checked mask')
 GlobalResult = collections.namedtuple('GlobalResult', 'transformation inliers flipped fitness inlier_rmse')
 
 
-def _errors(err, what):
-    if err & 4:
-        raise ValueError('%s: a coordinate is NaN or infinite' % what)
-    if err & 128:
-        raise ValueError('%s: a normal is NaN or infinite' % what)
-    if err & 256:
-        raise ValueError('%s: an index is out of range' % what)
-    if err & 512:
-        raise ValueError('%s: a code is outside 0 .. 127' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a global registration call (csrc/global_reg.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PC_ERR_FINITE, ValueError, 'a coordinate is NaN or infinite'),
+          (K.MVSDF_PC_ERR_NORMAL, ValueError, 'a normal is NaN or infinite'),
+          (K.MVSDF_PC_ERR_INDEX, ValueError, 'an index is out of range'),
+          (K.MVSDF_PC_ERR_CODE, ValueError, 'a code is outside 0 .. 127')]
 
 
 def _array(x, dtype, shape, what, name):
@@ -134,7 +128,7 @@ def spfh(points, normals, neighbors, radius=None):
     count = torch.empty(n, dtype=torch.int32, device=p.device)
     err = torch.zeros(1, dtype=torch.int32, device=p.device)
     check(lib().mvsdf_greg_spfh(_vp(p), _vp(nrm), _vp(nb), n, k, r2, _vp(hist), _vp(count), _vp(err), _stream(p)), 'mvsdf_greg_spfh')
-    _errors(int(err.item()), what)
+    raise_for_bits(int(err.item()), what, ERRORS)
     return hist, count
 
 
@@ -149,7 +143,7 @@ def fpfh(points, neighbors, hist, count, radius=None):
     codes = torch.empty(n, DIM, dtype=torch.int8, device=p.device)
     err = torch.zeros(1, dtype=torch.int32, device=p.device)
     check(lib().mvsdf_greg_fpfh(_vp(p), _vp(nb), _vp(hist), _vp(count), n, k, r2, _vp(feat), _vp(codes), _vp(err), _stream(p)), 'mvsdf_greg_fpfh')
-    _errors(int(err.item()), what)
+    raise_for_bits(int(err.item()), what, ERRORS)
     return feat, codes
 
 
@@ -183,7 +177,7 @@ def match_features(src_codes, dst_codes, mutual=False):
     index = torch.empty(ns, dtype=torch.int32, device=s.device)
     dist = torch.empty(ns, dtype=torch.int32, device=s.device)
     check(lib().mvsdf_greg_match(_vp(s), ns, _vp(t), nt, 1 if mutual else 0, _vp(ws), size, _vp(index), _vp(dist), _stream(s)), 'mvsdf_greg_match')
-    _errors(_header(ws, 1)[0], what)
+    raise_for_bits(_header(ws, K.MVSDF_ERRW_H_WORDS)[K.MVSDF_ERRW_H_ERR], what, ERRORS)
     return index, dist
 
 
@@ -227,11 +221,11 @@ def ransac(src, dst, corr, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9):
     mask = torch.empty(m, dtype=torch.uint8, device=s.device)
     check(lib().mvsdf_greg_ransac(_vp(s), s.shape[0], _vp(d), d.shape[0], _vp(c), m, H, int(seed), edge_ratio, max_dist, _vp(ws), size, _vp(mask),
                                   _stream(s)), 'mvsdf_greg_ransac')
-    h = _header(ws, 16)
-    _errors(h[3], what)
+    h = _header(ws, K.MVSDF_GREG_RANSAC_H_WORDS)
+    raise_for_bits(h[K.MVSDF_GREG_RANSAC_H_ERR], what, ERRORS)
     T = np.eye(4)
-    T[:3, :] = np.array([f64_from_bits(b) for b in h[4:16]], dtype=np.float64).reshape(3, 4)
-    return GlobalRegistration(T, h[1], h[0], h[2], mask.bool())
+    T[:3, :] = np.array([f64_from_bits(b) for b in h[K.MVSDF_GREG_RANSAC_H_T:K.MVSDF_GREG_RANSAC_H_WORDS]], dtype=np.float64).reshape(3, 4)
+    return GlobalRegistration(T, h[K.MVSDF_GREG_RANSAC_H_INLIERS], h[K.MVSDF_GREG_RANSAC_H_HYP], h[K.MVSDF_GREG_RANSAC_H_CHECKED], mask.bool())
 
 
 def _describe(points, given, voxel, k, radius, what, name):

@@ -57,24 +57,17 @@ import numpy as np
 import torch
 
 from . import viewsel
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, lib, K, MvsdfError, raise_for_bits, _header, _stream, _vp
 from .cloud import _device, _neighbors, _points
 
 SWEEPS = 6
 
 
-def _errors(err, what):
-    """raise for the error bits of a normals call (csrc/normals.hip; the low bits are those of csrc/nn_tree.h)"""
-    if err & 4:
-        raise ValueError('%s: a coordinate (or a view centre) is NaN or infinite' % what)
-    if err & 128:
-        raise ValueError('%s: a normal is NaN or infinite' % what)
-    if err & 256:
-        raise ValueError('%s: a neighbour index is outside [0, N)' % what)
-    if err & 32:
-        raise MvsdfError('%s: the orientation loop reached its round limit' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a normals call (csrc/normals.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PC_ERR_FINITE, ValueError, 'a coordinate (or a view centre) is NaN or infinite'),
+          (K.MVSDF_PC_ERR_NORMAL, ValueError, 'a normal is NaN or infinite'),
+          (K.MVSDF_PC_ERR_INDEX, ValueError, 'a neighbour index is outside [0, N)'),
+          (K.MVSDF_PC_ERR_ROUNDS, MvsdfError, 'the orientation loop reached its round limit')]
 
 
 def _knn(points, k, what, want_d2, want_normals):
@@ -91,7 +84,7 @@ def _knn(points, k, what, want_d2, want_normals):
     nrm = torch.empty(n, 3, dtype=torch.float64, device=dev) if want_normals else None
     var = torch.empty(n, dtype=torch.float64, device=dev) if want_normals else None
     check(lib().mvsdf_normals_knn(_vp(p), n, k, _vp(ws), size, _vp(idx), _vp(d2), _vp(nrm), _vp(var), _stream(p)), 'mvsdf_normals_knn')
-    _errors(_header(ws, 1)[0], what)
+    raise_for_bits(_header(ws, K.MVSDF_ERRW_H_WORDS)[K.MVSDF_ERRW_H_ERR], what, ERRORS)
     return idx, d2, nrm, var
 
 
@@ -145,7 +138,7 @@ def _visibility(visibility, V, n, what):
 def _pack(visibility, V, n, dev, what):
     """-> the bit matrix of viewsel.pack_visibility (its error bits checked)"""
     bits, hdr = viewsel.pack_visibility(visibility, V, n, dev)
-    viewsel._errors(_header(hdr, 2)[1], what)
+    raise_for_bits(_header(hdr, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, viewsel.ERRORS)
     return bits
 
 
@@ -202,8 +195,8 @@ def orient_normals(points, normals, neighbors, up=(0.0, 0.0, 1.0), centers=None,
     labels = torch.empty(n, dtype=torch.int32, device=dev)
     check(lib().mvsdf_normals_orient(_vp(p), _vp(nrm), _vp(nb), n, nb.shape[1], u[0], u[1], u[2], _vp(ctr), _vp(bits), V, _vp(ws), size, _vp(out),
                                      _vp(labels), _stream(p)), 'mvsdf_normals_orient')
-    n_components, rounds, err = _header(ws, 3)
-    _errors(err, what)
+    n_components, rounds, err = _header(ws, K.MVSDF_NR_ORIENT_H_WORDS)
+    raise_for_bits(err, what, ERRORS)
     return Oriented(out, labels, n_components, rounds)
 
 
@@ -225,5 +218,5 @@ def orient_to_views(points, normals, centers, visibility):
     out = torch.empty(n, 3, dtype=torch.float64, device=dev)
     hdr = torch.empty(256, dtype=torch.uint8, device=dev)
     check(lib().mvsdf_normals_to_views(_vp(p), _vp(nrm), n, _vp(ctr), _vp(bits), V, _vp(out), _vp(hdr), _stream(p)), 'mvsdf_normals_to_views')
-    _errors(_header(hdr, 1)[0], what)
+    raise_for_bits(_header(hdr, K.MVSDF_ERRW_H_WORDS)[K.MVSDF_ERRW_H_ERR], what, ERRORS)
     return out

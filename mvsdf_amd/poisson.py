@@ -43,9 +43,9 @@ import numpy as np
 import torch
 
 from . import mesh as _mesh
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from ._lib import check, f64_from_bits, K, lib, raise_for_bits, _header, _stream, _vp
 
-MIN_DEPTH, MAX_DEPTH = 2, 10
+MIN_DEPTH, MAX_DEPTH = K.MVSDF_PO_MIN_DEPTH, K.MVSDF_PO_MAX_DEPTH
 INT32_MAX = 2 ** 31 - 1
 STAGE_SPLAT, STAGE_SOLVE, STAGE_ISO = 1, 2, 4
 
@@ -63,15 +63,10 @@ def _depth(depth, what):
     return depth
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a coordinate, a normal, the origin or the voxel is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: depth must be in [2, 10], cycles >= 0, sweeps >= 1, voxel > 0' % what)
-    if err & 4:
-        raise ValueError('%s: between 1 and 2^31 - 1 points' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a poisson call (csrc/poisson.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PO_ERR_FINITE, ValueError, 'a coordinate, a normal, the origin or the voxel is NaN or infinite'),
+          (K.MVSDF_PO_ERR_RANGE, ValueError, 'depth must be in [2, 10], cycles >= 0, sweeps >= 1, voxel > 0'),
+          (K.MVSDF_PO_ERR_SHAPE, ValueError, 'between 1 and 2^31 - 1 points')]
 
 
 class Field:
@@ -170,8 +165,8 @@ class _Call:
               'mvsdf_poisson_reconstruct')
 
     def finish(self):
-        n_used, err, t, r0, r1 = _header(self.ws, 5)                        # the one wait of the call
-        _errors(err, self.what)
+        n_used, err, t, r0, r1 = _header(self.ws, K.MVSDF_PO_H_WORDS)                     # the one wait of the call
+        raise_for_bits(err, self.what, ERRORS)
         iso = f64_from_bits(t) / n_used if n_used else float('nan')
         return Field(self.chi, self.density, self.values[:n_used], iso, n_used, self.n - n_used, f64_from_bits(r0), f64_from_bits(r1), self.org.copy(),
                      self.h, self.depth)

@@ -34,13 +34,13 @@ anything is launched; a mesh on the CPU raises MvsdfError.  An empty mesh gives 
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, MvsdfError, raise_for_bits, _header, _stream, _vp
 from .mesh import Mesh
 
 LARGE_FACE_PIXELS = 16                               # faces whose clamped pixel box holds more go to the wave-per-face path
 KEY_BUDGET_PIXELS = 1 << 27                          # default view chunk: at most 1 GiB of keys ...
 ITEM_BUDGET = 1 << 26                                # ... and 2^26 (face, view) pairs per draw
-MAX_VIEWS = 65535
+MAX_VIEWS = K.MVSDF_RA_MAX_VIEWS
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -148,13 +148,9 @@ def _tol(name, x, what):
     return x
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a camera entry is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: a face index is outside the vertices' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a raster call (csrc/raster.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_RA_ERR_FINITE, ValueError, 'a camera entry is NaN or infinite'),
+          (K.MVSDF_RA_ERR_INDEX, ValueError, 'a face index is outside the vertices')]
 
 
 def rasterize(mesh, P=None, cams=None, hw=None, pixel_center=0.5, large_face_pixels=None, view_chunk=None, pretest=True, stats=False):
@@ -191,8 +187,8 @@ def rasterize(mesh, P=None, cams=None, hw=None, pixel_center=0.5, large_face_pix
         n = min(vc, V - v0)
         check(lib().mvsdf_raster_draw(_vp(v), _vp(f), nv, nf, _vp(Pd[v0:]), n, H, W, o, large, flags, _vp(ws), size, st), 'mvsdf_raster_draw')
         check(lib().mvsdf_raster_resolve(n, H, W, _vp(ws), size, _vp(depth[v0:]), _vp(face[v0:]), st), 'mvsdf_raster_resolve')
-        err, items, atomics, covered = _header(ws, 4)                     # one wait per chunk: the next draw reuses the workspace
-        _errors(err, what)
+        err, items, atomics, covered = _header(ws, K.MVSDF_RA_H_WORDS)                   # one wait per chunk: the next draw reuses the workspace
+        raise_for_bits(err, what, ERRORS)
         totals['large_items'] += items
         totals['atomics'] += atomics
         totals['covered'] += covered
@@ -224,7 +220,7 @@ def vertex_visibility(mesh, raster, masks=None, depth_tol=0.01):
     vis = torch.empty(V, nv, dtype=torch.uint8, device=dev)
     check(lib().mvsdf_raster_visibility(_vp(v), nv, _vp(Pd), V, H, W, raster.pixel_center, _vp(raster.depth.contiguous()), _vp(m), tol, _vp(ws), 256,
                                         _vp(vis), _stream(v)), 'mvsdf_raster_visibility')
-    _errors(_header(ws, 1)[0], what)
+    raise_for_bits(_header(ws, K.MVSDF_RA_H_WORDS)[K.MVSDF_RA_H_ERR], what, ERRORS)
     return vis
 
 
@@ -277,7 +273,7 @@ def color_vertices(mesh, images, P=None, cams=None, pixel_center=0.5, masks=None
     check(lib().mvsdf_raster_colors(_vp(v), _vp(n), nv, _vp(Pd), _vp(Cd), V, H, W, o, _vp(raster.depth.contiguous()), _vp(m), _vp(img), tol, cmin,
                                     1 if ignore_normals else 0, float(fb[0]), float(fb[1]), float(fb[2]), _vp(ws), 256, _vp(colors), _vp(n_views),
                                     _stream(v)), 'mvsdf_raster_colors')
-    _errors(_header(ws, 1)[0], what)
+    raise_for_bits(_header(ws, K.MVSDF_RA_H_WORDS)[K.MVSDF_RA_H_ERR], what, ERRORS)
     out = Mesh(mesh.vertices, mesh.faces, mesh.normals, colors)
     out.n_views = n_views
     out.raster = raster

@@ -59,10 +59,10 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp, f64_from_bits
+from ._lib import check, lib, K, raise_for_bits, _header, _stream, _vp, f64_from_bits
 from .mesh import Mesh
 
-MAX_POLYGON = 4096
+MAX_POLYGON = K.MVSDF_REG_MAX_POLYGON
 MAX_BINS = 4096
 IDENTITY = ((1.0, 0.0, 0.0, 0.0), (0.0, 1.0, 0.0, 0.0), (0.0, 0.0, 1.0, 0.0), (0.0, 0.0, 0.0, 1.0))
 JACOBI_SWEEPS = 16
@@ -74,13 +74,9 @@ TNT_TAU = {'Barn': 0.01, 'Caterpillar': 0.005, 'Church': 0.025, 'Courthouse': 0.
 Registration = collections.namedtuple('Registration', 'transformation fitness inlier_rmse iterations')
 
 
-def _errors(err, what):
-    if err & 4:
-        raise ValueError('%s: a coordinate is NaN or infinite' % what)
-    if err & 8:
-        raise ValueError('%s: the points span 2^21 or more voxels on an axis' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a registration call (csrc/registration.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PC_ERR_FINITE, ValueError, 'a coordinate is NaN or infinite'),
+          (K.MVSDF_PC_ERR_COORD, ValueError, 'the points span 2^21 or more voxels on an axis')]
 
 
 def _points(x, what, name='points', device=None, empty_ok=False):
@@ -128,9 +124,9 @@ class NearestTree:
             raise ValueError('%s: %d references (at most 2^31 - 1)' % (what, self.n))
         self._ws = torch.empty(self._size, dtype=torch.uint8, device=r.device)
         check(lib().mvsdf_reg_tree_build(_vp(r), self.n, _vp(self._ws), self._size, _stream(r)), 'mvsdf_reg_tree_build')
-        h = _header(self._ws, 4)
-        _errors(h[0], what)
-        self.centre = tuple(f64_from_bits(b) for b in h[1:4])
+        h = _header(self._ws, K.MVSDF_REG_TREE_H_WORDS)
+        raise_for_bits(h[K.MVSDF_REG_TREE_H_ERR], what, ERRORS)
+        self.centre = tuple(f64_from_bits(b) for b in h[K.MVSDF_REG_TREE_H_CENTRE:K.MVSDF_REG_TREE_H_WORDS])
 
     def __len__(self):
         return self.n
@@ -152,7 +148,7 @@ class NearestTree:
         check(lib().mvsdf_reg_tree_query(_vp(self._ws), self._size, self.n, _vp(q), nq, T, max_dist, _vp(dist), None, _vp(index), _vp(err),
                                          _stream(q)), 'mvsdf_reg_tree_query')
         if check_finite:
-            _errors(int(err.item()), what)
+            raise_for_bits(int(err.item()), what, ERRORS)
         return dist, index
 
 
@@ -192,7 +188,7 @@ def crop_volume(points, axis, axis_min, axis_max, polygon):
     out = torch.empty(n, 3, dtype=torch.float64, device=p.device)
     check(lib().mvsdf_reg_crop(_vp(p), n, a, axis_min, axis_max, _vp(dev_poly), poly.shape[0], _vp(ws), size, _vp(keep), _vp(out), _stream(p)),
           'mvsdf_reg_crop')
-    kept, = _header(ws, 1)
+    kept, = _header(ws, K.MVSDF_ROWS_H_WORDS)
     return keep.bool(), out[:kept]
 
 
@@ -211,8 +207,8 @@ def voxel_downsample(points, voxel):
     means = torch.empty(n, 3, dtype=torch.float64, device=p.device)
     counts = torch.empty(n, dtype=torch.int32, device=p.device)
     check(lib().mvsdf_reg_voxel(_vp(p), n, voxel, _vp(ws), size, _vp(means), _vp(counts), _stream(p)), 'mvsdf_reg_voxel')
-    m, err = _header(ws, 2)
-    _errors(err, what)
+    m, err = _header(ws, K.MVSDF_REG_VOXEL_H_WORDS)
+    raise_for_bits(err, what, ERRORS)
     return means[:m], counts[:m]
 
 
@@ -303,9 +299,9 @@ class _Pairs:
         t = self.tree
         check(lib().mvsdf_reg_icp_step(_vp(t._ws), t._size, t.n, _vp(t.refs), _vp(self.src), self.ns, _c16(T), max_dist, _vp(self.ws), self.size,
                                        _vp(self.d2), _vp(self.index), _stream(self.src)), 'mvsdf_reg_icp_step')
-        h = _header(self.ws, 18)
-        _errors(h[17], what)
-        return h[0], [f64_from_bits(b) for b in h[1:17]]
+        h = _header(self.ws, K.MVSDF_REG_ICP_H_WORDS)
+        raise_for_bits(h[K.MVSDF_REG_ICP_H_ERR], what, ERRORS)
+        return h[K.MVSDF_REG_ICP_H_N], [f64_from_bits(b) for b in h[K.MVSDF_REG_ICP_H_SUMS:K.MVSDF_REG_ICP_H_ERR]]
 
 
 def pair_sums(source, tree, T=IDENTITY, max_dist=float('inf')):

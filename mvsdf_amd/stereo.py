@@ -88,13 +88,13 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, raise_for_bits, _header, _stream, _vp
 from .fusion import projection_matrices
 
 PTHRESH = (0.7, 0.02, 0.9)        # thresholds on prob1, prob2, prob3 that suit these confidences (chosen on tests/stereo_scene.py: DESIGN.md)
-MAX_SRC, MAX_D = 255, 65535
-MAX_D_SGM = 4096                  # the most hypotheses regularize_scores takes
-MAX_D_BAND = 64                   # the most hypotheses of a band (band_sweep): the tile's scores and counts are then 36 KB of LDS
+MAX_SRC, MAX_D = K.MVSDF_PS_MAX_SRC, K.MVSDF_PS_MAX_D
+MAX_D_SGM = K.MVSDF_PS_MAX_D_SGM    # the most hypotheses regularize_scores takes
+MAX_D_BAND = K.MVSDF_PS_MAX_D_BAND  # the most hypotheses of a band (band_sweep): the tile's scores and counts are then 36 KB of LDS
 MAX_STAGES = 4                    # of a cascade
 CASCADE_DEFAULTS = ((None, 32, 16), (4, 2, 1))      # depth_nums, interval_scales: Vis-MVSNet's 64 / 32 / 16 at max_d 256
 SGM_DEFAULTS = (0.1, 0.8, 8)      # P1, P2, paths (chosen on the noisy test scene: DESIGN.md)
@@ -109,23 +109,14 @@ class Sweep:
         self.depths, self.probs, self.best_k, self.counts, self.scores, self.reg_scores = depths, probs, best_k, counts, scores, reg_scores
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a feature or a camera entry is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: a pair or view index is outside [0, V)' % what)
-    if err & 4:
-        raise ValueError('%s: the number of depth hypotheses must be in [1, %d]' % (what, MAX_D))
-    if err & 8:
-        raise ValueError('%s: shapes disagree or are out of range (V >= 1, R and S >= 2, C >= 1, at most %d sources)' % (what, MAX_SRC))
-    if err & 16:
-        raise ValueError('%s: the regularisation needs finite 0 <= P1 <= P2, paths 4 or 8 and at most %d hypotheses' % (what, MAX_D_SGM))
-    if err & 32:
-        raise ValueError('%s: a band needs 1 to %d hypotheses, finite positive steps and every view at most once' % (what, MAX_D_BAND))
-    if err & 64:
-        raise ValueError('%s: a centre is infinite' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a stereo call (csrc/stereo.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_PS_ERR_FINITE, ValueError, 'a feature or a camera entry is NaN or infinite'),
+          (K.MVSDF_PS_ERR_PAIR, ValueError, 'a pair or view index is outside [0, V)'),
+          (K.MVSDF_PS_ERR_DEPTHS, ValueError, 'the number of depth hypotheses must be in [1, %d]' % MAX_D),
+          (K.MVSDF_PS_ERR_SHAPE, ValueError, 'shapes disagree or are out of range (V >= 1, R and S >= 2, C >= 1, at most %d sources)' % MAX_SRC),
+          (K.MVSDF_PS_ERR_SGM, ValueError, 'the regularisation needs finite 0 <= P1 <= P2, paths 4 or 8 and at most %d hypotheses' % MAX_D_SGM),
+          (K.MVSDF_PS_ERR_BAND, ValueError, 'a band needs 1 to %d hypotheses, finite positive steps and every view at most once' % MAX_D_BAND),
+          (K.MVSDF_PS_ERR_CENTRE, ValueError, 'a centre is infinite')]
 
 
 def _checked_features(feats, what):
@@ -153,9 +144,9 @@ def normalize_descriptors(feats):
     what = 'normalize_descriptors'
     f, dev = _feature_tensor(feats, what)
     out = torch.empty_like(f)
-    hdr = torch.empty(2, dtype=torch.int64, device=dev)
+    hdr = torch.empty(K.MVSDF_RES_H_WORDS, dtype=torch.int64, device=dev)
     check(lib().mvsdf_stereo_normalize(_vp(f), f.numel() // f.shape[3], f.shape[3], _vp(out), _vp(hdr), _stream(f)), 'mvsdf_stereo_normalize')
-    _errors(int(hdr.cpu()[1]), what)
+    raise_for_bits(int(hdr.cpu()[K.MVSDF_RES_H_ERR]), what, ERRORS)
     return out
 
 
@@ -220,10 +211,8 @@ def regularize_scores(volume, p1=SGM_DEFAULTS[0], p2=SGM_DEFAULTS[1], paths=SGM_
     size = lib().mvsdf_stereo_sgm_workspace_bytes(R, S, D)
     ws = torch.empty(size, dtype=torch.uint8, device=v.device)
     check(lib().mvsdf_stereo_regularize(_vp(v), R, S, D, p1, p2, paths, _vp(ws), size, _vp(out), _stream(v)), 'mvsdf_stereo_regularize')
-    _, err = _header(ws, 2)
-    if err & 1:
-        raise ValueError('%s: a score is infinite' % what)
-    _errors(err, what)
+    _, err = _header(ws, K.MVSDF_RES_H_WORDS)
+    raise_for_bits(err, what, [(K.MVSDF_PS_ERR_FINITE, ValueError, 'a score is infinite')] + ERRORS)
     return out
 
 
@@ -309,8 +298,8 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, r
         check(lib().mvsdf_stereo_sweep_sgm(*head, sgm[0], sgm[1], sgm[2], *tail), 'mvsdf_stereo_sweep_sgm')
     else:
         check(lib().mvsdf_stereo_sweep(*head, *tail), 'mvsdf_stereo_sweep')
-    _, err = _header(ws, 2)                                                 # the one wait of the call; the host arrays live until here
-    _errors(err, what)
+    _, err = _header(ws, K.MVSDF_RES_H_WORDS)   # the one wait of the call; the host arrays live until here
+    raise_for_bits(err, what, ERRORS)
     vol = reg = None
     if scores:
         at = lib().mvsdf_stereo_volume_offset(R, S, dmax, npairs)
@@ -416,8 +405,8 @@ def _band_run(what, f, cams, views, used, c, Db, steps):
     check(lib().mvsdf_stereo_band(_vp(f), V, R, S, C, len(views), vw.ctypes.data, off.ctypes.data, src.ctypes.data if npairs else None, mats.ctypes.data,
                                   st.ctypes.data, _vp(c), Db, _vp(ws), size, _vp(depths), _vp(probs), _vp(best_k), _vp(counts), _stream(f)),
           'mvsdf_stereo_band')
-    _, err = _header(ws, 2)                                                 # the one wait of the call; the host arrays live until here
-    _errors(err, what)
+    _, err = _header(ws, K.MVSDF_RES_H_WORDS)   # the one wait of the call; the host arrays live until here
+    raise_for_bits(err, what, ERRORS)
     return Sweep(depths, probs, best_k, counts, None)
 
 

@@ -61,12 +61,12 @@ import numpy as np
 import torch
 
 from . import raster as R
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, lib, K, raise_for_bits, _header, _stream, _vp
 from .mesh import _write_textured_obj
 
 N_MIN, N_MAX, CLASSES = 4, 256, 7
-MAX_SIZE = 32768
-MAX_FACES = 1 << 28
+MAX_SIZE = K.MVSDF_TX_MAX_SIDE
+MAX_FACES = 1 << K.MVSDF_TX_MAX_FACES_LOG2
 
 
 class TexturedMesh:
@@ -123,7 +123,7 @@ def _face_views(mesh, raster, masks, depth_tol, cos_min, ignore_normals, what):
     check(lib().mvsdf_texture_face_views(_vp(v), _vp(n), _vp(f), nv, nf, _vp(Pd), _vp(Cd), V, H, W, raster.pixel_center, _vp(raster.depth.contiguous()),
                                          _vp(m), tol, cmin, 1 if ignore_normals else 0, _vp(ws), 256, _vp(label), _vp(score), _vp(screen),
                                          _stream(v)), 'mvsdf_texture_face_views')
-    R._errors(_header(ws, 1)[0], what)
+    raise_for_bits(_header(ws, K.MVSDF_TX_H_WORDS)[K.MVSDF_TX_H_ERR], what, R.ERRORS)
     return label, score, screen
 
 
@@ -148,7 +148,7 @@ def _classify(label, screen, d, ws, cls):
     """one count pass at density d -> the seven class counts (cls is written)"""
     nf = label.shape[0]
     check(lib().mvsdf_texture_classify(_vp(label), _vp(screen), nf, d, _vp(ws), ws.numel(), _vp(cls), _stream(ws)), 'mvsdf_texture_classify')
-    return _header(ws, 1 + CLASSES)[1:]
+    return _header(ws, K.MVSDF_TX_H_WORDS)[K.MVSDF_TX_H_COUNTS:]
 
 
 def _pack(cls, counts, ws):
@@ -159,9 +159,7 @@ def _pack(cls, counts, ws):
     patch = torch.empty(nf, 4, dtype=torch.int32, device=dev)
     uv = torch.empty(nf, 3, 2, dtype=torch.float32, device=dev)
     check(lib().mvsdf_texture_pack(_vp(cls), nf, carr, _vp(ws), ws.numel(), _vp(order), _vp(patch), _vp(uv), _stream(ws)), 'mvsdf_texture_pack')
-    err = _header(ws, 1)[0]
-    if err:
-        raise MvsdfError('build_atlas failed (error bits %d)' % err)
+    raise_for_bits(_header(ws, K.MVSDF_TX_H_WORDS)[K.MVSDF_TX_H_ERR], 'build_atlas', [])
     return order, patch, uv
 
 

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import mesh as _mesh
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, raise_for_bits, _header, _stream, _vp
 from .fusion import projection_matrices
 
 INT32_MAX = 2 ** 31 - 1
@@ -53,17 +53,11 @@ class Volume:
         return _mesh.marching_cubes_masked(self.tsdf, self.valid, 0.0, spacing=(self.voxel,) * 3, origin=tuple(self.origin))
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a camera entry, the origin, voxel or trunc is NaN or infinite (or jump is NaN)' % what)
-    if err & 2:
-        raise ValueError('%s: a view index is outside [0, V)' % what)
-    if err & 4:
-        raise ValueError('%s: voxel and trunc must be > 0, jump >= 0, min_views >= 1' % what)
-    if err & 8:
-        raise ValueError('%s: shapes disagree or are out of range (V >= 1, H and W >= 2, every dim >= 2, at least one view)' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a tsdf call (csrc/tsdf.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_TS_ERR_FINITE, ValueError, 'a camera entry, the origin, voxel or trunc is NaN or infinite (or jump is NaN)'),
+          (K.MVSDF_TS_ERR_VIEW, ValueError, 'a view index is outside [0, V)'),
+          (K.MVSDF_TS_ERR_RANGE, ValueError, 'voxel and trunc must be > 0, jump >= 0, min_views >= 1'),
+          (K.MVSDF_TS_ERR_SHAPE, ValueError, 'shapes disagree or are out of range (V >= 1, H and W >= 2, every dim >= 2, at least one view)')]
 
 
 def _int(name, x, what):
@@ -130,8 +124,8 @@ def integrate_depths(cams, depths, origin, voxel, dims, trunc=None, jump=None, m
     valid = torch.empty(dims, dtype=torch.bool, device=dev)
     check(lib().mvsdf_tsdf_integrate(_vp(d), V, H, W, mats.ctypes.data, vs.ctypes.data, len(vs), org.ctypes.data, h, dm.ctypes.data, trunc, jump,
                                      min_views, _vp(ws), size, _vp(tsdf), _vp(weight), _vp(valid), _stream(d)), 'mvsdf_tsdf_integrate')
-    _, err = _header(ws, 2)                                                 # the one wait of the call; mats / vs / org / dm live until here
-    _errors(err, what)
+    _, err = _header(ws, K.MVSDF_RES_H_WORDS)   # the one wait of the call; mats / vs / org / dm live until here
+    raise_for_bits(err, what, ERRORS)
     return Volume(tsdf, weight, valid, org.copy(), h, dims, trunc, jump, min_views)
 
 

@@ -50,7 +50,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, raise_for_bits, _header, _stream, _vp
 
 CHUNK_BYTES = 1 << 30                                # device memory one chunk of views may take, input plus output
 # model -> (family of csrc/undistort.hip, indices of fx, fy, cx, cy in the parameters, where the family's coefficients come from)
@@ -102,13 +102,9 @@ def _pinhole_block(camera, what):
     return camera_block(camera)[1][:4].copy()
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a non-finite value or a singular Jacobian in the inverse map (a point far outside what the model covers, or a NaN)' % what)
-    if err & 2:
-        raise ValueError('%s: the inverse map did not converge (the point lies outside what the distortion model reaches)' % what)
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of an undistort call (csrc/undistort.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_UD_ERR_FINITE, ValueError, 'a non-finite value or a singular Jacobian in the inverse map (a point far outside what the model covers, or a NaN)'),
+          (K.MVSDF_UD_ERR_CONVERGE, ValueError, 'the inverse map did not converge (the point lies outside what the distortion model reaches)')]
 
 
 def _map_points(points, camera, pinhole, inverse, what):
@@ -124,7 +120,7 @@ def _map_points(points, camera, pinhole, inverse, what):
     hdr = torch.empty(256, dtype=torch.uint8, device=dev)
     check(lib().mvsdf_undistort_points(_vp(p) if n else None, n, family, block.ctypes.data, pin.ctypes.data, inverse, _vp(out) if n else None, _vp(hdr),
                                        _stream(hdr)), 'mvsdf_undistort_points')
-    _errors(_header(hdr, 2)[1], what)                                       # the one wait of the call
+    raise_for_bits(_header(hdr, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, ERRORS)   # the one wait of the call
     return out
 
 

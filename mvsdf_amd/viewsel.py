@@ -46,22 +46,17 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import check, lib, MvsdfError, _header, _stream, _vp
+from ._lib import check, K, lib, raise_for_bits, _header, _stream, _vp
 
-MAX_VIEWS = 65535
+MAX_VIEWS = K.MVSDF_VS_MAX_VIEWS
 INT32_MAX = 2 ** 31 - 1
 DEPTH_CHUNK = 1 << 25                                # fp64 depths held at once by depth_ranges (256 MiB)
 
 
-def _errors(err, what):
-    if err & 1:
-        raise ValueError('%s: a point, a centre or an extrinsic entry is NaN or infinite' % what)
-    if err & 2:
-        raise ValueError('%s: a track view is outside [0, V) (or the track offsets do not ascend within the view list)' % what)
-    if err & 4:
-        raise ValueError('%s: V must be in [1, %d] and P below 2^31' % (what, MAX_VIEWS))
-    if err:
-        raise MvsdfError('%s failed (error bits %d)' % (what, err))
+# the error bits of a viewsel call (csrc/viewsel.hip), in the order they are looked at
+ERRORS = [(K.MVSDF_VS_ERR_FINITE, ValueError, 'a point, a centre or an extrinsic entry is NaN or infinite'),
+          (K.MVSDF_VS_ERR_TRACK, ValueError, 'a track view is outside [0, V) (or the track offsets do not ascend within the view list)'),
+          (K.MVSDF_VS_ERR_SHAPE, ValueError, 'V must be in [1, %d] and P below 2^31' % MAX_VIEWS)]
 
 
 def _params(theta0, sigma1, sigma2, what):
@@ -150,7 +145,7 @@ def view_scores(points, centers, visibility, theta0=5.0, sigma1=1.0, sigma2=10.0
     counts = torch.empty(V, V, dtype=torch.int64, device=dev)
     check(lib().mvsdf_viewsel_scores(_vp(pts) if P else None, _vp(ctr), _vp(bits) if P else None, V, P, theta0, sigma1, sigma2, _vp(ws), size, _vp(scores),
                                      _vp(counts), _vp(hdr), _stream(hdr)), 'mvsdf_viewsel_scores')
-    _errors(_header(hdr, 2)[1], what)                                       # the one wait of the call
+    raise_for_bits(_header(hdr, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, ERRORS)   # the one wait of the call
     return scores, counts
 
 
@@ -218,7 +213,7 @@ def depth_ranges(points, visibility, extrinsics, lo=0.01, hi=0.99):
     V, P = row2.shape[0], pts.shape[0]
     bits, hdr = pack_visibility(visibility, V, P, dev)
     if P == 0:
-        _errors(_header(hdr, 2)[1], what)
+        raise_for_bits(_header(hdr, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, ERRORS)
         raise ValueError('%s: view 0 sees no point' % what)
     out = torch.empty(V, 2, dtype=torch.float64, device=dev)
     seen = torch.empty(V, dtype=torch.int64, device=dev)
@@ -233,7 +228,7 @@ def depth_ranges(points, visibility, extrinsics, lo=0.01, hi=0.99):
         i0, i1 = _quantile_index(n, lo), _quantile_index(n, hi)
         out[v0:v0 + nv, 0] = zs.gather(1, i0.clamp(max=P - 1).unsqueeze(1)).squeeze(1)
         out[v0:v0 + nv, 1] = zs.gather(1, i1.clamp(max=P - 1).unsqueeze(1)).squeeze(1)
-    _errors(_header(hdr, 2)[1], what)                                       # the one wait of the call
+    raise_for_bits(_header(hdr, K.MVSDF_RES_H_WORDS)[K.MVSDF_RES_H_ERR], what, ERRORS)   # the one wait of the call
     empty = torch.nonzero(seen == 0).flatten().cpu()
     if len(empty):
         raise ValueError('%s: view %d sees no point' % (what, int(empty[0])))

@@ -141,7 +141,7 @@ def test_errors_raise_and_leave_the_device_usable():
 
 def test_the_library_refuses_what_the_binding_would_let_through():
     """the C entry validates on the host as well: its error bits reach the header without a launch"""
-    from mvsdf_amd._lib import lib
+    from mvsdf_amd._lib import K, lib
     from mvsdf_amd.mesh import _header
     V, H, W = 2, 4, 4
     d = torch.ones(V, H, W, device='cuda')
@@ -157,13 +157,13 @@ def test_the_library_refuses_what_the_binding_would_let_through():
         rc = lib().mvsdf_fusion_fuse(d.data_ptr(), None, pt.ctypes.data, V, H, W, off.ctypes.data, src.ctypes.data, mats.ctypes.data, view, 1, 1.0, 0.01,
                                      ws.data_ptr(), size, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert rc == 0
-        return _header(ws, 2)
+        return _header(ws, K.MVSDF_RES_H_WORDS)
     nan = eye.copy()
     nan[5] = np.nan
-    assert call([0, 1, 2], [1, 0], nan, 10) == [0, 1]
-    assert call([0, 1, 2], [1, 2], eye, 10) == [0, 2]
-    assert call([0, 1, 2], [1, 0], eye, 0) == [0, 4]
-    assert call([0, 2, 2], [1, 0], eye, 1) == [0, 8]                            # a pair list longer than view
+    assert call([0, 1, 2], [1, 0], nan, 10) == [0, K.MVSDF_FU_ERR_FINITE]
+    assert call([0, 1, 2], [1, 2], eye, 10) == [0, K.MVSDF_FU_ERR_PAIR]
+    assert call([0, 1, 2], [1, 0], eye, 0) == [0, K.MVSDF_FU_ERR_VIEW]
+    assert call([0, 2, 2], [1, 0], eye, 1) == [0, K.MVSDF_FU_ERR_SHAPE]                          # a pair list longer than view
     n, err = call([0, 1, 2], [1, 0], eye, 10)
     assert err == 0 and n == V * H * W                                          # identity transforms: every pixel sees itself
 

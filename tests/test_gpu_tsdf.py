@@ -286,7 +286,7 @@ def test_errors_raise_and_leave_the_device_usable():
 
 def test_the_library_refuses_what_the_binding_would_let_through():
     """the C entry validates on the host as well: its error bits reach the header without a launch"""
-    from mvsdf_amd._lib import lib, _header
+    from mvsdf_amd._lib import K, lib, _header
     V, H, W = 2, 4, 4
     d = torch.ones(V, H, W, device='cuda')
     size = lib().mvsdf_tsdf_workspace_bytes(V, H, W, 2)
@@ -305,14 +305,15 @@ def test_the_library_refuses_what_the_binding_would_let_through():
                                         trunc, jump, min_views, ws.data_ptr(), size, t.data_ptr(), w.data_ptr(), ok.data_ptr(),
                                         torch.cuda.current_stream().cuda_stream)
         assert rc == 0
-        return _header(ws, 2)
+        return _header(ws, K.MVSDF_RES_H_WORDS)
     nan = eye.copy()
     nan[5] = np.nan
-    assert call(mats=nan) == [0, 1] and call(trunc=float('inf')) == [0, 1] and call(jump=float('nan')) == [0, 1]
-    assert call(origin=np.array([0.0, np.inf, 0.0])) == [0, 1]
-    assert call(views=(0, 2)) == [0, 2] and call(views=(-1, 0)) == [0, 2]
-    assert call(voxel=0.0) == [0, 4] and call(trunc=-1.0) == [0, 4] and call(jump=-0.5) == [0, 4] and call(min_views=0) == [0, 4]
-    assert call(dims=(3, 1, 3)) == [0, 8]
+    fin, view, rng, shape = ([0, bit] for bit in (K.MVSDF_TS_ERR_FINITE, K.MVSDF_TS_ERR_VIEW, K.MVSDF_TS_ERR_RANGE, K.MVSDF_TS_ERR_SHAPE))
+    assert call(mats=nan) == fin and call(trunc=float('inf')) == fin and call(jump=float('nan')) == fin
+    assert call(origin=np.array([0.0, np.inf, 0.0])) == fin
+    assert call(views=(0, 2)) == view and call(views=(-1, 0)) == view
+    assert call(voxel=0.0) == rng and call(trunc=-1.0) == rng and call(jump=-0.5) == rng and call(min_views=0) == rng
+    assert call(dims=(3, 1, 3)) == shape
     assert bool((t == 5).all()) and bool((w == 5).all())                        # nothing was launched
     assert call() == [0, 0] and bool((w >= 0).all()) and bool((w <= 2).all())
 
