@@ -278,6 +278,17 @@ int mvsdf_render_forward(const MvsdfNetDesc* net, const float* points, const flo
 int mvsdf_render_backward(const MvsdfNetDesc* net, const MvsdfNetDesc* netT, int N, int Nctx, const float* drgb, const float* ctx,
                           float* dW_cat, float* db_cat, float* din, float* ws, void* stream);
 
+/* The form of the weight gradients dW = P^T Q of every backward above and of the training step (process-wide, for the calls that follow):
+ *   mode < 0 : by rule -- the three-term bf16 arithmetic (csrc/wgrad_x3.h) where the call's SDF descriptor carries the three-term packs (wx3), i.e. wherever
+ *              the chains run in that arithmetic; the fp32-input matrix instruction (k_wgrad_net) elsewhere.  The default.
+ *   mode 0 / 1 : the fp32 form / the three-term form for every call, whatever the descriptors carry.
+ * Returns the mode that was set before.  mvsdf_wgrad_x3_stage_rows: rows of the contraction the three-term form stages at a time.
+ * mvsdf_wgrad_uses_x3: 1 when a backward with this SDF descriptor forms its weight gradients in the three-term arithmetic now, else 0 -- a training step's one
+ * launch covers the rendering layers too, so a caller that runs the step's passes one by one sets that form around its mvsdf_render_backward to get the step's bits. */
+int mvsdf_set_wgrad_x3(int mode);
+int mvsdf_wgrad_x3_stage_rows(void);
+int mvsdf_wgrad_uses_x3(const MvsdfNetDesc* sdf);
+
 /* ---- IDRLoss.get_feat_loss_corr (model/loss.py:115-165 + utils/my_utils.py:98-110,152-165 + F.grid_sample) ----
  * forward AND analytic d(loss)/d(points) in one launch (feature maps are constants).  pts[N][3] = diff_surf_pts (hit points,
  * view-major); view_start[B+1] (device int32) = prefix sums of per-view hit counts; feat[B][C][H][W], feat_src[B][V][C][H][W]

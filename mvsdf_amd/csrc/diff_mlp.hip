@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include "layer_kernels.h"
 #include "chain_x3.h"
+#include "wgrad_x3.h"
 #include "capi_util.h"
 #include "step_internal.h"
 #include "diff_route.h"
@@ -260,28 +261,41 @@ static void wgrad_net_layers(WgradNetArgs& a, int l0, int n, int M, int nchunks,
     for (int l = l0; l < l0 + n; ++l) {
         WgradLayer& L = a.L[l];
         L.M = M; L.nchunks = nchunks; L.ch0 = 0; L.nch = nchunks;
-        L.nbx = (L.Ki + 63) / 64; L.nby = (L.No + 63) / 64;
         L.slab = slab + so; so += (size_t)nchunks * L.No * L.Ki;
         L.bslab = bslab + bo; bo += (size_t)nchunks * L.No;
         L.dW = dW_cat + wo; wo += (size_t)L.No * L.Ki;
         L.db = db_cat + b2; b2 += L.No;
     }
 }
-// one k_wgrad_net launch over the chunk ranges [ch0, ch0 + nch) of the layers (+ the column-sum workgroups when a.colX is set)
-static hipError_t wgrad_launch(WgradNetArgs& a, hipStream_t s) {
+// The form of the weight gradients, set at run time (mvsdf_set_wgrad_x3; -1: by rule, diff_route.h::mv_wgrad_uses_x3)
+static int g_wgrad_x3_mode = -1;
+static bool mv_desc_has_x3(const MvsdfNetDesc* d) {
+    if (!d || d->n_layers < 2 || d->n_layers > MV_MAXL) return false;
+    for (int l = 0; l < d->n_layers; ++l) if (!d->wx3[l]) return false;
+    return true;
+}
+static bool wgrad_x3_for(const MvsdfNetDesc* d) { return mv_wgrad_uses_x3(mv_desc_has_x3(d), g_wgrad_x3_mode, mv_dev_switches()); }
+
+// one k_wgrad_net / k_wgrad_net_x3 launch over the chunk ranges [ch0, ch0 + nch) of the layers (+ the column-sum workgroups when a.colX is set)
+static hipError_t wgrad_launch(WgradNetArgs& a, hipStream_t s, bool x3) {
+    const int tile = x3 ? MV_WGX_TILE : 64, run = x3 ? MV_WGX_RUN : 16;
     int blk = 0;
     for (int l = 0; l < a.n_layers; ++l) {
         WgradLayer& L = a.L[l];
+        L.nbx = (L.Ki + tile - 1) / tile; L.nby = (L.No + tile - 1) / tile;
         L.blk0 = blk; blk += L.nbx * L.nby * L.nch;
     }
     if (a.colX) { a.col_blk0 = blk; blk += ((a.col_n + 63) / 64) * a.col_nch; }
     // XCD-aware block order (layer_kernels.h; same blocks, same arithmetic, another placement): on by default, MVSDF_WG_XCD=0 turns it off.  Round 4, rocprofv3:
     // 92.9 -> 85.0 us at c2, 154.6 -> 153.9 at the c5 share, 310.7 -> 304.0 at c3 (round 2's two orders -- a contiguous range per XCD, and this one at c2 on the
-    // older kernel -- measured nothing)
+    // older kernel -- measured nothing).  Runs of 16 logical blocks per XCD (k_wgrad_net) / of MV_WGX_RUN (k_wgrad_net_x3): the grid is padded to 8 runs.
     a.nblocks = blk;
     a.xcd_runs = mv_dev_switches().wg_xcd;
-    const int grid = a.xcd_runs ? ((blk + 127) / 128) * 128 : blk;
-    if (blk > 0) hipLaunchKernelGGL(k_wgrad_net, dim3(grid), dim3(MV_THREADS), 0, s, a);
+    const int grid = a.xcd_runs ? ((blk + 8 * run - 1) / (8 * run)) * (8 * run) : blk;
+    if (blk > 0) {
+        if (x3) hipLaunchKernelGGL(k_wgrad_net_x3, dim3(grid), dim3(MV_WGX_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(k_wgrad_net, dim3(grid), dim3(MV_THREADS), 0, s, a);
+    }
     return hipGetLastError();
 }
 static hipError_t wgrad_reduce(WgradNetArgs& a, hipStream_t s) {
@@ -298,8 +312,8 @@ static hipError_t wgrad_reduce(WgradNetArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_reduce_net, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-static hipError_t launch_wgrad_net(WgradNetArgs& a, hipStream_t s) {
-    hipError_t e = wgrad_launch(a, s);
+static hipError_t launch_wgrad_net(WgradNetArgs& a, hipStream_t s, bool x3) {
+    hipError_t e = wgrad_launch(a, s, x3);
     return e != hipSuccess ? e : wgrad_reduce(a, s);
 }
 static void wgrad_colsum(WgradNetArgs& a, const float* X, int ld, int M, int n, int layer, int nchunks, float* colslab) {
@@ -606,7 +620,7 @@ int mvsdf_sdf_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, const floa
             const int Ki = net.L[nl - 1].K;
             wgrad_colsum(wa, ws + bl.VB[nl - 1], Ki, Mb, Ki, nl - 1, bl.nchunks, ws + bl.slabB);
         }
-        MV_TRY(launch_wgrad_net(wa, s));
+        MV_TRY(launch_wgrad_net(wa, s, wgrad_x3_for(d)));
     }
     // ---- E.3: input adjoint ----
     if (dx && !whole)
@@ -795,7 +809,7 @@ int mvsdf_sdf_backward_finish(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int
     wgrad_net_layers(wa, 0, nl, Mb, bl.nchunks, ws + bl.slabA, ws + bl.bslab, dW_cat, db_cat);
     const int Ki = net.L[nl - 1].K;                                                // W_last[0, :] += sum_rows ubar_last   (E.1 end)
     wgrad_colsum(wa, ws + bl.VB[nl - 1], Ki, Mb, Ki, nl - 1, bl.nchunks, ws + bl.slabB);
-    MV_TRY(launch_wgrad_net(wa, s));
+    MV_TRY(launch_wgrad_net(wa, s, wgrad_x3_for(d)));
     return mv_check(hipGetLastError(), "mvsdf_sdf_backward_finish");
 }
 
@@ -962,9 +976,17 @@ int mvsdf_render_backward(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int N, 
     wa.n_layers = net.n_layers; wa.chunk = bl.chunk;
     render_wgrad_operands(wa, 0, net, lo, bl, ctx, ws);
     wgrad_net_layers(wa, 0, net.n_layers, N, bl.nchunks, ws + bl.slab, ws + bl.bslab, dW_cat, db_cat);
-    MV_TRY(launch_wgrad_net(wa, s));
+    MV_TRY(launch_wgrad_net(wa, s, wgrad_x3_for(d)));
     return mv_check(hipGetLastError(), "mvsdf_render_backward");
 }
+
+int mvsdf_set_wgrad_x3(int mode) {
+    const int before = g_wgrad_x3_mode;
+    g_wgrad_x3_mode = mode < 0 ? -1 : (mode != 0);
+    return before;
+}
+int mvsdf_wgrad_x3_stage_rows(void) { return MV_WGX_STAGE; }
+int mvsdf_wgrad_uses_x3(const MvsdfNetDesc* sdf) { return wgrad_x3_for(sdf) ? 1 : 0; }
 
 }  // extern "C"
 
@@ -1045,7 +1067,7 @@ int mv_step_wgrad(const MvsdfNetDesc* sd, const MvsdfNetDesc* rd, int M, int Mg,
         for (int l = 0; l < nl; ++l) wa.L[l].mbase = cnt_base;
         for (int l = nl; l < nl + nr; ++l) wa.L[l].mbase = 0;
     }
-    MV_TRY(launch_wgrad_net(wa, (hipStream_t)stream));
+    MV_TRY(launch_wgrad_net(wa, (hipStream_t)stream, wgrad_x3_for(sd)));
     return mv_check(hipGetLastError(), "mv_step_wgrad");
 }
 

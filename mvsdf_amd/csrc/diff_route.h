@@ -16,6 +16,8 @@ struct MvDevSwitches {
     int delta_chain = 0;     // MVSDF_DELTA_CHAIN=1: the delta pass as a first-order chain instead of the scaling of the saved s_l
     int layer_mt = 0;        // MVSDF_LAYER_MT=1|2: row tiles per workgroup of the per-layer kernels
     int wg_xcd = 1;          // MVSDF_WG_XCD=0: k_wgrad_net's blocks in launch order instead of the XCD-aware order
+    int wgrad_x3 = -1;       // MVSDF_WGRAD_X3=0|1: the weight gradients on the fp32-input MFMA (k_wgrad_net) / in the three-term bf16 arithmetic (wgrad_x3.h)
+                             // whatever the descriptor carries; -1: by rule (mv_wgrad_uses_x3).  mvsdf_set_wgrad_x3 overrides it at run time.
 };
 // The struct from the environment (env: capi_util.h::mv_dev_env in the library, getenv in the route test).  The switches that pick the per-layer / split /
 // 8-wave fp32 launches mean the fp32 arithmetic everywhere: applied here and nowhere else.
@@ -28,6 +30,7 @@ inline MvDevSwitches mv_switches_from_env(const char* (*env)(const char*)) {
     if ((e = env("MVSDF_DELTA_CHAIN"))) v.delta_chain = atoi(e) != 0;
     if ((e = env("MVSDF_LAYER_MT"))) v.layer_mt = atoi(e);
     if ((e = env("MVSDF_WG_XCD")) && *e && atoi(e) >= 0) v.wg_xcd = atoi(e) != 0;
+    if ((e = env("MVSDF_WGRAD_X3")) && *e) v.wgrad_x3 = atoi(e) < 0 ? -1 : atoi(e) != 0;
     v.split_chains = env("MVSDF_SPLIT_CHAINS") != nullptr;          // (set at all, whatever its value -- historical, kept)
     const bool w8_set = (e = env("MVSDF_CHAIN_W8")) != nullptr;
     if (w8_set) v.chain_w8 = atoi(e) != 0;
@@ -99,6 +102,12 @@ inline MvRoute mv_route_x3(int net_ntw, int tiles16, bool two_tile, const MvDevS
     const int mt = two_tile ? mv_chain_mt_x3(tiles16, sw) : 1;
     if (mt == 2) return net_ntw == 4 ? MvRoute{MV_FAM_X3, 0, 2, 4, 8, 0} : MvRoute{MV_FAM_X3, 0, 2, 1, 16, MV_X3_PD2};
     return net_ntw == 2 ? MvRoute{MV_FAM_X3, 0, 1, 1, 16, MV_X3_PD1} : MvRoute{MV_FAM_X3, 0, 1, 2, 16, 0};
+}
+// weight gradients (k_wgrad_net / k_reduce_net): the three-term form wherever the x3 chains run -- the SDF descriptor of the call carries the three-term packs
+// (has_packs) and chain_x3 is on -- unless `mode` (the run-time setter, else MvDevSwitches::wgrad_x3) says 0 or 1
+inline bool mv_wgrad_uses_x3(bool has_packs, int mode, const MvDevSwitches& sw) {
+    if (mode < 0) mode = sw.wgrad_x3;
+    return mode < 0 ? (has_packs && sw.chain_x3 != 0) : mode != 0;
 }
 inline MvRoute mv_route_refuse(int rc) { return {MV_FAM_REFUSE, rc, 0, 0, 0, 0}; }
 inline MvRoute mv_route_layers() { return {MV_FAM_LAYERS, 0, 0, 0, 0, 0}; }

@@ -287,7 +287,7 @@ __device__ __forceinline__ int mv_wg_rows(const WgradNetArgs& a, const WgradLaye
 __device__ __forceinline__ int mv_wg_col_rows(const WgradNetArgs& a) { return a.cnt ? a.col_mbase + (int)a.cnt[0] : a.col_M; }
 
 // `scratch`: 256 floats of LDS (the caller's operand tile: a static array of its own here would push k_wgrad_net from 40 960 to 41 984 bytes of LDS, i.e.
-// from FOUR to THREE workgroups per CU)
+// from FOUR to THREE workgroups per CU).  The first four waves of the workgroup do the work (k_wgrad_net_x3 has eight: the same sums in the same order).
 __device__ __forceinline__ void mv_colsum_block(const WgradNetArgs& a, int local, float* scratch) {
     float (*red)[64] = (float (*)[64])scratch;
     const int nbx = (a.col_n + 63) / 64;
@@ -296,9 +296,9 @@ __device__ __forceinline__ void mv_colsum_block(const WgradNetArgs& a, int local
     const int rbeg = ch * a.chunk, rend = min(mv_wg_col_rows(a), rbeg + a.chunk);
     if (rbeg >= rend && a.cnt) return;                            // (deferred step: a chunk beyond the true rows; k_reduce_net does not read it)
     float s = 0.0f;
-    if (c < a.col_n)
+    if (c < a.col_n && g < 4)
         for (int row = rbeg + g; row < rend; row += 4) s += a.colX[(size_t)row * a.col_ld + c];
-    red[g][threadIdx.x & 63] = s;
+    if (g < 4) red[g][threadIdx.x & 63] = s;
     __syncthreads();
     if (g == 0 && c < a.col_n) a.colslab[(size_t)ch * a.col_n + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }

@@ -435,7 +435,7 @@ class _IdrStep(torch.autograd.Function):
             (w0, b0, e0), (w1, b1, e1) = plan.seg
             out_s, out_r = (dflat[w0:b0], dflat[b0:e0]), (dflat[w1:b1], dflat[b1:e1])
         if N > 0 and d_rgbv is not None:
-            dWr, dbr, din = ops.render_backward(rnet, N, d_rgbv[st.perm[:N]], st.rsaved, n_ctx=R, out=out_r)
+            dWr, dbr, din = ops.render_backward(rnet, N, d_rgbv[st.perm[:N]], st.rsaved, n_ctx=R, out=out_r, wgrad_like=net)
         elif plan is not None:
             dflat[w1:e1].zero_()
         common = (st.n_eik, st.n_ds, N, Nout, st.n_true, din, feat0, nrm0, use_geo)

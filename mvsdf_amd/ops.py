@@ -217,6 +217,19 @@ def fold_backward_net(vs, gs, dWs, dbs=None, sinks=None):
 CHAIN_X3 = True          # SDF networks get the three-term packs of W_l and W_l^T: their differentiable chains run on the bf16 matrix cores (csrc/chain_x3.h)
 
 
+def set_wgrad_x3(mode=None):
+    """Form of the weight gradients of every backward that follows (mvsdf_set_wgrad_x3, process-wide): None: by rule (the three-term bf16 form, csrc/wgrad_x3.h,
+    wherever the SDF descriptor carries the three-term packs), False / True: the fp32-input form / the three-term form everywhere.  Returns the setting before
+    (None / False / True)."""
+    before = lib().mvsdf_set_wgrad_x3(-1 if mode is None else int(bool(mode)))
+    return None if before < 0 else bool(before)
+
+
+def wgrad_x3_stage_rows():
+    """Rows of the contraction the three-term weight-gradient kernel stages at a time."""
+    return int(lib().mvsdf_wgrad_x3_stage_rows())
+
+
 def pack_x3_chain(net):
     """Three-term bf16 packs of every W_l and W_l^T of a folded SDF network (MvsdfNetDesc.wx3 of both descriptors)."""
     n = len(net.layers)
@@ -542,8 +555,10 @@ def render_forward(net, points, view, normals, feat, multires_view):
     return rgb, ctx
 
 
-def render_backward(net, N, drgb, ctx, n_ctx=None, out=None):
-    """n_ctx: rows the forward context was made with (default N); the backward covers its first N rows."""
+def render_backward(net, N, drgb, ctx, n_ctx=None, out=None, wgrad_like=None):
+    """n_ctx: rows the forward context was made with (default N); the backward covers its first N rows.
+    wgrad_like: the SDF network of the training step this backward is a piece of -- the weight gradients then take the form that network's take (the native step forms
+    both networks' in one launch: mvsdf_wgrad_uses_x3), so the step run pass by pass gives the native step's bits."""
     drgb = _f32(drgb)
     dev = drgb.device
     d, dT = net.desc(), net.desc(True)
@@ -555,8 +570,13 @@ def render_backward(net, N, drgb, ctx, n_ctx=None, out=None):
         db = torch.empty(sum(bs_n), dtype=torch.float32, device=dev)
     din = torch.empty(N, net.layers[0].K, dtype=torch.float32, device=dev)
     ws = torch.empty(lib().mvsdf_render_bwd_ws_floats(C.byref(d), N), dtype=torch.float32, device=dev)
-    check(lib().mvsdf_render_backward(C.byref(d), C.byref(dT), N, N if n_ctx is None else n_ctx, ptr(drgb), ptr(ctx), ptr(dW), ptr(db),
-                                      ptr(din), ptr(ws), stream_of(drgb)), 'mvsdf_render_backward')
+    before = None if wgrad_like is None else lib().mvsdf_set_wgrad_x3(lib().mvsdf_wgrad_uses_x3(C.byref(wgrad_like.desc())))
+    try:
+        check(lib().mvsdf_render_backward(C.byref(d), C.byref(dT), N, N if n_ctx is None else n_ctx, ptr(drgb), ptr(ctx), ptr(dW), ptr(db),
+                                          ptr(din), ptr(ws), stream_of(drgb)), 'mvsdf_render_backward')
+    finally:
+        if before is not None:
+            lib().mvsdf_set_wgrad_x3(before)
     if out is not None:
         return None, None, din
     dWs, dbs = _split_cat(net, dW, db)
