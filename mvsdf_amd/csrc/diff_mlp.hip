@@ -255,7 +255,7 @@ static SdfBwdLayout sdf_bwd_layout(const MvNet& net, int Mb) {
 
 // ---- weight / bias gradients: k_wgrad_net (+ folded column sums) and k_reduce_net over a list of layers ----
 // wgrad_net_layers: per-layer bookkeeping of one network's layers [l0, l0 + n) inside `a` (No / Ki / operands filled by the caller): M rows in
-// 128-row chunks, slabs carved from `slab` / `bslab`, reduction targets carved from dW_cat / db_cat.
+// MV_WG_CHUNK-row chunks, slabs carved from `slab` / `bslab`, reduction targets carved from dW_cat / db_cat.
 static void wgrad_net_layers(WgradNetArgs& a, int l0, int n, int M, int nchunks, float* slab, float* bslab, float* dW_cat, float* db_cat) {
     size_t so = 0, bo = 0, wo = 0, b2 = 0;
     for (int l = l0; l < l0 + n; ++l) {
@@ -278,24 +278,21 @@ static bool wgrad_x3_for(const MvsdfNetDesc* d) { return mv_wgrad_uses_x3(mv_des
 
 // one k_wgrad_net / k_wgrad_net_x3 launch over the chunk ranges [ch0, ch0 + nch) of the layers (+ the column-sum workgroups when a.colX is set)
 static hipError_t wgrad_launch(WgradNetArgs& a, hipStream_t s, bool x3) {
-    const int tile = x3 ? MV_WGX_TILE : 64, run = x3 ? MV_WGX_RUN : 16;
+    const WgForm f = x3 ? WG_X3 : WG_F32;
     int blk = 0;
     for (int l = 0; l < a.n_layers; ++l) {
         WgradLayer& L = a.L[l];
-        L.nbx = (L.Ki + tile - 1) / tile; L.nby = (L.No + tile - 1) / tile;
+        L.nbx = (L.Ki + f.TILE - 1) / f.TILE; L.nby = (L.No + f.TILE - 1) / f.TILE;
         L.blk0 = blk; blk += L.nbx * L.nby * L.nch;
     }
-    if (a.colX) { a.col_blk0 = blk; blk += ((a.col_n + 63) / 64) * a.col_nch; }
-    // XCD-aware block order (layer_kernels.h; same blocks, same arithmetic, another placement): on by default, MVSDF_WG_XCD=0 turns it off.  Round 4, rocprofv3:
-    // 92.9 -> 85.0 us at c2, 154.6 -> 153.9 at the c5 share, 310.7 -> 304.0 at c3 (round 2's two orders -- a contiguous range per XCD, and this one at c2 on the
-    // older kernel -- measured nothing).  Runs of 16 logical blocks per XCD (k_wgrad_net) / of MV_WGX_RUN (k_wgrad_net_x3): the grid is padded to 8 runs.
+    if (a.colX) { a.col_blk0 = blk; blk += ((a.col_n + MV_WG_COLS - 1) / MV_WG_COLS) * a.col_nch; }
+    // XCD-aware block order (layer_kernels.h: mv_wg_decode; same blocks, same arithmetic, another placement): on by default, MVSDF_WG_XCD=0 turns it off.  Round 4,
+    // rocprofv3: 92.9 -> 85.0 us at c2, 154.6 -> 153.9 at the c5 share, 310.7 -> 304.0 at c3 (round 2's two orders -- a contiguous range per XCD, and this one at
+    // c2 on the older kernel -- measured nothing).  The grid is padded to 8 runs of the form's RUN logical blocks.
     a.nblocks = blk;
     a.xcd_runs = mv_dev_switches().wg_xcd;
-    const int grid = a.xcd_runs ? ((blk + 8 * run - 1) / (8 * run)) * (8 * run) : blk;
-    if (blk > 0) {
-        if (x3) hipLaunchKernelGGL(k_wgrad_net_x3, dim3(grid), dim3(MV_WGX_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(k_wgrad_net, dim3(grid), dim3(MV_THREADS), 0, s, a);
-    }
+    const int grid = a.xcd_runs ? ((blk + 8 * f.RUN - 1) / (8 * f.RUN)) * (8 * f.RUN) : blk;
+    if (blk > 0) hipLaunchKernelGGL(x3 ? k_wgrad_net_x3 : k_wgrad_net, dim3(grid), dim3(f.THREADS), 0, s, a);
     return hipGetLastError();
 }
 static hipError_t wgrad_reduce(WgradNetArgs& a, hipStream_t s) {
@@ -985,7 +982,7 @@ int mvsdf_set_wgrad_x3(int mode) {
     g_wgrad_x3_mode = mode < 0 ? -1 : (mode != 0);
     return before;
 }
-int mvsdf_wgrad_x3_stage_rows(void) { return MV_WGX_STAGE; }
+int mvsdf_wgrad_x3_stage_rows(void) { return WG_X3.STAGE; }
 int mvsdf_wgrad_uses_x3(const MvsdfNetDesc* sdf) { return wgrad_x3_for(sdf) ? 1 : 0; }
 
 }  // extern "C"

@@ -190,66 +190,29 @@ __global__ __launch_bounds__(MV_THREADS) void k_layer(LayerArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Weight gradients dW[No][Ki] = P1^T Q1 (+ P2^T Q2) are GEMMs whose contraction runs over ROWS: split over 128-row chunks, partial 64x64 blocks go
-// to slabs that a second launch sums in a fixed order (deterministic, no atomics); tiles are staged through LDS with 16-byte loads (wg_stage).
-// The kernels are the network-wide k_wgrad_net / k_reduce_net below.
-__device__ __forceinline__ void wg_stage(const float* __restrict__ src, int ld, int row_lo, int row_hi, int c0, int ncols, float* __restrict__ dst,
-                                         int LD, int tid) {
-    // 64 rows x 64 cols -> LDS; 16-byte global loads when the source allows it
-    const bool vec = ((ld & 3) == 0) && ((c0 & 3) == 0) && ((((size_t)src) & 15) == 0);
-    if (vec) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int idx = u * MV_THREADS + tid, rr = idx >> 4, c4 = (idx & 15) * 4, row = row_lo + rr;
-            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < row_hi) {
-                if (c0 + c4 + 3 < ncols) v[u] = *(const float4*)(src + (size_t)row * ld + c0 + c4);
-                else {
-                    float t[4] = {0.f, 0.f, 0.f, 0.f};
-                    for (int e = 0; e < 4; ++e) if (c0 + c4 + e < ncols) t[e] = src[(size_t)row * ld + c0 + c4 + e];
-                    v[u] = make_float4(t[0], t[1], t[2], t[3]);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int idx = u * MV_THREADS + tid, rr = idx >> 4, c4 = (idx & 15) * 4;
-            *(float4*)(dst + rr * LD + c4) = v[u];
-        }
-    } else {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int idx = u * MV_THREADS + tid, rr = idx >> 6, c = idx & 63, row = row_lo + rr;
-            v[u] = (row < row_hi && c0 + c < ncols) ? src[(size_t)row * ld + c0 + c] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int idx = u * MV_THREADS + tid, rr = idx >> 6, c = idx & 63;
-            dst[rr * LD + c] = v[u];
-        }
-    }
-}
+// Weight gradients dW[No][Ki] = P1^T Q1 (+ P2^T Q2) are GEMMs whose contraction runs over ROWS: split over MV_WG_CHUNK-row chunks, partial output blocks go
+// to slabs that a second launch sums in a fixed order (deterministic, no atomics).  The kernels are the network-wide k_wgrad_net / k_reduce_net below.
 
 // dev probe (side build with -DMV_CHAIN_PROBE, tools/chain_probe.py): wave w of workgroup 0 accumulates the 100 MHz clock between the marks of
 // k_chain_fwd (tools/chain_probe.py) or of one 256 x 256 workgroup of k_wgrad_net (tools/chain_probe.py wgrad) into g_chain_ph[w][mark]; nothing in
-// the product build
+// the product build (ChPh, the marks' state, is a struct so that a kernel can hand it to mv_wg_pipeline: empty there)
 #ifdef MV_CHAIN_PROBE
 __device__ unsigned long long g_chain_ph[16][16];
-#define CH_PH_DECL unsigned long long chp_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long cht_ = wall_clock64();
-#define CH_PH(i) { const unsigned long long t_ = wall_clock64(); chp_[i] += t_ - cht_; cht_ = t_; }
-#define CH_PH_END if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_chain_ph[threadIdx.x >> 6][i_], chp_[i_]); }
-#define WG_PH_END(blk) if ((int)blockIdx.x == (blk) && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_chain_ph[8 + (threadIdx.x >> 6)][i_], chp_[i_]); }
+struct ChPh { unsigned long long acc[16], last; };
+#define CH_PH_DECL ChPh chp_ = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, (unsigned long long)wall_clock64()};
+#define CH_PH(i) { const unsigned long long t_ = wall_clock64(); chp_.acc[i] += t_ - chp_.last; chp_.last = t_; }
+#define CH_PH_END if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_chain_ph[threadIdx.x >> 6][i_], chp_.acc[i_]); }
+#define WG_PH_END(blk) if ((int)blockIdx.x == (blk) && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_chain_ph[8 + (threadIdx.x >> 6)][i_], chp_.acc[i_]); }
 #else
-#define CH_PH_DECL
+struct ChPh {};
+#define CH_PH_DECL [[maybe_unused]] ChPh chp_;
 #define CH_PH(i)
 #define CH_PH_END
 #define WG_PH_END(blk)
 #endif
 
 // ---- network-wide variants: the weight gradients of EVERY layer in one launch, then one reduction launch ----
-// Workgroup = (layer, 128-row chunk, 64x64 output block); both pairs of a layer (E.2 term zbar^T a and E.1 term s^T vbar) accumulate
+// Workgroup = (layer, MV_WG_CHUNK-row chunk, output block); both pairs of a layer (E.2 term zbar^T a and E.1 term s^T vbar) accumulate
 // in the same registers, so a layer needs one slab per chunk.
 #define MV_WG_MAXL 16                      // layers of one launch: both networks of a training step (9 + 5)
 // rows per weight-gradient chunk (one slab per chunk and layer).  128 -> 256: k_wgrad_net unchanged, k_reduce_net reads half the slabs (c2 20 -> 13 us,
@@ -264,7 +227,7 @@ struct WgradLayer {
     int No, Ki, nbx, nby;
     int M;                         // rows of this layer's operands (deferred step, WgradNetArgs.cnt set: mbase + cnt[0]; M then bounds the slabs)
     int mbase;
-    int nchunks;                   // 128-row chunks of M = slabs of this layer
+    int nchunks;                   // MV_WG_CHUNK-row chunks of M = slabs of this layer
     int ch0, nch;                  // the chunks THIS launch computes (a caller may split a layer's chunks over two launches)
     int blk0;                      // first workgroup of this layer in this launch
     float* slab; float* bslab;     // [nchunks][No * Ki], [nchunks][No]
@@ -280,8 +243,18 @@ struct WgradNetArgs {
     float* colslab;
     unsigned wtotal, btotal;
     const long long* cnt; int col_mbase;   // deferred step: device-side row counts (step_internal.h); the chunks beyond the true rows are neither computed nor summed
-    int xcd_runs, nblocks;             // xcd_runs: runs of 16 consecutive logical blocks per XCD (the launch grid is padded to a multiple of 128); nblocks: logical blocks
+    int xcd_runs, nblocks;             // xcd_runs: runs of WgForm::RUN consecutive logical blocks per XCD (the launch grid is padded to 8 runs); nblocks: logical blocks
 };
+// The two forms of the weight-gradient kernel, k_wgrad_net (fp32 matrix instruction) and k_wgrad_net_x3 (wgrad_x3.h: three bf16 terms).  They share chunks, slabs,
+// k_reduce_net, the column-sum workgroups and everything below up to k_wgrad_net; a form is its output block, how it stages a stage and its matrix instruction.
+struct WgForm {
+    int TILE;                      // output block: TILE x TILE
+    int RUN;                       // consecutive logical blocks per XCD run: the output blocks of one 256 x 256 layer and chunk (they share their operand rows)
+    int THREADS;
+    int STAGE;                     // rows per stage
+};
+constexpr WgForm WG_F32 = {64, 16, MV_THREADS, 64}, WG_X3 = {128, 4, 512, 32};
+constexpr int MV_WG_COLS = 64;     // columns per column-sum workgroup
 
 __device__ __forceinline__ int mv_wg_rows(const WgradNetArgs& a, const WgradLayer& L) { return a.cnt ? L.mbase + (int)a.cnt[0] : L.M; }
 __device__ __forceinline__ int mv_wg_col_rows(const WgradNetArgs& a) { return a.cnt ? a.col_mbase + (int)a.cnt[0] : a.col_M; }
@@ -289,10 +262,10 @@ __device__ __forceinline__ int mv_wg_col_rows(const WgradNetArgs& a) { return a.
 // `scratch`: 256 floats of LDS (the caller's operand tile: a static array of its own here would push k_wgrad_net from 40 960 to 41 984 bytes of LDS, i.e.
 // from FOUR to THREE workgroups per CU).  The first four waves of the workgroup do the work (k_wgrad_net_x3 has eight: the same sums in the same order).
 __device__ __forceinline__ void mv_colsum_block(const WgradNetArgs& a, int local, float* scratch) {
-    float (*red)[64] = (float (*)[64])scratch;
-    const int nbx = (a.col_n + 63) / 64;
+    float (*red)[MV_WG_COLS] = (float (*)[MV_WG_COLS])scratch;
+    const int nbx = (a.col_n + MV_WG_COLS - 1) / MV_WG_COLS;
     const int ch = a.col_ch0 + local / nbx, bx = local - (local / nbx) * nbx;
-    const int c = bx * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;
+    const int c = bx * MV_WG_COLS + (threadIdx.x & 63), g = threadIdx.x >> 6;
     const int rbeg = ch * a.chunk, rend = min(mv_wg_col_rows(a), rbeg + a.chunk);
     if (rbeg >= rend && a.cnt) return;                            // (deferred step: a chunk beyond the true rows; k_reduce_net does not read it)
     float s = 0.0f;
@@ -303,73 +276,133 @@ __device__ __forceinline__ void mv_colsum_block(const WgradNetArgs& a, int local
     if (g == 0 && c < a.col_n) a.colslab[(size_t)ch * a.col_n + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-__global__ __launch_bounds__(MV_THREADS) void k_wgrad_net(WgradNetArgs a) {
-    constexpr int LD = 80;
-    __shared__ __attribute__((aligned(16))) float Pt[64 * LD];
-    __shared__ __attribute__((aligned(16))) float Qt[64 * LD];
+// blockIdx.x -> the (layer, chunk, output block) and row window [rbeg, rend) of this workgroup.  false: no block to compute -- grid padding, a column-sum
+// workgroup (summed here; `scratch` as in mv_colsum_block) or, in the deferred step, a chunk beyond the true rows (k_reduce_net does not read its slab).
+// XCD-aware order (a.xcd_runs): the dispatcher places workgroup b on XCD b % 8, and the RUN output blocks of one (layer, chunk) share their operand rows: in
+// launch order every operand tile is pulled into several L2s.  Here each XCD takes runs of RUN consecutive logical blocks: workgroup b = 8 i + x  ->  logical
+// block ((i / RUN) * 8 + x) * RUN + i % RUN.
+struct WgBlock { int l, ch, bx, by, rbeg, rend; };     // (the layer as an index: a pointer into the kernel's arguments would send them to scratch)
+template <int RUN>
+__device__ __forceinline__ bool mv_wg_decode(const WgradNetArgs& a, float* scratch, WgBlock& b) {
     int bid = blockIdx.x;
     if (a.xcd_runs) {
-        // The dispatcher places workgroup b on XCD b % 8.  The 16 output blocks of one (layer, 256-row chunk) share their operand tiles: in launch order
-        // every tile is pulled into several L2s.  Here each XCD takes RUNS of 16 consecutive logical blocks: workgroup b = 8 i + x  ->  logical block
-        // ((i >> 4) * 8 + x) * 16 + (i & 15).
         const int x = bid & 7, i = bid >> 3;
-        bid = (((i >> 4) << 3) + x) * 16 + (i & 15);
-        if (bid >= a.nblocks) return;
+        bid = (((i / RUN) << 3) + x) * RUN + (i % RUN);
+        if (bid >= a.nblocks) return false;
     }
-    if (a.colX && bid >= a.col_blk0) { mv_colsum_block(a, bid - a.col_blk0, Pt); return; }
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
+    if (a.colX && bid >= a.col_blk0) { mv_colsum_block(a, bid - a.col_blk0, scratch); return false; }
     int l = 0;
     while (l + 1 < a.n_layers && bid >= a.L[l + 1].blk0) ++l;
     const WgradLayer& L = a.L[l];
     const int local = bid - L.blk0, nb = L.nbx * L.nby;
     const int chl = local / nb, rem = local - chl * nb, by = rem / L.nbx, bx = rem - by * L.nbx;
-    const int ch = L.ch0 + chl;
-    const int i0 = bx * 64, o0 = by * 64, No = L.No, Ki = L.Ki;
-    const int rbeg = ch * a.chunk, rend = min(mv_wg_rows(a, L), rbeg + a.chunk);
-    if (rbeg >= rend && a.cnt) return;                            // (deferred step: a chunk beyond the true rows; k_reduce_net does not read its slab)
+    const int ch = L.ch0 + chl, rbeg = ch * a.chunk, rend = min(mv_wg_rows(a, L), rbeg + a.chunk);
+    b = WgBlock{l, ch, bx, by, rbeg, rend};
+    return !(rbeg >= rend && a.cnt);
+}
+// the operand pair of stage st and its first row: the nrb stages of pair 0 (P1, Q1), then those of pair 1 (P2, Q2)
+struct WgOperands { const float* P; const float* Q; int ldp, ldq, rb, pair; };
+__device__ __forceinline__ WgOperands mv_wg_operands(const WgradLayer& L, int st, int nrb, int rbeg, int stage_rows) {
+    const int pair = st >= nrb ? 1 : 0;
+    return WgOperands{pair ? L.P2 : L.P1, pair ? L.Q2 : L.Q1, pair ? L.ldp2 : L.ldp1, pair ? L.ldq2 : L.ldq1, rbeg + (st - pair * nrb) * stage_rows, pair};
+}
+// The stage loop: the operands of stage st + 1 are requested into registers (issue) BEFORE the matrix instructions of stage st (compute) and written to LDS (store)
+// after them -- the probe (tools/chain_probe.py wgrad) showed a workgroup spending half of its life waiting for the tiles it had just asked for.  issue's loads
+// must be unconditional (indices clamped, masked when stored): a load inside a branch cannot stay in flight across compute, the compiler waits for it at the merge.
+template <class Issue, class Store, class Compute>
+__device__ __forceinline__ void mv_wg_pipeline(int nst, [[maybe_unused]] ChPh& chp_, Issue&& issue, Store&& store, Compute&& compute) {
+    if (nst <= 0) return;
+    auto stage = [&](int st) {
+        __syncthreads();
+        CH_PH(1)
+        store(st);
+        CH_PH(2)
+        __syncthreads();
+        CH_PH(3)
+    };
+    issue(0);
+    for (int st = 0; st + 1 < nst; ++st) {
+        stage(st);
+        issue(st + 1);
+        compute(st);
+        CH_PH(4)
+    }
+    stage(nst - 1);
+    compute(nst - 1);
+    CH_PH(4)
+}
+// one 16 x 16 accumulator tile -> slab[No][Ki]: a lane holds output rows o .. o + 3 of column i (lane (q, r) of the matrix instruction: rows 4 q .. 4 q + 3, column r)
+__device__ __forceinline__ void mv_wg_slab_store(float* __restrict__ slab, const f32x4& acc, int o, int i, int No, int Ki) {
+    if (i < Ki) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (o + e < No) slab[(size_t)(o + e) * Ki + i] = acc[e];
+    }
+}
+
+// One operand's stage of k_wgrad_net: 64 rows from row rb x 64 columns from column c0 of X[.][ld] (n columns, rows end at rend), 16 floats per thread, read by
+// wg_f32_load -- unconditional: rows and columns clamped to a valid element -- and written to the operand's LDS tile by wg_f32_store, where the mask is applied.
+// VEC (the 64 columns lie inside the layer, rows 16-byte aligned: every 256-wide operand): float4 u = row 16 u + (tid >> 4), columns 4 (tid & 15) .. + 3;
+// otherwise dwords, (u, e) = row 4 (4 u + e) + w (the wave's), column tid & 63.  The LDS image, hence every sum and its order, is the same either way.
+template <bool VEC>
+__device__ __forceinline__ void wg_f32_load(f32x4 (&v)[4], const float* __restrict__ X, int ld, int c0, int n, int rb, int rend, int tid, int w) {
+    const int c = min(c0 + (VEC ? 4 * (tid & 15) : tid & 63), n - 1), r0 = rb + (VEC ? tid >> 4 : w);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if constexpr (VEC) v[u] = *(const f32x4*)(X + (size_t)min(r0 + 16 * u, rend - 1) * ld + c);
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[u][e] = X[(size_t)min(r0 + 4 * (4 * u + e), rend - 1) * ld + c];
+        }
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void wg_f32_store(float* tile, int LD, const f32x4 (&v)[4], int c0, int n, int rb, int rend, int tid, int w) {
+    const int c = VEC ? 4 * (tid & 15) : tid & 63, r0 = VEC ? tid >> 4 : w;
+    const bool c_in = c0 + c < n;
+    float* d = tile + r0 * LD + c;                                // (one address, constant offsets)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if constexpr (VEC) *(f32x4*)(d + 16 * u * LD) = rb + r0 + 16 * u < rend ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[4 * (4 * u + e) * LD] = (c_in && rb + r0 + 4 * (4 * u + e) < rend) ? v[u][e] : 0.0f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(WG_F32.THREADS, 4) void k_wgrad_net(WgradNetArgs a) {
+    constexpr int LD = 80, TILE = WG_F32.TILE, STAGE = WG_F32.STAGE;
+    __shared__ __attribute__((aligned(16))) float Pt[STAGE * LD];
+    __shared__ __attribute__((aligned(16))) float Qt[STAGE * LD];
+    WgBlock b;
+    if (!mv_wg_decode<WG_F32.RUN>(a, Pt, b)) return;
+    const WgradLayer& L = a.L[b.l];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
+    const int i0 = b.bx * TILE, o0 = b.by * TILE, No = L.No, Ki = L.Ki, rbeg = b.rbeg, rend = b.rend;
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum = 0.0f;
-    const bool do_bias = bx == 0;
+    const bool do_bias = b.bx == 0;
     CH_PH_DECL
-    const int npairs = L.P2 ? 2 : 1;
-    // Fast path (full 64-column tiles, 16-byte aligned rows: every 256-wide layer): the operand tiles of stage s + 1 are requested into
-    // registers BEFORE the MFMA loop of stage s and written to LDS after it -- the probe (tools/chain_probe.py) showed a workgroup spending half
-    // of its life waiting for the tiles it had just asked for.  The loads are unconditional (rows clamped, masked when stored): a load inside a
-    // branch cannot stay in flight across the loop (the compiler waits for it at the merge) -- why the same idea measured nothing in round 3's
-    // first attempt.
-    const int nrb = (rend - rbeg + 63) / 64, nst = npairs * nrb;
-    const bool fast = ((L.ldp1 & 3) == 0) && ((L.ldq1 & 3) == 0) && ((((size_t)L.P1) & 15) == 0) && ((((size_t)L.Q1) & 15) == 0) && o0 + 64 <= No && i0 + 64 <= Ki &&
-                      (!L.P2 || (((L.ldp2 & 3) == 0) && ((L.ldq2 & 3) == 0) && ((((size_t)L.P2) & 15) == 0) && ((((size_t)L.Q2) & 15) == 0))) && nst > 0;
-    if (fast) {
-        float4 pv[4], qv[4];
+    const int nrb = rend > rbeg ? (rend - rbeg + STAGE - 1) / STAGE : 0, nst = (L.P2 ? 2 : 1) * nrb;
+    auto run = [&](auto vp, auto vq) {
+        constexpr bool VP = decltype(vp)::value, VQ = decltype(vq)::value;
+        f32x4 pv[4], qv[4];
         auto issue = [&](int st) {
-            const int pair = st >= nrb ? 1 : 0, rb = rbeg + (st - pair * nrb) * 64;
-            const float* P = pair ? L.P2 : L.P1;
-            const float* Q = pair ? L.Q2 : L.Q1;
-            const int ldp = pair ? L.ldp2 : L.ldp1, ldq = pair ? L.ldq2 : L.ldq1;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = u * MV_THREADS + tid, rr = idx >> 4, c4 = (idx & 15) * 4;
-                const int row = min(rb + rr, rend - 1);
-                pv[u] = *(const float4*)(P + (size_t)row * ldp + o0 + c4);
-                qv[u] = *(const float4*)(Q + (size_t)row * ldq + i0 + c4);
-            }
+            const WgOperands s = mv_wg_operands(L, st, nrb, rbeg, STAGE);
+            wg_f32_load<VP>(pv, s.P, s.ldp, o0, No, s.rb, rend, tid, w);
+            wg_f32_load<VQ>(qv, s.Q, s.ldq, i0, Ki, s.rb, rend, tid, w);
         };
         auto store = [&](int st) {
-            const int pair = st >= nrb ? 1 : 0, rb = rbeg + (st - pair * nrb) * 64;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int idx = u * MV_THREADS + tid, rr = idx >> 4, c4 = (idx & 15) * 4;
-                const bool in = rb + rr < rend;
-                *(float4*)(Pt + rr * LD + c4) = in ? pv[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-                *(float4*)(Qt + rr * LD + c4) = in ? qv[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+            const int rb = mv_wg_operands(L, st, nrb, rbeg, STAGE).rb;
+            wg_f32_store<VP>(Pt, LD, pv, o0, No, rb, rend, tid, w);
+            wg_f32_store<VQ>(Qt, LD, qv, i0, Ki, rb, rend, tid, w);
         };
         auto compute = [&](int st) {
-            if (do_bias && st < nrb && tid < 64) {
-                for (int rr = 0; rr < 64; ++rr) bsum += Pt[rr * LD + tid];
+            if (do_bias && st < nrb && tid < TILE) {                  // bias sums: over pair 0 only
+                for (int rr = 0; rr < STAGE; ++rr) bsum += Pt[rr * LD + tid];
             }
             // operands of k-step s + 1 are read from LDS while the four MFMAs of k-step s issue (the plain loop reads, waits ~100 cycles, issues two
             // MFMAs, reads again: each wave kept the matrix pipe busy 40 % of its own time)
@@ -380,8 +413,8 @@ __global__ __launch_bounds__(MV_THREADS) void k_wgrad_net(WgradNetArgs a) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) bq[0][t] = pb[16 * t];
 #pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                if (s + 1 < 16) {
+            for (int s = 0; s < STAGE / 4; ++s) {
+                if (s + 1 < STAGE / 4) {
                     av[(s + 1) & 1] = pa[4 * (s + 1) * LD];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) bq[(s + 1) & 1][t] = pb[4 * (s + 1) * LD + 16 * t];
@@ -392,59 +425,24 @@ __global__ __launch_bounds__(MV_THREADS) void k_wgrad_net(WgradNetArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        issue(0);
-        for (int st = 0; st + 1 < nst; ++st) {
-            __syncthreads();
-            store(st);
-            __syncthreads();
-            issue(st + 1);
-            compute(st);
-        }
-        __syncthreads();
-        store(nst - 1);
-        __syncthreads();
-        compute(nst - 1);
-    } else
-    for (int pair = 0; pair < npairs; ++pair) {
-        const float* P = pair ? L.P2 : L.P1;
-        const float* Q = pair ? L.Q2 : L.Q1;
-        const int ldp = pair ? L.ldp2 : L.ldp1, ldq = pair ? L.ldq2 : L.ldq1;
-        for (int rb = rbeg; rb < rend; rb += 64) {
-            CH_PH(0)
-            __syncthreads();
-            CH_PH(1)
-            wg_stage(P, ldp, rb, rend, o0, No, Pt, LD, tid);
-            wg_stage(Q, ldq, rb, rend, i0, Ki, Qt, LD, tid);
-            CH_PH(2)
-            __syncthreads();
-            CH_PH(3)
-            if (do_bias && pair == 0 && tid < 64) {
-                for (int rr = 0; rr < 64; ++rr) bsum += Pt[rr * LD + tid];
-            }
-            CH_PH(4)
-#pragma unroll 4
-            for (int s = 0; s < 16; ++s) {
-                const float av = Pt[(4 * s + q) * LD + 16 * w + r];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, Qt[(4 * s + q) * LD + 16 * t + r], acc[t], 0, 0, 0);
-            }
-        }
-    }
+        mv_wg_pipeline(nst, chp_, issue, store, compute);
+    };
+    // The staging of each operand is chosen by itself (layer 0, the skip layer, the 257-output layer and the rendering net's first and last layers have one
+    // operand that cannot take 16-byte loads and one that can: three blocks in ten of a step).  Instantiations, not a branch inside issue / store: the loads of
+    // a stage and the wait for them must lie in one branch arm (mv_wg_pipeline).
+    auto vec = [](const float* X1, int ld1, const float* X2, int ld2, int c0, int n) {
+        return (ld1 & 3) == 0 && (((size_t)X1) & 15) == 0 && c0 + TILE <= n && (!X2 || ((ld2 & 3) == 0 && (((size_t)X2) & 15) == 0));
+    };
+    const bool vp = vec(L.P1, L.ldp1, L.P2, L.ldp2, o0, No), vq = vec(L.Q1, L.ldq1, L.Q2, L.ldq2, i0, Ki);
+    if (vp && vq) run(std::true_type{}, std::true_type{});
+    else if (vp) run(std::true_type{}, std::false_type{});
+    else if (vq) run(std::false_type{}, std::true_type{});
+    else run(std::false_type{}, std::false_type{});
     CH_PH(5)
-    float* slab = L.slab + (size_t)ch * No * Ki;
+    float* slab = L.slab + (size_t)b.ch * No * Ki;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int i = i0 + 16 * t + r;
-        if (i < Ki) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = o0 + 16 * w + 4 * q + e;
-                if (o < No) slab[(size_t)o * Ki + i] = acc[t][e];
-            }
-        }
-    }
-    if (do_bias && tid < 64 && o0 + tid < No) L.bslab[(size_t)ch * No + o0 + tid] = bsum;
+    for (int t = 0; t < 4; ++t) mv_wg_slab_store(slab, acc[t], o0 + 16 * w + 4 * q, i0 + 16 * t + r, No, Ki);
+    if (do_bias && tid < TILE && o0 + tid < No) L.bslab[(size_t)b.ch * No + o0 + tid] = bsum;
     CH_PH(6)
     WG_PH_END(a.L[1].blk0 + 1)                                   // a bx = 1 block (no bias sum) of the first chunk of layer 1 (256 x 256)
 }
@@ -485,19 +483,6 @@ __global__ void k_reduce_net(WgradNetArgs a) {
             L.dW[j] = v;
         }
     }
-}
-
-// part[chunk][c] = sum over the chunk's rows of X[row][c]   (summed by k_reduce_net)
-__global__ void k_colsum(const float* __restrict__ X, int ld, int M, int n, int chunk, float* __restrict__ part) {
-    __shared__ float red[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, ch = blockIdx.y;
-    const int rbeg = ch * chunk, rend = min(M, rbeg + chunk);
-    float s = 0.0f;
-    if (c < n)
-        for (int row = rbeg + g; row < rend; row += 4) s += X[(size_t)row * ld + c];
-    red[g][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (g == 0 && c < n) part[(size_t)ch * n + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

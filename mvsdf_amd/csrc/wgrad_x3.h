@@ -3,54 +3,34 @@
 // (mv_split_pk<3>: p = p0 + p1 + p2 exactly; no flush, as in the chains), a product the six exact term products p_s q_j, s + j <= 2, of
 // v_mfma_f32_16x16x32_bf16 accumulated in fp32.  The contraction runs over ROWS, 32 per instruction.
 //
-// Same chunks (MV_WG_CHUNK rows), same slabs, same k_reduce_net, same device-count form, same column-sum workgroups and fp32 bias sums as k_wgrad_net; what
-// differs:
+// The form WG_X3 of the skeleton in layer_kernels.h (block decode, stage loop, slab store, column-sum workgroups, fp32 bias sums); its own:
 //   * workgroup = (layer, chunk, 128 x 128 output block), 8 waves, wave (wo, wi) = (w >> 1, w & 1) owns the 2 x 4 accumulator tiles of output rows
 //     32 wo .. + 31 and columns 64 wi .. + 63: a quarter of k_wgrad_net's blocks, half its operand re-reads and half the split work per product;
 //   * operands are loaded with lane <-> COLUMN: thread (col, g) = (tid & 127, tid >> 7) reads the 8 consecutive rows 8 g .. 8 g + 7 of its column with dword
-//     loads (a wave-instruction is 256 contiguous bytes of one row), so leading dimensions and row windows need no alignment and there is ONE path.  Rows
+//     loads (a wave-instruction is 256 contiguous bytes of one row), so leading dimensions and row windows need no alignment and there is ONE staging.  Rows
 //     beyond the chunk's end and columns beyond the layer's are CLAMPED to a valid element when read and enter as zero terms (never a padded value times zero);
 //   * each element is split ONCE per workgroup, in registers, and its 8 rows x 3 terms go to LDS as three 16-byte pieces: the matrix instruction wants, per
 //     lane (q, r), rows 8 q .. 8 q + 7 of column r.  LDS image per operand and term: [g][col] pieces (48 KiB in all) -- the 16 lanes of a ds_read_b128 group
 //     read 256 contiguous bytes, the 8 lanes of a ds_write_b128 group write 128: both free of bank conflicts;
-//   * one stage = MV_WGX_STAGE = 32 rows = one matrix instruction's contraction; the operands of stage s + 1 are requested into registers before the matrix
-//     instructions of stage s and split + written after them (k_wgrad_net's scheme).
+//   * one stage = 32 rows = one matrix instruction's contraction.
 // Measured on one MI355X (profiles/wgrad_x3_ab.txt): c2 90.8 -> 52.2 us, c3 272.5 -> 176.3 us, the 8x512 shipped step 4.17 -> 2.49 ms per launch.
 // Measured and NOT kept:
 //   * all twelve Q fragments of a stage in registers at once (130 VGPRs: one workgroup per CU instead of two) -- not run: the form below needs 106;
 //   * TWO stages requested ahead in two register sets (126 VGPRs, still two workgroups per CU): 55.2 vs 53.5 us at c2, 188.8 vs 183.9 us at c3 in one job --
 //     the exposed load latency is not what bounds the kernel (as k_wgrad_net found).
 // Not measured yet: ds_read_b64_tr_b16 on row-major term tiles, 64-row stages, other tiles than 128 x 128.
-// The XCD-aware block order takes runs of MV_WGX_RUN = 4 logical blocks (the four output blocks of one 256 x 256 layer and chunk share their operand rows).
 #pragma once
 #include "layer_kernels.h"
 #include "tile_engine_bf16s.h"
 
-#define MV_WGX_TILE 128                    // output block: 128 x 128
-#define MV_WGX_STAGE 32                    // rows per stage
-#define MV_WGX_THREADS 512
-#define MV_WGX_RUN 4                       // consecutive logical blocks per XCD run
-
-__global__ __launch_bounds__(MV_WGX_THREADS, 2) void k_wgrad_net_x3(WgradNetArgs a) {
-    __shared__ __attribute__((aligned(16))) uint4 T[2][3][4][MV_WGX_TILE];        // [P | Q][term][row group g][column]: rows 8 g .. 8 g + 7 of the column, one term
-    int bid = blockIdx.x;
-    if (a.xcd_runs) {
-        // workgroup b = 8 i + x runs on XCD x  ->  logical block ((i / RUN) * 8 + x) * RUN + i % RUN   (the grid is padded to a multiple of 8 RUN)
-        const int x = bid & 7, i = bid >> 3;
-        bid = (((i / MV_WGX_RUN) << 3) + x) * MV_WGX_RUN + (i % MV_WGX_RUN);
-        if (bid >= a.nblocks) return;
-    }
-    if (a.colX && bid >= a.col_blk0) { mv_colsum_block(a, bid - a.col_blk0, (float*)T); return; }
+__global__ __launch_bounds__(WG_X3.THREADS, 2) void k_wgrad_net_x3(WgradNetArgs a) {
+    constexpr int TILE = WG_X3.TILE, STAGE = WG_X3.STAGE;
+    __shared__ __attribute__((aligned(16))) uint4 T[2][3][4][TILE];               // [P | Q][term][row group g][column]: rows 8 g .. 8 g + 7 of the column, one term
+    WgBlock b;
+    if (!mv_wg_decode<WG_X3.RUN>(a, (float*)T, b)) return;
+    const WgradLayer& L = a.L[b.l];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
-    int l = 0;
-    while (l + 1 < a.n_layers && bid >= a.L[l + 1].blk0) ++l;
-    const WgradLayer& L = a.L[l];
-    const int local = bid - L.blk0, nb = L.nbx * L.nby;
-    const int chl = local / nb, rem = local - chl * nb, by = rem / L.nbx, bx = rem - by * L.nbx;
-    const int ch = L.ch0 + chl;
-    const int i0 = bx * MV_WGX_TILE, o0 = by * MV_WGX_TILE, No = L.No, Ki = L.Ki;
-    const int rbeg = ch * a.chunk, rend = min(mv_wg_rows(a, L), rbeg + a.chunk);
-    if (rbeg >= rend && a.cnt) return;                            // (deferred step: a chunk beyond the true rows; k_reduce_net does not read its slab)
+    const int i0 = b.bx * TILE, o0 = b.by * TILE, No = L.No, Ki = L.Ki, rbeg = b.rbeg, rend = b.rend;
     const int wo = w >> 1, wi = w & 1;
     f32x4 acc[2][4];
 #pragma unroll
@@ -58,50 +38,48 @@ __global__ __launch_bounds__(MV_WGX_THREADS, 2) void k_wgrad_net_x3(WgradNetArgs
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsum = 0.0f;
-    const bool do_bias = bx == 0;
-    const int npairs = L.P2 ? 2 : 1;
-    const int nrb = rend > rbeg ? (rend - rbeg + MV_WGX_STAGE - 1) / MV_WGX_STAGE : 0, nst = npairs * nrb;
+    const bool do_bias = b.bx == 0;
+    CH_PH_DECL
+    const int nrb = rend > rbeg ? (rend - rbeg + STAGE - 1) / STAGE : 0, nst = (L.P2 ? 2 : 1) * nrb;
     // staging role: column scol of both operand tiles, rows 8 sg .. 8 sg + 7 of the stage
-    const int scol = tid & (MV_WGX_TILE - 1), sg = tid >> 7;
+    const int scol = tid & (TILE - 1), sg = tid >> 7;
     const bool p_in = o0 + scol < No, q_in = i0 + scol < Ki;
     const int pc = min(o0 + scol, No - 1), qc = min(i0 + scol, Ki - 1);
     // a wave whose 32 x 64 corner lies outside the layer has no products to form (it still stages)
     const bool wave_on = o0 + 32 * wo < No && i0 + 64 * wi < Ki;
     float pv[8], qv[8];
     auto issue = [&](int st) {
-        const int pair = st >= nrb ? 1 : 0, rb = rbeg + (st - pair * nrb) * MV_WGX_STAGE + 8 * sg;
-        const float* P = (pair ? L.P2 : L.P1) + pc;
-        const float* Q = (pair ? L.Q2 : L.Q1) + qc;
-        const int ldp = pair ? L.ldp2 : L.ldp1, ldq = pair ? L.ldq2 : L.ldq1;
+        const WgOperands s = mv_wg_operands(L, st, nrb, rbeg, STAGE);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int row = min(rb + e, rend - 1);                // unconditional, clamped: a load inside a branch cannot stay in flight across the matrix loop
-            pv[e] = P[(size_t)row * ldp];
-            qv[e] = Q[(size_t)row * ldq];
+            const int row = min(s.rb + 8 * sg + e, rend - 1);
+            pv[e] = s.P[(size_t)row * s.ldp + pc];
+            qv[e] = s.Q[(size_t)row * s.ldq + qc];
         }
     };
     auto store = [&](int st) {
-        const int pair = st >= nrb ? 1 : 0, rb = rbeg + (st - pair * nrb) * MV_WGX_STAGE + 8 * sg;
+        const WgOperands s = mv_wg_operands(L, st, nrb, rbeg, STAGE);
+        const int rb = s.rb + 8 * sg;
         uint32_t tp[3][4], tq[3][4];
 #pragma unroll
         for (int e = 0; e < 8; e += 2) {
             const bool in0 = rb + e < rend, in1 = rb + e + 1 < rend;
             const dm_f2 hp = dm_f2{(p_in && in0) ? pv[e] : 0.0f, (p_in && in1) ? pv[e + 1] : 0.0f};
             const dm_f2 hq = dm_f2{(q_in && in0) ? qv[e] : 0.0f, (q_in && in1) ? qv[e + 1] : 0.0f};
-            if (do_bias && pair == 0) bsum += hp.x + hp.y;
+            if (do_bias && s.pair == 0) bsum += hp.x + hp.y;
             uint32_t sp[3], sq[3];
             mv_split_pk<3>(hp, sp);
             mv_split_pk<3>(hq, sq);
 #pragma unroll
-            for (int s = 0; s < 3; ++s) { tp[s][e >> 1] = sp[s]; tq[s][e >> 1] = sq[s]; }
+            for (int t = 0; t < 3; ++t) { tp[t][e >> 1] = sp[t]; tq[t][e >> 1] = sq[t]; }
         }
 #pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            T[0][s][sg][scol] = uint4{tp[s][0], tp[s][1], tp[s][2], tp[s][3]};
-            T[1][s][sg][scol] = uint4{tq[s][0], tq[s][1], tq[s][2], tq[s][3]};
+        for (int t = 0; t < 3; ++t) {
+            T[0][t][sg][scol] = uint4{tp[t][0], tp[t][1], tp[t][2], tp[t][3]};
+            T[1][t][sg][scol] = uint4{tq[t][0], tq[t][1], tq[t][2], tq[t][3]};
         }
     };
-    auto compute = [&]() {
+    auto compute = [&](int) {
         if (!wave_on) return;
         // the P fragments of both row tiles stay in registers; the Q fragments of one column tile at a time (all of them at once: 130 VGPRs, one workgroup per CU)
         mv_bf8 pa[2][3];
@@ -123,41 +101,17 @@ __global__ __launch_bounds__(MV_WGX_THREADS, 2) void k_wgrad_net_x3(WgradNetArgs
                     for (int m = 0; m < 2; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[m][s], qb[o - s], acc[m][t], 0, 0, 0);
         }
     };
-    if (nst > 0) {
-        issue(0);
-        for (int st = 0; st + 1 < nst; ++st) {
-            __syncthreads();
-            store(st);
-            __syncthreads();
-            issue(st + 1);
-            compute();
-        }
-        __syncthreads();
-        store(nst - 1);
-        __syncthreads();
-        compute();
-    }
-    // accumulator layout as in k_wgrad_net: lane (q, r) holds output rows 4 q .. 4 q + 3 of column r of each 16 x 16 tile
-    float* slab = L.slab + (size_t)ch * No * Ki;
+    mv_wg_pipeline(nst, chp_, issue, store, compute);
+    float* slab = L.slab + (size_t)b.ch * No * Ki;
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int i = i0 + 64 * wi + 16 * t + r;
-            if (i < Ki) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int o = o0 + 32 * wo + 16 * m + 4 * q + e;
-                    if (o < No) slab[(size_t)o * Ki + i] = acc[m][t][e];
-                }
-            }
-        }
+        for (int t = 0; t < 4; ++t) mv_wg_slab_store(slab, acc[m][t], o0 + 32 * wo + 16 * m + 4 * q, i0 + 64 * wi + 16 * t + r, No, Ki);
     if (do_bias) {                                                // bias sums: plain fp32, the four row groups of a column added in a fixed order
         float* red = (float*)T;
         __syncthreads();
-        red[sg * MV_WGX_TILE + scol] = bsum;
+        red[sg * TILE + scol] = bsum;
         __syncthreads();
-        if (tid < MV_WGX_TILE && o0 + tid < No)
-            L.bslab[(size_t)ch * No + o0 + tid] = (red[tid] + red[MV_WGX_TILE + tid]) + (red[2 * MV_WGX_TILE + tid] + red[3 * MV_WGX_TILE + tid]);
+        if (tid < TILE && o0 + tid < No) L.bslab[(size_t)b.ch * No + o0 + tid] = (red[tid] + red[TILE + tid]) + (red[2 * TILE + tid] + red[3 * TILE + tid]);
     }
 }

@@ -41,10 +41,11 @@ print('%-34s' % 'phase' + ''.join('  w%-4d' % w for w in (0, 1, 4, 5, 8, 12, 15)
 for i, nm in enumerate(names):
     print('%-34s' % nm + ''.join(' %6.2f' % a[w, i] for w in (0, 1, 4, 5, 8, 12, 15)) + '   %6.2f' % a[:, i].max())
 print('%-34s' % 'sum' + ''.join(' %6.2f' % a[w, :13].sum() for w in (0, 1, 4, 5, 8, 12, 15)))
-wn = ['MFMA loop (+ loop back)', 'wait: tiles free', 'stage P, Q (global -> LDS)', 'wait: tiles staged', 'bias sum', 'last MFMA loop', 'slab store']
+# marks 1-4: mv_wg_pipeline (layer_kernels.h), once per stage; 5, 6: the kernel's end
+wn = {1: 'wait: tiles free (+ first request)', 2: 'store: registers -> LDS', 3: 'wait: tiles staged', 4: 'request next stage + MFMA loop', 5: 'pipeline end', 6: 'slab store'}
 print('k_wgrad_net, one 64 x 64 block of a 256 x 256 layer (256 rows, two operand pairs = 8 stages), us per launch')
 print('%-34s' % 'phase' + ''.join('  w%-4d' % w for w in range(4)))
-for i, nm in enumerate(wn):
+for i, nm in wn.items():
     print('%-34s' % nm + ''.join(' %6.2f' % a[8 + w, i] for w in range(4)))
-print('%-34s' % 'sum' + ''.join(' %6.2f' % a[8 + w, :7].sum() for w in range(4)))
+print('%-34s' % 'sum' + ''.join(' %6.2f' % a[8 + w, 1:7].sum() for w in range(4)))
 
