@@ -925,7 +925,10 @@ enum {
     MVSDF_PS_ERR_SHAPE = 8,     /* V < 1, R or S < 2, C < 1, R*S > INT32_MAX, R*S*D or V*R*S*C > 2^40, more than MVSDF_PS_MAX_SRC sources for a view */
     MVSDF_PS_ERR_SGM = 16,      /* the regularisation's p1, p2 or paths refused, or a hypothesis count above MVSDF_PS_MAX_D_SGM */
     MVSDF_PS_ERR_BAND = 32,     /* the band's depth_num outside [1, MVSDF_PS_MAX_D_BAND], a step that is not finite and positive, a view listed twice */
-    MVSDF_PS_ERR_CENTRE = 64    /* an infinite centre (found on the device) */
+    MVSDF_PS_ERR_CENTRE = 64,   /* an infinite centre (found on the device) */
+    MVSDF_PS_ERR_CODE = 128,    /* keypoints: a descriptor code outside 0 .. 127 */
+    MVSDF_PS_ERR_INDEX = 256,   /* keypoints: a keypoint index outside its view, or offsets that do not ascend */
+    MVSDF_PS_ERR_ROUNDS = 512   /* keypoints: the round limit of the track labelling was reached */
 };
 enum {
     MVSDF_PS_MAX_D = 65535,     /* hypotheses of a sweep */
@@ -1326,6 +1329,81 @@ int mvsdf_greg_match(const int8_t* src, int64_t ns, const int8_t* dst, int64_t n
 size_t mvsdf_greg_ransac_workspace_bytes(int64_t m, int64_t hypotheses);
 int mvsdf_greg_ransac(const double* src, int64_t ns, const double* dst, int64_t nd, const int32_t* corr, int64_t m, int64_t hypotheses, uint64_t seed,
                       double edge_ratio, double max_dist, void* ws, size_t ws_bytes, uint8_t* mask, void* stream);
+
+/* ---- Sparse points from posed images (keypoints.hip; Python: mvsdf_amd/keypoints.py, which states the definition) ----
+ * Keypoints of V views (1 <= V <= MVSDF_VS_MAX_VIEWS) lie one view after the other: view v owns the rows view_off[v] .. view_off[v + 1] of xy fp64 [N][2]
+ * and codes int8 [N][MVSDF_KP_DIM] (codes in 0 .. 127), N = view_off[V] <= MVSDF_KP_MAX_KEYPOINTS per view and INT32_MAX in all.  Error bits: MVSDF_PS_ERR_FINITE (a
+ * coordinate or matrix entry), _PAIR (a view index), _SHAPE (a count outside the limits: nothing is launched), _CODE, _INDEX and _ROUNDS.  Every workspace
+ * starts with MVSDF_RES_H_* (COUNT: the rows written) unless another block is named; outputs are sized by the caller for the largest possible result.
+ * mvsdf_kp_match: view_off int64 [V + 1] and pairs int32 [M][2] (views a < b, 1 <= M <= MVSDF_KP_MAX_PAIRS) are HOST arrays.  For every pair and every
+ * keypoint i of view a: the nearest (j1, D1) and the second distance D2 over the keypoints of view b under (D, j), D = the squared code difference,
+ * on the int8 matrix cores (both directions of every pair in one launch); kept iff (no D2 or fp64(D1) < ratio2 * fp64(D2)) and D1 <= max_dist and
+ * (no mutual or the search from b sends j1 back to i).  off int64 [M + 1], idx int32 [cap][2], dist int32 [cap] with cap = the sum over the pairs of
+ * view a's keypoints; kept matches by i ascending.  Waits for the stream once (its tables travel from the host).  mvsdf_kp_match_splits: over how many
+ * workgroups the walk over a view's targets is split at these sizes.
+ * mvsdf_kp_verify: everything on the device: pairs int32 [M][2], off int64 [M + 1], idx int32 [E][2], dist int32 [E] (E = off[M] >= 1), F fp64 [M][9] (row-major,
+ * x_b^T F x_a = 0).  A match is kept iff both point-line distances are <= max_epipolar.  Outputs as mvsdf_kp_match's, cap = E.  No host wait.
+ * mvsdf_kp_tracks: nodes = the N keypoints, edges = the E matches (same arrays as mvsdf_kp_verify's inputs); components by minimum-label rounds, at
+ * most max_rounds of them (the host reads a flag every MVSDF_KP_ROUND_BATCH rounds: MVSDF_PS_ERR_ROUNDS); a component with two keypoints of one view
+ * is dropped.  track_off int64 [N / 2 + 1], track_view and track_kp int32 [N] -> MVSDF_KP_TRACKS_H_*.
+ * mvsdf_kp_triangulate: per-view fp64 arrays on the device: centers [V][3], rays [V][9] (R^T K^-1, row-major), proj [V][12] (K [R | t]).  One lane per
+ * track -> xyz fp64 [T][3], error fp64 [T], keep uint8 [T], obs_keep uint8 [nnz].  hdr: 256 device bytes, MVSDF_ERRW_H_*, zeroed by the call.  No host wait. */
+enum {
+    MVSDF_KP_DIM = 128,                 /* codes of a descriptor */
+    MVSDF_KP_MAX_KEYPOINTS = 1 << 20,   /* keypoints of one view */
+    MVSDF_KP_MAX_PAIRS = 32767,         /* view pairs of one matcher call: both directions ride on one grid axis */
+    MVSDF_KP_MAX_DIST = 2064512,        /* 128 * 127 * 127: the largest squared code difference */
+    MVSDF_KP_ROUND_BATCH = 4            /* labelling rounds per host check */
+};
+enum {
+    MVSDF_KP_TRACKS_H_TRACKS = 0,       /* tracks written */
+    MVSDF_KP_TRACKS_H_ENTRIES = 1,      /* their entries */
+    MVSDF_KP_TRACKS_H_ERR = 2,          /* error bits */
+    MVSDF_KP_TRACKS_H_ROUNDS = 3,       /* labelling rounds run */
+    MVSDF_KP_TRACKS_H_WORDS = 4
+};
+size_t mvsdf_kp_match_workspace_bytes(const int64_t* view_off, int64_t V, const int32_t* pairs, int64_t M);
+int32_t mvsdf_kp_match_splits(const int64_t* view_off, int64_t V, const int32_t* pairs, int64_t M);
+int mvsdf_kp_match(const int8_t* codes, const int64_t* view_off, int64_t V, const int32_t* pairs, int64_t M, double ratio2, int32_t max_dist,
+                   int32_t mutual, void* ws, size_t ws_bytes, int64_t* off, int32_t* idx, int32_t* dist, void* stream);
+size_t mvsdf_kp_verify_workspace_bytes(int64_t E);
+int mvsdf_kp_verify(const double* xy, const int64_t* view_off, int64_t V, const int32_t* pairs, int64_t M, const int64_t* off, const int32_t* idx,
+                    const int32_t* dist, int64_t E, const double* F, double max_epipolar, void* ws, size_t ws_bytes, int64_t* off_out,
+                    int32_t* idx_out, int32_t* dist_out, void* stream);
+size_t mvsdf_kp_tracks_workspace_bytes(int64_t N, int64_t E);
+int mvsdf_kp_tracks(const int64_t* view_off, int64_t V, int64_t N, const int32_t* pairs, int64_t M, const int64_t* off, const int32_t* idx, int64_t E,
+                    int32_t max_rounds, void* ws, size_t ws_bytes, int64_t* track_off, int32_t* track_view, int32_t* track_kp, void* stream);
+/* The detector: scale space, extrema, orientation and descriptor (Python composes them: keypoints.detect).  All arrays on the device.  mvsdf_kp_grey: n pixels of `channels` (1 or 3) uint8
+ * (is_float == 0) or fp32 values -> fp64 grey, (299 R + 587 G + 114 B) / 1000 (integers for uint8, ((299 R + 587 G) + 114 B) / 1000 in fp64 for fp32), one
+ * channel as it is.  mvsdf_kp_blur: planes x [h][w] fp64 -> dst, separable, rows first then columns, every sum from 0.0 over taps[0 .. 2 radius] left
+ * to right with clamped borders (0 <= radius <= MVSDF_KP_MAX_RADIUS; tmp: as large as src; dst may be src).  mvsdf_kp_half: every second pixel,
+ * [h][w] -> [(h + 1) / 2][(w + 1) / 2].  mvsdf_kp_dog: L [planes][levels][hw] -> D [planes][levels - 1][hw], D_s = L_(s+1) - L_s.  No host wait. */
+/* mvsdf_kp_extrema: D fp64 [V][5][h][w] (mvsdf_kp_dog of six levels) -> the refined extrema of levels s = 1 .. 3 at least `border` (>= 1) pixels from the
+ * edges, in the order (view, level, y, x): cand int32 [cap][4] = (view, level, y, x), out fp64 [cap][4] = (X, Y, scale, response) with X = ((x + off_x)
+ * + 0.5) * step, scale = sigma[level - 1] * step (sigma: three HOST doubles).  Workspace: mvsdf_kp_extrema_workspace_bytes(V, h, w) (0 beyond 2^31 - 1
+ * sites) -> MVSDF_RES_H_* (COUNT: the extrema found; more than cap: MVSDF_PS_ERR_SHAPE and only cap are written).  No host wait. */
+enum { MVSDF_KP_MAX_RADIUS = 64 };
+size_t mvsdf_kp_extrema_workspace_bytes(int64_t V, int64_t h, int64_t w);
+int mvsdf_kp_extrema(const double* D, int64_t V, int64_t h, int64_t w, double contrast, double edge_ratio, int32_t border, double step,
+                     const double* sigma, int64_t cap, void* ws, size_t ws_bytes, int32_t* cand, double* out, void* stream);
+int mvsdf_kp_grey(const void* images, int32_t is_float, int32_t channels, int64_t n, double* out, void* stream);
+int mvsdf_kp_blur(const double* src, int64_t planes, int64_t h, int64_t w, const double* taps, int32_t radius, double* tmp, double* dst, void* stream);
+int mvsdf_kp_half(const double* src, int64_t planes, int64_t h, int64_t w, double* dst, void* stream);
+int mvsdf_kp_dog(const double* L, int64_t planes, int64_t levels, int64_t hw, double* D, void* stream);
+/* mvsdf_kp_describe: L fp64 [V][6][h][w] of one octave, cand int32 [n][4] = (view, level 1 .. 3, y, x) as mvsdf_kp_extrema writes them -> angle fp64 [n]
+ * (radians in [0, 2 pi); 0 with upright != 0), codes int8 [n][128] and valid uint8 [n] (0: an all-zero descriptor or a site outside the level).
+ * HOST arrays of 3 (levels 1 .. 3): cell = the descriptor's cell width, radius = its window radius, ogauss = 1 / (2 sigma_w^2) of the orientation
+ * window, oradius = its radius (radii <= 4 MVSDF_KP_MAX_RADIUS).  trig: DEVICE fp64 [MVSDF_KP_TRIG_WORDS], the coefficients of the sine (14) and
+ * cosine (15) polynomials in ascending order.  acc: int64 [n][128] device scratch.  Histogram entries and votes are quantised to 2^-32 and summed as
+ * integers.  No host wait. */
+enum { MVSDF_KP_TRIG_WORDS = 29 };
+int mvsdf_kp_describe(const double* L, int64_t V, int64_t h, int64_t w, const int32_t* cand, int64_t n, int32_t upright, const double* cell,
+                      const int32_t* radius, const double* ogauss, const int32_t* oradius, const double* trig, int64_t* acc, double* angle,
+                      int8_t* codes, uint8_t* valid, void* stream);
+int mvsdf_kp_triangulate(const double* xy, const int64_t* view_off, int64_t V, const int64_t* track_off, const int32_t* track_view,
+                         const int32_t* track_kp, int64_t T, int64_t nnz, const double* centers, const double* rays, const double* proj,
+                         double max_reproj, double cos_min_angle, double* xyz, double* error, uint8_t* keep, uint8_t* obs_keep, void* hdr,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 """COLMAP sparse models as MVS input: load_colmap_model reads a model directory (text, else binary; numpy only) and colmap_to_mvs writes what
 stereo.estimate_scene, tools/fusion.py and tools/vismvsnet2mvsdf.py start from -- images/<i:08>.jpg|png, cams/<i:08>_cam.txt with depth ranges and
-pair.txt -- with the view scores and depth ranges computed on the device (mvsdf_amd/viewsel.py).
+pair.txt -- with the view scores and depth ranges computed on the device (mvsdf_amd/viewsel.py).  A model that has poses but no (or unwanted)
+points3D is served by colmap_to_mvs(..., triangulate=True): the points then come from the images themselves (mvsdf_amd/keypoints.py).
 
 The file formats are COLMAP's documented ones.  Text: `#` lines are comments; cameras.txt `CAMERA_ID MODEL WIDTH HEIGHT PARAMS...`; images.txt two
 lines per image, `IMAGE_ID QW QX QY QZ TX TY TZ CAMERA_ID NAME` and `X Y POINT3D_ID ...` (which may be empty); points3D.txt `POINT3D_ID X Y Z R G B
@@ -235,14 +236,15 @@ def model_views(model):
 
 
 def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, num_pairs=10, theta0=5, sigma1=1, sigma2=10, undistort=False,
-                  blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
+                  blank_pixels=0.0, min_scale=0.2, max_scale=2.0, triangulate=False):
     """A COLMAP model and its (undistorted) images -> out_root/images/<i:08>.jpg|png (jpg and png copied as they are, other formats re-encoded as png),
     out_root/cams/<i:08>_cam.txt (extrinsic, intrinsic, `depth_min interval max_d depth_max` with interval = (depth_max - depth_min) / (max_d - 1) /
     interval_scale, from viewsel.depth_ranges) and out_root/pair.txt (viewsel.view_scores + select_pairs over the model's tracks).  max_d = 0, the
     automatic hypothesis count of MVSNet's script, is not built.  undistort=True takes a model with distorted cameras (load_colmap_model's
     allow_distortion): every image is resampled on the device to its camera's pinhole view (undistort.undistorted_camera with blank_pixels, min_scale,
     max_scale) and written as png, and the camera files carry that view's intrinsics; pairs and depth ranges use points, centres and extrinsics only
-    and are what they are without it.  -> {'ids', 'names', 'cams' [V,2,4,4], 'pairs', 'pair_scores', 'scores', 'counts'}."""
+    and are what they are without it.  triangulate=True replaces the model's points (which may be empty) by keypoints.sparse_model's: keypoints,
+    matches and triangulated tracks from the images themselves (pinhole images only: undistort first).  -> {'ids', 'names', 'cams' [V,2,4,4], 'pairs', 'pair_scores', 'scores', 'counts'}."""
     from .. import viewsel
     from ..stereo import _write_cam
     what = 'colmap_to_mvs'
@@ -251,7 +253,12 @@ def colmap_to_mvs(model_dir, image_dir, out_root, max_d=256, interval_scale=1, n
         raise ValueError('%s: max_d must be >= 2 (max_d = 0, the automatic hypothesis count, is not built), got %d' % (what, max_d))
     if not float(interval_scale) > 0:
         raise ValueError('%s: interval_scale must be > 0' % what)
+    if triangulate and undistort:
+        raise ValueError('%s: triangulate needs pinhole images: run tools/undistort.py first, then triangulate its output' % what)
     model = load_colmap_model(model_dir, allow_distortion=bool(undistort))
+    if triangulate:
+        from ..keypoints import sparse_model
+        model = sparse_model(model, image_dir)
     if undistort:
         from .. import undistort as und
         source_cameras = model['cameras']

@@ -1,6 +1,7 @@
 """View selection on the device: the pairwise view score behind MVSNet-style pair.txt files, the per-view depth ranges of the camera files, and
-the pair lists chosen from them -- what the reference's BYOD.md supposes to exist ("Suppose you have the camera files and the view selection
-file").  Kernels: csrc/viewsel.hip (the design: DESIGN.md); tests/viewsel_ref.py restates every step in numpy.  The score is the well-known one of
+the pair lists chosen from them -- what the reference's BYOD.md supposes to exist.  The points and tracks it reads come from a COLMAP model, or,
+for posed images without one, from keypoints.py (keypoints, matching, verification, tracks and triangulation: keypoints.sparse_points, or
+tools/sparse_points.py, which also writes pair.txt and the camera files).  Kernels: csrc/viewsel.hip (the design: DESIGN.md); tests/viewsel_ref.py restates every step in numpy.  The score is the well-known one of
 MVSNet's colmap2mvsnet.py (a Gaussian of the triangulation angle, summed over the common points); that script's text is not available to this
 project and the reference has no counterpart, so the definition below is this project's own statement of it and no agreement beyond the formula
 is claimed.
