@@ -928,7 +928,8 @@ enum {
     MVSDF_PS_ERR_CENTRE = 64,   /* an infinite centre (found on the device) */
     MVSDF_PS_ERR_CODE = 128,    /* keypoints: a descriptor code outside 0 .. 127 */
     MVSDF_PS_ERR_INDEX = 256,   /* keypoints: a keypoint index outside its view, or offsets that do not ascend */
-    MVSDF_PS_ERR_ROUNDS = 512   /* keypoints: the round limit of the track labelling was reached */
+    MVSDF_PS_ERR_ROUNDS = 512,  /* keypoints: the round limit of the track labelling was reached */
+    MVSDF_PS_ERR_BEHIND = 1024  /* bundle adjustment: an active observation's point lies behind its camera (q2 <= 0) at the initial parameters */
 };
 enum {
     MVSDF_PS_MAX_D = 65535,     /* hypotheses of a sweep */
@@ -1404,6 +1405,57 @@ int mvsdf_kp_triangulate(const double* xy, const int64_t* view_off, int64_t V, c
                          const int32_t* track_kp, int64_t T, int64_t nnz, const double* centers, const double* rays, const double* proj,
                          double max_reproj, double cos_min_angle, double* xyz, double* error, uint8_t* keep, uint8_t* obs_keep, void* hdr,
                          void* stream);
+
+/* ---- Bundle adjustment (bundle.hip; Python: mvsdf_amd/bundle.py, which states the definition) ----
+ * Levenberg-Marquardt over the poses of V views (1 <= V <= MVSDF_BA_MAX_VIEWS: the 6 V unknowns of the reduced system fill one chunk of the sum tree) and P
+ * points (1 <= P <= INT32_MAX) with nnz observations (1 <= nnz <= MVSDF_BA_MAX_OBS), the points eliminated and the reduced system solved by
+ * preconditioned conjugate gradients.  All arrays on the device, fp64 unless named: pose [V][12] (R row-major, then t), intr [V][5] (fx, s, cx, fy, cy),
+ * xyz [P][3], track_off int64 [P + 1], track_view int32 [nnz], obs fp64 [nnz][2], fixed uint8 [V] (non-zero: the pose stays), rod [MVSDF_BA_ROD_WORDS]
+ * (the coefficients of sin t / t and (1 - cos t) / t^2 in t^2, ascending, MVSDF_BA_ROD_TERMS each, valid for t <= MVSDF_BA_MAX_THETA radians).
+ * The workspace (mvsdf_ba_workspace_bytes; 0 outside the limits) starts with MVSDF_BA_H_*.  Error bits: MVSDF_PS_ERR_SHAPE (a count outside the limits:
+ * nothing is launched), _FINITE, _INDEX (offsets that do not ascend from 0 to nnz, a view index outside [0, V)) and _BEHIND; with any set the
+ * remaining launches return at once.  No call waits for the stream.
+ * mvsdf_ba_residuals: r [nnz][2] (unweighted; 0 for an inactive observation), terms [nnz] (robust cost terms; +inf behind a camera when trial != 0, else
+ * MVSDF_PS_ERR_BEHIND), the cost into MVSDF_BA_H_COST0 and _COST.  mvsdf_ba_blocks: linearises at the given parameters and leaves the workspace ready
+ * for the three calls below (which take the same V, P, nnz): U [V][36], gc [V][6], Vb [P][9], gp [P][3] undamped, bvec [V][6] the right-hand side at lambda.
+ * mvsdf_ba_schur: out [V][6] = S x.  mvsdf_ba_solve: b == NULL: the workspace's right-hand side; x [V][6]; the iterations into MVSDF_BA_H_CG.
+ * mvsdf_ba_step: the parameters after the step x [V][6] -> pose_out, xyz_out; a rotation beyond the bound sets MVSDF_BA_H_ITER to 1 (else 0) and
+ * copies the poses.  mvsdf_ba_adjust: `iterations` rounds -> pose_out, xyz_out, r [nnz][2], terms [nnz] and every header word. */
+enum {
+    MVSDF_BA_MAX_VIEWS = 341,           /* 6 * 341 <= 2048, one chunk of the sum tree */
+    MVSDF_BA_MAX_OBS = 1 << 22,         /* observations of one call: a view's sums take at most 2048 chunks */
+    MVSDF_BA_MAX_THETA = 1,             /* radians: the bound of a rotation step and of the polynomials' table */
+    MVSDF_BA_ROD_TERMS = 10,            /* terms of each polynomial */
+    MVSDF_BA_ROD_WORDS = 20,
+    MVSDF_BA_MAX_ITERATIONS = 1000,
+    MVSDF_BA_MAX_CG = 10000
+};
+enum {
+    MVSDF_BA_H_ERR = 0,                 /* error bits */
+    MVSDF_BA_H_ITER = 1,                /* iterations run (those before convergence) */
+    MVSDF_BA_H_ACCEPTED = 2,            /* steps accepted */
+    MVSDF_BA_H_CG = 3,                  /* conjugate-gradient iterations in total */
+    MVSDF_BA_H_COST0 = 4,               /* the initial cost, fp64 bits */
+    MVSDF_BA_H_COST = 5,                /* the final cost, fp64 bits */
+    MVSDF_BA_H_LAMBDA = 6,              /* the final damping, fp64 bits */
+    MVSDF_BA_H_WORDS = 7
+};
+size_t mvsdf_ba_workspace_bytes(int64_t V, int64_t P, int64_t nnz);
+int mvsdf_ba_residuals(const double* pose, const double* intr, const double* xyz, const int64_t* track_off, const int32_t* track_view, const double* obs,
+                       int64_t V, int64_t P, int64_t nnz, double loss_scale, int32_t trial, void* ws, size_t ws_bytes, double* r, double* terms,
+                       void* stream);
+int mvsdf_ba_blocks(const double* pose, const double* intr, const double* xyz, const int64_t* track_off, const int32_t* track_view, const double* obs,
+                    const uint8_t* fixed, int64_t V, int64_t P, int64_t nnz, double loss_scale, double lambda, double floor_diag, void* ws,
+                    size_t ws_bytes, double* U, double* gc, double* Vb, double* gp, double* bvec, void* stream);
+int mvsdf_ba_schur(int64_t V, int64_t P, int64_t nnz, void* ws, size_t ws_bytes, const double* x, double* out, void* stream);
+int mvsdf_ba_solve(int64_t V, int64_t P, int64_t nnz, const double* b, int32_t cg_iters, double cg_tol, void* ws, size_t ws_bytes, double* x,
+                   void* stream);
+int mvsdf_ba_step(int64_t V, int64_t P, int64_t nnz, const double* rod, void* ws, size_t ws_bytes, const double* x, double* pose_out,
+                  double* xyz_out, void* stream);
+int mvsdf_ba_adjust(const double* pose, const double* intr, const double* xyz, const int64_t* track_off, const int32_t* track_view, const double* obs,
+                    const uint8_t* fixed, int64_t V, int64_t P, int64_t nnz, const double* rod, double loss_scale, int32_t iterations, double lambda0,
+                    double lambda_min, double lambda_max, double floor_diag, int32_t cg_iters, double cg_tol, double ftol, void* ws, size_t ws_bytes,
+                    double* pose_out, double* xyz_out, double* r, double* terms, void* stream);
 
 #ifdef __cplusplus
 }

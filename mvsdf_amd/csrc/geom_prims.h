@@ -196,3 +196,28 @@ static __global__ __launch_bounds__(MV_THREADS) void k_any_nonfinite(const T* __
     for (long long i = (long long)blockIdx.x * MV_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MV_THREADS) bad = bad || !isfinite(f[i]);
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(word, bit);
 }
+
+// ================================================================ the canonical pairwise sum ================================================================
+// A sum over the canonical tree pads its terms with +0.0 to a power of two and adds adjacent pairs until one value is left, so the result depends on
+// neither the workgroup size nor the schedule.  One chunk of it: a workgroup of MV_THREADS lanes over MV_CHUNK values, lane t holding values
+// MV_ITEMS t .. MV_ITEMS t + MV_ITEMS - 1 in a[] (adjacent pairs in registers, then in LDS); every lane receives the sum.  Chunk sums are reduced the
+// same way (poisson.hip: the isovalue; bundle.hip: the sums over a view's observations, the cost, the solver's dot products).  sh: MV_THREADS doubles
+// of LDS, free to be reused at once by another call.
+__device__ __forceinline__ double mv_tree_chunk(double* a, double* sh) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int m = MV_ITEMS / 2; m; m >>= 1)
+#pragma unroll
+        for (int q = 0; q < m; ++q) a[q] = a[2 * q] + a[2 * q + 1];
+    __syncthreads();
+    sh[t] = a[0];
+    __syncthreads();
+    for (int m = MV_THREADS / 2; m; m >>= 1) {
+        double v = 0.0;
+        if (t < m) v = sh[2 * t] + sh[2 * t + 1];
+        __syncthreads();
+        if (t < m) sh[t] = v;
+        __syncthreads();
+    }
+    return sh[0];
+}

@@ -246,20 +246,9 @@ __global__ __launch_bounds__(PO_THREADS) void k_po_tree(const double* __restrict
     double a[PO_TREE_ITEMS];
 #pragma unroll
     for (int q = 0; q < PO_TREE_ITEMS; ++q) a[q] = base + q < n ? in[base + q] : 0.0;
-#pragma unroll
-    for (int m = PO_TREE_ITEMS / 2; m; m >>= 1)
-#pragma unroll
-        for (int q = 0; q < m; ++q) a[q] = a[2 * q] + a[2 * q + 1];
-    sh[t] = a[0];
-    __syncthreads();
-    for (int m = PO_THREADS / 2; m; m >>= 1) {
-        double v = 0.0;
-        if (t < m) v = sh[2 * t] + sh[2 * t + 1];
-        __syncthreads();
-        if (t < m) sh[t] = v;
-        __syncthreads();
-    }
-    if (t == 0) out[blockIdx.x] = sh[0];
+    static_assert(PO_THREADS == MV_THREADS && PO_TREE_ITEMS == MV_ITEMS, "k_po_tree reduces one chunk of geom_prims.h's tree");
+    const double v = mv_tree_chunk(a, sh);
+    if (t == 0) out[blockIdx.x] = v;
 }
 
 __global__ __launch_bounds__(PO_THREADS) void k_po_valid0(const double* __restrict__ density, long long n, double min_density, unsigned char* __restrict__ out) {

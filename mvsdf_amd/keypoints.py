@@ -102,7 +102,7 @@ after view.  The stages below read xy, codes and view_off only.
    load_colmap_model reads back the same bits.  datasets.colmap.colmap_to_mvs(..., triangulate=True) replaces the model's points by these before
    scores and ranges are computed (tools/colmap2mvs.py --triangulate); tools/sparse_points.py is the command.
 
-NOT BUILT.  Pose estimation (unposed images); bundle adjustment; guided matching that restricts candidates to the epipolar band inside the
+NOT BUILT.  Pose estimation (unposed images; bundle.py refines given poses: sparse_model(refine=True)); guided matching that restricts candidates to the epipolar band inside the
 matcher; several orientations per keypoint; an upsampled first octave; vocabulary-tree pair selection; a wave-per-keypoint descriptor kernel.
 
 ValueError before any launch: a dtype other than the one named (nothing is converted silently), a wrong shape, view offsets that do not ascend from
@@ -601,6 +601,14 @@ def sparse_points(images, cams, pairs=None, max_keypoints=8192, contrast=2.0, ed
     verified = verify_matches(kp, matches, c, max_epipolar)
     tracks = build_tracks(kp, verified)
     xyz, error, keep, obs_keep = triangulate_tracks(kp, tracks, c, max_reproj, min_angle)
+    if report is not None:
+        report.update(views=V, keypoints=int(kp.view_off[-1]), matches=int(matches.idx.shape[0]), verified=int(verified.idx.shape[0]),
+                      tracks=int(keep.shape[0]), points=int(keep.sum()))
+    return _kept(kp, tracks, xyz, error, keep, obs_keep, views)
+
+
+def _kept(kp, tracks, xyz, error, keep, obs_keep, views):
+    """the kept tracks with their kept observations, and the colour under each point's first observation -> SparsePoints"""
     dev = xyz.device
     track_off, track_view, track_kp = (t.to(dev) for t in tracks)
     T = keep.shape[0]
@@ -612,9 +620,6 @@ def sparse_points(images, cams, pairs=None, max_keypoints=8192, contrast=2.0, ed
     fv = tv[first].cpu().numpy() if len(first) else np.zeros(0, np.int64)
     fxy = kp.xy.to(dev)[kp.view_off.to(dev)[tv[first].long()] + tk[first].long()].cpu().numpy() if len(first) else np.zeros((0, 2))
     rgb = torch.from_numpy(_texels(views, fv, fxy)).to(dev)
-    if report is not None:
-        report.update(views=V, keypoints=int(kp.view_off[-1]), matches=int(matches.idx.shape[0]), verified=int(verified.idx.shape[0]),
-                      tracks=int(T), points=int(keep.sum()))
     return SparsePoints(xyz[keep], rgb, error[keep], off, tv, tk, kp)
 
 
@@ -639,8 +644,23 @@ def assemble_model(model, ids, xy, view_off, xyz, rgb, error, track_off, track_v
     return {'cameras': model['cameras'], 'images': images, 'points': points}
 
 
-def sparse_model(model, image_dir, report=None, **kw):
-    """definition 6 -> the model dict with observations, points and tracks from the images; kw: sparse_points' options"""
+def refine_points(sp, cams, images, max_reproj=2.0, min_angle=1.5, report=None, **options):
+    """bundle.bundle_adjust (options) over the cameras and the points of a SparsePoints, then stage 5 once more over its tracks with the refined
+    cameras, so that max_reproj and the angle test hold for the new poses -> (SparsePoints, cams fp64 numpy [V,2,4,4])"""
+    from . import bundle
+    tracks = (sp.track_off, sp.track_view, sp.track_kp)
+    res = bundle.bundle_adjust(cams, sp.xyz, sp.track_off, sp.track_view, bundle.observations(sp.keypoints, tracks), **options)
+    xyz, error, keep, obs_keep = triangulate_tracks(sp.keypoints, tracks, res.cams, max_reproj, min_angle)
+    if report is not None:
+        report.update(refine=dict(cost0=res.cost0, cost=res.cost, iterations=res.iterations, accepted=res.accepted,
+                                  cg_iterations=res.cg_iterations, points=int(keep.sum())))
+    views = [np.asarray(i.cpu() if isinstance(i, torch.Tensor) else i) for i in images]
+    return _kept(sp.keypoints, tracks, xyz, error, keep, obs_keep, views), res.cams
+
+
+def sparse_model(model, image_dir, report=None, refine=False, refine_options=None, **kw):
+    """definition 6 -> the model dict with observations, points and tracks from the images; kw: sparse_points' options.  refine=True: the cameras
+    and points then go through `refine_points` (refine_options: bundle.bundle_adjust's) and the images' q / t are the refined poses"""
     import os
     from PIL import Image
     from .datasets import colmap
@@ -656,5 +676,10 @@ def sparse_model(model, image_dir, report=None, **kw):
         with Image.open(path) as im:
             images.append(np.asarray(im.convert('RGB')))
     sp = sparse_points(images, cams, report=report, **kw)
+    if refine:
+        from . import bundle
+        sp, cams = refine_points(sp, cams, images, kw.get('max_reproj', 2.0), kw.get('min_angle', 1.5), report, **(refine_options or {}))
+        model = dict(model, images={iid: dict(model['images'][iid], q=bundle.quaternion(cams[i, 0, :3, :3]), t=cams[i, 0, :3, 3].copy())
+                                    for i, iid in enumerate(ids)})
     host = [t.cpu().numpy() for t in (sp.keypoints.xy, sp.keypoints.view_off, sp.xyz, sp.rgb, sp.error, sp.track_off, sp.track_view, sp.track_kp)]
     return assemble_model(model, ids, *host)

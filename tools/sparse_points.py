@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sparse points from posed images on the GPU (mvsdf_amd/keypoints.py: keypoints, int8 MFMA matching, epipolar verification, tracks, triangulation):
 
-    python tools/sparse_points.py MODEL_DIR IMAGE_DIR OUT_MODEL_DIR [--max_keypoints N --ratio R --max_epipolar E --max_reproj E --min_angle A --upright]
+    python tools/sparse_points.py MODEL_DIR IMAGE_DIR OUT_MODEL_DIR [--max_keypoints N --ratio R --max_epipolar E --max_reproj E --min_angle A --upright] [--refine]
     python tools/sparse_points.py --mvs_dir DIR --out OUT [--max_d 256 --interval_scale 1 --num_pairs 10] [the same options]
 
 The first form takes a COLMAP model (cameras / images / points3D as .txt or .bin, pinhole cameras, points3D may be empty) and the images it names,
@@ -9,7 +9,8 @@ and writes OUT_MODEL_DIR/cameras.txt, images.txt and points3D.txt with the keypo
 what tools/colmap2mvs.py and tools/estimate_normals.py --colmap take.  The second form is BYOD.md's "suppose you have the camera files and the view
 selection file" made into a command: DIR/images/<name>.jpg|png and DIR/cams/<name>_cam.txt (extrinsic and intrinsic; depth words are not needed)
 -> OUT/pair.txt and OUT/cams/<name>_cam.txt with `depth_min interval max_d depth_max` from the points (mvsdf_amd/viewsel.py).  DIR's own cams/ are
-never overwritten: OUT must be another directory.  Prints views, keypoints, matches, verified matches, tracks and points."""
+never overwritten: OUT must be another directory.  --refine (first form): the cameras and points then go through bundle adjustment
+(mvsdf_amd/bundle.py), the points are triangulated once more with the refined cameras and the written images carry the refined poses.  Prints views, keypoints, matches, verified matches, tracks and points."""
 import argparse
 import os
 import sys
@@ -30,6 +31,7 @@ def parser():
     p.add_argument('--max_reproj', type=float, default=2.0)
     p.add_argument('--min_angle', type=float, default=1.5)
     p.add_argument('--upright', action='store_true', help='no keypoint orientation (cameras that share their up direction)')
+    p.add_argument('--refine', action='store_true', help='bundle adjustment of the given poses and the points (first form only)')
     p.add_argument('--max_d', type=int, default=256, help='with --mvs_dir: depth hypotheses per view written into the camera files')
     p.add_argument('--interval_scale', type=float, default=1.0)
     p.add_argument('--num_pairs', type=int, default=10)
@@ -83,14 +85,18 @@ def main(argv=None):
     if a.mvs_dir is not None:
         if a.out is None or a.model_dir is not None:
             p.exit(1, 'sparse_points.py: --mvs_dir DIR goes with --out OUT and without positional arguments\n')
+        if a.refine:
+            p.exit(1, 'sparse_points.py: --refine goes with a COLMAP model (the camera files of --mvs_dir are never rewritten)\n')
         return from_mvs_dir(a, options)
     if a.model_dir is None or a.image_dir is None or a.out_model_dir is None:
         p.exit(1, 'sparse_points.py: MODEL_DIR IMAGE_DIR OUT_MODEL_DIR, or --mvs_dir DIR --out OUT\n')
     from mvsdf_amd import keypoints
     from mvsdf_amd.datasets.colmap import load_colmap_model, write_colmap_text
     rep = {}
-    model = keypoints.sparse_model(load_colmap_model(a.model_dir), a.image_dir, report=rep, **options)
+    model = keypoints.sparse_model(load_colmap_model(a.model_dir), a.image_dir, report=rep, **dict(options, **({'refine': True} if a.refine else {})))
     _report(rep)
+    if a.refine:
+        print('[sparse_points] refined: cost %(cost0).6g -> %(cost).6g in %(accepted)d accepted steps, %(points)d points' % rep['refine'])
     write_colmap_text(model, a.out_model_dir)
     return {'model': model, 'report': rep}
 
