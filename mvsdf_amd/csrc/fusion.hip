@@ -5,15 +5,15 @@
 // * k_fu_mask: masked depth of every pixel (fp32 compares against the probability thresholds).
 // * k_fu_fuse: one lane per reference pixel, the source loop inside.  The 4x4 transforms T_rs / T_sr are kernel data indexed by (view, source slot),
 //   the same for every lane of a workgroup, so they come through the scalar cache; the four source texels are plain gathers (the projection and the
-//   2x2 sample are geom_prims.h's mv_project_texel / mv_cell2, which tsdf.hip's integration uses too).  Writes counts, the
-//   fp32 fused depth, the fp64 fused depth (the emit pass back-projects at it) and a keep flag.
+//   2x2 sample are view_prims.h's mv_project_texel / mv_cell2, which tsdf.hip's integration uses too; the way back is its mv_project).  Writes
+//   counts, the fp32 fused depth, the fp64 fused depth (the emit pass back-projects at it) and a keep flag.
 // * an int64 exclusive scan of the keep flags over all views (geom_prims.h: mv_scan_blocks, i.e. k_scan_block_sum and k_scan_top); the emit pass ranks
 //   its own chunk (mv_chunk_rank), so no per-pixel offset is stored.  Points come out in (view, y, x) order.  No float atomics anywhere.
 // * k_fu_normals (fusion.py: depth_normals): one lane per fused point; the tangents are differences of back-projected neighbour texels of the fused
 //   depth map, never taken across a hole or a depth edge, their cross product is oriented towards the camera.
 //
 // Every argument is validated on the host before anything is launched: an error leaves {0, error bits} in the header and the device untouched.
-#include "geom_prims.h"
+#include "view_prims.h"
 
 #define FU_THREADS 256
 #define FU_HDR 256                                    // bytes at the start of the workspace: MVSDF_RES_H_*
@@ -85,10 +85,9 @@ __global__ __launch_bounds__(FU_THREADS) void k_fu_fuse(const float* __restrict_
             const double ds = c.bilinear();
             const double b0q = (pr.u + 0.5) * ds, b1q = (pr.v + 0.5) * ds;
             const double* __restrict__ B = T + 16;
-            const double b2 = mv_row4(B + 8, b0q, b1q, ds, 1.0);
-            if (!(b2 > 0.0)) continue;
-            const double ex = mv_row4(B, b0q, b1q, ds, 1.0) / b2 - X;
-            const double ey = mv_row4(B + 4, b0q, b1q, ds, 1.0) / b2 - Y;
+            double bx = 0.0, by = 0.0, b2;                                     // set: nothing is carried around the loop (view_prims.h: mv_project)
+            if (!mv_project(B, b0q, b1q, ds, bx, by, b2)) continue;
+            const double ex = bx - X, ey = by - Y;
             if (ex * ex + ey * ey < pix2 && fabs(b2 - d) < dep_thresh * d) {
                 ++n;
                 acc += b2;
@@ -213,9 +212,7 @@ int mvsdf_fusion_normals(const float* fused, int64_t V, int64_t H, int64_t W, co
     hipStream_t s = (hipStream_t)stream;
     long long err = 0;
     if (V < 1 || H < 2 || W < 2 || V > INT_MAX || H > INT_MAX || W > INT_MAX || H * W > INT_MAX || n < 1 || n > FU_MAX_PIXELS) err |= MVSDF_FU_ERR_SHAPE;
-    if (!(err & MVSDF_FU_ERR_SHAPE))
-        for (long long k = 0; k < V * FU_NM_ROW; ++k)
-            if (!isfinite(mats[k])) err |= MVSDF_FU_ERR_FINITE;
+    if (!(err & MVSDF_FU_ERR_SHAPE) && !mv_all_finite(mats, V * FU_NM_ROW)) err |= MVSDF_FU_ERR_FINITE;
     if (isnan(jump) || jump < 0.0) err |= MVSDF_FU_ERR_FINITE;
     if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < mvsdf_fusion_normals_workspace_bytes(V)) return mv_fail(-1, "mvsdf_fusion_normals: workspace too small (mvsdf_fusion_normals_workspace_bytes)");
@@ -257,9 +254,7 @@ int mvsdf_fusion_fuse(const float* depths, const float* probs, const float* pthr
     if (!(err & MVSDF_FU_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
             if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_FU_ERR_PAIR;
-        const long long nm = npairs * 32 + V * 16;
-        for (long long k = 0; k < nm; ++k)
-            if (!isfinite(mats[k])) err |= MVSDF_FU_ERR_FINITE;
+        if (!mv_all_finite(mats, npairs * 32 + V * 16)) err |= MVSDF_FU_ERR_FINITE;
         if (!isfinite(pix_thresh) || !isfinite(dep_thresh)) err |= MVSDF_FU_ERR_FINITE;
         if (probs && !(isfinite(pthresh[0]) && isfinite(pthresh[1]) && isfinite(pthresh[2]))) err |= MVSDF_FU_ERR_FINITE;
     }

@@ -1,6 +1,6 @@
 // geom_prims.h -- what the scene-side modules (mesh extraction and trimming, Chamfer, cloud cleaning, fusion, rasterisation, stereo, view selection)
-// share: workspace arithmetic, the header copies, the 4x4 row product, the projection into a depth map with its 2x2 bilinear sample (mv_project_texel,
-// mv_cell2: fusion.hip and tsdf.hip), the two-level exclusive scan with its in-chunk rank, and the finite check.
+// share: workspace arithmetic, the header copies, the 4x4 row product, the two-level exclusive scan with its in-chunk rank, and the finite check.  What
+// looks through a camera into an image (projection, the 2x2 bilinear cell, visibility) is view_prims.h, which includes this file.
 // Everything here is integer or order-fixed fp64 arithmetic, so every caller gets the same bits.  Kernels are static: each including file gets its own copies.
 #pragma once
 #include <limits.h>
@@ -55,35 +55,6 @@ static inline int mv_read(void* host, const void* dev, size_t bytes, hipStream_t
 // one row of a 4x4 matrix times q, in the definitions' order
 __device__ __forceinline__ double mv_row4(const double* __restrict__ t, double q0, double q1, double q2, double q3) {
     return ((t[0] * q0 + t[1] * q1) + t[2] * q2) + t[3] * q3;
-}
-
-// The depth-map sample of fusion.hip and tsdf.hip, which must agree: TSDF fusion consumes what the depth-map fusion produces.  Coordinates are
-// texel-centre ones: texel (x, y) of map[H][W] has its centre at u = x, v = y.
-struct MvProj {
-    double z, u, v;
-};
-
-// (q0, q1, q2, 1) through the 4x4 matrix P (rows u z, v z, z) -> o; false when z <= 0 or (u, v) lies outside [0, W - 1] x [0, H - 1], the area the
-// 2x2 cells cover
-__device__ __forceinline__ bool mv_project_texel(const double* __restrict__ P, double q0, double q1, double q2, int W, int H, MvProj* o) {
-    o->z = mv_row4(P + 8, q0, q1, q2, 1.0);
-    if (!(o->z > 0.0)) return false;
-    o->u = mv_row4(P, q0, q1, q2, 1.0) / o->z - 0.5;
-    o->v = mv_row4(P + 4, q0, q1, q2, 1.0) / o->z - 0.5;
-    return o->u >= 0.0 && o->u <= (double)(W - 1) && o->v >= 0.0 && o->v <= (double)(H - 1);
-}
-
-// the 2x2 cell of map[H][W] that holds such a (u, v), the last column / row belonging to the cell before it: its four texels and the weights.  Which
-// texels count as valid is the caller's rule.
-struct MvCell2 {
-    double d00, d01, d10, d11, fx, fy;
-    __device__ __forceinline__ double bilinear() const { return (d00 * (1.0 - fx) + d01 * fx) * (1.0 - fy) + (d10 * (1.0 - fx) + d11 * fx) * fy; }
-};
-
-__device__ __forceinline__ MvCell2 mv_cell2(const float* __restrict__ map, int W, int H, double u, double v) {
-    const double x0 = fmin(floor(u), (double)(W - 2)), y0 = fmin(floor(v), (double)(H - 2));
-    const float* __restrict__ t = map + (long long)(int)y0 * W + (int)x0;
-    return {(double)t[0], (double)t[1], (double)t[W], (double)t[W + 1], u - x0, v - y0};
 }
 
 // inclusive Hillis-Steele scan of x over the THREADS lanes of the workgroup (sh: THREADS entries; T() is zero)

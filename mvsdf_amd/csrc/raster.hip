@@ -15,8 +15,9 @@
 // * k_ra_visibility: one lane per (vertex, view); k_ra_colors: one lane per vertex, the views in order inside, so the weighted sum has one order.
 //
 // There is no clipping: a face with a vertex not in front of the camera is skipped.  Every device loop is bounded by the clamped pixel box or the
-// view count; every index read from the caller (face -> vertex) is range-checked before it is used.
-#include "geom_prims.h"
+// view count; every index read from the caller (face -> vertex) is range-checked before it is used.  The projection, the visibility test, the edge
+// function and the colour gather are view_prims.h's (mv_project, mv_visible, mv_edge, mv_cell / mv_gather_rgb), which texture.hip uses too.
+#include "view_prims.h"
 
 #define RA_THREADS 256
 #define RA_HDR 256                                    // bytes at the start of the workspace: MVSDF_RA_H_*
@@ -32,9 +33,7 @@ struct RaLayout {
     long long items, nb;
 };
 
-static bool ra_shape(long long views, long long H, long long W) {
-    return views >= 1 && views <= MVSDF_RA_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX && views * H * W <= RA_MAX_PIXELS;
-}
+static bool ra_shape(long long views, long long H, long long W) { return mv_view_shape(views, H, W) && views * H * W <= RA_MAX_PIXELS; }
 
 static bool ra_layout(long long nv, long long nf, long long views, long long H, long long W, RaLayout* L) {
     if (nv < 0 || nf < 0 || nv > INT_MAX || nf > INT_MAX || !ra_shape(views, H, W) || nf * views > INT_MAX) return false;
@@ -46,25 +45,6 @@ static bool ra_layout(long long nv, long long nf, long long views, long long H, 
     L->list = c.take((size_t)(L->items > 0 ? L->items : 1) * 4);
     L->bsum = c.take(mv_scan_tmp_bytes(L->items));
     L->total = c.o;
-    return true;
-}
-
-// one row of a 4x4 matrix times (q0, q1, q2, 1), in the definition's order
-__device__ __forceinline__ double ra_row(const double* __restrict__ t, double q0, double q1, double q2) {
-    return mv_row4(t, q0, q1, q2, 1.0);
-}
-
-__device__ __forceinline__ double ra_edge(double px, double py, double qx, double qy, double rx, double ry) {
-    return (qx - px) * (ry - py) - (qy - py) * (rx - px);
-}
-
-// the projection of a vertex; false: not in front
-__device__ __forceinline__ bool ra_project(const double* __restrict__ P, const float* __restrict__ X, double& sx, double& sy, double& z) {
-    const double q0 = (double)X[0], q1 = (double)X[1], q2 = (double)X[2];
-    z = ra_row(P + 8, q0, q1, q2);
-    if (!(z > 0.0)) return false;
-    sx = ra_row(P, q0, q1, q2) / z;
-    sy = ra_row(P + 4, q0, q1, q2) / z;
     return true;
 }
 
@@ -82,13 +62,13 @@ __device__ __forceinline__ bool ra_setup(const float* __restrict__ verts, const 
         atomicOr(hdr + MVSDF_RA_H_ERR, (unsigned long long)MVSDF_RA_ERR_INDEX);
         return false;
     }
-    if (!ra_project(P, verts + (long long)a * 3, g.ax, g.ay, g.az)) return false;
-    if (!ra_project(P, verts + (long long)b * 3, g.bx, g.by, g.bz)) return false;
-    if (!ra_project(P, verts + (long long)c * 3, g.cx, g.cy, g.cz)) return false;
+    if (!mv_project(P, verts + (long long)a * 3, g.ax, g.ay, g.az)) return false;
+    if (!mv_project(P, verts + (long long)b * 3, g.bx, g.by, g.bz)) return false;
+    if (!mv_project(P, verts + (long long)c * 3, g.cx, g.cy, g.cz)) return false;
     if (!(isfinite(g.ax) && isfinite(g.ay) && isfinite(g.az) && isfinite(g.bx) && isfinite(g.by) && isfinite(g.bz) && isfinite(g.cx) &&
           isfinite(g.cy) && isfinite(g.cz)))
         return false;
-    const double A = ra_edge(g.ax, g.ay, g.bx, g.by, g.cx, g.cy);
+    const double A = mv_edge(g.ax, g.ay, g.bx, g.by, g.cx, g.cy);
     if (A == 0.0) return false;
     g.flip = A < 0.0;
     g.A = g.flip ? -A : A;
@@ -106,9 +86,9 @@ template <bool PRE, bool STATS>
 __device__ __forceinline__ void ra_pixel(const RaFace& g, int x, int y, double o, unsigned f, unsigned long long* __restrict__ keys, int W,
                                          unsigned& n_atomic, unsigned& n_covered) {
     const double px = (double)x + o, py = (double)y + o;
-    double w0 = ra_edge(g.bx, g.by, g.cx, g.cy, px, py);
-    double w1 = ra_edge(g.cx, g.cy, g.ax, g.ay, px, py);
-    double w2 = ra_edge(g.ax, g.ay, g.bx, g.by, px, py);
+    double w0 = mv_edge(g.bx, g.by, g.cx, g.cy, px, py);
+    double w1 = mv_edge(g.cx, g.cy, g.ax, g.ay, px, py);
+    double w2 = mv_edge(g.ax, g.ay, g.bx, g.by, px, py);
     if (g.flip) {
         w0 = -w0;
         w1 = -w1;
@@ -132,12 +112,6 @@ __device__ __forceinline__ void ra_pixel(const RaFace& g, int x, int y, double o
 __device__ __forceinline__ void ra_stats(unsigned long long* hdr, unsigned n_atomic, unsigned n_covered) {
     if (n_atomic) atomicAdd(hdr + MVSDF_RA_H_ATOMICS, (unsigned long long)n_atomic);
     if (n_covered) atomicAdd(hdr + MVSDF_RA_H_COVERED, (unsigned long long)n_covered);
-}
-
-__global__ __launch_bounds__(RA_THREADS) void k_ra_check_cams(const double* __restrict__ P, long long n, unsigned long long* hdr) {
-    bool bad = false;
-    for (long long i = threadIdx.x; i < n; i += RA_THREADS) bad = bad || !isfinite(P[i]);
-    if (bad) atomicOr(hdr + MVSDF_RA_H_ERR, (unsigned long long)MVSDF_RA_ERR_FINITE);
 }
 
 // the small path.  blockIdx.y = view; flags[view * nf + f] = 1 where the face is left to the large path
@@ -211,21 +185,6 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_resolve(const unsigned long l
     face[i] = drawn ? (int)(unsigned)(k & 0xffffffffull) : -1;
 }
 
-// the definition's visibility test of X in one view; sx, sy are valid when it returns true
-__device__ __forceinline__ bool ra_visible(const double* __restrict__ P, const float* __restrict__ X, double o, int H, int W,
-                                           const float* __restrict__ depth, const unsigned char* __restrict__ mask, double depth_tol, double& sx,
-                                           double& sy) {
-    double z;
-    if (!ra_project(P, X, sx, sy, z)) return false;
-    const double x = floor(sx - o + 0.5), y = floor(sy - o + 0.5);
-    if (!(x >= 0.0 && x < (double)W && y >= 0.0 && y < (double)H)) return false;
-    const long long at = (long long)(int)y * W + (int)x;
-    const float D = depth[at];
-    if (!(D > 0.0f)) return false;
-    if (!(z <= (double)D * (1.0 + depth_tol))) return false;
-    return !mask || mask[at] != 0;
-}
-
 // blockIdx.y = view
 __global__ __launch_bounds__(RA_THREADS) void k_ra_visibility(const float* __restrict__ verts, long long nv, const double* __restrict__ P, double o, int H,
                                                                int W, const float* __restrict__ depth, const unsigned char* __restrict__ masks,
@@ -234,7 +193,7 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_visibility(const float* __res
     const long long v = blockIdx.y, hw = (long long)H * W;
     if (i >= nv) return;
     double sx, sy;
-    vis[v * nv + i] = ra_visible(P + v * 16, verts + i * 3, o, H, W, depth + v * hw, masks ? masks + v * hw : nullptr, depth_tol, sx, sy) ? 1 : 0;
+    vis[v * nv + i] = mv_visible(P + v * 16, verts + i * 3, o, H, W, depth + v * hw, masks ? masks + v * hw : nullptr, depth_tol, sx, sy) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(RA_THREADS) void k_ra_colors(const float* __restrict__ verts, const float* __restrict__ normals, long long nv,
@@ -256,7 +215,7 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_colors(const float* __restric
     if (!(flat && !ignore_normals)) {
         for (int v = 0; v < V; ++v) {
             double sx, sy;
-            if (!ra_visible(P + (long long)v * 16, X, o, H, W, depth + v * hw, masks ? masks + v * hw : nullptr, depth_tol, sx, sy)) continue;
+            if (!mv_visible(P + (long long)v * 16, X, o, H, W, depth + v * hw, masks ? masks + v * hw : nullptr, depth_tol, sx, sy)) continue;
             double wgt = 1.0;
             if (!flat) {
                 const double g0 = C[v * 3] - X0, g1 = C[v * 3 + 1] - X1, g2 = C[v * 3 + 2] - X2;
@@ -264,17 +223,9 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_colors(const float* __restric
                 if (!(cosang > cos_min)) continue;
                 wgt = cosang;
             }
-            const double u = sx - o, t = sy - o;
-            if (!(u >= 0.0 && u <= wmax && t >= 0.0 && t <= hmax)) continue;
-            const double x0 = fmin(floor(u), (double)(W - 2)), y0 = fmin(floor(t), (double)(H - 2));
-            const double fx = u - x0, fy = t - y0;
-            const unsigned char* __restrict__ q = images + ((long long)v * hw + (long long)(int)y0 * W + (int)x0) * 3;
+            if (!mv_in_image(sx, sy, o, wmax, hmax)) continue;
             double col[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double c00 = (double)q[c], c01 = (double)q[3 + c], c10 = (double)q[(long long)W * 3 + c], c11 = (double)q[(long long)W * 3 + 3 + c];
-                col[c] = (c00 * (1.0 - fx) + c01 * fx) * (1.0 - fy) + (c10 * (1.0 - fx) + c11 * fx) * fy;
-            }
+            mv_gather_rgb(images, v * hw, W, mv_cell(sx - o, sy - o, W, H), col);
             S0 += wgt * col[0];
             S1 += wgt * col[1];
             S2 += wgt * col[2];
@@ -289,7 +240,11 @@ __global__ __launch_bounds__(RA_THREADS) void k_ra_colors(const float* __restric
     n_views[i] = used;
 }
 
-static bool ra_center(double o) { return o == 0.5 || o == 0.0; }
+// MVSDF_RA_ERR_FINITE into the header where an entry of the cameras or centres m[n] is NaN or infinite
+static void ra_check_finite(const double* m, long long n, void* ws, hipStream_t s) {
+    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(1), dim3(MV_THREADS), 0, s, m, n, (unsigned long long*)ws + MVSDF_RA_H_ERR,
+                       (unsigned long long)MVSDF_RA_ERR_FINITE);
+}
 
 template <bool PRE, bool STATS>
 static void ra_launch_draw(const float* verts, const int32_t* faces, long long nv, long long nf, const double* P, long long views, double o, int H, int W,
@@ -319,7 +274,7 @@ int mvsdf_raster_draw(const float* verts, const int32_t* faces, int64_t nv, int6
                       double pixel_center, int64_t large_face_pixels, int32_t flags, void* ws, size_t ws_bytes, void* stream) {
     const char* what = "mvsdf_raster_draw";
     RaLayout L;
-    if (!P || !ws || (nf > 0 && (!verts || !faces)) || !ra_center(pixel_center) || large_face_pixels < 0 || !ra_layout(nv, nf, views, H, W, &L))
+    if (!P || !ws || (nf > 0 && (!verts || !faces)) || !mv_pixel_center(pixel_center) || large_face_pixels < 0 || !ra_layout(nv, nf, views, H, W, &L))
         return mv_fail(-1, "mvsdf_raster_draw: bad arguments");
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_raster_draw: workspace too small (mvsdf_raster_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
@@ -327,7 +282,7 @@ int mvsdf_raster_draw(const float* verts, const int32_t* faces, int64_t nv, int6
     int rc;
     if ((rc = mv_check(hipMemsetAsync(ws, 0, RA_HDR, s), what))) return rc;
     if ((rc = mv_check(hipMemsetAsync(w + L.keys, 0xff, (size_t)(views * H * W) * 8, s), what))) return rc;
-    hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
+    ra_check_finite(P, views * 16, ws, s);
     if (nf > 0) {
         const bool pre = !(flags & RA_FLAG_NO_PRETEST), stats = (flags & RA_FLAG_STATS) != 0;
         if (pre && !stats) ra_launch_draw<true, false>(verts, faces, nv, nf, P, views, pixel_center, (int)H, (int)W, large_face_pixels, w, L, s);
@@ -350,12 +305,12 @@ int mvsdf_raster_resolve(int64_t views, int64_t H, int64_t W, void* ws, size_t w
 int mvsdf_raster_visibility(const float* verts, int64_t nv, const double* P, int64_t views, int64_t H, int64_t W, double pixel_center,
                             const float* depth, const uint8_t* masks, double depth_tol, void* ws, size_t ws_bytes, uint8_t* vis, void* stream) {
     const char* what = "mvsdf_raster_visibility";
-    if (!P || !depth || !ws || ws_bytes < RA_HDR || nv < 0 || nv > INT_MAX || (nv > 0 && (!verts || !vis)) || !ra_center(pixel_center) ||
+    if (!P || !depth || !ws || ws_bytes < RA_HDR || nv < 0 || nv > INT_MAX || (nv > 0 && (!verts || !vis)) || !mv_pixel_center(pixel_center) ||
         !isfinite(depth_tol) || !ra_shape(views, H, W))
         return mv_fail(-1, "mvsdf_raster_visibility: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = mv_check(hipMemsetAsync(ws, 0, RA_HDR, s), what)) return rc;
-    hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
+    ra_check_finite(P, views * 16, ws, s);
     if (nv > 0)
         hipLaunchKernelGGL(k_ra_visibility, dim3(mv_grid(nv, RA_THREADS), (unsigned)views), dim3(RA_THREADS), 0, s, verts, (long long)nv, P,
                            pixel_center, (int)H, (int)W, depth, masks, depth_tol, vis);
@@ -368,12 +323,12 @@ int mvsdf_raster_colors(const float* verts, const float* normals, int64_t nv, co
                         float* colors, int32_t* n_views, void* stream) {
     const char* what = "mvsdf_raster_colors";
     if (!P || !centers || !depth || !images || !ws || ws_bytes < RA_HDR || nv < 0 || nv > INT_MAX || (nv > 0 && (!verts || !normals || !colors || !n_views)) ||
-        !ra_center(pixel_center) || !isfinite(depth_tol) || !isfinite(cos_min) || !ra_shape(views, H, W))
+        !mv_pixel_center(pixel_center) || !isfinite(depth_tol) || !isfinite(cos_min) || !ra_shape(views, H, W))
         return mv_fail(-1, "mvsdf_raster_colors: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = mv_check(hipMemsetAsync(ws, 0, RA_HDR, s), what)) return rc;
-    hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
-    hipLaunchKernelGGL(k_ra_check_cams, dim3(1), dim3(RA_THREADS), 0, s, centers, (long long)views * 3, (unsigned long long*)ws);
+    ra_check_finite(P, views * 16, ws, s);
+    ra_check_finite(centers, views * 3, ws, s);
     if (nv > 0)
         hipLaunchKernelGGL(k_ra_colors, dim3(mv_grid(nv, RA_THREADS)), dim3(RA_THREADS), 0, s, verts, normals, (long long)nv, P, centers,
                            (int)views, pixel_center, (int)H, (int)W, depth, masks, images, depth_tol, cos_min, (int)ignore_normals, fallback_r, fallback_g,

@@ -8,7 +8,9 @@
 //   pixel's descriptor in registers as doubles and walks k.  The 8 x 8 pixels of a wave at one k read a patch of about 9 x 9 source texels, and the next k
 //   moves that patch along the epipolar lines by about a texel, so the four-tap gathers are served by the CU's L1 and the XCD's L2 after the first touch.
 //   The dot products use fma(): the product of two fp32 values is exact in fp64, so fma(a, b, t) is t + a*b rounded once, the definition's value bit for
-//   bit (signed zeros included); nothing else is contracted.  Writes score[k][y][x] (a quiet NaN where no source is valid) and the count n_k as a byte.
+//   bit (signed zeros included); nothing else is contracted.  The projection of a hypothesis into a source, its 2x2 cell and the blend of the four dot
+//   products (ps_sample) are view_prims.h's mv_project_texel and MvCell, the ones fusion.hip and tsdf.hip sample depth maps with.  Writes
+//   score[k][y][x] (a quiet NaN where no source is valid) and the count n_k as a byte.
 // * k_ps_pick: one lane per pixel walks the volume (coalesced over the lanes): winner, refinement, b2, the three confidences.
 // * k_sg_path: one direction of the semi-global regularisation (stereo.py: "Regularisation").  A 256-lane workgroup owns a bundle of G adjacent paths and
 //   walks them step by step; lane t owns path t % G and the hypotheses t / G, t / G + 256 / G, ...  The previous step's path costs L live in LDS, k-major
@@ -23,7 +25,7 @@
 // One call sweeps every requested view in turn on the caller's stream; the score volume in the workspace is reused from view to view and holds the last
 // view's scores afterwards.  Every argument is validated on the host before anything is launched; only the finiteness of the descriptors is checked on the
 // device.  No atomics on floating point (the only atomic is the OR of an error bit).
-#include "geom_prims.h"
+#include "view_prims.h"
 
 #define PS_THREADS 256
 #define PS_TILE 16
@@ -138,23 +140,16 @@ template <int CFIX>
 __device__ __forceinline__ double ps_sample(const float* __restrict__ desc, long long hw, long long row, int R, int S, int C, const double* ref,
                                             const float* __restrict__ fr, double X, double Y, double d, int nsrc, const int* __restrict__ src,
                                             const double* __restrict__ mats, int& n) {
-    const double smax = (double)(S - 1), rmax = (double)(R - 1);
     const double q0 = X * d, q1 = Y * d;
     double acc = 0.0;
     for (int j = 0; j < nsrc; ++j) {
-        const double* __restrict__ T = mats + (long long)j * 16;
-        const double p2 = mv_row4(T + 8, q0, q1, d, 1.0);
-        if (!(p2 > 0.0)) continue;
-        const double u = mv_row4(T, q0, q1, d, 1.0) / p2 - 0.5;
-        const double v = mv_row4(T + 4, q0, q1, d, 1.0) / p2 - 0.5;
-        if (!(u >= 0.0 && u <= smax && v >= 0.0 && v <= rmax)) continue;
-        const double x0 = fmin(floor(u), (double)(S - 2)), y0 = fmin(floor(v), (double)(R - 2));
-        const double fx = u - x0, fy = v - y0;
-        const float* __restrict__ g = desc + ((long long)src[j] * hw + (long long)(int)y0 * S + (int)x0) * C;
+        MvProj pr = {};                                                   // set: nothing is carried around the loop (view_prims.h: mv_project)
+        if (!mv_project_texel(mats + (long long)j * 16, q0, q1, d, S, R, &pr)) continue;
+        const MvCell at = mv_cell(pr.u, pr.v, S, R);
+        const float* __restrict__ g = desc + ((long long)src[j] * hw + (long long)at.y0 * S + at.x0) * C;
         double t00, t01, t10, t11;
         ps_dots<CFIX>(ref, fr, g, row, C, t00, t01, t10, t11);
-        const double cs = (t00 * (1.0 - fx) + t01 * fx) * (1.0 - fy) + (t10 * (1.0 - fx) + t11 * fx) * fy;
-        acc = acc + cs;
+        acc = acc + at.blend(t00, t01, t10, t11);
         ++n;
     }
     return acc;
@@ -259,9 +254,9 @@ __global__ __launch_bounds__(PS_THREADS) void k_ps_upsample(const float* __restr
     const int p = (int)(i - v * HW), y = p / S, x = p - y * S;
     const double u = fmin(fmax((((double)x + 0.5) * (double)s) / (double)S - 0.5, 0.0), (double)(s - 1));
     const double w = fmin(fmax((((double)y + 0.5) * (double)r) / (double)R - 0.5, 0.0), (double)(r - 1));
-    const double x0 = fmin(floor(u), (double)(s - 2)), y0 = fmin(floor(w), (double)(r - 2));
-    const double fx = u - x0, fy = w - y0;
-    const long long at = v * ((long long)r * s) + (long long)(int)y0 * s + (int)x0;
+    const MvCell c = mv_cell(u, w, s, r);                                 // the cell alone: the weights below are renormalised over the parents with a winner
+    const double fx = c.fx, fy = c.fy;
+    const long long at = v * ((long long)r * s) + (long long)c.y0 * s + c.x0;
     const double wt[4] = {(1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy};
     double num = 0.0, den = 0.0;
 #pragma unroll
@@ -531,8 +526,7 @@ static int ps_sweep(const char* what, bool sgm, double p1, double p2, int paths,
     if (!(err & MVSDF_PS_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
             if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_PS_ERR_PAIR;
-        for (long long k = 0; k < npairs * 16; ++k)
-            if (!isfinite(mats[k])) err |= MVSDF_PS_ERR_FINITE;
+        if (!mv_all_finite(mats, npairs * 16)) err |= MVSDF_PS_ERR_FINITE;
     }
     if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total + (sgm ? mv_align256((size_t)(R * S * dmax) * 8) : 0))
@@ -710,8 +704,7 @@ int mvsdf_stereo_band(const float* desc, int64_t V, int64_t R, int64_t S, int64_
     if (!(err & MVSDF_PS_ERR_SHAPE)) {
         for (long long k = 0; k < npairs; ++k)
             if (pair_src[k] < 0 || pair_src[k] >= V) err |= MVSDF_PS_ERR_PAIR;
-        for (long long k = 0; k < npairs * 16; ++k)
-            if (!isfinite(mats[k])) err |= MVSDF_PS_ERR_FINITE;
+        if (!mv_all_finite(mats, npairs * 16)) err |= MVSDF_PS_ERR_FINITE;
     }
     if (err) return mv_refuse_header(ws, err, s, what);
     if (ws_bytes < L.total) return mv_fail(-1, "mvsdf_stereo_band: workspace too small (mvsdf_stereo_band_workspace_bytes)");

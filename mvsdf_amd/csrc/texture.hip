@@ -5,7 +5,8 @@
 //
 // * k_tx_face_views: one lane per face, the views in order inside (the label takes the first view of the largest |A|, so there is one order).  It
 //   also writes the six screen coordinates of the face in its view, which the later stages read (the fill can project them again instead:
-//   TX_FLAG_RECOMPUTE, the A/B of DESIGN.md).  The projection and the visibility test are raster.hip's, restated here over mv_row4.
+//   TX_FLAG_RECOMPUTE, the A/B of DESIGN.md).  The projection, the visibility test, the edge function and the texel gather are the ones raster.hip
+//   uses: view_prims.h's mv_project, mv_visible, mv_edge and mv_cell / mv_gather_rgb.
 // * k_tx_classify: the size class of every face at a texel density, and the seven class counts (integer atomics).  The host reads the counts: the
 //   atlas size follows from them alone (tx_layout), and the max_size loop repeats only this pass.
 // * the stable counting sort is ONE scan: flags[(6 - class) * nf + f] over 7 * nf bytes, so the exclusive prefix of a set flag is the face's place in
@@ -16,7 +17,7 @@
 //
 // Every index read from the caller (face -> vertex, order -> face, label -> view) is range-checked before it is used; the image position is clamped
 // before it becomes an address; all offsets into the images are 64-bit.
-#include "geom_prims.h"
+#include "view_prims.h"
 
 #define TX_THREADS 256
 #define TX_HDR 256                                    // bytes at the start of the workspace: MVSDF_TX_H_*
@@ -81,52 +82,6 @@ static bool tx_ws(long long nf, TxWs* w) {
     return true;
 }
 
-static bool tx_shape(long long views, long long H, long long W) {
-    return views >= 1 && views <= MVSDF_RA_MAX_VIEWS && H >= 2 && W >= 2 && H <= INT_MAX && W <= INT_MAX && H * W <= INT_MAX;
-}
-
-static bool tx_center(double o) { return o == 0.5 || o == 0.0; }
-
-__device__ __forceinline__ double tx_edge(double px, double py, double qx, double qy, double rx, double ry) {
-    return (qx - px) * (ry - py) - (qy - py) * (rx - px);
-}
-
-// raster.hip's projection of a vertex; false: not in front
-__device__ __forceinline__ bool tx_project(const double* __restrict__ P, const float* __restrict__ X, double& sx, double& sy, double& z) {
-    const double q0 = (double)X[0], q1 = (double)X[1], q2 = (double)X[2];
-    z = mv_row4(P + 8, q0, q1, q2, 1.0);
-    if (!(z > 0.0)) return false;
-    sx = mv_row4(P, q0, q1, q2, 1.0) / z;
-    sy = mv_row4(P + 4, q0, q1, q2, 1.0) / z;
-    return true;
-}
-
-// raster.hip's visibility test of X in one view; sx, sy are valid when it returns true
-__device__ __forceinline__ bool tx_visible(const double* __restrict__ P, const float* __restrict__ X, double o, int H, int W,
-                                           const float* __restrict__ depth, const unsigned char* __restrict__ mask, double depth_tol, double& sx,
-                                           double& sy) {
-    double z;
-    if (!tx_project(P, X, sx, sy, z)) return false;
-    const double x = floor(sx - o + 0.5), y = floor(sy - o + 0.5);
-    if (!(x >= 0.0 && x < (double)W && y >= 0.0 && y < (double)H)) return false;
-    const long long at = (long long)(int)y * W + (int)x;
-    const float D = depth[at];
-    if (!(D > 0.0f)) return false;
-    if (!(z <= (double)D * (1.0 + depth_tol))) return false;
-    return !mask || mask[at] != 0;
-}
-
-__device__ __forceinline__ bool tx_in_image(double sx, double sy, double o, double wmax, double hmax) {
-    const double u = sx - o, t = sy - o;
-    return u >= 0.0 && u <= wmax && t >= 0.0 && t <= hmax;
-}
-
-__global__ __launch_bounds__(TX_THREADS) void k_tx_check(const double* __restrict__ P, long long n, unsigned long long* hdr) {
-    bool bad = false;
-    for (long long i = threadIdx.x; i < n; i += TX_THREADS) bad = bad || !isfinite(P[i]);
-    if (bad) atomicOr(hdr + MVSDF_TX_H_ERR, (unsigned long long)MVSDF_TX_ERR_FINITE);
-}
-
 __global__ __launch_bounds__(TX_THREADS) void k_tx_face_views(const float* __restrict__ verts, const float* __restrict__ normals,
                                                                const int* __restrict__ faces, long long nv, long long nf,
                                                                const double* __restrict__ P, const double* __restrict__ C, int V, double o, int H, int W,
@@ -157,11 +112,11 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_face_views(const float* __res
                 const float* dv = depth + v * hw;
                 const unsigned char* mv = masks ? masks + v * hw : nullptr;
                 double ax, ay, bx, by, cx, cy;
-                if (!tx_visible(Pv, Xa, o, H, W, dv, mv, depth_tol, ax, ay)) continue;
-                if (!tx_visible(Pv, Xb, o, H, W, dv, mv, depth_tol, bx, by)) continue;
-                if (!tx_visible(Pv, Xc, o, H, W, dv, mv, depth_tol, cx, cy)) continue;
-                if (!(tx_in_image(ax, ay, o, wmax, hmax) && tx_in_image(bx, by, o, wmax, hmax) && tx_in_image(cx, cy, o, wmax, hmax))) continue;
-                const double A = tx_edge(ax, ay, bx, by, cx, cy);
+                if (!mv_visible(Pv, Xa, o, H, W, dv, mv, depth_tol, ax, ay)) continue;
+                if (!mv_visible(Pv, Xb, o, H, W, dv, mv, depth_tol, bx, by)) continue;
+                if (!mv_visible(Pv, Xc, o, H, W, dv, mv, depth_tol, cx, cy)) continue;
+                if (!(mv_in_image(ax, ay, o, wmax, hmax) && mv_in_image(bx, by, o, wmax, hmax) && mv_in_image(cx, cy, o, wmax, hmax))) continue;
+                const double A = mv_edge(ax, ay, bx, by, cx, cy);
                 if (!(A != 0.0)) continue;
                 if (!flat) {
                     const double g0 = C[v * 3] - m0, g1 = C[v * 3 + 1] - m1, g2 = C[v * 3 + 2] - m2;
@@ -326,9 +281,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_fill(const unsigned char* __r
                 if (a < 0 || b < 0 || cc < 0 || a >= nv || b >= nv || cc >= nv) continue;
                 const double* Pv = P + (long long)v * 16;
                 double z;
-                if (!tx_project(Pv, verts + (long long)a * 3, s[0], s[1], z)) continue;
-                if (!tx_project(Pv, verts + (long long)b * 3, s[2], s[3], z)) continue;
-                if (!tx_project(Pv, verts + (long long)cc * 3, s[4], s[5], z)) continue;
+                if (!mv_project(Pv, verts + (long long)a * 3, s[0], s[1], z)) continue;
+                if (!mv_project(Pv, verts + (long long)b * 3, s[2], s[3], z)) continue;
+                if (!mv_project(Pv, verts + (long long)cc * 3, s[4], s[5], z)) continue;
             } else {
 #pragma unroll
                 for (int q = 0; q < 6; ++q) s[q] = screen[f * 6 + q];
@@ -341,17 +296,11 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_fill(const unsigned char* __r
             const double beta = (qx - TX_INSET) / leg, gamma = (qy - TX_INSET) / leg, alpha = (1.0 - beta) - gamma;
             const double sx = (alpha * s[0] + beta * s[2]) + gamma * s[4], sy = (alpha * s[1] + beta * s[3]) + gamma * s[5];
             const double u = fmin(fmax(sx - o, 0.0), wmax), w = fmin(fmax(sy - o, 0.0), hmax);      // a NaN becomes 0: always an address inside
-            const double xf = fmin(floor(u), (double)(W - 2)), yf = fmin(floor(w), (double)(H - 2));
-            const double fx = u - xf, fy = w - yf;
-            const unsigned char* __restrict__ q = images + ((long long)v * hw + (long long)(int)yf * W + (int)xf) * 3;
+            double col[3];
+            mv_gather_rgb(images, v * hw, W, mv_cell(u, w, W, H), col);
             unsigned out[3];
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const double c00 = (double)q[ch], c01 = (double)q[3 + ch], c10 = (double)q[(long long)W * 3 + ch],
-                             c11 = (double)q[(long long)W * 3 + 3 + ch];
-                const double col = (c00 * (1.0 - fx) + c01 * fx) * (1.0 - fy) + (c10 * (1.0 - fx) + c11 * fx) * fy;
-                out[ch] = (unsigned)floor(col + 0.5) & 0xffu;
-            }
+            for (int ch = 0; ch < 3; ++ch) out[ch] = (unsigned)floor(col[ch] + 0.5) & 0xffu;
             px[e] = {out[0], out[1], out[2], 1u};
         }
     }
@@ -376,13 +325,14 @@ int mvsdf_texture_face_views(const float* verts, const float* normals, const int
                              double* screen, void* stream) {
     const char* what = "mvsdf_texture_face_views";
     if (!P || !centers || !depth || !ws || ws_bytes < TX_HDR || nv < 0 || nv > INT_MAX || nf < 0 || nf > TX_MAX_FACES ||
-        (nf > 0 && (!verts || !normals || !faces || !label || !score || !screen)) || !tx_center(pixel_center) || !isfinite(depth_tol) ||
-        !isfinite(cos_min) || !tx_shape(views, H, W))
+        (nf > 0 && (!verts || !normals || !faces || !label || !score || !screen)) || !mv_pixel_center(pixel_center) || !isfinite(depth_tol) ||
+        !isfinite(cos_min) || !mv_view_shape(views, H, W))
         return mv_fail(-1, "mvsdf_texture_face_views: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (int rc = mv_check(hipMemsetAsync(ws, 0, TX_HDR, s), what)) return rc;
-    hipLaunchKernelGGL(k_tx_check, dim3(1), dim3(TX_THREADS), 0, s, P, (long long)views * 16, (unsigned long long*)ws);
-    hipLaunchKernelGGL(k_tx_check, dim3(1), dim3(TX_THREADS), 0, s, centers, (long long)views * 3, (unsigned long long*)ws);
+    unsigned long long* errword = (unsigned long long*)ws + MVSDF_TX_H_ERR;
+    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(1), dim3(MV_THREADS), 0, s, P, (long long)views * 16, errword, (unsigned long long)MVSDF_TX_ERR_FINITE);
+    hipLaunchKernelGGL(k_any_nonfinite<double>, dim3(1), dim3(MV_THREADS), 0, s, centers, (long long)views * 3, errword, (unsigned long long)MVSDF_TX_ERR_FINITE);
     if (nf > 0)
         hipLaunchKernelGGL(k_tx_face_views, dim3(mv_grid(nf, TX_THREADS)), dim3(TX_THREADS), 0, s, verts, normals, faces, (long long)nv, (long long)nf, P,
                            centers, (int)views, pixel_center, (int)H, (int)W, depth, masks, depth_tol, cos_min, (int)ignore_normals, label, score, screen,
@@ -432,7 +382,7 @@ int mvsdf_texture_fill(const uint8_t* images, int64_t views, int64_t H, int64_t 
     const char* what = "mvsdf_texture_fill";
     TxLayout L;
     const bool re = (flags & TX_FLAG_RECOMPUTE) != 0;
-    if (!images || !texture || !valid || !tx_center(pixel_center) || !tx_shape(views, H, W) || nv < 0 || nv > INT_MAX ||
+    if (!images || !texture || !valid || !mv_pixel_center(pixel_center) || !mv_view_shape(views, H, W) || nv < 0 || nv > INT_MAX ||
         (nf > 0 && (!label || !order || (re ? (!verts || !faces || !P) : !screen))) || fallback_r < 0 || fallback_r > 255 || fallback_g < 0 ||
         fallback_g > 255 || fallback_b < 0 || fallback_b > 255 || !tx_layout(counts, nf, &L))
         return mv_fail(-1, "mvsdf_texture_fill: bad arguments");

@@ -5,12 +5,12 @@
 //   the count as an int), so there are no float atomics and the result cannot depend on the schedule.  A workgroup is a brick of 4 x 8 x 8 lattice
 //   points with k fastest: a wave's 64 points (one 8 x 8 slab in j, k) project to a compact patch of every depth map.  The 4x4 matrices P_v and the
 //   view list are kernel data indexed by the loop counter alone, the same for every lane, so they come through the scalar cache; the four texels are
-//   plain gathers.  The projection and the 2x2 sample are geom_prims.h's mv_project_texel / mv_cell2, the ones fusion.hip's k_fu_fuse uses: the depth
+//   plain gathers.  The projection and the 2x2 sample are view_prims.h's mv_project_texel / mv_cell2, the ones fusion.hip's k_fu_fuse uses: the depth
 //   maps this reads are the ones that writes.  One pass writes tsdf, weight and valid.  All arithmetic is fp64 without contraction, in the order the
 //   definition writes it.
 //
 // Every argument of the integration is validated on the host before anything is launched: an error leaves {0, error bits} in the header.
-#include "geom_prims.h"
+#include "view_prims.h"
 
 #define TS_HDR 256                                    // bytes at the start of the integration workspace: MVSDF_RES_H_*
 static_assert(MVSDF_RES_H_WORDS * 8 <= TS_HDR, "the result words fit the header");
@@ -106,8 +106,7 @@ int mvsdf_tsdf_integrate(const float* depths, int64_t V, int64_t H, int64_t W, c
     if (!(err & MVSDF_TS_ERR_SHAPE)) {
         for (long long q = 0; q < nviews; ++q)
             if (views[q] < 0 || views[q] >= V) err |= MVSDF_TS_ERR_VIEW;
-        for (long long q = 0; q < nviews * 16; ++q)
-            if (!isfinite(mats[q])) err |= MVSDF_TS_ERR_FINITE;
+        if (!mv_all_finite(mats, nviews * 16)) err |= MVSDF_TS_ERR_FINITE;
     }
     if (!isfinite(origin[0]) || !isfinite(origin[1]) || !isfinite(origin[2]) || !isfinite(voxel) || !isfinite(trunc) || isnan(jump)) err |= MVSDF_TS_ERR_FINITE;
     if (!(err & MVSDF_TS_ERR_FINITE) && (!(voxel > 0.0) || !(trunc > 0.0) || !(jump >= 0.0))) err |= MVSDF_TS_ERR_RANGE;
