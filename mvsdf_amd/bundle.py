@@ -191,8 +191,8 @@ def residuals(cams, xyz, track_off, track_view, obs_xy, loss_scale=None, trial=F
     pr = _problem(cams, xyz, track_off, track_view, obs_xy, (), what)
     delta = _delta(loss_scale, what)
     ws = _workspace(pr)
-    r = torch.zeros(pr.nnz, 2, dtype=torch.float64, device=pr.dev)
-    terms = torch.zeros(pr.nnz, dtype=torch.float64, device=pr.dev)
+    r = torch.empty(pr.nnz, 2, dtype=torch.float64, device=pr.dev)
+    terms = torch.empty(pr.nnz, dtype=torch.float64, device=pr.dev)
     check(lib().mvsdf_ba_residuals(_vp(pr.pose), _vp(pr.intr), _vp(pr.xyz), _vp(pr.off), _vp(pr.view), _vp(pr.obs), pr.V, pr.P, pr.nnz, delta,
                                    1 if trial else 0, _vp(ws), ws.numel(), _vp(r), _vp(terms), _stream(ws)), 'mvsdf_ba_residuals')
     h = _head(ws, what)
@@ -206,7 +206,7 @@ def normal_blocks(cams, xyz, track_off, track_view, obs_xy, fixed_views=(0,), la
     pr = _problem(cams, xyz, track_off, track_view, obs_xy, fixed_views, what)
     delta, lam = _delta(loss_scale, what), _number(lam, 'lam', what)
     ws = _workspace(pr)
-    z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=pr.dev)                                   # noqa: E731
+    z = lambda *s: torch.empty(*s, dtype=torch.float64, device=pr.dev)  # noqa: E731  (k_ba_export_blocks writes every entry of all five)
     U, gc, Vb, gp, b = z(pr.V, 6, 6), z(pr.V, 6), z(pr.P, 3, 3), z(pr.P, 3), z(pr.V, 6)
     check(lib().mvsdf_ba_blocks(_vp(pr.pose), _vp(pr.intr), _vp(pr.xyz), _vp(pr.off), _vp(pr.view), _vp(pr.obs), _vp(pr.fixed), pr.V, pr.P, pr.nnz,
                                 delta, lam, FLOOR, _vp(ws), ws.numel(), _vp(U), _vp(gc), _vp(Vb), _vp(gp), _vp(b), _stream(ws)), 'mvsdf_ba_blocks')
@@ -222,7 +222,7 @@ def schur_apply(blocks, x):
     """stage 6 -> S x fp64 [V,6]"""
     what = 'schur_apply'
     x = _vec(x, blocks, what)
-    out = torch.zeros_like(x)
+    out = torch.empty_like(x)
     check(lib().mvsdf_ba_schur(*blocks.sizes, _vp(blocks.ws), blocks.ws.numel(), _vp(x), _vp(out), _stream(x)), 'mvsdf_ba_schur')
     _head(blocks.ws, what)
     return out
@@ -233,7 +233,7 @@ def solve_reduced(blocks, cg_iters=64, cg_tol=1e-8, b=None):
     what = 'solve_reduced'
     cg_iters, cg_tol = _count(cg_iters, 'cg_iters', what, K.MVSDF_BA_MAX_CG), _number(cg_tol, 'cg_tol', what)
     b = None if b is None else _vec(b, blocks, what)
-    x = torch.zeros(blocks.sizes[0], 6, dtype=torch.float64, device=blocks.ws.device)
+    x = torch.empty(blocks.sizes[0], 6, dtype=torch.float64, device=blocks.ws.device)
     check(lib().mvsdf_ba_solve(*blocks.sizes, _vp(b), cg_iters, cg_tol, _vp(blocks.ws), blocks.ws.numel(), _vp(x), _stream(x)), 'mvsdf_ba_solve')
     return x, _head(blocks.ws, what)[K.MVSDF_BA_H_CG]
 
@@ -243,8 +243,8 @@ def apply_step(blocks, x):
     what = 'apply_step'
     x = _vec(x, blocks, what)
     dev = x.device
-    pose = torch.zeros(blocks.sizes[0], 12, dtype=torch.float64, device=dev)
-    xyz = torch.zeros(blocks.sizes[1], 3, dtype=torch.float64, device=dev)
+    pose = torch.empty(blocks.sizes[0], 12, dtype=torch.float64, device=dev)
+    xyz = torch.empty(blocks.sizes[1], 3, dtype=torch.float64, device=dev)
     rod = torch.from_numpy(rodrigues_table()).to(dev)
     check(lib().mvsdf_ba_step(*blocks.sizes, _vp(rod), _vp(blocks.ws), blocks.ws.numel(), _vp(x), _vp(pose), _vp(xyz), _stream(x)), 'mvsdf_ba_step')
     h = _head(blocks.ws, what)
@@ -264,10 +264,10 @@ def bundle_adjust(cams, xyz, track_off, track_view, obs_xy, fixed_views=(0,), it
     if not 0 < lambda_min <= lambda0 <= lambda_max:
         raise ValueError('%s: 0 < lambda_min <= lambda0 <= lambda_max must hold, got %r, %r, %r' % (what, lambda_min, lambda0, lambda_max))
     ws = _workspace(pr)
-    pose = torch.zeros(pr.V, 12, dtype=torch.float64, device=pr.dev)
-    out = torch.zeros(pr.P, 3, dtype=torch.float64, device=pr.dev)
-    r = torch.zeros(pr.nnz, 2, dtype=torch.float64, device=pr.dev)
-    terms = torch.zeros(pr.nnz, dtype=torch.float64, device=pr.dev)
+    pose = torch.empty(pr.V, 12, dtype=torch.float64, device=pr.dev)
+    out = torch.empty(pr.P, 3, dtype=torch.float64, device=pr.dev)
+    r = torch.empty(pr.nnz, 2, dtype=torch.float64, device=pr.dev)
+    terms = torch.empty(pr.nnz, dtype=torch.float64, device=pr.dev)
     rod = torch.from_numpy(rodrigues_table()).to(pr.dev)
     check(lib().mvsdf_ba_adjust(_vp(pr.pose), _vp(pr.intr), _vp(pr.xyz), _vp(pr.off), _vp(pr.view), _vp(pr.obs), _vp(pr.fixed), pr.V, pr.P, pr.nnz,
                                 _vp(rod), delta, iterations, lambda0, lambda_min, lambda_max, FLOOR, cg_iters, cg_tol, ftol, _vp(ws), ws.numel(),

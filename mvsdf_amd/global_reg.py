@@ -126,7 +126,7 @@ def spfh(points, normals, neighbors, radius=None):
     nrm = nrm.to(p.device).contiguous()
     hist = torch.empty(n, DIM, dtype=torch.int32, device=p.device)
     count = torch.empty(n, dtype=torch.int32, device=p.device)
-    err = torch.zeros(1, dtype=torch.int32, device=p.device)
+    err = torch.zeros(1, dtype=torch.int32, device=p.device)     # zeros: the kernels only OR error bits into this word
     check(lib().mvsdf_greg_spfh(_vp(p), _vp(nrm), _vp(nb), n, k, r2, _vp(hist), _vp(count), _vp(err), _stream(p)), 'mvsdf_greg_spfh')
     raise_for_bits(int(err.item()), what, ERRORS)
     return hist, count
@@ -141,7 +141,7 @@ def fpfh(points, neighbors, hist, count, radius=None):
     count = _array(count, torch.int32, (n,), what, 'count').to(p.device).contiguous()
     feat = torch.empty(n, DIM, dtype=torch.float64, device=p.device)
     codes = torch.empty(n, DIM, dtype=torch.int8, device=p.device)
-    err = torch.zeros(1, dtype=torch.int32, device=p.device)
+    err = torch.zeros(1, dtype=torch.int32, device=p.device)     # zeros: the kernels only OR error bits into this word
     check(lib().mvsdf_greg_fpfh(_vp(p), _vp(nb), _vp(hist), _vp(count), n, k, r2, _vp(feat), _vp(codes), _vp(err), _stream(p)), 'mvsdf_greg_fpfh')
     raise_for_bits(int(err.item()), what, ERRORS)
     return feat, codes

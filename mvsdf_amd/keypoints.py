@@ -408,13 +408,14 @@ def match_descriptors(kp, pairs=None, ratio=0.8, mutual=True, max_dist=None):
     M = p.shape[0]
     pair = torch.from_numpy(p.copy()).to(dev)
     cap = int((vo[p[:, 0] + 1] - vo[p[:, 0]]).sum()) if M else 0
-    off = torch.zeros(M + 1, dtype=torch.int64, device=dev)
-    if cap == 0:
-        return Matches(pair, off, torch.empty(0, 2, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+    if cap == 0:                                                  # no kernel runs: the offsets of no match
+        none = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+        return Matches(pair, none, torch.empty(0, 2, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
     size = lib().mvsdf_kp_match_workspace_bytes(_hp(vo), V, _hp(p), M)
     if size == 0:
         raise ValueError('%s: the sizes are outside the limits' % what)
     ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    off = torch.empty(M + 1, dtype=torch.int64, device=dev)      # k_kp_offsets writes all M + 1
     idx = torch.empty(cap, 2, dtype=torch.int32, device=dev)
     dist = torch.empty(cap, dtype=torch.int32, device=dev)
     check(lib().mvsdf_kp_match(_vp(codes), _hp(vo), V, _hp(p), M, ratio * ratio, int(max_dist), 1 if mutual else 0, _vp(ws), size, _vp(off), _vp(idx),
@@ -549,12 +550,15 @@ def triangulate_tracks(kp, tracks, cams, max_reproj=2.0, min_angle=1.5):
     min_angle = float(min_angle)
     if not 0 <= min_angle <= 180:
         raise ValueError('%s: min_angle must be in [0, 180] degrees, got %r' % (what, min_angle))
-    xyz = torch.zeros(T, 3, dtype=torch.float64, device=dev)
-    error = torch.zeros(T, dtype=torch.float64, device=dev)
-    keep = torch.zeros(T, dtype=torch.uint8, device=dev)
+    if T == 0 or nnz == 0:                                        # no kernel runs: no track is kept, no point is made
+        z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)  # noqa: E731
+        return z(T, 3), z(T), torch.zeros(T, dtype=torch.bool, device=dev), torch.zeros(nnz, dtype=torch.bool, device=dev)
+    xyz = torch.empty(T, 3, dtype=torch.float64, device=dev)      # k_kp_triangulate writes every track's xyz, error and keep
+    error = torch.empty(T, dtype=torch.float64, device=dev)
+    keep = torch.empty(T, dtype=torch.uint8, device=dev)
+    # zeros: the kernel writes obs_keep only at the entries its tracks own, track_off[t] .. track_off[t + 1]; the entries before track_off[0] and
+    # behind track_off[T] stay as allocated
     obs_keep = torch.zeros(nnz, dtype=torch.uint8, device=dev)
-    if T == 0 or nnz == 0:
-        return xyz, error, keep.bool(), obs_keep.bool()
     centers, rays, proj = (torch.from_numpy(a).to(dev).contiguous() for a in camera_arrays(c))
     hdr = torch.empty(256, dtype=torch.uint8, device=dev)
     vod = torch.from_numpy(vo).to(dev)

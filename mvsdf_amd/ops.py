@@ -692,7 +692,7 @@ def dsurf_samples(depths, depth_cams, size, center, bb, jitter_rad, seed, n):
     kinv = torch.linalg.inv(depth_cams[:, 1, :3, :3]).contiguous()                # my_utils.py:84
     einv = torch.linalg.inv(depth_cams[:, 0]).contiguous()                        # my_utils.py:93
     size, center = _f32(size.reshape(-1)[:1]), _f32(center.reshape(-1)[:3])
-    idx = torch.full((2, n), 1 << 62, dtype=torch.int64, device=dev)
+    idx = torch.full((2, n), 1 << 62, dtype=torch.int64, device=dev)             # the kernel writes counts[s] entries of row s; the fill sorts behind them
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     geo = (ptr(depths), ptr(kinv), ptr(einv), N, H, W, ptr(size), ptr(center), bb, jitter_rad, seed, n)
     check(lib().mvsdf_dsurf_select(*geo, ptr(idx), ptr(counts), stream_of(depths)), 'mvsdf_dsurf_select')
@@ -747,7 +747,7 @@ def trace_generic(sdf, cam_loc, ray_dirs, object_mask, params, training, interva
     state = torch.empty(L.mvsdf_tracegen_state_bytes(R), dtype=torch.uint8, device=dev)
     req = torch.empty(R, 2, dtype=torch.uint8, device=dev)
     rpts = torch.empty(R, 2, 3, dtype=torch.float32, device=dev)
-    vals = torch.zeros(R, 2, dtype=torch.float32, device=dev)
+    vals = torch.zeros(R, 2, dtype=torch.float32, device=dev)      # an input of the kernels, filled on the host side at the requested rows only
     counters = torch.empty(16, dtype=torch.int64, device=dev)
     pts = torch.empty(R, 3, dtype=torch.float32, device=dev)
     mask = torch.empty(R, dtype=torch.uint8, device=dev)

@@ -37,8 +37,8 @@ class FlatAdam(torch.optim.Optimizer):
         assert all(p.is_cuda and p.dtype == torch.float32 and p.device == p0.device for p in ps), 'fp32 parameters on one GPU expected'
         total = sum(p.numel() for p in ps)
         self.flat_p = torch.empty(total, dtype=torch.float32, device=p0.device)
-        self.flat_g = torch.zeros_like(self.flat_p)
-        self.flat_m = torch.zeros_like(self.flat_p)
+        self.flat_g = torch.zeros_like(self.flat_p)                                    # zeros by definition: the sum of no gradient, Adam's moments at t = 0,
+        self.flat_m = torch.zeros_like(self.flat_p)                                    # and a norm that may be read before the first step
         self.flat_v = torch.zeros_like(self.flat_p)
         self._ws = torch.empty(lib().mvsdf_adam_ws_floats(), dtype=torch.float32, device=p0.device)
         self.norm_and_coef = torch.zeros(2, dtype=torch.float32, device=p0.device)     # {||grad||, clip coefficient} of the last step

@@ -143,7 +143,7 @@ class NearestTree:
         index = torch.empty(nq, dtype=torch.int32, device=q.device)
         if nq == 0:
             return dist, index
-        err = torch.zeros(1, dtype=torch.int32, device=q.device)
+        err = torch.zeros(1, dtype=torch.int32, device=q.device)  # zeros: the kernel only ORs error bits into this word
         T = None if transform is None else _c16(_matrix(transform, what))
         check(lib().mvsdf_reg_tree_query(_vp(self._ws), self._size, self.n, _vp(q), nq, T, max_dist, _vp(dist), None, _vp(index), _vp(err),
                                          _stream(q)), 'mvsdf_reg_tree_query')

@@ -285,6 +285,7 @@ def plane_sweep(descriptors, cams, pairs, num_src=2, views=None, scores=False, r
     if size == 0:
         raise ValueError('%s: %d x %d texels of %d hypotheses are beyond the limits (R*S < 2^31, R*S*D <= 2^40)' % (what, R, S, dmax))
     ws = torch.empty(size, dtype=torch.uint8, device=dev)
+    # zeros / -1: the kernels write the maps of the views in `views` only; every other view keeps the "no estimate" values it is allocated with
     depths = torch.zeros(V, R, S, dtype=torch.float32, device=dev)
     probs = torch.zeros(V, 3, R, S, dtype=torch.float32, device=dev)
     best_k = torch.full((V, R, S), -1, dtype=torch.int32, device=dev)
@@ -390,6 +391,7 @@ def _band_run(what, f, cams, views, used, c, Db, steps):
     V, R, S, C = f.shape
     off, src, npairs, mats = _pair_tables(what, cams, views, used)
     c = c.to(dev, torch.float64).contiguous()
+    # zeros / -1: the kernels write the maps of the views in `views` only; every other view keeps the "no estimate" values it is allocated with
     depths = torch.zeros(V, R, S, dtype=torch.float32, device=dev)
     probs = torch.zeros(V, 3, R, S, dtype=torch.float32, device=dev)
     best_k = torch.full((V, R, S), -1, dtype=torch.int32, device=dev)

@@ -1,3 +1,5 @@
+import contextlib
+
 import numpy as np
 import torch
 
@@ -44,6 +46,77 @@ def depth_check(g, dists, hit, tol=1e-4):
     assert rel[hit & ~tie].max() < tol, float(rel[hit & ~tie].max())
     assert int(tie.sum()) <= 2 and (not tie.any() or np.abs(dists - g['dists'])[tie].max() < 1e-3), (int(tie.sum()))
     return int(tie.sum())
+
+
+POISON_PATTERNS = (0xff, 0x00, 0x5a)
+# 0xff: NaN in every float type, -1 in signed ints, the EMPTY value of every min-key, True -- exposes a missing clear-to-zero
+# 0x00: zeros -- exposes a missing EMPTY / +inf / -1 initialisation (what fresh memory usually gives, made deterministic)
+# 0x5a: large finite garbage (float32 ~1.5e16, float64 ~2.7e130, int32 1515870810, True) -- exposes what both of the above happen to satisfy
+
+
+_TRUE_EMPTY = (torch.empty, torch.empty_like)
+
+
+class PoisonLog:
+    """what dirty_allocations() poisoned so far: .count allocations, .bytes bytes (zero-length tensors count as an allocation of 0 bytes)"""
+
+    def __init__(self):
+        self.count = 0
+        self.bytes = 0
+
+
+def poison_bytes(x, pattern):
+    """Fill the storage extent of CUDA tensor `x` with the byte `pattern`, whatever its dtype: through a uint8 view, so an int32 reads
+    0x5a5a5a5a and not the value 0x5a.  -> bytes written."""
+    n = x.numel() * x.element_size()
+    if n == 0:
+        return 0
+    if x.is_contiguous():
+        x.view(-1).view(torch.uint8).fill_(pattern)
+        return n
+    lo = x.storage_offset() * x.element_size()          # a strided torch.empty_like: every byte between its first and last element
+    hi = lo + (sum((s - 1) * st for s, st in zip(x.shape, x.stride())) + 1) * x.element_size()
+    torch.tensor([], dtype=torch.uint8, device=x.device).set_(x.untyped_storage())[lo:hi].fill_(pattern)
+    return hi - lo
+
+
+@contextlib.contextmanager
+def dirty_allocations(pattern):
+    """Under this context every CUDA tensor that torch.empty / torch.empty_like returns (every output and workspace the library allocates: they are
+    its only uninitialised-allocation spellings, held by tests/test_dirty_memory_table_host.py) is filled with the byte `pattern` before it is
+    handed out.  -> a PoisonLog that counts them.  A plain context manager: it restores torch.empty itself, nesting included."""
+    assert 0 <= pattern <= 0xff
+    e0, el0 = torch.empty, torch.empty_like
+    log = PoisonLog()
+
+    def poison(x):
+        if torch.is_tensor(x) and x.is_cuda:
+            log.bytes += poison_bytes(x, pattern)
+            log.count += 1
+        return x
+
+    def empty(*a, **k):
+        return poison(e0(*a, **k))
+
+    def empty_like(*a, **k):
+        return poison(el0(*a, **k))
+
+    torch.empty, torch.empty_like = empty, empty_like
+    try:
+        yield log
+    finally:
+        torch.empty, torch.empty_like = e0, el0
+
+
+@contextlib.contextmanager
+def clean_allocations():
+    """inside dirty_allocations: torch.empty as it really is, for a test's own set-up (a shared fixture made once)"""
+    cur = torch.empty, torch.empty_like
+    torch.empty, torch.empty_like = _TRUE_EMPTY
+    try:
+        yield
+    finally:
+        torch.empty, torch.empty_like = cur
 
 
 def t(a, dev='cuda'):

@@ -9,7 +9,6 @@ fp32 is PyTorch's own fp32 CPU evaluation of the same formulas.
 Every call is made twice and must return the same bits; one case per entry point runs with every buffer ops allocates filled with NaN (0xff for
 the byte packs) first, and must return the same bits again: a kernel that read unwritten workspace, context or padding and relied on a zero weight
 to cancel it would turn those into NaN.  One named exception: SECOND_ORDER_WGRAD.  Every test runs on both chain arithmetics ('x3': csrc/chain_x3.h; 'f32': the fp32-input MFMA chains)."""
-import contextlib
 import json
 import math
 import os
@@ -19,7 +18,7 @@ import pytest
 import torch
 
 import diff_ref as R
-from helpers import sdf_packed_net
+from helpers import dirty_allocations, sdf_packed_net
 from mvsdf_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -43,23 +42,10 @@ def _report():
 
 
 @pytest.fixture
-def nan_workspace(monkeypatch):
+def nan_workspace():
     """-> a context manager under which every CUDA tensor made by torch.empty / torch.empty_like (every output, context, workspace and pack that
-    ops allocates) starts as NaN (float) or 0xff bytes (a NaN in every bf16 term of a pack)."""
-    e0, el0 = torch.empty, torch.empty_like
-
-    def poison(t):
-        if t.is_cuda:
-            t.fill_(float('nan') if t.is_floating_point() else 0xff)
-        return t
-
-    @contextlib.contextmanager
-    def on():
-        with monkeypatch.context() as m:
-            m.setattr(torch, 'empty', lambda *a, **k: poison(e0(*a, **k)))
-            m.setattr(torch, 'empty_like', lambda *a, **k: poison(el0(*a, **k)))
-            yield
-    return on
+    ops allocates) starts as all-ones bytes (helpers.dirty_allocations): NaN in every float type and in every bf16 term of a pack, -1 in the ints."""
+    return lambda: dirty_allocations(0xff)
 
 
 def _check(entry, kind, got, ref64, ref32, k32=4):
