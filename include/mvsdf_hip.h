@@ -1079,7 +1079,8 @@ enum {
 enum {                          /* bits 1 and 2 are MVSDF_RA_ERR_*'s */
     MVSDF_TX_ERR_FINITE = 1,    /* a camera or centre entry is NaN or infinite */
     MVSDF_TX_ERR_INDEX = 2,     /* a face refers to a vertex outside [0, nv) */
-    MVSDF_TX_ERR_COUNTS = 4     /* the class counts passed to the pack are not those of cls */
+    MVSDF_TX_ERR_COUNTS = 4,    /* the class counts passed to the pack are not those of cls; seams: the counts passed to mvsdf_seams_graph are not the header's */
+    MVSDF_TX_ERR_LABEL = 8      /* seams: a face label outside [-1, V), or a node's view outside [0, V) */
 };
 enum {
     MVSDF_TX_MAX_SIDE = 32768,      /* texels: block coordinates fit 13 bits, block indices 26 */
@@ -1098,6 +1099,54 @@ int mvsdf_texture_fill(const uint8_t* images, int64_t views, int64_t H, int64_t 
                        const int32_t* order, int64_t nf, const int64_t* counts, const float* verts, const int32_t* faces, int64_t nv, const double* P,
                        int32_t flags, int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, int64_t Ht, int64_t Wt, uint8_t* texture,
                        uint8_t* valid, void* stream);
+
+/* ---- Seam levelling of a texture atlas (seams.hip, the fill in texture.hip; Python: mvsdf_amd/seams.py, which states the definition) ----
+ * An additive colour correction g per node = (vertex, view) pair that a labelled face's corner makes, so that the corrected colours agree where
+ * labels meet.  All on the device, fp64, no call waits.  Every workspace starts with the MVSDF_SL_H_* words (256 bytes); error bits are
+ * MVSDF_TX_ERR_*.  Every call but mvsdf_seams_graph starts by zeroing that header.  mvsdf_seams_workspace_bytes(nf, nv, views, nodes): what
+ * the node / graph calls need for nf faces and the solve for `nodes` nodes, whichever is more (0 beyond the limits).
+ * mvsdf_seams_nodes: corner_node int32 [nf][3] (-1 on unlabelled faces); header: MVSDF_SL_H_NODES = K, MVSDF_SL_H_NNZ = the adjacency entries;
+ * MVSDF_TX_ERR_INDEX (a vertex id outside [0, nv)), MVSDF_TX_ERR_LABEL (a label outside [-1, views)); such a face counts as unlabelled.
+ * mvsdf_seams_graph: with the SAME workspace, untouched since mvsdf_seams_nodes, and the K and nnz read from it: node_vertex, node_view int32 [K],
+ * adj_off int64 [K + 1], adj_seam int32 [K] (the leading entries of a node's list that are seam partners), adj_node int32 [nnz].
+ * MVSDF_TX_ERR_COUNTS: K or nnz are not the header's, or corner_node is not the one written (nothing else is valid).
+ * mvsdf_seams_colors: f fp64 [K][3]; MVSDF_TX_ERR_FINITE (P or a node's vertex), _INDEX (a node's vertex id), _LABEL (a node's view).
+ * mvsdf_seams_apply: out [K][3] = A x.  mvsdf_seams_solve: g [K][3]; header: per channel MVSDF_SL_H_ITERS + c, the final rho (fp64 bits) at
+ * MVSDF_SL_H_RHO + c and the first at MVSDF_SL_H_RHO0 + c; cg_iters in [0, MVSDF_SL_MAX_CG], cg_tol >= 0, smoothness >= 0, anchor > 0, all finite.
+ * Both raise MVSDF_TX_ERR_INDEX for an offset, a seam count or an entry out of range (such an entry is skipped).
+ * mvsdf_seams_fill: mvsdf_texture_fill (from the screen table) with the correction of the face's three nodes blended by the texel's barycentric
+ * weights; MVSDF_TX_ERR_INDEX: a labelled face's corner_node outside [0, K) (its texels stay uncorrected). */
+enum {
+    MVSDF_SL_H_ERR = 0,         /* error bits */
+    MVSDF_SL_H_NODES = 1,       /* mvsdf_seams_nodes: K */
+    MVSDF_SL_H_NNZ = 2,         /* mvsdf_seams_nodes: adjacency entries */
+    MVSDF_SL_H_ITERS = 3,       /* the solve, three words each, one per colour channel: iterations run */
+    MVSDF_SL_H_RHO = 6,         /* r . z, fp64 bits */
+    MVSDF_SL_H_RHO0 = 9,        /* the first r . z, fp64 bits */
+    MVSDF_SL_H_DONE = 12,       /* the channel has ended */
+    MVSDF_SL_H_SIGMA = 15,      /* p . A p of the running iteration, fp64 bits */
+    MVSDF_SL_H_RHON = 18,       /* r . z of the running iteration, fp64 bits */
+    MVSDF_SL_H_WORDS = 21
+};
+enum {
+    MVSDF_SL_MAX_CG = 100000    /* iterations of one solve */
+};
+size_t mvsdf_seams_workspace_bytes(int64_t nf, int64_t nv, int64_t views, int64_t nodes);
+int mvsdf_seams_nodes(const int32_t* faces, const int32_t* label, int64_t nv, int64_t nf, int64_t views, void* ws, size_t ws_bytes,
+                      int32_t* corner_node, void* stream);
+int mvsdf_seams_graph(int64_t nv, int64_t nf, int64_t views, int64_t nodes, int64_t nnz, const int32_t* corner_node, void* ws, size_t ws_bytes,
+                      int32_t* node_vertex, int32_t* node_view, int64_t* adj_off, int32_t* adj_seam, int32_t* adj_node, void* stream);
+int mvsdf_seams_colors(const int32_t* node_vertex, const int32_t* node_view, int64_t nodes, const float* verts, int64_t nv, const double* P,
+                       int64_t views, int64_t H, int64_t W, double pixel_center, const uint8_t* images, void* ws, size_t ws_bytes, double* f,
+                       void* stream);
+int mvsdf_seams_apply(const int64_t* adj_off, const int32_t* adj_seam, const int32_t* adj_node, int64_t nodes, int64_t nnz, const double* x,
+                      double smoothness, double anchor, void* ws, size_t ws_bytes, double* out, void* stream);
+int mvsdf_seams_solve(const int64_t* adj_off, const int32_t* adj_seam, const int32_t* adj_node, int64_t nodes, int64_t nnz, const double* f,
+                      double smoothness, double anchor, int32_t cg_iters, double cg_tol, void* ws, size_t ws_bytes, double* g, void* stream);
+int mvsdf_seams_fill(const uint8_t* images, int64_t views, int64_t H, int64_t W, double pixel_center, const int32_t* label, const double* screen,
+                     const int32_t* order, int64_t nf, const int64_t* counts, const int32_t* corner_node, const double* g, int64_t nodes,
+                     int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, void* ws, size_t ws_bytes, int64_t Ht, int64_t Wt, uint8_t* texture,
+                     uint8_t* valid, void* stream);
 
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.

@@ -13,7 +13,8 @@
 //   the order by class descending, face ascending (mv_scan_blocks, then k_tx_emit ranks its own chunk with mv_chunk_rank).  k_tx_emit writes the
 //   order, the patch and the UVs of its faces.
 // * k_tx_fill: one lane per four texels of a row (they share their 4 x 4 block, hence their cell), rows along the wave: 12-byte stores side by side.
-//   The owner of a texel follows from the Morton index of its block and the class offsets; no per-texel table exists.
+//   The owner of a texel follows from the Morton index of its block and the class offsets; no per-texel table exists.  Its LEVEL flag adds the seam
+//   levelling correction of the face's three nodes before the rounding (mvsdf_seams_fill, the last entry below; the rest of that module: seams.hip).
 //
 // Every index read from the caller (face -> vertex, order -> face, label -> view) is range-checked before it is used; the image position is clamped
 // before it becomes an address; all offsets into the images are 64-bit.
@@ -22,7 +23,7 @@
 #define TX_THREADS 256
 #define TX_HDR 256                                    // bytes at the start of the workspace: MVSDF_TX_H_*
 #define TX_CLASSES 7
-static_assert(MVSDF_TX_H_WORDS * 8 <= TX_HDR && MVSDF_TX_H_COUNTS + TX_CLASSES == MVSDF_TX_H_WORDS, "the result words fit the header");
+static_assert(MVSDF_TX_H_WORDS * 8 <= TX_HDR && MVSDF_SL_H_WORDS * 8 <= TX_HDR && MVSDF_TX_H_COUNTS + TX_CLASSES == MVSDF_TX_H_WORDS, "the result words fit the header");
 #define TX_NMIN 4
 #define TX_MAX_FACES (1ll << MVSDF_TX_MAX_FACES_LOG2)
 #define TX_INSET 0.75                                 // the right-angle corner's distance from the cell's edges, in texels
@@ -241,13 +242,16 @@ struct TxTexel {
     unsigned r, g, b, valid;
 };
 
-template <bool RECOMPUTE>
+// LEVEL (seam levelling, seams.py's step 6): the unrounded colour gets the face's three node corrections g blended with the texel's barycentric
+// weights, and is clamped to [0, 255] before it is rounded.  A face whose nodes are out of range raises MVSDF_TX_ERR_INDEX and stays unlevelled.
+template <bool RECOMPUTE, bool LEVEL>
 __global__ __launch_bounds__(TX_THREADS) void k_tx_fill(const unsigned char* __restrict__ images, int V, int H, int W, double o,
                                                          const int* __restrict__ label, const double* __restrict__ screen,
                                                          const int* __restrict__ order, long long nf, const float* __restrict__ verts,
                                                          const int* __restrict__ faces, long long nv, const double* __restrict__ P, TxLayout L,
                                                          unsigned fr, unsigned fg, unsigned fb, unsigned* __restrict__ texture,
-                                                         unsigned* __restrict__ valid) {
+                                                         unsigned* __restrict__ valid, const int* __restrict__ corner_node,
+                                                         const double* __restrict__ g, long long K, unsigned long long* hdr) {
     const long long t = (long long)blockIdx.x * TX_THREADS + threadIdx.x;
     const int Wq = L.Wt / 4;
     if (t >= (long long)Wq * L.Ht) return;
@@ -298,6 +302,17 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_fill(const unsigned char* __r
             const double u = fmin(fmax(sx - o, 0.0), wmax), w = fmin(fmax(sy - o, 0.0), hmax);      // a NaN becomes 0: always an address inside
             double col[3];
             mv_gather_rgb(images, v * hw, W, mv_cell(u, w, W, H), col);
+            if (LEVEL) {
+                const int na = corner_node[f * 3], nb = corner_node[f * 3 + 1], nc = corner_node[f * 3 + 2];
+                if (na < 0 || nb < 0 || nc < 0 || na >= K || nb >= K || nc >= K) {
+                    atomicOr(hdr + MVSDF_SL_H_ERR, (unsigned long long)MVSDF_TX_ERR_INDEX);
+                } else {
+                    const double *ga = g + (long long)na * 3, *gb = g + (long long)nb * 3, *gc = g + (long long)nc * 3;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch)
+                        col[ch] = fmin(fmax(col[ch] + ((alpha * ga[ch] + beta * gb[ch]) + gamma * gc[ch]), 0.0), 255.0);   // a NaN becomes 0
+                }
+            }
             unsigned out[3];
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) out[ch] = (unsigned)floor(col[ch] + 0.5) & 0xffu;
@@ -390,13 +405,36 @@ int mvsdf_texture_fill(const uint8_t* images, int64_t views, int64_t H, int64_t 
     const long long quads = (long long)(L.Wt / 4) * L.Ht;
     hipStream_t s = (hipStream_t)stream;
     if (re)
-        hipLaunchKernelGGL(k_tx_fill<true>, dim3(mv_grid(quads, TX_THREADS)), dim3(TX_THREADS), 0, s, images, (int)views, (int)H, (int)W, pixel_center,
+        hipLaunchKernelGGL((k_tx_fill<true, false>), dim3(mv_grid(quads, TX_THREADS)), dim3(TX_THREADS), 0, s, images, (int)views, (int)H, (int)W, pixel_center,
                            label, screen, order, (long long)nf, verts, faces, (long long)nv, P, L, (unsigned)fallback_r, (unsigned)fallback_g,
-                           (unsigned)fallback_b, (unsigned*)texture, (unsigned*)valid);
+                           (unsigned)fallback_b, (unsigned*)texture, (unsigned*)valid, (const int*)nullptr, (const double*)nullptr, 0ll,
+                           (unsigned long long*)nullptr);
     else
-        hipLaunchKernelGGL(k_tx_fill<false>, dim3(mv_grid(quads, TX_THREADS)), dim3(TX_THREADS), 0, s, images, (int)views, (int)H, (int)W, pixel_center,
+        hipLaunchKernelGGL((k_tx_fill<false, false>), dim3(mv_grid(quads, TX_THREADS)), dim3(TX_THREADS), 0, s, images, (int)views, (int)H, (int)W, pixel_center,
                            label, screen, order, (long long)nf, verts, faces, (long long)nv, P, L, (unsigned)fallback_r, (unsigned)fallback_g,
-                           (unsigned)fallback_b, (unsigned*)texture, (unsigned*)valid);
+                           (unsigned)fallback_b, (unsigned*)texture, (unsigned*)valid, (const int*)nullptr, (const double*)nullptr, 0ll,
+                           (unsigned long long*)nullptr);
+    return mv_check(hipGetLastError(), what);
+}
+
+int mvsdf_seams_fill(const uint8_t* images, int64_t views, int64_t H, int64_t W, double pixel_center, const int32_t* label, const double* screen,
+                     const int32_t* order, int64_t nf, const int64_t* counts, const int32_t* corner_node, const double* g, int64_t nodes,
+                     int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, void* ws, size_t ws_bytes, int64_t Ht, int64_t Wt, uint8_t* texture,
+                     uint8_t* valid, void* stream) {
+    const char* what = "mvsdf_seams_fill";
+    TxLayout L;
+    if (!images || !texture || !valid || !ws || ws_bytes < TX_HDR || !mv_pixel_center(pixel_center) || !mv_view_shape(views, H, W) || nodes < 0 ||
+        nodes > 3 * TX_MAX_FACES || (nf > 0 && (!label || !order || !screen || !corner_node)) || (nodes > 0 && !g) || fallback_r < 0 ||
+        fallback_r > 255 || fallback_g < 0 || fallback_g > 255 || fallback_b < 0 || fallback_b > 255 || !tx_layout(counts, nf, &L))
+        return mv_fail(-1, "mvsdf_seams_fill: bad arguments");
+    if (Ht != L.Ht || Wt != L.Wt) return mv_fail(-1, "mvsdf_seams_fill: Ht x Wt is not the atlas of these counts");
+    const long long quads = (long long)(L.Wt / 4) * L.Ht;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mv_check(hipMemsetAsync(ws, 0, TX_HDR, s), what)) return rc;
+    hipLaunchKernelGGL((k_tx_fill<false, true>), dim3(mv_grid(quads, TX_THREADS)), dim3(TX_THREADS), 0, s, images, (int)views, (int)H, (int)W,
+                       pixel_center, label, screen, order, (long long)nf, (const float*)nullptr, (const int*)nullptr, 0ll, (const double*)nullptr, L,
+                       (unsigned)fallback_r, (unsigned)fallback_g, (unsigned)fallback_b, (unsigned*)texture, (unsigned*)valid, corner_node, g,
+                       (long long)nodes, (unsigned long long*)ws);
     return mv_check(hipGetLastError(), what);
 }
 

@@ -72,11 +72,13 @@ MAX_FACES = 1 << K.MVSDF_TX_MAX_FACES_LOG2
 class TexturedMesh:
     """The result of build_atlas: mesh (the Mesh that was textured), uv fp32 [F,3,2], texture uint8 [Ht,Wt,3], valid uint8 [Ht,Wt] (1: the texel
     was gathered from a photograph), face_view int32 [F] (-1: no view), patch int32 [F,4] = (x0, y0, n, half), all on the device; density, the
-    texel density finally used; raster, the Raster behind the labels."""
+    texel density finally used; raster, the Raster behind the labels; screen fp64 [F,6], order int32 [F] and counts (seven ints): what the fill
+    read, which seams.level_atlas reads again."""
 
-    def __init__(self, mesh, uv, texture, valid, face_view, patch, density, raster=None, score=None):
+    def __init__(self, mesh, uv, texture, valid, face_view, patch, density, raster=None, score=None, screen=None, order=None, counts=None):
         self.mesh, self.uv, self.texture, self.valid, self.face_view, self.patch = mesh, uv, texture, valid, face_view, patch
         self.density, self.raster, self.score = density, raster, score
+        self.screen, self.order, self.counts = screen, order, counts
 
     def export(self, path):
         """write `path` (.obj: mtllib, usemtl, v, vn, one vt per face corner, f a/t/a b/t/b c/t/c; floats as %.9g), <stem>.mtl (map_Kd <stem>.png)
@@ -178,11 +180,14 @@ def _fill(img, o, label, screen, order, counts, verts, faces, Pd, fallback, reco
 
 def build_atlas(mesh, images, P=None, cams=None, pixel_center=0.5, masks=None, raster=None, texel_density=1.0, max_size=8192,
                 fallback=(128, 128, 128), depth_tol=0.01, cos_min=0.0, ignore_normals=False, large_face_pixels=None, view_chunk=None,
-                recompute=False):
+                recompute=False, level_seams=False, level_options=None):
     """The module's atlas of `mesh` (device tensors, world coordinates) from images uint8 [V,H,W,3] -> TexturedMesh.  The mesh is drawn into the
     cameras first (rasterize with large_face_pixels / view_chunk) unless `raster` holds that already.  recompute=True lets the fill project the
-    face's corners again instead of reading the table step 1 wrote (the same bits; for measuring)."""
+    face's corners again instead of reading the table step 1 wrote (the same bits; for measuring).  level_seams=True corrects the texture with
+    seams.level_atlas (level_options: its smoothness, anchor, cg_iters, cg_tol, info); labels, UVs, patches and valid stay as they are."""
     what = 'build_atlas'
+    if level_options is not None and not isinstance(level_options, dict):
+        raise ValueError('%s: level_options must be a dict, got %s' % (what, type(level_options).__name__))
     R._mesh(mesh, what)
     img = torch.as_tensor(images)
     if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8:
@@ -236,7 +241,11 @@ def build_atlas(mesh, images, P=None, cams=None, pixel_center=0.5, masks=None, r
     order, patch, uv = _pack(cls, counts, ws)
     v, f = mesh.vertices.contiguous(), mesh.faces.to(dev).contiguous()
     texture, valid = _fill(img, o, label, screen, order, counts, v, f, torch.from_numpy(Pm).to(dev), fb, recompute)
-    return TexturedMesh(mesh, uv, texture, valid, label, patch, d, raster, score)
+    t = TexturedMesh(mesh, uv, texture, valid, label, patch, d, raster, score, screen, order, [int(c) for c in counts])
+    if level_seams:
+        from . import seams
+        t = seams.level_atlas(t, img, P=Pm, pixel_center=o, fallback=fb, **(level_options or {}))
+    return t
 
 
 def texture_mesh_from_scene(mesh, data_dir, masks=True, **kw):

@@ -2,12 +2,14 @@
 """Give a mesh a texture atlas from the input photographs of a scene, on the GPU:
 
     python tools/texture_mesh.py IN OUT.obj --data_dir SCENE [--density D] [--max_size S] [--faces N | --cell C] [--no_masks]
+                                 [--level_seams [--seam_smoothness L]]
 
 IN is any mesh in world coordinates that load_mesh reads (OBJ / PLY), for example the evaluation's surface_world_coordinates_<epoch>.obj.  With
 --faces N or --cell C it is simplified first (Mesh.simplify(target_faces=N) / (cell=C)).  The mesh is drawn into the cameras of
 SCENE/cameras_hd.npz (world_mat_i, pixel centres at integer coordinates); every face takes the view of SCENE/image_hd/ that sees it largest and
 gets a patch of the atlas at --density texels per image pixel (mvsdf_amd/texture.py states the definition).  Visibility is also masked by
-SCENE/mask_hd/ unless --no_masks.  Faces that no view sees are grey.  Written: OUT.obj with vt / mtllib, OUT.mtl and OUT.png beside it."""
+SCENE/mask_hd/ unless --no_masks.  Faces that no view sees are grey.  With --level_seams the
+colours are levelled across the label boundaries (mvsdf_amd/seams.py; only the PNG's colours change).  Written: OUT.obj with vt / mtllib, OUT.mtl and OUT.png beside it."""
 import argparse
 import os
 import sys
@@ -29,6 +31,8 @@ def parser():
     p.add_argument('--depth_tol', type=float, default=0.01, help='a vertex is visible when its depth is within (1 + depth_tol) of the drawn depth')
     p.add_argument('--cos_min', type=float, default=0.0, help='views whose ray meets the face normal at a cosine not above this are left out')
     p.add_argument('--ignore_normals', default=False, action='store_true', help='faces with a zero normal take every view that sees them')
+    p.add_argument('--level_seams', default=False, action='store_true', help='level exposure differences across label boundaries (seams.level_atlas)')
+    p.add_argument('--seam_smoothness', type=float, default=None, help='the weight of the smoothness entries of the levelling (default 0.1)')
     return p
 
 
@@ -39,6 +43,8 @@ def main(argv=None):
         p.exit(1, 'texture_mesh.py: %s: no such file\n' % args.in_file)
     if os.path.splitext(args.out_file)[1].lower() != '.obj':
         p.exit(1, 'texture_mesh.py: %s: the output is an .obj (with its .mtl and .png beside it)\n' % args.out_file)
+    if args.seam_smoothness is not None and not args.level_seams:
+        p.exit(1, 'texture_mesh.py: --seam_smoothness needs --level_seams\n')
     from mvsdf_amd import texture
     from mvsdf_amd.mesh import load_mesh
     mesh = load_mesh(args.in_file).to('cuda')
@@ -48,11 +54,16 @@ def main(argv=None):
         if mesh is None:
             p.exit(1, 'texture_mesh.py: no face survives the simplification\n')
         print('[texture] simplified: %d -> %d faces' % (n, len(mesh)))
+    level, info = {}, {}
+    if args.level_seams:
+        level = dict(level_seams=True, level_options=dict(info=info, **({} if args.seam_smoothness is None else dict(smoothness=args.seam_smoothness))))
     out = texture.texture_mesh_from_scene(mesh, args.data_dir, masks=not args.no_masks, texel_density=args.density, max_size=args.max_size,
-                                          depth_tol=args.depth_tol, cos_min=args.cos_min, ignore_normals=args.ignore_normals)
+                                          depth_tol=args.depth_tol, cos_min=args.cos_min, ignore_normals=args.ignore_normals, **level)
     seen = int((out.face_view >= 0).sum())
     print('[texture] %d of %d faces textured from %d views; atlas %d x %d at %.6g texels per pixel, %.1f%% of its texels from photographs'
           % (seen, len(mesh), out.raster.depth.shape[0], out.texture.shape[1], out.texture.shape[0], out.density, 100.0 * float(out.valid.float().mean())))
+    if args.level_seams:
+        print('[texture] seams levelled: %d nodes, %d adjacency entries, %s iterations' % (info['nodes'], info['nnz'], '/'.join(str(i) for i in info['iterations'])))
     out.export(args.out_file)
     return out
 

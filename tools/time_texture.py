@@ -10,7 +10,14 @@ bytes) over its time are also given as a share of the 6.3e12 B/s that tools/time
 of their header, which waits for the stream.  For the split by kernel run the script under rocprofv3 --kernel-trace --stats in a run of its
 own (--repeats 1).
 
+With --level_seams the stages of seam levelling (mvsdf_amd/seams.py) are timed in the same repeats: the graph build (it includes the read of its
+header), the node colours, one A x, a whole solve (with its iteration counts) and the levelled fill, which stands next to the plain fill of the
+same repeat.  One A x is also given in bytes moved (per adjacency entry 4 bytes of index and 24 of gathered x; per node 16 of offsets, 4 of the
+seam count, 24 of x and 24 written) as a share of 6.3e12 B/s, and next to the same product by torch.sparse_csr's fp64 mat-vec on the same
+graph, with the largest difference between the two.
+
     python tools/time_texture.py [--resolution 512 --faces 50000 --views 49 --hw 1200,1600 --density 1.0 --max_size 8192 --repeats 5]
+                                 [--level_seams [--seam_smoothness 0.1 --cg_iters 200]]
 """
 import argparse
 import json
@@ -37,6 +44,9 @@ def parser():
     ap.add_argument('--max_size', type=int, default=8192)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--width', type=int, default=256, help='hidden width of the synthetic model')
+    ap.add_argument('--level_seams', default=False, action='store_true', help='also time the stages of seam levelling')
+    ap.add_argument('--seam_smoothness', type=float, default=0.1)
+    ap.add_argument('--cg_iters', type=int, default=200)
     return ap
 
 
@@ -74,6 +84,11 @@ def main(argv=None):
     Pd = torch.from_numpy(P).cuda()
     names = ('face_views_ms', 'count_pass_ms', 'pack_ms', 'fill_table_ms', 'fill_recompute_ms')
     runs = {k: [] for k in names}
+    if a.level_seams:
+        from mvsdf_amd import seams as SL
+    lnames = ('seam_graph_ms', 'node_colors_ms', 'apply_ms', 'solve_ms', 'fill_levelled_ms', 'sparse_csr_ms')
+    lruns = {k: [] for k in lnames}
+    anchor = 1e-3
     passes = 0
     for rep in range(a.repeats + 1):                                  # the first round warms up
         ev = _events(6)
@@ -100,6 +115,36 @@ def main(argv=None):
         if rep:
             for k, name in enumerate(names):
                 runs[name].append(ev[k].elapsed_time(ev[k + 1]))
+        if a.level_seams:
+            tm = X.TexturedMesh(mesh, uv, tex, valid, label, patch, d, raster, score, screen, order, [int(c) for c in counts])
+            le = _events(7)
+            le[0].record()
+            graph = SL.seam_graph(mesh, label, views=a.views)
+            le[1].record()
+            fcol = SL.node_colors(graph, mesh, images, P=P)
+            le[2].record()
+            ax = SL.apply_operator(graph, fcol, a.seam_smoothness, anchor)
+            le[3].record()
+            gsol, sinfo = SL.solve_levels(graph, fcol, a.seam_smoothness, anchor, a.cg_iters)
+            le[4].record()
+            tex3, valid3 = SL.levelled_fill(tm, images, graph, gsol)
+            if rep == 0:                                              # the yardstick's matrix, built once: A as torch.sparse_csr
+                K = graph.nodes
+                deg = (graph.adj_off[1:] - graph.adj_off[:-1])
+                rows = torch.repeat_interleave(torch.arange(K, device='cuda'), deg)
+                pos = torch.arange(graph.nnz, device='cuda') - graph.adj_off[:-1][rows]
+                w = torch.where(pos < graph.adj_seam.long()[rows], 1.0, a.seam_smoothness).double()
+                diag = torch.zeros(K, dtype=torch.float64, device='cuda').index_add_(0, rows, w) + anchor
+                A = torch.sparse_coo_tensor(torch.stack([torch.cat([rows, torch.arange(K, device='cuda')]), torch.cat([graph.adj_node.long(), torch.arange(K, device='cuda')])]),
+                                            torch.cat([-w, diag]), (K, K)).coalesce().to_sparse_csr()
+            le[5].record()
+            ax2 = A @ fcol
+            le[6].record()
+            torch.cuda.synchronize()
+            assert torch.equal(valid3, valid)
+            if rep:
+                for k, name in enumerate(lnames):
+                    lruns[name].append(le[k].elapsed_time(le[k + 1]))
     med = lambda x: round(float(np.median(x)), 3)                     # noqa: E731
     Wt, Ht, T = X.atlas_size(counts)
     n_valid = int(valid.sum())
@@ -115,6 +160,18 @@ def main(argv=None):
         res[name]['bytes_per_s'] = float('%.4g' % rate)
         res[name]['share_of_6.3e12'] = round(rate / PEAK_BYTES_PER_S, 4)
         res[name]['texels_per_s'] = float('%.4g' % (Wt * Ht / (res[name]['median'] * 1e-3)))
+    if a.level_seams:
+        K, nnz = graph.nodes, graph.nnz
+        for name in lnames:
+            res[name] = {'median': med(lruns[name]), 'runs': [round(x, 3) for x in lruns[name]]}
+        abytes = 28 * nnz + 68 * K
+        rate = abytes / (res['apply_ms']['median'] * 1e-3)
+        res['apply_ms'].update({'bytes': abytes, 'bytes_per_s': float('%.4g' % rate), 'share_of_6.3e12': round(rate / PEAK_BYTES_PER_S, 4)})
+        res['sparse_csr_ms']['max_abs_difference'] = float((ax - ax2).abs().max())
+        res['sparse_csr_ms']['max_abs_value'] = float(ax.abs().max())
+        res.update({'nodes': K, 'adjacency_entries': nnz, 'seam_nodes': int((graph.adj_seam > 0).sum()), 'cg_iterations': sinfo['iterations'],
+                    'cg_rho': sinfo['rho'], 'cg_rho0': sinfo['rho0'], 'seam_smoothness': a.seam_smoothness, 'anchor': anchor,
+                    'levelled_texels_changed': int((tex3 != tex).any(-1).sum())})
     print(json.dumps(res), flush=True)
     return res
 
