@@ -133,19 +133,18 @@ int mvsdf_fold_backward_net(int n_layers, const float* const* v, const float* co
 /* backward of the fold: dW[N][K] -> dv[N][K], dg[N]    */
 int mvsdf_fold_backward(const float* v, const float* g, const float* dW, int N, int K, float* dv, float* dg, void* stream);
 
-/* bytes of one layer's bf16 pack in the layout of v_mfma_f32_16x16x32_bf16 (wp16[l] of trace_dtype 3 / 4; three times that for trace_dtype 5);
- * nsplit = 0 (duplicated hi / lo input columns belonged to trace_dtype 1, removed in round 5). */
-size_t mvsdf_packed_bf16_bytes(int N, int K, int nsplit);
+/* bytes of one layer's bf16 pack in the layout of v_mfma_f32_16x16x32_bf16 (wp16[l] of trace_dtype 3 / 4; three times that for trace_dtype 5) */
+size_t mvsdf_packed_bf16_bytes(int N, int K);
 /* trace_dtype = 2: fp32 MFMA packs (layout of mvsdf_fold_pack's wp) of the folded weights w[l] rounded to bf16 (nearest even) */
 int mvsdf_pack_bf16w_net(int n_layers, const float* const* w, const int* N, const int* K, float* const* wp_rounded, void* stream);
 /* trace_dtype = 3 / 4: bf16 packs (v_mfma_f32_16x16x32_bf16 B-operand layout) WITHOUT duplicated columns (the positional-encoding inputs are split into bf16 terms like
- * every other activation); wp16[l]: mvsdf_packed_bf16_bytes(N, K, 0) bytes.  idr.py:77-94 on bf16-rounded weights. */
+ * every other activation); wp16[l]: mvsdf_packed_bf16_bytes(N, K) bytes.  idr.py:77-94 on bf16-rounded weights. */
 int mvsdf_pack_bf16s_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wp16, void* stream);
 /* trace_dtype = 5: the folded fp32 weights as three bf16 terms (t0 = bf16(w), t1 = bf16(w - t0), t2 = bf16(w - t0 - t1)), layout of mvsdf_pack_bf16s_net
- * with a k-block's three term fragments behind each other; wp16[l]: 3 * mvsdf_packed_bf16_bytes(N, K, 0) bytes.  idr.py:77-94 on the fp32 weights.
+ * with a k-block's three term fragments behind each other; wp16[l]: 3 * mvsdf_packed_bf16_bytes(N, K) bytes.  idr.py:77-94 on the fp32 weights.
  * The weights must be finite with |w| <= 0x7f7f7fff as a bit pattern (the largest float whose bf16 rounding stays finite); |w| < 2^-40 packs as +0. */
 int mvsdf_pack_bf16x3_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wp16, void* stream);
-/* the same three-term pack of W_l^T (N, K are W_l's dims): 3 * mvsdf_packed_bf16_bytes(K, N, 0) bytes per layer -- MvsdfNetDesc.wx3 of the transposed descriptor */
+/* the same three-term pack of W_l^T (N, K are W_l's dims): 3 * mvsdf_packed_bf16_bytes(K, N) bytes per layer -- MvsdfNetDesc.wx3 of the transposed descriptor */
 int mvsdf_pack_bf16x3t_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wx3t, void* stream);
 
 /* ImplicitNetwork.forward(x)[:, 0] (idr.py:77-94) for n points: the tracing MLP alone. */

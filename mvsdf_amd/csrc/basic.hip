@@ -1,5 +1,6 @@
-// basic.hip -- weight-norm fold + MFMA packing, camera rays, the stand-alone tracing-MLP kernel and the
-// device self-test of det_math.  C ABI entry points for these live at the bottom (see include/mvsdf_hip.h).
+// basic.hip -- weight-norm fold + MFMA packing, camera rays, the stand-alone tracing-MLP kernel and the device self-test of det_math.  The packs' layout and
+// values are pack_layout.h's: the kernels here only choose where an element comes from (global W, its transpose, or k_step_prologue's LDS tile) and where
+// the block goes.  C ABI entry points for these live in the middle (see include/mvsdf_hip.h), the training step's prologue at the bottom.
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -7,41 +8,58 @@
 #include "trace_params.h"
 #include "capi_util.h"
 #include "det_math_pk.h"
+#include "step_internal.h"
 
-// ---- weight norm (idr.py:70-71): one wave per output row.  The row is loaded coalesced; lane 0 then walks it through
-// v_readlane in ascending k -- the SAME k-ascending fmaf chain as the CPU restatement (bit-exact), at ~1 us per row. ----
-__global__ __launch_bounds__(256) void k_fold(const float* __restrict__ v, const float* __restrict__ g, int N, int K, float* __restrict__ w) {
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= N) return;
-    const float* vr = v + (size_t)j * K;
+// ---- weight norm (idr.py:70-71): sum of squares of one row [K] by one wave.  The row is loaded coalesced in chunks of 64; every lane then walks a chunk through
+// v_readlane in ascending k (uniform i) -- the SAME k-ascending fmaf chain as the CPU restatement (bit-exact), at ~1 us per row. ----
+__device__ __forceinline__ float mv_norm_chain(const float* __restrict__ vr, int K, int lane) {
     float ss = 0.0f;
     for (int k0 = 0; k0 < K; k0 += 64) {
         const float mine = (k0 + lane < K) ? vr[k0 + lane] : 0.0f;
         const int n = min(64, K - k0);
         for (int i = 0; i < n; ++i) {
-            const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), i));   // uniform i -> v_readlane
+            const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), i));
             ss = fmaf(x, x, ss);
         }
     }
-    const float a = g[j] / sqrtf(ss);
-    for (int k = lane; k < K; k += 64) w[(size_t)j * K + k] = vr[k] * a;
+    return ss;
 }
 
-// wp[ct][kb][lane][s] = W[ct*16 + (lane&15)][kb*16 + 4s + (lane>>4)];  transposed=1 packs W^T ([K][N] seen as out=K, in=N)
-__global__ void k_pack(const float* __restrict__ w, int N, int K, int transposed, float* __restrict__ wp) {
-    const int No = transposed ? K : N, Ko = transposed ? N : K;
-    const int KB = mv_kpad(Ko) / 16;
-    const size_t total = (size_t)mv_ceil16(No) * mv_kpad(Ko);
+// ---- packs.  Element sources: (o, k) of the matrix being packed -> its value, +0 outside it.
+struct MvSrcW {                                     // global W [N][K], or (tr) its transpose: out = K, in = N
+    const float* w; int N, K, tr;
+    __device__ int No() const { return tr ? K : N; }
+    __device__ int Ko() const { return tr ? N : K; }
+    __device__ float operator()(int o, int k) const { return (o < No() && k < Ko()) ? (tr ? w[(size_t)k * K + o] : w[(size_t)o * K + k]) : 0.0f; }
+};
+// A whole pack, grid-stride over its flat index: KW = 16 (fp32 fragments) or 32 (bf16), TERMS fragments per k-block; val(w, term) -> the stored element
+template <int KW, int TERMS, class T, class SRC, class VAL>
+__device__ __forceinline__ void mv_pack_flat(T* __restrict__ dst, const SRC src, const VAL val) {
+    const int KB = KW == 16 ? mv_kpad(src.Ko()) / 16 : mv_bf_kb(src.Ko());
+    const size_t total = (size_t)TERMS * mv_ceil16(src.No()) * KB * KW;
+    constexpr int SH = KW == 16 ? 8 : 9;                                     // 256- / 512-element blocks
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int s = idx & 3, lane = (idx >> 2) & 63;
-        const size_t blk = idx >> 8;
-        const int kb = (int)(blk % KB), ct = (int)(blk / KB);
-        const int o = ct * 16 + (lane & 15), i = kb * 16 + 4 * s + (lane >> 4);
-        float val = 0.0f;
-        if (o < No && i < Ko) val = transposed ? w[(size_t)i * K + o] : w[(size_t)o * K + i];
-        wp[idx] = val;
+        const MvBlock b = mv_block_at(idx >> SH, KB, TERMS);
+        const int e = (int)idx & ((1 << SH) - 1);
+        const MvFrag f = KW == 16 ? mv_frag_f32(e) : mv_frag_bf16(e);
+        dst[idx] = val(src(b.ct * 16 + f.row, b.kb * KW + f.k), b.term);
     }
 }
+// One tile row of a pack (all KB k-blocks of 16 rows) from k_step_prologue's LDS tile [16][ld] of those rows (rows beyond the matrix are zero there)
+template <int KW, int TERMS, class T, class VAL>
+__device__ __forceinline__ void mv_pack_tile_row(T* __restrict__ dst, int KB, const float* tile, int ld, int K, int tid, const VAL val) {
+    constexpr int SH = KW == 16 ? 8 : 9;
+    for (int idx = tid; idx < (KB * TERMS) << SH; idx += 1024) {
+        const int blk = idx >> SH, term = blk % TERMS, kb = blk / TERMS, e = idx & ((1 << SH) - 1);      // (TERMS is a constant: no division instruction)
+        const MvFrag f = KW == 16 ? mv_frag_f32(e) : mv_frag_bf16(e);
+        const int k = kb * KW + f.k;
+        dst[idx] = val(k < K ? tile[f.row * ld + k] : 0.0f, term);
+    }
+}
+struct MvValF32 { __device__ float operator()(float w, int) const { return w; } };
+struct MvValRound { __device__ float operator()(float w, int) const { return mv_bf_round(w); } };
+struct MvValBf16 { __device__ uint16_t operator()(float w, int) const { return mv_f2bf(w); } };
+struct MvValX3 { __device__ uint16_t operator()(float w, int term) const { return mv_x3_term(w, term); } };
 
 // ---- whole-network variants: one launch folds / packs every layer (blockIdx.y selects the layer); the layer list may span several
 // networks (SDF + rendering net of a step: 9 + 5 layers) ----
@@ -65,16 +83,7 @@ __global__ __launch_bounds__(256) void k_fold_net(FoldNetArgs a) {
         for (int k = lane; k < K; k += 64) wr0[k] = vr[k];
         return;
     }
-    float ss = 0.0f;
-    for (int k0 = 0; k0 < K; k0 += 64) {
-        const float mine = (k0 + lane < K) ? vr[k0 + lane] : 0.0f;
-        const int n = min(64, K - k0);
-        for (int i = 0; i < n; ++i) {
-            const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), i));
-            ss = fmaf(x, x, ss);
-        }
-    }
-    const float s = a.g[l][j] / sqrtf(ss);
+    const float s = a.g[l][j] / sqrtf(mv_norm_chain(vr, K, lane));
     float* wr = a.w[l] + (size_t)j * K;
     for (int k = lane; k < K; k += 64) wr[k] = vr[k] * s;
 }
@@ -82,21 +91,7 @@ __global__ __launch_bounds__(256) void k_fold_net(FoldNetArgs a) {
 __global__ void k_pack_net(FoldNetArgs a) {
     const int l = blockIdx.y >> 1, transposed = blockIdx.y & 1;
     float* wp = transposed ? a.wpT[l] : a.wp[l];
-    if (!wp) return;
-    const float* w = a.w[l];
-    const int N = a.N[l], K = a.K[l];
-    const int No = transposed ? K : N, Ko = transposed ? N : K;
-    const int KB = mv_kpad(Ko) / 16;
-    const size_t total = (size_t)mv_ceil16(No) * mv_kpad(Ko);
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int s = idx & 3, lane = (idx >> 2) & 63;
-        const size_t blk = idx >> 8;
-        const int kb = (int)(blk % KB), ct = (int)(blk / KB);
-        const int o = ct * 16 + (lane & 15), i = kb * 16 + 4 * s + (lane >> 4);
-        float val = 0.0f;
-        if (o < No && i < Ko) val = transposed ? w[(size_t)i * K + o] : w[(size_t)o * K + i];
-        wp[idx] = val;
-    }
+    if (wp) mv_pack_flat<16, 1>(wp, MvSrcW{a.w[l], a.N[l], a.K[l], transposed}, MvValF32());
 }
 
 __global__ void k_fold_bwd_net(FoldNetArgs a) {
@@ -171,11 +166,9 @@ __global__ void k_fold_bwd(const float* __restrict__ v, const float* __restrict_
     if (lane == 0) dg[j] = dgj;
 }
 
-// ---- rend_util.get_camera_params + lift (rend_util.py:48-75, 87-100) ----
-__global__ void k_camera_rays(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin, int B, int P,
-                              float* __restrict__ dirs, float* __restrict__ cam_loc) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * P) return;
+// ---- rend_util.get_camera_params + lift (rend_util.py:48-75, 87-100): ray idx of B * P; the first ray of a view writes the view's camera centre ----
+__device__ __forceinline__ void mv_camera_ray(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin, int P, int idx,
+                                              float* __restrict__ dirs, float* __restrict__ cam_loc) {
     const int b = idx / P;
     const float* p = pose + 16 * b;
     const float* k = Kin + 16 * b;
@@ -197,6 +190,11 @@ __global__ void k_camera_rays(const float* __restrict__ uv, const float* __restr
     dirs[3 * (size_t)idx] = wv[0] / nn;
     dirs[3 * (size_t)idx + 1] = wv[1] / nn;
     dirs[3 * (size_t)idx + 2] = wv[2] / nn;
+}
+__global__ void k_camera_rays(const float* __restrict__ uv, const float* __restrict__ pose, const float* __restrict__ Kin, int B, int P,
+                              float* __restrict__ dirs, float* __restrict__ cam_loc) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < B * P) mv_camera_ray(uv, pose, Kin, P, idx, dirs, cam_loc);
 }
 
 // ---- rend_util.get_sphere_intersection (rend_util.py:141-162), same op order as the tracer's fused copy ----
@@ -237,56 +235,22 @@ __global__ __launch_bounds__(64 * NW) void k_sdf_col0(MvNet net, const float* __
     if (tid < ROWS && row0 + tid < n) y[row0 + tid] = out[tid];
 }
 
-// bf16 packs (tile_engine_bf16.h): one thread per packed element
-struct PackBfArgs { const float* w[MV_MAXL]; uint16_t* wp[MV_MAXL]; int N[MV_MAXL], K[MV_MAXL], nsplit[MV_MAXL]; int tr; };   // tr (k_pack_bf16x3_net): pack W^T (N, K stay W's dims)
+// the packs of the bf16 engines and the rounded fp32 pack: blockIdx.y selects the layer
+struct PackBfArgs { const float* w[MV_MAXL]; uint16_t* wp[MV_MAXL]; int N[MV_MAXL], K[MV_MAXL]; int tr; };   // tr (k_pack_bf16x3_net): pack W^T (N, K stay W's dims)
+// trace_dtype = 3 / 4: one bf16 term
 __global__ void k_pack_bf16_net(PackBfArgs a) {
     const int l = blockIdx.y;
-    const int N = a.N[l], K = a.K[l], ns = a.nsplit[l], KB = mv_bf_kb(K, ns);
-    const size_t total = mv_packed_bf16_elems(N, K, ns);
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = idx & 7, lane = (idx >> 3) & 63;
-        const size_t blk = idx >> 9;
-        const int kb = (int)(blk % KB), ct = (int)(blk / KB);
-        const int o = ct * 16 + (lane & 15), kp = kb * 32 + 8 * (lane >> 4) + i;
-        const int col = kp < K ? kp : (kp < K + ns ? kp - ns : -1);          // the lo copy of a split column shares the hi column's weight
-        a.wp[l][idx] = (o < N && col >= 0) ? mv_f2bf(a.w[l][(size_t)o * K + col]) : (uint16_t)0;
-    }
+    mv_pack_flat<32, 1>(a.wp[l], MvSrcW{a.w[l], a.N[l], a.K[l], 0}, MvValBf16());
 }
-
-// trace_dtype = 5: the packs of tile_engine_bf16s.h's weight-term engine: w = t0 + t1 + t2 exactly, wp[((ct * KB + kb) * 3 + term) * 64 + lane][8]
+// trace_dtype = 5 and the x3 chains: w = t0 + t1 + t2 exactly, a k-block's three term fragments behind each other
 __global__ void k_pack_bf16x3_net(PackBfArgs a) {
     const int l = blockIdx.y;
-    const int N = a.tr ? a.K[l] : a.N[l], K = a.tr ? a.N[l] : a.K[l], KB = mv_bf_kb(K, 0);      // dims of the matrix being packed (W or W^T)
-    const size_t total = 3 * mv_packed_bf16_elems(N, K, 0);
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = idx & 7, lane = (idx >> 3) & 63;
-        const size_t blk = idx >> 9;
-        const int term = (int)(blk % 3), kb = (int)((blk / 3) % KB), ct = (int)(blk / 3 / KB);
-        const int o = ct * 16 + (lane & 15), kp = kb * 32 + 8 * (lane >> 4) + i;
-        uint16_t v = 0;
-        if (o < N && kp < K) {
-            float r = a.tr ? a.w[l][(size_t)kp * N + o] : a.w[l][(size_t)o * K + kp];
-            if (fabsf(r) < 9.094947017729282e-13f) r = 0.0f;                            // |w| < 2^-40 -> 0 (tile_engine_bf16s.h, MV_X3_FLUSH: the oracle does the same)
-            v = mv_f2bf(r);
-            for (int t = 0; t < term; ++t) { r = r - mv_bf2f(v); v = mv_f2bf(r); }       // every subtraction is exact
-        }
-        a.wp[l][idx] = v;
-    }
+    mv_pack_flat<32, 3>(a.wp[l], MvSrcW{a.w[l], a.N[l], a.K[l], a.tr}, MvValX3());
 }
-
-// trace_dtype = 2: fp32 packs of the bf16-rounded weights (layout of k_pack, non-transposed)
+// trace_dtype = 2: fp32 packs of the bf16-rounded weights (layout of k_pack_net, non-transposed)
 __global__ void k_pack_round_net(PackBfArgs a) {
     const int l = blockIdx.y;
-    const int N = a.N[l], K = a.K[l], KB = mv_kpad(K) / 16;
-    float* wp = (float*)a.wp[l];
-    const size_t total = mv_packed_floats(N, K);
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int s = idx & 3, lane = (idx >> 2) & 63;
-        const size_t blk = idx >> 8;
-        const int kb = (int)(blk % KB), ct = (int)(blk / KB);
-        const int o = ct * 16 + (lane & 15), i = kb * 16 + 4 * s + (lane >> 4);
-        wp[idx] = (o < N && i < K) ? mv_bf2f(mv_f2bf(a.w[l][(size_t)o * K + i])) : 0.0f;
-    }
+    mv_pack_flat<16, 1>((float*)a.wp[l], MvSrcW{a.w[l], a.N[l], a.K[l], 0}, MvValRound());
 }
 
 template <int MT, int NTW, bool CARRY, class NET>
@@ -364,17 +328,6 @@ int mvsdf_version(void) { return 100; }
 
 size_t mvsdf_packed_floats(int N, int K) { return mv_packed_floats(N, K); }
 
-int mvsdf_fold_pack(const float* v, const float* g, int N, int K, float* w, float* wp, float* wpT, void* stream) {
-    if (!v || !g || N <= 0 || K <= 0 || !w) return mv_fail(-1, "mvsdf_fold_pack: bad arguments (w must be given)");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_fold, dim3((N + 3) / 4), dim3(256), 0, s, v, g, N, K, w);
-    const size_t total = mv_packed_floats(N, K);
-    const int blocks = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-    if (wp) hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, s, w, N, K, 0, wp);
-    if (wpT) hipLaunchKernelGGL(k_pack, dim3(blocks), dim3(256), 0, s, w, N, K, 1, wpT);
-    return mv_check(hipGetLastError(), "mvsdf_fold_pack");
-}
-
 static int fill_fold_args(FoldNetArgs& a, int n_layers, const int* N, const int* K, int* maxN, size_t* maxTot) {
     if (n_layers < 1 || n_layers > MV_FOLD_MAXL || !N || !K) return mv_fail(-1, "fold (net): bad layer count / dims");
     memset(&a, 0, sizeof(a));
@@ -390,6 +343,26 @@ static int fill_fold_args(FoldNetArgs& a, int n_layers, const int* N, const int*
     return 0;
 }
 
+// fold (one launch) + pack of W and W^T (one launch) of the layers of `a`
+static int launch_fold_pack(const FoldNetArgs& a, int maxN, size_t maxTot, void* stream, const char* where) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_fold_net, dim3((maxN + 3) / 4, a.n_layers), dim3(256), 0, s, a);
+    const int blocks = (int)((maxTot + 255) / 256 < 256 ? (maxTot + 255) / 256 : 256);
+    hipLaunchKernelGGL(k_pack_net, dim3(blocks, 2 * a.n_layers), dim3(256), 0, s, a);
+    return mv_check(hipGetLastError(), where);
+}
+
+/* one layer: mvsdf_fold_pack_net's kernels on a one-layer list (g is required here; wp / wpT may be NULL) */
+int mvsdf_fold_pack(const float* v, const float* g, int N, int K, float* w, float* wp, float* wpT, void* stream) {
+    if (!v || !g || N <= 0 || K <= 0 || !w) return mv_fail(-1, "mvsdf_fold_pack: bad arguments (w must be given)");
+    FoldNetArgs a;
+    int maxN; size_t maxTot;
+    int rc = fill_fold_args(a, 1, &N, &K, &maxN, &maxTot);
+    if (rc) return rc;
+    a.v[0] = v; a.g[0] = g; a.w[0] = w; a.wp[0] = wp; a.wpT[0] = wpT;
+    return launch_fold_pack(a, maxN, maxTot, stream, "mvsdf_fold_pack");
+}
+
 /* every layer of a network in one call: fold (one launch) + pack W and W^T (one launch).  Pointer arrays are HOST arrays of
  * device pointers; wp / wpT entries may be NULL. */
 int mvsdf_fold_pack_net(int n_layers, const float* const* v, const float* const* g, const int* N, const int* K, float* const* w,
@@ -403,11 +376,7 @@ int mvsdf_fold_pack_net(int n_layers, const float* const* v, const float* const*
         if (!v[l] || !w[l]) return mv_fail(-1, "mvsdf_fold_pack_net: null layer pointer");    // g[l] NULL: layer without weight norm (w = v)
         a.v[l] = v[l]; a.g[l] = g[l]; a.w[l] = w[l]; a.wp[l] = wp[l]; a.wpT[l] = wpT[l];
     }
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_fold_net, dim3((maxN + 3) / 4, n_layers), dim3(256), 0, s, a);
-    const int blocks = (int)((maxTot + 255) / 256 < 256 ? (maxTot + 255) / 256 : 256);
-    hipLaunchKernelGGL(k_pack_net, dim3(blocks, 2 * n_layers), dim3(256), 0, s, a);
-    return mv_check(hipGetLastError(), "mvsdf_fold_pack_net");
+    return launch_fold_pack(a, maxN, maxTot, stream, "mvsdf_fold_pack_net");
 }
 
 int mvsdf_fold_backward_net(int n_layers, const float* const* v, const float* const* g, const float* const* dW, const float* const* db,
@@ -451,7 +420,7 @@ int mvsdf_sphere_intersection(const float* cam_loc, const float* ray_dirs, int B
     return mv_check(hipGetLastError(), "mvsdf_sphere_intersection");
 }
 
-size_t mvsdf_packed_bf16_bytes(int N, int K, int nsplit) { return mv_packed_bf16_elems(N, K, nsplit) * 2; }
+size_t mvsdf_packed_bf16_bytes(int N, int K) { return mv_packed_bf16_elems(N, K) * 2; }
 
 /* trace_dtype = 3 / 4: the bf16 packs without duplicated columns (every activation, the positional encoding included, is split into bf16
  * terms in LDS: tile_engine_bf16s.h) */
@@ -462,8 +431,8 @@ int mvsdf_pack_bf16s_net(int n_layers, const float* const* w, const int* N, cons
     size_t maxTot = 0;
     for (int l = 0; l < n_layers; ++l) {
         if (!w[l] || !wp16[l] || N[l] <= 0 || K[l] <= 0) return mv_fail(-1, "mvsdf_pack_bf16s_net: null layer pointer / bad dims");
-        a.w[l] = w[l]; a.wp[l] = (uint16_t*)wp16[l]; a.N[l] = N[l]; a.K[l] = K[l]; a.nsplit[l] = 0;
-        const size_t t = mv_packed_bf16_elems(N[l], K[l], 0);
+        a.w[l] = w[l]; a.wp[l] = (uint16_t*)wp16[l]; a.N[l] = N[l]; a.K[l] = K[l];
+        const size_t t = mv_packed_bf16_elems(N[l], K[l]);
         if (t > maxTot) maxTot = t;
     }
     const int blocks = (int)((maxTot + 255) / 256 < 256 ? (maxTot + 255) / 256 : 256);
@@ -471,7 +440,7 @@ int mvsdf_pack_bf16s_net(int n_layers, const float* const* w, const int* N, cons
     return mv_check(hipGetLastError(), "mvsdf_pack_bf16s_net");
 }
 
-/* trace_dtype = 5: three-term bf16 packs of the fp32 weights (3 x mvsdf_packed_bf16_bytes(N, K, 0) bytes per layer) */
+/* trace_dtype = 5: three-term bf16 packs of the fp32 weights (3 x mvsdf_packed_bf16_bytes(N, K) bytes per layer) */
 static int pack_x3_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* out, int tr, void* stream) {
     if (n_layers < 1 || n_layers > MV_MAXL || !w || !N || !K || !out) return mv_fail(-1, "mvsdf_pack_bf16x3_net / mvsdf_pack_bf16x3t_net: bad arguments");
     PackBfArgs a;
@@ -480,8 +449,8 @@ static int pack_x3_net(int n_layers, const float* const* w, const int* N, const 
     size_t maxTot = 0;
     for (int l = 0; l < n_layers; ++l) {
         if (!w[l] || !out[l] || N[l] <= 0 || K[l] <= 0) return mv_fail(-1, "mvsdf_pack_bf16x3_net / mvsdf_pack_bf16x3t_net: null layer pointer / bad dims");
-        a.w[l] = w[l]; a.wp[l] = (uint16_t*)out[l]; a.N[l] = N[l]; a.K[l] = K[l]; a.nsplit[l] = 0;
-        const size_t t = 3 * (tr ? mv_packed_bf16_elems(K[l], N[l], 0) : mv_packed_bf16_elems(N[l], K[l], 0));
+        a.w[l] = w[l]; a.wp[l] = (uint16_t*)out[l]; a.N[l] = N[l]; a.K[l] = K[l];
+        const size_t t = 3 * (tr ? mv_packed_bf16_elems(K[l], N[l]) : mv_packed_bf16_elems(N[l], K[l]));
         if (t > maxTot) maxTot = t;
     }
     const int blocks = (int)((maxTot + 255) / 256 < 512 ? (maxTot + 255) / 256 : 512);
@@ -491,7 +460,7 @@ static int pack_x3_net(int n_layers, const float* const* w, const int* N, const 
 int mvsdf_pack_bf16x3_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wp16, void* stream) {
     return pack_x3_net(n_layers, w, N, K, wp16, 0, stream);
 }
-/* the same pack of W^T (N, K: W's dims; 3 x mvsdf_packed_bf16_bytes(K, N, 0) bytes per layer): MvsdfNetDesc.wx3 of the transposed descriptor */
+/* the same pack of W^T (N, K: W's dims; 3 x mvsdf_packed_bf16_bytes(K, N) bytes per layer): MvsdfNetDesc.wx3 of the transposed descriptor */
 int mvsdf_pack_bf16x3t_net(int n_layers, const float* const* w, const int* N, const int* K, void* const* wx3t, void* stream) {
     return pack_x3_net(n_layers, w, N, K, wx3t, 1, stream);
 }
@@ -529,17 +498,19 @@ int mvsdf_det_math(int op, const float* x, int n, float* y0, float* y1, void* st
 
 // ================================================================================================ step prologue (step_internal.h)
 // Everything a training forward needs before the tracer, in ONE launch: the weight-norm fold of every layer of both networks (idr.py:70-71),
-// the MFMA packs of W and W^T, the bf16 packs of the tracing MLP (trace_dtype = 1) and the camera rays (rend_util.py:48-75,87-100) -- the work
-// of k_fold_net, k_pack_net, k_pack_bf16_net and k_camera_rays.  A workgroup owns 16 rows of one layer: its sixteen waves fold one row each
-// (the same serialised fmaf chain over k as k_fold_net: bit-identical), the 16 folded rows stay in LDS and the workgroup writes its tile row of the
-// W pack, its k-block column of the W^T pack and its tile row of the bf16 pack from there.  The last workgroups compute the rays.
+// the MFMA packs of W and W^T, the tracing MLP's pack (MvWp16Mode), the three-term packs of the differentiable chains and the camera rays
+// (rend_util.py:48-75,87-100) -- the work of k_fold_net, k_pack_net, k_pack_round_net / k_pack_bf16_net / k_pack_bf16x3_net and k_camera_rays, over the
+// same definitions: pack_layout.h's maps and values, mv_norm_chain's fold chain (in a second, register-resident schedule for K <= 576) and mv_camera_ray.
+// What is this kernel's own is where the blocks go (rg, kbt) -- tests/test_gpu_weight_packs.py holds it to the stand-alone entries end to end.
+// A workgroup owns 16 rows of one layer: its sixteen waves fold one row each, the 16 folded rows stay in LDS and the workgroup writes its tile row of the
+// W pack, its k-block column of the W^T pack and its tile row of the bf16 packs from there.  The last workgroups compute the rays.
 // 16 waves per workgroup, one row each: a row's norm is a serial fmaf chain of ~K steps (~10 us), so the rows must all run side by side.
 struct ProloArgs {
     FoldNetArgs f;
     int blk0[MV_FOLD_MAXL + 1];          // first workgroup of each layer; blk0[n_layers] = first ray workgroup
- uint16_t* wp16[MV_FOLD_MAXL]; int nsplit[MV_FOLD_MAXL];
+    uint16_t* wp16[MV_FOLD_MAXL];        // optional: the tracing MLP's pack of W_l, in the form wp16_mode names
     uint16_t* wx3[MV_FOLD_MAXL]; uint16_t* wx3T[MV_FOLD_MAXL];   // optional three-term bf16 packs of W_l / W_l^T (the differentiable chains of chain_x3.h)
-    int wp16_mode;                       // 0: bf16 pack; 1: wp16[l] receives the fp32 pack of the bf16-rounded weights (trace_dtype = 2); 2: the three-term bf16 pack (trace_dtype = 5)
+    int wp16_mode;                       // MvWp16Mode
     const float* uv; const float* pose; const float* Kin; int B, P; float* dirs; float* cam_loc;
     uint8_t* ones;                       // optional [B * P]: filled with 1 (the all-ones object mask of the output dict, idr.py:187)
     unsigned long long* counters;        // optional [16]: zeroed (the tracer's device counters: saves its memset node)
@@ -563,27 +534,7 @@ __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
         }
         if (idx >= a.B * a.P) return;
         if (a.ones) a.ones[idx] = 1;
-        const int b = idx / a.P;
-        const float* p = a.pose + 16 * b;
-        const float* k = a.Kin + 16 * b;
-        const float fx = k[0], fy = k[5], cx = k[2], cy = k[6], sk = k[1];
-        const float cl[3] = {p[3], p[7], p[11]};
-        if (idx == b * a.P) { a.cam_loc[3 * b] = cl[0]; a.cam_loc[3 * b + 1] = cl[1]; a.cam_loc[3 * b + 2] = cl[2]; }
-        const float x = a.uv[2 * (size_t)idx] + 0.5f, y = a.uv[2 * (size_t)idx + 1] + 0.5f, z = 1.0f;
-        const float xl = (x - cx + cy * sk / fy - sk * y / fy) / fx * z;
-        const float yl = (y - cy) / fy * z;
-        const float h[4] = {xl, yl, z, 1.0f};
-        float wvv[3];
-        for (int r = 0; r < 3; ++r) {
-            float acc = 0.0f;
-            for (int c = 0; c < 4; ++c) acc = fmaf(p[4 * r + c], h[c], acc);
-            wvv[r] = acc - cl[r];
-        }
-        float nn = sqrtf(wvv[0] * wvv[0] + wvv[1] * wvv[1] + wvv[2] * wvv[2]);
-        if (nn < 1e-12f) nn = 1e-12f;
-        a.dirs[3 * (size_t)idx] = wvv[0] / nn;
-        a.dirs[3 * (size_t)idx + 1] = wvv[1] / nn;
-        a.dirs[3 * (size_t)idx + 2] = wvv[2] / nn;
+        mv_camera_ray(a.uv, a.pose, a.Kin, a.P, idx, a.dirs, a.cam_loc);
         return;
     }
     int l = 0;
@@ -610,7 +561,7 @@ __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
                 const float gj = a.f.g[l][j];
 #pragma unroll
                 for (int c = 0; c < 9; ++c) { const int k = 64 * c + lane; const float x = vr[k < K ? k : K - 1]; mine[c] = k < K ? x : 0.0f; }
-                // the k-ascending fmaf chain of orc_fold, bit for bit.  Full 64-blocks are unrolled with constant lane numbers: the v_readlane of the
+                // mv_norm_chain's k-ascending fmaf chain (orc_fold's, bit for bit) in another schedule.  Full 64-blocks are unrolled with constant lane numbers: the v_readlane of the
                 // elements ahead are independent of the chain and get issued early, so a step costs the fma's latency and not the
                 // readlane -> SGPR -> VALU round trip of a rolled loop (which made this chain ~10 us of the launch's 18)
                 float ss = 0.0f;
@@ -634,119 +585,51 @@ __global__ __launch_bounds__(1024) void k_step_prologue(ProloArgs a) {
 #pragma unroll
                 for (int c = 0; c < 9; ++c) { const int k = 64 * c + lane; if (k < K) { const float x = mine[c] * sc; wr[k] = x; tr[k] = x; } }
             } else {
-                float ss = 0.0f;
-                for (int k0 = 0; k0 < K; k0 += 64) {
-                    const float mine = (k0 + lane < K) ? vr[k0 + lane] : 0.0f;
-                    const int n = min(64, K - k0);
-                    for (int i = 0; i < n; ++i) {
-                        const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine), i));
-                        ss = fmaf(x, x, ss);
-                    }
-                }
-                const float sc = a.f.g[l][j] / sqrtf(ss);
+                const float sc = a.f.g[l][j] / sqrtf(mv_norm_chain(vr, K, lane));
                 for (int k = lane; k < K; k += 64) { const float x = vr[k] * sc; wr[k] = x; tr[k] = x; }
             }
         }
     }
     __syncthreads();
     // ---- pack of W: tile row ct = rg, every k-block
-    const int NT = mv_ceil16(N) / 16, KB = mv_kpad(K) / 16;
-    if (a.f.wp[l] && rg < NT) {
-        float* dst = a.f.wp[l] + (size_t)rg * KB * 256;
-        for (int idx = tid; idx < KB * 256; idx += 1024) {
-            const int s = idx & 3, ln = (idx >> 2) & 63, kb = idx >> 8;
-            const int ol = ln & 15, i = kb * 16 + 4 * s + (ln >> 4);
-            dst[idx] = (i < K) ? tile[ol * ld + i] : 0.0f;                      // rows >= N are zero in the tile
-        }
-    }
-    // ---- pack of W^T: k-block kb' = rg of every tile row ct' (columns of W)
+    const int NT = mv_ceil16(N) / 16, KB = mv_kpad(K) / 16, KB32 = mv_bf_kb(K);
+    if (a.f.wp[l] && rg < NT) mv_pack_tile_row<16, 1>(a.f.wp[l] + (size_t)rg * KB * 256, KB, tile, ld, K, tid, MvValF32());
+    // ---- pack of W^T: k-block kb' = rg of every tile row ct' (columns of W); the tile is W^T's block read across: (row, k) of W^T = tile[k][row]
     if (a.f.wpT[l]) {
         const int NTt = mv_ceil16(K) / 16, KBt = mv_kpad(N) / 16;
         for (int idx = tid; idx < NTt * 256; idx += 1024) {
             const int e = idx & 255, ct = idx >> 8;
-            const int s = e & 3, ln = (e >> 2) & 63;
-            const int o = ct * 16 + (ln & 15), il = 4 * s + (ln >> 4);
-            a.f.wpT[l][((size_t)ct * KBt + rg) * 256 + e] = (o < K) ? tile[il * ld + o] : 0.0f;
+            const MvFrag f = mv_frag_f32(e);
+            const int o = ct * 16 + f.row;
+            a.f.wpT[l][mv_block_index(ct, rg, KBt) * 256 + e] = (o < K) ? tile[f.k * ld + o] : 0.0f;
         }
     }
-    // ---- bf16 pack of the tracing MLP: tile row ct = rg
-    if (a.wp16[l] && rg < NT && a.wp16_mode == 1) {                                 // trace_dtype = 2: the W pack again, values rounded to bf16
-        float* dst = (float*)a.wp16[l] + (size_t)rg * KB * 256;
-        for (int idx = tid; idx < KB * 256; idx += 1024) {
-            const int s = idx & 3, ln = (idx >> 2) & 63, kb = idx >> 8;
-            const int ol = ln & 15, i = kb * 16 + 4 * s + (ln >> 4);
-            dst[idx] = (i < K) ? mv_bf2f(mv_f2bf(tile[ol * ld + i])) : 0.0f;
-        }
-    } else if (a.wp16[l] && rg < NT && a.wp16_mode == 2) {                     // trace_dtype = 5: three bf16 terms of every weight (k_pack_bf16x3_net's layout)
-        const int KB32 = mv_bf_kb(K, 0);
-        uint16_t* dst = a.wp16[l] + (size_t)rg * KB32 * 3 * 512;
-        for (int idx = tid; idx < KB32 * 3 * 512; idx += 1024) {
-            const int i = idx & 7, ln = (idx >> 3) & 63, blk = idx >> 9, term = blk % 3, kb = blk / 3;
-            const int ol = ln & 15, kp = kb * 32 + 8 * (ln >> 4) + i;
-            uint16_t v = 0;
-            if (16 * rg + ol < N && kp < K) {
-                float r = tile[ol * ld + kp];
-                if (fabsf(r) < 9.094947017729282e-13f) r = 0.0f;
-                v = mv_f2bf(r);
-                for (int t = 0; t < term; ++t) { r = r - mv_bf2f(v); v = mv_f2bf(r); }
-            }
-            dst[idx] = v;
-        }
+    // ---- the tracing MLP's pack, tile row ct = rg: the W pack again with values rounded to bf16, one bf16 term, or three
+    if (a.wp16[l] && rg < NT) {
+        if (a.wp16_mode == MV_WP16_ROUNDED_F32) mv_pack_tile_row<16, 1>((float*)a.wp16[l] + (size_t)rg * KB * 256, KB, tile, ld, K, tid, MvValRound());
+        else if (a.wp16_mode == MV_WP16_X3) mv_pack_tile_row<32, 3>(a.wp16[l] + (size_t)rg * KB32 * 3 * 512, KB32, tile, ld, K, tid, MvValX3());
+        else mv_pack_tile_row<32, 1>(a.wp16[l] + (size_t)rg * KB32 * 512, KB32, tile, ld, K, tid, MvValBf16());
     }
-    if (a.wx3[l] && rg < NT) {                                                  // three bf16 terms of every weight (k_pack_bf16x3_net's layout) for the differentiable chains
-        const int KB32 = mv_bf_kb(K, 0);
-        uint16_t* dst = a.wx3[l] + (size_t)rg * KB32 * 3 * 512;
-        for (int idx = tid; idx < KB32 * 3 * 512; idx += 1024) {
-            const int i = idx & 7, ln = (idx >> 3) & 63, blk = idx >> 9, term = blk % 3, kb = blk / 3;
-            const int ol = ln & 15, kp = kb * 32 + 8 * (ln >> 4) + i;
-            uint16_t v = 0;
-            if (16 * rg + ol < N && kp < K) {
-                float r = tile[ol * ld + kp];
-                if (fabsf(r) < 9.094947017729282e-13f) r = 0.0f;
-                v = mv_f2bf(r);
-                for (int t = 0; t < term; ++t) { r = r - mv_bf2f(v); v = mv_f2bf(r); }
-            }
-            dst[idx] = v;
-        }
-    }
-    if (a.wx3T[l]) {                                                            // ... and of W^T: this workgroup's 16 rows of W are half a k-block of every column tile
-        const int NTt = mv_ceil16(K) / 16, KBt = mv_bf_kb(N, 0);
-        const int kbt = rg >> 1, qh = 2 * (rg & 1);                             // k-block of W^T, lane quarter (lane >> 4) of the first 8 of the 16 rows
+    // ---- the three-term packs of the differentiable chains
+    if (a.wx3[l] && rg < NT) mv_pack_tile_row<32, 3>(a.wx3[l] + (size_t)rg * KB32 * 3 * 512, KB32, tile, ld, K, tid, MvValX3());
+    if (a.wx3T[l]) {                                                            // ... of W^T: this workgroup's 16 rows of W are half a k-block of every column tile
+        const int NTt = mv_ceil16(K) / 16, KBt = mv_bf_kb(N);
+        const int kbt = rg >> 1, k0 = 16 * (rg & 1);                            // k-block of W^T, and where in it the tile's first row stands
         for (int g = tid; g < NTt * 3 * 32; g += 1024) {                        // one 16-byte group (8 consecutive k of one lane) per iteration
             const int jh = g & 1, rl = (g >> 1) & 15, term = (g >> 5) % 3, ct = (g >> 5) / 3;
             const int o = ct * 16 + rl;                                         // column of W = row of W^T
             uint16_t v8[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                uint16_t v = 0;
-                if (o < K) {                                                    // (rows >= N are zero in the tile)
-                    float r = tile[(8 * jh + i) * ld + o];
-                    if (fabsf(r) < 9.094947017729282e-13f) r = 0.0f;
-                    v = mv_f2bf(r);
-                    for (int t = 0; t < term; ++t) { r = r - mv_bf2f(v); v = mv_f2bf(r); }
-                }
-                v8[i] = v;
-            }
-            const int ln = 16 * (qh + jh) + rl;
+            for (int i = 0; i < 8; ++i) v8[i] = mv_x3_term(o < K ? tile[(8 * jh + i) * ld + o] : 0.0f, term);      // (rows >= N are zero in the tile)
             uint4 pk;
             pk.x = v8[0] | ((uint32_t)v8[1] << 16); pk.y = v8[2] | ((uint32_t)v8[3] << 16); pk.z = v8[4] | ((uint32_t)v8[5] << 16); pk.w = v8[6] | ((uint32_t)v8[7] << 16);
-            if (kbt < KBt) *(uint4*)(a.wx3T[l] + ((((size_t)ct * KBt + kbt) * 3 + term) * 64 + ln) * 8) = pk;
-        }
-    }
-    if (a.wp16[l] && rg < NT && a.wp16_mode != 1 && a.wp16_mode != 2) {
-        const int ns = a.nsplit[l], KB32 = mv_bf_kb(K, ns);
-        uint16_t* dst = a.wp16[l] + (size_t)rg * KB32 * 512;
-        for (int idx = tid; idx < KB32 * 512; idx += 1024) {
-            const int i = idx & 7, ln = (idx >> 3) & 63, kb = idx >> 9;
-            const int ol = ln & 15, kp = kb * 32 + 8 * (ln >> 4) + i;
-            const int col = kp < K ? kp : (kp < K + ns ? kp - ns : -1);        // the lo copy of a split column shares the hi column's weight
-            dst[idx] = (16 * rg + ol < N && col >= 0) ? mv_f2bf(tile[ol * ld + col]) : (uint16_t)0;
+            if (kbt < KBt) *(uint4*)(a.wx3T[l] + mv_block_index(ct, kbt, KBt, term, 3) * 512 + mv_frag_bf16_at(rl, k0 + 8 * jh)) = pk;
         }
     }
 }
 
 int mv_step_prologue(int n_layers, const float* const* v, const float* const* g, const int* N, const int* K, float* const* w, float* const* wp,
-                     float* const* wpT, void* const* wp16, const int* nsplit, int wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
+                     float* const* wpT, void* const* wp16, MvWp16Mode wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
                      const float* intrinsics, int B, int P,
                      float* ray_dirs, float* cam_loc, uint8_t* ones, unsigned long long* counters, const float* stage_src, float* stage_a, int stage_na,
                      float* stage_b, int stage_nb, float* stage_a2, const float* const* bias, float* const* bias_copy, void* stream) {
@@ -759,13 +642,13 @@ int mv_step_prologue(int n_layers, const float* const* v, const float* const* g,
     for (int l = 0; l < n_layers; ++l) {
         if (!v[l] || !w[l] || !wp[l] || !wpT[l]) return mv_fail(-1, "mv_step_prologue: null layer pointer");
         a.f.v[l] = v[l]; a.f.g[l] = g[l]; a.f.w[l] = w[l]; a.f.wp[l] = wp[l]; a.f.wpT[l] = wpT[l];
-        a.wp16[l] = wp16 ? (uint16_t*)wp16[l] : nullptr; a.nsplit[l] = nsplit ? nsplit[l] : 0;
+        a.wp16[l] = wp16 ? (uint16_t*)wp16[l] : nullptr;
         a.wx3[l] = wx3 ? (uint16_t*)wx3[l] : nullptr; a.wx3T[l] = wx3T ? (uint16_t*)wx3T[l] : nullptr;
         if (bias && bias_copy && bias[l] && bias_copy[l]) { a.f.db[l] = bias[l]; a.f.dbias[l] = bias_copy[l]; }
         a.blk0[l] = blk; blk += mv_kpad(N[l]) / 16;                              // row groups incl. the W^T pack's zero padding (N padded to 32)
         if (K[l] > maxK) maxK = K[l];
     }
-    for (int l = n_layers; l < MV_FOLD_MAXL; ++l) { a.wp16[l] = nullptr; a.wx3[l] = a.wx3T[l] = nullptr; a.nsplit[l] = 0; a.blk0[l] = blk; }
+    for (int l = n_layers; l < MV_FOLD_MAXL; ++l) { a.wp16[l] = nullptr; a.wx3[l] = a.wx3T[l] = nullptr; a.blk0[l] = blk; }
     a.blk0[n_layers] = blk;
     a.uv = uv; a.pose = pose; a.Kin = intrinsics; a.B = B; a.P = P; a.dirs = ray_dirs; a.cam_loc = cam_loc;
     a.wp16_mode = wp16_mode;

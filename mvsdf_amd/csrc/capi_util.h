@@ -32,7 +32,6 @@ int mv_make_net_x3(const MvsdfNetDesc* d, MvNetBf* net);        // the three-ter
 int mv_make_net_trace(const MvsdfNetDesc* d, MvNet* net);     // the fp32-engine tracing net: the fp32 packs, or (trace_dtype == 2) the fp32 packs of the bf16-rounded weights
 // skip layers of a descriptor as a bit mask (skip_mask wins; else the single skip_layer)
 static inline unsigned mv_desc_skip_mask(const MvsdfNetDesc* d) { return d->skip_mask ? d->skip_mask : (d->skip_layer >= 0 ? 1u << d->skip_layer : 0u); }
-static inline int mv_bf_nsplit(const MvsdfNetDesc* d, int l) { return (l == 0 || mv_skip_at(mv_desc_skip_mask(d), l)) ? 3 + 6 * d->multires : 0; }
 
 // column tiles per wave the fused chain kernels need for this network (8 waves per workgroup): 2 up to width 256, 4 up to 512,
 // 0 = too wide for them (per-layer kernels take over).  Width = the widest tile row ANY phase of a chain produces: the hidden layers' outputs N_l (value /

@@ -67,8 +67,7 @@ int mv_make_net_x3(const MvsdfNetDesc* d, MvNetBf* net) {
         L.wp = (const uint4*)d->wx3[l];
         L.bias = d->bias[l];
         L.K = d->K[l]; L.N = d->N[l];
-        L.nsplit = 0;
-        L.KB = mv_bf_kb(L.K, 0); L.NT = mv_ceil16(L.N) / 16;
+        L.KB = mv_bf_kb(L.K); L.NT = mv_ceil16(L.N) / 16;
         if (L.KB > maxkb) maxkb = L.KB;
     }
     net->n_layers = d->n_layers; net->skip_mask = mv_desc_skip_mask(d); net->multires = d->multires;
@@ -89,8 +88,7 @@ int mv_make_net_bs(const MvsdfNetDesc* d, MvNetBf* net, int ns) {
         L.wp = (const uint4*)d->wp16[l];
         L.bias = d->bias[l];
         L.K = d->K[l]; L.N = d->N[l];
-        L.nsplit = 0;
-        L.KB = mv_bf_kb(L.K, 0); L.NT = mv_ceil16(d->N[l]) / 16;
+        L.KB = mv_bf_kb(L.K); L.NT = mv_ceil16(d->N[l]) / 16;
         if (L.KB * 32 > maxk) maxk = L.KB * 32;
     }
     net->n_layers = d->n_layers; net->skip_mask = chk.skip_mask; net->multires = d->multires;

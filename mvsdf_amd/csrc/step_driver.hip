@@ -171,13 +171,13 @@ int mvsdf_step_create(const MvsdfStepDesc* desc, MvsdfStepLayout* layout, void**
         if (l < d.n_sdf && d.trace_dtype == 2) {
             fo.wp16[l] = take(mvsdf_packed_floats(d.N[l], d.K[l]) * 4);
         } else if (l < d.n_sdf && (d.trace_dtype == 3 || d.trace_dtype == 4)) {
-            fo.wp16[l] = take(mvsdf_packed_bf16_bytes(d.N[l], d.K[l], 0));      // no duplicated columns: the activations are split into bf16 terms in LDS
+            fo.wp16[l] = take(mvsdf_packed_bf16_bytes(d.N[l], d.K[l]));      // no duplicated columns: the activations are split into bf16 terms in LDS
         } else if (l < d.n_sdf && d.trace_dtype == 5) {
-            fo.wp16[l] = take(3 * mvsdf_packed_bf16_bytes(d.N[l], d.K[l], 0));  // ... and so are the fp32 weights (three terms)
+            fo.wp16[l] = take(3 * mvsdf_packed_bf16_bytes(d.N[l], d.K[l]));  // ... and so are the fp32 weights (three terms)
         }
         if (l < d.n_sdf && fo.chain_x3) {                                     // the differentiable chains' three-term packs (the tracer's own under trace_dtype 5)
-            fo.wx3[l] = d.trace_dtype == 5 ? fo.wp16[l] : take(3 * mvsdf_packed_bf16_bytes(d.N[l], d.K[l], 0));
-            fo.wx3T[l] = take(3 * mvsdf_packed_bf16_bytes(d.K[l], d.N[l], 0));
+            fo.wx3[l] = d.trace_dtype == 5 ? fo.wp16[l] : take(3 * mvsdf_packed_bf16_bytes(d.N[l], d.K[l]));
+            fo.wx3T[l] = take(3 * mvsdf_packed_bf16_bytes(d.K[l], d.N[l]));
         }
     }
     L.perm = take((size_t)R * 8); fo.inv = take((size_t)R * 8); fo.true_rows = take((size_t)R * 8); fo.true_rank = take((size_t)R * 4); fo.counts = take(4 * 8 + 4 * 4);   // int64 counts[4], then float term_rows[3] (mvsdf_step_counts_offset + 32)
@@ -329,7 +329,7 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
     for (int l = 0; l < nl; ++l) { w[l] = (float*)(fwd + fo.w[l]); wp[l] = (float*)(fwd + fo.wp[l]); wpT[l] = (float*)(fwd + fo.wpT[l]); }
     float* ray_dirs = (float*)(fwd + L.ray_dirs); float* cam_loc = (float*)(fwd + L.cam_loc);
     {
-        void* wp16[MVSDF_STEP_MAX_LAYERS]; int nsplit[MVSDF_STEP_MAX_LAYERS];
+        void* wp16[MVSDF_STEP_MAX_LAYERS];
         void* wx3[MVSDF_STEP_MAX_LAYERS]; void* wx3T[MVSDF_STEP_MAX_LAYERS];
         for (int l = 0; l < nl; ++l) {
             const bool bf = l < d.n_sdf && d.trace_dtype != 0;
@@ -337,8 +337,8 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
             const bool x3 = l < d.n_sdf && fo.chain_x3;
             wx3[l] = (x3 && d.trace_dtype != 5) ? (void*)(fwd + fo.wx3[l]) : nullptr;       // (trace_dtype 5: the tracer's pack IS this pack)
             wx3T[l] = x3 ? (void*)(fwd + fo.wx3T[l]) : nullptr;
-            nsplit[l] = 0;                                        // (duplicated hi / lo input columns: the removed trace_dtype 1 only)
         }
+        const MvWp16Mode wp16_mode = d.trace_dtype == 2 ? MV_WP16_ROUNDED_F32 : (d.trace_dtype == 5 ? MV_WP16_X3 : MV_WP16_BF16);
         // ... and the camera rays (idr.py:190), all in one launch
         // the CPU-generator draws (min-sdf steps, eikonal points) may arrive in pinned host memory: the prologue reads them from there
         const float* stage_dev = nullptr;
@@ -353,7 +353,7 @@ int mvsdf_step_forward(void* step, const MvsdfStepParams* prm, const MvsdfStepIn
         for (int l = 0; l < nl; ++l) bias_copy[l] = (lazy && l < d.n_sdf) ? (float*)(fwd + fo.bias[l]) : nullptr;
         float* steps_copy = lazy ? (float*)(fwd + fo.steps) : nullptr;
         if (lazy && !stage_dev) ST_HIP(hipMemcpyAsync(steps_copy, in->minsdf_steps, (size_t)d.tp.n_steps * 4, hipMemcpyDeviceToDevice, s));
-        ST_TRY(mv_step_prologue(nl, prm->v, prm->g, d.N, d.K, w, wp, wpT, wp16, nsplit, d.trace_dtype == 2 ? 1 : (d.trace_dtype == 5 ? 2 : 0), wx3, wx3T, in->uv, in->pose, in->intrinsics, d.B, d.P, ray_dirs, cam_loc,
+        ST_TRY(mv_step_prologue(nl, prm->v, prm->g, d.N, d.K, w, wp, wpT, wp16, wp16_mode, wx3, wx3T, in->uv, in->pose, in->intrinsics, d.B, d.P, ray_dirs, cam_loc,
                                 (uint8_t*)(fwd + L.object_mask_out), (unsigned long long*)(fwd + L.counters), stage_dev, (float*)in->minsdf_steps, d.tp.n_steps,
                                 (float*)in->eik_points, 3 * d.n_eik, steps_copy, prm->b, bias_copy, stream));
     }

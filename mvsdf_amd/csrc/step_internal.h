@@ -64,10 +64,16 @@ int mv_sdf_backward_delta(const MvsdfNetDesc* d, const MvsdfNetDesc* dT, int M, 
 int mv_step_wgrad(const MvsdfNetDesc* sd, const MvsdfNetDesc* rd, int M, int Mg, int Mb, const float* dy, const float* ctx, float* wsA, int N, int Nctx,
                   const float* rctx, float* rws, float* dW_s, float* db_s, float* dW_r, float* db_r, const long long* cnt, int cnt_base, void* stream);
 
-// fold + MFMA packs (+ bf16 packs where wp16[l] is set: nsplit[l] = its PE split width) of every layer + the camera rays in ONE launch
-// (basic.hip::k_step_prologue): the work of mvsdf_fold_pack_net, mvsdf_pack_bf16_net_skips and mvsdf_camera_rays, same results
+// what mv_step_prologue writes to wp16[l], by the tracer's arithmetic
+enum MvWp16Mode {
+    MV_WP16_BF16 = 0,          // the one-term bf16 pack (trace_dtype 3 / 4; mvsdf_pack_bf16s_net)
+    MV_WP16_ROUNDED_F32 = 1,   // the fp32 pack of the bf16-rounded weights (trace_dtype 2; mvsdf_pack_bf16w_net)
+    MV_WP16_X3 = 2,            // the three-term bf16 pack (trace_dtype 5; mvsdf_pack_bf16x3_net)
+};
+// fold + MFMA packs (+ the tracer's pack where wp16[l] is set, in the form wp16_mode names) of every layer + the camera rays in ONE launch
+// (basic.hip::k_step_prologue): the work of mvsdf_fold_pack_net, mvsdf_pack_bf16w_net / _bf16s_net / _bf16x3_net and mvsdf_camera_rays, same results
 int mv_step_prologue(int n_layers, const float* const* v, const float* const* g, const int* N, const int* K, float* const* w, float* const* wp,
-                     float* const* wpT, void* const* wp16, const int* nsplit, int wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
+                     float* const* wpT, void* const* wp16, MvWp16Mode wp16_mode, void* const* wx3, void* const* wx3T, const float* uv, const float* pose,
                      const float* intrinsics, int B, int P,
                      float* ray_dirs, float* cam_loc, uint8_t* ones, unsigned long long* counters, const float* stage_src, float* stage_a, int stage_na,
                      float* stage_b, int stage_nb, float* stage_a2, const float* const* bias, float* const* bias_copy,

@@ -11,7 +11,7 @@
 // vs oracle.Net(sd, bf16='weights')) is the ORDER of the fp32 additions inside the matrix core and the softplus below: accumulation noise of a
 // few 1e-8 on |z| ~ 1, no 8-bit rounding anywhere.  The L2 weight stream -- what bounds the bf16 engine -- does not grow: only the LDS activation
 // reads and the (16x cheaper than fp32) matrix instructions are multiplied by NS.
-//   * weights: bf16 packs of tile_engine_bf16.h WITHOUT duplicated columns (nsplit = 0: the positional-encoding columns are split like
+//   * weights: bf16 packs of tile_engine_bf16.h WITHOUT duplicated columns (the positional-encoding columns are split like
 //     every other activation, into the term tiles);
 //   * LDS: NS term tiles [rows][S16] bf16 behind each other (term stride rows * S16), row stride 64*KB + 16 bytes (conflict-free b128 reads);
 //   * softplus: max(z, 0) + (ln 2 / 100) log2(1 + 2^(-100 log2(e) |z|)) by v_exp_f32 / v_log_f32: absolute error <= 8e-9, the accuracy class of
@@ -26,7 +26,7 @@
 #include "tile_engine_bf16.h"
 
 template <int NS, int WT = 1>
-struct MvNetBs : MvNetBf {};        // S = NS * (32 * KBmax + 8) / 2 floats per row (all term tiles); L[l].nsplit == 0
+struct MvNetBs : MvNetBf {};        // S = NS * (32 * KBmax + 8) / 2 floats per row (all term tiles)
                                     // WT = 3 (trace_dtype 5): fp32 WEIGHTS as three bf16 terms too (packs of mvsdf_pack_bf16x3_net), see mv_gemm_rolling_bw
 
 __host__ __device__ constexpr int mv_bs_pa(int NS) { return NS == 1 ? 4 : 2; }          // activation k-blocks in flight (LDS), CARRIED
@@ -54,9 +54,7 @@ __device__ __forceinline__ dm_f2 mv_softplus100_acc2(dm_f2 z) { return dm_f2{mv_
 // trace_dtype 5 ("f32x3") is reproduced BIT FOR BIT by the CPU oracle (oracle/oracle_mvsdf.c::sdf_row_f32x3 models the matrix instruction: tools/micro/mfma_bf16_model/),
 // so its activation is det_math's softplus (IEEE operations only), not the hardware exp / log form above, and every value that enters the matrix core is first
 // flushed to zero below 2^-40 (no bf16 term is ever denormal, every product stays above 2^-112: the instruction model is verified on products inside the fp32 normal
-// range -- below it the hardware deviates, tools/micro/mfma_bf16_model/mfma_fuzz.hip `tiny`; 1e-12 on values up to 10)
-#define MV_X3_FLUSH 9.094947017729282e-13f                          // 2^-40
-__device__ __forceinline__ float mv_x3_flush(float v) { return fabsf(v) < MV_X3_FLUSH ? 0.0f : v; }
+// range -- below it the hardware deviates, tools/micro/mfma_bf16_model/mfma_fuzz.hip `tiny`; 1e-12 on values up to 10): pack_layout.h::mv_x3_flush
 __device__ __forceinline__ dm_f2 mv_x3_flush2(dm_f2 v) { return dm_f2{mv_x3_flush(v.x), mv_x3_flush(v.y)}; }
 
 __device__ __forceinline__ dm_f2 mv_bf_unpack2(uint32_t p) { return dm_f2{__uint_as_float(p << 16), __uint_as_float(p & 0xffff0000u)}; }

@@ -238,8 +238,8 @@ def pack_x3_chain(net):
     K = (C.c_int * n)(*[L.K for L in net.layers])
     ws = _int_ptr_array([L.w.data_ptr() if L.w is not None else L.w_ptr for L in net.layers])
     for L in net.layers:
-        L.wx3 = torch.empty(3 * lib().mvsdf_packed_bf16_bytes(L.N, L.K, 0), dtype=torch.uint8, device=dev)
-        L.wx3T = torch.empty(3 * lib().mvsdf_packed_bf16_bytes(L.K, L.N, 0), dtype=torch.uint8, device=dev)
+        L.wx3 = torch.empty(3 * lib().mvsdf_packed_bf16_bytes(L.N, L.K), dtype=torch.uint8, device=dev)
+        L.wx3T = torch.empty(3 * lib().mvsdf_packed_bf16_bytes(L.K, L.N), dtype=torch.uint8, device=dev)
     s = stream_of(net.layers[0].bias)
     check(lib().mvsdf_pack_bf16x3_net(n, ws, N, K, _ptr_array([L.wx3 for L in net.layers]), s), 'mvsdf_pack_bf16x3_net')
     check(lib().mvsdf_pack_bf16x3t_net(n, ws, N, K, _ptr_array([L.wx3T for L in net.layers]), s), 'mvsdf_pack_bf16x3t_net')
@@ -297,7 +297,7 @@ def pack_bf16_net(net, weights_only=False, terms=0, weight_terms=1):
         assert terms in (2, 3) and not weights_only and weight_terms in (1, 3) and (weight_terms == 1 or terms == 3)
         dev = net.layers[0].bias.device
         for L in net.layers:
-            L.wp16 = torch.empty(weight_terms * lib().mvsdf_packed_bf16_bytes(L.N, L.K, 0), dtype=torch.uint8, device=dev)
+            L.wp16 = torch.empty(weight_terms * lib().mvsdf_packed_bf16_bytes(L.N, L.K), dtype=torch.uint8, device=dev)
         N = (C.c_int * n)(*[L.N for L in net.layers])
         K = (C.c_int * n)(*[L.K for L in net.layers])
         fn = lib().mvsdf_pack_bf16x3_net if weight_terms == 3 else lib().mvsdf_pack_bf16s_net

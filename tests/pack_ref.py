@@ -11,7 +11,7 @@ import numpy as np
 
 from oracle import oracle
 
-FLUSH = np.float32(2.0 ** -40)                   # |w| < 2^-40 counts as zero in the three-term packs (tile_engine_bf16s.h)
+FLUSH = np.float32(2.0 ** -40)                   # |w| < 2^-40 counts as zero in the three-term packs (pack_layout.h, MV_X3_FLUSH)
 
 
 def ceil16(x):

@@ -170,7 +170,7 @@ def test_transposed_three_term_pack_equals_the_pack_of_the_transposed_matrix():
     n = len(ws)
     N = (C.c_int * n)(*[w.shape[0] for w in ws]); K = (C.c_int * n)(*[w.shape[1] for w in ws])
     Nt = (C.c_int * n)(*[w.shape[0] for w in wts]); Kt = (C.c_int * n)(*[w.shape[1] for w in wts])
-    size = lambda nn, kk: 3 * lib().mvsdf_packed_bf16_bytes(nn, kk, 0)
+    size = lambda nn, kk: 3 * lib().mvsdf_packed_bf16_bytes(nn, kk)
     a = [torch.full((size(w.shape[1], w.shape[0]),), 0x5a, dtype=torch.uint8, device='cuda') for w in ws]       # pack of W^T through the transposing entry point
     b = [torch.full((size(w.shape[0], w.shape[1]),), 0xa5, dtype=torch.uint8, device='cuda') for w in wts]     # pack of the explicit transpose
     s = stream_of(ws[0])

@@ -6,8 +6,11 @@ mvsdf_pack_bf16x3t_net) bit for bit to the numpy restatement of tests/pack_ref.p
 says and pre-filled with a byte pattern, twice with two patterns: the bytes beyond the stated size must keep the pattern, the bytes inside it must come out
 the same under both patterns (so each of them was written), dense content must equal the restatement and every pad element must be +0.
 
-Part two holds the native step's prologue (k_step_prologue: its own fold, five packs, camera rays in one launch) to those stand-alone kernels, on networks
+Part two holds the native step's prologue (k_step_prologue: fold, five packs, camera rays in one launch) to those stand-alone kernels, on networks
 away from the geometric initialisation, through the inspection offsets of NativeStep.pack_offsets.  Nothing is asserted on what the step computes from them.
+Both sides take the layout, the split, the fold chain and the camera ray from one definition each (csrc/pack_layout.h, basic.hip::mv_norm_chain,
+mv_camera_ray; the layout is held to pack_ref on the CPU by tests/test_pack_layout_host.py): what this part alone holds is the prologue's own schedule --
+where its row groups' blocks go in every pack, its register-resident form of the fold chain, the index arithmetic of its ray workgroups.
 
 Input domain of the bf16 packs: finite weights with a finite bf16 rounding (|w| <= 0x7f7f7fff as a bit pattern)."""
 import ctypes as C
@@ -31,7 +34,7 @@ SCALES = (-40, -10, 0, 10, 40)
 
 
 def _bf16_bytes(N, K):
-    return int(lib().mvsdf_packed_bf16_bytes(N, K, 0))
+    return int(lib().mvsdf_packed_bf16_bytes(N, K))
 
 
 def _f32_bytes(N, K):
@@ -324,6 +327,17 @@ def test_step_prologue_equals_the_standalone_kernels(W, dtype):
     w == orc_fold(v, g) and its wp, wpT, wp16, wx3, wx3T == what the stand-alone entry points write for that w (all bit for bit, pads +0), the bias copy ==
     the bias, and the block's ray_dirs / cam_loc == ops.camera_rays.  The trace dtypes cover the prologue's wp16 forms (absent, rounded fp32 pack, one-term
     bf16 pack, three-term pack) and wx3 separate from / shared with wp16."""
+    _prologue_case(W, dtype, B, P)
+
+
+@pytest.mark.parametrize('B,P', [(1, 1025), (2, 513)], ids=['1x1025', '2x513'])
+def test_step_prologue_at_ray_workgroup_edges(B, P):
+    """The same comparison, every region, at the two edges of the prologue's 1024-lane ray workgroups that 96 rays of one view do not reach: a second ray
+    workgroup that holds a single ray (1 x 1025), and the view boundary inside the first workgroup, where lane 513 writes the cam_loc of view 1 (2 x 513)."""
+    _prologue_case(64, 'f32x3', B, P)
+
+
+def _prologue_case(W, dtype, B, P):
     from mvsdf_amd.model.implicit_differentiable_renderer import IDRNetwork
     from mvsdf_amd.utils import synth
     from mvsdf_amd.utils.config import ConfigDict

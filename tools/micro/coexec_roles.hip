@@ -115,9 +115,9 @@ int main(int argc, char** argv) {
     const uint4* wstream = nullptr; int wstream_n = 0;
     for (int l = 0; l < nl; ++l) {
         MvLayerBf& L = net.L[l];
-        L.K = K[l]; L.N = N[l]; L.nsplit = 0; L.KB = mv_bf_kb(K[l], 0); L.NT = mv_ceil16(N[l]) / 16;
+        L.K = K[l]; L.N = N[l]; L.KB = mv_bf_kb(K[l]); L.NT = mv_ceil16(N[l]) / 16;
         maxk = L.KB * 32 > maxk ? L.KB * 32 : maxk;
-        const size_t el = 3 * mv_packed_bf16_elems(N[l], K[l], 0);
+        const size_t el = 3 * mv_packed_bf16_elems(N[l], K[l]);
         std::vector<uint16_t> h(el);
         for (size_t i = 0; i < el; ++i) h[i] = mv_f2bf(((rand() & 0xffff) / 65536.0f - 0.5f) * ((i / 512) % 3 == 0 ? 0.12f : ((i / 512) % 3 == 1 ? 4e-4f : 2e-6f)));
         std::vector<float> b(mv_ceil16(N[l]), 0.01f);

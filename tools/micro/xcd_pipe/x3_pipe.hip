@@ -349,10 +349,10 @@ int main(int argc, char** argv) {
     srand(1);
     for (int l = 0; l < nl; ++l) {
         MvLayerBf& L = net.L[l];
-        L.K = K[l]; L.N = N[l]; L.nsplit = 0; L.KB = mv_bf_kb(K[l], 0); L.NT = mv_ceil16(N[l]) / 16;
+        L.K = K[l]; L.N = N[l]; L.KB = mv_bf_kb(K[l]); L.NT = mv_ceil16(N[l]) / 16;
         maxk = L.KB * 32 > maxk ? L.KB * 32 : maxk;
         // three-term packs of random fp32 weights (w = t0 + t1 + t2 exactly), padding rows / columns zero: wp[((ct * KB + kb) * 3 + j) * 64 + lane][8]
-        const size_t el = 3 * mv_packed_bf16_elems(N[l], K[l], 0);
+        const size_t el = 3 * mv_packed_bf16_elems(N[l], K[l]);
         std::vector<uint16_t> h(el, 0);
         const float scale = 1.6f / sqrtf((float)K[l]);
         for (int ct = 0; ct < L.NT; ++ct)
