@@ -1079,7 +1079,8 @@ enum {                          /* bits 1 and 2 are MVSDF_RA_ERR_*'s */
     MVSDF_TX_ERR_FINITE = 1,    /* a camera or centre entry is NaN or infinite */
     MVSDF_TX_ERR_INDEX = 2,     /* a face refers to a vertex outside [0, nv) */
     MVSDF_TX_ERR_COUNTS = 4,    /* the class counts passed to the pack are not those of cls; seams: the counts passed to mvsdf_seams_graph are not the header's */
-    MVSDF_TX_ERR_LABEL = 8      /* seams: a face label outside [-1, V), or a node's view outside [0, V) */
+    MVSDF_TX_ERR_LABEL = 8,     /* seams, charts: a face label outside [-1, V), or a node's view outside [0, V) */
+    MVSDF_TX_ERR_ROUNDS = 16    /* charts: the components did not settle within MVSDF_CA_MAX_ROUNDS rounds */
 };
 enum {
     MVSDF_TX_MAX_SIDE = 32768,      /* texels: block coordinates fit 13 bits, block indices 26 */
@@ -1146,6 +1147,73 @@ int mvsdf_seams_fill(const uint8_t* images, int64_t views, int64_t H, int64_t W,
                      const int32_t* order, int64_t nf, const int64_t* counts, const int32_t* corner_node, const double* g, int64_t nodes,
                      int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, void* ws, size_t ws_bytes, int64_t Ht, int64_t Wt, uint8_t* texture,
                      uint8_t* valid, void* stream);
+
+/* ---- Chart atlases (charts.hip; Python: mvsdf_amd/charts.py, which states the definition) ----
+ * A chart is a connected region of faces with one label; its patch is a rectangle cut from that view's photograph with a margin of `pad` texels
+ * (1, 2, 4 or 8).  All on the device, fp64.  Every workspace starts with the MVSDF_CA_H_* words (256 bytes), which every call zeroes first; error
+ * bits are MVSDF_TX_ERR_*.  mvsdf_charts_workspace_bytes(nf, texels): what every call needs for nf faces, and mvsdf_charts_face_map for an atlas of
+ * `texels` texels (0 beyond the limits).  Only mvsdf_charts_components waits (it reads one word per MVSDF_CA_ROUND_BATCH rounds).
+ * mvsdf_charts_face_scores: texture.hip's test of face f in the one view view[f] -> score fp64 [nf] (|A|, 0 where the view is no candidate or -1),
+ * screen fp64 [nf][6].  MVSDF_TX_ERR_INDEX (a vertex id), _LABEL (a view outside [-1, views)), _FINITE; such a face scores 0.
+ * mvsdf_charts_neighbors: nbr int32 [nf][3], across edge e (corners e, (e + 1) % 3) the other face, -1 unless exactly two of the 3 nf edges join these
+ * two different vertex ids and belong to two faces.  MVSDF_TX_ERR_INDEX: a vertex id outside [0, nv) (its edges have no neighbour).
+ * mvsdf_charts_components: face_chart int32 [nf] (-1: unlabelled), and in the first C entries of chart_view and chart_faces int32 [nf] each chart's
+ * label and faces; charts ascending by their lowest face.  Header: MVSDF_CA_H_CHARTS = C.  MVSDF_TX_ERR_LABEL (a label below -1: unlabelled),
+ * _INDEX (a neighbour outside [-1, nf): none), _ROUNDS.
+ * mvsdf_charts_absorb: one round of the absorption of charts with fewer than min_faces faces: label_out int32 [nf]; score and screen are updated
+ * where a label changed.  Header: MVSDF_CA_H_CHANGES.
+ * mvsdf_charts_pack: chart_rect int32 [C][6] = {X, Y, w, h, u0, t0}, order int32 [C] (the charts by h descending, id ascending), xs int32 [C] (X by
+ * place in that order) and shelves int32 [C + 1][2] = {first place, Y}, entry MVSDF_CA_H_SHELVES = {C, Ht}.  Header: MVSDF_CA_H_WT, _HT, _SHELVES,
+ * _AREA, _MAXW, _MAXH.  MVSDF_TX_ERR_INDEX: a face's chart outside [-1, C); MVSDF_TX_ERR_COUNTS: a chart without a face.
+ * mvsdf_charts_uv: uv fp32 [nf][3][2].  mvsdf_charts_face_map: face_map int32 [Ht][Wt], the lowest covering face, dilated `pad` rounds.
+ * mvsdf_charts_fill: texture uint8 [Ht][Wt][3] and valid uint8 [Ht][Wt] (both 4-byte aligned, Wt a multiple of 4); with face_map (else NULL, and
+ * the arguments from face_chart to nodes unused) the correction g fp64 [nodes][3] of the face's three nodes is added before the rounding.
+ * MVSDF_TX_ERR_INDEX: an entry of the tables, of face_map or of corner_node out of range (the texel gets the fallback, or stays uncorrected). */
+enum {
+    MVSDF_CA_H_ERR = 0,         /* error bits */
+    MVSDF_CA_H_CHARTS = 1,      /* mvsdf_charts_components: C */
+    MVSDF_CA_H_CHANGES = 2,     /* mvsdf_charts_absorb: the labels that changed */
+    MVSDF_CA_H_WT = 3,          /* mvsdf_charts_pack: the atlas */
+    MVSDF_CA_H_HT = 4,
+    MVSDF_CA_H_SHELVES = 5,     /* shelves */
+    MVSDF_CA_H_AREA = 6,        /* the sum of w * h */
+    MVSDF_CA_H_MAXW = 7,        /* the largest w and h */
+    MVSDF_CA_H_MAXH = 8,
+    MVSDF_CA_H_ROUNDS = 9,      /* mvsdf_charts_components: the rounds enqueued */
+    MVSDF_CA_H_WORDS = 10
+};
+enum {
+    MVSDF_CA_MAX_ROUNDS = 64,       /* hook-and-jump rounds of the components */
+    MVSDF_CA_ROUND_BATCH = 8,       /* rounds between two reads of the settled word */
+    MVSDF_CA_RECT_CAP = 65536,      /* the cap of a rectangle's side: 2 * MVSDF_TX_MAX_SIDE, a multiple of every pad */
+    MVSDF_CA_LARGE_FACE = 256       /* texels in a face's box above which a wave draws it into the face map */
+};
+size_t mvsdf_charts_workspace_bytes(int64_t nf, int64_t texels);
+int mvsdf_charts_face_scores(const float* verts, const float* normals, const int32_t* faces, int64_t nv, int64_t nf, const double* P,
+                             const double* centers, int64_t views, int64_t H, int64_t W, double pixel_center, const float* depth, const uint8_t* masks,
+                             double depth_tol, double cos_min, int32_t ignore_normals, const int32_t* view, void* ws, size_t ws_bytes, double* score,
+                             double* screen, void* stream);
+int mvsdf_charts_neighbors(const int32_t* faces, int64_t nv, int64_t nf, void* ws, size_t ws_bytes, int32_t* nbr, void* stream);
+int mvsdf_charts_components(const int32_t* label, const int32_t* nbr, int64_t nf, void* ws, size_t ws_bytes, int32_t* face_chart,
+                            int32_t* chart_view, int32_t* chart_faces, void* stream);
+int mvsdf_charts_absorb(const float* verts, const float* normals, const int32_t* faces, int64_t nv, int64_t nf, const double* P,
+                        const double* centers, int64_t views, int64_t H, int64_t W, double pixel_center, const float* depth, const uint8_t* masks,
+                        double depth_tol, double cos_min, int32_t ignore_normals, const int32_t* label, const int32_t* nbr, const int32_t* face_chart,
+                        const int32_t* chart_faces, int64_t charts, int64_t min_faces, void* ws, size_t ws_bytes, int32_t* label_out, double* score,
+                        double* screen, void* stream);
+int mvsdf_charts_pack(const int32_t* face_chart, const double* screen, int64_t nf, int64_t charts, double pixel_center, int64_t H, int64_t W,
+                      double density, int32_t pad, void* ws, size_t ws_bytes, int32_t* chart_rect, int32_t* order, int32_t* xs, int32_t* shelves,
+                      void* stream);
+int mvsdf_charts_uv(const int32_t* face_chart, const double* screen, int64_t nf, const int32_t* chart_rect, int64_t charts, double pixel_center,
+                    double density, int32_t pad, int64_t Ht, int64_t Wt, void* ws, size_t ws_bytes, float* uv, void* stream);
+int mvsdf_charts_face_map(const int32_t* face_chart, const double* screen, int64_t nf, double pixel_center, const int32_t* chart_rect,
+                          const int32_t* order, const int32_t* xs, const int32_t* shelves, int64_t charts, int64_t nshelves, double density,
+                          int32_t pad, int64_t Ht, int64_t Wt, void* ws, size_t ws_bytes, int32_t* face_map, void* stream);
+int mvsdf_charts_fill(const uint8_t* images, int64_t views, int64_t H, int64_t W, const int32_t* chart_view, const int32_t* chart_rect,
+                      const int32_t* order, const int32_t* xs, const int32_t* shelves, int64_t charts, int64_t nshelves, double density, int32_t pad,
+                      int32_t fallback_r, int32_t fallback_g, int32_t fallback_b, int64_t Ht, int64_t Wt, const int32_t* face_map,
+                      const int32_t* face_chart, const double* screen, double pixel_center, int64_t nf, const int32_t* corner_node, const double* g,
+                      int64_t nodes, void* ws, size_t ws_bytes, uint8_t* texture, uint8_t* valid, void* stream);
 
 /* ---- MVS feature extraction (featext.hip; Python: mvsdf_amd/features.py, which states the network) ----
  * Inference of the Vis-MVSNet feature CNN FeatExt on NHWC fp32 activations, eval-mode BatchNorm folded into the weights at pack time.

@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SO = os.path.join(HERE, 'libmvsdf_hip.so')
-SOURCES = ['capi_util.hip', 'basic.hip', 'trace.hip', 'diff_mlp.hip', 'loss_kernels.hip', 'optim_kernels.hip', 'step_kernels.hip', 'sample_kernels.hip', 'step_driver.hip', 'mesh_kernels.hip', 'mesh_sparse.hip', 'mesh_cut.hip', 'mesh_simplify.hip', 'chamfer.hip', 'registration.hip', 'cloud.hip', 'normals.hip', 'global_reg.hip', 'keypoints.hip', 'bundle.hip', 'fusion.hip', 'tsdf.hip', 'poisson.hip', 'raster.hip', 'texture.hip', 'seams.hip', 'featext.hip', 'stereo.hip', 'viewsel.hip', 'undistort.hip', 'batch_kernels.hip']
+SOURCES = ['capi_util.hip', 'basic.hip', 'trace.hip', 'diff_mlp.hip', 'loss_kernels.hip', 'optim_kernels.hip', 'step_kernels.hip', 'sample_kernels.hip', 'step_driver.hip', 'mesh_kernels.hip', 'mesh_sparse.hip', 'mesh_cut.hip', 'mesh_simplify.hip', 'chamfer.hip', 'registration.hip', 'cloud.hip', 'normals.hip', 'global_reg.hip', 'keypoints.hip', 'bundle.hip', 'fusion.hip', 'tsdf.hip', 'poisson.hip', 'raster.hip', 'texture.hip', 'seams.hip', 'charts.hip', 'featext.hip', 'stereo.hip', 'viewsel.hip', 'undistort.hip', 'batch_kernels.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math',
          '-Wno-unused-result', '-Wno-pass-failed']
 TAG_FLAGS = {'dev': ['-DMVSDF_DEV_SWITCHES']}

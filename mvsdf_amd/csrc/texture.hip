@@ -6,7 +6,8 @@
 // * k_tx_face_views: one lane per face, the views in order inside (the label takes the first view of the largest |A|, so there is one order).  It
 //   also writes the six screen coordinates of the face in its view, which the later stages read (the fill can project them again instead:
 //   TX_FLAG_RECOMPUTE, the A/B of DESIGN.md).  The projection, the visibility test, the edge function and the texel gather are the ones raster.hip
-//   uses: view_prims.h's mv_project, mv_visible, mv_edge and mv_cell / mv_gather_rgb.
+//   uses: view_prims.h's mv_project, mv_visible, mv_edge and mv_cell / mv_gather_rgb.  The test of one face in one view is tx_prims.h's
+//   tx_face_in_view, which charts.hip asks for the one view it names.
 // * k_tx_classify: the size class of every face at a texel density, and the seven class counts (integer atomics).  The host reads the counts: the
 //   atlas size follows from them alone (tx_layout), and the max_size loop repeats only this pass.
 // * the stable counting sort is ONE scan: flags[(6 - class) * nf + f] over 7 * nf bytes, so the exclusive prefix of a set flag is the face's place in
@@ -18,7 +19,7 @@
 //
 // Every index read from the caller (face -> vertex, order -> face, label -> view) is range-checked before it is used; the image position is clamped
 // before it becomes an address; all offsets into the images are 64-bit.
-#include "view_prims.h"
+#include "tx_prims.h"
 
 #define TX_THREADS 256
 #define TX_HDR 256                                    // bytes at the start of the workspace: MVSDF_TX_H_*
@@ -98,37 +99,18 @@ __global__ __launch_bounds__(TX_THREADS) void k_tx_face_views(const float* __res
     if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) {
         atomicOr(hdr + MVSDF_TX_H_ERR, (unsigned long long)MVSDF_TX_ERR_INDEX);
     } else {
-        const float *Xa = verts + (long long)a * 3, *Xb = verts + (long long)b * 3, *Xc = verts + (long long)c * 3;
-        const float *Na = normals + (long long)a * 3, *Nb = normals + (long long)b * 3, *Nc = normals + (long long)c * 3;
-        const double n0 = ((double)Na[0] + (double)Nb[0]) + (double)Nc[0], n1 = ((double)Na[1] + (double)Nb[1]) + (double)Nc[1],
-                     n2 = ((double)Na[2] + (double)Nb[2]) + (double)Nc[2];
-        const double m0 = (((double)Xa[0] + (double)Xb[0]) + (double)Xc[0]) / 3.0, m1 = (((double)Xa[1] + (double)Xb[1]) + (double)Xc[1]) / 3.0,
-                     m2 = (((double)Xa[2] + (double)Xb[2]) + (double)Xc[2]) / 3.0;
-        const double nn = (n0 * n0 + n1 * n1) + n2 * n2;
-        const bool flat = nn == 0.0;
-        const double wmax = (double)(W - 1), hmax = (double)(H - 1);
-        if (!(flat && !ignore_normals)) {
+        const TxFace F = tx_face(verts, normals, a, b, c);
+        if (!(F.flat && !ignore_normals)) {
             for (int v = 0; v < V; ++v) {
-                const double* Pv = P + (long long)v * 16;
-                const float* dv = depth + v * hw;
-                const unsigned char* mv = masks ? masks + v * hw : nullptr;
-                double ax, ay, bx, by, cx, cy;
-                if (!mv_visible(Pv, Xa, o, H, W, dv, mv, depth_tol, ax, ay)) continue;
-                if (!mv_visible(Pv, Xb, o, H, W, dv, mv, depth_tol, bx, by)) continue;
-                if (!mv_visible(Pv, Xc, o, H, W, dv, mv, depth_tol, cx, cy)) continue;
-                if (!(mv_in_image(ax, ay, o, wmax, hmax) && mv_in_image(bx, by, o, wmax, hmax) && mv_in_image(cx, cy, o, wmax, hmax))) continue;
-                const double A = mv_edge(ax, ay, bx, by, cx, cy);
-                if (!(A != 0.0)) continue;
-                if (!flat) {
-                    const double g0 = C[v * 3] - m0, g1 = C[v * 3 + 1] - m1, g2 = C[v * 3 + 2] - m2;
-                    const double cosang = ((n0 * g0 + n1 * g1) + n2 * g2) / sqrt(((g0 * g0 + g1 * g1) + g2 * g2) * nn);
-                    if (!(cosang > cos_min)) continue;
-                }
-                const double sc = fabs(A);
+                double sc, sv[6];
+                if (!tx_face_in_view(F, P + (long long)v * 16, C + (long long)v * 3, o, H, W, depth + v * hw, masks ? masks + v * hw : nullptr, depth_tol,
+                                     cos_min, sc, sv))
+                    continue;
                 if (sc > bs) {                                    // strictly: a tie stays with the lower view
                     bs = sc;
                     best = v;
-                    s[0] = ax, s[1] = ay, s[2] = bx, s[3] = by, s[4] = cx, s[5] = cy;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) s[q] = sv[q];
                 }
             }
         }

@@ -79,7 +79,8 @@ def write_simplified_mesh(mesh, path, epoch, cell=None, target_faces=None):
 
 def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name='evals', timestamp='latest', checkpoint='latest', resolution=512,
              eval_rendering=False, exps_root='../', feat_ckpt=None, printer=print, sparse_mesh=False, mesh_block=None, mesh_margin=None,
-             color_mesh=False, simplify_cell=None, simplify_faces=None, texture_mesh=False, level_seams=False):
+             color_mesh=False, simplify_cell=None, simplify_faces=None, texture_mesh=False, level_seams=False, charts=False,
+             chart_pad=None, min_chart_faces=None):
     """The testing command (eval.py:19-185, eval_cameras off): the model of <exps_root>/<exps_folder>/<train.expname>_<expname>/<timestamp>/checkpoints
     -> <exps_root>/<evals_folder>/<train.expname>_<expname>/surface_world_coordinates_<epoch>.obj (extract_world_mesh) and, with eval_rendering, every
     view rendered with its perfect mask as the object mask (eval.py:137) to rendering/eval_<idx:03>.png plus psnr.txt with the reference's line.
@@ -90,7 +91,8 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     without them), write_simplified_mesh's surface_world_coordinates_<epoch>_simplified.obj; the result gets 'simplified_mesh'.  texture_mesh:
     also surface_world_coordinates_<epoch>_textured.{obj,mtl,png}, texture.texture_mesh_from_scene of the simplified mesh when a simplify option is
     given, else of the world mesh; the result gets 'textured_mesh' (the TexturedMesh, or None without a mesh); level_seams (with texture_mesh):
-    its colours levelled across the label boundaries (seams.level_atlas)."""
+    its colours levelled across the label boundaries (seams.level_atlas); charts (with texture_mesh): the atlas of charts (charts.build_chart_atlas) with
+    chart_pad texels of margin and charts of fewer than min_chart_faces faces absorbed (None: that module's defaults)."""
     from PIL import Image
     from .checkpoint import MODEL_SUBDIR
     from .datasets.device_batches import DeviceBatches
@@ -137,7 +139,11 @@ def evaluate(data_dir, conf, expname, exps_folder_name='exps', evals_folder_name
     textured = None
     if texture_mesh and (simplified if simplify else mesh) is not None:
         from . import texture
-        textured = texture.texture_mesh_from_scene(simplified if simplify else mesh, data_dir, **(dict(level_seams=True) if level_seams else {}))
+        kw = dict(level_seams=True) if level_seams else {}
+        if charts:
+            opts = {} if chart_pad is None else dict(pad=chart_pad)
+            kw.update(charts=True, chart_options=dict(opts, **({} if min_chart_faces is None else dict(min_faces=min_chart_faces))))
+        textured = texture.texture_mesh_from_scene(simplified if simplify else mesh, data_dir, **kw)
         textured.export(os.path.join(evaldir, 'surface_world_coordinates_{0}_textured.obj'.format(epoch)))
         printer('textured: %d faces, atlas %d x %d at %.6g texels per pixel' % (len(textured.mesh), textured.texture.shape[1], textured.texture.shape[0],
                                                                               textured.density))
@@ -198,6 +204,10 @@ def eval_parser():
                         'world mesh) with a texture atlas from image_hd/ (mvsdf_amd/texture.py).')
     p.add_argument('--level_seams', default=False, action='store_true',
                    help='With --texture_mesh: level the colours across the label boundaries of the atlas (mvsdf_amd/seams.py).')
+    p.add_argument('--charts', default=False, action='store_true',
+                   help='With --texture_mesh: one rectangle per connected region of a view instead of one patch per face (mvsdf_amd/charts.py).')
+    p.add_argument('--chart_pad', default=None, type=int, choices=(1, 2, 4, 8), help='With --charts: margin and alignment of the rectangles in texels (default 4).')
+    p.add_argument('--min_chart_faces', default=None, type=int, help='With --charts: charts of fewer faces are absorbed by their neighbours (default 4).')
     return p
 
 
@@ -209,4 +219,5 @@ def main(argv=None, printer=print):
                     timestamp=opt.timestamp, checkpoint=opt.checkpoint, resolution=opt.resolution, eval_rendering=opt.eval_rendering,
                     exps_root=opt.exps_root, feat_ckpt=opt.feat_ckpt, printer=printer, sparse_mesh=opt.sparse_mesh, mesh_block=opt.mesh_block,
                     mesh_margin=opt.mesh_margin, color_mesh=opt.color_mesh, simplify_cell=opt.simplify_cell, simplify_faces=opt.simplify_faces,
-                    texture_mesh=opt.texture_mesh, level_seams=opt.level_seams)
+                    texture_mesh=opt.texture_mesh, level_seams=opt.level_seams, charts=opt.charts, chart_pad=opt.chart_pad,
+                    min_chart_faces=opt.min_chart_faces)

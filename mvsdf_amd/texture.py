@@ -73,12 +73,15 @@ class TexturedMesh:
     """The result of build_atlas: mesh (the Mesh that was textured), uv fp32 [F,3,2], texture uint8 [Ht,Wt,3], valid uint8 [Ht,Wt] (1: the texel
     was gathered from a photograph), face_view int32 [F] (-1: no view), patch int32 [F,4] = (x0, y0, n, half), all on the device; density, the
     texel density finally used; raster, the Raster behind the labels; screen fp64 [F,6], order int32 [F] and counts (seven ints): what the fill
-    read, which seams.level_atlas reads again."""
+    read, which seams.level_atlas reads again.  An atlas of charts (charts.build_chart_atlas) has patch, order and counts None and carries
+    face_chart int32 [F], chart_view int32 [C], chart_rect int32 [C,6] = (X, Y, w, h, u0, t0) and face_map int32 [Ht,Wt] instead."""
 
-    def __init__(self, mesh, uv, texture, valid, face_view, patch, density, raster=None, score=None, screen=None, order=None, counts=None):
+    def __init__(self, mesh, uv, texture, valid, face_view, patch, density, raster=None, score=None, screen=None, order=None, counts=None,
+                 face_chart=None, chart_view=None, chart_rect=None, face_map=None):
         self.mesh, self.uv, self.texture, self.valid, self.face_view, self.patch = mesh, uv, texture, valid, face_view, patch
         self.density, self.raster, self.score = density, raster, score
         self.screen, self.order, self.counts = screen, order, counts
+        self.face_chart, self.chart_view, self.chart_rect, self.face_map = face_chart, chart_view, chart_rect, face_map
 
     def export(self, path):
         """write `path` (.obj: mtllib, usemtl, v, vn, one vt per face corner, f a/t/a b/t/b c/t/c; floats as %.9g), <stem>.mtl (map_Kd <stem>.png)
@@ -180,12 +183,24 @@ def _fill(img, o, label, screen, order, counts, verts, faces, Pd, fallback, reco
 
 def build_atlas(mesh, images, P=None, cams=None, pixel_center=0.5, masks=None, raster=None, texel_density=1.0, max_size=8192,
                 fallback=(128, 128, 128), depth_tol=0.01, cos_min=0.0, ignore_normals=False, large_face_pixels=None, view_chunk=None,
-                recompute=False, level_seams=False, level_options=None):
+                recompute=False, level_seams=False, level_options=None, charts=False, chart_options=None):
     """The module's atlas of `mesh` (device tensors, world coordinates) from images uint8 [V,H,W,3] -> TexturedMesh.  The mesh is drawn into the
     cameras first (rasterize with large_face_pixels / view_chunk) unless `raster` holds that already.  recompute=True lets the fill project the
     face's corners again instead of reading the table step 1 wrote (the same bits; for measuring).  level_seams=True corrects the texture with
-    seams.level_atlas (level_options: its smoothness, anchor, cg_iters, cg_tol, info); labels, UVs, patches and valid stay as they are."""
+    seams.level_atlas (level_options: its smoothness, anchor, cg_iters, cg_tol, info); labels, UVs, patches and valid stay as they are.
+    charts=True builds the atlas of charts instead (charts.build_chart_atlas; chart_options: its pad, min_faces, smooth_rounds, info); without it
+    nothing of that module runs."""
     what = 'build_atlas'
+    if chart_options is not None and not isinstance(chart_options, dict):
+        raise ValueError('%s: chart_options must be a dict, got %s' % (what, type(chart_options).__name__))
+    if charts:
+        if recompute:
+            raise ValueError('%s: recompute belongs to the per-face fill, not to charts=True' % what)
+        from . import charts as CH
+        return CH.build_chart_atlas(mesh, images, P=P, cams=cams, pixel_center=pixel_center, masks=masks, raster=raster, texel_density=texel_density,
+                                    max_size=max_size, fallback=fallback, depth_tol=depth_tol, cos_min=cos_min, ignore_normals=ignore_normals,
+                                    large_face_pixels=large_face_pixels, view_chunk=view_chunk, level_seams=level_seams, level_options=level_options,
+                                    **(chart_options or {}))
     if level_options is not None and not isinstance(level_options, dict):
         raise ValueError('%s: level_options must be a dict, got %s' % (what, type(level_options).__name__))
     R._mesh(mesh, what)

@@ -16,8 +16,14 @@ same repeat.  One A x is also given in bytes moved (per adjacency entry 4 bytes 
 seam count, 24 of x and 24 written) as a share of 6.3e12 B/s, and next to the same product by torch.sparse_csr's fp64 mat-vec on the same
 graph, with the largest difference between the two.
 
+With --charts the stages of the chart atlas (mvsdf_amd/charts.py) are timed in the same repeats on the same labels: the neighbours, the components,
+the absorption (its score pass, and per round the components and one absorb pass; the reads of the headers included), the components of the
+smoothed labels, the packing (every halving pass), the UVs, the chart fill, which stands next to the per-face fill of the same repeat with the
+same byte model, and the face map.  Both atlases report their size and the share of their area that lies under a face (the sum of the UV
+triangles' areas); the charts before and after the absorption are given.
+
     python tools/time_texture.py [--resolution 512 --faces 50000 --views 49 --hw 1200,1600 --density 1.0 --max_size 8192 --repeats 5]
-                                 [--level_seams [--seam_smoothness 0.1 --cg_iters 200]]
+                                 [--level_seams [--seam_smoothness 0.1 --cg_iters 200]] [--charts [--chart_pad 4 --min_chart_faces 4]]
 """
 import argparse
 import json
@@ -47,6 +53,9 @@ def parser():
     ap.add_argument('--level_seams', default=False, action='store_true', help='also time the stages of seam levelling')
     ap.add_argument('--seam_smoothness', type=float, default=0.1)
     ap.add_argument('--cg_iters', type=int, default=200)
+    ap.add_argument('--charts', default=False, action='store_true', help='also time the stages of the chart atlas')
+    ap.add_argument('--chart_pad', type=int, default=4, choices=(1, 2, 4, 8))
+    ap.add_argument('--min_chart_faces', type=int, default=4)
     return ap
 
 
@@ -90,6 +99,12 @@ def main(argv=None):
     lruns = {k: [] for k in lnames}
     anchor = 1e-3
     passes = 0
+    if a.charts:
+        from mvsdf_amd import charts as CH
+        cws, big = torch.zeros(CH.chart_workspace_bytes(nf, 0), dtype=torch.uint8, device='cuda'), None
+    cnames = ('chart_neighbors_ms', 'chart_components_ms', 'chart_absorb_ms', 'chart_components_smoothed_ms', 'chart_pack_ms', 'chart_uv_ms',
+              'chart_fill_ms', 'chart_face_map_ms')
+    cruns = {k: [] for k in cnames}
     for rep in range(a.repeats + 1):                                  # the first round warms up
         ev = _events(6)
         ev[0].record()
@@ -145,6 +160,33 @@ def main(argv=None):
             if rep:
                 for k, name in enumerate(lnames):
                     lruns[name].append(le[k].elapsed_time(le[k + 1]))
+        if a.charts:
+            ce = _events(9)
+            ce[0].record()
+            nbr = CH.face_neighbors(mesh, workspace=cws)
+            ce[1].record()
+            before = CH.face_charts(label, nbr, workspace=cws)
+            ce[2].record()
+            lab2, sc2, scr2, changes = CH.smooth_labels(mesh, raster, label, a.min_chart_faces, 2, nbr=nbr, workspace=cws)
+            ce[3].record()
+            fc, cv, cf = CH.face_charts(lab2, nbr, workspace=cws)
+            ce[4].record()
+            pk = CH.pack_charts(fc, cv.shape[0], scr2, hw, 0.5, a.density, a.max_size, a.chart_pad, workspace=cws)
+            ce[5].record()
+            cuv = CH.chart_uvs(fc, scr2, pk, 0.5, workspace=cws)
+            ce[6].record()
+            ctex, cvalid = CH.chart_fill(images, cv, pk, workspace=cws)
+            ce[7].record()
+            if big is None:                                           # the face map's second map lies behind the rest of the workspace
+                big = torch.zeros(CH.chart_workspace_bytes(nf, pk.Ht * pk.Wt), dtype=torch.uint8, device='cuda')
+                torch.cuda.synchronize()
+                ce[7].record()
+            fmap = CH.face_map(fc, scr2, pk, 0.5, workspace=big)
+            ce[8].record()
+            torch.cuda.synchronize()
+            if rep:
+                for k, name in enumerate(cnames):
+                    cruns[name].append(ce[k].elapsed_time(ce[k + 1]))
     med = lambda x: round(float(np.median(x)), 3)                     # noqa: E731
     Wt, Ht, T = X.atlas_size(counts)
     n_valid = int(valid.sum())
@@ -160,6 +202,24 @@ def main(argv=None):
         res[name]['bytes_per_s'] = float('%.4g' % rate)
         res[name]['share_of_6.3e12'] = round(rate / PEAK_BYTES_PER_S, 4)
         res[name]['texels_per_s'] = float('%.4g' % (Wt * Ht / (res[name]['median'] * 1e-3)))
+    def under(uvs):                                             # the share of a w x h atlas under a face: the UV triangles' areas
+        q = uvs.double()
+        e1, e2 = q[:, 1] - q[:, 0], q[:, 2] - q[:, 0]
+        return round(float((e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]).abs().sum()) / 2.0, 4)
+    res['area_under_faces'] = under(uv[label >= 0])
+    if a.charts:
+        for name in cnames:
+            res[name] = {'median': med(cruns[name]), 'runs': [round(x, 3) for x in cruns[name]]}
+        cvalid_n = int(cvalid.sum())
+        cbytes = 4 * pk.Wt * pk.Ht + 12 * cvalid_n
+        rate = cbytes / (res['chart_fill_ms']['median'] * 1e-3)
+        res['chart_fill_ms'].update({'bytes': cbytes, 'bytes_per_s': float('%.4g' % rate), 'share_of_6.3e12': round(rate / PEAK_BYTES_PER_S, 4),
+                                     'texels_per_s': float('%.4g' % (pk.Wt * pk.Ht / (res['chart_fill_ms']['median'] * 1e-3)))})
+        res.update({'chart_pad': a.chart_pad, 'min_chart_faces': a.min_chart_faces, 'charts_before': int(before[1].shape[0]), 'charts': int(cv.shape[0]),
+                    'charts_below_min_before': int((before[2] < a.min_chart_faces).sum()), 'charts_below_min': int((cf < a.min_chart_faces).sum()),
+                    'absorb_changes': changes, 'chart_atlas': [pk.Wt, pk.Ht], 'chart_density_used': pk.density, 'chart_valid_texels': cvalid_n,
+                    'chart_valid_fraction': round(cvalid_n / (pk.Wt * pk.Ht), 4), 'chart_area_under_faces': under(cuv[fc >= 0]),
+                    'chart_face_map_fraction': round(float((fmap >= 0).float().mean()), 4), 'largest_chart_faces': int(cf.max()) if cf.numel() else 0})
     if a.level_seams:
         K, nnz = graph.nodes, graph.nnz
         for name in lnames:
