@@ -9,19 +9,7 @@ import struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get('MVSDF_LIB') or os.path.join(_HERE, 'libmvsdf_hip.so')   # MVSDF_LIB: dev override (ablation builds)
-MAX_LAYERS = 12
 _lib = None
-
-
-class NetDesc(C.Structure):
-    _fields_ = [('n_layers', C.c_int), ('K', C.c_int * MAX_LAYERS), ('N', C.c_int * MAX_LAYERS),
-                ('wp', C.c_void_p * MAX_LAYERS), ('bias', C.c_void_p * MAX_LAYERS), ('w', C.c_void_p * MAX_LAYERS),
-                ('skip_layer', C.c_int), ('multires', C.c_int), ('wp16', C.c_void_p * MAX_LAYERS), ('trace_dtype', C.c_int), ('skip_mask', C.c_uint), ('wx3', C.c_void_p * MAX_LAYERS)]
-
-
-class TraceParams(C.Structure):
-    _fields_ = [('r', C.c_float), ('thr', C.c_float), ('line_search_step', C.c_float), ('line_step_iters', C.c_int),
-                ('st_iters', C.c_int), ('n_steps', C.c_int), ('n_secant', C.c_int), ('dist_clip', C.c_float)]
 
 
 class MvsdfError(RuntimeError):
@@ -52,6 +40,9 @@ _SCALARS = {'int': C.c_int, 'unsigned': C.c_uint, 'unsigned int': C.c_uint, 'lon
             'float': C.c_float, 'double': C.c_double}
 
 
+_COMMENTS = re.compile(r'/\*.*?\*/|//[^\n]*', re.S)
+
+
 def _ctype(spelling, fn, named):
     """ctypes type of one parameter (`named`: a last word that completes no known type is the parameter's name) or return type.  Pointers and arrays are
     c_void_p: byref(), ctypes arrays, None, data_ptr() ints and c_void_p instances all pass."""
@@ -68,7 +59,7 @@ def _ctype(spelling, fn, named):
 
 def parse_header(text):
     """{name: (restype, [argtypes])} of every `ret mvsdf_name(args);` declaration of a C header, in its order."""
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = _COMMENTS.sub(' ', text)
     text = re.sub(r'^[ \t]*#(?:[^\n]*\\\n)*[^\n]*', ' ', text, flags=re.M)                # preprocessor lines with their continuations
     protos = {}
     for ret, fn, args in re.findall(r'(?<=[;{}])\s*([\w\s*]+?)\s*\b(mvsdf_\w+)\s*\(([^()]*)\)\s*;', ';' + text):
@@ -84,20 +75,63 @@ def parse_header(text):
     return protos
 
 
+_LITERAL = r'(0[xX][0-9a-fA-F]+|\d+)(?:[ \t]*<<[ \t]*(0[xX][0-9a-fA-F]+|\d+))?'
+
+
 def parse_constants(text):
-    """{name: value} of every enumerator of a C header's anonymous enums.  A value is a decimal or hex literal or a shift of two; anything else is an error."""
-    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
-    consts = {}
+    """{name: value} of every enumerator of a C header's anonymous enums, then of every `#define MVSDF_NAME <literal>`.  A value is a decimal or hex
+    literal or a shift of two; in an enumerator anything else is an error, any other macro (the include guard, a function-like one) is left alone."""
+    text = _COMMENTS.sub(' ', text)
+    items = []
     for body in re.findall(r'\benum\s*\{([^{}]*)\}\s*;', text):
         for item in filter(None, (i.strip() for i in body.split(','))):
             name, _, expr = (w.strip() for w in item.partition('='))
-            m = re.fullmatch(r'(0[xX][0-9a-fA-F]+|\d+)(?:\s*<<\s*(0[xX][0-9a-fA-F]+|\d+))?', expr)
+            m = re.fullmatch(_LITERAL, expr)
             if not m:
                 raise MvsdfError('enumerator %s: %s' % (name, 'cannot evaluate "%s"' % expr if expr else 'no explicit value'))
-            if name in consts:
-                raise MvsdfError('enumerator %s is declared twice' % name)
-            consts[name] = int(m.group(1), 0) << int(m.group(2) or '0', 0)
+            items.append((name,) + m.groups())
+    items += re.findall(r'^[ \t]*#[ \t]*define[ \t]+(MVSDF_\w+)[ \t]+%s[ \t]*$' % _LITERAL, text, flags=re.M)
+    consts = {}
+    for name, value, shift in items:
+        if name in consts:
+            raise MvsdfError('%s is declared twice' % name)
+        consts[name] = int(value, 0) << int(shift or '0', 0)
     return consts
+
+
+def parse_structs(text, consts=None):
+    """{name: ctypes.Structure subclass} of every anonymous `typedef struct { ... } MvsdfName;` of a C header, in its order; `cls._fields_` is the
+    ordered (field, ctype) list.  A member is `type a, b[N];`: a _SCALARS spelling or a struct declared earlier by value, c_void_p for anything with
+    a `*`, N a decimal literal or one of `consts` (default: the header's own).  Anything else is an error that names the struct and the member."""
+    text = _COMMENTS.sub(' ', text)
+    consts = parse_constants(text) if consts is None else consts
+    structs = {}
+    pieces = re.split(r'typedef\s+struct\s*\{([^{}]*(?:\{[^{}]*\}[^{}]*)*)\}\s*(\w+)\s*;', text)     # [outside, body, name, outside, ...]
+    for body, name in zip(pieces[1::3], pieces[2::3]):
+        fields = []
+        for decl in filter(None, (' '.join(d.split()) for d in re.sub(r'\{[^{}]*\}', '{}', body).split(';'))):
+            def refuse(why):
+                raise MvsdfError('%s, member "%s": %s' % (name, decl, why))
+            m = re.fullmatch(r'([\w *]*[ *])(\w+ ?(?:\[[^\[\]]*\])?(?: ?, ?\w+ ?(?:\[[^\[\]]*\])?)*)', decl)
+            if not m:
+                refuse('not of the form `type a, b[N]` (no bit-field, union, nested struct, function pointer or second array dimension)')
+            spelling = ' '.join(w for w in m.group(1).split() if w != 'const')
+            if '*' in spelling and ',' in decl:
+                refuse('a pointer declaration with more than one declarator')
+            ctype = C.c_void_p if '*' in spelling else _SCALARS.get(spelling) or structs.get(spelling)
+            if ctype is None:
+                refuse('no ctypes mapping for the C type "%s" (a struct is declared before its use)' % spelling)
+            for field, dim in re.findall(r'(\w+) ?(\[[^\[\]]*\])?', m.group(2)):
+                n = dim[1:-1].strip()
+                n = int(n) if n.isdecimal() else consts.get(n)
+                if dim and not n:
+                    refuse('cannot evaluate the array length %s' % dim)
+                fields.append((field, ctype * n if dim else ctype))
+        structs[name] = type(name, (C.Structure,), {'_fields_': fields})
+    unparsed = re.search(r'\b(?:struct|union)\b.{0,60}', ' '.join(pieces[0::3]), flags=re.S)      # a keyword outside the blocks the pattern above took
+    if unparsed:
+        raise MvsdfError('cannot parse the declaration at "%s"' % ' '.join(unparsed.group(0).split()))
+    return structs
 
 
 class _Namespace:
@@ -107,12 +141,14 @@ class _Namespace:
 
 try:
     with open(HEADER_PATH) as _f:
-        _text = _f.read()
+        _text = _COMMENTS.sub(' ', _f.read())                   # once for the three parsers
     PROTOTYPES = parse_header(_text)
     K = _Namespace(parse_constants(_text))                      # K.MVSDF_*: the result words, error bits and limits the header declares
+    STRUCTS = parse_structs(_text, vars(K))                     # the header's structs as ctypes.Structure classes, in its order
 except OSError as e:
-    raise MvsdfError('the C header %s cannot be read (%s): the ctypes prototypes are derived from it, the package needs include/ beside it' % (HEADER_PATH, e)) from None
+    raise MvsdfError('the C header %s cannot be read (%s): the ctypes prototypes and structs are derived from it, the package needs include/ beside it' % (HEADER_PATH, e)) from None
 EXPORTS = list(PROTOTYPES)                                       # every symbol include/mvsdf_hip.h declares
+NetDesc, TraceParams, MAX_LAYERS = STRUCTS['MvsdfNetDesc'], STRUCTS['MvsdfTraceParams'], K.MVSDF_MAX_LAYERS
 
 
 def check(rc, what=''):

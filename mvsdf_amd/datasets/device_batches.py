@@ -18,13 +18,7 @@ from .. import _lib
 from .._lib import check, lib
 
 
-class BatchArgs(C.Structure):
-    """ctypes mirror of MvsdfBatchArgs (include/mvsdf_hip.h)."""
-    _fields_ = ([('B', C.c_int), ('n', C.c_int), ('num_src', C.c_int)]
-                + [(k, C.c_int64) for k in ('P', 'img_w', 'total_pixels', 'depth_floats', 'fmap_floats')]
-                + [(k, C.c_void_p) for k in ('views', 'pix', 'src', 'rgb', 'omask', 'pmask', 'pose', 'intrinsics', 'cams_hd', 'depth_cams', 'depths',
-                                             'size', 'center', 'feats', 'o_rgb', 'o_uv', 'o_omask', 'o_pmask', 'o_pose', 'o_intrinsics', 'o_cam',
-                                             'o_src_cams', 'o_depths', 'o_depth_cams', 'o_size', 'o_center', 'o_feat', 'o_feat_src')])
+BatchArgs = _lib.STRUCTS['MvsdfBatchArgs']
 
 
 def source_table(dataset):

@@ -12,54 +12,13 @@ import operator
 
 import torch
 
-from ._lib import TraceParams, check, lib
+from ._lib import K, STRUCTS, TraceParams, check, lib  # noqa: F401  -- TraceParams: the type of StepDesc.tp, read from here by the model
 
-STEP_MAX_LAYERS = 24
+STEP_MAX_LAYERS = K.MVSDF_STEP_MAX_LAYERS
+StepDesc, StepParams, StepInputs, StepLayout, LossArgs, LossLayout = (
+    STRUCTS['Mvsdf' + n] for n in ('StepDesc', 'StepParams', 'StepInputs', 'StepLayout', 'LossArgs', 'LossLayout'))
 _DATA_PTR = torch.Tensor.data_ptr
 _VERSION_OF = operator.attrgetter('_version')
-
-
-class StepDesc(C.Structure):
-    _fields_ = [('B', C.c_int), ('P', C.c_int), ('n_eik', C.c_int), ('n_ds', C.c_int), ('n_sdf', C.c_int), ('n_render', C.c_int),
-                ('N', C.c_int * STEP_MAX_LAYERS), ('K', C.c_int * STEP_MAX_LAYERS), ('skip_mask', C.c_uint), ('multires', C.c_int),
-                ('view_spec', C.c_int), ('trace_dtype', C.c_int), ('use_object_mask', C.c_int), ('tp', TraceParams), ('mt', C.c_int),
-                ('mt_samples', C.c_int)]
-
-
-class StepParams(C.Structure):
-    _fields_ = [('v', C.c_void_p * STEP_MAX_LAYERS), ('g', C.c_void_p * STEP_MAX_LAYERS), ('b', C.c_void_p * STEP_MAX_LAYERS)]
-
-
-class StepInputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ('uv', 'pose', 'intrinsics', 'object_mask', 'object_mask_true', 'intervals', 'minsdf_steps', 'eik_points',
-                                          'ds_on', 'ds_jit', 'ds_counts', 'host_stage')]
-
-
-class StepLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in ('fwd_bytes', 'bwd_bytes', 'ray_dirs', 'cam_loc', 'points', 'mask', 'dists', 'counters', 'object_mask_out',
-                                          'rgb_values', 'sdf_output', 'diff_pts', 'eik_out', 'points_hom', 'grad_theta', 'surf', 'perm', 'dflat',
-                                          'dflat_floats')]
-
-
-class LossArgs(C.Structure):
-    _fields_ = [('R', C.c_int), ('B', C.c_int), ('N', C.c_int), ('n_grad', C.c_int), ('n_depth', C.c_int), ('n_surf', C.c_int),
-                ('net_mask', C.c_void_p), ('obj_mask', C.c_void_p), ('true_mask', C.c_void_p), ('rgb', C.c_void_p), ('rgb_gt', C.c_void_p),
-                ('grad_theta', C.c_void_p), ('eik_out', C.c_void_p), ('surf', C.c_void_p), ('diff_pts', C.c_void_p), ('points_hom', C.c_void_p),
-                ('feat_on', C.c_int), ('surf_on', C.c_int), ('V', C.c_int), ('C', C.c_int), ('H', C.c_int), ('W', C.c_int),
-                ('feat', C.c_void_p), ('feat_strides', C.c_longlong * 4), ('feat_src', C.c_void_p), ('src_strides', C.c_longlong * 5),
-                ('cam', C.c_void_p), ('src_cams', C.c_void_p), ('size', C.c_void_p), ('center', C.c_void_p),
-                ('depths', C.c_void_p), ('dB', C.c_int), ('dh', C.c_int), ('dw', C.c_int), ('depth_cams', C.c_void_p),
-                ('out_thresh_perc', C.c_float), ('far_thresh', C.c_float), ('far_att', C.c_float), ('near_thresh', C.c_float), ('near_att', C.c_float),
-                ('w_rgb', C.c_float), ('w_eik', C.c_float), ('w_surf', C.c_float), ('w_feat', C.c_float), ('w_depth', C.c_float),
-                ('use_invalid', C.c_int), ('smooth', C.c_float), ('inv_counts', C.c_void_p),
-                # deferred step: device pointer to {N, n_true}; N / n_grad / n_depth / n_surf above are then upper bounds (N = R), see include/mvsdf_hip.h
-                ('counts_dev', C.c_void_p), ('n_eik', C.c_int), ('n_ds', C.c_int), ('d_mask', C.c_int), ('e_mask', C.c_int)]
-
-
-class LossLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in ('bytes', 'out', 'hit', 'view_start', 'n_pos', 'loss_pp', 'dpts', 'dist_r', 'weight', 'd_rgb', 'd_grad',
-                                          'd_eo', 'd_sf', 's_rgb', 's_grad', 's_eo', 's_sf', 's_diff')]
-
 
 loss_timing = None                                             # bench.py sets a list: (start, end) events around every mvsdf_loss_forward are appended
 

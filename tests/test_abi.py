@@ -44,15 +44,16 @@ def test_product_does_not_import_oracle():
 
 
 def test_ctypes_structs_have_the_sizes_the_library_was_compiled_with():
-    """The ctypes mirrors of the header's structs (mvsdf_amd/_lib.py, native_step.py) against sizeof() inside the library: a field added on one
-    side only shows up here instead of as silently shifted arguments."""
-    from mvsdf_amd import _lib, native_step as ns
+    """The ctypes classes derived from the header's structs (mvsdf_amd/_lib.py::STRUCTS, in header order) against sizeof() inside the library: a
+    library compiled against another header shows up here instead of as silently shifted arguments."""
+    from mvsdf_amd import _lib
     out = (ctypes.c_size_t * 8)()
     assert _lib.lib().mvsdf_abi_struct_sizes(out) == 8
-    mirrors = [_lib.NetDesc, _lib.TraceParams, ns.StepDesc, ns.StepParams, ns.StepInputs, ns.StepLayout, ns.LossArgs, ns.LossLayout]
-    for cls, size in zip(mirrors, list(out)):
-        assert ctypes.sizeof(cls) == size, (cls.__name__, ctypes.sizeof(cls), size)
-
+    sizes = list(out) + [_lib.lib().mvsdf_batch_args_bytes()]
+    assert list(_lib.STRUCTS) == ['MvsdfNetDesc', 'MvsdfTraceParams', 'MvsdfStepDesc', 'MvsdfStepParams', 'MvsdfStepInputs', 'MvsdfStepLayout',
+                                  'MvsdfLossArgs', 'MvsdfLossLayout', 'MvsdfBatchArgs']             # the order of the two exports
+    for (name, cls), size in zip(_lib.STRUCTS.items(), sizes):
+        assert ctypes.sizeof(cls) == size, (name, ctypes.sizeof(cls), size)
 
 
 def test_build_is_keyed_by_content(tmp_path, monkeypatch):

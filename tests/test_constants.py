@@ -1,5 +1,5 @@
 """The result words, error bits and limits of include/mvsdf_hip.h as the Python side reads them (mvsdf_amd/_lib.py::parse_constants, K, raise_for_bits):
-the parser on small snippets, the real header's blocks, and every module's error table.  No GPU needed."""
+the parser on small snippets (enumerators and object-like macros), the real header's blocks, and every module's error table.  No GPU needed."""
 import collections
 import importlib
 import re
@@ -31,12 +31,38 @@ def test_parser_on_small_snippets():
     assert parse_constants('int mvsdf_no_enum(void);') == {}
 
 
+def test_object_like_macros_are_constants_too():
+    text = '''
+    #ifndef MVSDF_GUARD_H
+    #define MVSDF_GUARD_H                  /* no value: left alone */
+    #define MVSDF_DEC 12
+      #  define MVSDF_HEX 0x1F             /* a comment behind the value; #define MVSDF_IN_A_COMMENT 3 */
+    #define MVSDF_SHIFT 1 << 4             // #define MVSDF_IN_A_LINE_COMMENT 4
+    enum { MVSDF_ENUM = 7 };
+    #define MVSDF_FUNCTION_LIKE(x) 3
+    #define MVSDF_PAREN (3)
+    #define MVSDF_SUM 1 + 2
+    #define MVSDF_NAMED MVSDF_DEC
+    #define MVSDF_FLOAT 1.5
+    #define MVSDF_STRING "12"
+    #define OTHER_PREFIX 5
+    #define MVSDF_CONTINUED 1 \\
+                            << 2
+    #endif
+    '''
+    assert parse_constants(text) == {'MVSDF_ENUM': 7, 'MVSDF_DEC': 12, 'MVSDF_HEX': 31, 'MVSDF_SHIFT': 16}
+
+
 @pytest.mark.parametrize('text, name', [
     ('enum { MVSDF_A = 0, MVSDF_NO_VALUE, MVSDF_C = 2 };', 'MVSDF_NO_VALUE'),
     ('enum { MVSDF_A = 0 };\nenum { MVSDF_B = 1, MVSDF_A = 2 };', 'MVSDF_A'),
     ('enum { MVSDF_A = 0, MVSDF_SUM = 1 + 2 };', 'MVSDF_SUM'),
     ('enum { MVSDF_A = 1, MVSDF_REF = MVSDF_A };', 'MVSDF_REF'),
     ('enum { MVSDF_WIDE = 1ll << 40 };', 'MVSDF_WIDE'),
+    ('#define MVSDF_A 1\n#define MVSDF_A 2\n', 'MVSDF_A'),
+    ('#define MVSDF_A 1\n#define MVSDF_A 1\n', 'MVSDF_A'),
+    ('#define MVSDF_A 1\nenum { MVSDF_B = 0, MVSDF_A = 1 };\n', 'MVSDF_A'),
+    ('enum { MVSDF_B = 0, MVSDF_A = 1 };\n#define MVSDF_A 1\n', 'MVSDF_A'),
 ])
 def test_parser_refuses_what_it_cannot_evaluate(text, name):
     with pytest.raises(MvsdfError, match=r'\b%s\b' % name):
@@ -47,6 +73,8 @@ def test_the_namespace_is_the_real_header():
     assert CONSTS and vars(K) == CONSTS
     assert K.MVSDF_CNT_ROWS_SPHERE == 0 and K.MVSDF_CNT_LATE_ROUNDS == 15          # the block that was there before
     assert K.MVSDF_GREG_MAX_HYPOTHESES == 1 << 22 and K.MVSDF_PC_MAX_K == 32
+    assert K.MVSDF_MAX_LAYERS == 12 and K.MVSDF_STEP_MAX_LAYERS == 24 and K.MVSDF_STEP_COUNT_RING == 64          # the object-like macros
+    assert K.MVSDF_STEP_UNHIT_DEFER == 0 and K.MVSDF_STEP_UNHIT_EAGER == 1 and not hasattr(K, 'MVSDF_HIP_H')
 
 
 def _blocks(kind):
